@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- leapfrog-steps/sec of batched ftHMC chains on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,5}] [--scaling {weak,strong}]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,5}] [--scaling {weak,strong}] [--full] [--dump-outputs DIR]
 
 Default workload = BASELINE.json configs[2] (`--config 3`): 2D U(1), L=64, beta=6.0, 8-layer flow
 (hidden [8,8], k=3, n_mix=2, SiLU, PyTorch default init), 128 chains per GPU, tau=1.0, nstep=10,
@@ -21,7 +21,16 @@ SUM all-reduce of run statistics per trajectory (RCCL), inside the timed region.
 With `--gpus N > 1` and no torchrun environment the script starts its own N ranks (one process per GPU,
 `python -m torch.distributed.run`) BEFORE anything touches the GPU and relays rank 0's line.
 
-Prints ONE JSON line on rank 0.  `value` = chain-leapfrog-steps per second over all ranks.  Also:
+Prints ONE JSON line on rank 0.  `value` = chain-leapfrog-steps per second over all ranks, `ms_per_step` = milliseconds
+per trajectory, both from ONE timed region of exactly --steps trajectories after --warmup untimed ones.
+`--dump-outputs DIR` writes what the last timed trajectory returned (x_new, dH, acc, H0, H1, plaq, Q and, with the flow,
+state) as DIR/<name>.npy in float64; the inputs depend on the arguments only, so two builds can be compared array by array.
+
+Everything else is measured only with `--full` (a plain run sets up, warms up, times and reports, nothing more):
+  regions      -- more timed regions of --steps trajectories each (five when the first is shorter than 1 s, and until
+                  --min-seconds of timed GPU work have accumulated); `value` / `ms_per_step` are then the median region;
+  stateless    -- one more region with H0 recomputed by a flow sweep (the reference's way);
+  train        -- config 5: train_step's compute and whole training steps;
   roofline     -- the kernel with the largest share of a trajectory (coupling-layer forward for the
                   flowed configs: fp64 matrix/vector peak; the fused trajectory kernel for plain HMC:
                   HBM), duration measured here with HIP events on the launch stream;
@@ -84,14 +93,21 @@ def parse():
                          'kernel drains); default: 2 for large launches, else 1')
     ap.add_argument('--group-sizes', type=str, default=None, help='explicit chain-group sizes, e.g. 96,32 (experiments)')
     ap.add_argument('--regions', type=int, default=None,
-                    help='timed regions of --steps trajectories each (value = the median region); default: 1, or 5 when '
-                         'the first region is shorter than 1 s')
-    ap.add_argument('--min-seconds', type=float, default=6.0,
+                    help='timed regions of --steps trajectories each (value = the median region); default: 1, and with --full '
+                         '5 when the first region is shorter than 1 s')
+    ap.add_argument('--min-seconds', type=float, default=None,
                     help='keep timing regions of exactly --steps trajectories until this many seconds of timed GPU work have '
-                         'accumulated (the value is the median region; a monitor that samples the card every few seconds sees it busy)')
+                         'accumulated (the value is the median region; a monitor that samples the card every few seconds sees it busy); '
+                         'default: 6 with --full, else 0')
     ap.add_argument('--dump', type=str, default=None,
                     help='write every rank\'s per-chain end state (global chain ids, field, last dH / acc / Q) to '
                          'DUMP.<world>.<rank>.npz (sharding tests)')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help='write the outputs of the last timed trajectory to DIR/<name>.npy (float64; with --gpus N > 1 each '
+                         'rank writes its chains to DIR/<name>.rank<r>.npy)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the extra measurements and checks: more timed regions, the stateless side figure, the training '
+                         'leg of config 5, the roofline kernel timings and the CPU baseline with its parity check')
     return ap.parse_args()
 
 
@@ -381,7 +397,7 @@ def main():
             # thread_local: the process group's watchdog thread may poll its events while this thread captures
             with graph_loop.capture(graph, stream):
                 enqueue()
-            if flowed:                      # the stateless variant of the same trajectory, for the side figure below
+            if flowed and args.full:        # the stateless variant of the same trajectory, for the side figure below
                 graph_sl = torch.cuda.CUDAGraph()
                 with graph_loop.capture(graph_sl, stream):
                     enqueue(stateless=True)
@@ -428,16 +444,19 @@ def main():
         log('timed region ...')
         stats.vec.zero_(); stats.glob = None
         times = [region()]
-        # a region shorter than a second is at the mercy of the clock ramp and of one late host wake-up: time more
+        # --full: a region shorter than a second is at the mercy of the clock ramp and of one late host wake-up: time more
         # regions of the same --steps trajectories and report the median one (every rank sees the same MAX-reduced
         # time, so all ranks agree on the count)
         # ... and keep going until --min-seconds of timed GPU work have accumulated, so that the record of a run shows the
-        # card busy whatever --steps was (20 trajectories are 0.12 s)
-        nmin = args.regions if args.regions else (5 if times[0] < 1.0 else 1)
-        while len(times) < nmin or (not args.regions and sum(times) < args.min_seconds and len(times) < 400):
+        # card busy whatever --steps was (20 trajectories are 0.12 s).  A plain run times its one region of --steps.
+        min_seconds = args.min_seconds if args.min_seconds is not None else (6.0 if args.full else 0.0)
+        nmin = args.regions if args.regions else (5 if (args.full and times[0] < 1.0) else 1)
+        while len(times) < nmin or (not args.regions and sum(times) < min_seconds and len(times) < 400):
             times.append(region())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, rank, world)
         # side figure: the same trajectories with H0 recomputed (one more flow sweep per trajectory), one region
-        elapsed_sl = region(stateless=True) if flowed else None
+        elapsed_sl = region(stateless=True) if (flowed and args.full) else None
     elapsed = sorted(times)[len(times) // 2]
     if args.dump:
         import numpy as np
@@ -447,7 +466,7 @@ def main():
     # ---- training leg (config 5): train_step's compute = ops.train_grad on a fixed prior draw, all ranks,
     #      gradients all-reduced (C2) like train.train_step does
     train = None
-    if cfg['train']:
+    if cfg['train'] and args.full:
         gxi, _ = ops.random_momenta(parallel.chain_seeds(SEED + 31, lo, hi, 0).to(dev), (B, 2, L, L), need_u=False)
         xi = (math.pi * torch.erf(gxi / math.sqrt(2.0))).contiguous()          # prior draw U(-pi, pi), keyed by chain id
         Gt = ops.default_train_groups(B, L)
@@ -523,8 +542,59 @@ def main():
     chain_steps = B_total * NSTEP * args.steps
     value = chain_steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    roofline = roofline_fig(args, stream, x, v, u, w, L, B, BETA, N_LAYERS, dt, G, Gsplit, elapsed) if args.full else None
+    cpu, parity_ok = cpu_baseline(args, cfg, flow, x0, w, dev, world, L, B, BETA, N_LAYERS, dt) if args.full else (None, True)
 
-    # ---- roofline of the dominant kernel, HIP events on this stream
+    m = stats.means()
+    line = {
+        'metric': 'leapfrog-steps/sec (batched chains)', 'value': round(value, 2),
+        'unit': 'chain-leapfrog-steps/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': args.scaling,
+        'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic', 'full': args.full,
+        'config': {'workload': cfg['label'], 'baseline_config': args.config,
+                   'chains_per_gpu': B, 'chains_total': B_total, 'L': L, 'beta': BETA, 'n_layers': N_LAYERS,
+                   'nstep': NSTEP, 'tau': TAU, 'parallelism': f'chains sharded x{world}',
+                   'process_group': (torch.distributed.get_backend() if grouped else None),
+                   'launch': 'eager' if graph is None else 'hipGraph replay', 'chain_groups': G,
+                   'path': 'small-lattice fused (one launch per trajectory)' if (flowed and L <= 16 and ops.get_small_path()) else
+                           ('tiled, one launch per layer' if flowed else 'plain HMC, one launch per trajectory')},
+        'batched_leapfrog_steps_per_s': round(NSTEP * args.steps / elapsed, 3),
+        'stateless': (None if elapsed_sl is None else
+                      {'ms_per_step': round(elapsed_sl / args.steps * 1e3, 4), 'value': round(chain_steps / elapsed_sl, 2),
+                       'note': 'H0 recomputed by a flow sweep at the start of every trajectory, as the reference does '
+                               '(ft_hmc.py:205); `value` carries S_eff of the accepted field over instead (bit-identical)'}),
+        'regions': {'n': len(times), 'seconds': [round(t, 7) for t in times], 'value_from': 'median region',
+                    'spread': round((max(times) - min(times)) / elapsed, 4),
+                    'note': f'each region = exactly {args.steps} trajectories between barrier + synchronize brackets, '
+                            'MAX over ranks; with --full more than one region is timed when the first is shorter than 1 s'},
+        'acceptance': round(m['acc'], 4), 'plaq': round(m['plaq'], 6),
+        'acceptance_note': 'untrained random-init flow as the workload prescribes: throughput of the MD path, not a tuned sampler',
+        'roofline': roofline, 'cpu_baseline': cpu,
+    }
+    if train is not None:
+        line['train'] = train
+    print(json.dumps(line), flush=True)
+    if grouped:
+        torch.distributed.destroy_process_group()
+    if not parity_ok:
+        log(f'PARITY FAILURE against the oracle (tolerance {PARITY_TOL}): {cpu["parity"]}')
+        sys.exit(3)
+
+
+def dump_outputs(d, out, rank, world):
+    """--dump-outputs: what the last timed trajectory returned to its caller, DIR/<name>.npy in float64 (config 5, the largest:
+    x_new 32 MiB, the rest a few KiB).  Several ranks: each writes its own chains, DIR/<name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    sfx = '' if world == 1 else f'.rank{rank}'
+    for k, t in out.items():
+        np.save(os.path.join(d, f'{k}{sfx}.npy'), t.detach().to(torch.float64).cpu().numpy())
+
+
+def roofline_fig(args, stream, x, v, u, w, L, B, BETA, N_LAYERS, dt, G, Gsplit, elapsed):
+    """--full: roofline of the dominant kernel, HIP events on this stream"""
+    from fthmc_amd import ops
+    flowed = N_LAYERS > 0
     with torch.cuda.stream(stream):
         ms_leap = ops.time_kernel('leap_step', x, beta=BETA, reps=40)
         ms_traj = ops.time_kernel('hmc_trajectory', x, beta=BETA, reps=20) if L <= 64 else None
@@ -628,8 +698,13 @@ def main():
                     'note': f'{B} chain(s) of {L}x{L}: {2 * L * L * 8 * B} B of state -- one workgroup per chain; '
                             'the launch is latency-bound, not bandwidth-bound',
                     'stencil': stencil}
+    return roofline
 
-    # ---- CPU baseline (oracle = "port") on a bounded sample + parity of the HIP path on it
+
+def cpu_baseline(args, cfg, flow, x0, w, dev, world, L, B, BETA, N_LAYERS, dt):
+    """--full: CPU baseline (oracle = "port") on a bounded sample + parity of the HIP path on it -> (cpu, parity_ok)"""
+    from fthmc_amd import ops
+    flowed = N_LAYERS > 0
     cpu = None
     parity_ok = True
     if not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only
@@ -694,41 +769,7 @@ def main():
                            'sample': f'{nstep1} leapfrog steps + H0/H1 of {nb1} chain(s), median of {reps1}: {t1thr:.4g} s'},
             'parity': par,
         }
-
-    m = stats.means()
-    line = {
-        'metric': 'leapfrog-steps/sec (batched chains)', 'value': round(value, 2),
-        'unit': 'chain-leapfrog-steps/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': args.scaling,
-        'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-        'config': {'workload': cfg['label'], 'baseline_config': args.config,
-                   'chains_per_gpu': B, 'chains_total': B_total, 'L': L, 'beta': BETA, 'n_layers': N_LAYERS,
-                   'nstep': NSTEP, 'tau': TAU, 'parallelism': f'chains sharded x{world}',
-                   'process_group': (torch.distributed.get_backend() if grouped else None),
-                   'launch': 'eager' if graph is None else 'hipGraph replay', 'chain_groups': G,
-                   'path': 'small-lattice fused (one launch per trajectory)' if (flowed and L <= 16 and ops.get_small_path()) else
-                           ('tiled, one launch per layer' if flowed else 'plain HMC, one launch per trajectory')},
-        'batched_leapfrog_steps_per_s': round(NSTEP * args.steps / elapsed, 3),
-        'stateless': (None if elapsed_sl is None else
-                      {'ms_per_step': round(elapsed_sl / args.steps * 1e3, 4), 'value': round(chain_steps / elapsed_sl, 2),
-                       'note': 'H0 recomputed by a flow sweep at the start of every trajectory, as the reference does '
-                               '(ft_hmc.py:205); `value` carries S_eff of the accepted field over instead (bit-identical)'}),
-        'regions': {'n': len(times), 'seconds': [round(t, 7) for t in times], 'value_from': 'median region',
-                    'spread': round((max(times) - min(times)) / elapsed, 4),
-                    'note': f'each region = exactly {args.steps} trajectories between barrier + synchronize brackets, '
-                            'MAX over ranks; more than one region is timed when the first is shorter than 1 s'},
-        'acceptance': round(m['acc'], 4), 'plaq': round(m['plaq'], 6),
-        'acceptance_note': 'untrained random-init flow as the workload prescribes: throughput of the MD path, not a tuned sampler',
-        'roofline': roofline, 'cpu_baseline': cpu,
-    }
-    if train is not None:
-        line['train'] = train
-    print(json.dumps(line), flush=True)
-    if grouped:
-        torch.distributed.destroy_process_group()
-    if not parity_ok:
-        log(f'PARITY FAILURE against the oracle (tolerance {PARITY_TOL}): {cpu["parity"]}')
-        sys.exit(3)
+    return cpu, parity_ok
 
 
 # Attainable bound of the coupling-layer forward kernel at 16 x 16 tiles, from the work it cannot avoid with this

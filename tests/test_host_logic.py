@@ -395,6 +395,19 @@ def test_bench_launch_command_and_refusal_without_gpu():
         assert p.returncode != 0 and 'MI355X' in (p.stderr + p.stdout)
 
 
+def test_bench_is_plain_unless_asked_for_full(monkeypatch):
+    """bench.py's options: a plain run times one region of --steps and nothing else; --full asks for the extra measurements,
+    --dump-outputs DIR for the last timed trajectory's arrays."""
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    assert a.regions is None and a.min_seconds is None
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', '/nonexistent/out'])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == '/nonexistent/out'
+
+
 def test_net_shapes_and_their_limits():
     """Any s/t net the reference's make_conv_net accepts is packed for the HIP path (the default shape for the tuned kernels,
     anything else for csrc/flow_generic.hip); what the kernels cannot take raises before anything is launched -- never a

@@ -372,7 +372,7 @@ def test_bench_self_launches_its_ranks(tmp_path):
         env.pop(k, None)
     for scaling, total in (('weak', 32), ('strong', 16)):
         p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--config', '2', '--batch', '16',
-                            '--scaling', scaling, '--steps', '2', '--warmup', '1', '--thermalize', '2', '--no-cpu-baseline'],
+                            '--scaling', scaling, '--steps', '2', '--warmup', '1', '--thermalize', '2', '--no-cpu-baseline', '--full'],
                            env=env, capture_output=True, text=True, timeout=900)
         assert p.returncode == 0, p.stderr[-3000:]
         line = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])

@@ -136,7 +136,8 @@ def test_bench_times_several_regions_when_one_is_short(tmp_path):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', '1', '--steps', '5', '--warmup', '2',
-                        '--thermalize', '2', '--no-cpu-baseline', '--min-seconds', '0.02'], env=env, capture_output=True, text=True, timeout=600)
+                        '--thermalize', '2', '--no-cpu-baseline', '--min-seconds', '0.02', '--full'], env=env, capture_output=True, text=True,
+                       timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])
     reg = line['regions']
@@ -145,6 +146,31 @@ def test_bench_times_several_regions_when_one_is_short(tmp_path):
     med = sorted(reg['seconds'])[reg['n'] // 2]
     assert abs(line['ms_per_step'] - med / 5 * 1e3) < 1e-2 * line['ms_per_step']
     assert abs(line['value'] - line['config']['chains_total'] * 10 * 5 / med) < 1e-2 * line['value']
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full the bench times ONE region of exactly --steps trajectories and measures nothing else; --dump-outputs
+    writes what the last timed trajectory returned, and two runs with the same arguments write the same arrays."""
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        env.pop(k, None)
+    runs = []
+    for tag in ('a', 'b'):
+        d = tmp_path / tag
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', '2', '--steps', '3', '--warmup', '1',
+                            '--thermalize', '2', '--dump-outputs', str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])
+        assert line['full'] is False and line['steps'] == 3 and line['regions']['n'] == 1
+        assert line['roofline'] is None and line['cpu_baseline'] is None and line['stateless'] is None
+        assert abs(line['ms_per_step'] - line['regions']['seconds'][0] / 3 * 1e3) < 1e-3 * line['ms_per_step']
+        runs.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = runs
+    assert set(a) == {'x_new', 'dH', 'acc', 'H0', 'H1', 'plaq', 'Q', 'state'}
+    assert a['x_new'].shape == (32, 2, 16, 16) and a['state'].shape == (3, 32)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
 
 
 # ---------------------------------------------------------------- the reference's import path
