@@ -106,7 +106,12 @@ inline int flow_fwd(const Ctx& C, const FlowLayerArgs& a, hipStream_t s) {
 }
 inline size_t ws_doubles(const FlowArch& A, int B, int L, int nl, bool train = false) { return ws_layout(A, nullptr, B, L, nl, train).total; }
 
-inline bool bad_shape(int B, int L) { return B <= 0 || L < 4 || (L % 4) != 0; }
+// FTHMC_MAX_B / FTHMC_MAX_L (fthmc_hip.h): the plain-lattice kernels (wilson.hip, rng.hip) hold the site count of a chain's
+// field, 2 L^2, in int (launch_kinetic, launch_metropolis and its (2 L^2 + 2047) / 2048, k_leap_rows' plane offsets), and
+// k_metropolis walks s < 2 L^2 with s += its y extent min(that / 2048, 16) * 256 <= 4096: all below 2^31 for L <= 32764, the
+// last multiple of 4 before 2 L^2 reaches 2^31.  A chain is one workgroup of up to 1024 threads along x (k_action_charge,
+// k_kinetic, k_traj_energy), whose extent in work-items must stay below 2^32
+inline bool bad_shape(int B, int L) { return B <= 0 || B > FTHMC_MAX_B || L < 4 || L > FTHMC_MAX_L || (L % 4) != 0; }
 
 // The caller's canonical weights: the tuned kernels read their own expansion (k_pack_weights -> W.wint), the kernels for
 // other net shapes (flow_generic.hip) read the canonical layout itself.
@@ -410,7 +415,8 @@ int fthmc_stats_accumulate(const double* acc, const double* plaq, const double* 
 }
 
 int fthmc_random_momenta(const int64_t* seeds, int B, int n_per_chain, double* v, double* u, void* stream) {
-    if (!seeds || !v || B <= 0 || n_per_chain <= 0) return FTHMC_ERR_ARG;
+    // n_per_chain: at most a field of the largest lattice (the launcher and k_random_momenta form (n + 1) / 2 in int)
+    if (!seeds || !v || B <= 0 || B > FTHMC_MAX_B || n_per_chain <= 0 || n_per_chain > 2 * FTHMC_MAX_L * FTHMC_MAX_L) return FTHMC_ERR_ARG;
     return launch_random_momenta(seeds, B, n_per_chain, v, u, ft_stream(stream));
 }
 

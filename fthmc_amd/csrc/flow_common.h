@@ -163,8 +163,10 @@ __device__ __forceinline__ double ft_min_neg(double z, double hi) {
 //     c = r - r^2 P(r^2) (degree 4 in r^2),  exp(r) = (m + 2 r) / m  with  m = 2 - c,
 //     sigmoid = m / (m + 2^n (m + 2 r)):
 // 24 DP operations per value with h and act' instead of 26 (six polynomial steps instead of eleven, one multiply more at
-// the end).  Against quad precision over |z| <= 40 (tools/sigmoid_check.c): max 2.8 ulp / mean 0.50 (polynomial form: 2.3 /
-// 0.42).  0: the degree-11 polynomial of exp(r).
+// the end).  Against quad precision over |z| <= 40 (tools/sigmoid_check.c, with the hi / lo ln 2 pair): max 2.8 ulp / mean 0.50
+// (polynomial form: 2.3 / 0.42).  With FT_SIG_LN2_ONE (below) the relative error of a small sigma grows by |n| 2.3e-17: measured
+// against 80-bit references (tests/test_device_math_gpu.py) max 13.5 ulp at z = -39.5, within 3 + 0.21 max(0, -z log2 e) ulp
+// everywhere.  0: the degree-11 polynomial of exp(r).
 #ifndef FT_SIG_RATIONAL
 #define FT_SIG_RATIONAL 1
 #endif

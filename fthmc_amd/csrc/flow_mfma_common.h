@@ -83,14 +83,18 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // v_mad_u64_u32 run at quarter rate, and the per-thread index set-up ahead of the first loads used to cost
 // more cycles than the HBM round trip it precedes.
 //   mul24: operands < 2^23 (lattice extents, window indices)
-//   fdiv<D>(u) = u / D for 0 <= u < 32768, 2 <= D <= 32, via one 24-bit multiply (exact: u (M D - 2^20) < 2^20)
+//   fdiv<D>(u) = u / D for 0 <= u < 32768, 2 <= D <= 32, via one 24-bit multiply: M = ceil(2^S / D), floor(u M / 2^S) is
+//   exact while u (M D - 2^S) < 2^S; __umul24 returns a SIGNED int here and the shift is arithmetic, so u M < 2^31 as well.
+//   S = 16 + floor(log2 D) meets both for every u < 32768 (a fixed S = 20 was wrong for every D < 16 somewhere below 32768: u / 3 from u = 6144 on)
 __device__ __forceinline__ int mul24(int a, int b) { return __mul24(a, b); }
 template <int D> __device__ __forceinline__ int fdiv(int u) {
     static_assert(D >= 1 && D <= 32, "small divisors");
     if (D == 1) return u;
     if ((D & (D - 1)) == 0) return (int)((unsigned)u >> __builtin_ctz(D));
-    constexpr unsigned M = ((1u << 20) + D - 1) / D;
-    return (int)(__umul24((unsigned)u, M) >> 20);
+    constexpr int S = 16 + (31 - __builtin_clz((unsigned)D));
+    constexpr unsigned M = ((1u << S) + D - 1) / D;
+    static_assert(32767ull * M < (1ull << 31) && 32767ull * (M * D - (1u << S)) < (1u << S), "fdiv: exact for u < 32768");
+    return (int)(__umul24((unsigned)u, M) >> S);
 }
 // base + (a launch- or wave-uniform element offset forced into SGPRs): loads through the result take the
 // scalar-base form (global_load v, v_offset32, s[base]), their per-lane address is one 32-bit offset and

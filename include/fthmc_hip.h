@@ -12,7 +12,15 @@
  * two groups of independent chains) need a workspace each.
  *
  * Field layout: x[B][2][L][L], angle of the U(1) link in radians, mu-major
- * (the reference's [batch, Nd, Nt, Nx]).  L % 4 == 0.
+ * (the reference's [batch, Nd, Nt, Nx]).  L % 4 == 0, 4 <= L <= FTHMC_MAX_L,
+ * 1 <= B <= FTHMC_MAX_B for every entry point that takes (B, L), and B <= FTHMC_MAX_B,
+ * n_per_chain <= 2 FTHMC_MAX_L^2 for fthmc_random_momenta; beyond, FTHMC_ERR_ARG.
+ * With the default net shape the flow entry points run the tuned kernels, which accept
+ * less: L <= 8192 (the largest byte offset inside a stash plane, 64 L^2 - 8, fits 32
+ * bits) and B <= 2^20, else FTHMC_ERR_ARG; and one layer's stash below 2^32 doubles --
+ * 19 B L^2 for the force, 35 B L^2 for training -- else FTHMC_ERR_UNSUPPORTED (callers
+ * split larger batches into chain groups, ops.train_grad(groups=...)).  Other net shapes
+ * (fthmc_arch_t, flow_generic.hip) check no limit beyond the plain-lattice ones.
  * Flow weights: n_layers * FTHMC_W_PER_LAYER doubles; per layer the six
  * nn.Conv2d tensors of `layers[i].plaq_coupling.net` in state_dict order and
  * PyTorch [Cout][Cin][kh][kw] layout:
@@ -32,6 +40,10 @@ extern "C" {
 #endif
 
 #define FTHMC_W_PER_LAYER 955
+/* shape limits of the plain-lattice kernels (int site counts: 2 L^2 plus a loop stride of at
+ * most 4096 below 2^31; one workgroup of up to 1024 threads per chain along x: B * 1024 < 2^32) */
+#define FTHMC_MAX_L 32764
+#define FTHMC_MAX_B 4194303
 
 #define FTHMC_OK               0
 #define FTHMC_ERR_ARG         -1   /* bad shape / null pointer              */

@@ -1,0 +1,247 @@
+// Test-only device probe (tests/test_device_math_gpu.py): the kernels' own fp64 math helpers (common.h, flow_common.h) and
+// integer index helpers (flow_mfma_common.h), applied elementwise to arrays, exactly as the headers define them -- nothing is
+// copied.  Built by `make -C fthmc_amd/csrc probe` with the kernels' CXXFLAGS (same FP-contraction policy), never linked into
+// libfthmc_hip.so.  Every launcher takes HOST arrays, copies them in and out, and returns the first HIP error (0 = success).
+#include <hip/hip_runtime.h>
+#include <utility>
+#include "../../fthmc_amd/csrc/common.h"
+#include "../../fthmc_amd/csrc/flow_common.h"
+#include "../../fthmc_amd/csrc/flow_mfma_common.h"
+
+using namespace fthmc_flow;
+
+enum {
+    P_SIGMOID = 0, P_SIGMOID4, P_EXP, P_EXPN4, P_EXPN2, P_ACT, P_ACT4, P_SINCOS, P_ATAN, P_RCP, P_WRAP, P_WRAP_PM_PI,
+    P_REGULARIZE, P_COMPOSITE, P_NOPS
+};
+
+// scalar ops: one element per thread; the N-wide forms (sigmoid4, ft_expN, act_eval4): N consecutive elements per thread
+template <int OP>
+__global__ void k_math(const double* __restrict__ x, const double* __restrict__ s, double* o0, double* o1, double* o2, int n, int act) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (OP == P_SIGMOID4 || OP == P_EXPN4 || OP == P_ACT4) {
+        if (4 * t >= n) return;
+        const double z[4] = {x[4 * t], x[4 * t + 1], x[4 * t + 2], x[4 * t + 3]};
+        double a[4], b[4] = {0.0, 0.0, 0.0, 0.0};
+        if (OP == P_SIGMOID4) sigmoid4(z, a);
+        else if (OP == P_EXPN4) ft_expN<4>(z, a);
+        else act_eval4(z, act, a, b);
+        for (int q = 0; q < 4; ++q) { o0[4 * t + q] = a[q]; if (OP == P_ACT4) o1[4 * t + q] = b[q]; }
+        return;
+    }
+    if (OP == P_EXPN2) {
+        if (2 * t >= n) return;
+        const double z[2] = {x[2 * t], x[2 * t + 1]};
+        double e[2];
+        ft_expN<2>(z, e);
+        o0[2 * t] = e[0]; o0[2 * t + 1] = e[1];
+        return;
+    }
+    if (t >= n) return;
+    const double v = x[t];
+    if (OP == P_SIGMOID) o0[t] = ft_sigmoid(v);
+    if (OP == P_EXP) o0[t] = ft_exp(v);
+    if (OP == P_ACT) { double h, d; act_eval(v, act, h, d); o0[t] = h; o1[t] = d; }
+    if (OP == P_SINCOS) { double sn, cs; ft_sincos(v, &sn, &cs); o0[t] = sn; o1[t] = cs; }
+    if (OP == P_ATAN) o0[t] = ft_atan(v);
+    if (OP == P_RCP) o0[t] = ft_rcp(v);
+    if (OP == P_WRAP) o0[t] = ft_wrap(v);
+    if (OP == P_WRAP_PM_PI) o0[t] = ft_wrap_pm_pi(v);
+    if (OP == P_REGULARIZE) o0[t] = ft_regularize(v);
+    if (OP == P_COMPOSITE) {
+        // one mixture component of the tan-mixture transform as the MFMA forward evaluates it (flow_fwd.hip: the sincos of P / 2
+        // in the plaquette stage, then y_k and D_k): x = P, s = s_k
+        double sn, cs;
+        ft_sincos(0.5 * v, &sn, &cs);
+        const double es = ft_exp(s[t]), ems = ft_rcp(es);
+        const double cs2 = cs * cs, sn2 = sn * sn;
+        const double D = ems * cs2 + es * sn2;
+        o0[t] = ft_wrap_pm_pi(2 * ft_atan(es * (sn / cs)));
+        o1[t] = D;
+        o2[t] = ft_rcp(D);
+    }
+}
+
+template <int D> __global__ void k_fdiv(int* out, int n) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u < n) out[u] = fdiv<D>(u);
+}
+
+// blockIdx.y = lattice k: L = lstart + 4 k, v = -L .. -L + cnt(L) - 1 with cnt(L) = 3 L + extra, written at out + base(k)
+template <bool FAST, bool POW2>
+__global__ void k_wrap_line(int lstart, int extra, const long long* __restrict__ base, int* out) {
+    const int L = lstart + 4 * (int)blockIdx.y, cnt = 3 * L + extra;
+    const unsigned magic = POW2 ? (unsigned)(L - 1) : (FAST ? 0u : wrap_magic(L));
+    int* o = out + base[blockIdx.y];
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < cnt; k += gridDim.x * blockDim.x)
+        o[k] = wrap_line<FAST, POW2>(k - L, L, magic);
+}
+
+// every stash index map at the sites (rows[r], j) for all j, then (i, cols[c]) for all i; the host keeps the sites each map is for
+__global__ void k_stash(int L, int mu, int off, const int* __restrict__ rows, int nrows, const int* __restrict__ cols, int ncols,
+                        int* act, int* live, int* live2, int* frozen) {
+    const long long nsite = (long long)(nrows + ncols) * L;
+    for (long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x; k < nsite; k += (long long)gridDim.x * blockDim.x) {
+        const int r = (int)(k / L), m = (int)(k % L);
+        const int i = r < nrows ? rows[r] : m, j = r < nrows ? m : cols[r - nrows];
+        act[k] = stash_active_idx(i, j, L, mu);
+        live[k] = stash_live_idx<false>(i, j, L, mu, off);
+        live2[k] = (L & (L - 1)) == 0 ? stash_live_idx<true>(i, j, L, mu, off) : -1;
+        frozen[k] = stash_frozen_idx(i, j, L, mu, off);
+    }
+}
+
+// the block at the far corner of a (1, gy, gz) grid reports in: whether a launch of that extent runs at all
+__global__ void k_grid_corner(int* seen) {
+    if (threadIdx.x == 0 && blockIdx.y == gridDim.y - 1 && blockIdx.z == gridDim.z - 1) seen[0] = (int)(blockIdx.y + 1) ^ (int)(blockIdx.z + 1);
+}
+
+namespace {
+
+struct Dev {                                   // device copies of the host arrays of one call, freed on every path
+    void* p[8] = {};
+    int np = 0;
+    hipError_t err = hipSuccess;
+    template <class T> T* in(const T* h, size_t n) {
+        T* d = alloc<T>(n);
+        if (d && h && err == hipSuccess) err = hipMemcpy(d, h, n * sizeof(T), hipMemcpyHostToDevice);
+        return d;
+    }
+    template <class T> T* alloc(size_t n) {
+        void* d = nullptr;
+        if (err == hipSuccess && n) err = hipMalloc(&d, n * sizeof(T));
+        if (d) p[np++] = d;
+        return static_cast<T*>(d);
+    }
+    template <class T> void out(T* h, const T* d, size_t n) {
+        if (h && d && err == hipSuccess) err = hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost);
+    }
+    void launched() {
+        if (err == hipSuccess) err = hipGetLastError();
+        if (err == hipSuccess) err = hipDeviceSynchronize();
+    }
+    ~Dev() { for (int k = 0; k < np; ++k) (void)hipFree(p[k]); }
+};
+
+template <int OP> void launch_math(int n, int act, const double* x, const double* s, double* o0, double* o1, double* o2) {
+    const int per = (OP == P_SIGMOID4 || OP == P_EXPN4 || OP == P_ACT4) ? 4 : OP == P_EXPN2 ? 2 : 1;
+    const int nt = (n + per - 1) / per;
+    hipLaunchKernelGGL(k_math<OP>, dim3((nt + 255) / 256), dim3(256), 0, 0, x, s, o0, o1, o2, n, act);
+}
+
+template <int... OPS>
+void math_dispatch(int op, std::integer_sequence<int, OPS...>, int n, int act, const double* x, const double* s, double* o0, double* o1,
+                   double* o2) {
+    ((op == OPS ? launch_math<OPS>(n, act, x, s, o0, o1, o2) : void()), ...);
+}
+
+template <int D> void launch_fdiv(int* out, int n) {
+    hipLaunchKernelGGL(k_fdiv<D>, dim3((n + 255) / 256), dim3(256), 0, 0, out, n);
+}
+template <int... DS> void fdiv_dispatch(int d, std::integer_sequence<int, DS...>, int* out, int n) {
+    ((d == DS + 2 ? launch_fdiv<DS + 2>(out, n) : void()), ...);
+}
+
+}  // namespace
+
+extern "C" {
+
+int probe_nops(void) { return P_NOPS; }
+
+// n elements (a multiple of 4 for the four-wide forms, of 2 for ft_expN<2>); s: the composite's s_k, else unused (may be null);
+// o1: the second output of act_eval / act_eval4 / ft_sincos / the composite (D_k), o2: the composite's ft_rcp(D_k)
+int probe_math(int op, int act, const double* x, const double* s, double* o0, double* o1, double* o2, int n) {
+    if (op < 0 || op >= P_NOPS || n <= 0 || !x || !o0) return (int)hipErrorInvalidValue;
+    if ((op == P_SIGMOID4 || op == P_EXPN4 || op == P_ACT4) && n % 4) return (int)hipErrorInvalidValue;
+    if (op == P_EXPN2 && n % 2) return (int)hipErrorInvalidValue;
+    if ((op == P_ACT || op == P_ACT4 || op == P_SINCOS || op == P_COMPOSITE) && !o1) return (int)hipErrorInvalidValue;
+    if (op == P_COMPOSITE && (!s || !o2)) return (int)hipErrorInvalidValue;
+    Dev d;
+    const size_t N = (size_t)n;
+    const double* dx = d.in(x, N);
+    const double* ds = s ? d.in(s, N) : nullptr;
+    double* d0 = d.alloc<double>(N);
+    double* d1 = d.alloc<double>(N);
+    double* d2 = d.alloc<double>(N);
+    if (d.err != hipSuccess) return (int)d.err;
+    math_dispatch(op, std::make_integer_sequence<int, P_NOPS>{}, n, act, dx, ds, d0, d1, d2);
+    d.launched();
+    d.out(o0, d0, N); d.out(o1, d1, N); d.out(o2, d2, N);
+    return (int)d.err;
+}
+
+// out[u] = fdiv<D>(u), u < n, 2 <= D <= 32
+int probe_fdiv(int D, int* out, int n) {
+    if (D < 2 || D > 32 || n <= 0 || !out) return (int)hipErrorInvalidValue;
+    Dev d;
+    int* o = d.alloc<int>((size_t)n);
+    if (d.err != hipSuccess) return (int)d.err;
+    fdiv_dispatch(D, std::make_integer_sequence<int, 31>{}, o, n);
+    d.launched();
+    d.out(out, o, (size_t)n);
+    return (int)d.err;
+}
+
+// form 0: general (wrap_magic), 1: FAST, 2: POW2 (FAST + POW2, as the EXACT kernel instances); lattices L = lstart + 4 k,
+// k < nl; lattice k's results wrap_line(v) for v = -L .. 2 L + extra - 1 at out + base[k]
+int probe_wrap_line(int form, int lstart, int nl, int extra, const long long* base, int* out, long long total) {
+    if (form < 0 || form > 2 || lstart < 4 || lstart % 4 || nl <= 0 || nl > 65535 || extra < 0 || !base || !out || total <= 0)
+        return (int)hipErrorInvalidValue;
+    const int lmax = lstart + 4 * (nl - 1);
+    for (int k = 0; k < nl; ++k)
+        if (base[k] < 0 || base[k] + 3LL * (lstart + 4 * k) + extra > total) return (int)hipErrorInvalidValue;
+    Dev d;
+    const long long* db = d.in(base, (size_t)nl);
+    int* o = d.alloc<int>((size_t)total);
+    if (d.err != hipSuccess) return (int)d.err;
+    const dim3 grid((3 * lmax + extra + 255) / 256, nl);
+    if (form == 0) hipLaunchKernelGGL((k_wrap_line<false, false>), grid, dim3(256), 0, 0, lstart, extra, db, o);
+    if (form == 1) hipLaunchKernelGGL((k_wrap_line<true, false>), grid, dim3(256), 0, 0, lstart, extra, db, o);
+    if (form == 2) hipLaunchKernelGGL((k_wrap_line<true, true>), grid, dim3(256), 0, 0, lstart, extra, db, o);
+    d.launched();
+    d.out(out, o, (size_t)total);
+    return (int)d.err;
+}
+
+// the four stash maps at (nrows + ncols) * L sites (k_stash); every output array holds that many ints
+int probe_stash(int L, int mu, int off, const int* rows, int nrows, const int* cols, int ncols, int* act, int* live, int* live2,
+                int* frozen) {
+    if (L < 4 || L % 4 || mu < 0 || mu > 1 || off < 0 || off > 3 || nrows < 0 || ncols < 0 || nrows + ncols == 0) return (int)hipErrorInvalidValue;
+    if ((nrows && !rows) || (ncols && !cols) || !act || !live || !live2 || !frozen) return (int)hipErrorInvalidValue;
+    for (int r = 0; r < nrows; ++r) if (rows[r] < 0 || rows[r] >= L) return (int)hipErrorInvalidValue;
+    for (int c = 0; c < ncols; ++c) if (cols[c] < 0 || cols[c] >= L) return (int)hipErrorInvalidValue;
+    const size_t ns = (size_t)(nrows + ncols) * (size_t)L;
+    Dev d;
+    const int* dr = nrows ? d.in(rows, (size_t)nrows) : nullptr;
+    const int* dc = ncols ? d.in(cols, (size_t)ncols) : nullptr;
+    int* o[4];
+    for (int k = 0; k < 4; ++k) o[k] = d.alloc<int>(ns);
+    if (d.err != hipSuccess) return (int)d.err;
+    const size_t blocks = (ns + 255) / 256;
+    hipLaunchKernelGGL(k_stash, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, 0, L, mu, off, dr, nrows, dc, ncols,
+                       o[0], o[1], o[2], o[3]);
+    d.launched();
+    d.out(act, o[0], ns); d.out(live, o[1], ns); d.out(live2, o[2], ns); d.out(frozen, o[3], ns);
+    return (int)d.err;
+}
+
+// the runtime's grid limits (hipDeviceProp_t::maxGridSize), and whether a (1, gy, gz) grid launches and reaches its last block:
+// seen = gy ^ gz then; the launch error otherwise
+int probe_grid_limits(int* xyz) {
+    hipDeviceProp_t p;
+    const hipError_t e = hipGetDeviceProperties(&p, 0);
+    if (e == hipSuccess) for (int k = 0; k < 3; ++k) xyz[k] = p.maxGridSize[k];
+    return (int)e;
+}
+int probe_grid_launch(unsigned gy, unsigned gz, int* seen) {
+    if (!seen || gy == 0 || gz == 0) return (int)hipErrorInvalidValue;
+    Dev d;
+    int* o = d.in(seen, 1);
+    if (d.err != hipSuccess) return (int)d.err;
+    hipLaunchKernelGGL(k_grid_corner, dim3(1, gy, gz), dim3(64), 0, 0, o);
+    d.launched();
+    d.out(seen, o, 1);
+    return (int)d.err;
+}
+
+}  // extern "C"
