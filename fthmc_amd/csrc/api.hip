@@ -4,6 +4,7 @@
 // trajectory can be captured into a hipGraph by the caller.
 #include "common.h"
 #include "kernels.h"
+#include "dual.h"
 #include <math.h>
 
 #include <stdio.h>
@@ -94,6 +95,36 @@ WS ws_layout(const FlowArch& A, double* base, int B, int L, int nl, bool train =
     w.hbuf = take(gen ? (size_t)B * A.cmax() * L * L : 0);
     w.gbuf = take(gen ? (size_t)2 * B * A.cmax() * L * L : 0);
     w.total = o;
+    return w;
+}
+
+// Workspace of the second-order entry points (fthmc_ft_action_vjp, fthmc_ft_force_vjp): the head of every layout (the weight
+// expansions and their stamps, fthmc_ws_head_bytes()) is skipped and never written; behind it, regions sized in dual numbers (the
+// action VJP runs the double kernels in their first halves): the dual input x + eps g, every layer's output and activation
+// stash, the generic kernels' scratch, the gP ping-pong, the dual weight gradients and the per-chain log J coefficients.
+// total = 0: the sizes overflow size_t.
+struct VWS { Dual *xd, *X, *stash, *hbuf, *gbuf, *gp, *gp2, *gw; double* glj; size_t total; };
+VWS vjp_layout(const FlowArch& A, double* base, int B, int L, int nl) {
+    VWS w{};
+    bool ovf = false;
+    auto mul = [&](size_t a, size_t b) { size_t r = 0; ovf |= __builtin_mul_overflow(a, b, &r); return r; };
+    size_t o = up((size_t)FLOW_WHEAD_LAYERS * FLOW_WINT);
+    auto take = [&](size_t nd) {                                   // nd dual numbers
+        Dual* p = base && !ovf ? reinterpret_cast<Dual*>(base + o) : nullptr;
+        ovf |= __builtin_add_overflow(o, up(mul(nd, 2)), &o);
+        return p;
+    };
+    const size_t n1 = (size_t)B * L * L, n2 = 2 * n1, nh = nl > 0 ? mul((size_t)B * L * L, A.cmax()) : 0;
+    w.xd = take(n2);
+    w.X = take(mul((size_t)nl, n2));
+    w.stash = take(nl > 0 ? mul((size_t)nl, A.stash_doubles(B, L)) : 0);
+    w.hbuf = take(nh);
+    w.gbuf = take(mul(nh, 2));
+    w.gp = take(n1);
+    w.gp2 = take(n1);
+    w.gw = take(mul((size_t)nl, (size_t)A.params()));
+    w.glj = reinterpret_cast<double*>(take(B));
+    w.total = ovf || o > SIZE_MAX / sizeof(double) ? 0 : o;
     return w;
 }
 
@@ -1099,6 +1130,105 @@ int fthmc_profile_stages(int kind, const double* x, const double* w, const fthmc
         }
     free(h);
     return FTHMC_OK;
+}
+
+}  // extern "C"
+
+// ---- second order: the VJPs of S_eff / log det J (plain kernels) and of the force (the same kernels on dual numbers)
+namespace {
+// shared argument checks and the workspace view of both entry points
+int vjp_begin(const double* x, const double* w, const fthmc_arch_t* arch, int nl, int B, int L, int act, const double* cot,
+              const double* gx, const double* gw, void* ws, size_t ws_bytes, void* stream, Ctx* C, VWS* W) {
+    (void)hipGetLastError();
+    if (!x || !cot || (!gx && !gw) || (nl > 0 && !w) || bad_shape(B, L) || nl < 0) return FTHMC_ERR_ARG;
+    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(make_ctx(arch, stream, C));
+    if (nl > 0 && C->A.k / 2 > L) return FTHMC_ERR_UNSUPPORTED;
+    const VWS v = vjp_layout(C->A, nullptr, B, L, nl);
+    if (v.total == 0) return FTHMC_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < v.total * sizeof(double)) return FTHMC_ERR_WS;
+    *W = vjp_layout(C->A, static_cast<double*>(ws), B, L, nl);
+    C->wcan = w;
+    return FTHMC_OK;
+}
+template <typename T>
+GenLayerArgsT<T> vjp_args(const Ctx& C, const VWS& V, int l, int B, int L, int act) {
+    GenLayerArgsT<T> g{};
+    g.arch = C.A;
+    g.w = C.wcan + (size_t)l * C.A.params();
+    g.stash = reinterpret_cast<T*>(V.stash) + (size_t)l * C.A.stash_doubles(B, L);
+    g.hbuf = reinterpret_cast<T*>(V.hbuf); g.gbuf = reinterpret_cast<T*>(V.gbuf);
+    g.B = B; g.L = L; g.mu = l % 2; g.off = (l / 2) % 4; g.act = act;
+    return g;
+}
+}  // namespace
+
+extern "C" {
+
+size_t fthmc_vjp_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
+    Ctx C;
+    if (bad_shape(B, L) || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
+    if (n_layers > 0 && C.A.k / 2 > L) return 0;
+    return vjp_layout(C.A, nullptr, B, L, n_layers).total * sizeof(double);
+}
+
+int fthmc_ft_action_vjp(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
+                        double beta, const double* gS, const double* glogdet, double* gx, double* gw,
+                        void* ws, size_t ws_bytes, void* stream) {
+    Ctx C; VWS V;
+    FT_TRY(vjp_begin(x, w, arch, n_layers, B, L, act, gS, gx, gw, ws, ws_bytes, stream, &C, &V));
+    const hipStream_t s = C.s;
+    const size_t n2 = (size_t)B * 2 * L * L;
+    double* X = reinterpret_cast<double*>(V.X);
+    for (int l = 0; l < n_layers; ++l) {                          // forward sweep, every layer's activations kept
+        GenLayerArgs g = vjp_args<double>(C, V, l, B, L, act);
+        g.x = l == 0 ? x : X + (size_t)(l - 1) * n2;
+        g.y = X + (size_t)l * n2;
+        FT_TRY(launch_gen_fwd(g, false, s));
+    }
+    // d/d logJ of every layer, per chain: glogdet[b] - gS[b]
+    if (n_layers > 0) FT_TRY(glogdet ? launch_lincomb(glogdet, 1.0, gS, -1.0, 0.0, V.glj, B, s)
+                                     : launch_lincomb(gS, -1.0, nullptr, 0.0, 0.0, V.glj, B, s));
+    double* gcur = reinterpret_cast<double*>(V.gp);
+    double* galt = reinterpret_cast<double*>(V.gp2);
+    FT_TRY(launch_gen_seed(n_layers == 0 ? x : X + (size_t)(n_layers - 1) * n2, gS, B, L, beta, gcur, s));
+    for (int l = n_layers - 1; l >= 0; --l) {
+        GenLayerArgs g = vjp_args<double>(C, V, l, B, L, act);
+        g.up_gp = gcur; g.glogj = V.glj; g.gp_out = galt;
+        g.gw = gw ? gw + (size_t)l * C.A.params() : nullptr;
+        FT_TRY(launch_gen_bwd(g, s));
+        double* t_ = gcur; gcur = galt; galt = t_;
+    }
+    return gx ? launch_kick_from_gp(gcur, nullptr, nullptr, gx, B, L, 0.0, 0.0, s) : FTHMC_OK;
+}
+
+int fthmc_ft_force_vjp(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
+                       double beta, const double* g, double* gx, double* gw, void* ws, size_t ws_bytes, void* stream) {
+    Ctx C; VWS V;
+    FT_TRY(vjp_begin(x, w, arch, n_layers, B, L, act, g, gx, gw, ws, ws_bytes, stream, &C, &V));
+    const hipStream_t s = C.s;
+    const size_t n2 = (size_t)B * 2 * L * L;
+    // the first-order sweep of force_gp on the dual field x + eps g: the eps parts of its link and weight gradients are H g and
+    // d/dw <g, F>
+    FT_TRY(launch_dual_pack(x, g, V.xd, n2, s));
+    for (int l = 0; l < n_layers; ++l) {
+        GenLayerArgsT<Dual> a = vjp_args<Dual>(C, V, l, B, L, act);
+        a.x = l == 0 ? V.xd : V.X + (size_t)(l - 1) * n2;
+        a.y = V.X + (size_t)l * n2;
+        FT_TRY(launch_gen_fwd_dual(a, s));
+    }
+    Dual* gcur = V.gp;
+    Dual* galt = V.gp2;
+    FT_TRY(launch_gen_seed_dual(n_layers == 0 ? V.xd : V.X + (size_t)(n_layers - 1) * n2, nullptr, B, L, beta, gcur, s));
+    for (int l = n_layers - 1; l >= 0; --l) {
+        GenLayerArgsT<Dual> a = vjp_args<Dual>(C, V, l, B, L, act);
+        a.up_gp = gcur; a.glogj_const = -1.0; a.gp_out = galt;
+        a.gw = gw ? V.gw + (size_t)l * C.A.params() : nullptr;
+        FT_TRY(launch_gen_bwd_dual(a, s));
+        Dual* t_ = gcur; gcur = galt; galt = t_;
+    }
+    if (gw && n_layers > 0) FT_TRY(launch_dual_tangent(V.gw, gw, (size_t)n_layers * C.A.params(), s));
+    return gx ? launch_dual_links(gcur, gx, B, L, s) : FTHMC_OK;
 }
 
 }  // extern "C"

@@ -217,29 +217,43 @@ struct FlowArch {
 inline FlowArch flow_arch_default() { return FlowArch{2, {8, 8, 0, 0, 0, 0, 0, 0}, 3, 2, 0}; }
 // validated copy of a caller's shape (FTHMC_ERR_UNSUPPORTED beyond the limits of flow_generic.hip)
 int make_flow_arch(int n_hidden, const int* hidden_sizes, int kernel_size, int n_mix, int final_tanh, FlowArch* out);
-struct GenLayerArgs {
+// T: double (every first-order call), or Dual (dual.h: the forward-over-reverse sweeps of fthmc_ft_force_vjp; weights and the
+// per-chain log J coefficients stay plain doubles)
+struct Dual;
+template <typename T> struct GenLayerArgsT {
     FlowArch arch;           // the net's shape
-    const double* x;         // [B][2][L][L] layer input (null with pin)
-    const double* pin;       // plaquette-level map: input plaquette field [B][L][L]
+    const T* x;              // [B][2][L][L] layer input (null with pin)
+    const T* pin;            // plaquette-level map: input plaquette field [B][L][L]
     const double* w;         // this layer's weights, canonical layout
-    double* y;               // forward / reverse: output links (may alias x), or null
-    double* pout;            // plaquette-level map: output plaquette field
-    double* logj;            // [B] or null
+    T* y;                    // forward / reverse: output links (may alias x), or null
+    T* pout;                 // plaquette-level map: output plaquette field
+    T* logj;                 // [B] or null
     int logj_accumulate;     // logj[b] += instead of =
     double tol;              // reverse
-    double* stash;           // this layer's region (arch.stash_doubles): written by the forward, read by the backward
-    double* hbuf;            // [B][cmax][n] scratch: activations of the conv input
-    double* gbuf;            // [2][B][cmax][n] scratch: gradients, ping-pong
-    const double* up_gp;     // backward: upstream plaquette gradient [B][L][L] or null
-    const double* up_link;   // backward: upstream link gradient [B][2][L][L] or null
+    T* stash;                // this layer's region (arch.stash_doubles): written by the forward, read by the backward
+    T* hbuf;                 // [B][cmax][n] scratch: activations of the conv input
+    T* gbuf;                 // [2][B][cmax][n] scratch: gradients, ping-pong
+    const T* up_gp;          // backward: upstream plaquette gradient [B][L][L] or null
+    const T* up_link;        // backward: upstream link gradient [B][2][L][L] or null
     const double* glogj;     // backward: [B] or null (then glogj_const)
     double glogj_const;
-    double* gp_out;          // backward: plaquette gradient behind this layer (not up_gp)
-    double* gw;              // backward: this layer's weight gradient (canonical layout) or null
+    T* gp_out;               // backward: plaquette gradient behind this layer (not up_gp)
+    T* gw;                   // backward: this layer's weight gradient (canonical layout) or null
     int B, L, mu, off, act;
 };
+using GenLayerArgs = GenLayerArgsT<double>;
 int launch_gen_fwd(const GenLayerArgs& a, bool rev, hipStream_t s);
 int launch_gen_bwd(const GenLayerArgs& a, hipStream_t s);
+// the same layer sequences on dual numbers (forward direction only); gw: value and tangent of this layer's weight gradient
+int launch_gen_fwd_dual(const GenLayerArgsT<Dual>& a, hipStream_t s);
+int launch_gen_bwd_dual(const GenLayerArgsT<Dual>& a, hipStream_t s);
+// seeds of the backward sweeps: gp[b] = coef[b] beta sin P(x[b]) (coef NULL: 1), dual: plus its tangent coef[b] beta cos P P'
+int launch_gen_seed(const double* x, const double* coef, int B, int L, double beta, double* gp, hipStream_t s);
+int launch_gen_seed_dual(const Dual* x, const double* coef, int B, int L, double beta, Dual* gp, hipStream_t s);
+// x + eps g as one dual field; the link gradient (adjoint of the plaquette stencil) of the TANGENT of a dual gP field; tangents
+int launch_dual_pack(const double* x, const double* g, Dual* out, size_t n, hipStream_t s);
+int launch_dual_links(const Dual* gp, double* gx, int B, int L, hipStream_t s);
+int launch_dual_tangent(const Dual* in, double* out, size_t n, hipStream_t s);
 
 // ---- flow_small.hip: L <= 16, one workgroup per chain, whole sequences of the flowed path in one launch
 struct SmallArgs {

@@ -68,8 +68,8 @@ struct Arch {
 
 struct Workspace {
     Tensor buf; size_t bytes;
-    Workspace(const Tensor& like, const fthmc_arch_t* arch, int B, int L, int nl, bool train = false) {
-        bytes = train ? fthmc_train_ws_bytes(arch, B, L, nl) : fthmc_ws_bytes(arch, B, L, nl);
+    Workspace(const Tensor& like, const fthmc_arch_t* arch, int B, int L, int nl, bool train = false, bool vjp = false) {
+        bytes = vjp ? fthmc_vjp_ws_bytes(arch, B, L, nl) : train ? fthmc_train_ws_bytes(arch, B, L, nl) : fthmc_ws_bytes(arch, B, L, nl);
         TORCH_CHECK(bytes > 0, "unsupported shape (B = ", B, ", L = ", L, ", n_layers = ", nl, ")");
         buf = at::empty({(int64_t)((bytes + 7) / 8)}, like.options());
     }
@@ -186,6 +186,36 @@ std::tuple<Tensor, Tensor, Tensor> ft_action_force(const Tensor& x_, const Tenso
     ok(fthmc_ft_force(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, mp(F), ws.ptr(), ws.bytes, cur_stream(x)), "fthmc_ft_force");
     return {S, logdet, F};
 }
+// second order (the autograd formula of ft_action_force, torch_ops.py): gw has n_layers * params entries (none without layers)
+std::tuple<Tensor, Tensor> ft_action_vjp(const Tensor& x_, const Tensor& w_all, int64_t n_layers, double beta, int64_t act, const Tensor& gS_,
+                                         const c10::optional<Tensor>& glogdet_, int64_t n_mix, IntList hidden, int64_t kernel_size) {
+    FT_DEVICE_GUARD(x_);
+    Tensor x = field(x_, "x");
+    Arch A(n_mix, hidden, kernel_size);
+    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
+    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
+    Tensor gS = perchain(gS_, B, "gS");
+    Tensor glogdet = glogdet_.has_value() ? perchain(*glogdet_, B, "glogdet") : Tensor();
+    Tensor gx = at::empty_like(x), gw = at::zeros({w.numel()}, x.options());
+    Workspace ws(x, A.ptr(), B, L, nl, false, true);
+    ok(fthmc_ft_action_vjp(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, cp(gS), glogdet.defined() ? cp(glogdet) : nullptr, mp(gx),
+                           nl > 0 ? mp(gw) : nullptr, ws.ptr(), ws.bytes, cur_stream(x)), "fthmc_ft_action_vjp");
+    return {gx, gw};
+}
+std::tuple<Tensor, Tensor> ft_force_vjp(const Tensor& x_, const Tensor& w_all, int64_t n_layers, double beta, int64_t act, const Tensor& g_,
+                                        int64_t n_mix, IntList hidden, int64_t kernel_size) {
+    FT_DEVICE_GUARD(x_);
+    Tensor x = field(x_, "x"), g = field(g_, "g");
+    TORCH_CHECK(g.sizes() == x.sizes(), "g: shaped like x expected");
+    Arch A(n_mix, hidden, kernel_size);
+    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
+    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
+    Tensor gx = at::empty_like(x), gw = at::zeros({w.numel()}, x.options());
+    Workspace ws(x, A.ptr(), B, L, nl, false, true);
+    ok(fthmc_ft_force_vjp(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, cp(g), mp(gx), nl > 0 ? mp(gw) : nullptr, ws.ptr(), ws.bytes,
+                          cur_stream(x)), "fthmc_ft_force_vjp");
+    return {gx, gw};
+}
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> fthmc_trajectory(const Tensor& x_, const Tensor& v_, const Tensor& u_, const Tensor& w_all,
                                                                     int64_t n_layers, double beta, double dt, int64_t nstep, int64_t mode,
                                                                     int64_t act, int64_t n_mix, IntList hidden, int64_t kernel_size) {
@@ -233,6 +263,8 @@ TORCH_LIBRARY(fthmc_hip, m) {
     m.def("ft_action_force(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor)");
     m.def("fthmc_trajectory(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, float beta, float dt, int nstep, int mode, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("train_grad(Tensor xi, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor)");
+    m.def("ft_action_vjp(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor gS, Tensor? glogdet=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
+    m.def("ft_force_vjp(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor g, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
 }
 
 // "CUDA" is the dispatch key of HIP devices in PyTorch-ROCm
@@ -248,4 +280,6 @@ TORCH_LIBRARY_IMPL(fthmc_hip, CUDA, m) {
     m.impl("ft_action_force", &ft_action_force);
     m.impl("fthmc_trajectory", &fthmc_trajectory);
     m.impl("train_grad", &train_grad);
+    m.impl("ft_action_vjp", &ft_action_vjp);
+    m.impl("ft_force_vjp", &ft_force_vjp);
 }

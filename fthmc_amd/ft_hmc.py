@@ -128,7 +128,13 @@ class FieldTransformation(nn.Module):
 
     # ---- reference methods ----------------------------------------------------------
     def action(self, x: torch.Tensor):
-        """ft_hmc.py:135-141: S_W(F(x)) - sum logJ, per chain."""
+        """ft_hmc.py:135-141: S_W(F(x)) - sum logJ, per chain.  Differentiable in x and every conv parameter (as the reference's)
+        when grad mode is on and either requires grad: autograd.grad(action(x).sum(), x, create_graph=True) is the force, and
+        differentiable again (qed_helpers.flowed_action)."""
+        return qed.flowed_action(self.flow, x, self.config.beta, self.weights(x.device))
+
+    def _action(self, x: torch.Tensor):
+        """S_eff without an autograd graph: what the drivers (calc_energy, hmc, run) use"""
         return ops.ft_action(x, self.weights(x.device), len(self.flow), self.config.beta, self._act)[0]
 
     def flow_forward(self, x: torch.Tensor):
@@ -151,8 +157,8 @@ class FieldTransformation(nn.Module):
     def calc_energy(self, x: torch.Tensor, v: torch.Tensor):
         """ft_hmc.py:177-178 (literal) or the per-chain Hamiltonian."""
         if self.energy_mode == 'reference_literal':
-            return self.action(x) + ops.kinetic(v).sum()
-        return self.action(x) + 0.5 * ops.kinetic(v)
+            return self._action(x) + ops.kinetic(v).sum()
+        return self._action(x) + 0.5 * ops.kinetic(v)
 
     def leapfrog(self, x: torch.Tensor, v: torch.Tensor):
         """ft_hmc.py:180-188."""
@@ -189,10 +195,10 @@ class FieldTransformation(nn.Module):
             self._carry = (xnew, xnew._version, wkey, self.config.beta, r['state'])
             self._last_obs = (r['plaq'], r['Q'])
         else:
-            h0 = self.action(x).sum() + 0.5 * ops.kinetic(v).sum()
+            h0 = self._action(x).sum() + 0.5 * ops.kinetic(v).sum()
             x_, v_ = self.leapfrog(x, v)
             x_ = self.wrap(x_)
-            dh = self.action(x_).sum() + 0.5 * ops.kinetic(v_).sum() - h0
+            dh = self._action(x_).sum() + 0.5 * ops.kinetic(v_).sum() - h0
             acc = u < torch.exp(-dh)
             xnew = x_ if bool(acc) else x
         metrics.update({'dt': time.time() - t0, 'acc': acc.detach(), 'dh': dh.detach()})

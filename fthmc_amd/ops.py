@@ -47,8 +47,16 @@ def ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
     return int(_lib.load().fthmc_ws_bytes(_arch(arch), B, L, n_layers))
 
 
-def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None):
-    need = int(_lib.load().fthmc_train_ws_bytes(_arch(arch), B, L, nl)) if train else ws_bytes(B, L, nl, arch)
+def vjp_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
+    """Scratch of the second-order calls (ft_action_vjp, ft_force_vjp); 0 for a refused shape."""
+    return int(_lib.load().fthmc_vjp_ws_bytes(_arch(arch), B, L, n_layers))
+
+
+def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None, vjp: bool = False):
+    if vjp:
+        need = vjp_ws_bytes(B, L, nl, arch)
+    else:
+        need = int(_lib.load().fthmc_train_ws_bytes(_arch(arch), B, L, nl)) if train else ws_bytes(B, L, nl, arch)
     # one workspace per (device, stream): chain groups running on concurrent streams must not share scratch
     key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream)
     buf = _WS.get(key)
@@ -612,6 +620,50 @@ def ft_force(x, w, n_layers: int, beta: float, act='silu', arch=None, wkey=None)
     check(_lib.load().fthmc_ft_force_v(_p(x), _p(w), ap, n_layers, B, L, act_code(act), float(beta), _p(F), ws, nb,
                                      _stream(x), weights_version(wkey)), 'fthmc_ft_force')
     return F
+
+
+def _chains(t, B: int, name: str):
+    t = _dev(t, name).reshape(-1)
+    if t.numel() != B:
+        raise FthmcError(f'{name}: expected {B} per-chain entries, got {t.numel()}')
+    return t
+
+
+def ft_action_vjp(x, w, n_layers: int, beta: float, gS, glogdet=None, act='silu', arch=None, need_gx=True, need_gw=True):
+    """-> (gx, gw): d/dx and d/dw of sum_b [gS[b] S_eff[b] + glogdet[b] logdet[b]] (C ABI fthmc_ft_action_vjp: the backward of
+    ft_action, autograd of qed_helpers.py:212-223).  gx [B, 2, L, L]; gw flat [n_layers * params] like `w` (empty without
+    layers); either is None when not asked for.  Plain kernels for every net shape, deterministic."""
+    x = _field(x); B, _, L, _ = x.shape
+    w, ap, a = _wall(w, n_layers, arch)
+    gS = _chains(gS, B, 'gS')
+    glogdet = None if glogdet is None else _chains(glogdet, B, 'glogdet')
+    gx = torch.empty_like(x) if need_gx else None
+    gw = _tag(torch.zeros(n_layers * arch_params(a), dtype=x.dtype, device=x.device), w, a) if need_gw else None
+    if gx is None and not n_layers:
+        return gx, gw
+    ws, nb = _ws(x, B, L, n_layers, arch=a, vjp=True)
+    check(_lib.load().fthmc_ft_action_vjp(_p(x), _p(w), ap, n_layers, B, L, act_code(act), float(beta), _p(gS), _p(glogdet),
+                                          _p(gx), _p(gw) if n_layers else None, ws, nb, _stream(x)), 'fthmc_ft_action_vjp')
+    return gx, gw
+
+
+def ft_force_vjp(x, w, n_layers: int, beta: float, g, act='silu', arch=None, need_gx=True, need_gw=True):
+    """-> (gx, gw) for the force F = d(sum_b S_eff)/dx (ft_force) and a cotangent g shaped like x: gx = (dF/dx)^T g = H g (the
+    Hessian of sum_b S_eff applied to g), gw = d/dw <g, F> flat like `w` (C ABI fthmc_ft_force_vjp: autograd of
+    qed_helpers.py:226-242 with create_graph=True).  Dual-number instances of the plain kernels, deterministic."""
+    x = _field(x); B, _, L, _ = x.shape
+    g = _field(g, 'g')
+    if g.shape != x.shape:
+        raise FthmcError(f'g: expected {tuple(x.shape)}, got {tuple(g.shape)}')
+    w, ap, a = _wall(w, n_layers, arch)
+    gx = torch.empty_like(x) if need_gx else None
+    gw = _tag(torch.zeros(n_layers * arch_params(a), dtype=x.dtype, device=x.device), w, a) if need_gw else None
+    if gx is None and not n_layers:
+        return gx, gw
+    ws, nb = _ws(x, B, L, n_layers, arch=a, vjp=True)
+    check(_lib.load().fthmc_ft_force_vjp(_p(x), _p(w), ap, n_layers, B, L, act_code(act), float(beta), _p(g), _p(gx),
+                                         _p(gw) if n_layers else None, ws, nb, _stream(x)), 'fthmc_ft_force_vjp')
+    return gx, gw
 
 
 def ft_leapfrog(x, v, w, n_layers: int, beta: float, dt: float, nstep: int, act='silu', arch=None, wkey=None):

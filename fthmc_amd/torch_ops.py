@@ -26,6 +26,10 @@ Operators (reference call site each one replaces):
   fthmc_trajectory(x, v, u, w_all, n_layers, beta, dt, nstep, mode, act, n_mix=2, hidden, kernel_size)
                    -> (x_new, dH, acc, plaq, Q)                        ft_hmc.py:180-224 / ipynb/ft_hmc.py:394-435
   train_grad(xi, w_all, n_layers, beta, act, n_mix=2, hidden, kernel_size) -> (x, logq, logp, gw)     train.py:162-228
+  ft_action_vjp(x, w_all, n_layers, beta, act, gS, glogdet=None, n_mix=2, hidden, kernel_size) -> (gx, gw)
+                   d/dx, d/dw of sum_b gS_b S_eff_b + glogdet_b logdet_b        (autograd of qed_helpers.py:212-223)
+  ft_force_vjp(x, w_all, n_layers, beta, act, g, n_mix=2, hidden, kernel_size) -> (gx, gw)
+                   H g and d/dw <g, F> for the force F                         (autograd of qed_helpers.py:226-242, create_graph)
 `act` is the integer code of fthmc_hip.h (0 silu/swish, 1 relu, 2 leaky_relu); `mode` 0 = MD
 semantics, 1 = literal reference leapfrog.  The s/t net's shape travels IN the schema, as plain
 integers: `n_mix` mixture components, `hidden` = hidden_sizes (None = the reference default [8, 8]), `kernel_size` --
@@ -141,6 +145,22 @@ if BACKEND == 'python':
         return r['x'], r['logq'], r['logp'], r['gw']
 
 
+    @torch.library.custom_op('fthmc_hip::ft_action_vjp', mutates_args=(), device_types=_DEV)
+    def ft_action_vjp(x: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta: float, act: int, gS: torch.Tensor,
+                      glogdet: Optional[torch.Tensor] = None, n_mix: int = 2, hidden: Optional[Sequence[int]] = None,
+                      kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
+        gx, gw = ops.ft_action_vjp(x, w_all, n_layers, beta, gS, glogdet, _act(act), arch=_arch(n_mix, hidden, kernel_size))
+        return gx, gw
+
+
+    @torch.library.custom_op('fthmc_hip::ft_force_vjp', mutates_args=(), device_types=_DEV)
+    def ft_force_vjp(x: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta: float, act: int, g: torch.Tensor,
+                     n_mix: int = 2, hidden: Optional[Sequence[int]] = None,
+                     kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
+        gx, gw = ops.ft_force_vjp(x, w_all, n_layers, beta, g, _act(act), arch=_arch(n_mix, hidden, kernel_size))
+        return gx, gw
+
+
 # ---------------------------------------------------------------- shapes for tracing (meta tensors)
 def _b(x):
     return x.new_empty(x.shape[0])
@@ -201,6 +221,16 @@ def _(xi, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
     return torch.empty_like(xi), _b(xi), _b(xi), xi.new_empty(w_all.numel())
 
 
+@torch.library.register_fake('fthmc_hip::ft_action_vjp')
+def _(x, w_all, n_layers, beta, act, gS, glogdet=None, n_mix=2, hidden=None, kernel_size=3):
+    return torch.empty_like(x), x.new_empty(w_all.numel())
+
+
+@torch.library.register_fake('fthmc_hip::ft_force_vjp')
+def _(x, w_all, n_layers, beta, act, g, n_mix=2, hidden=None, kernel_size=3):
+    return torch.empty_like(x), x.new_empty(w_all.numel())
+
+
 # ---------------------------------------------------------------- autograd formulas
 def _wilson_setup(ctx, inputs, output):
     x, beta = inputs
@@ -242,10 +272,38 @@ def _layer_backward(ctx, gy, glogJ):
 
 torch.library.register_autograd('fthmc_hip::flow_layer_fwd', _layer_backward, setup_context=_layer_setup)
 
+
+def _action_force_setup(ctx, inputs, output):
+    x, w_all, n_layers, beta, act, n_mix, hidden, kernel_size = inputs
+    ctx.save_for_backward(x, w_all)
+    ctx.args = (n_layers, beta, act)
+    ctx.arch = (n_mix, hidden, kernel_size)
+
+
+def _action_force_backward(ctx, gS, glogdet, gF):
+    # S_eff and logdet: the action VJP; F: the force VJP (gx = H gF, gw = d/dw <gF, F>).  First order in this formula: the VJP
+    # operators carry no autograd formula of their own
+    x, w = ctx.saved_tensors
+    gx, gw = torch.zeros_like(x), torch.zeros(w.numel(), dtype=x.dtype, device=x.device)
+    if gS is not None or glogdet is not None:
+        gS_ = gS.contiguous() if gS is not None else torch.zeros(x.shape[0], dtype=x.dtype, device=x.device)
+        gld = glogdet.contiguous() if glogdet is not None else None
+        a, b = torch.ops.fthmc_hip.ft_action_vjp(x, w, *ctx.args, gS_, gld, *ctx.arch)
+        gx, gw = gx + a, gw + b
+    if gF is not None:
+        a, b = torch.ops.fthmc_hip.ft_force_vjp(x, w, *ctx.args, gF.contiguous(), *ctx.arch)
+        gx, gw = gx + a, gw + b
+    return gx, gw.view_as(w), None, None, None, None, None, None
+
+
+torch.library.register_autograd('fthmc_hip::ft_action_force', _action_force_backward, setup_context=_action_force_setup)
+
 if BACKEND == 'compiled':                        # the module's names are the dispatcher's operators themselves
     for _n in ('wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x', 'flow_layer_bwd_w',
-               'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad'):
+               'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad', 'ft_action_vjp',
+               'ft_force_vjp'):
         globals()[_n] = getattr(torch.ops.fthmc_hip, _n)
 
 __all__ = ['wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x',
-           'flow_layer_bwd_w', 'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad']
+           'flow_layer_bwd_w', 'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad',
+           'ft_action_vjp', 'ft_force_vjp']

@@ -12,7 +12,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .layers import flow_activation, flow_weights, weights_generation
+from torch.autograd.function import once_differentiable
+
+from .layers import _flow_rows, flow_activation, flow_weights, weights_generation
 
 TWO_PI = 2 * PI
 
@@ -146,16 +148,112 @@ def ft_flow_inv(flow: nn.ModuleList, x: torch.Tensor, tol: float = 1e-12):
     return ops.flow_reverse(x, flow_weights(flow, x.device), len(flow), flow_activation(flow), tol=tol)[0]
 
 
+# ---------------------------------------------------------------- autograd through S_eff and the force
+# meta of a flow call: (n_layers, beta, activation, net shape); the conv parameters go in as inputs of their own, so that their
+# gradients land in each one's .grad as torch puts them (plain flows and flows flattened by flatten_flow alike)
+def _flow_call(flow, beta, dev, w=None):
+    w = flow_weights(flow, dev) if w is None else w
+    params = [p for row in _flow_rows(flow) for p in row]
+    return w, (len(flow), float(beta), flow_activation(flow), ops.arch_of(w)), params
+
+
+def _split_params(gw, meta, nparams: int):
+    """flat [n_layers * params] -> one gradient per conv parameter, in the order _flow_call lists them"""
+    nl, _, _, arch = meta
+    return [g for row in ops.unpack_weight_grads(gw, nl, arch=arch) for g in row] if nl else [None] * nparams
+
+
+class _FtForceFn(torch.autograd.Function):
+    """F = d(sum_b S_eff)/dx (the tuned ft_force) attached to autograd wrt the field and every conv parameter: the backward is
+    the force VJP (fthmc_ft_force_vjp: gx = H g, gw = d/dw <g, F>).  Third order raises (once_differentiable)."""
+
+    @staticmethod
+    def forward(ctx, x, w, meta, *params):
+        nl, beta, act, arch = meta
+        ctx.save_for_backward(x, w)
+        ctx.meta = meta
+        return ops.ft_force(x, w, nl, beta, act, arch=arch)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        nl, beta, act, arch = ctx.meta
+        need_gx, need_gw = ctx.needs_input_grad[0], any(ctx.needs_input_grad[3:])
+        if not (need_gx or need_gw):
+            return (None, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
+        gx, gw = ops.ft_force_vjp(x, w, nl, beta, g.contiguous(), act, arch=arch, need_gx=need_gx, need_gw=need_gw)
+        npar = len(ctx.needs_input_grad) - 3
+        gparams = _split_params(gw, ctx.meta, npar) if need_gw else [None] * npar
+        return (gx, None, None, *gparams)
+
+
+class _ActionGwFn(torch.autograd.Function):
+    """d/dw sum_b gS_b S_eff_b (the action VJP) as a node whose own derivative raises: second derivatives of S_eff with respect
+    to the flow weights are not part of the HIP path"""
+
+    @staticmethod
+    def forward(ctx, x, w, gS, meta, *params):
+        nl, beta, act, arch = meta
+        return ops.ft_action_vjp(x, w, nl, beta, gS.contiguous(), None, act, arch=arch, need_gx=False)[1]
+
+    @staticmethod
+    def backward(ctx, ggw):
+        raise RuntimeError('ft_action: second derivatives with respect to the flow weights are not supported '
+                           '(only the force, d S_eff / dx, can be differentiated again)')
+
+
+class _FtActionFn(torch.autograd.Function):
+    """S_eff per chain, differentiable in the field and every conv parameter: gx = gS_b F_b through _FtForceFn (so that
+    autograd.grad(S.sum(), x, create_graph=True) is the differentiable force), gw from the action VJP"""
+
+    @staticmethod
+    def forward(ctx, x, w, meta, *params):
+        nl, beta, act, arch = meta
+        ctx.save_for_backward(x, w, *params)
+        ctx.meta = meta
+        return ops.ft_action(x, w, nl, beta, act, arch=arch)[0]
+
+    @staticmethod
+    def backward(ctx, gS):
+        x, w, *params = ctx.saved_tensors
+        meta = ctx.meta
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = _FtForceFn.apply(x, w, meta, *params) * gS[:, None, None, None]
+        gparams = [None] * len(params)
+        if any(ctx.needs_input_grad[3:]):
+            gparams = _split_params(_ActionGwFn.apply(x, w, gS, meta, *params), meta, len(params))
+        return (gx, None, None, *gparams)
+
+
+def _wants_graph(x, params):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+
+
+def flowed_action(flow, x: torch.Tensor, beta: float, w: Optional[torch.Tensor] = None):
+    """S_eff = S_W(F(x)) - log det J per chain; attached to autograd (field and conv parameters) when grad mode is on and either
+    requires grad, plain numbers otherwise.  `w`: the flow's flat weights when the caller has them."""
+    w, meta, params = _flow_call(flow, beta, x.device, w)
+    if _wants_graph(x, params):
+        return _FtActionFn.apply(x, w, meta, *params)
+    return ops.ft_action(x, w, meta[0], beta, meta[2], arch=meta[3])[0]
+
+
 def ft_action(param, flow, x: torch.Tensor):
-    """qed_helpers.py:212-223: S_W(F(x)) - sum_l logJ_l, per chain."""
-    return ops.ft_action(x, flow_weights(flow, x.device), len(flow), param.beta, flow_activation(flow))[0]
+    """qed_helpers.py:212-223: S_W(F(x)) - sum_l logJ_l, per chain.  Differentiable in the field and every conv parameter (as
+    the reference's) when grad mode is on and either requires grad; the same numbers either way."""
+    return flowed_action(flow, x, param.beta)
 
 
 def ft_force(param, flow, field: torch.Tensor, create_graph=False):
-    """qed_helpers.py:226-242: d(sum_b S_eff)/dx."""
+    """qed_helpers.py:226-242: d(sum_b S_eff)/dx.  create_graph=True: the same numbers, attached to autograd with respect to the
+    field (when it requires grad) and every conv parameter, whose backward is the force VJP (fthmc_ft_force_vjp): losses of the
+    force, Hessian-vector products of S_eff.  Third derivatives raise."""
+    w, meta, params = _flow_call(flow, param.beta, field.device)
     if create_graph:
-        raise NotImplementedError('second-order graphs through the force are not part of the HIP path')
-    return ops.ft_force(field, flow_weights(flow, field.device), len(flow), param.beta, flow_activation(flow))
+        return _FtForceFn.apply(field, w, meta, *params)
+    return ops.ft_force(field, w, meta[0], param.beta, meta[2], arch=meta[3])
 
 
 # ---------------------------------------------------------------- plain HMC

@@ -256,6 +256,25 @@ int fthmc_ft_force(const double* x, const double* w, const fthmc_arch_t* arch, i
                    double beta, double* F, void* ws, size_t ws_bytes, void* stream);
 int fthmc_ft_force_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
                    double beta, double* F, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version);
+/* Second order: the vector-Jacobian products autograd takes through ft_action / ft_force.  Every net shape, the default one
+ * included, runs on the plain kernels (csrc/flow_generic.hip; the force VJP on their dual-number instances, csrc/dual.h),
+ * reductions in a fixed order: the same inputs give the same bits, whatever fthmc_set_variant / fthmc_set_small_path say.
+ * Shape limits: those of the plain kernels (n_layers = 0 allowed).  gx[B][2][L][L], gw[n_layers * fthmc_arch_params(arch)]:
+ * either may be NULL (not wanted), not both.  ws: fthmc_vjp_ws_bytes(arch, B, L, n_layers); its first fthmc_ws_head_bytes()
+ * bytes (the weight expansions of the other entry points) are never written.
+ *
+ * gx, gw = d/dx, d/dw of sum_b [ gS[b] S_eff[b] + glogdet[b] logdet[b] ]   (glogdet NULL = 0)
+ * autograd of fthmc/utils/qed_helpers.py:212-223 (ft_action), fthmc/ft_hmc.py:135-141 */
+int fthmc_ft_action_vjp(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
+                        double beta, const double* gS, const double* glogdet, double* gx, double* gw,
+                        void* ws, size_t ws_bytes, void* stream);
+/* with F = d(sum_b S_eff)/dx (fthmc_ft_force) and a cotangent g[B][2][L][L]: gx = (dF/dx)^T g = H g, gw = d/dw <g, F>
+ * autograd of fthmc/utils/qed_helpers.py:226-242 with create_graph=True (the reference's force is
+ * torch.autograd.grad(ft_action(x).sum(), x, create_graph=...)); n_layers = 0: the Hessian of the Wilson action */
+int fthmc_ft_force_vjp(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
+                       double beta, const double* g, double* gx, double* gw, void* ws, size_t ws_bytes, void* stream);
+/* Scratch for the two calls above (0 for a refused shape). */
+size_t fthmc_vjp_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers);
 /* x_, v_ = leapfrog with ft_force.  ipynb/ft_hmc.py:394-418. */
 int fthmc_ft_leapfrog(const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int n_layers,
                       int B, int L, int act, double beta, double dt, int nstep,
