@@ -6,6 +6,9 @@
 //   plaquettes + net input (cos P, sin P) on tile+3  ->  conv1 (2 -> 8) + act on tile+2  ->  conv2 (8 -> 8) + act
 //   on the live lines of tile+1  ->  conv3 (8 -> 3) at the tile's active sites  ->  tan-mixture transform,
 //   log J  ->  link update x' = wrap(x +- (P' - P)) at the active links.
+// Where the tiles divide a power-of-two lattice (the EXACT instances: every production shape) the tile grid of a layer starts at
+// the layer's stripe phase instead of at 0 (ALIGNED tile origins, below): the windows across the stripe lines shrink to
+// tile+3 -> 20 lines, tile+2 -> 18 lines, and the live lines of tile+1 to the tile's own twelve.
 // conv1 and conv2 are implicit GEMMs on v_mfma_f64_16x16x4_f64 (conv2: flow_mfma_common.h mfma_stage; conv1: the frozen
 // taps only, below), both operands one ds_read_b64 per MFMA out of LDS; conv3 (N = 3) stays on the fp64 VALU with its
 // wave-uniform weights in SGPRs.
@@ -23,11 +26,12 @@ using namespace fthmc_flow;
 
 constexpr unsigned FWD_HAS_POUT = 1u << 16, FWD_HAS_DBG = 1u << 17, FWD_HAS_PIN = 1u << 18;     // flags in the forward kernel's hoa word
 
-// LDS plan: three workgroups share a CU (3 x 51.7 KB), so planes whose lifetimes do not overlap share memory:
+// LDS plan: three workgroups share a CU (3 x 53 696 B; with aligned tile origins, whose windows are two lines shorter across the
+// stripe direction, 3 x 51 296 B), so planes whose lifetimes do not overlap share memory:
 //   region A: h1 (conv1 -> conv2's MFMA reads), then h2 (conv2's epilogue, after a barrier -> conv3)
 //   region B: the net input (stage 0 -> conv1), then the conv3 partials / delta and the transform scratch
-template <int TR, int TC> struct SmemF {
-    using G = Geom<TR, TC>;
+template <int TR, int TC, int MU, bool AL> struct SmemF {
+    using G = Geom<TR, TC, MU, AL>;
     static constexpr int cmax2(int a, int b) { return a > b ? a : b; }
     static constexpr int H1 = 0;                              // [8][PS1]
     static constexpr int H2 = 0;                              // [8][PS2]   (over h1)
@@ -49,7 +53,8 @@ template <int TR, int TC> struct SmemF {
 // code paths instead of both (selects on per-lane values by a uniform mu were ~5 % of the VALU instructions).
 // EXACT: the tiles divide the lattice and L is a power of two (L = 64, 128, 256: BASELINE configs 3, 4, 5), so every tile site
 // is a lattice site -- the lattice-edge halves of the bounds tests of the stash stores, the link update and the active sites
-// fold away -- and a window line wraps by one v_and.
+// fold away -- and a window line wraps by one v_and.  These instances also start their tiles at the layer's stripe phase (AL in the
+// kernel): the stripe classes of the window lines are compile-time constants and conv1 / conv2 run fewer MFMA tiles (11 + 7 for 12 + 8).
 // Hot arguments: the explicit scalars ahead of the argument block arrive in SGPRs WITH the wave (kernarg preload: csrc/Makefile
 // -amdgpu-kernarg-preload-count=16; 15 dwords here), so the first loads of a workgroup do not wait for a scalar load of a cold
 // argument segment; the block itself (A0) serves what is needed later or rarely.  hoa = off | act << 8 | flags << 16
@@ -76,9 +81,10 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     const bool has_stash = FS || TS || (!ES && A.stash != nullptr), has_y = SW || A.y != nullptr;
     const bool want_logj = ES || TS || (!FS && A.logj_part != nullptr);
     const bool stash_h = TS || (!SW && has_stash && A0.stash_h != 0);
-    using S = SmemF<TR, TC>;
-    using G = Geom<TR, TC>;
-    constexpr int R0C = G::R0C, R1R = G::R1R, R1C = G::R1C, R2R = G::R2R, R2C = G::R2C;
+    using S = SmemF<TR, TC, MU, EXACT>;
+    using G = Geom<TR, TC, MU, EXACT>;
+    // R0C, RS1: the LDS row strides of the input / h1 windows; R0A, R1 (below): their extent ALONG the stripe lines
+    constexpr int R0C = G::R0C, R0A = TC + 6, R1R = G::R1R, R1C = G::R1C, R2R = G::R2R, R2C = G::R2C;
     constexpr int N3 = G::N3, NA = G::NA, NAS = G::NAS, TQ = 2, RS1 = G::RS1;
     constexpr int PS0 = G::PS0, PS1 = G::PS1, PS2 = G::PS2;
     __shared__ __attribute__((aligned(16))) double sm[S::SIZE];
@@ -101,7 +107,28 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     BlockTile bt;
     if (!block_tile(A.B, nti_, ntj_, bt)) return;               // padding blocks when B % 8 != 0 (whole block exits)
     const int b = bt.b, tile = bt.tile, ntiles = nti_ * ntj_;
-    const int i0 = bt.ti * TR, j0 = bt.tj * TC;
+    // ALIGNED tile origins (the EXACT instances): the stripe pattern has period 4 across the lines (active line a: h2 live on a - 1,
+    // a, a + 1, dead on a + 2; net input frozen on a + 1, a + 2) and the lattice is periodic, so a layer's tile grid may start anywhere:
+    // across the lines (columns for mu = 0, rows for mu = 1) tile t starts at (16 t + shift) mod L with shift = off + 3 (mod 4), the
+    // same for every tile and chain.  In tile coordinates the active lines then sit at the fixed residue TOFF = 1 (lines 1, 5, 9, 13),
+    // whatever `off`: the twelve h2 lines conv3 reads (0 1 2, 4 5 6, ...) are exactly the tile's own twelve live lines -- conv2 has no
+    // halo across the lines (108 pairs = 7 MFMA tiles instead of 8), conv1 is needed on 18 lines across (tile lines -2 .. 15: 9 pair
+    // positions = 11 tiles + 4 leftover pairs instead of 12 + 8), the net input on 10 frozen lines instead of 12 -- and every stripe
+    // class below is a constant of the lane.  shift = off + 3 rather than off + 2: the 18 h1 lines are then the pair positions
+    // u = 0 .. 8 of the window as it stands (the spare 18th line falls on its low side, window line 0), and the leftover pairs keep
+    // their corner.  A tile may straddle the lattice edge: every GLOBAL line of an own site is (origin + r) & (L - 1) (gi / gj below);
+    // along the lines nothing moves.  The stash is addressed by global site, so the backward kernels do not care where the forward's
+    // tiles start.  Non-EXACT instances (ragged lattices, L not a power of two) keep origin 0 and the run-time classes.
+    constexpr bool AL = EXACT;
+    constexpr int TOFF = 1;
+    const int shift = AL ? (off + 3) & 3 : 0;
+    const int i0 = (AL && mu == 1) ? (bt.ti * TR + shift) & (L - 1) : bt.ti * TR;
+    const int j0 = (AL && mu == 0) ? (bt.tj * TC + shift) & (L - 1) : bt.tj * TC;
+    const int offt = AL ? TOFF : off;                                 // the active lines' residue mod 4 in TILE coordinates
+    const int o4 = AL ? 0 : (mu == 0 ? j0 : i0);                      // the tile origin across the lines, as far as stripe classes go
+    // global row / column of tile row r / column c, 0 <= r, c < 16 (window lines go through wrap_line)
+    auto gi = [&](int r) { return (AL && mu == 1) ? (i0 + r) & (L - 1) : i0 + r; };
+    auto gj = [&](int c) { return (AL && mu == 0) ? (j0 + c) & (L - 1) : j0 + c; };
     __builtin_assume(i0 >= 0 && i0 < L && j0 >= 0 && j0 < L && b >= 0 && b < (1 << 20) && A.B > 0 && A.B <= (1 << 20));
     const unsigned bn = (unsigned)b * (unsigned)n;                    // 32-bit plane offsets: uniform_at()
     const double* __restrict__ x0 = uniform_at(A.x, 2u * bn);
@@ -137,7 +164,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     if ((has_y || has_pout) && tid < N3) {
         const int r = fdiv<TC>(tid), c = tid - r * TC;
         if (EXACT || (i0 + r < L && j0 + c < L)) {
-            const unsigned at = (unsigned)(mul24(i0 + r, L) + j0 + c);
+            const unsigned at = (unsigned)(mul24(gi(r), L) + gj(c));
             if (pin) xv0 = ldu(pin, at); else { xv0 = ldu(x0, at); xv1 = ldu(x1, at); }
         }
     }
@@ -153,26 +180,36 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     //                       read with all 18 taps (rows and columns 16 .. 21)
     // Five waves instead of eight run the loads, the wrapped addresses and the sincos; passive and foreign active
     // plaquettes are never formed.
-    constexpr int NFL = (R0C + 3) / 4 * 2, NFT = R0C * NFL;
-    static_assert(G::R0R == R0C && NFT + NA + 36 <= NT && R0C == 22, "stage-0 task list");
+    // Aligned tiles: conv1 runs on window lines 0 .. 17 across, so the input is read on lines 0 .. 19 of which 1 2, 5 6, .. 17 18 are
+    // frozen: 10 lines x 22 + 64 active; the leftover pairs (h1 lines 16, 17 across, 16 .. 19 along) read the constant on lines 16
+    // and 19 across, 16 .. 21 along: 12 sites.
+    constexpr int NFL = AL ? 10 : (R0A + 3) / 4 * 2, NFT = R0A * NFL, NCC = AL ? 12 : 36;
+    static_assert(TR == TC && (AL ? (mu == 0 ? G::R0R : G::R0C) == R0A && G::N0 == R0A * (R0A - 2) : G::R0R == R0C && R0C == R0A) &&
+                  NFT + NA + NCC <= NT && R0A == 22, "stage-0 task list");
     {
-        const int ps = off == 3 ? -1 : off;                                // first line of the first frozen pair (class 1: x = off mod 4)
+        const int ps = AL ? TOFF : (off == 3 ? -1 : off);                  // first line of the first frozen pair (class 1: x = off mod 4)
         int r = 0, c = 0;
         bool fz = false, ao = false;
         if (tid < NFT) {
             const int a = fdiv<NFL>(tid), k = tid - a * NFL;
             const int x = ps + 4 * (k >> 1) + (k & 1);
-            fz = (unsigned)x < (unsigned)R0C;
+            fz = (unsigned)x < (unsigned)(AL ? R0A - 2 : R0A);
             r = mu == 0 ? a : x; c = mu == 0 ? x : a;
         } else if (tid < NFT + NA) {
             const int a = tid - NFT;
-            r = 3 + (mu == 0 ? a / (TC / 4) : off + 4 * (a / TC));
-            c = 3 + (mu == 0 ? off + 4 * (a % (TC / 4)) : a % TC);
+            r = 3 + (mu == 0 ? a / (TC / 4) : offt + 4 * (a / TC));
+            c = 3 + (mu == 0 ? offt + 4 * (a % (TC / 4)) : a % TC);
             ao = true;
-        } else if (tid < NFT + NA + 36) {
-            const int k = tid - (NFT + NA), rr = 16 + fdiv<6>(k), cc = 16 + (k - 6 * fdiv<6>(k));
-            const int sel = ((mu == 0 ? cc : rr) - 3 - off) & 3;
-            if (sel != 1 && sel != 2) { sIn[rr * R0C + cc] = 1.0; sIn[PS0 + rr * R0C + cc] = 0.0; }
+        } else if (tid < NFT + NA + NCC) {
+            const int k = tid - (NFT + NA);
+            if (AL) {
+                const int x = 16 + 3 * (k & 1), al = 16 + (k >> 1), at = mu == 0 ? al * R0C + x : x * R0C + al;
+                sIn[at] = 1.0; sIn[PS0 + at] = 0.0;
+            } else {
+                const int rr = 16 + fdiv<6>(k), cc = 16 + (k - 6 * fdiv<6>(k));
+                const int sel = ((mu == 0 ? cc : rr) - 3 - off) & 3;
+                if (sel != 1 && sel != 2) { sIn[rr * R0C + cc] = 1.0; sIn[PS0 + rr * R0C + cc] = 0.0; }
+            }
         }
         if (fz || ao) {
             const int iL = mul24(wrap_line<FASTW, EXACT>(i0 - 3 + r, L, fastw), L), ipL = mul24(wrap_line<FASTW, EXACT>(i0 - 2 + r, L, fastw), L);
@@ -194,7 +231,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
                 if (has_stash && (unsigned)(r - 3) < (unsigned)(EXACT ? TR : min(TR, L - i0)) &&
                     (unsigned)(c - 3) < (unsigned)(EXACT ? TC : min(TC, L - j0))) {         // the net input of the tile's own frozen sites
                     double* cs_ = uniform_at(A.stash, 18u * (unsigned)A.B * (unsigned)n + bn);
-                    const unsigned fi = (unsigned)stash_frozen_idx(i0 + r - 3, j0 + c - 3, L, mu, off);
+                    const unsigned fi = (unsigned)stash_frozen_idx(gi(r - 3), gj(c - 3), L, mu, off);
                     sts<NTS>(cs_, fi, cs); sts<NTS>(cs_, fi + (unsigned)(n >> 1), sn);
                 }
             }
@@ -233,21 +270,22 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     //     pair index inside a parity class = uu * R1 + v  (u = 2 uu + parity across, v along the lines),
     // 6 whole tiles per class; the last few pairs (v >= R1 - 4 of the last uu: 12.5 tiles in all, a 13th would land
     // on one SIMD as a 4th) run on the VALU, all 18 taps, on the waves that own one tile only.
-    static_assert(R1R == R1C && R1R % 2 == 0, "square window, pairs across either direction");
-    constexpr int R1 = R1C, NU1 = R1 / 2, NPC = (NU1 / 2) * R1;          // pairs per parity class (NU1 even)
-    static_assert(NU1 % 2 == 0, "as many even as odd pair positions");
-    constexpr int NTC = NPC / 16, NREMP = NPC - NTC * 16, NREM1 = 2 * (2 * NREMP) * 8;   // whole tiles per class; leftover outputs
-    static_assert(2 * NTC <= 2 * NW && NREM1 <= NT / 2 && NREMP <= R1, "tile rounds; leftover outputs go to the upper waves");
+    static_assert((AL ? (mu == 0 ? R1R == R1C + 2 : R1C == R1R + 2) : R1R == R1C) && R1R % 2 == 0 && R1C % 2 == 0, "window: pairs across either direction");
+    // Aligned tiles (AL): 9 pair positions u = 0 .. 8 (window lines 0 .. 17; lines 18, 19 are not computed), five even and four odd:
+    // tiles 0 .. 8 as below, tiles 9, 10 take v = 16 .. 19 of the even / odd u < 8, and u = 8 there is the leftover: 11 tiles + 4 pairs.
+    constexpr int R1 = TC + 4, NU1 = AL ? R1 / 2 - 1 : R1 / 2;           // positions along the lines; pair positions across them
+    constexpr int NREMP = 4, NREM1 = (AL ? 1 : 2) * (2 * NREMP) * 8;     // leftover pairs per parity class of the last position(s); outputs
+    static_assert(NREM1 <= NT / 2 && NREMP <= R1, "leftover outputs go to the upper waves");
     // Tile -> pairs: tiles 0 .. NU1 - 1 hold ONE pair position u = tile across the lines and v = lane & 15 along them, so
     // that everything that depends on u -- the window lines, the stripe class, the LDS row / column of the outputs, the
     // stash row and its bounds -- is wave-uniform (scalar instructions) and what depends on the lane is the same for both
     // tiles of a wave; tiles NU1, NU1 + 1 take v = 16 .. 19 of the even / odd u < 8 (four u per tile), and u = 8, 9 there are
     // the leftover pairs below.  (Tiles of 16 consecutive pairs of a (u, v) enumeration cost ~50 VALU instructions of index
     // arithmetic per tile and wave: division by the window width, per-lane parity, per-lane bounds.)
-    static_assert(R1 == 20 && NU1 == 10 && NTC == 6 && NREMP == 4, "conv1 tile map: 16 + 4 positions along the lines, 10 across");
+    static_assert(R1 == 20 && NU1 == (AL ? 9 : 10) && NREMP == 4 && 2 * NU1 == (mu == 0 ? R1C : R1R), "conv1 tile map: 16 + 4 positions along the lines, 10 (aligned: 9) across");
     {
         const int g = lane >> 4, i = lane & 15, cN = i & 7, dd = i >> 3;
-        const int sbase = ((mu == 0 ? j0 : i0) - 3 - off) & 3;           // stripe class of the input window's first line
+        const int sbase = (o4 - 3 - offt) & 3;                           // stripe class of the input window's first line (AL: 0)
         const int lstep = mu == 0 ? 1 : R0C;                             // LDS step across the lines / along them
         const int astep = mu == 0 ? R0C : 1;
         auto conv1_tile = [&](int u, int v, int par) {
@@ -271,21 +309,27 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
             ph[0] = h[0]; ph[PS1] = h[1]; ph[ds] = h[2]; ph[PS1 + ds] = h[3];
             if (FT_RECOMP_D1 ? stash_h : has_stash) {   // act'(z1) (and h1) of the tile's own sites
                 const int r0 = r - 2, c0 = c - 2, r1 = mu == 0 ? r0 : r0 + 1, c1 = mu == 0 ? c0 + 1 : c0;
-                const int at = mul24(i0 + r0, L) + j0 + c0, dat = mu == 0 ? 1 : L;
+                // the pair's two sites lie ACROSS the lines: with aligned origins the lattice edge can fall between them, so each
+                // site's global line is wrapped on its own (out-of-tile members fail the bounds tests below, their index is unused)
+                const int gr0 = gi(r0), gc0 = gj(c0), gr1 = gi(r1), gc1 = gj(c1);
+                const int at = mul24(gr0, L) + gc0, at1 = mul24(gr1, L) + gc1;
                 // act'(z1) of a mu = 0 layer: transposed site index (FT_D1_T): the lanes of a tile run down a column
-                const int atd = (FT_D1_T && mu == 0) ? mul24(j0 + c0, L) + i0 + r0 : at, datd = (FT_D1_T && mu == 0) ? L : dat;
+                const int atd = (FT_D1_T && mu == 0) ? mul24(gc0, L) + gr0 : at, atd1 = (FT_D1_T && mu == 0) ? mul24(gc1, L) + gr1 : at1;
                 if ((unsigned)r0 < (unsigned)rmax && (unsigned)c0 < (unsigned)cmax) {
                     if (!FT_RECOMP_D1) sts2<NTS>(st_d1, 8u * (unsigned)atd + stg, double2_t{d[0], d[1]});
                     if (stash_h) sts2<NTS>(st_h1, 8u * (unsigned)at + stg, double2_t{h[0], h[1]});
                 }
                 if ((unsigned)r1 < (unsigned)rmax && (unsigned)c1 < (unsigned)cmax) {
-                    if (!FT_RECOMP_D1) sts2<NTS>(st_d1, 8u * (unsigned)(atd + datd) + stg, double2_t{d[2], d[3]});
-                    if (stash_h) sts2<NTS>(st_h1, 8u * (unsigned)(at + dat) + stg, double2_t{h[2], h[3]});
+                    if (!FT_RECOMP_D1) sts2<NTS>(st_d1, 8u * (unsigned)atd1 + stg, double2_t{d[2], d[3]});
+                    if (stash_h) sts2<NTS>(st_h1, 8u * (unsigned)at1 + stg, double2_t{h[2], h[3]});
                 }
             }
         };
         static_assert(NW <= NU1 && 2 * NW >= NU1 + 2, "first round: whole-u tiles only; second round: the rest");
         conv1_tile(wave, i, wave & 1);
+        // second round: tile 8 (u = 8) on wave 0, the two v >= 16 tiles on waves 1, 2.  Measured: dealing them to the SIMD that is
+        // short of a conv2 tile (waves 3, 7) changes nothing, and THREE tiles on wave 7 cost +2.7 % of a trajectory -- the stage lasts
+        // as long as its slowest wave (profiles/r07_ab_aligned_tiles.txt)
         const int T = wave + NW;
         if (T < NU1) conv1_tile(T, i, T & 1);
         else if (T < NU1 + 2) conv1_tile(2 * (i >> 2) + (T - NU1), 16 + (i & 3), T - NU1);
@@ -293,7 +337,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     if (NREM1 > 0 && tid >= NT / 2 && tid < NT / 2 + NREM1) {
         // leftover pairs of either class: uu = NU1 / 2 - 1, v = R1 - NREMP ..; thread = (site, output channel), all 18 taps
         const int idx = tid - NT / 2, co = idx & 7, site = idx >> 3, pair = site >> 1, sd = site & 1;
-        const int par = pair >= NREMP, v = R1 - NREMP + (pair - par * NREMP), u = NU1 - 2 + par;
+        const int par = pair >= NREMP, v = R1 - NREMP + (pair - par * NREMP), u = AL ? NU1 - 1 : NU1 - 2 + par;
         const int r = mu == 0 ? v : 2 * u + sd, c = mu == 0 ? 2 * u + sd : v;
         const double* in = sIn + r * R0C + c;
         const double* wp = sP1 + (co >> 1) + 4 * (co & 1) + 8;         // P1[a][ci][line + 1][row], ft_chan(row) = co
@@ -309,8 +353,8 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         if (has_stash) {
             const int rr = r - 2, cc = c - 2;
             if ((unsigned)rr < (unsigned)rmax && (unsigned)cc < (unsigned)cmax) {
-                const int at = mul24(i0 + rr, L) + j0 + cc;
-                if (!FT_RECOMP_D1) sts<NTS>(st_d1, 8u * (unsigned)((FT_D1_T && mu == 0) ? mul24(j0 + cc, L) + i0 + rr : at) + (unsigned)co, d);
+                const int grr = gi(rr), gcc = gj(cc), at = mul24(grr, L) + gcc;
+                if (!FT_RECOMP_D1) sts<NTS>(st_d1, 8u * (unsigned)((FT_D1_T && mu == 0) ? mul24(gcc, L) + grr : at) + (unsigned)co, d);
                 if (stash_h) sts<NTS>(st_h1, 8u * (unsigned)at + (unsigned)co, h);
             }
         }
@@ -330,7 +374,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     constexpr int NLC = R2C - R2C / 4, NLR = R2R - R2R / 4;            // live columns / rows at most
     static_assert(((R2R / 2) * NLC + 15) / 16 == NW && (NLR * (R2C / 2) + 15) / 16 == NW,
                   "one conv2 tile per wave: its epilogue holds a workgroup barrier");
-    const int d0 = ((off + 3) - (mu == 0 ? j0 : i0)) & 3;               // first dead line of the window
+    const int d0 = ((offt + 3) - o4) & 3;                               // first dead line of the window (AL: 0)
     auto conv2_epi = [&](int g, bool ok, int r, int c, int dr, int dc, double (&z)[4]) {
         // sites (r, c) and (r + dr, c + dc) in window coordinates; z[q]: channel 2 g + (q & 1), site q >> 1
         double h[4], d[4];                                  // the bias came in through the accumulator (bias2 below)
@@ -342,9 +386,10 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
             ph[0] = h[0]; ph[PS2] = h[1]; ph[so] = h[2]; ph[PS2 + so] = h[3];
         }
         if (has_stash && ok) {                                // act'(z2) (and h2) of the tile's own sites
-            const int at = mul24(i0 + r - 1, L) + j0 + c - 1;
+            // (the pair lies ALONG the lines, where the origin is a multiple of 16: its second site never wraps)
+            const int at = mul24(gi(r - 1), L) + gj(c - 1);
             // act'(z2): live lines only (FT_D2_C, stash_live_idx); the pair's second site is one line-step along the stripe lines
-            const int a2 = FT_D2_C ? stash_live_idx<EXACT>(i0 + r - 1, j0 + c - 1, L, mu, off) : at;
+            const int a2 = FT_D2_C ? stash_live_idx<EXACT>(gi(r - 1), gj(c - 1), L, mu, off) : at;
             const int da2 = FT_D2_C ? (mu == 0 ? dr * 3 * (L >> 2) + dc : dr * L + dc) : dr * L + dc;
 #pragma unroll
             for (int q = 0; q < 2; ++q)
@@ -361,20 +406,32 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     // live lines l = lane & 15 < NLC across it; the ninth pair line is spread over the two spare lanes of tiles 0 .. 6
     // (l = 2 T + lane - NLC).  The pair line is then wave-uniform for 14 of 16 lanes and the live-line index a per-lane
     // constant, instead of a division of the pair number by the line count per lane and tile.
+    // Aligned tiles (AL): the live lines of the window are the tile's own twelve (window lines 1 2 3, 5 6 7, 9 10 11, 13 14 15): 9 pair
+    // lines x 12 = 108 pairs, enumerated linearly -- pair 16 T + (lane & 15) = 12 pl + l, one division per lane, once -- on SEVEN
+    // tiles.  Wave 7 has none: it only joins the barrier inside the epilogue and goes on to fetch its conv3 weights.
     constexpr int NPL = R2R / 2;                                        // pair lines (rows or columns of pairs)
-    static_assert(NLC == 14 && NLR == 14 && NPL == 9 && NPL - 1 == NW && 2 * (NW - 1) == NLC, "conv2 tile map");
+    constexpr int NL2 = 12, NT2 = AL ? (NPL * NL2 + 15) / 16 : NW;      // aligned: live lines; conv2 tiles
+    static_assert(NLC == 14 && NLR == 14 && NPL == 9 && NPL - 1 == NW && 2 * (NW - 1) == NLC && NT2 <= NW, "conv2 tile map");
     // one tile per wave: this lane's pair (pair line pl, live-line index -> window line wl) once, for the operand address and
     // for the epilogue alike
     int pl, wl;
     bool pok;
-    {
+    if (AL) {
+        const int p_ = 16 * wave + (lane & 15);
+        pok = p_ < NPL * NL2;
+        const int p = pok ? p_ : 0;                                     // padding lanes (and wave 7): any valid address
+        pl = fdiv<NL2>(p);
+        const int l = p - NL2 * pl;
+        wl = 1 + l + fdiv<3>(l);
+    } else {
         const int i = lane & 15;
         const bool own = i < NLC;
         pl = own ? wave : NPL - 1;
         wl = live_line(own ? i : 2 * wave + i - NLC, d0);
         pok = (own || wave < NW - 1) && wl < R2C;
     }
-    if (mu == 0) {
+    if (AL && wave >= NT2) lds_barrier();                               // the barrier of conv2_epi
+    else if (mu == 0) {
         // B[k = (tap = ky4 * 3 + kx, ci)][n = (co, dd)] = W1[co][ci][ky4 - dd][kx]; pairs = rows (2 pr, 2 pr + 1)
         mfma_stage<KConv2Row, 16 * NW, RS1, PS1, false, false, FT_NCH ? FT_NCH : 1>(sH1, sW + LF_P2, wave, lane,
             [&](int) { return 2 * pl * RS1 + min(wl, R2C - 1); },
@@ -418,10 +475,11 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
 #endif
 
     // ---- conv3 (8 -> 3) at the NA active sites; one input channel per wave ------
-    // active site `lane`: mu=0 columns off+4m, mu=1 rows off+4m (tile origin % 4 == 0)
-    const int ar = mu == 0 ? lane / (TC / 4) : off + 4 * (lane / TC);
-    const int ac = mu == 0 ? off + 4 * (lane % (TC / 4)) : lane % TC;
-    const int ai = i0 + ar, aj = j0 + ac;
+    // active site `lane`: mu=0 columns offt+4m, mu=1 rows offt+4m of the tile (offt = off with tile origin % 4 == 0, the constant
+    // TOFF with aligned origins)
+    const int ar = mu == 0 ? lane / (TC / 4) : offt + 4 * (lane / TC);
+    const int ac = mu == 0 ? offt + 4 * (lane % (TC / 4)) : lane % TC;
+    const int ai = gi(ar), aj = gj(ac);
     const bool alane = lane < NA;
     const bool avalid = alane && (EXACT || ((ai < L) && (aj < L)));
     if (alane) {
@@ -501,7 +559,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         lds_barrier();
         if (has_y && tid < N3) {
             const int r = fdiv<TC>(tid), c = tid - r * TC;
-            const int i = i0 + r, j = j0 + c;
+            const int i = gi(r), j = gj(c);
             if (EXACT || (i < L && j < L)) {
                 double v0 = xv0, v1 = xv1;
                 if (ft_stripe(i, j, mu, off) == 0) {
@@ -515,7 +573,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         }
         if (has_pout && tid < N3) {                                    // plaquette-level inverse: x1 at the active sites, fx elsewhere
             const int r = fdiv<TC>(tid), c = tid - r * TC;
-            const int i = i0 + r, j = j0 + c;
+            const int i = gi(r), j = gj(c);
             if (EXACT || (i < L && j < L)) A.pout[(size_t)b * n + mul24(i, L) + j] = ft_stripe(i, j, mu, off) == 0 ? sDL[tid] : xv0;
         }
         return;
@@ -583,7 +641,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         lds_barrier();
         if (has_y && tid < N3) {
             const int r = fdiv<TC>(tid), c = tid - r * TC;
-            const int i = i0 + r, j = j0 + c;
+            const int i = gi(r), j = gj(c);
             if (EXACT || (i < L && j < L)) {
                 double v0 = xv0, v1 = xv1;
                 if (ft_stripe(i, j, mu, off) == 0) {
@@ -597,7 +655,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         }
         if (has_pout && tid < N3) {                                    // plaquette-level map: P' at the active sites, P elsewhere
             const int r = fdiv<TC>(tid), c = tid - r * TC;
-            const int i = i0 + r, j = j0 + c;
+            const int i = gi(r), j = gj(c);
             if (EXACT || (i < L && j < L)) A.pout[(size_t)b * n + mul24(i, L) + j] = ft_stripe(i, j, mu, off) == 0 ? sDL[tid] : xv0;
         }
         STAMP(6);
@@ -636,7 +694,8 @@ template <bool REV> void launch_fwd(const fthmc::FlowLayerArgs& a, dim3 grid, hi
     const bool nt_stash = FT_NT_STASH && a.stash && ((FT_NT_STASH <= 2 && fthmc::flow_stash_doubles(a.B, a.L, a.stash_h != 0) * sizeof(double) >= FT_NT_MIN_BYTES) ||
                                                       (FT_NT_STASH >= 2 && a.stash_far));
     const bool fast = wrap_fast_ok(a.L, TR, TC);
-    const bool exact = fast && a.L % TR == 0 && a.L % TC == 0 && (a.L & (a.L - 1)) == 0;
+    // (a power of two wraps any window line by one v_and: L = 16, a single tile that wraps onto itself, is EXACT too)
+    const bool exact = a.L % TR == 0 && a.L % TC == 0 && (a.L & (a.L - 1)) == 0;
     if (a.mu == 0) {
         if (exact) { if constexpr (REV) FWD_LAUNCH(TR, TC, true, REV, 0, true); else FWD_LAUNCH_SWEEPS(TR, TC, true, REV, 0, true); }
         else if (fast) FWD_LAUNCH(TR, TC, true, REV, 0, false);

@@ -175,9 +175,13 @@ constexpr int ps_round(int n) { return ((n - 18 + 31) / 32) * 32 + 18; }
 #endif
 constexpr int ps_round16(int n) { return ((n - FT_PSMOD + 31) / 32) * 32 + FT_PSMOD; }
 
-template <int TR, int TC> struct Geom {
-    static constexpr int R0R = TR + 6, R0C = TC + 6, N0 = R0R * R0C;   // plaquette / input window
-    static constexpr int R1R = TR + 4, R1C = TC + 4, N1 = R1R * R1C;   // h1 window
+// AL (aligned tile origins, flow_fwd.hip: the active lines sit at tile lines 1, 5, 9, 13 whatever the layer's offset): ACROSS the
+// stripe lines (columns for MU = 0, rows for MU = 1) conv1 is needed on 18 lines and the net input on 20, two fewer than along
+// the lines; the windows keep their origin (tile - 3, tile - 2) and lose their last two lines across.
+template <int TR, int TC, int MU = 0, bool AL = false> struct Geom {
+    static constexpr int XR = (AL && MU == 1) ? 2 : 0, XC = (AL && MU == 0) ? 2 : 0;   // lines not needed across the stripe direction
+    static constexpr int R0R = TR + 6 - XR, R0C = TC + 6 - XC, N0 = R0R * R0C;   // plaquette / input window (AL: 20 across x 22 along)
+    static constexpr int R1R = TR + 4 - XR, R1C = TC + 4 - XC, N1 = R1R * R1C;   // h1 window (AL: 18 across x 20 along)
     // LDS row stride of the h1 planes: odd, so that a column of sites (the conv1 epilogue's stores for mu = 0 run down one:
     // 16 consecutive rows per MFMA tile) spreads over 16 bank pairs; with the window width (20) they collapsed onto 8
     static constexpr int RS1 = R1C + 1;
@@ -187,7 +191,7 @@ template <int TR, int TC> struct Geom {
     static constexpr int PS0 = ps_round16(N0), PS1 = ps_round16(R1R * RS1), PS2 = ps_round(N2);   // net input, h1: MFMA operands
     static_assert(PS0 % 32 == FT_PSMOD && PS1 % 32 == FT_PSMOD && PS2 % 32 == 18, "bank layout");
     static_assert(PS0 >= N0 && PS1 >= R1R * RS1 && PS2 >= N2, "plane size");
-    static_assert(TR % 4 == 0 && TC % 4 == 0 && NA <= 64, "tile shape");
+    static_assert(TR % 4 == 0 && TC % 4 == 0 && NA <= 64 && RS1 % 2 == 1, "tile shape");
 };
 
 
