@@ -9,6 +9,7 @@
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <utility>
 
 using namespace fthmc;
 
@@ -56,6 +57,10 @@ inline int make_ctx(const fthmc_arch_t* arch, void* stream, Ctx* c) {
     return FTHMC_OK;
 }
 
+// The calls whose training backward computes the layer's weight gradients itself (flow_bwd_train.hip) and leaves every layer's
+// partials side by side: ws_layout sizes the rows force_gp then finds
+inline bool fused_train_bwd(const FlowArch& A, int B, int L) { return A.is_default() && flow_bwd_train_shape(L) && flow_stash_fits32(B, L, true); }
+
 WS ws_layout(const FlowArch& A, double* base, int B, int L, int nl, bool train = false) {
     WS w{};
     const size_t n1 = (size_t)B * L * L, n2 = 2 * n1;
@@ -78,8 +83,7 @@ WS ws_layout(const FlowArch& A, double* base, int B, int L, int nl, bool train =
     const size_t nlw = train && A.is_default() && ft_small_shape(L, nl) ? (size_t)nl : 1;
     w.gw_rows = nl > 0 ? nlw * B * nt : 0;
     w.gw_tmp_rows = nl > 0 ? nlw * FLOW_REDUCE_GROUPS : 0;
-    if (train && nl > 0 && A.is_default() && flow_bwd_train_shape(L) && flow_stash_fits32(B, L, true)) {   // the shapes force_gp takes the fused path on
-        // the fused training backward (flow_bwd_train.hip) leaves every layer's partials side by side: ONE reduction behind the sweep
+    if (train && nl > 0 && fused_train_bwd(A, B, L)) {                    // ONE reduction behind the sweep
         const size_t np = (size_t)flow_bwd_train_nparts(B, L), ng = (size_t)flow_reduce_groups((int)np);
         if (w.gw_rows < (size_t)nl * np) w.gw_rows = (size_t)nl * np;
         if (w.gw_tmp_rows < (size_t)nl * ng) w.gw_tmp_rows = (size_t)nl * ng;
@@ -159,14 +163,18 @@ inline int use_weights(Ctx& C, const double* w, int nl, const WS& W, hipStream_t
     C.wcan = w;
     return C.A.is_default() ? launch_pack_weights(w, nl, W.wint, s, weights_token(w, wver)) : FTHMC_OK;
 }
-inline GenLayerArgs gen_args(const Ctx& C, const WS& w, int l, int B, int L, int act, bool own_region) {
-    GenLayerArgs g{};
+// layer l of a sweep on the plain kernels (T: double, or Dual in the second-order sweeps): weights, scratch and stripe
+template <typename T>
+GenLayerArgsT<T> gen_layer(const Ctx& C, int l, int B, int L, int act, T* stash, T* hbuf, T* gbuf) {
+    GenLayerArgsT<T> g{};
     g.arch = C.A;
     g.w = C.wcan + (size_t)l * C.A.params();
-    g.stash = w.stash + (own_region ? (size_t)l * C.A.stash_doubles(B, L) : 0);
-    g.hbuf = w.hbuf; g.gbuf = w.gbuf;
-    g.B = B; g.L = L; g.mu = l % 2; g.off = (l / 2) % 4; g.act = act;
+    g.stash = stash; g.hbuf = hbuf; g.gbuf = gbuf;
+    g.B = B; g.L = L; g.mu = layer_mu(l); g.off = layer_off(l); g.act = act;
     return g;
+}
+inline GenLayerArgs gen_args(const Ctx& C, const WS& w, int l, int B, int L, int act, bool own_region) {
+    return gen_layer<double>(C, l, B, L, act, w.stash + (own_region ? (size_t)l * C.A.stash_doubles(B, L) : 0), w.hbuf, w.gbuf);
 }
 
 // small lattices: the fused single-launch path (flow_small.hip)
@@ -178,11 +186,46 @@ inline SmallArgs small_args(const double* x, const WS& w, int nl, int B, int act
 
 #define FT_TRY(expr) do { int rc_ = (expr); if (rc_ != FTHMC_OK) return rc_; } while (0)
 
-// 1 (default): the training backward of the tiled-exactly shapes computes its weight gradients itself (flow_bwd_train.hip);
-// 0: k_flow_bwd_gather writes the pre-activation gradients and k_flow_wgrad reads them back (rounds 2-5; A/B builds: EXTRA=-DFT_FUSED_WGRAD=0)
-#ifndef FT_FUSED_WGRAD
-#define FT_FUSED_WGRAD 1
-#endif
+// Argument checks of the entry points, in the precedence every one of them keeps: FTHMC_ERR_ARG, then FTHMC_ERR_UNSUPPORTED
+// (then the workspace: FT_WS).  ptrs_ok: the call's own pointers and counts.
+inline int check_layer_call(bool ptrs_ok, int B, int L, int mu, int off, int act) {            // one layer (mu, off)
+    if (!ptrs_ok || bad_shape(B, L) || mu < 0 || mu > 1 || off < 0 || off > 3) return FTHMC_ERR_ARG;
+    return act < 0 || act > 2 ? FTHMC_ERR_UNSUPPORTED : FTHMC_OK;
+}
+inline int check_flow_call(bool ptrs_ok, const double* w, int nl, int B, int L, int act) {     // a whole flow of nl layers
+    if (!ptrs_ok || (nl > 0 && !w) || bad_shape(B, L) || nl < 0) return FTHMC_ERR_ARG;
+    return act < 0 || act > 2 ? FTHMC_ERR_UNSUPPORTED : FTHMC_OK;
+}
+
+// One layer forward (rev: inverse) and the sum of its log J partials: logJ[b] = (accumulate ? logJ[b] : 0) + sum over the tiles
+// (logJ null: no sum).  `a` carries the fields, weights and stripe; l: the layer's place in the caller's weights.
+int layer_forward(const Ctx& C, const WS& W, int l, FlowLayerArgs a, bool rev, double* logJ, int accumulate = 0) {
+    if (C.gen()) {                                // any other net shape (flow_generic.hip)
+        GenLayerArgs g = gen_args(C, W, l, a.B, a.L, a.act, false);
+        g.mu = a.mu; g.off = a.off; g.x = a.pin ? nullptr : a.x; g.pin = a.pin; g.y = a.y; g.pout = a.pout; g.tol = a.tol;
+        g.logj = logJ; g.logj_accumulate = accumulate;
+        if (a.stash) g.stash = a.stash;
+        return launch_gen_fwd(g, rev, C.s);
+    }
+    a.logj_part = W.lj_part;
+    FT_TRY(rev ? flow_rev(C, a, C.s) : flow_fwd(C, a, C.s));
+    if (logJ) FT_TRY(launch_sum_parts(W.lj_part, a.B, flow_fwd_geom(C.mfma).ntiles(a.L), 1.0, accumulate, logJ, C.s));
+    return FTHMC_OK;
+}
+
+// One layer backward from its stash (a.stash; a.gp_out = the plaquette gradient behind the layer); gw != null: also the layer's
+// weight gradient, from the pre-activation gradients the backward kernel leaves in W.gz (two kernels and the reduction)
+int layer_backward_stash(const WS& W, FlowLayerArgs a, double* gw, hipStream_t s) {
+    a.gw_part = W.gw_part;
+    a.gz = gw ? W.gz : nullptr;
+    FT_TRY(launch_flow_bwd_gather(a, s));
+    if (gw) {
+        a.tpw = flow_wgrad_tpw(a.B, a.L, 1);
+        FT_TRY(launch_flow_wgrad(a, s));
+        FT_TRY(launch_reduce_gw(W.gw_part, flow_wgrad_nparts(a.B, a.L, a.tpw), 1.0, 0, gw, W.gw_tmp, s));
+    }
+    return FTHMC_OK;
+}
 
 // Forward sweep x -> X[0..nl-1] (X[l] = output of layer l).  logdet (device [B]) optional.
 // parts_only: leave the log J partials of every layer in w.lj_part ([layer][chain][tile]) and skip the summing launch (the
@@ -200,18 +243,16 @@ int sweep_forward(const Ctx& C, const double* x, const WS& w, int nl, int B, int
         return FTHMC_OK;
     }
     for (int l = 0; l < nl; ++l) {
-        FlowLayerArgs a{};
+        FlowLayerArgs a(w.wint, l, B, L, act);
         a.stash = stash ? w.stash + (size_t)l * flow_stash_doubles(B, L, train) : nullptr;
         a.stash_h = train ? 1 : 0;
-        // the layers behind this one write their stash before the backward reads this one's: beyond FT_STASH_FAR_BYTES of it the
+        // the layers behind this one write their stash before the backward reads this one's: beyond STASH_FAR_BYTES of it the
         // 256 MB Infinity Cache will have let go of this layer's (the forward then stores it past the caches: flow_fwd.hip)
-        a.stash_far = stash && (size_t)(nl - 1 - l) * flow_stash_doubles(B, L, train) * sizeof(double) >= FT_STASH_FAR_BYTES ? 1 : 0;
+        a.stash_far = stash && (size_t)(nl - 1 - l) * flow_stash_doubles(B, L, train) * sizeof(double) >= STASH_FAR_BYTES ? 1 : 0;
         a.x = l == 0 ? x : w.X + (size_t)(l - 1) * w.n2;
-        a.wint = w.wint + (size_t)l * FLOW_WINT;
         a.y = w.X + (size_t)l * w.n2;
         // logJ partials of all layers side by side, summed by ONE launch behind the sweep (layer by layer, in order)
         a.logj_part = (logdet || parts_only) ? w.lj_part + (size_t)l * B * flow_fwd_geom(C.mfma).ntiles(L) : nullptr;
-        a.B = B; a.L = L; a.mu = l % 2; a.off = (l / 2) % 4; a.act = act;
         FT_TRY(flow_fwd(C, a, s));
     }
     if (logdet && nl > 0) FT_TRY(launch_sum_parts(w.lj_part, B, flow_fwd_geom(C.mfma).ntiles(L), 1.0, 0, logdet, s, nl));
@@ -247,7 +288,7 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
             g.up_gp = gcur; g.glogj_const = glogj; g.gp_out = galt;
             g.gw = gw ? gw + (size_t)l * C.A.params() : nullptr;
             FT_TRY(launch_gen_bwd(g, s));
-            double* t_ = gcur; gcur = galt; galt = t_;
+            std::swap(gcur, galt);
         }
         return FTHMC_OK;
     }
@@ -262,55 +303,39 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
     double* gcur = (stash && (nl & 1)) ? w.gp2 : w.gp;
     double* galt = gcur == w.gp ? w.gp2 : w.gp;
     FT_TRY(launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gcur, s));
-#if FT_FUSED_WGRAD
-    const bool fused = gw && train && flow_bwd_train_built() && flow_bwd_train_shape(L) && flow_stash_fits32(B, L, true);
+    // training on the tiled-exactly shapes: the layer's backward and its weight gradients in ONE kernel (flow_bwd_train.hip: the
+    // pre-activation gradients never leave LDS), one partial per workgroup
+    const bool fused = gw && train && fused_train_bwd(C.A, B, L);
     const int npf = fused ? (int)flow_bwd_train_nparts(B, L) : 0;
     // the layers' partials side by side and ONE reduction behind the sweep (two launches instead of two per layer), where the
     // workspace has the rows (a training layout: ws_layout)
     const bool one_reduction = fused && (size_t)nl * npf <= w.gw_rows && (size_t)nl * flow_reduce_groups(npf) <= w.gw_tmp_rows;
-#endif
     for (int l = nl - 1; l >= 0; --l) {
-        FlowLayerArgs a{};
+        FlowLayerArgs a(w.wint, l, B, L, act);
         a.x = l == 0 ? x : w.X + (size_t)(l - 1) * w.n2;
-        a.wint = w.wint + (size_t)l * FLOW_WINT;
         a.up_gp = gcur;
         a.glogj_const = glogj;
         a.gp_part = w.gp_part;
         a.gw_part = w.gw_part;
-        a.B = B; a.L = L; a.mu = l % 2; a.off = (l / 2) % 4; a.act = act;
-        if (stash) {
-            a.stash = w.stash + (size_t)l * flow_stash_doubles(B, L, train);
-            a.gp_out = galt;
-#if FT_FUSED_WGRAD
-            if (fused) {
-                // training: the layer's backward and its weight gradients in ONE kernel (flow_bwd_train.hip: the pre-activation
-                // gradients never leave LDS), one partial per workgroup
-                if (one_reduction) a.gw_part = w.gw_part + (size_t)l * npf * FLOW_GW_STRIDE;
-                FT_TRY(launch_flow_bwd_train(a, s));
-                if (!one_reduction) FT_TRY(launch_reduce_gw(w.gw_part, npf, 1.0, 0, gw + (size_t)l * FTHMC_W_PER_LAYER, w.gw_tmp, s));
-                double* t_ = gcur; gcur = galt; galt = t_;
-                continue;
-            }
-#endif
-            a.gz = train ? w.gz : nullptr;
-            FT_TRY(launch_flow_bwd_gather(a, s));
-            if (gw) {                                                 // weight gradients from the pre-activation gradients
-                a.tpw = flow_wgrad_tpw(B, L, 1);
-                FT_TRY(launch_flow_wgrad(a, s));
-                FT_TRY(launch_reduce_gw(w.gw_part, flow_wgrad_nparts(B, L, a.tpw), 1.0, 0,
-                                        gw + (size_t)l * FTHMC_W_PER_LAYER, w.gw_tmp, s));
-            }
-            double* t_ = gcur; gcur = galt; galt = t_;
+        double* gwl = gw ? gw + (size_t)l * FTHMC_W_PER_LAYER : nullptr;
+        if (!stash) {                                                 // VALU variant: scatter form + gather
+            FT_TRY(launch_flow_bwd(a, gw != nullptr, s));
+            if (gw) FT_TRY(launch_reduce_gw(w.gw_part, B * flow_geom(false).ntiles(L), 1.0, 0, gwl, w.gw_tmp, s));
+            FT_TRY(launch_gather_gp(w.gp_part, B, L, flow_geom(false), 1, gcur, s));
             continue;
         }
-        FT_TRY(launch_flow_bwd(a, gw != nullptr, s));                // VALU variant: scatter form + gather
-        if (gw) FT_TRY(launch_reduce_gw(w.gw_part, B * flow_geom(false).ntiles(L), 1.0, 0,
-                                        gw + (size_t)l * FTHMC_W_PER_LAYER, w.gw_tmp, s));
-        FT_TRY(launch_gather_gp(w.gp_part, B, L, flow_geom(false), 1, gcur, s));
+        a.stash = w.stash + (size_t)l * flow_stash_doubles(B, L, train);
+        a.gp_out = galt;
+        if (fused) {
+            if (one_reduction) a.gw_part = w.gw_part + (size_t)l * npf * FLOW_GW_STRIDE;
+            FT_TRY(launch_flow_bwd_train(a, s));
+            if (!one_reduction) FT_TRY(launch_reduce_gw(w.gw_part, npf, 1.0, 0, gwl, w.gw_tmp, s));
+        } else {
+            FT_TRY(layer_backward_stash(w, a, gwl, s));
+        }
+        std::swap(gcur, galt);
     }
-#if FT_FUSED_WGRAD
     if (one_reduction && nl > 0) FT_TRY(launch_reduce_gw(w.gw_part, npf, 1.0, 0, gw, w.gw_tmp, s, nl, (size_t)npf * FLOW_GW_STRIDE));
-#endif
     return FTHMC_OK;
 }
 
@@ -340,6 +365,45 @@ int leapfrog_ws(const double* x, const double* p, const WS& w, int B, int L, dou
     // final half drift into the free x buffer
     FT_TRY(launch_axpy(xi, pi, 0.5 * dt, xs[cur], w.n2, s));
     *xo = xs[cur]; *po = const_cast<double*>(pi);
+    return FTHMC_OK;
+}
+
+// Event timing of `reps` calls of launch() behind two untimed warm-up calls: *ms_avg = milliseconds per call.  The events are
+// created here, after the caller's last early return, and destroyed on every path.
+template <class Launch> int time_launches(int reps, hipStream_t s, double* ms_avg, Launch launch) {
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return FTHMC_ERR_LAUNCH; }
+    int rc = FTHMC_OK;
+    for (int it = -2; it < reps && rc == FTHMC_OK; ++it) {
+        if (it == 0) (void)hipEventRecord(e0, s);
+        rc = launch();
+    }
+    (void)hipEventRecord(e1, s);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    *ms_avg = (double)ms / reps;
+    return rc;
+}
+
+// Cycle stamps of a profiled launch, read back and averaged: dbg = nrec records of nslot stamps on the device;
+// out[k] = sum over the records of (stamp k - stamp ref(k)) / denom, where both were written (ref(k) < 0: stamp k itself), k >= k0
+template <class Ref> int mean_stamps(const long long* dbg, size_t nrec, int nslot, int k0, size_t denom, hipStream_t s, double* out, Ref ref) {
+    const size_t bytes = nrec * nslot * sizeof(long long);
+    long long* h = (long long*)malloc(bytes);
+    if (!h) return FTHMC_ERR_ARG;
+    if (hipMemcpyAsync(h, dbg, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) { free(h); return FTHMC_ERR_LAUNCH; }
+    for (int k = 0; k < nslot; ++k) out[k] = 0.0;
+    for (size_t r = 0; r < nrec; ++r)
+        for (int k = k0; k < nslot; ++k) {
+            const int q = ref(k);
+            const long long t = h[r * nslot + k], t0 = q < 0 ? 0 : h[r * nslot + q];
+            if (t && (q < 0 || t0)) out[k] += (double)(t - t0) / denom;
+        }
+    free(h);
     return FTHMC_OK;
 }
 
@@ -409,9 +473,9 @@ size_t fthmc_train_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers
     (void)hipGetLastError();   /* drop stale (non-sticky) errors left by the host framework */ \
     Ctx C; { const int rc_ = make_ctx((arch_), stream, &C); if (rc_ != FTHMC_OK) return rc_; } \
     hipStream_t s = C.s; (void)s
-#define FT_WS(nl)                                                                   \
-    if (!ws || ws_bytes < ws_doubles(C.A, B, L, (nl)) * sizeof(double)) return FTHMC_ERR_WS; \
-    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, (nl))
+#define FT_WS(nl, train)                                                            \
+    if (!ws || ws_bytes < ws_doubles(C.A, B, L, (nl), (train)) * sizeof(double)) return FTHMC_ERR_WS; \
+    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, (nl), (train))
 
 int fthmc_wrap(const double* x, double* out, size_t n, void* stream) {
     if (!x || !out) return FTHMC_ERR_ARG;
@@ -476,7 +540,7 @@ int fthmc_train_metrics(const double* xi, const double* x, const double* logq, c
                         double beta, double dkl_factor, double* row, void* ws, size_t ws_bytes, void* stream) {
     if (!xi || !x || !logq || !logp || !row || bad_shape(B, L) || !(beta != 0.0)) return FTHMC_ERR_ARG;
     FT_CTX(nullptr);
-    FT_WS(0);
+    FT_WS(0, false);
     double* q = W.scal + (size_t)SC_Q * B; double* qi = W.scal + (size_t)SC_OLD0 * B;
     FT_TRY(launch_action_charge(x, B, L, beta, nullptr, q, nullptr, s, W.act_part));
     FT_TRY(launch_action_charge(xi, B, L, beta, nullptr, qi, nullptr, s, W.act_part));
@@ -494,7 +558,7 @@ int fthmc_leapfrog(const double* x, const double* p, int B, int L, double beta, 
                    double* x_out, double* p_out, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !p || !x_out || !p_out || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
     FT_CTX(nullptr);
-    FT_WS(0);
+    FT_WS(0, false);
     double *xo, *po;
     FT_TRY(leapfrog_ws(x, p, W, B, L, beta, dt, nstep, &xo, &po, s));
     if (hipMemcpyAsync(x_out, xo, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
@@ -511,7 +575,7 @@ int fthmc_hmc_trajectory(const double* x, const double* v, const double* u, int 
     // L <= 64 (x_new must not alias x): one persistent launch per trajectory, state in LDS / registers
     if (L <= 64 && C.mfma && x_new != x)
         return launch_hmc_trajectory_fused(x, v, u, B, L, beta, dt, nstep, x_new, dH, acc, H0, H1, s);
-    FT_WS(0);
+    FT_WS(0, false);
     double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
     double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
     double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
@@ -529,64 +593,37 @@ int fthmc_hmc_trajectory(const double* x, const double* v, const double* u, int 
 
 int fthmc_flow_layer_fwd(const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
                          double* y, double* logJ, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !w || !y || bad_shape(B, L) || mu < 0 || mu > 1 || off < 0 || off > 3) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_layer_call(x && w && y, B, L, mu, off, act));
     FT_CTX(arch);
-    FT_WS(1);
+    FT_WS(1, false);
     FT_TRY(use_weights(C, w, 1, W, s));
-    if (C.gen()) {
-        GenLayerArgs g = gen_args(C, W, 0, B, L, act, false);
-        g.mu = mu; g.off = off; g.x = x; g.y = y; g.logj = logJ;
-        return launch_gen_fwd(g, false, s);
-    }
-    FlowLayerArgs a{};
-    a.x = x; a.wint = W.wint; a.y = y; a.logj_part = W.lj_part;
-    a.B = B; a.L = L; a.mu = mu; a.off = off; a.act = act;
-    FT_TRY(flow_fwd(C, a, s));
-    if (logJ) FT_TRY(launch_sum_parts(W.lj_part, B, flow_fwd_geom(C.mfma).ntiles(L), 1.0, 0, logJ, s));
-    return FTHMC_OK;
+    FlowLayerArgs a(W.wint, B, L, mu, off, act);
+    a.x = x; a.y = y;
+    return layer_forward(C, W, 0, a, false, logJ);
 }
 
 int fthmc_flow_layer_rev(const double* y, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
                          double tol, double* x, double* logJ, void* ws, size_t ws_bytes, void* stream) {
-    if (!y || !w || !x || bad_shape(B, L) || mu < 0 || mu > 1 || off < 0 || off > 3) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_layer_call(y && w && x, B, L, mu, off, act));
     FT_CTX(arch);
-    FT_WS(1);
+    FT_WS(1, false);
     FT_TRY(use_weights(C, w, 1, W, s));
-    if (C.gen()) {
-        GenLayerArgs g = gen_args(C, W, 0, B, L, act, false);
-        g.mu = mu; g.off = off; g.x = y; g.y = x; g.logj = logJ; g.tol = tol;
-        return launch_gen_fwd(g, true, s);
-    }
-    FlowLayerArgs a{};
-    a.x = y; a.wint = W.wint; a.y = x; a.logj_part = W.lj_part; a.tol = tol;
-    a.B = B; a.L = L; a.mu = mu; a.off = off; a.act = act;
-    FT_TRY(flow_rev(C, a, s));
-    if (logJ) FT_TRY(launch_sum_parts(W.lj_part, B, flow_geom(false).ntiles(L), 1.0, 0, logJ, s));
-    return FTHMC_OK;
+    FlowLayerArgs a(W.wint, B, L, mu, off, act);
+    a.x = y; a.y = x; a.tol = tol;
+    return layer_forward(C, W, 0, a, true, logJ);
 }
 
 // plaquette-level map: the coupling kernel with the plaquette field as input and output (MFMA kernels only)
 static int plaq_coupling(const double* P, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act, double tol,
                          bool rev, double* out, double* logJ, void* ws, size_t ws_bytes, void* stream) {
-    if (!P || !w || !out || bad_shape(B, L) || mu < 0 || mu > 1 || off < 0 || off > 3) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_layer_call(P && w && out, B, L, mu, off, act));
     FT_CTX(arch);
     if (!C.mfma && C.A.is_default()) return FTHMC_ERR_UNSUPPORTED;
-    FT_WS(1);
+    FT_WS(1, false);
     FT_TRY(use_weights(C, w, 1, W, s));
-    if (C.gen()) {
-        GenLayerArgs g = gen_args(C, W, 0, B, L, act, false);
-        g.mu = mu; g.off = off; g.pin = P; g.pout = out; g.logj = logJ; g.tol = tol;
-        return launch_gen_fwd(g, rev, s);
-    }
-    FlowLayerArgs a{};
-    a.x = P; a.pin = P; a.pout = out; a.wint = W.wint; a.logj_part = W.lj_part; a.tol = tol;
-    a.B = B; a.L = L; a.mu = mu; a.off = off; a.act = act;
-    FT_TRY(rev ? launch_flow_rev_mfma(a, s) : launch_flow_fwd_mfma(a, s));
-    if (logJ) FT_TRY(launch_sum_parts(W.lj_part, B, flow_fwd_geom(true).ntiles(L), 1.0, 0, logJ, s));
-    return FTHMC_OK;
+    FlowLayerArgs a(W.wint, B, L, mu, off, act);
+    a.x = P; a.pin = P; a.pout = out; a.tol = tol;
+    return layer_forward(C, W, 0, a, rev, logJ);
 }
 
 int fthmc_plaq_coupling_fwd(const double* P, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
@@ -606,12 +643,10 @@ int fthmc_plaq_coupling_rev(const double* fP, const double* w, const fthmc_arch_
 // (launch_plane_from), the forward runs on the plaquette field itself (FlowLayerArgs::pin), gP = W.gp + gfP.
 int fthmc_plaq_coupling_bwd(const double* P, const double* w, const fthmc_arch_t* arch, const double* gfP, const double* glogJ,
                             int B, int L, int mu, int off, int act, double* gP, double* gw, void* ws, size_t ws_bytes, void* stream) {
-    if (!P || !w || !gfP || !glogJ || !gP || bad_shape(B, L) || mu < 0 || mu > 1 || off < 0 || off > 3) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_layer_call(P && w && gfP && glogJ && gP, B, L, mu, off, act));
     FT_CTX(arch);
     if (!C.mfma && C.A.is_default()) return FTHMC_ERR_UNSUPPORTED;          // as fthmc_plaq_coupling_fwd: MFMA kernels (or the plain ones)
-    if (!ws || ws_bytes < ws_doubles(C.A, B, L, 1, gw != nullptr) * sizeof(double)) return FTHMC_ERR_WS;
-    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, 1, gw != nullptr);
+    FT_WS(1, gw != nullptr);
     FT_TRY(use_weights(C, w, 1, W, s));
     double* fake = W.xa;                                                     // [B][2][L][L]: only plane mu is read
     FT_TRY(launch_plane_from(gfP, B, L, mu, mu == 0 ? 1.0 : -1.0, fake, s));
@@ -624,19 +659,12 @@ int fthmc_plaq_coupling_bwd(const double* P, const double* w, const fthmc_arch_t
         FT_TRY(launch_gen_bwd(g, s));
         return launch_axpy(W.gp, gfP, 1.0, gP, n1, s);
     }
-    FlowLayerArgs a{};
-    a.x = P; a.pin = P; a.wint = W.wint; a.up_link = fake; a.glogj = glogJ;
+    FlowLayerArgs a(W.wint, B, L, mu, off, act);
+    a.x = P; a.pin = P; a.up_link = fake; a.glogj = glogJ;
     a.gw_part = W.gw_part; a.stash = W.stash; a.stash_h = gw ? 1 : 0;
-    a.B = B; a.L = L; a.mu = mu; a.off = off; a.act = act;
     FT_TRY(launch_flow_fwd_mfma(a, s));                                      // fills the stash (no output field, no log J)
     a.gp_out = W.gp;
-    a.gz = gw ? W.gz : nullptr;
-    FT_TRY(launch_flow_bwd_gather(a, s));
-    if (gw) {
-        a.tpw = flow_wgrad_tpw(B, L, 1);
-        FT_TRY(launch_flow_wgrad(a, s));
-        FT_TRY(launch_reduce_gw(W.gw_part, flow_wgrad_nparts(B, L, a.tpw), 1.0, 0, gw, W.gw_tmp, s));
-    }
+    FT_TRY(layer_backward_stash(W, a, gw, s));
     return launch_axpy(W.gp, gfP, 1.0, gP, n1, s);
 }
 
@@ -644,14 +672,11 @@ int fthmc_plaq_coupling_bwd(const double* P, const double* w, const fthmc_arch_t
 // else the layer is run forward first from `x`.
 static int layer_bwd_impl(const double* x, const double* stash, const double* w, const fthmc_arch_t* arch, const double* gy, const double* glogJ,
                           int B, int L, int mu, int off, int act, double* gx, double* gw, void* ws, size_t ws_bytes, void* stream) {
-    if ((!x && !stash) || !w || !gy || !glogJ || !gx || bad_shape(B, L) || mu < 0 || mu > 1 || off < 0 || off > 3)
-        return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_layer_call((x || stash) && w && gy && glogJ && gx, B, L, mu, off, act));
     FT_CTX(arch);
     const bool mfma = C.mfma;
     if (stash && !mfma && C.A.is_default()) return FTHMC_ERR_UNSUPPORTED;      // the VALU variant has no stash
-    if (!ws || ws_bytes < ws_doubles(C.A, B, L, 1, gw != nullptr && mfma) * sizeof(double)) return FTHMC_ERR_WS;
-    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, 1, gw != nullptr && mfma);
+    FT_WS(1, gw != nullptr && mfma);
     FT_TRY(use_weights(C, w, 1, W, s));
     if (C.gen()) {
         // the adjoint seeded by the link gradient; W.gp holds the layer's plaquette gradient alone
@@ -663,10 +688,9 @@ static int layer_bwd_impl(const double* x, const double* stash, const double* w,
         FT_TRY(launch_gen_bwd(g, s));
         return launch_adj_add(W.gp, gy, B, L, gx, s);
     }
-    FlowLayerArgs a{};
-    a.x = x; a.wint = W.wint; a.up_link = gy; a.glogj = glogJ;
+    FlowLayerArgs a(W.wint, B, L, mu, off, act);
+    a.x = x; a.up_link = gy; a.glogj = glogJ;
     a.gp_part = W.gp_part; a.gw_part = W.gw_part;
-    a.B = B; a.L = L; a.mu = mu; a.off = off; a.act = act;
     if (mfma) {
         // the gather-form backward seeded by the link gradient; gP_out holds the layer's plaquette gradient alone (no
         // upstream gP field).  Without a caller's stash: forward once with the stash (no link update, no log J).
@@ -676,13 +700,7 @@ static int layer_bwd_impl(const double* x, const double* stash, const double* w,
             FT_TRY(launch_flow_fwd_mfma(a, s));
         }
         a.gp_out = W.gp;
-        a.gz = gw ? W.gz : nullptr;
-        FT_TRY(launch_flow_bwd_gather(a, s));
-        if (gw) {
-            a.tpw = flow_wgrad_tpw(B, L, 1);
-            FT_TRY(launch_flow_wgrad(a, s));
-            FT_TRY(launch_reduce_gw(W.gw_part, flow_wgrad_nparts(B, L, a.tpw), 1.0, 0, gw, W.gw_tmp, s));
-        }
+        FT_TRY(layer_backward_stash(W, a, gw, s));
         return launch_adj_add(W.gp, gy, B, L, gx, s);
     }
     FT_TRY(launch_flow_bwd(a, gw != nullptr, s));
@@ -707,22 +725,14 @@ size_t fthmc_layer_stash_bytes(const fthmc_arch_t* arch, int B, int L) {
 
 int fthmc_flow_layer_fwd_stash(const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act, double* y,
                                double* logJ, double* stash, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !w || !y || !stash || bad_shape(B, L) || mu < 0 || mu > 1 || off < 0 || off > 3) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2 || fthmc_layer_stash_bytes(arch, B, L) == 0) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_layer_call(x && w && y && stash, B, L, mu, off, act));
+    if (fthmc_layer_stash_bytes(arch, B, L) == 0) return FTHMC_ERR_UNSUPPORTED;        // the VALU variant has no stash
     FT_CTX(arch);
-    FT_WS(1);
+    FT_WS(1, false);
     FT_TRY(use_weights(C, w, 1, W, s));
-    if (C.gen()) {
-        GenLayerArgs g = gen_args(C, W, 0, B, L, act, false);
-        g.mu = mu; g.off = off; g.x = x; g.y = y; g.logj = logJ; g.stash = stash;
-        return launch_gen_fwd(g, false, s);
-    }
-    FlowLayerArgs a{};
-    a.x = x; a.wint = W.wint; a.y = y; a.logj_part = W.lj_part; a.stash = stash; a.stash_h = 1;
-    a.B = B; a.L = L; a.mu = mu; a.off = off; a.act = act;
-    FT_TRY(launch_flow_fwd_mfma(a, s));
-    if (logJ) FT_TRY(launch_sum_parts(W.lj_part, B, flow_fwd_geom(true).ntiles(L), 1.0, 0, logJ, s));
-    return FTHMC_OK;
+    FlowLayerArgs a(W.wint, B, L, mu, off, act);
+    a.x = x; a.y = y; a.stash = stash; a.stash_h = 1;
+    return layer_forward(C, W, 0, a, false, logJ);
 }
 
 int fthmc_flow_layer_bwd_stash(const double* stash, const double* w, const fthmc_arch_t* arch, const double* gy, const double* glogJ, int B, int L,
@@ -733,10 +743,9 @@ int fthmc_flow_layer_bwd_stash(const double* stash, const double* w, const fthmc
 
 int fthmc_flow_forward_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
                        double* y, double* logdet, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    if (!x || (n_layers > 0 && !w) || bad_shape(B, L) || n_layers < 0) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_flow_call(x != nullptr, w, n_layers, B, L, act));
     FT_CTX(arch);
-    FT_WS(n_layers);
+    FT_WS(n_layers, false);
     FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
     double* ld = logdet ? logdet : W.scal + (size_t)SC_LOGDET * B;
     if (n_layers == 0 && hipMemsetAsync(ld, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
@@ -758,10 +767,9 @@ int fthmc_flow_forward(const double* x, const double* w, const fthmc_arch_t* arc
 
 int fthmc_flow_reverse_v(const double* y, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double tol,
                        double* x, double* logdet, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    if (!y || !x || (n_layers > 0 && !w) || bad_shape(B, L) || n_layers < 0) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_flow_call(y && x, w, n_layers, B, L, act));
     FT_CTX(arch);
-    FT_WS(n_layers);
+    FT_WS(n_layers, false);
     FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
     double* ld = logdet ? logdet : W.scal + (size_t)SC_LOGDET * B;
     if (hipMemsetAsync(ld, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
@@ -770,23 +778,10 @@ int fthmc_flow_reverse_v(const double* y, const double* w, const fthmc_arch_t* a
     // links the layer never writes plus the workgroup's own active links, which it loads before it stores them; the
     // active / passive plaquettes of the halo, which a neighbour's update can tear, are never read.
     const double* src = y;
-    if (C.gen()) {
-        for (int l = n_layers - 1; l >= 0; --l) {
-            GenLayerArgs g = gen_args(C, W, l, B, L, act, false);
-            g.x = src; g.y = x; g.logj = ld; g.logj_accumulate = 1; g.tol = tol;
-            FT_TRY(launch_gen_fwd(g, true, s));
-            src = x;
-        }
-        if (n_layers == 0 && x != y && hipMemcpyAsync(x, y, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return FTHMC_ERR_LAUNCH;
-        return FTHMC_OK;
-    }
     for (int l = n_layers - 1; l >= 0; --l) {
-        FlowLayerArgs a{};
-        a.x = src; a.wint = W.wint + (size_t)l * FLOW_WINT; a.y = x; a.logj_part = W.lj_part; a.tol = tol;
-        a.B = B; a.L = L; a.mu = l % 2; a.off = (l / 2) % 4; a.act = act;
-        FT_TRY(flow_rev(C, a, s));
-        FT_TRY(launch_sum_parts(W.lj_part, B, flow_geom(false).ntiles(L), 1.0, 1, ld, s));
+        FlowLayerArgs a(W.wint, l, B, L, act);
+        a.x = src; a.y = x; a.tol = tol;
+        FT_TRY(layer_forward(C, W, l, a, true, ld, 1));
         src = x;
     }
     if (n_layers == 0 && x != y && hipMemcpyAsync(x, y, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
@@ -802,10 +797,9 @@ int fthmc_flow_reverse(const double* y, const double* w, const fthmc_arch_t* arc
 int fthmc_ft_action_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
                     double* S_eff, double* logdet, double* plaq, double* Q, void* ws, size_t ws_bytes,
                     void* stream, uint64_t weights_version) {
-    if (!x || (n_layers > 0 && !w) || bad_shape(B, L) || n_layers < 0) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_flow_call(x != nullptr, w, n_layers, B, L, act));
     FT_CTX(arch);
-    FT_WS(n_layers);
+    FT_WS(n_layers, false);
     FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
     if (n_layers == 0 && logdet && hipMemsetAsync(logdet, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     if (C.small(L, n_layers)) {
@@ -824,10 +818,9 @@ int fthmc_ft_action(const double* x, const double* w, const fthmc_arch_t* arch, 
 
 int fthmc_ft_force_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
                    double* F, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    if (!x || !F || (n_layers > 0 && !w) || bad_shape(B, L) || n_layers < 0) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_flow_call(x && F, w, n_layers, B, L, act));
     FT_CTX(arch);
-    FT_WS(n_layers);
+    FT_WS(n_layers, false);
     FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
     if (C.small(L, n_layers)) {
         SmallArgs a = small_args(x, W, n_layers, B, act, beta, 1);
@@ -846,11 +839,9 @@ int fthmc_ft_force(const double* x, const double* w, const fthmc_arch_t* arch, i
 int fthmc_ft_leapfrog_v(const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
                       int act, double beta, double dt, int nstep, double* x_out, double* v_out,
                       void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    if (!x || !v || !x_out || !v_out || (n_layers > 0 && !w) || bad_shape(B, L) || n_layers < 0 || nstep < 1)
-        return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_flow_call(x && v && x_out && v_out && nstep >= 1, w, n_layers, B, L, act));
     FT_CTX(arch);
-    FT_WS(n_layers);
+    FT_WS(n_layers, false);
     FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
     if (C.small(L, n_layers)) {
         SmallArgs a = small_args(x, W, n_layers, B, act, beta, 2);
@@ -875,11 +866,10 @@ int fthmc_ft_trajectory_v(const double* x, const double* v, const double* u, con
                         double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
                         const double* state_in, double* state_out,
                         void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    if (!x || !v || !u || !x_new || (n_layers > 0 && !w) || bad_shape(B, L) || n_layers < 0 || nstep < 1)
-        return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2 || (mode != FTHMC_MODE_MD && mode != FTHMC_MODE_LITERAL)) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_flow_call(x && v && u && x_new && nstep >= 1, w, n_layers, B, L, act));
+    if (mode != FTHMC_MODE_MD && mode != FTHMC_MODE_LITERAL) return FTHMC_ERR_UNSUPPORTED;
     FT_CTX(arch);
-    FT_WS(n_layers);
+    FT_WS(n_layers, false);
     double* K = W.scal + (size_t)SC_K * B;
     double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
     double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
@@ -948,11 +938,9 @@ int fthmc_ft_trajectory(const double* x, const double* v, const double* u, const
 int fthmc_train_grad(const double* xi, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
                      double* x, double* logq, double* logp, double* gw, void* ws, size_t ws_bytes,
                      void* stream) {
-    if (!xi || !w || bad_shape(B, L) || n_layers < 1) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_flow_call(xi && w && n_layers >= 1, w, n_layers, B, L, act));
     FT_CTX(arch);
-    if (!ws || ws_bytes < ws_doubles(C.A, B, L, n_layers, true) * sizeof(double)) return FTHMC_ERR_WS;
-    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, n_layers, true);
+    FT_WS(n_layers, true);
     FT_TRY(use_weights(C, w, n_layers, W, s));
     if (gw && C.small(L, n_layers)) {
         // small lattices: ONE launch runs the forward sweep (stash + h1, h2 + log J), the loss pieces and the backward sweep of
@@ -960,9 +948,8 @@ int fthmc_train_grad(const double* xi, const double* w, const fthmc_arch_t* arch
         SmallArgs a = small_args(xi, W, n_layers, B, act, beta, 4);
         a.x_out = x; a.logq = logq; a.logp = logp; a.gz = W.gz;
         FT_TRY(launch_ft_small(a, L, s));
-        FlowLayerArgs f{};                                            // every layer's weight gradient in ONE launch + one reduction
+        FlowLayerArgs f(nullptr, B, L, 0, 0, act);                    // every layer's weight gradient in ONE launch + one reduction
         f.stash = W.stash; f.gz = W.gz; f.gw_part = W.gw_part;
-        f.B = B; f.L = L; f.act = act;
         f.nlb = n_layers;
         f.stash_lstride = flow_stash_doubles(B, L, true); f.gz_lstride = flow_gz_doubles(B, L);
         f.tpw = flow_wgrad_tpw(B, L, n_layers);
@@ -997,14 +984,14 @@ int fthmc_time_kernel(int kind, const double* x, const double* w, const fthmc_ar
     if (kind < 2 && !w) return FTHMC_ERR_ARG;
     FT_CTX(arch);
     if (C.gen() && kind < 2) return FTHMC_ERR_UNSUPPORTED;         // the tuned kernels serve the default net shape
-    FT_WS(1);
+    FT_WS(1, false);
     FlowLayerArgs a{};
     if (kind < 2) {
         FT_TRY(use_weights(C, w, 1, W, s));
         FT_TRY(launch_wilson_gp(x, B, L, beta, W.gp, s));
-        a.x = x; a.wint = W.wint; a.y = W.X; a.logj_part = W.lj_part;
+        a = FlowLayerArgs(W.wint, B, L, mu, off, act);
+        a.x = x; a.y = W.X; a.logj_part = W.lj_part;
         a.up_gp = W.gp; a.glogj_const = -1.0; a.gp_part = W.gp_part; a.gp_out = W.gp2;
-        a.B = B; a.L = L; a.mu = mu; a.off = off; a.act = act;
 #ifdef FT_DIAG
         if (const char* e = getenv("FTHMC_DBG_STOP")) a.dbg_stop = atoi(e);
 #endif
@@ -1018,25 +1005,12 @@ int fthmc_time_kernel(int kind, const double* x, const double* w, const fthmc_ar
         if (hipMemsetAsync(seeds, 0, (size_t)B * sizeof(int64_t), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
         FT_TRY(launch_random_momenta(seeds, B, 2 * L * L, W.va, nullptr, s));
     }
-    // the events are created after the last early return and destroyed on every path below
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess) return FTHMC_ERR_LAUNCH;
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return FTHMC_ERR_LAUNCH; }
-    int rc = FTHMC_OK;
-    for (int it = -2; it < reps && rc == FTHMC_OK; ++it) {          // two untimed warm-up launches
-        if (it == 0) (void)hipEventRecord(e0, s);
-        if (kind == 0) rc = flow_fwd(C, a, s);
-        else if (kind == 1) rc = a.stash ? launch_flow_bwd_gather(a, s) : launch_flow_bwd(a, false, s);
-        else if (kind == 2) rc = launch_leap_step(x, W.va, W.xa, W.vb, B, L, beta, 0.05, 0.1, s);
-        else rc = launch_hmc_trajectory_fused(x, W.va, W.scal + B, B, L, beta, 0.1, 10, W.xa, nullptr, nullptr, nullptr, nullptr, s);
-    }
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *ms_avg_host = (double)ms / reps;
-    return rc;
+    return time_launches(reps, s, ms_avg_host, [&] {
+        if (kind == 0) return flow_fwd(C, a, s);
+        if (kind == 1) return a.stash ? launch_flow_bwd_gather(a, s) : launch_flow_bwd(a, false, s);
+        if (kind == 2) return launch_leap_step(x, W.va, W.xa, W.vb, B, L, beta, 0.05, 0.1, s);
+        return launch_hmc_trajectory_fused(x, W.va, W.scal + B, B, L, beta, 0.1, 10, W.xa, nullptr, nullptr, nullptr, nullptr, s);
+    });
 }
 
 int fthmc_time_small(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
@@ -1044,26 +1018,12 @@ int fthmc_time_small(const double* x, const double* v, const double* u, const do
     if (!x || !v || !u || !w || !ms_avg_host || bad_shape(B, L) || n_layers < 1 || nstep < 1 || reps < 1) return FTHMC_ERR_ARG;
     FT_CTX(arch);
     if (!C.small(L, n_layers)) return FTHMC_ERR_UNSUPPORTED;
-    FT_WS(n_layers);
+    FT_WS(n_layers, false);
     FT_TRY(use_weights(C, w, n_layers, W, s));
     SmallArgs a = small_args(x, W, n_layers, B, act, beta, 3);
     a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = W.xb;
     // H0 is evaluated in the launch (no state_in): nstep force sweeps + 2 action sweeps
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess) return FTHMC_ERR_LAUNCH;
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return FTHMC_ERR_LAUNCH; }
-    int rc = FTHMC_OK;
-    for (int it = -2; it < reps && rc == FTHMC_OK; ++it) {          // two untimed warm-up launches
-        if (it == 0) (void)hipEventRecord(e0, s);
-        rc = launch_ft_small(a, L, s);
-    }
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *ms_avg_host = (double)ms / reps;
-    return rc;
+    return time_launches(reps, s, ms_avg_host, [&] { return launch_ft_small(a, L, s); });
 }
 
 int fthmc_small_profile(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
@@ -1072,23 +1032,14 @@ int fthmc_small_profile(const double* x, const double* v, const double* u, const
     if (!x || !v || !u || !w || !cycles_host32 || bad_shape(B, L) || n_layers < 1 || nstep < 1) return FTHMC_ERR_ARG;
     FT_CTX(arch);
     if (!C.small(L, n_layers)) return FTHMC_ERR_UNSUPPORTED;
-    FT_WS(n_layers);
+    FT_WS(n_layers, false);
     long long* dbg = reinterpret_cast<long long*>(W.gw_part);            // unused by the force path; B * 32 stamps fit
     if (hipMemsetAsync(dbg, 0, (size_t)B * 32 * sizeof(long long), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     FT_TRY(use_weights(C, w, n_layers, W, s));
     SmallArgs a = small_args(x, W, n_layers, B, act, beta, 3);
     a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = W.xb; a.dbg = dbg;
     FT_TRY(launch_ft_small(a, L, s));
-    long long* h = (long long*)malloc((size_t)B * 32 * sizeof(long long));
-    if (!h) return FTHMC_ERR_ARG;
-    if (hipMemcpyAsync(h, dbg, (size_t)B * 32 * sizeof(long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) { free(h); return FTHMC_ERR_LAUNCH; }
-    for (int k = 0; k < 32; ++k) {
-        cycles_host32[k] = 0.0;
-        for (int b = 0; b < B; ++b) cycles_host32[k] += (double)h[(size_t)b * 32 + k] / B;
-    }
-    free(h);
-    return FTHMC_OK;
+    return mean_stamps(dbg, (size_t)B, 32, 0, (size_t)B, s, cycles_host32, [](int) { return -1; });
 }
 
 int fthmc_profile_stages(int kind, const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
@@ -1097,18 +1048,16 @@ int fthmc_profile_stages(int kind, const double* x, const double* w, const fthmc
     FT_CTX(arch);
     if (C.gen()) return FTHMC_ERR_UNSUPPORTED;                     // the tuned kernels serve the default net shape
     const bool train = kind >= 2;                                  // kind 2: the backward in training mode (also writes A.gz); 3: k_flow_wgrad behind it
-    if (!ws || ws_bytes < ws_doubles(C.A, B, L, 1, train) * sizeof(double)) return FTHMC_ERR_WS;
-    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, 1, train);
+    FT_WS(1, train);
     const size_t nrec = (size_t)B * (kind >= 1 ? flow_gather_geom() : flow_fwd_geom(true)).ntiles(L);
     // stamp buffer: a workspace region the profiled launch does not write (B * ntiles * 16 stamps fit in either)
     long long* dbg = reinterpret_cast<long long*>(train ? W.gp_part : W.gw_part);
     if (hipMemsetAsync(dbg, 0, nrec * 16 * sizeof(long long), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     FT_TRY(use_weights(C, w, 1, W, s));
     FT_TRY(launch_wilson_gp(x, B, L, beta, W.gp, s));
-    FlowLayerArgs a{};
-    a.x = x; a.wint = W.wint; a.y = W.X; a.logj_part = train ? W.lj_part : nullptr;      // kind 0, 1: the launch of a force sweep
+    FlowLayerArgs a(W.wint, B, L, mu, off, act);
+    a.x = x; a.y = W.X; a.logj_part = train ? W.lj_part : nullptr;                       // kind 0, 1: the launch of a force sweep
     a.up_gp = W.gp; a.glogj_const = -1.0; a.gp_part = W.gp_part; a.gp_out = W.gp2; a.dbg = dbg;
-    a.B = B; a.L = L; a.mu = mu; a.off = off; a.act = act;
     if (kind == 0) a.stash = W.stash;             // the forward as a force sweep launches it: with the activation stash, without log J
     if (kind >= 1) {                              // stash backward needs the forward's stash first
         a.stash = W.stash; a.stash_h = train ? 1 : 0; a.gw_part = W.gw_part; a.gz = train ? W.gz : nullptr; a.dbg = nullptr;
@@ -1118,18 +1067,10 @@ int fthmc_profile_stages(int kind, const double* x, const double* w, const fthmc
     FT_TRY(kind == 0 ? launch_flow_fwd_mfma(a, s) : launch_flow_bwd_gather(a, s));
     size_t nused = nrec;                                           // records the profiled launch stamps
     if (kind == 3) { a.dbg = dbg; a.tpw = flow_wgrad_tpw(B, L, 1); nused = (size_t)flow_wgrad_nparts(B, L, a.tpw); FT_TRY(launch_flow_wgrad(a, s)); }
-    long long* h = (long long*)malloc(nrec * 16 * sizeof(long long));
-    if (!h) return FTHMC_ERR_ARG;
-    if (hipMemcpyAsync(h, dbg, nrec * 16 * sizeof(long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) { free(h); return FTHMC_ERR_LAUNCH; }
-    for (int k = 0; k < 16; ++k) cycles_host16[k] = 0.0;
-    for (size_t r = 0; r < nrec; ++r)
-        for (int k = 1; k < 16; ++k) {
-            const int ref = k == 15 ? 14 : kind == 3 ? k - 1 : (kind >= 1 && k >= 6) ? 0 : (kind == 0 && k == 7) ? 1 : (kind == 0 && k == 11) ? 2 : k - 1;   // forward 7..12 (-DFT_DIAG builds): inside conv1 / conv2      // backward, slots 6..13: per-wave arrival at the first barrier
-            if (h[r * 16 + k] && h[r * 16 + ref]) cycles_host16[k] += (double)(h[r * 16 + k] - h[r * 16 + ref]) / nused;
-        }
-    free(h);
-    return FTHMC_OK;
+    // forward 7..12 (-DFT_DIAG builds): inside conv1 / conv2; backward, slots 6..13: per-wave arrival at the first barrier
+    return mean_stamps(dbg, nrec, 16, 1, nused, s, cycles_host16, [kind](int k) {
+        return k == 15 ? 14 : kind == 3 ? k - 1 : (kind >= 1 && k >= 6) ? 0 : (kind == 0 && k == 7) ? 1 : (kind == 0 && k == 11) ? 2 : k - 1;
+    });
 }
 
 }  // extern "C"
@@ -1140,8 +1081,7 @@ namespace {
 int vjp_begin(const double* x, const double* w, const fthmc_arch_t* arch, int nl, int B, int L, int act, const double* cot,
               const double* gx, const double* gw, void* ws, size_t ws_bytes, void* stream, Ctx* C, VWS* W) {
     (void)hipGetLastError();
-    if (!x || !cot || (!gx && !gw) || (nl > 0 && !w) || bad_shape(B, L) || nl < 0) return FTHMC_ERR_ARG;
-    if (act < 0 || act > 2) return FTHMC_ERR_UNSUPPORTED;
+    FT_TRY(check_flow_call(x && cot && (gx || gw), w, nl, B, L, act));
     FT_TRY(make_ctx(arch, stream, C));
     if (nl > 0 && C->A.k / 2 > L) return FTHMC_ERR_UNSUPPORTED;
     const VWS v = vjp_layout(C->A, nullptr, B, L, nl);
@@ -1153,13 +1093,41 @@ int vjp_begin(const double* x, const double* w, const fthmc_arch_t* arch, int nl
 }
 template <typename T>
 GenLayerArgsT<T> vjp_args(const Ctx& C, const VWS& V, int l, int B, int L, int act) {
-    GenLayerArgsT<T> g{};
-    g.arch = C.A;
-    g.w = C.wcan + (size_t)l * C.A.params();
-    g.stash = reinterpret_cast<T*>(V.stash) + (size_t)l * C.A.stash_doubles(B, L);
-    g.hbuf = reinterpret_cast<T*>(V.hbuf); g.gbuf = reinterpret_cast<T*>(V.gbuf);
-    g.B = B; g.L = L; g.mu = l % 2; g.off = (l / 2) % 4; g.act = act;
-    return g;
+    return gen_layer<T>(C, l, B, L, act, reinterpret_cast<T*>(V.stash) + (size_t)l * C.A.stash_doubles(B, L),
+                        reinterpret_cast<T*>(V.hbuf), reinterpret_cast<T*>(V.gbuf));
+}
+// The sweeps of both entry points, on T = double (the action's VJP) or Dual (the force's: the first-order sweep of force_gp on the
+// dual field x + eps g).  Forward: x -> X[0 .. nl - 1], every layer's activations kept; returns the flowed field.
+template <typename T>
+int vjp_forward(const Ctx& C, const VWS& V, const T* x, int nl, int B, int L, int act, const T** xphys) {
+    const size_t n2 = (size_t)B * 2 * L * L;
+    T* X = reinterpret_cast<T*>(V.X);
+    for (int l = 0; l < nl; ++l) {
+        GenLayerArgsT<T> g = vjp_args<T>(C, V, l, B, L, act);
+        g.x = l == 0 ? x : X + (size_t)(l - 1) * n2;
+        g.y = X + (size_t)l * n2;
+        FT_TRY(launch_gen_fwd(g, false, C.s));
+    }
+    *xphys = nl == 0 ? x : X + (size_t)(nl - 1) * n2;
+    return FTHMC_OK;
+}
+// Backward: the seed coef[b] beta sin P at the flowed field, then layer by layer; d/d logJ = glogj[b] (null: glogj_const); gw
+// (optional): every layer's weight gradient.  Returns the plaquette gradient at x.
+template <typename T>
+int vjp_backward(const Ctx& C, const VWS& V, const T* xphys, int nl, int B, int L, int act, double beta, const double* coef,
+                 const double* glogj, double glogj_const, T* gw, T** gp) {
+    T* gcur = reinterpret_cast<T*>(V.gp);
+    T* galt = reinterpret_cast<T*>(V.gp2);
+    FT_TRY(launch_gen_seed(xphys, coef, B, L, beta, gcur, C.s));
+    for (int l = nl - 1; l >= 0; --l) {
+        GenLayerArgsT<T> g = vjp_args<T>(C, V, l, B, L, act);
+        g.up_gp = gcur; g.glogj = glogj; g.glogj_const = glogj_const; g.gp_out = galt;
+        g.gw = gw ? gw + (size_t)l * C.A.params() : nullptr;
+        FT_TRY(launch_gen_bwd(g, C.s));
+        std::swap(gcur, galt);
+    }
+    *gp = gcur;
+    return FTHMC_OK;
 }
 }  // namespace
 
@@ -1178,28 +1146,14 @@ int fthmc_ft_action_vjp(const double* x, const double* w, const fthmc_arch_t* ar
     Ctx C; VWS V;
     FT_TRY(vjp_begin(x, w, arch, n_layers, B, L, act, gS, gx, gw, ws, ws_bytes, stream, &C, &V));
     const hipStream_t s = C.s;
-    const size_t n2 = (size_t)B * 2 * L * L;
-    double* X = reinterpret_cast<double*>(V.X);
-    for (int l = 0; l < n_layers; ++l) {                          // forward sweep, every layer's activations kept
-        GenLayerArgs g = vjp_args<double>(C, V, l, B, L, act);
-        g.x = l == 0 ? x : X + (size_t)(l - 1) * n2;
-        g.y = X + (size_t)l * n2;
-        FT_TRY(launch_gen_fwd(g, false, s));
-    }
+    const double* xphys;
+    FT_TRY(vjp_forward<double>(C, V, x, n_layers, B, L, act, &xphys));
     // d/d logJ of every layer, per chain: glogdet[b] - gS[b]
     if (n_layers > 0) FT_TRY(glogdet ? launch_lincomb(glogdet, 1.0, gS, -1.0, 0.0, V.glj, B, s)
                                      : launch_lincomb(gS, -1.0, nullptr, 0.0, 0.0, V.glj, B, s));
-    double* gcur = reinterpret_cast<double*>(V.gp);
-    double* galt = reinterpret_cast<double*>(V.gp2);
-    FT_TRY(launch_gen_seed(n_layers == 0 ? x : X + (size_t)(n_layers - 1) * n2, gS, B, L, beta, gcur, s));
-    for (int l = n_layers - 1; l >= 0; --l) {
-        GenLayerArgs g = vjp_args<double>(C, V, l, B, L, act);
-        g.up_gp = gcur; g.glogj = V.glj; g.gp_out = galt;
-        g.gw = gw ? gw + (size_t)l * C.A.params() : nullptr;
-        FT_TRY(launch_gen_bwd(g, s));
-        double* t_ = gcur; gcur = galt; galt = t_;
-    }
-    return gx ? launch_kick_from_gp(gcur, nullptr, nullptr, gx, B, L, 0.0, 0.0, s) : FTHMC_OK;
+    double* gp;
+    FT_TRY(vjp_backward<double>(C, V, xphys, n_layers, B, L, act, beta, gS, V.glj, 0.0, gw, &gp));
+    return gx ? launch_kick_from_gp(gp, nullptr, nullptr, gx, B, L, 0.0, 0.0, s) : FTHMC_OK;
 }
 
 int fthmc_ft_force_vjp(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
@@ -1208,27 +1162,14 @@ int fthmc_ft_force_vjp(const double* x, const double* w, const fthmc_arch_t* arc
     FT_TRY(vjp_begin(x, w, arch, n_layers, B, L, act, g, gx, gw, ws, ws_bytes, stream, &C, &V));
     const hipStream_t s = C.s;
     const size_t n2 = (size_t)B * 2 * L * L;
-    // the first-order sweep of force_gp on the dual field x + eps g: the eps parts of its link and weight gradients are H g and
-    // d/dw <g, F>
+    // the eps parts of the dual sweep's link and weight gradients are H g and d/dw <g, F>
     FT_TRY(launch_dual_pack(x, g, V.xd, n2, s));
-    for (int l = 0; l < n_layers; ++l) {
-        GenLayerArgsT<Dual> a = vjp_args<Dual>(C, V, l, B, L, act);
-        a.x = l == 0 ? V.xd : V.X + (size_t)(l - 1) * n2;
-        a.y = V.X + (size_t)l * n2;
-        FT_TRY(launch_gen_fwd_dual(a, s));
-    }
-    Dual* gcur = V.gp;
-    Dual* galt = V.gp2;
-    FT_TRY(launch_gen_seed_dual(n_layers == 0 ? V.xd : V.X + (size_t)(n_layers - 1) * n2, nullptr, B, L, beta, gcur, s));
-    for (int l = n_layers - 1; l >= 0; --l) {
-        GenLayerArgsT<Dual> a = vjp_args<Dual>(C, V, l, B, L, act);
-        a.up_gp = gcur; a.glogj_const = -1.0; a.gp_out = galt;
-        a.gw = gw ? V.gw + (size_t)l * C.A.params() : nullptr;
-        FT_TRY(launch_gen_bwd_dual(a, s));
-        Dual* t_ = gcur; gcur = galt; galt = t_;
-    }
+    const Dual* xphys;
+    FT_TRY(vjp_forward<Dual>(C, V, V.xd, n_layers, B, L, act, &xphys));
+    Dual* gp;
+    FT_TRY(vjp_backward<Dual>(C, V, xphys, n_layers, B, L, act, beta, nullptr, nullptr, -1.0, gw ? V.gw : nullptr, &gp));
     if (gw && n_layers > 0) FT_TRY(launch_dual_tangent(V.gw, gw, (size_t)n_layers * C.A.params(), s));
-    return gx ? launch_dual_links(gcur, gx, B, L, s) : FTHMC_OK;
+    return gx ? launch_dual_links(gp, gx, B, L, s) : FTHMC_OK;
 }
 
 }  // extern "C"

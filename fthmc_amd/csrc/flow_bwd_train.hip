@@ -46,7 +46,6 @@
 // (fthmc/utils/layers.py:196-202,348-371) and make_conv_net (:138-167).
 #include "flow_mfma_common.h"
 
-#if !FT_RECOMP_D1       // the act'(z1)-recompute build (an A/B switch of the force path) keeps the two-kernel form
 namespace {
 
 using namespace fthmc;
@@ -152,7 +151,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
     const unsigned Bn = (unsigned)A.B * (unsigned)n;
     auto ldu2 = [](const double* base, unsigned idx_) {                  // 16-byte load, scalar base + 32-bit element offset
         const double2_t* p = reinterpret_cast<const double2_t*>(reinterpret_cast<const char*>(base) + idx_ * 8u);
-        return FT_NT_LOAD >= 1 ? __builtin_nontemporal_load(p) : *p;
+        return *p;
     };
 
     // ---- once per walk: the layer's backward weight block, the zeros behind the windows (read by discarded ky = 3 columns only)
@@ -300,7 +299,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
         const double* pl = uniform_at(A.stash, 8u * (Bn + (unsigned)q.b * (unsigned)n));
         auto ldu2o = [](const double* base, unsigned o) {
             const double2_t* p = reinterpret_cast<const double2_t*>(reinterpret_cast<const char*>(base) + o);
-            return FT_NT_LOAD >= 1 ? __builtin_nontemporal_load(p) : *p;
+            return *p;
         };
 #pragma unroll
         for (int e = 0; e < C3::NIT; ++e) {
@@ -310,11 +309,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
                 // on a dead line (no active site within reach: an exact 0 there) the stash holds nothing: record 0 instead
                 const bool live = P.ok && !P.dead(dd);
                 const int i = wi_(q, P.row(dd) - 2), j = WJ_(q, P.col(dd) - 2);
-#if FT_D2_C
                 const int go = mu == 0 ? mul24(i, 3 * (L >> 2)) + stash_live_line<true>(j, L, off) : mul24(stash_live_line<true>(i, L, off), L) + j;
-#else
-                const int go = mul24(i, L) + j;
-#endif
                 const double2_t vd = ldu2o(pl, ft_off32((unsigned)(live ? go : 0) * 8u) + 16u * (unsigned)(lane >> 4));
                 d2v[e][2 * dd] = vd.x; d2v[e][2 * dd + 1] = vd.y;
             }
@@ -325,9 +320,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
 #pragma unroll
         for (int e = 0; e < NIT1; ++e) {
             const int ra = mu == 0 ? pv[e] : 2 * pu[e], ca = mu == 0 ? 2 * pu[e] : pv[e];
-            // mu = 0: the act'(z1) plane is stored transposed (FT_D1_T, flow_mfma_common.h): site index j L + i
-            const int ga = (FT_D1_T && mu == 0) ? mul24(WJ_(q, ca - 1), L) + wi_(q, ra - 1) : WI_(q, ra - 1) + WJ_(q, ca - 1);
-            const int gb = mu == 0 ? (FT_D1_T ? mul24(WJ_(q, ca), L) + wi_(q, ra - 1) : WI_(q, ra - 1) + WJ_(q, ca)) : WI_(q, ra) + WJ_(q, ca - 1);
+            // mu = 0: the act'(z1) plane is stored transposed (flow_mfma_common.h): site index j L + i
+            const int ga = mu == 0 ? mul24(WJ_(q, ca - 1), L) + wi_(q, ra - 1) : WI_(q, ra - 1) + WJ_(q, ca - 1);
+            const int gb = mu == 0 ? mul24(WJ_(q, ca), L) + wi_(q, ra - 1) : WI_(q, ra) + WJ_(q, ca - 1);
             const unsigned og = 2u * (unsigned)(lane >> 4);                  // channels 2 g, 2 g + 1: one 16-byte load per site
             const double2_t va = ldu2(st1, (unsigned)ga * 8u + og), vb = ldu2(st1, (unsigned)gb * 8u + og);
             d1v[e][0] = va.x; d1v[e][1] = va.y; d1v[e][2] = vb.x; d1v[e][3] = vb.y;
@@ -652,17 +647,10 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
 }
 
 }  // namespace
-#endif
 
 namespace fthmc {
 
-bool flow_bwd_train_built() { return !FT_RECOMP_D1; }
-
 int launch_flow_bwd_train(const FlowLayerArgs& a, hipStream_t s) {
-#if FT_RECOMP_D1
-    (void)a; (void)s;
-    return FTHMC_ERR_UNSUPPORTED;
-#else
     if (!flow_shape_ok(a.B, a.L, a.off)) return FTHMC_ERR_ARG;
     if (!flow_bwd_train_shape(a.L) || !a.up_gp || a.up_link || a.glogj || !a.stash || !a.gp_out || !a.gw_part) return FTHMC_ERR_UNSUPPORTED;
     if (!flow_stash_fits32(a.B, a.L, true)) return FTHMC_ERR_UNSUPPORTED;                   // 32-bit plane offsets (uniform_at)
@@ -675,7 +663,6 @@ int launch_flow_bwd_train(const FlowLayerArgs& a, hipStream_t s) {
     if (a.mu == 0) hipLaunchKernelGGL((k_flow_bwd_train<MG_TR, MG_TC, 0>), grid, dim3(NT), 0, s, b);
     else hipLaunchKernelGGL((k_flow_bwd_train<MG_TR, MG_TC, 1>), grid, dim3(NT), 0, s, b);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
-#endif
 }
 
 }  // namespace fthmc

@@ -67,7 +67,7 @@ template <int TR, int TC, int MU, bool AL> struct SmemF {
 // (tools/lifetime.py, fthmc_profile_stages: those run SWEEP = 2, the same specialization WITH the stamps).  SWEEP = 3: a layer
 // of an ACTION sweep (the H1 sweep of a trajectory, ft_action: link field in and out, log J, no stash).  SWEEP = 4: a layer of a
 // TRAINING sweep (fthmc_train_grad: stash with h1 / h2, log J).  5, 6: SWEEP = 1, 4 with NON-TEMPORAL stash stores, for a stash
-// nobody finds in a cache again (launch_fwd: a layer's stash beyond FT_NT_MIN_BYTES).  0: whatever the argument block says.
+// nobody finds in a cache again (launch_fwd: a layer's stash beyond NT_MIN_BYTES).  0: whatever the argument block says.
 template <int TR, int TC, bool FASTW, bool REV, int MU, bool EXACT, bool SILU, int SWEEP>
 __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const double* hx, const double* hw, double* hy, double* hstash, double* hlogj,
                                                                           int hB, int hL, unsigned hoa, FlowLayerArgs A0) {
@@ -307,20 +307,20 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
             const int ds = mu == 0 ? 1 : RS1;
             double* ph = sH1 + 2 * g * PS1 + r * RS1 + c;
             ph[0] = h[0]; ph[PS1] = h[1]; ph[ds] = h[2]; ph[PS1 + ds] = h[3];
-            if (FT_RECOMP_D1 ? stash_h : has_stash) {   // act'(z1) (and h1) of the tile's own sites
+            if (has_stash) {   // act'(z1) (and h1) of the tile's own sites
                 const int r0 = r - 2, c0 = c - 2, r1 = mu == 0 ? r0 : r0 + 1, c1 = mu == 0 ? c0 + 1 : c0;
                 // the pair's two sites lie ACROSS the lines: with aligned origins the lattice edge can fall between them, so each
                 // site's global line is wrapped on its own (out-of-tile members fail the bounds tests below, their index is unused)
                 const int gr0 = gi(r0), gc0 = gj(c0), gr1 = gi(r1), gc1 = gj(c1);
                 const int at = mul24(gr0, L) + gc0, at1 = mul24(gr1, L) + gc1;
-                // act'(z1) of a mu = 0 layer: transposed site index (FT_D1_T): the lanes of a tile run down a column
-                const int atd = (FT_D1_T && mu == 0) ? mul24(gc0, L) + gr0 : at, atd1 = (FT_D1_T && mu == 0) ? mul24(gc1, L) + gr1 : at1;
+                // act'(z1) of a mu = 0 layer: transposed site index: the lanes of a tile run down a column
+                const int atd = mu == 0 ? mul24(gc0, L) + gr0 : at, atd1 = mu == 0 ? mul24(gc1, L) + gr1 : at1;
                 if ((unsigned)r0 < (unsigned)rmax && (unsigned)c0 < (unsigned)cmax) {
-                    if (!FT_RECOMP_D1) sts2<NTS>(st_d1, 8u * (unsigned)atd + stg, double2_t{d[0], d[1]});
+                    sts2<NTS>(st_d1, 8u * (unsigned)atd + stg, double2_t{d[0], d[1]});
                     if (stash_h) sts2<NTS>(st_h1, 8u * (unsigned)at + stg, double2_t{h[0], h[1]});
                 }
                 if ((unsigned)r1 < (unsigned)rmax && (unsigned)c1 < (unsigned)cmax) {
-                    if (!FT_RECOMP_D1) sts2<NTS>(st_d1, 8u * (unsigned)atd1 + stg, double2_t{d[2], d[3]});
+                    sts2<NTS>(st_d1, 8u * (unsigned)atd1 + stg, double2_t{d[2], d[3]});
                     if (stash_h) sts2<NTS>(st_h1, 8u * (unsigned)at1 + stg, double2_t{h[2], h[3]});
                 }
             }
@@ -354,7 +354,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
             const int rr = r - 2, cc = c - 2;
             if ((unsigned)rr < (unsigned)rmax && (unsigned)cc < (unsigned)cmax) {
                 const int grr = gi(rr), gcc = gj(cc), at = mul24(grr, L) + gcc;
-                if (!FT_RECOMP_D1) sts<NTS>(st_d1, 8u * (unsigned)((FT_D1_T && mu == 0) ? mul24(gcc, L) + grr : at) + (unsigned)co, d);
+                sts<NTS>(st_d1, 8u * (unsigned)(mu == 0 ? mul24(gcc, L) + grr : at) + (unsigned)co, d);
                 if (stash_h) sts<NTS>(st_h1, 8u * (unsigned)at + (unsigned)co, h);
             }
         }
@@ -388,9 +388,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         if (has_stash && ok) {                                // act'(z2) (and h2) of the tile's own sites
             // (the pair lies ALONG the lines, where the origin is a multiple of 16: its second site never wraps)
             const int at = mul24(gi(r - 1), L) + gj(c - 1);
-            // act'(z2): live lines only (FT_D2_C, stash_live_idx); the pair's second site is one line-step along the stripe lines
-            const int a2 = FT_D2_C ? stash_live_idx<EXACT>(gi(r - 1), gj(c - 1), L, mu, off) : at;
-            const int da2 = FT_D2_C ? (mu == 0 ? dr * 3 * (L >> 2) + dc : dr * L + dc) : dr * L + dc;
+            // act'(z2): live lines only (stash_live_idx); the pair's second site is one line-step along the stripe lines
+            const int a2 = stash_live_idx<EXACT>(gi(r - 1), gj(c - 1), L, mu, off);
+            const int da2 = mu == 0 ? dr * 3 * (L >> 2) + dc : dr * L + dc;
 #pragma unroll
             for (int q = 0; q < 2; ++q)
                 if ((unsigned)(r - 1 + q * dr) < (unsigned)rmax && (unsigned)(c - 1 + q * dc) < (unsigned)cmax) {
@@ -433,7 +433,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     if (AL && wave >= NT2) lds_barrier();                               // the barrier of conv2_epi
     else if (mu == 0) {
         // B[k = (tap = ky4 * 3 + kx, ci)][n = (co, dd)] = W1[co][ci][ky4 - dd][kx]; pairs = rows (2 pr, 2 pr + 1)
-        mfma_stage<KConv2Row, 16 * NW, RS1, PS1, false, false, FT_NCH ? FT_NCH : 1>(sH1, sW + LF_P2, wave, lane,
+        mfma_stage<KConv2Row, 16 * NW, RS1, PS1, false, false, 1>(sH1, sW + LF_P2, wave, lane,
             [&](int) { return 2 * pl * RS1 + min(wl, R2C - 1); },
             [&](int g, int, bool, double (&z)[4], int) { conv2_epi(g, pok, 2 * pl, wl, 1, 0, z); },
 #ifdef FT_DIAG
@@ -444,7 +444,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
             bias2);
     } else {
         // B[k = (tap = ky * 4 + kx4, ci)][n = (co, dd)] = W1[co][ci][ky][kx4 - dd]; pairs = columns (2 pc, 2 pc + 1)
-        mfma_stage<KConv2Col, 16 * NW, RS1, PS1, false, false, FT_NCH ? FT_NCH : 1>(sH1, sW + LF_P2, wave, lane,
+        mfma_stage<KConv2Col, 16 * NW, RS1, PS1, false, false, 1>(sH1, sW + LF_P2, wave, lane,
             [&](int) { return min(wl, R2R - 1) * RS1 + 2 * pl; },
             [&](int g, int, bool, double (&z)[4], int) { conv2_epi(g, pok, wl, 2 * pl, 0, 1, z); },
             nullptr, bias2);
@@ -691,8 +691,7 @@ template <bool REV> void launch_fwd(const fthmc::FlowLayerArgs& a, dim3 grid, hi
     // training step (6.92 -> 6.6 ms).  At the headline shape (40 MB per layer and chain group) the backward finds the LAST layers'
     // stash in the caches -- the hint on every layer cost 0.8 % there, on all but the last two (stash_far) it gains 0.3-1.1 %
     // (profiles/r06_ab_nontemporal_stash.txt).
-    const bool nt_stash = FT_NT_STASH && a.stash && ((FT_NT_STASH <= 2 && fthmc::flow_stash_doubles(a.B, a.L, a.stash_h != 0) * sizeof(double) >= FT_NT_MIN_BYTES) ||
-                                                      (FT_NT_STASH >= 2 && a.stash_far));
+    const bool nt_stash = a.stash && (fthmc::flow_stash_doubles(a.B, a.L, a.stash_h != 0) * sizeof(double) >= NT_MIN_BYTES || a.stash_far);
     const bool fast = wrap_fast_ok(a.L, TR, TC);
     // (a power of two wraps any window line by one v_and: L = 16, a single tile that wraps onto itself, is EXACT too)
     const bool exact = a.L % TR == 0 && a.L % TC == 0 && (a.L & (a.L - 1)) == 0;

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void k_gen_transform(const T* __restrict__ x, 
             if (mu == 0) yb[s] = ft_wrap(d + yb[s]); else yb[n + s] = ft_wrap(-d + yb[n + s]);
         }
     }
-    if constexpr (std::is_same<T, double>::value) {         // the dual sweeps need no log J (launch_gen_fwd_dual refuses one)
+    if constexpr (std::is_same<T, double>::value) {         // the dual sweeps need no log J (launch_gen_fwd refuses one)
         if (logJ) {
             const T tot = ft_block_sum(lj, red);
             if (threadIdx.x == 0) logJ[b] = (accumulate ? logJ[b] : 0.0) + tot;
@@ -465,12 +465,12 @@ int gen_seed(const T* x, const double* coef, int B, int L, double beta, T* gp, h
 
 int launch_gen_fwd(const GenLayerArgs& a, bool rev, hipStream_t s) { return gen_fwd(a, rev, s); }
 int launch_gen_bwd(const GenLayerArgs& a, hipStream_t s) { return gen_bwd(a, s); }
-int launch_gen_fwd_dual(const GenLayerArgsT<Dual>& a, hipStream_t s) { return a.logj ? FTHMC_ERR_UNSUPPORTED : gen_fwd(a, false, s); }
-int launch_gen_bwd_dual(const GenLayerArgsT<Dual>& a, hipStream_t s) { return gen_bwd(a, s); }
+int launch_gen_fwd(const GenLayerArgsT<Dual>& a, bool rev, hipStream_t s) { return a.logj || rev ? FTHMC_ERR_UNSUPPORTED : gen_fwd(a, false, s); }
+int launch_gen_bwd(const GenLayerArgsT<Dual>& a, hipStream_t s) { return gen_bwd(a, s); }
 int launch_gen_seed(const double* x, const double* coef, int B, int L, double beta, double* gp, hipStream_t s) {
     return gen_seed(x, coef, B, L, beta, gp, s);
 }
-int launch_gen_seed_dual(const Dual* x, const double* coef, int B, int L, double beta, Dual* gp, hipStream_t s) {
+int launch_gen_seed(const Dual* x, const double* coef, int B, int L, double beta, Dual* gp, hipStream_t s) {
     return gen_seed(x, coef, B, L, beta, gp, s);
 }
 int launch_dual_pack(const double* x, const double* g, Dual* out, size_t n, hipStream_t s) {

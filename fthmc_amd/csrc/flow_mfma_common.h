@@ -20,54 +20,30 @@
 #define FT_LDS_B64
 #endif
 
-// accumulator chains of the MFMA stages (0 = default rule); a build-time knob for A/B runs
-#ifndef FT_NCH
-#define FT_NCH 0
-#endif
-
-// 1: the backward kernel recomputes act'(z1) (conv1 on the matrix cores over the stashed cos / sin of the frozen
-// plaquettes, on the pair map of conv2^T so that the values land in the registers that multiply by them, + one sigmoid
-// per value) instead of reading it back: the forward kernel then writes 9 (training: 25) instead of 17 (33) doubles per
-// site and layer.  0 (default): act'(z1) travels through the stash.  Measured in round 3 (tools/abn.sh, config 3, one
-// device, alternating): forward 26.2 -> 24.9 us per 64-chain launch, backward 19.8 -> 22.6 us (full batch 35.1 -> 41.8),
-// trajectory 6.375 -> 6.578 ms: the backward is not as idle as its load phase suggests, the 33 MFMAs + 11 sigmoid
-// epilogues per workgroup cost more than the forward saves.  Kept as a build switch (make EXTRA=-DFT_RECOMP_D1=1).
-#ifndef FT_RECOMP_D1
-#define FT_RECOMP_D1 0
-#endif
-
-// 1 (default): the act'(z1) plane of a mu = 0 layer is stored TRANSPOSED ([j][i][8]: site index j L + i).  Both kernels walk that
-// plane down the stripe lines -- conv1 and conv2^T pair their output sites ACROSS the lines, so the 16 lanes of a tile are 16
-// positions ALONG a line: 16 consecutive rows for mu = 0 --, and row-major storage made every one of those 16-byte accesses its own
-// 64-byte piece of a line 4 KB from the next (16 half lines per wave instruction where mu = 1 touches 8 whole ones): the mu = 0
-// instances were 4 % (forward) and 10 % (backward) slower than the mu = 1 ones, all of it in load / store issue.
-#ifndef FT_D1_T
-#define FT_D1_T 1
-#endif
+// Stash layout and store policy of the coupling kernels (the measurements behind them: DESIGN.md 4, profiles/README.md; the
+// measured alternative to the first, act'(z1) recomputed in the backward instead of stashed: experiments/bwd_recompute_act_z1.patch)
+//
+// act'(z1) travels through the stash, and the plane of a mu = 0 layer is stored TRANSPOSED ([j][i][8]: site index j L + i).  Both
+// kernels walk that plane down the stripe lines -- conv1 and conv2^T pair their output sites ACROSS the lines, so the 16 lanes of a
+// tile are 16 positions ALONG a line: 16 consecutive rows for mu = 0 --, and row-major storage made every one of those 16-byte
+// accesses its own 64-byte piece of a line 4 KB from the next (16 half lines per wave instruction where mu = 1 touches 8 whole ones):
+// the mu = 0 instances were 4 % (forward) and 10 % (backward) slower than the mu = 1 ones, all of it in load / store issue.
+//
 // The forward's stash stores carry the non-temporal hint (flow_fwd.hip launch_fwd: the SWEEP = 5, 6 instances) where the backward
-// will not find the stash in a cache again.  2 (default): one layer's stash is FT_NT_MIN_BYTES or more, OR the layers behind this
-// one write FT_STASH_FAR_BYTES (kernels.h) or more before the backward comes back to it (FlowLayerArgs::stash_far: at the headline
-// shape every layer but the last two); 1: the first rule only; 3: the second only; 0: never (A/B knob)
-#ifndef FT_NT_STASH
-#define FT_NT_STASH 2
-#endif
-#ifndef FT_NT_MIN_BYTES
-#define FT_NT_MIN_BYTES ((size_t)128 << 20)
-#endif
-// 1: the training backward's stash LOADS carry the hint too; 2: also k_flow_bwd_gather's (A/B knob)
-#ifndef FT_NT_LOAD
-#define FT_NT_LOAD 0
-#endif
-// 1 (default): the act'(z2) plane holds the live stripe lines only, in order (stash_live_idx).  conv3 reads h2 within one site of
+// will not find the stash in a cache again: one layer's stash is NT_MIN_BYTES or more, OR the layers behind this one write
+// STASH_FAR_BYTES (kernels.h) or more before the backward comes back to it (FlowLayerArgs::stash_far: at the headline shape every
+// layer but the last two).  The backward's stash loads carry no hint.
+//
+// The act'(z2) plane holds the live stripe lines only, in order (stash_live_idx).  conv3 reads h2 within one site of
 // an active line, so every fourth line (x = off + 2 mod 4) is dead: never written, never used.  Row-major storage left the dead
 // COLUMNS of a mu = 0 layer inside the cache lines the backward fetches (record = 64 B, line = 128 B: a window row cost 10 lines
 // for 15 live records; per-kernel counters: 32 % more L2 read requests and 11 % more HBM reads than the mu = 1 instance, whose
 // dead ROWS are skipped whole).  Compact, both instances read the same from HBM; the backward's mu = 0 / mu = 1 gap went from 8.5 % to 5.6 %.
-#ifndef FT_D2_C
-#define FT_D2_C 1
-#endif
 
 namespace fthmc_flow {
+
+// a layer's stash of this size or more is stored with the non-temporal hint whatever comes behind it (launch_fwd, see above)
+constexpr size_t NT_MIN_BYTES = (size_t)128 << 20;
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -137,7 +113,7 @@ __device__ __forceinline__ void stu2(double* base, unsigned idx, double2u_t v) {
     *(FT_G double2u_t*)((FT_G char*)base + idx * 8u) = v;
 }
 // ... and the same with the non-temporal hint (NTS, a template flag of the caller's instance): the stash of a TRAINING sweep is
-// 280 bytes per site and layer that nobody reads before the whole sweep has gone by (FT_NT_STASH, flow_fwd.hip)
+// 280 bytes per site and layer that nobody reads before the whole sweep has gone by (flow_fwd.hip launch_fwd)
 template <bool NTS> __device__ __forceinline__ void sts(double* base, unsigned idx, double v) {
     FT_G double* p = (FT_G double*)((FT_G char*)base + idx * 8u);
     if (NTS) __builtin_nontemporal_store(v, p); else *p = v;
@@ -170,10 +146,7 @@ constexpr int ps_round(int n) { return ((n - 18 + 31) / 32) * 32 + 18; }
 // Plane stride of the planes an MFMA stage reads its activation operand from: = 16 (mod 32).  A ds_read_b64 is banked
 // over 32 lanes = 16 pairs x two K lane groups g, g + 1 (one plane apart): consecutive pair sites + 16 fill the 32
 // double-wide banks exactly (with 18 two lanes collide and the read takes a third LDS cycle).
-#ifndef FT_PSMOD
-#define FT_PSMOD 16
-#endif
-constexpr int ps_round16(int n) { return ((n - FT_PSMOD + 31) / 32) * 32 + FT_PSMOD; }
+constexpr int ps_round16(int n) { return ((n - 16 + 31) / 32) * 32 + 16; }
 
 // AL (aligned tile origins, flow_fwd.hip: the active lines sit at tile lines 1, 5, 9, 13 whatever the layer's offset): ACROSS the
 // stripe lines (columns for MU = 0, rows for MU = 1) conv1 is needed on 18 lines and the net input on 20, two fewer than along
@@ -189,7 +162,7 @@ template <int TR, int TC, int MU = 0, bool AL = false> struct Geom {
     static constexpr int N3 = TR * TC, NA = N3 / 4;                    // tile, active sites
     static constexpr int NAS = NA <= 32 ? 32 : 64;                     // lane stride of per-active-site scratch
     static constexpr int PS0 = ps_round16(N0), PS1 = ps_round16(R1R * RS1), PS2 = ps_round(N2);   // net input, h1: MFMA operands
-    static_assert(PS0 % 32 == FT_PSMOD && PS1 % 32 == FT_PSMOD && PS2 % 32 == 18, "bank layout");
+    static_assert(PS0 % 32 == 16 && PS1 % 32 == 16 && PS2 % 32 == 18, "bank layout");
     static_assert(PS0 >= N0 && PS1 >= R1R * RS1 && PS2 >= N2, "plane size");
     static_assert(TR % 4 == 0 && TC % 4 == 0 && NA <= 64 && RS1 % 2 == 1, "tile shape");
 };
@@ -197,8 +170,8 @@ template <int TR, int TC, int MU = 0, bool AL = false> struct Geom {
 
 // Per-layer activation stash written by the forward kernel and read back by the gather-form backward
 // (n = L * L; per chain b):
-//   d1  [n][8]     act'(z1), channel-minor (mu = 0 layers: site index TRANSPOSED, j L + i: FT_D1_T)
-//   d2  [3n/4][8]  act'(z2), channel-minor, the LIVE stripe lines only, compact (FT_D2_C, stash_live_idx; the tiled kernels --
+//   d1  [n][8]     act'(z1), channel-minor (mu = 0 layers: site index TRANSPOSED, j L + i)
+//   d2  [3n/4][8]  act'(z2), channel-minor, the LIVE stripe lines only, compact (stash_live_idx; the tiled kernels --
 //                  k_ft_small keeps [n][8] with its dead lines unwritten; the plane is n records either way): a window row of a
 //                  mu = 0 layer is 15 consecutive records, not 20 of which every fourth is fetched with its cache line and dropped
 //                  (64 B per site: a window row of 20 sites is 10 cache lines for all channels, not 8 x 2..3,
@@ -227,7 +200,7 @@ __device__ __forceinline__ int stash_active_idx(int i, int j, int L, int mu) {
     // unsigned 24-bit multiply-adds (coordinates are lattice sites): the signed form came out as v_bfe_i32 + the quarter-rate v_mad_u64_u32
     return (int)(mu == 0 ? __umul24((unsigned)i, (unsigned)(L >> 2)) + (unsigned)(j >> 2) : __umul24((unsigned)(i >> 2), (unsigned)L) + (unsigned)j);
 }
-// act'(z2) plane: index of site (i, j) when only the live stripe lines are stored (FT_D2_C): conv3 reads h2 within one site of an
+// act'(z2) plane: index of site (i, j) when only the live stripe lines are stored: conv3 reads h2 within one site of an
 // active line, so the lines x = off + 2 (mod 4) are never written nor used; live lines in order, 3 of every 4
 template <bool POW2> __device__ __forceinline__ int stash_live_line(int x, int L, int off) {     // compact index of stripe line x
     int u = x - off - 3;                                  // (x - off - 3) mod L: class 0, 1, 2 live (off - 1, off, off + 1), 3 dead
@@ -327,9 +300,6 @@ __device__ __forceinline__ void mfma_stage(const double* __restrict__ A, const d
 #pragma unroll
         for (int t = 0; t < NSTEP; ++t) {
             accs[t % NCH] = __builtin_amdgcn_mfma_f64_16x16x4f64(wp[KO::bimm(t)], a0[KO::template aimm<RSA, PSA>(t)], accs[t % NCH], 0, 0, 0);
-#ifdef FT_MFMA_FENCE      // a scheduling fence every FT_MFMA_FENCE K steps: bounds how many operand reads are hoisted (register budget)
-            if (t % FT_MFMA_FENCE == FT_MFMA_FENCE - 1) __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         double4_t acc = accs[0];
 #pragma unroll

@@ -4,13 +4,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+namespace fthmc {
+
 // FlowLayerArgs::stash_far (api.hip sweep_forward): a layer's stash counts as gone from the caches when the layers behind it write this
 // much before the backward returns to it -- the 256 MB Infinity Cache over two chain groups, each writing and reading back
-#ifndef FT_STASH_FAR_BYTES
-#define FT_STASH_FAR_BYTES ((size_t)64 << 20)
-#endif
-
-namespace fthmc {
+constexpr size_t STASH_FAR_BYTES = (size_t)64 << 20;
 
 // ---- wilson.hip
 int launch_wrap(const double* x, double* o, size_t n, int reg, hipStream_t s);
@@ -95,6 +93,10 @@ inline size_t flow_gp_part_max(int L) { return (size_t)flow_geom(false).ntiles(L
 // token = 0: expand unconditionally (and clear the stamps); else see FLOW_WSTAMPS above
 int launch_pack_weights(const double* w, int n_layers, double* wint, hipStream_t s, unsigned long long token = 0ull);
 
+// layer l of a flow: stripe direction and offset (fthmc/utils/layers.py: the eight masks of a block, in order)
+inline int layer_mu(int l) { return l % 2; }
+inline int layer_off(int l) { return (l / 2) % 4; }
+
 struct FlowLayerArgs {
     const double* x;         // [B][2][L][L] layer input
     const double* wint;      // this layer's weights, kernel layout
@@ -125,6 +127,15 @@ struct FlowLayerArgs {
     size_t stash_lstride, gz_lstride, gwp_lstride;
     int tpw;                 // k_flow_wgrad: (chain, tile) items a workgroup walks (flow_wgrad_tpw; 0 = 1)
     int wg_ns;               // k_flow_wgrad: stride of the walk = workgroups that stand on consecutive tiles (set by the launcher)
+    // host side: everything zero / null but the layer's weights, shape and stripe
+    FlowLayerArgs() = default;
+    FlowLayerArgs(const double* wint_, int B_, int L_, int mu_, int off_, int act_) {
+        *this = FlowLayerArgs();
+        wint = wint_; B = B_; L = L_; mu = mu_; off = off_; act = act_;
+    }
+    // layer l of a flow whose expanded weights start at wint0
+    FlowLayerArgs(const double* wint0, int l, int B_, int L_, int act_)
+        : FlowLayerArgs(wint0 + (size_t)l * FLOW_WINT, B_, L_, layer_mu(l), layer_off(l), act_) {}
 };
 int launch_flow_fwd(const FlowLayerArgs& a, hipStream_t s);
 int launch_flow_rev(const FlowLayerArgs& a, hipStream_t s);
@@ -167,7 +178,6 @@ inline int flow_wgrad_nparts(int B, int L, int tpw) {
 // [flow_bwd_train_nparts(B, L)][FLOW_GW_STRIDE]; a.gp_out as launch_flow_bwd_gather.  Built for the shapes 16 x 16 tiles divide with
 // L a power of two (flow_bwd_train_shape); FTHMC_ERR_UNSUPPORTED otherwise: the caller keeps the two-kernel form.
 int launch_flow_bwd_train(const FlowLayerArgs& a, hipStream_t s);
-bool flow_bwd_train_built();          // false in the act'(z1)-recompute build (FT_RECOMP_D1: the fused kernel reads act'(z1) from the stash)
 inline bool flow_bwd_train_shape(int L) { return L >= 32 && (L & (L - 1)) == 0; }
 // items per workgroup: as many as leave one workgroup per CU (256), at most 64
 inline int flow_bwd_train_tpw(int B, int L) {
@@ -244,12 +254,13 @@ template <typename T> struct GenLayerArgsT {
 using GenLayerArgs = GenLayerArgsT<double>;
 int launch_gen_fwd(const GenLayerArgs& a, bool rev, hipStream_t s);
 int launch_gen_bwd(const GenLayerArgs& a, hipStream_t s);
-// the same layer sequences on dual numbers (forward direction only); gw: value and tangent of this layer's weight gradient
-int launch_gen_fwd_dual(const GenLayerArgsT<Dual>& a, hipStream_t s);
-int launch_gen_bwd_dual(const GenLayerArgsT<Dual>& a, hipStream_t s);
+// the same layer sequences on dual numbers (forward direction, no log J: FTHMC_ERR_UNSUPPORTED otherwise); gw: value and tangent
+// of this layer's weight gradient
+int launch_gen_fwd(const GenLayerArgsT<Dual>& a, bool rev, hipStream_t s);
+int launch_gen_bwd(const GenLayerArgsT<Dual>& a, hipStream_t s);
 // seeds of the backward sweeps: gp[b] = coef[b] beta sin P(x[b]) (coef NULL: 1), dual: plus its tangent coef[b] beta cos P P'
 int launch_gen_seed(const double* x, const double* coef, int B, int L, double beta, double* gp, hipStream_t s);
-int launch_gen_seed_dual(const Dual* x, const double* coef, int B, int L, double beta, Dual* gp, hipStream_t s);
+int launch_gen_seed(const Dual* x, const double* coef, int B, int L, double beta, Dual* gp, hipStream_t s);
 // x + eps g as one dual field; the link gradient (adjoint of the plaquette stencil) of the TANGENT of a dual gP field; tangents
 int launch_dual_pack(const double* x, const double* g, Dual* out, size_t n, hipStream_t s);
 int launch_dual_links(const Dual* gp, double* gx, int B, int L, hipStream_t s);
