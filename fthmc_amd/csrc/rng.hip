@@ -3,27 +3,11 @@
 // how the batch is sharded over GPUs (SURVEY 7 "RNG").  Box-Muller in fp64.
 #include "common.h"
 #include "kernels.h"
+#include "rng_common.h"
 
 namespace {
 
-struct u4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u4 philox4x32_10(u4 c, uint32_t k0, uint32_t k1) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(M0, c.x), lo0 = M0 * c.x;
-        const uint32_t hi1 = __umulhi(M1, c.z), lo1 = M1 * c.z;
-        c = u4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += W0; k1 += W1;
-    }
-    return c;
-}
-
-__device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {     // (0, 1]
-    const uint64_t m = (((uint64_t)hi << 32) | lo) >> 11;
-    return ((double)m + 1.0) * (1.0 / 9007199254740992.0);
-}
+using namespace fthmc_rng;
 
 // v[b][0..n) ~ N(0,1) (pairs from one Philox block), u[b] ~ U[0,1)
 __global__ void k_random_momenta(const int64_t* __restrict__ seeds, int n, double* __restrict__ v,
@@ -34,19 +18,17 @@ __global__ void k_random_momenta(const int64_t* __restrict__ seeds, int n, doubl
     const int npair = (n + 1) / 2;
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npair; p += gridDim.x * blockDim.x) {
         const u4 r = philox4x32_10(u4{(uint32_t)p, 0u, 0u, 0u}, k0, k1);
-        const double u1 = u53(r.x, r.y), u2 = u53(r.z, r.w);
-        const double rad = sqrt(-2.0 * log(u1));
-        double sn, cs; sincos(FT_TWO_PI * u2, &sn, &cs);
-        v[(size_t)b * n + 2 * p] = rad * cs;
-        if (2 * p + 1 < n) v[(size_t)b * n + 2 * p + 1] = rad * sn;
+        const normal_pair g(r);
+        v[(size_t)b * n + 2 * p] = g.first();
+        if (2 * p + 1 < n) v[(size_t)b * n + 2 * p + 1] = g.second();
     }
     if (u && blockIdx.x == 0 && threadIdx.x == 0) {
         const u4 r = philox4x32_10(u4{0u, 0u, 1u, 0u}, k0, k1);      // separate counter plane
-        u[b] = 1.0 - u53(r.x, r.y);                                   // [0, 1)
+        u[b] = accept_uniform(r.x, r.y);                              // [0, 1)
     }
 }
 
-// out[b][0..n) ~ U[lo, hi): the prior draw of the reverse-KL training step (MultivariateUniform.sample_n,
+// out[b][0..n) ~ U[lo, hi) on (0, 1) and (-pi, pi), U[lo, hi] in general (include/fthmc_hip.h): the prior draw of the reverse-KL training step (MultivariateUniform.sample_n,
 // fthmc/utils/distributions.py:65-76), two values per Philox block, counter plane 2 (disjoint from the momenta's)
 __global__ void k_random_uniform(const int64_t* __restrict__ seeds, int n, double lo, double hi, double* __restrict__ out) {
     const int b = blockIdx.y;
@@ -56,8 +38,8 @@ __global__ void k_random_uniform(const int64_t* __restrict__ seeds, int n, doubl
     const double w = hi - lo;
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npair; p += gridDim.x * blockDim.x) {
         const u4 r = philox4x32_10(u4{(uint32_t)p, 0u, 2u, 0u}, k0, k1);
-        out[(size_t)b * n + 2 * p] = fma(1.0 - u53(r.x, r.y), w, lo);             // 1 - (0, 1] = [0, 1)
-        if (2 * p + 1 < n) out[(size_t)b * n + 2 * p + 1] = fma(1.0 - u53(r.z, r.w), w, lo);
+        out[(size_t)b * n + 2 * p] = uniform_value(r.x, r.y, lo, w);
+        if (2 * p + 1 < n) out[(size_t)b * n + 2 * p + 1] = uniform_value(r.z, r.w, lo, w);
     }
 }
 

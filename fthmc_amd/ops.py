@@ -378,7 +378,9 @@ def chain_seeds(seed: int, lo: int, B: int, traj: int = 0, counter: Optional[tor
 
 
 def random_uniform(seeds, shape, lo: float, hi: float, out=None):
-    """U[lo, hi) of `shape` = (B, ...) from per-chain int64 seeds: the prior draw of a training step on the device."""
+    """U[lo, hi) of `shape` = (B, ...) from per-chain int64 seeds: the prior draw of a training step on the device.
+    Half-open on (0, 1) and (-pi, pi); on a range whose width is not above |hi| the last rounding can return hi itself
+    (include/fthmc_hip.h, fthmc_random_uniform)."""
     if not seeds.is_cuda or seeds.dtype != torch.int64:
         raise FthmcError('seeds: expected an int64 tensor on the HIP device')
     seeds = seeds.contiguous()

@@ -316,7 +316,13 @@ int fthmc_train_grad(const double* xi, const double* w, const fthmc_arch_t* arch
 
 /* The prior draw of a training step on the device: out[b][0..n) ~ U[lo, hi) from Philox4x32-10 keyed by the per-chain
  * seed (MultivariateUniform.sample_n, fthmc/utils/distributions.py:65-76, called at fthmc/train.py:191 through
- * apply_flow_to_prior, fthmc/utils/samplers.py:40-56).  A chain's draw depends on its seed only, not on the sharding. */
+ * apply_flow_to_prior, fthmc/utils/samplers.py:40-56).  A chain's draw depends on its seed only, not on the sharding.
+ * Each value is t * w + lo rounded ONCE (an fma), with w = hi - lo as fp64 rounds it and t = 1 - k / 2^53 for an integer
+ * 1 <= k <= 2^53, i.e. t in [0, 1 - 2^-53] exactly.  So lo <= out <= hi always, out = lo for t = 0, and out < hi exactly
+ * where the top value's distance from hi, w 2^-53, is more than half the spacing of the doubles below hi.  That holds on
+ * (0, 1) and on the prior's (-pi, pi), and roughly wherever w > |hi| (lo <= 0 <= hi with |lo| not much smaller than hi); it
+ * fails already on (1, 2) or (3, 4), and on (1e6, 1e6 + 1) the draws of the last half spacing below hi come out as hi:
+ * U[lo, hi) is a property of the range, not of the call. */
 int fthmc_random_uniform(const int64_t* seeds, int B, int n_per_chain, double lo, double hi, double* out, void* stream);
 
 /* Per-chain seeds of one trajectory / training step, formed on the device: seeds[b] = the 63-bit SplitMix64 mix of

@@ -1,12 +1,14 @@
-// Test-only device probe (tests/test_device_math_gpu.py): the kernels' own fp64 math helpers (common.h, flow_common.h) and
-// integer index helpers (flow_mfma_common.h), applied elementwise to arrays, exactly as the headers define them -- nothing is
-// copied.  Built by `make -C fthmc_amd/csrc probe` with the kernels' CXXFLAGS (same FP-contraction policy), never linked into
+// Test-only device probe (tests/test_device_math_gpu.py, tests/test_rng_gpu.py): the kernels' own fp64 math helpers (common.h,
+// flow_common.h), integer index helpers (flow_mfma_common.h) and the draws of the random streams from raw words
+// (rng_common.h), applied elementwise to arrays, exactly as the headers define them -- nothing is copied.  Built by
+// `make -C fthmc_amd/csrc probe` with the kernels' CXXFLAGS (same FP-contraction policy), never linked into
 // libfthmc_hip.so.  Every launcher takes HOST arrays, copies them in and out, and returns the first HIP error (0 = success).
 #include <hip/hip_runtime.h>
 #include <utility>
 #include "../../fthmc_amd/csrc/common.h"
 #include "../../fthmc_amd/csrc/flow_common.h"
 #include "../../fthmc_amd/csrc/flow_mfma_common.h"
+#include "../../fthmc_amd/csrc/rng_common.h"
 
 using namespace fthmc_flow;
 
@@ -94,6 +96,31 @@ __global__ void k_stash(int L, int mu, int off, const int* __restrict__ rows, in
 // the block at the far corner of a (1, gy, gz) grid reports in: whether a launch of that extent runs at all
 __global__ void k_grid_corner(int* seen) {
     if (threadIdx.x == 0 && blockIdx.y == gridDim.y - 1 && blockIdx.z == gridDim.z - 1) seen[0] = (int)(blockIdx.y + 1) ^ (int)(blockIdx.z + 1);
+}
+
+// raw Philox blocks: out[k][0..4) = philox4x32_10(ctr[k][0..4), key[k][0..2))
+__global__ void k_philox(const uint32_t* __restrict__ ctr, const uint32_t* __restrict__ key, uint32_t* __restrict__ out, int n) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const fthmc_rng::u4 r = fthmc_rng::philox4x32_10(fthmc_rng::u4{ctr[4 * k], ctr[4 * k + 1], ctr[4 * k + 2], ctr[4 * k + 3]},
+                                                     key[2 * k], key[2 * k + 1]);
+    out[4 * k] = r.x; out[4 * k + 1] = r.y; out[4 * k + 2] = r.z; out[4 * k + 3] = r.w;
+}
+
+// every draw of rng.hip from one block of words w[k][0..4): o[0] = u53(w0, w1), o[1] = u53(w2, w3), (o[2], o[3]) = normal_pair,
+// o[4] = accept_uniform(w0, w1), o[5] = uniform_value(w0, w1, lo, wd), o[6] = uniform_value(w2, w3, lo, wd); o: 7 planes of n
+__global__ void k_draws(const uint32_t* __restrict__ w, double lo, double wd, double* __restrict__ o, int n) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const fthmc_rng::u4 r{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]};
+    const size_t N = (size_t)n;
+    o[k] = fthmc_rng::u53(r.x, r.y);
+    o[N + k] = fthmc_rng::u53(r.z, r.w);
+    const fthmc_rng::normal_pair g(r);
+    o[2 * N + k] = g.first(); o[3 * N + k] = g.second();
+    o[4 * N + k] = fthmc_rng::accept_uniform(r.x, r.y);
+    o[5 * N + k] = fthmc_rng::uniform_value(r.x, r.y, lo, wd);
+    o[6 * N + k] = fthmc_rng::uniform_value(r.z, r.w, lo, wd);
 }
 
 namespace {
@@ -222,6 +249,37 @@ int probe_stash(int L, int mu, int off, const int* rows, int nrows, const int* c
                        o[0], o[1], o[2], o[3]);
     d.launched();
     d.out(act, o[0], ns); d.out(live, o[1], ns); d.out(live2, o[2], ns); d.out(frozen, o[3], ns);
+    return (int)d.err;
+}
+
+// n Philox blocks: ctr [n][4], key [n][2] -> out [n][4]
+int probe_philox(const uint32_t* ctr, const uint32_t* key, uint32_t* out, int n) {
+    if (!ctr || !key || !out || n <= 0) return (int)hipErrorInvalidValue;
+    Dev d;
+    const size_t N = (size_t)n;
+    const uint32_t* dc = d.in(ctr, 4 * N);
+    const uint32_t* dk = d.in(key, 2 * N);
+    uint32_t* o = d.alloc<uint32_t>(4 * N);
+    if (d.err != hipSuccess) return (int)d.err;
+    hipLaunchKernelGGL(k_philox, dim3((n + 255) / 256), dim3(256), 0, 0, dc, dk, o, n);
+    d.launched();
+    d.out(out, o, 4 * N);
+    return (int)d.err;
+}
+
+// the draws of n word blocks (k_draws): words [n][4], out: 7 planes of n doubles; the prior on [lo, lo + w) with w = hi - lo
+// formed here as k_random_uniform forms it
+int probe_draws(const uint32_t* words, double lo, double hi, double* out, int n) {
+    if (!words || !out || n <= 0) return (int)hipErrorInvalidValue;
+    Dev d;
+    const size_t N = (size_t)n;
+    const uint32_t* dw = d.in(words, 4 * N);
+    double* o = d.alloc<double>(7 * N);
+    if (d.err != hipSuccess) return (int)d.err;
+    const double w = hi - lo;
+    hipLaunchKernelGGL(k_draws, dim3((n + 255) / 256), dim3(256), 0, 0, dw, lo, w, o, n);
+    d.launched();
+    d.out(out, o, 7 * N);
     return (int)d.err;
 }
 
