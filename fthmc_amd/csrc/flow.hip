@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void k_flow_layer(FlowLayerArgs A) {
                 double f = 0.0, fp = 0.0;
 #pragma unroll
                 for (int k = 0; k < NMIX; ++k) {
-                    f += ft_wrap(2 * atan(ek[k] * th));
+                    f += ft_round_pm_pi(2 * atan(ek[k] * th));            // monotone: no move of pi to -pi
                     fp += 1.0 / (emk[k] * cs * cs + ek[k] * sn * sn);
                 }
                 f /= NMIX; fp /= NMIX;

@@ -534,7 +534,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
                     fp = 0.0;
 #pragma unroll
                     for (int k = 0; k < NMIX; ++k) {
-                        f += ft_wrap_pm_pi(2 * ft_atan(eo[2 * k] * th));
+                        f += ft_round_pm_pi(2 * ft_atan(eo[2 * k] * th));     // monotone: no move of pi to -pi
                         fp += 1.0 / (eo[2 * k + 1] * cs * cs + eo[2 * k] * sn * sn);
                     }
                     f /= NMIX; fp /= NMIX;

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_gen_transform(const T* __restrict__ x, 
                 fp = 0.0;
                 for (int k = 0; k < K; ++k) {
                     const double es = ft_exp(Zb[(size_t)k * n + s]), ems = ft_rcp(es);
-                    f += ft_wrap_pm_pi(2 * ft_atan(es * tn));
+                    f += ft_round_pm_pi(2 * ft_atan(es * tn));          // monotone: no move of pi to -pi
                     fp += 1.0 / (ems * cs * cs + es * sn * sn);
                 }
                 f /= K; fp /= K;

@@ -252,9 +252,13 @@ def test_train_grad_vs_oracle_random(B, L, nl, beta):
 
 @pytest.mark.parametrize('B,L,nl,act,scale,beta', [(2, 4, 8, 'silu', 1.0, 2.0), (3, 16, 4, 'relu', 1.0, 3.0),
                                                   (2, 28, 3, 'leaky_relu', 1.0, 2.5), (2, 16, 4, 'silu', 4.0, 4.0),
-                                                  (1, 36, 2, 'relu', 3.0, 2.0), (10, 8, 5, 'leaky_relu', 2.0, 2.0)])
+                                                  (1, 36, 2, 'relu', 3.0, 2.0), (10, 8, 5, 'leaky_relu', 2.0, 2.0),
+                                                  # L a power of two >= 32: the multi-tile EXACT forward instances with the
+                                                  # run-time activation (SILU = false) and k_flow_bwd_train on their stash
+                                                  (2, 32, 4, 'relu', 1.0, 3.0), (2, 32, 3, 'leaky_relu', 2.0, 2.5),
+                                                  (2, 32, 8, 'silu', 3.0, 4.0), (1, 64, 2, 'relu', 3.0, 2.0)])
 def test_activations_and_extremes_vs_oracle(B, L, nl, act, scale, beta):
-    """Every activation on lattices of every kind (the smallest one, ragged tiles, a partial block group), weights
+    """Every activation on lattices of every kind (the smallest one, ragged tiles, a partial block group, exact tiles), weights
     scaled up until the sigmoids saturate and the transform's slopes get steep, plaquettes pinned near +-pi:
     forward, log det, force and the training gradient against the oracle."""
     gen = torch.Generator().manual_seed(4242 + L + nl)
@@ -277,6 +281,28 @@ def test_activations_and_extremes_vs_oracle(B, L, nl, act, scale, beta):
     for li in range(nl):
         for pi in range(6):
             close(gws[li][pi], grads[li][pi], rtol=1e-7, atol=1e-9 * max(gmax, 1.0))
+
+
+@pytest.mark.parametrize('act', ['relu', 'leaky_relu'])
+def test_reverse_with_activations_exact_tiles(act):
+    """The REV twins of the exact-tile instances with a run-time activation: L = 32 (two tiles per side), all eight (mu, off);
+    rev(fwd(x)) against x and -log J at the tolerances of test_layers_golden, and against the oracle's bisection at its own."""
+    gen = torch.Generator().manual_seed(3232)
+    B, L = 2, 32
+    flow = R.default_flow(8, gen)
+    x = (torch.rand(B, 2, L, L, generator=gen, dtype=torch.float64) * 2 - 1) * math.pi
+    for li, w in enumerate(flow):
+        mu, off = R.layer_mu_off(li)
+        wl = W([w])
+        y, lj = ops.flow_layer_fwd(x.cuda(), wl, mu, off, act)
+        yo, ljo = R.layer_forward(x, w, mu, off, act)
+        angle_close(y, yo, atol=1e-12); close(lj, ljo, atol=1e-12)
+        xr, ljr = ops.flow_layer_rev(y, wl, mu, off, act, tol=1e-13)
+        angle_close(xr, x, atol=1e-9)                       # exact inverse, not the 1e-6 bisection
+        close(ljr, -lj, atol=1e-8)
+        xo, ljro = R.layer_reverse(y.cpu(), w, mu, off, act)
+        angle_close(xr, xo, atol=5e-6)                      # reference bisection tolerance
+        close(ljr, ljro, atol=5e-5)
 
 
 def test_config5_shape_properties():
