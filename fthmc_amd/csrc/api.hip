@@ -227,7 +227,15 @@ int layer_backward_stash(const WS& W, FlowLayerArgs a, double* gw, hipStream_t s
     return FTHMC_OK;
 }
 
+// a forward layer whose output field IS its input field updates only the links it changes, where the kernel has that instance
+inline bool layer_inplace(const Ctx& C, int L, int act) { return C.mfma && !C.gen() && flow_fwd_inplace_ok(L, act); }
+
 // Forward sweep x -> X[0..nl-1] (X[l] = output of layer l).  logdet (device [B]) optional.
+// MFMA variant on the exact tiles (flow_fwd_inplace_ok): no checkpoints -- layer 0 maps the caller's field (never written) into
+// the LAST region of w.X, layers 1 .. nl - 1 update that region in place, each touching only the links it changes (flow_fwd.hip
+// INPL); phys_field() names the same region either way.  Nothing behind such a sweep reads a checkpoint: the stash backward
+// kernels (flow_bwd_gather.hip, flow_bwd_train.hip, flow_wgrad.hip) never dereference FlowLayerArgs::x.  The VALU variant
+// (its backward recomputes each layer from X[l - 1]), the ragged and non-silu shapes and the plain kernels keep the chain.
 // parts_only: leave the log J partials of every layer in w.lj_part ([layer][chain][tile]) and skip the summing launch (the
 // caller folds them into its own reduction: launch_traj_energy); tuned kernels only.
 int sweep_forward(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, int act, double* logdet,
@@ -242,6 +250,7 @@ int sweep_forward(const Ctx& C, const double* x, const WS& w, int nl, int B, int
         }
         return FTHMC_OK;
     }
+    const bool inplace = layer_inplace(C, L, act);
     for (int l = 0; l < nl; ++l) {
         FlowLayerArgs a(w.wint, l, B, L, act);
         a.stash = stash ? w.stash + (size_t)l * flow_stash_doubles(B, L, train) : nullptr;
@@ -251,6 +260,7 @@ int sweep_forward(const Ctx& C, const double* x, const WS& w, int nl, int B, int
         a.stash_far = stash && (size_t)(nl - 1 - l) * flow_stash_doubles(B, L, train) * sizeof(double) >= STASH_FAR_BYTES ? 1 : 0;
         a.x = l == 0 ? x : w.X + (size_t)(l - 1) * w.n2;
         a.y = w.X + (size_t)l * w.n2;
+        if (inplace) { a.y = w.X + (size_t)(nl - 1) * w.n2; if (l > 0) { a.x = a.y; a.inplace = 1; } }
         // logJ partials of all layers side by side, summed by ONE launch behind the sweep (layer by layer, in order)
         a.logj_part = (logdet || parts_only) ? w.lj_part + (size_t)l * B * flow_fwd_geom(C.mfma).ntiles(L) : nullptr;
         FT_TRY(flow_fwd(C, a, s));
@@ -263,7 +273,7 @@ inline const double* phys_field(const double* x, const WS& w, int nl) {
     return nl == 0 ? x : w.X + (size_t)(nl - 1) * w.n2;
 }
 
-// S_eff (and friends) of x; leaves the checkpoints in w.X
+// S_eff (and friends) of x; leaves the flowed field (phys_field) in w.X
 int eval_action(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, int act, double beta,
                 double* S_eff, double* logdet, double* plaq, double* Q, hipStream_t s) {
     double* ld = logdet ? logdet : w.scal + (size_t)SC_LOGDET * B;
@@ -312,7 +322,7 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
     const bool one_reduction = fused && (size_t)nl * npf <= w.gw_rows && (size_t)nl * flow_reduce_groups(npf) <= w.gw_tmp_rows;
     for (int l = nl - 1; l >= 0; --l) {
         FlowLayerArgs a(w.wint, l, B, L, act);
-        a.x = l == 0 ? x : w.X + (size_t)(l - 1) * w.n2;
+        if (!stash) a.x = l == 0 ? x : w.X + (size_t)(l - 1) * w.n2;  // the VALU backward recomputes the layer; the stash kernels read no field
         a.up_gp = gcur;
         a.glogj_const = glogj;
         a.gp_part = w.gp_part;
@@ -599,6 +609,7 @@ int fthmc_flow_layer_fwd(const double* x, const double* w, const fthmc_arch_t* a
     FT_TRY(use_weights(C, w, 1, W, s));
     FlowLayerArgs a(W.wint, B, L, mu, off, act);
     a.x = x; a.y = y;
+    a.inplace = y == x && layer_inplace(C, L, act);
     return layer_forward(C, W, 0, a, false, logJ);
 }
 
@@ -732,6 +743,7 @@ int fthmc_flow_layer_fwd_stash(const double* x, const double* w, const fthmc_arc
     FT_TRY(use_weights(C, w, 1, W, s));
     FlowLayerArgs a(W.wint, B, L, mu, off, act);
     a.x = x; a.y = y; a.stash = stash; a.stash_h = 1;
+    a.inplace = y == x && layer_inplace(C, L, act);
     return layer_forward(C, W, 0, a, false, logJ);
 }
 
@@ -999,6 +1011,11 @@ int fthmc_time_kernel(int kind, const double* x, const double* w, const fthmc_ar
             a.stash = W.stash;
             a.logj_part = nullptr;       // ... and asks for no log J: exactly what a layer of a force sweep launches (the SWEEP / FS instances)
             FT_TRY(launch_flow_fwd_mfma(a, s));
+            // the forward as layers 1 .. nl - 1 of a sweep launch it: in place on the work buffer (sweep_forward)
+            if (kind == 0 && flow_fwd_inplace_ok(L, act)) {
+                if (hipMemcpyAsync(W.X, x, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+                a.x = W.X; a.inplace = 1;
+            }
         }
     } else {
         int64_t* seeds = reinterpret_cast<int64_t*>(W.scal);             // B int64 seeds = 0 .. (any values do)
@@ -1059,6 +1076,10 @@ int fthmc_profile_stages(int kind, const double* x, const double* w, const fthmc
     a.x = x; a.y = W.X; a.logj_part = train ? W.lj_part : nullptr;                       // kind 0, 1: the launch of a force sweep
     a.up_gp = W.gp; a.glogj_const = -1.0; a.gp_part = W.gp_part; a.gp_out = W.gp2; a.dbg = dbg;
     if (kind == 0) a.stash = W.stash;             // the forward as a force sweep launches it: with the activation stash, without log J
+    if (kind == 0 && flow_fwd_inplace_ok(L, act)) {                // ... in place on the work buffer, as layers 1 .. nl - 1 are
+        if (hipMemcpyAsync(W.X, x, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+        a.x = W.X; a.inplace = 1;
+    }
     if (kind >= 1) {                              // stash backward needs the forward's stash first
         a.stash = W.stash; a.stash_h = train ? 1 : 0; a.gw_part = W.gw_part; a.gz = train ? W.gz : nullptr; a.dbg = nullptr;
         FT_TRY(launch_flow_fwd_mfma(a, s));

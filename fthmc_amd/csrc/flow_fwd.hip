@@ -68,7 +68,19 @@ template <int TR, int TC, int MU, bool AL> struct SmemF {
 // of an ACTION sweep (the H1 sweep of a trajectory, ft_action: link field in and out, log J, no stash).  SWEEP = 4: a layer of a
 // TRAINING sweep (fthmc_train_grad: stash with h1 / h2, log J).  5, 6: SWEEP = 1, 4 with NON-TEMPORAL stash stores, for a stash
 // nobody finds in a cache again (launch_fwd: a layer's stash beyond NT_MIN_BYTES).  0: whatever the argument block says.
-template <int TR, int TC, bool FASTW, bool REV, int MU, bool EXACT, bool SILU, int SWEEP>
+// INPL (sweep instances only, FlowLayerArgs::inplace): the layer runs IN PLACE on its field, y == x (layers 1 .. nl - 1 of a sweep,
+// api.hip sweep_forward), and touches only the links it changes: the 64 links of direction MU at the tile's active sites.  The
+// lanes of wave 0 form the active plaquettes in stage 0 (the task list starts with the active sites then), keep their link in a
+// register and store its update from the finish stage themselves: no load and no store of the other 448 links, no delta through
+// LDS, no barrier behind the transform's combine -- waves 1 .. 7 leave at the transform's barrier.
+// Race-free, by the stripe pattern (period 4 across the lines; the masks of tests/test_tile_maps.py and tests/golden/masks.npz):
+// the layer updates link MU of the sites on the lines of class 0.  That link is part of two plaquettes: the site's own (class 0,
+// ACTIVE) and the one on the line before it (class 3, PASSIVE).  A workgroup reads the FROZEN plaquettes (classes 1, 2) of its window, none
+// of which holds a link this layer writes, and the active plaquettes of its OWN sites, each of which holds exactly one such link,
+// its own site's: the lane that forms the plaquette is the only one that reads that link and the only one that writes it, after the
+// read.  Passive plaquettes, and active plaquettes of other tiles, are never formed.  So no workgroup reads a link another one
+// writes, in whatever order the tiles of a launch run.
+template <int TR, int TC, bool FASTW, bool REV, int MU, bool EXACT, bool SILU, int SWEEP, bool INPL = false>
 __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const double* hx, const double* hw, double* hy, double* hstash, double* hlogj,
                                                                           int hB, int hL, unsigned hoa, FlowLayerArgs A0) {
     FlowLayerArgs A = A0;
@@ -76,6 +88,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     A.off = (int)(hoa & 0xffu); A.act = (int)((hoa >> 8) & 0xffu);
     constexpr bool FS = SWEEP == 1 || SWEEP == 2 || SWEEP == 5, ES = SWEEP == 3, TS = SWEEP == 4 || SWEEP == 6, SW = FS || ES || TS;
     constexpr bool NTS = SWEEP == 5 || SWEEP == 6;                    // stash stores with the non-temporal hint (launch_fwd: big stashes)
+    static_assert(!INPL || (SW && EXACT && !REV), "in place: the sweep instances of the exact tiles");
     const bool has_pout = !SW && (hoa & FWD_HAS_POUT) != 0, has_pin = !SW && (hoa & FWD_HAS_PIN) != 0;
     const bool has_dbg = (SWEEP == 0 || SWEEP == 2) && (hoa & FWD_HAS_DBG) != 0;
     const bool has_stash = FS || TS || (!ES && A.stash != nullptr), has_y = SW || A.y != nullptr;
@@ -161,7 +174,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
     }
     // the tile's own links for the final link update: issued now, consumed in the last stage
     double xv0 = 0.0, xv1 = 0.0;
-    if ((has_y || has_pout) && tid < N3) {
+    if (!INPL && (has_y || has_pout) && tid < N3) {
         const int r = fdiv<TC>(tid), c = tid - r * TC;
         if (EXACT || (i0 + r < L && j0 + c < L)) {
             const unsigned at = (unsigned)(mul24(gi(r), L) + gj(c));
@@ -190,18 +203,21 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         const int ps = AL ? TOFF : (off == 3 ? -1 : off);                  // first line of the first frozen pair (class 1: x = off mod 4)
         int r = 0, c = 0;
         bool fz = false, ao = false;
-        if (tid < NFT) {
-            const int a = fdiv<NFL>(tid), k = tid - a * NFL;
+        // in place: the active sites first, so that active site a is lane a of wave 0, the lane that updates its link at the end
+        static_assert(!INPL || NA == 64, "in place: the active sites are the lanes of wave 0");
+        const int tk = !INPL ? tid : tid < NA ? tid + NFT : tid < NFT + NA ? tid - NA : tid;
+        if (tk < NFT) {
+            const int a = fdiv<NFL>(tk), k = tk - a * NFL;
             const int x = ps + 4 * (k >> 1) + (k & 1);
             fz = (unsigned)x < (unsigned)(AL ? R0A - 2 : R0A);
             r = mu == 0 ? a : x; c = mu == 0 ? x : a;
-        } else if (tid < NFT + NA) {
-            const int a = tid - NFT;
+        } else if (tk < NFT + NA) {
+            const int a = tk - NFT;
             r = 3 + (mu == 0 ? a / (TC / 4) : offt + 4 * (a / TC));
             c = 3 + (mu == 0 ? offt + 4 * (a % (TC / 4)) : a % TC);
             ao = true;
-        } else if (tid < NFT + NA + NCC) {
-            const int k = tid - (NFT + NA);
+        } else if (tk < NFT + NA + NCC) {
+            const int k = tk - (NFT + NA);
             if (AL) {
                 const int x = 16 + 3 * (k & 1), al = 16 + (k >> 1), at = mu == 0 ? al * R0C + x : x * R0C + al;
                 sIn[at] = 1.0; sIn[PS0 + at] = 0.0;
@@ -214,8 +230,13 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         if (fz || ao) {
             const int iL = mul24(wrap_line<FASTW, EXACT>(i0 - 3 + r, L, fastw), L), ipL = mul24(wrap_line<FASTW, EXACT>(i0 - 2 + r, L, fastw), L);
             const int j = wrap_line<FASTW, EXACT>(j0 - 3 + c, L, fastw), jp = wrap_line<FASTW, EXACT>(j0 - 2 + c, L, fastw);
-            const double p = pin ? ldu(pin, (unsigned)(iL + j))
-                                 : ldu(x0, (unsigned)(iL + j)) - ldu(x1, (unsigned)(iL + j)) - ldu(x0, (unsigned)(iL + jp)) + ldu(x1, (unsigned)(ipL + j));
+            double p;
+            if (pin) p = ldu(pin, (unsigned)(iL + j));
+            else {
+                const double l0 = ldu(x0, (unsigned)(iL + j)), l1 = ldu(x1, (unsigned)(iL + j));
+                p = l0 - l1 - ldu(x0, (unsigned)(iL + jp)) + ldu(x1, (unsigned)(ipL + j));
+                if (INPL && ao) xv0 = mu == 0 ? l0 : l1;              // the link this lane updates (wave 0: tk - NFT = lane)
+            }
             const int at = r * R0C + c;
             // one sincos per task: of P where the plaquette is frozen (the net input), of P / 2 at an own active site (the
             // transform needs it) -- left in the plaquette plane next to P, in the two slots of the following lines
@@ -631,6 +652,11 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
             for (int k = 0; k < NMIX; ++k) { ysum += sT2[(k * TQ) * NAS + (lane & (NAS - 1))]; si += sT2[(k * TQ + 1) * NAS + (lane & (NAS - 1))]; }
             const double tval = sP[(ar + 3) * R0C + ac + 3 + 3 * (mu == 0 ? 1 : R0C)];
             const double newP = ft_wrap(ysum / NMIX + tval);
+            if (INPL) {                                            // the link update, by the lane that loaded the link (stage 0)
+                const double d = newP - Pa;
+                double* ym = uniform_at(A.y, 2u * bn + (mu == 0 ? 0u : (unsigned)n));
+                stu(ym, (unsigned)(mul24(ai, L) + aj), mu == 0 ? ft_wrap(d + xv0) : ft_wrap(-d + xv0));
+            } else
             if (avalid) sDL[ar * TC + ac] = has_pout ? newP : newP - Pa;
             if (want_logj) {                                       // force sweeps do not ask for log J
                 const double lj = avalid ? log(si) - log((double)NMIX) : 0.0;
@@ -638,8 +664,8 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
                 if (lane == 0) A.logj_part[(size_t)b * ntiles + tile] = tot;
             }
         }
-        lds_barrier();
-        if (has_y && tid < N3) {
+        if (!INPL) lds_barrier();
+        if (!INPL && has_y && tid < N3) {
             const int r = fdiv<TC>(tid), c = tid - r * TC;
             const int i = gi(r), j = gj(c);
             if (EXACT || (i < L && j < L)) {
@@ -672,12 +698,15 @@ namespace {
 // the silu / other-activation instances of a shape, generic in everything else
 #define FWD_LAUNCH(...) do { if (a.act != FTHMC_ACT_SILU) FWD_LAUNCH_(__VA_ARGS__, false, 0); else FWD_LAUNCH_(__VA_ARGS__, true, 0); } while (0)
 // ... and with the sweep specializations (SWEEP template parameter): the forward map on the tiled-exactly shapes, silu
+// ... each of them also IN PLACE (a.inplace: layers 1 .. nl - 1 of a sweep); an instance without the specialization runs a.y == a.x
+// with the full copy, which is just as safe (the links it rewrites unchanged are rewritten with their own values)
+#define FWD_LAUNCH_SW(n, ...) do { if (a.inplace) FWD_LAUNCH_(__VA_ARGS__, true, n, true); else FWD_LAUNCH_(__VA_ARGS__, true, n); } while (0)
 #define FWD_LAUNCH_SWEEPS(...) do { if (a.act != FTHMC_ACT_SILU) FWD_LAUNCH_(__VA_ARGS__, false, 0); \
-                             else if (force_sweep && !a.dbg && nt_stash) FWD_LAUNCH_(__VA_ARGS__, true, 5); \
-                             else if (force_sweep && !a.dbg) FWD_LAUNCH_(__VA_ARGS__, true, 1); \
-                             else if (force_sweep) FWD_LAUNCH_(__VA_ARGS__, true, 2); else if (action_sweep) FWD_LAUNCH_(__VA_ARGS__, true, 3); \
-                             else if (train_sweep && nt_stash) FWD_LAUNCH_(__VA_ARGS__, true, 6); \
-                             else if (train_sweep) FWD_LAUNCH_(__VA_ARGS__, true, 4); \
+                             else if (force_sweep && !a.dbg && nt_stash) FWD_LAUNCH_SW(5, __VA_ARGS__); \
+                             else if (force_sweep && !a.dbg) FWD_LAUNCH_SW(1, __VA_ARGS__); \
+                             else if (force_sweep) FWD_LAUNCH_SW(2, __VA_ARGS__); else if (action_sweep) FWD_LAUNCH_SW(3, __VA_ARGS__); \
+                             else if (train_sweep && nt_stash) FWD_LAUNCH_SW(6, __VA_ARGS__); \
+                             else if (train_sweep) FWD_LAUNCH_SW(4, __VA_ARGS__); \
                              else FWD_LAUNCH_(__VA_ARGS__, true, 0); } while (0)
 template <bool REV> void launch_fwd(const fthmc::FlowLayerArgs& a, dim3 grid, hipStream_t s) {
     constexpr int TR = fthmc::MF_FWD_TR, TC = fthmc::MF_FWD_TC;
@@ -716,6 +745,7 @@ int get_flow_variant() { return g_variant; }
 int launch_flow_fwd_mfma(const FlowLayerArgs& a, hipStream_t s) {
     if (!flow_shape_ok(a.B, a.L, a.off)) return FTHMC_ERR_ARG;
     if (!flow_stash_fits32(a.B, a.L, a.stash_h != 0)) return FTHMC_ERR_UNSUPPORTED;                  // 32-bit plane offsets (uniform_at)
+    if (a.inplace && a.y != a.x) return FTHMC_ERR_ARG;                                               // in place means y == x
     // 16 x 16 tiles, three workgroups per CU (SmemF)
     const dim3 grid = xcd_grid(a.B, (a.L + MF_FWD_TR - 1) / MF_FWD_TR, (a.L + MF_FWD_TC - 1) / MF_FWD_TC);
     launch_fwd<false>(a, grid, s);

@@ -116,6 +116,8 @@ struct FlowLayerArgs {
     double* stash;           // optional: this layer's activation stash (MFMA forward writes, stash backward reads)
     int stash_h;             // forward: also stash h1, h2 (training: the weight gradients need them)
     int stash_far;           // forward: this layer's stash will have left the caches when the backward comes for it (sweep_forward)
+    int inplace;             // forward, MFMA variant: y == x and the layer loads and stores only the links it changes (flow_fwd.hip INPL:
+                             // the sweep instances of the exact tiles; any other instance copies the field onto itself)
     double* gz;              // training: gradients wrt the pre-activations of this layer, written by the backward kernel at
                              // every tile's own sites and read by k_flow_wgrad: per chain gz2 [n][8], gz1 [n][8]
                              // (channel-minor), g_out [n/4][4] (dL/ds_0, dL/ds_1, dL/dt, 0 at the active sites, compact)
@@ -142,6 +144,11 @@ int launch_flow_rev(const FlowLayerArgs& a, hipStream_t s);
 int launch_flow_bwd(const FlowLayerArgs& a, bool wgrad, hipStream_t s);
 // flow_fwd.hip: MFMA forward (same arguments and results as launch_flow_fwd; optionally writes the stash)
 int launch_flow_fwd_mfma(const FlowLayerArgs& a, hipStream_t s);
+// the shapes whose sweeps run layers 1 .. nl - 1 in place (api.hip sweep_forward): the exact tiles of flow_fwd.hip (16 x 16 tiles
+// that divide a power-of-two lattice) with the activation its sweep instances are compiled for
+inline bool flow_fwd_inplace_ok(int L, int act) {
+    return L % MF_FWD_TR == 0 && L % MF_FWD_TC == 0 && (L & (L - 1)) == 0 && act == 0 /* FTHMC_ACT_SILU */;
+}
 // the inverse layer on the same kernel (conv net unchanged, scalar map inverted by safeguarded Newton)
 int launch_flow_rev_mfma(const FlowLayerArgs& a, hipStream_t s);
 // flow_bwd_gather.hip: backward from the stash in gather form: a tile produces the complete

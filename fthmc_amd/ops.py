@@ -470,9 +470,10 @@ def _w1(w, x, arch=None):
     return w, _arch(a), a
 
 
-def flow_layer_fwd(x, w, mu: int, off: int, act='silu', arch=None):
+def flow_layer_fwd(x, w, mu: int, off: int, act='silu', arch=None, inplace=False):
+    """-> (y, logJ); inplace: y IS x (a contiguous float64 device tensor, updated where the layer changes it)."""
     x = _field(x); w, ap, a = _w1(w, x, arch); B, _, L, _ = x.shape
-    y = torch.empty_like(x); logJ = torch.empty(B, dtype=x.dtype, device=x.device)
+    y = x if inplace else torch.empty_like(x); logJ = torch.empty(B, dtype=x.dtype, device=x.device)
     ws, nb = _ws(x, B, L, 1, arch=a)
     check(_lib.load().fthmc_flow_layer_fwd(_p(x), _p(w), ap, B, L, int(mu), int(off), act_code(act), _p(y), _p(logJ),
                                            ws, nb, _stream(x)), 'fthmc_flow_layer_fwd')
@@ -490,15 +491,20 @@ def flow_layer_bwd(x, w, gy, glogJ, mu: int, off: int, act='silu', need_gw=False
     return gx, gw
 
 
-def flow_layer_fwd_stash(x, w, mu: int, off: int, act='silu', arch=None):
+def flow_layer_fwd_stash(x, w, mu: int, off: int, act='silu', arch=None, inplace=False, stash=None):
     """-> (y, logJ, stash): the layer forward that keeps its activations for `flow_layer_bwd_stash` (stash is None where
-    the kernels have none -- the VALU variant: use flow_layer_bwd then)."""
+    the kernels have none -- the VALU variant: use flow_layer_bwd then); inplace: as in `flow_layer_fwd`; stash: a float64
+    device tensor of fthmc_layer_stash_bytes / 8 entries to write into (the kernel leaves the entries no backward reads as
+    they are)."""
     x = _field(x); w, ap, a = _w1(w, x, arch); B, _, L, _ = x.shape
     nbytes = int(_lib.load().fthmc_layer_stash_bytes(ap, B, L))
     if nbytes == 0:
-        return (*flow_layer_fwd(x, w, mu, off, act, arch=a), None)
-    y = torch.empty_like(x); logJ = torch.empty(B, dtype=x.dtype, device=x.device)
-    stash = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+        return (*flow_layer_fwd(x, w, mu, off, act, arch=a, inplace=inplace), None)
+    y = x if inplace else torch.empty_like(x); logJ = torch.empty(B, dtype=x.dtype, device=x.device)
+    if stash is None:
+        stash = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    elif stash.dtype != torch.float64 or not stash.is_cuda or not stash.is_contiguous() or stash.numel() != nbytes // 8:
+        raise FthmcError(f'stash: expected a contiguous float64 device tensor of {nbytes // 8} entries')
     ws, nb = _ws(x, B, L, 1, arch=a)
     check(_lib.load().fthmc_flow_layer_fwd_stash(_p(x), _p(w), ap, B, L, int(mu), int(off), act_code(act), _p(y), _p(logJ),
                                                  _p(stash), ws, nb, _stream(x)), 'fthmc_flow_layer_fwd_stash')
