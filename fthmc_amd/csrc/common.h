@@ -140,10 +140,8 @@ __device__ __forceinline__ double ft_wrap_pm_pi(double x) {
     return r - FT_PI;
 }
 
-// A mixture component 2 atan(.) INSIDE the inverse's Newton loop: ft_wrap_pm_pi's rounding (so that the loop solves the map the
-// forward rounds) without its move of pi to -pi.  At an iterate where e^{s} tan(x/2) is beyond ~1e16 the atan rounds to pi/2
-// exactly; read as -pi the error changes sign, the bracket closes on the wrong side and the root is lost (met with s = 10 at a
-// target 2e-13 below pi: the start itself saturates, the loop ended at pi, 4.7e-9 off).  Unwrapped the mean is monotone on [-pi, pi].
+// ft_wrap_pm_pi's rounding without its move of pi to -pi: a mixture component inside the inverse's Newton loop (mix_inverse,
+// flow_transform.h, which says why)
 __device__ __forceinline__ double ft_round_pm_pi(double x) { return (x + FT_PI) - FT_PI; }
 
 __device__ __forceinline__ int ft_modL(int v, int L) {   // v >= -L

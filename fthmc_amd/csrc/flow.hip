@@ -279,7 +279,9 @@ __global__ __launch_bounds__(256) void k_flow_layer(FlowLayerArgs A) {
     }
 
     if (MODE == 3) {
-        // reverse: solve mean_k y_k(x) = wrap(P' - t) per active site (layers.py:373-396)
+        // reverse: solve mean_k y_k(x) = wrap(P' - t) per active site (layers.py:373-396).  Deliberately a second statement of the
+        // loop (ocml's exp / sin / cos / tan / atan, started at 0): the first one is mix_inverse, flow_transform.h, and
+        // tests/test_steep_inverse_gpu.py holds the two against each other
         if (wave == 0) {
             const double Pn = sP[(ar + 3) * R0 + ac + 3];
             double sk[NMIX], ek[NMIX], emk[NMIX];

@@ -23,6 +23,7 @@
 // Reference: autograd of GaugeEquivCouplingLayer.forward (fthmc/utils/layers.py:196-202,348-371)
 // as used by ft_force (qed_helpers.py:226-242) and train_step (train.py:162-228).
 #include "flow_mfma_common.h"
+#include "flow_transform.h"
 
 namespace {
 
@@ -267,27 +268,20 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 4) void k_flow_bwd_gather(const doub
 #pragma unroll
     for (int k = 0; k < NWC; ++k) if (tid + k * NT < LB_SIZE) sW[tid + k * NT] = wsw[k];
     if (ttask) {
-        // adjoint of the tan-mixture transform (layers.py:66-90) from the forward's coefficients
+        // adjoint of the tan-mixture transform from the forward's coefficients (MixAdjoint, flow_transform.h)
         const double gdelta = has_uplink ? (mu == 0 ? ag[0] : -ag[0]) : ag[0] - ag[1];
         const int at = tr3 * W3C + tc3;
-        double csum = 0.0, esum = 0.0;
+        const MixAdjoint<double> adj(gdelta, cb, tcv, NMIX);
 #pragma unroll
-        for (int k = 0; k < NMIX; ++k) { csum += tcv[4 * k + 2]; esum += tcv[4 * k + 3]; }
-        const double tsum = NMIX * csum;                                 // sum_k 1 / D_k
-        double rs = __builtin_amdgcn_rcp(tsum);
-        rs = fma(fma(-tsum, rs, 1.0), rs, rs);
-        rs = fma(fma(-tsum, rs, 1.0), rs, rs);
-        const double cbr = cb * rs;
-#pragma unroll
-        for (int k = 0; k < NMIX; ++k) sGO[k * N3W + at] = gdelta * tcv[4 * k] + cbr * tcv[4 * k + 1];   // dL/ds_k
+        for (int k = 0; k < NMIX; ++k) sGO[k * N3W + at] = adj.gs(tcv[4 * k], tcv[4 * k + 1]);   // dL/ds_k
         sGO[NMIX * N3W + at] = gdelta;                                   // dL/dt
         const int r = tr3 - 3, c = tc3 - 3;
         if ((unsigned)r < (unsigned)TR && (unsigned)c < (unsigned)TC) {
-            sDir[r * TC + c] = gdelta * (csum - 1.0) - cbr * esum;
+            sDir[r * TC + c] = adj.dir();
             if (goo && r < rmax && c < cmax) {                           // training: g_out of the own active sites
                 static_assert(NMIX == 2, "g_out record: dL/ds_0, dL/ds_1, dL/dt, 0");
                 double* po = goo + 4 * (size_t)stash_active_idx(i0 + r, j0 + c, L, mu);
-                *reinterpret_cast<double2_t*>(po) = double2_t{gdelta * tcv[0] + cbr * tcv[1], gdelta * tcv[4] + cbr * tcv[5]};
+                *reinterpret_cast<double2_t*>(po) = double2_t{adj.gs(tcv[0], tcv[1]), adj.gs(tcv[4], tcv[5])};
                 *reinterpret_cast<double2_t*>(po + 2) = double2_t{gdelta, 0.0};
             }
         }

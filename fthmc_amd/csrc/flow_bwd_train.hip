@@ -45,6 +45,7 @@
 // two-kernel form.  Reference: loss.backward() of fthmc/train.py:191-210 through GaugeEquivCouplingLayer.forward
 // (fthmc/utils/layers.py:196-202,348-371) and make_conv_net (:138-167).
 #include "flow_mfma_common.h"
+#include "flow_transform.h"
 
 namespace {
 
@@ -370,24 +371,17 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
 
         // ---- stage 1: transform adjoint -> g_out; the net-input window into LDS -----------------------------------
         if (ttask) {
-            // adjoint of the tan-mixture transform (layers.py:66-90) from the forward's coefficients
+            // adjoint of the tan-mixture transform from the forward's coefficients (MixAdjoint, flow_transform.h)
             const double gdelta = ag[0] - ag[1];
             const int at = tr3 * W3C + tc3;
-            double csum = 0.0, esum = 0.0;
-#pragma unroll
-            for (int k = 0; k < NMIX; ++k) { csum += tcv[4 * k + 2]; esum += tcv[4 * k + 3]; }
-            const double tsum = NMIX * csum;                                 // sum_k 1 / D_k
-            double rs = __builtin_amdgcn_rcp(tsum);
-            rs = fma(fma(-tsum, rs, 1.0), rs, rs);
-            rs = fma(fma(-tsum, rs, 1.0), rs, rs);
-            const double cbr = cb * rs;
+            const MixAdjoint<double> adj(gdelta, cb, tcv, NMIX);
             static_assert(NMIX == 2, "g_out record: dL/ds_0, dL/ds_1, dL/dt");
-            const double gs0 = gdelta * tcv[0] + cbr * tcv[1], gs1 = gdelta * tcv[4] + cbr * tcv[5];
+            const double gs0 = adj.gs(tcv[0], tcv[1]), gs1 = adj.gs(tcv[4], tcv[5]);
             sGO[at] = gs0; sGO[N3W + at] = gs1;                              // dL/ds_k
             sGO[2 * N3W + at] = gdelta;                                      // dL/dt
             const int r = tr3 - 3, c = tc3 - 3;
             if ((unsigned)r < (unsigned)TR && (unsigned)c < (unsigned)TC) {
-                sDir[r * TC + c] = gdelta * (csum - 1.0) - cbr * esum;
+                sDir[r * TC + c] = adj.dir();
                 // the own active sites once more, compact, in k_flow_wgrad's task order: conv3's weight gradient reads them in pairs
                 const int a = mu == 0 ? r * (TC / 4) + ((c - off) >> 2) : ((r - off) >> 2) * TC + c;
                 sGOC[a] = gs0; sGOC[NA + a] = gs1; sGOC[2 * NA + a] = gdelta;

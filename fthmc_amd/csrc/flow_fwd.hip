@@ -18,6 +18,7 @@
 // Measured on MI355X (tools/microbench): fp64 MFMA and fp64 VALU share one DP pipe, so the matrix path
 // buys issue efficiency and register-free operands, not extra flops.
 #include "flow_mfma_common.h"
+#include "flow_transform.h"
 
 namespace {
 
@@ -524,9 +525,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
 #endif
 
     if (REV) {
-        // ---- inverse of the tan-mixture transform: solve mean_k y_k(P) = wrap(P' - t) per active site by
-        //      safeguarded Newton (the map is monotone with derivative mean_k 1/D_k; the reference bisects
-        //      to a global 1e-6, layers.py:294-320), started from the target (s ~ 0: identity) ------------
+        // ---- inverse of the tan-mixture transform: solve mean_k y_k(P) = wrap(P' - t) per active site (mix_inverse) ------------
         if (wave == 0) {
             double dl = 0.0, lj = 0.0, xsol = 0.0;
             if (alane) {
@@ -544,29 +543,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
 #pragma unroll
                 for (int k = 0; k < NMIX; ++k) { ea[2 * k] = sk[k]; ea[2 * k + 1] = -sk[k]; }
                 ft_expN<2 * NMIX>(ea, eo);
-                const double target = ft_wrap(Pn - tval);
-                double lo = -FT_PI, hi = FT_PI, xs = target, fp = 1.0;
-                bool done = false;
-                for (int it = 0; it < 200 && !done; ++it) {
-                    double sn, cs;
-                    ft_sincos(xs / 2, &sn, &cs);
-                    const double th = sn / cs;
-                    double f = 0.0;
-                    fp = 0.0;
-#pragma unroll
-                    for (int k = 0; k < NMIX; ++k) {
-                        f += ft_round_pm_pi(2 * ft_atan(eo[2 * k] * th));     // monotone: no move of pi to -pi
-                        fp += 1.0 / (eo[2 * k + 1] * cs * cs + eo[2 * k] * sn * sn);
-                    }
-                    f /= NMIX; fp /= NMIX;
-                    const double err = target - f;
-                    if (fabs(err) <= A.tol) { done = true; break; }
-                    if (err > 0) lo = xs; else hi = xs;
-                    double xn = xs + err / fp;
-                    if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
-                    if (xn == xs) done = true;
-                    xs = xn;
-                }
+                double fp;
+                const double xs = mix_inverse(ft_wrap(Pn - tval), NMIX, A.tol,
+                                              [&](int k) { return ExpPair{eo[2 * k], eo[2 * k + 1]}; }, fp);
                 dl = xs - Pn;
                 xsol = xs;
                 lj = -(log(fp));                                     // log J of the inverse = -log mean_k 1/D_k at the root
@@ -600,9 +579,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         return;
     }
 
-    // ---- tan-mixture transform: wave k evaluates mixture component k -------------
-    //   y_k = wrap(2 atan(e^{s_k} tan(P/2))),  D_k = e^{-s_k} cos^2(P/2) + e^{s_k} sin^2(P/2),
-    //   log J = log(sum_k 1/D_k) - log K   (= logsumexp_k(-log D_k) - log K of layers.py:85-90)
+    // ---- tan-mixture transform (flow_transform.h): wave k evaluates mixture component k -------------
     double Pa = 0.0;
     if (wave < NMIX && alane) {
         Pa = sP[(ar + 3) * R0C + ac + 3];
@@ -611,26 +588,19 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
         for (int q = 0; q < 8; ++q) sk += sST[(q * 3 + wave) * NAS + lane];
         const int pst = mu == 0 ? 1 : R0C;
         const double cs = sP[(ar + 3) * R0C + ac + 3 + pst], sn = sP[(ar + 3) * R0C + ac + 3 + 2 * pst];   // of P / 2
-        // e^{-s} = 1 / e^{s} and the two quotients by reciprocal + one correction step (ft_rcp): |s| is O(1) for any
-        // usable flow and clamped to +-700 by ft_exp, so every denominator is far from the ends of the range
-        const double es = ft_exp(sk), ems = ft_rcp(es);
-        const double cs2 = cs * cs, sn2 = sn * sn, sincs = sn * cs;
-        const double invD = ft_rcp(ems * cs2 + es * sn2);
-        sT2[(wave * TQ + 1) * NAS + lane] = invD;
-        // tan(P/2) = sn / cs: |cs| can be tiny (P near +-pi) -- a true division keeps the correctly rounded quotient there
-        sT2[(wave * TQ + 0) * NAS + lane] = ft_wrap_pm_pi(2 * ft_atan(es * (sn / cs)));
+        const MixComp<double> m(sk, cs, sn);
+        sT2[(wave * TQ + 1) * NAS + lane] = m.invD;
+        sT2[(wave * TQ + 0) * NAS + lane] = m.y();
         if (has_stash && avalid) {
             // coefficients of the transform's adjoint (struct Stash): the backward kernel then needs no
             // plaquettes, sincos or exp at the active sites of its tile+3 window
-            const double sinP = 2.0 * sincs, invD2 = invD * invD;
+            const double sinP = m.sinP(), invD2 = m.invD2();
             // component-major [k][n/4][A B C E]: the wave of component k writes whole cache lines (site-major, two waves
             // wrote the two 32-byte halves of every 64-byte record at different times)
             double* tc = uniform_ptr(sv.tc, (size_t)wave * n);
             const unsigned ti = 4u * (unsigned)stash_active_idx(ai, aj, L, mu);
-            sts2<NTS>(tc, ti, double2_t{sinP * invD / NMIX,                                             // A_k
-                                   (ems * cs2 - es * sn2) * invD2});                               // B_k
-            sts2<NTS>(tc, ti + 2u, double2_t{invD / NMIX,                                               // C_k
-                                        sinP * 0.5 * (es - ems) * invD2});                         // E_k
+            sts2<NTS>(tc, ti, double2_t{m.A(sinP, NMIX), m.B(invD2)});
+            sts2<NTS>(tc, ti + 2u, double2_t{m.C(NMIX), m.E(sinP, invD2)});
         }
     }
     if (wave == NMIX && alane) {                                 // t on an otherwise idle wave
@@ -651,7 +621,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
 #pragma unroll
             for (int k = 0; k < NMIX; ++k) { ysum += sT2[(k * TQ) * NAS + (lane & (NAS - 1))]; si += sT2[(k * TQ + 1) * NAS + (lane & (NAS - 1))]; }
             const double tval = sP[(ar + 3) * R0C + ac + 3 + 3 * (mu == 0 ? 1 : R0C)];
-            const double newP = ft_wrap(ysum / NMIX + tval);
+            const double newP = mix_new_plaq(ysum, NMIX, tval);
             if (INPL) {                                            // the link update, by the lane that loaded the link (stage 0)
                 const double d = newP - Pa;
                 double* ym = uniform_at(A.y, 2u * bn + (mu == 0 ? 0u : (unsigned)n));
@@ -659,7 +629,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, REV ? 4 : 6) void k_flow_fwd(const d
             } else
             if (avalid) sDL[ar * TC + ac] = has_pout ? newP : newP - Pa;
             if (want_logj) {                                       // force sweeps do not ask for log J
-                const double lj = avalid ? log(si) - log((double)NMIX) : 0.0;
+                const double lj = avalid ? mix_logj(si, NMIX) : 0.0;
                 const double tot = ft_wave_sum(lj);
                 if (lane == 0) A.logj_part[(size_t)b * ntiles + tile] = tot;
             }

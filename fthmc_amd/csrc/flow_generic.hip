@@ -14,6 +14,7 @@
 #include "kernels.h"
 #include "flow_common.h"
 #include "dual.h"
+#include "flow_transform.h"
 
 #include <type_traits>
 
@@ -101,14 +102,13 @@ template <typename T>
 __device__ __forceinline__ MixOut<T> mix_forward(const T* __restrict__ Zb, int n, int s, int K, T Pa) {
     T sn, cs;
     ft_sincos(0.5 * Pa, &sn, &cs);
-    const T tn = sn / cs, cs2 = cs * cs, sn2 = sn * sn;
     T ysum = 0.0, si = 0.0;
     for (int k = 0; k < K; ++k) {
-        const T es = ft_exp(Zb[(size_t)k * n + s]), ems = ft_rcp(es);
-        ysum += ft_wrap_pm_pi(2 * ft_atan(es * tn));
-        si += ft_rcp(ems * cs2 + es * sn2);
+        const MixComp<T> m(Zb[(size_t)k * n + s], cs, sn);
+        ysum += m.y();
+        si += m.invD;
     }
-    return MixOut<T>{ft_wrap(ysum / K + Zb[(size_t)K * n + s]), si};
+    return MixOut<T>{mix_new_plaq(ysum, K, Zb[(size_t)K * n + s]), si};
 }
 
 // ---- tan-mixture transform at the active sites + link update (or plaquette-level output); one workgroup per chain
@@ -139,32 +139,12 @@ __global__ __launch_bounds__(256) void k_gen_transform(const T* __restrict__ x, 
         if constexpr (!REV) {
             const MixOut<T> m = mix_forward(Zb, n, s, K, Pa);
             newP = m.newP;
-            if constexpr (std::is_same<T, double>::value) lj += log(m.si) - log((double)K);
+            if constexpr (std::is_same<T, double>::value) lj += mix_logj(m.si, K);
         } else {
-            // inverse: solve mean_k y_k(xs) = wrap(P' - t) by safeguarded Newton (monotone map, derivative mean_k 1 / D_k;
-            // the reference bisects to a global 1e-6, layers.py:294-320)
-            const double target = ft_wrap(Pa - Zb[(size_t)K * n + s]);
-            double lo = -FT_PI, hi = FT_PI, xs = target, fp = 1.0;
-            for (int it = 0; it < 200; ++it) {
-                double sn, cs;
-                ft_sincos(0.5 * xs, &sn, &cs);
-                const double tn = sn / cs;
-                double f = 0.0;
-                fp = 0.0;
-                for (int k = 0; k < K; ++k) {
-                    const double es = ft_exp(Zb[(size_t)k * n + s]), ems = ft_rcp(es);
-                    f += ft_round_pm_pi(2 * ft_atan(es * tn));          // monotone: no move of pi to -pi
-                    fp += 1.0 / (ems * cs * cs + es * sn * sn);
-                }
-                f /= K; fp /= K;
-                const double err = target - f;
-                if (fabs(err) <= tol) break;
-                if (err > 0) lo = xs; else hi = xs;
-                double xn = xs + err / fp;
-                if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
-                if (xn == xs) break;
-                xs = xn;
-            }
+            // inverse: solve mean_k y_k(xs) = wrap(P' - t) (mix_inverse); e^{+-s_k} once more in every iteration
+            double fp;
+            const double xs = mix_inverse(ft_wrap(Pa - Zb[(size_t)K * n + s]), K, tol, [&](int k) {
+                const double es = ft_exp(Zb[(size_t)k * n + s]); return ExpPair{es, ft_rcp(es)}; }, fp);
             newP = xs;
             lj += -log(fp);
         }
@@ -210,22 +190,22 @@ __global__ void k_gen_transform_bwd(const T* __restrict__ P, const T* __restrict
         const T Pa = P[(size_t)b * n + s];
         T sn, cs;
         ft_sincos(0.5 * Pa, &sn, &cs);
-        const T cs2 = cs * cs, sn2 = sn * sn, sinP = 2.0 * sn * cs;
+        // the coefficients of struct Stash recomputed per component; B_k and E_k as (. invD) invD, the normalisation by a true
+        // division and the sum onto g_up from the left: this kernel's own roundings, kept
+        const T sinP = 2.0 * sn * cs;
         T csum = 0.0, esum = 0.0;
-        for (int k = 0; k < K; ++k) {                                  // C_k = 1 / (K D_k), E_k (struct Stash, flow_mfma_common.h)
-            const T es = ft_exp(Zb[(size_t)k * n + s]), ems = ft_rcp(es);
-            const T invD = ft_rcp(ems * cs2 + es * sn2);
-            csum += invD / K;
-            esum += sinP * 0.5 * (es - ems) * invD * invD;
-        }
-        const T cbr = cb / (K * csum);
         for (int k = 0; k < K; ++k) {
-            const T es = ft_exp(Zb[(size_t)k * n + s]), ems = ft_rcp(es);
-            const T invD = ft_rcp(ems * cs2 + es * sn2);
-            Gb[(size_t)k * n + s] = gdelta * (sinP * invD / K) + cbr * ((ems * cs2 - es * sn2) * invD * invD);   // dL/ds_k
+            const MixComp<T> m(Zb[(size_t)k * n + s], cs, sn);
+            csum += m.C(K);
+            esum += m.En(sinP) * m.invD * m.invD;
+        }
+        const MixAdjoint<T> adj(gdelta, cb / (K * csum), csum, esum);
+        for (int k = 0; k < K; ++k) {
+            const MixComp<T> m(Zb[(size_t)k * n + s], cs, sn);
+            Gb[(size_t)k * n + s] = adj.gs(m.A(sinP, K), m.Bn() * m.invD * m.invD);                          // dL/ds_k
         }
         Gb[(size_t)K * n + s] = gdelta;                                                                      // dL/dt
-        gp_out[(size_t)b * n + s] = g_up + gdelta * (csum - 1.0) - cbr * esum;
+        gp_out[(size_t)b * n + s] = adj.dir_onto(g_up);
     }
 }
 

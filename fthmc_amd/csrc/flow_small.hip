@@ -18,6 +18,7 @@
 // Reference: GaugeEquivCouplingLayer.forward (fthmc/utils/layers.py:196-202, 348-371), ft_action / ft_force
 // (fthmc/utils/qed_helpers.py:212-242), the leapfrog and accept step of ipynb/ft_hmc.py:394-435.
 #include "flow_mfma_common.h"
+#include "flow_transform.h"
 #include <stdlib.h>
 
 namespace {
@@ -394,16 +395,14 @@ template <int L, bool TRAIN> struct Chain {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < 8; ++q) sk += sq[q];
-            const double es = ft_exp(sk), ems = ft_rcp(es);
-            const double cs2 = cs * cs, sn2 = sn * sn, sincs = sn * cs;
-            const double invD = ft_rcp(ems * cs2 + es * sn2);
-            sT2[(wave * 2 + 1) * NAS + lane] = invD;
-            sT2[(wave * 2 + 0) * NAS + lane] = ft_wrap_pm_pi(2 * ft_atan(es * (sn / cs)));
+            const MixComp<double> m(sk, cs, sn);
+            sT2[(wave * 2 + 1) * NAS + lane] = m.invD;
+            sT2[(wave * 2 + 0) * NAS + lane] = m.y();
             if (STASH) {
-                const double sinP = 2.0 * sincs, invD2 = invD * invD;
+                const double sinP = m.sinP(), invD2 = m.invD2();
                 double* tc = sv.tc + (size_t)wave * N + 4 * (size_t)lane;
-                gst2(tc, double2_t{sinP * invD / NMIX, (ems * cs2 - es * sn2) * invD2});
-                gst2(tc + 2, double2_t{invD / NMIX, sinP * 0.5 * (es - ems) * invD2});
+                gst2(tc, double2_t{m.A(sinP, NMIX), m.B(invD2)});
+                gst2(tc + 2, double2_t{m.C(NMIX), m.E(sinP, invD2)});
             }
         }
         if (wave == NMIX && alane) {
@@ -426,10 +425,10 @@ template <int L, bool TRAIN> struct Chain {
                 double ysum = 0.0, si = 0.0;
 #pragma unroll
                 for (int k = 0; k < NMIX; ++k) { ysum += sT2[(k * 2) * NAS + lane]; si += sT2[(k * 2 + 1) * NAS + lane]; }
-                const double d = ft_wrap(ysum / NMIX + sT2[2 * NMIX * NAS + lane]) - sPA[lane];
+                const double d = mix_new_plaq(ysum, NMIX, sT2[2 * NMIX * NAS + lane]) - sPA[lane];
                 const int at = ai * L + aj;
                 if (mu == 0) sX[at] = ft_wrap(d + sX[at]); else sX[N + at] = ft_wrap(-d + sX[N + at]);
-                if (want_logj) lj = log(si) - log((double)NMIX);
+                if (want_logj) lj = mix_logj(si, NMIX);
             }
             if (want_logj) {
                 const double tot = ft_wave_sum(lj);
@@ -522,22 +521,15 @@ template <int L, bool TRAIN> struct Chain {
             const double g0 = sGP[i * L + j];
             const double g1 = mu == 0 ? sGP[i * L + (j == 0 ? L - 1 : j - 1)] : sGP[(i == 0 ? L - 1 : i - 1) * L + j];
             const double gdelta = g0 - g1;
-            double csum = 0.0, esum = 0.0;
+            const MixAdjoint<double> adj(gdelta, cb, pre.tcv, NMIX);
 #pragma unroll
-            for (int k = 0; k < NMIX; ++k) { csum += pre.tcv[4 * k + 2]; esum += pre.tcv[4 * k + 3]; }
-            const double tsum = NMIX * csum;
-            double rs = __builtin_amdgcn_rcp(tsum);
-            rs = fma(fma(-tsum, rs, 1.0), rs, rs);
-            rs = fma(fma(-tsum, rs, 1.0), rs, rs);
-            const double cbr = cb * rs;
-#pragma unroll
-            for (int k = 0; k < NMIX; ++k) put1i<RS>(sGO + k * PSZ, i, j, gdelta * pre.tcv[4 * k] + cbr * pre.tcv[4 * k + 1]);
+            for (int k = 0; k < NMIX; ++k) put1i<RS>(sGO + k * PSZ, i, j, adj.gs(pre.tcv[4 * k], pre.tcv[4 * k + 1]));
             put1i<RS>(sGO + NMIX * PSZ, i, j, gdelta);
-            sGP[i * L + j] = g0 + (gdelta * (csum - 1.0) - cbr * esum);
+            sGP[i * L + j] = g0 + adj.dir();
             if (gzo) {                                                     // g_out record of active site tid: dL/ds_0, dL/ds_1, dL/dt, 0
                 static_assert(NMIX == 2, "g_out record");
                 double* po = gzo + 16 * (size_t)N + 4 * (size_t)tid;
-                gst2(po, double2_t{gdelta * pre.tcv[0] + cbr * pre.tcv[1], gdelta * pre.tcv[4] + cbr * pre.tcv[5]});
+                gst2(po, double2_t{adj.gs(pre.tcv[0], pre.tcv[1]), adj.gs(pre.tcv[4], pre.tcv[5])});
                 gst2(po + 2, double2_t{gdelta, 0.0});
             }
         }

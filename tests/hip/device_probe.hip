@@ -1,6 +1,7 @@
 // Test-only device probe (tests/test_device_math_gpu.py, tests/test_rng_gpu.py): the kernels' own fp64 math helpers (common.h,
-// flow_common.h), integer index helpers (flow_mfma_common.h) and the draws of the random streams from raw words
-// (rng_common.h), applied elementwise to arrays, exactly as the headers define them -- nothing is copied.  Built by
+// flow_common.h), the tan-mixture transform (flow_transform.h), integer index helpers (flow_mfma_common.h) and the draws of the
+// random streams from raw words (rng_common.h), applied elementwise to arrays, exactly as the headers define them -- nothing is
+// copied.  Built by
 // `make -C fthmc_amd/csrc probe` with the kernels' CXXFLAGS (same FP-contraction policy), never linked into
 // libfthmc_hip.so.  Every launcher takes HOST arrays, copies them in and out, and returns the first HIP error (0 = success).
 #include <hip/hip_runtime.h>
@@ -8,16 +9,18 @@
 #include "../../fthmc_amd/csrc/common.h"
 #include "../../fthmc_amd/csrc/flow_common.h"
 #include "../../fthmc_amd/csrc/flow_mfma_common.h"
+#include "../../fthmc_amd/csrc/flow_transform.h"
 #include "../../fthmc_amd/csrc/rng_common.h"
 
 using namespace fthmc_flow;
 
 enum {
     P_SIGMOID = 0, P_SIGMOID4, P_EXP, P_EXPN4, P_EXPN2, P_ACT, P_ACT4, P_SINCOS, P_ATAN, P_RCP, P_WRAP, P_WRAP_PM_PI,
-    P_REGULARIZE, P_COMPOSITE, P_NOPS
+    P_REGULARIZE, P_COMPOSITE, P_INVERSE, P_ADJOINT, P_NOPS
 };
 
-// scalar ops: one element per thread; the N-wide forms (sigmoid4, ft_expN, act_eval4): N consecutive elements per thread
+// scalar ops: one element per thread; the N-wide forms (sigmoid4, ft_expN, act_eval4): N consecutive elements per thread; the
+// transform's inverse and adjoint: one record of 4 / 8 consecutive elements per thread
 template <int OP>
 __global__ void k_math(const double* __restrict__ x, const double* __restrict__ s, double* o0, double* o1, double* o2, int n, int act) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -39,6 +42,26 @@ __global__ void k_math(const double* __restrict__ x, const double* __restrict__ 
         o0[2 * t] = e[0]; o0[2 * t + 1] = e[1];
         return;
     }
+    if (OP == P_INVERSE) {
+        // mix_inverse as flow_fwd.hip's REV instances call it: x = (P', t, s_0, s_1), s[0] = tol -> o0 = (root, mean_k 1 / D_k there)
+        if (4 * t >= n) return;
+        const double ea[4] = {x[4 * t + 2], -x[4 * t + 2], x[4 * t + 3], -x[4 * t + 3]};
+        double eo[4], fp;
+        ft_expN<4>(ea, eo);
+        o0[4 * t] = mix_inverse(ft_wrap(x[4 * t] - x[4 * t + 1]), NMIX, s[4 * t],
+                                [&](int k) { return ExpPair{eo[2 * k], eo[2 * k + 1]}; }, fp);
+        o0[4 * t + 1] = fp;
+        return;
+    }
+    if (OP == P_ADJOINT) {
+        // MixAdjoint from a stash record: x = (A_0 B_0 C_0 E_0 A_1 B_1 C_1 E_1), s = (gd, cb) -> o0 = (dL/ds_0, dL/ds_1, dir)
+        if (8 * t >= n) return;
+        double tc[8];
+        for (int q = 0; q < 8; ++q) tc[q] = x[8 * t + q];
+        const MixAdjoint<double> adj(s[8 * t], s[8 * t + 1], tc, NMIX);
+        o0[8 * t] = adj.gs(tc[0], tc[1]); o0[8 * t + 1] = adj.gs(tc[4], tc[5]); o0[8 * t + 2] = adj.dir();
+        return;
+    }
     if (t >= n) return;
     const double v = x[t];
     if (OP == P_SIGMOID) o0[t] = ft_sigmoid(v);
@@ -52,15 +75,13 @@ __global__ void k_math(const double* __restrict__ x, const double* __restrict__ 
     if (OP == P_REGULARIZE) o0[t] = ft_regularize(v);
     if (OP == P_COMPOSITE) {
         // one mixture component of the tan-mixture transform as the MFMA forward evaluates it (flow_fwd.hip: the sincos of P / 2
-        // in the plaquette stage, then y_k and D_k): x = P, s = s_k
+        // in the plaquette stage, then MixComp): x = P, s = s_k
         double sn, cs;
         ft_sincos(0.5 * v, &sn, &cs);
-        const double es = ft_exp(s[t]), ems = ft_rcp(es);
-        const double cs2 = cs * cs, sn2 = sn * sn;
-        const double D = ems * cs2 + es * sn2;
-        o0[t] = ft_wrap_pm_pi(2 * ft_atan(es * (sn / cs)));
-        o1[t] = D;
-        o2[t] = ft_rcp(D);
+        const MixComp<double> m(s[t], cs, sn);
+        o0[t] = m.y();
+        o1[t] = m.D;
+        o2[t] = m.invD;
     }
 }
 
@@ -151,7 +172,7 @@ struct Dev {                                   // device copies of the host arra
 };
 
 template <int OP> void launch_math(int n, int act, const double* x, const double* s, double* o0, double* o1, double* o2) {
-    const int per = (OP == P_SIGMOID4 || OP == P_EXPN4 || OP == P_ACT4) ? 4 : OP == P_EXPN2 ? 2 : 1;
+    const int per = (OP == P_SIGMOID4 || OP == P_EXPN4 || OP == P_ACT4 || OP == P_INVERSE) ? 4 : OP == P_ADJOINT ? 8 : OP == P_EXPN2 ? 2 : 1;
     const int nt = (n + per - 1) / per;
     hipLaunchKernelGGL(k_math<OP>, dim3((nt + 255) / 256), dim3(256), 0, 0, x, s, o0, o1, o2, n, act);
 }
@@ -175,14 +196,17 @@ extern "C" {
 
 int probe_nops(void) { return P_NOPS; }
 
-// n elements (a multiple of 4 for the four-wide forms, of 2 for ft_expN<2>); s: the composite's s_k, else unused (may be null);
+// n elements (a multiple of 4 for the four-wide forms and the inverse, of 8 for the adjoint, of 2 for ft_expN<2>); s: the
+// composite's s_k, the inverse's tol and the adjoint's (gd, cb) at the head of each record, else unused (may be null);
 // o1: the second output of act_eval / act_eval4 / ft_sincos / the composite (D_k), o2: the composite's ft_rcp(D_k)
 int probe_math(int op, int act, const double* x, const double* s, double* o0, double* o1, double* o2, int n) {
     if (op < 0 || op >= P_NOPS || n <= 0 || !x || !o0) return (int)hipErrorInvalidValue;
-    if ((op == P_SIGMOID4 || op == P_EXPN4 || op == P_ACT4) && n % 4) return (int)hipErrorInvalidValue;
+    if ((op == P_SIGMOID4 || op == P_EXPN4 || op == P_ACT4 || op == P_INVERSE) && n % 4) return (int)hipErrorInvalidValue;
+    if (op == P_ADJOINT && n % 8) return (int)hipErrorInvalidValue;
     if (op == P_EXPN2 && n % 2) return (int)hipErrorInvalidValue;
     if ((op == P_ACT || op == P_ACT4 || op == P_SINCOS || op == P_COMPOSITE) && !o1) return (int)hipErrorInvalidValue;
     if (op == P_COMPOSITE && (!s || !o2)) return (int)hipErrorInvalidValue;
+    if ((op == P_INVERSE || op == P_ADJOINT) && !s) return (int)hipErrorInvalidValue;
     Dev d;
     const size_t N = (size_t)n;
     const double* dx = d.in(x, N);

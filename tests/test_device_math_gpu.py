@@ -1,4 +1,5 @@
-"""The kernels' hand-written fp64 math (common.h, flow_common.h) and integer index helpers (flow_mfma_common.h), pinned one by one.
+"""The kernels' hand-written fp64 math (common.h, flow_common.h), the tan-mixture transform they share (flow_transform.h) and
+integer index helpers (flow_mfma_common.h), pinned one by one.
 
 Every other GPU test checks whole kernels on random fields, where the inputs at which such code breaks (P near +-pi, the atan fold at
 |x| = 1, the exp clamps, large |z| in the sigmoid, reduction boundaries) are rare.  tests/hip/device_probe.hip applies each helper
@@ -29,7 +30,7 @@ mpmath.mp.dps = 40
 CSRC = os.path.join(ROOT, 'fthmc_amd', 'csrc')
 PROBE = os.path.join(ROOT, 'tests', 'hip', 'libdevice_probe.so')
 (P_SIGMOID, P_SIGMOID4, P_EXP, P_EXPN4, P_EXPN2, P_ACT, P_ACT4, P_SINCOS, P_ATAN, P_RCP, P_WRAP, P_WRAP_PM_PI,
- P_REGULARIZE, P_COMPOSITE, P_NOPS) = range(15)
+ P_REGULARIZE, P_COMPOSITE, P_INVERSE, P_ADJOINT, P_NOPS) = range(17)
 SILU, RELU, LEAKY = 0, 1, 2
 FT_PI, FT_TWO_PI = 3.14159265358979323846, 6.28318530717958647692
 LD = np.longdouble
@@ -391,6 +392,81 @@ def test_tan_mixture_component_near_p_pm_pi(probe):
     k = int(np.argmax(ey)); assert ey[k] <= 6 * float(ulp(np.pi)), (ey[k], PP[k], SS[k])
     k = int(np.argmax(eD)); assert eD[k] <= 9 * u, (eD[k] / u, PP[k], SS[k])
     k = int(np.argmax(eI)); assert eI[k] <= 10 * u, (eI[k] / u, PP[k], SS[k])
+
+
+# ----------------------------------------------------------------------------------------------------------------- the inverse, the adjoint
+@pytest.mark.parametrize('tol', [1e-13, 0.0])
+def test_transform_inverse_on_the_steep_fixture(probe, tol):
+    """flow_transform.h mix_inverse, called as flow_fwd.hip's REV instances call it (e^{+-s_k} by one ft_expN<4>, target =
+    ft_wrap(P' - t)), on the 20 x 2 x 64 active sites of tests/golden/steep_inverse.npz at L = 16: s, t of the oracle, P' = the
+    mpmath forward of the true P.  Per site the bound of test_steep_inverse_gpu.py for the plaquette-level kernels,
+    (tol + 8 delta_ref) / fp + 4 ulp(pi); test_steep_reference.py's numpy port of the loop reaches 0.93 of it on these inputs.  At
+    tol = 0 the loop has to end through xn == xs or an error of exactly 0."""
+    import steep_fixture as SF
+    g = SF.load()
+    worst_q = 0.0
+    for r, ci, si, mu, off in SF.plaq_combos(g, 16):
+        P = g['P_L16'][si][:, SF.active_mask(16, mu, off)].ravel()
+        s = g['s_L16'][r]                                                   # [B, K, na]
+        assert s.shape[1] == 2 and s.shape[0] * s.shape[2] == len(P) == 128
+        rec = np.stack([g['fP_L16'][r].ravel(), g['t_L16'][r].ravel(), s[:, 0].ravel(), s[:, 1].ravel()], axis=1).ravel()
+        o = run(probe, P_INVERSE, rec, np.full(len(rec), tol))[0].reshape(-1, 4)
+        x, fpd = o[:, 0], o[:, 1]
+        fp = g['fp_L16'][r].astype(np.float64).ravel()
+        bound = (tol + 8 * g['delta_ref'][si]) / fp + 4 * SF.ULP_PI
+        dx = np.abs(SF.wrapdiff(x, P))
+        q = float(np.max(dx / bound))
+        worst_q = max(worst_q, q)
+        assert np.all(np.isfinite(x)) and np.all(np.isfinite(fpd)) and np.all(fpd > 0), (r, ci, mu, off)
+        assert q <= 1.0, (r, ci, mu, off, q, float(dx.max()))
+    print(f'mix_inverse, tol = {tol}: worst |dx| / bound {worst_q:.3f}')
+
+
+def test_transform_adjoint_from_stash_coefficients(probe):
+    """flow_transform.h MixAdjoint from a stash record (A_k B_k C_k E_k, K = 2), as the three backward kernels build it:
+        gs_k = gd A_k + cb B_k / (K sum C),    dir = gd (sum C - 1) - cb sum E / (K sum C)
+    against mpmath on the same doubles.  Roundings of the helper, u = 2^-53 (half an ulp, relative) each unless stated; a
+    contraction into an FMA only removes one:
+      csum = (0 + C_0) + C_1: 1 (C_k > 0: no cancellation); esum = E_0 + E_1: 1, relative to |E_0| + |E_1|; K csum: exact;
+      1 / (K csum) by v_rcp_f64 and two correction steps: within 1 ulp = 2 u; cbr = cb rs: 1   -> cbr within 4 u of cb / (K sum C);
+      gs_k = gd A_k + cbr B_k: two products and the sum -> |error| <= (2 T1 + 6 T2) u, T1 = |gd A_k|, T2 = |cb B_k| / (K sum C);
+      dir: csum - 1 carries csum's rounding (u sum C) and its own (u |sum C - 1|), the product one more, cbr esum 4 + 1 + 1, the
+      last subtraction u (|gd| |sum C - 1| + TE) -> |error| <= (4 G + 7 TE) u, G = |gd| (sum C + 1), TE = |cb| (|E_0| + |E_1|) / (K sum C):
+      in units of the terms' magnitudes, so that the cancellation in sum C - 1 (sum C = dP'/dP is 1 for the identity map) is not
+      held against the helper.
+    Second-order terms are below 2^-45 of these (at most 11 factors 1 + u): the bounds are asserted with a factor 1 + 2^-40."""
+    g = rng(9)
+    n = 4096
+    C = np.exp(g.uniform(-9.0, 3.0, (n, 2)))                                # 1 / (K D_k): e^{-|s|} .. e^{|s|} / K
+    near1 = g.random(n) < 0.25                                               # sum C near 1: the near-identity flows
+    C[near1, 0] = g.uniform(0.01, 0.99, near1.sum())
+    C[near1, 1] = 1.0 - C[near1, 0] + g.normal(0, 1e-9, near1.sum())
+    A, Bc, E = (g.normal(0, 1, (n, 2)) * np.exp(g.uniform(-6, 6, (n, 2))) for _ in range(3))
+    gd = g.normal(0, 1, n) * np.exp(g.uniform(-8, 8, n))
+    cb = g.normal(0, 1, n) * np.exp(g.uniform(-8, 8, n))
+    assert np.all(C > 0) and (gd > 0).any() and (gd < 0).any() and (cb > 0).any() and (cb < 0).any()
+    rec = np.stack([A[:, 0], Bc[:, 0], C[:, 0], E[:, 0], A[:, 1], Bc[:, 1], C[:, 1], E[:, 1]], axis=1).ravel()
+    sv = np.zeros((n, 8))
+    sv[:, 0], sv[:, 1] = gd, cb
+    o = run(probe, P_ADJOINT, rec, sv.ravel())[0].reshape(n, 8)
+    u = 2.0 ** -53 * (1 + 2.0 ** -40)
+    m = mpmath.mpf
+    worst_gs = worst_dir = 0.0
+    for i in range(n):
+        sc, se = m(C[i, 0]) + m(C[i, 1]), m(E[i, 0]) + m(E[i, 1])
+        cbr = m(cb[i]) / (2 * sc)
+        for k in range(2):
+            ref = m(gd[i]) * m(A[i, k]) + cbr * m(Bc[i, k])
+            bound = (2 * abs(m(gd[i]) * m(A[i, k])) + 6 * abs(cbr * m(Bc[i, k]))) * u
+            q = float(abs(m(o[i, k]) - ref) / bound)
+            worst_gs = max(worst_gs, q)
+            assert q <= 1.0, ('gs', i, k, q)
+        ref = m(gd[i]) * (sc - 1) - cbr * se
+        bound = (4 * abs(m(gd[i])) * (sc + 1) + 7 * abs(cbr) * (abs(m(E[i, 0])) + abs(m(E[i, 1])))) * u
+        q = float(abs(m(o[i, 2]) - ref) / bound)
+        worst_dir = max(worst_dir, q)
+        assert q <= 1.0, ('dir', i, q)
+    print(f'MixAdjoint: worst error / bound: gs {worst_gs:.3f}, dir {worst_dir:.3f}')
 
 
 # ----------------------------------------------------------------------------------------------------------------- index helpers

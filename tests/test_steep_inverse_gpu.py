@@ -1,9 +1,9 @@
 """The coupling layer and its inverse on STEEP flows (|s| = 2 .. 20) against tests/golden/steep_inverse.npz: mpmath at 40 digits
 on the oracle's s, t (tests/golden/make_golden_steep.py).  Every other inverse test draws default-init weights, |s| < 0.3, where
 the tan-mixture map is almost the identity and the safeguarded Newton loop needs 4 plain steps; here it needs its bracket, its
-bisection fallback, its xn == xs stop, and log J at ill-conditioned roots.  All three copies of the loop run: csrc/flow_fwd.hip
-(REV instances: exact tiles at L = 32, ragged at L = 20, L = 16 with the fused small path off), csrc/flow.hip (VALU variant,
-link level), csrc/flow_generic.hip (n_mix 1 and 3).
+bisection fallback, its xn == xs stop, and log J at ill-conditioned roots.  Both statements of the loop run, through every
+caller: csrc/flow_transform.h mix_inverse from csrc/flow_fwd.hip (REV instances: exact tiles at L = 32, ragged at L = 20, L = 16
+with the fused small path off) and from csrc/flow_generic.hip (n_mix 1 and 3), and csrc/flow.hip's own (VALU variant, link level).
 
 Tolerances follow the conditioning, never a kernel's output.  delta_ref = max |oracle fp64 forward - mpmath forward| over the
 active sites is the reference's own noise floor, measured by the generator per s0 and stored in the fixture:
@@ -23,7 +23,7 @@ with the roundings of d and of the wrap: 16 ulp(pi) in place of 4.
 
 Found by these inputs: inside the loop a component 2 atan(.) that rounds to exactly pi was wrapped to -pi as in the forward map;
 at s0 = 10, (+,+), P = pi - d the loop then ended at pi, 4.7e-9 from the root (2.06 times the per-site bound; 21 times at tol = 0)
-in every copy of the MFMA kernel.  The loop keeps the component monotone now (common.h ft_round_pm_pi).
+in every copy the loop then had.  The loop keeps the component monotone now (flow_transform.h mix_inverse, common.h ft_round_pm_pi).
 
 No site is left out of any check.  The test prints the observed maxima as fractions of their bounds (pytest -s)."""
 import math
@@ -180,9 +180,9 @@ def test_link_level(g, variant):
 
 
 def test_loop_ends_without_a_tolerance(g):
-    """tol = 0.0 is met only by an error of exactly 0.0: otherwise each copy of the loop has to end through xn == xs
+    """tol = 0.0 is met only by an error of exactly 0.0: otherwise the loop has to end through xn == xs in each of its callers
     (test_steep_reference.py shows the plain port ending in at most 60 of its 200 iterations), at (8 delta_ref) / fp + 4 ulp(pi) per
-    site.  Once per copy, at L = 16, on the steepest regular case (s0 = 10, (+,+): at the planted pi - d the target lies 2e-13
+    site.  Once per caller, at L = 16, on the steepest regular case (s0 = 10, (+,+): at the planted pi - d the target lies 2e-13
     below pi and the start of the iteration itself saturates the atan)."""
     wst = Worst()
     ops.set_small_path(False)

@@ -1,7 +1,8 @@
 """CPU checks behind tests/test_steep_inverse_gpu.py: the steep-flow fixture regenerates, its mpmath forward agrees with the
-oracle where the oracle is trustworthy, and a plain fp64 port of the kernels' safeguarded Newton loop (csrc/flow_fwd.hip REV,
-flow.hip MODE 3, flow_generic.hip k_gen_transform<REV>) meets, on the fixture's own inputs, the bounds the GPU test asks of the
-kernels -- so the inputs are fair to a correct kernel.
+oracle where the oracle is trustworthy, and a plain fp64 port of the kernels' safeguarded Newton loop (csrc/flow_transform.h
+mix_inverse, which csrc/flow_fwd.hip REV and flow_generic.hip k_gen_transform<REV> call, and flow.hip MODE 3, the VALU variant's
+own statement of it) meets, on the fixture's own inputs, the bounds the GPU tests ask of the kernels -- so the inputs are fair
+to a correct kernel.
 
 Measured with the port (tol = 1e-13): at most 15 / 20 / 22 / 35 iterations at s0 = 2 / 5 / 10 / 20, worst |dx| = 0.93 of its
 bound, worst log J error 0.14 of its bound; at tol = 0 (L = 16) at most 60 iterations, ending through xn == xs or through an
@@ -9,7 +10,7 @@ error of exactly 0.0 (the loop's f is rounded like the forward's wrap, so it mee
 
 The port is the loop as it stands since this test exists: with the component 2 atan(.) wrapped to [-pi, pi) as in the forward
 map, the port (and every kernel) missed the per-site bound twice over at the planted pi - d of s0 = 10, signs (+,+) -- see
-common.h ft_round_pm_pi."""
+flow_transform.h mix_inverse (common.h ft_round_pm_pi)."""
 import math
 import os
 import sys
