@@ -75,6 +75,11 @@ SIGNATURES = {
     'fthmc_ft_action_vjp': [_D, _D, _A, c_int, c_int, c_int, c_int, c_double, _D, _D, _D, _D, _P, c_size_t, _P],
     'fthmc_ft_force_vjp': [_D, _D, _A, c_int, c_int, c_int, c_int, c_double, _D, _D, _D, _P, c_size_t, _P],
     'fthmc_vjp_ws_bytes': [_A, c_int, c_int, c_int],
+    'fthmc_train_force_ws_bytes': [_A, c_int, c_int, c_int],
+    'fthmc_train_force_grad': [_D, _D, _A, c_int, c_int, c_int, c_int, c_double, _D, _D, _D, _P, c_size_t, _P],
+    'fthmc_set_dual_path': [c_int],
+    'fthmc_get_dual_path': [],
+    'fthmc_train_force_path': [_A, c_int, c_int],
     'fthmc_random_uniform': [_D, c_int, c_int, c_double, c_double, _D, _P],
     'fthmc_chain_seeds': [ctypes.c_int64, ctypes.c_int64, c_int, ctypes.c_int64, _D, c_int, _D, _P],
     'fthmc_ws_head_bytes': [],
@@ -89,7 +94,7 @@ SIGNATURES = {
 # the `_v` twins of the whole-flow entry points: the same arguments + the caller's weight version (include/fthmc_hip.h)
 for _n in ('fthmc_flow_forward', 'fthmc_flow_reverse', 'fthmc_ft_action', 'fthmc_ft_force', 'fthmc_ft_leapfrog', 'fthmc_ft_trajectory'):
     SIGNATURES[_n + '_v'] = SIGNATURES[_n] + [c_uint64]
-_RESTYPE = {'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t}
+_RESTYPE = {'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None
 

@@ -108,11 +108,12 @@ WS ws_layout(const FlowArch& A, double* base, int B, int L, int nl, bool train =
 // stash, the generic kernels' scratch, the gP ping-pong, the dual weight gradients and the per-chain log J coefficients.
 // total = 0: the sizes overflow size_t.
 struct VWS { Dual *xd, *X, *stash, *hbuf, *gbuf, *gp, *gp2, *gw; double* glj; size_t total; };
-VWS vjp_layout(const FlowArch& A, double* base, int B, int L, int nl) {
+// o0: where the regions start (fthmc_train_force_grad puts them behind a whole force workspace)
+VWS vjp_layout(const FlowArch& A, double* base, int B, int L, int nl, size_t o0 = up((size_t)FLOW_WHEAD_LAYERS * FLOW_WINT)) {
     VWS w{};
     bool ovf = false;
     auto mul = [&](size_t a, size_t b) { size_t r = 0; ovf |= __builtin_mul_overflow(a, b, &r); return r; };
-    size_t o = up((size_t)FLOW_WHEAD_LAYERS * FLOW_WINT);
+    size_t o = o0;
     auto take = [&](size_t nd) {                                   // nd dual numbers
         Dual* p = base && !ovf ? reinterpret_cast<Dual*>(base + o) : nullptr;
         ovf |= __builtin_add_overflow(o, up(mul(nd, 2)), &o);
@@ -1191,6 +1192,146 @@ int fthmc_ft_force_vjp(const double* x, const double* w, const fthmc_arch_t* arc
     FT_TRY(vjp_backward<Dual>(C, V, xphys, n_layers, B, L, act, beta, nullptr, nullptr, -1.0, gw ? V.gw : nullptr, &gp));
     if (gw && n_layers > 0) FT_TRY(launch_dual_tangent(V.gw, gw, (size_t)n_layers * C.A.params(), s));
     return gx ? launch_dual_links(gp, gx, B, L, s) : FTHMC_OK;
+}
+
+// ---- force-norm training: sum_b |F_b|^2 and its weight gradient (ipynb/ft_hmc.py:253-299).  With xi fixed and F = d(sum S_eff)/dxi,
+// d/dw sum_b |F_b|^2 = 2 d/dw <g, F> at g = F: one first-order force, then the dual sweep of fthmc_ft_force_vjp seeded with it.
+int fthmc_set_dual_path(int on) {
+    if (on < 0 || on > 3) return FTHMC_ERR_ARG;
+    set_dual_path(on);
+    return FTHMC_OK;
+}
+int fthmc_get_dual_path(void) { return get_dual_path(); }
+
+}  // extern "C"
+
+namespace {
+int g_dual_path = 1;
+// the tile of the fused dual kernels that serves a call (flow_dual.hip), -1: the plain dual kernels
+inline int force_dual_tile(const FlowArch& A, int B, int L, int path) {
+    if (path == 0 || !A.is_default()) return -1;
+    // 8 x 16 tiles where they divide the lattice and give every CU a workgroup (measured: config 3 9.6 vs 11.8 ms, config-5 shard
+    // 75 vs 92 ms; config 2, 64 such tiles on 256 CUs: 0.41 vs 0.33 ms), 8 x 8 tiles otherwise
+    const bool wide = flow_dual_shape(B, L, 1) && (path == 3 || (path == 1 && (long)B * flow_dual_geom(1).ntiles(L) >= 256));
+    if (wide) return 1;
+    return flow_dual_shape(B, L, 0) ? 0 : -1;
+}
+// Workspace of fthmc_train_force_grad: a whole workspace of fthmc_ft_force first (the head with the weight expansions included:
+// the first-order sweep runs there as in any force call), behind it the force itself and the regions of the dual sweep -- the
+// fused kernels' (dual input, checkpoint chain, plaquette gradient, its partial windows, the weight-gradient partial rows and
+// the reduction's rows) or the plain kernels' (vjp_layout).  total = 0: the sizes overflow size_t.
+struct FWS { size_t first; double* F; Dual *xd, *X, *gp, *gpp; double *gwp, *gwt; VWS V; size_t total; };
+FWS force_layout(const FlowArch& A, double* base, int B, int L, int nl, int tile) {
+    FWS w{};
+    // ws_layout (the first-order workspace) adds its regions unchecked: it is asked only where the plain dual layout, which is
+    // larger region by region and IS checked, stays far from the end of size_t.  Everything this function adds itself is checked.
+    const size_t bound = vjp_layout(A, nullptr, B, L, nl, 0).total;
+    if (bound == 0 || bound > SIZE_MAX / 64) return w;
+    bool ovf = false;
+    auto mul = [&](size_t a, size_t b) { size_t r = 0; ovf |= __builtin_mul_overflow(a, b, &r); return r; };
+    w.first = up(ws_doubles(A, B, L, nl));
+    size_t o = w.first;
+    auto take = [&](size_t n) {                                    // n doubles
+        double* p = base && !ovf ? base + o : nullptr;
+        size_t padded = 0;
+        ovf |= __builtin_add_overflow(n, ALIGN - 1, &padded);
+        ovf |= __builtin_add_overflow(o, padded / ALIGN * ALIGN, &o);
+        return p;
+    };
+    const size_t n1 = mul(mul((size_t)B, (size_t)L), (size_t)L), n2 = mul(2, n1);
+    w.F = take(n2);
+    if (tile < 0) {
+        if (ovf) return w;
+        w.V = vjp_layout(A, base, B, L, nl, o);
+        w.total = w.V.total;
+        return w;
+    }
+    w.xd = reinterpret_cast<Dual*>(take(mul(2, n2)));
+    w.X = reinterpret_cast<Dual*>(take(mul(mul(2, (size_t)nl), n2)));
+    w.gp = reinterpret_cast<Dual*>(take(mul(2, n1)));
+    const FlowGeom g = flow_dual_geom(tile);
+    w.gpp = reinterpret_cast<Dual*>(take(nl > 0 ? mul(2, mul(mul((size_t)B, (size_t)g.ntiles(L)), (size_t)g.n0())) : 0));
+    w.gwp = take(nl > 0 ? mul((size_t)flow_dual_nparts(B, L, tile), FLOW_GW_STRIDE) : 0);
+    w.gwt = take(nl > 0 ? mul((size_t)FLOW_REDUCE_GROUPS, FLOW_GW_STRIDE) : 0);
+    w.total = ovf || o > SIZE_MAX / sizeof(double) ? 0 : o;
+    if (w.total == 0) w = FWS{};
+    return w;
+}
+}  // namespace
+
+namespace fthmc {
+void set_dual_path(int v) { g_dual_path = v; }
+int get_dual_path() { return g_dual_path; }
+}  // namespace fthmc
+
+extern "C" {
+
+int fthmc_train_force_path(const fthmc_arch_t* arch, int B, int L) {
+    Ctx C;
+    if (make_ctx(arch, nullptr, &C) != FTHMC_OK) return FTHMC_ERR_UNSUPPORTED;
+    return force_dual_tile(C.A, B, L, get_dual_path()) >= 0 ? 1 : 0;
+}
+
+size_t fthmc_train_force_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
+    Ctx C;
+    if (bad_shape(B, L) || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
+    if (n_layers > 0 && C.A.k / 2 > L) return 0;
+    return force_layout(C.A, nullptr, B, L, n_layers, force_dual_tile(C.A, B, L, get_dual_path())).total * sizeof(double);
+}
+
+int fthmc_train_force_grad(const double* xi, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
+                           int act, double beta, double* F, double* force_sq, double* gw,
+                           void* ws, size_t ws_bytes, void* stream) {
+    (void)hipGetLastError();
+    FT_TRY(check_flow_call(xi && force_sq, w, n_layers, B, L, act));
+    Ctx C;
+    FT_TRY(make_ctx(arch, stream, &C));
+    if (n_layers > 0 && C.A.k / 2 > L) return FTHMC_ERR_UNSUPPORTED;
+    const hipStream_t s = C.s;
+    const int nl = n_layers, tile = force_dual_tile(C.A, B, L, get_dual_path());
+    if (force_layout(C.A, nullptr, B, L, nl, tile).total == 0) return FTHMC_ERR_UNSUPPORTED;
+    const FWS W = force_layout(C.A, static_cast<double*>(ws), B, L, nl, tile);
+    if (!ws || ws_bytes < W.total * sizeof(double)) return FTHMC_ERR_WS;
+    // the first-order force, as fthmc_ft_force computes it, in the front part of the workspace
+    double* Fo = F ? F : W.F;
+    FT_TRY(fthmc_ft_force_v(xi, w, arch, nl, B, L, act, beta, Fo, ws, W.first * sizeof(double), stream, 0));
+    FT_TRY(launch_kinetic(Fo, B, L, force_sq, s));                       // sum over the links of F^2, one workgroup per chain
+    if (!gw || nl == 0) return FTHMC_OK;
+    const size_t n1 = (size_t)B * L * L, n2 = 2 * n1;
+    if (tile < 0) {                                                      // the plain dual kernels: fthmc_ft_force_vjp's sweep at g = F
+        C.wcan = w;
+        FT_TRY(launch_dual_pack(xi, Fo, W.V.xd, n2, s));
+        const Dual* xphys;
+        FT_TRY(vjp_forward<Dual>(C, W.V, W.V.xd, nl, B, L, act, &xphys));
+        Dual* gp;
+        FT_TRY(vjp_backward<Dual>(C, W.V, xphys, nl, B, L, act, beta, nullptr, nullptr, -1.0, W.V.gw, &gp));
+        return launch_dual_tangent(W.V.gw, gw, (size_t)nl * C.A.params(), s, 2.0);
+    }
+    // the fused dual kernels (flow_dual.hip) on the weight expansion the force call has just left in the head
+    const double* wint = static_cast<const double*>(ws);
+    FT_TRY(launch_dual_pack(xi, Fo, W.xd, n2, s));
+    auto layer = [&](int l) {
+        FlowDualArgs a{};
+        a.x = l == 0 ? W.xd : W.X + (size_t)(l - 1) * n2;
+        a.wint = wint + (size_t)l * FLOW_WINT;
+        a.B = B; a.L = L; a.mu = layer_mu(l); a.off = layer_off(l); a.act = act;
+        return a;
+    };
+    for (int l = 0; l < nl; ++l) {
+        FlowDualArgs a = layer(l);
+        a.y = W.X + (size_t)l * n2;
+        FT_TRY(launch_flow_dual_fwd(a, tile, s));
+    }
+    FT_TRY(launch_gen_seed(W.X + (size_t)(nl - 1) * n2, nullptr, B, L, beta, W.gp, s));
+    const int np = flow_dual_nparts(B, L, tile);
+    for (int l = nl - 1; l >= 0; --l) {
+        FlowDualArgs a = layer(l);
+        a.up_gp = W.gp; a.gp_part = W.gpp; a.gw_part = W.gwp; a.glogj_const = -1.0;
+        FT_TRY(launch_flow_dual_bwd(a, tile, s));
+        FT_TRY(launch_reduce_gw(W.gwp, np, 2.0, 0, gw + (size_t)l * FTHMC_W_PER_LAYER, W.gwt, s));
+        if (l > 0) FT_TRY(launch_gather_gp_dual(W.gpp, B, L, tile, W.gp, s));      // nothing reads the plaquette gradient at xi
+    }
+    return FTHMC_OK;
 }
 
 }  // extern "C"

@@ -294,10 +294,10 @@ __global__ void k_dual_pack(const double* __restrict__ x, const double* __restri
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) out[i] = Dual(x[i], g[i]);
 }
-__global__ void k_dual_tangent(const Dual* __restrict__ in, double* __restrict__ out, size_t n) {
+__global__ void k_dual_tangent(const Dual* __restrict__ in, double* __restrict__ out, size_t n, double scale) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) out[i] = in[i].t;
+    for (; i < n; i += stride) out[i] = scale * in[i].t;
 }
 // gx = the adjoint of the plaquette stencil applied to the tangent of gP (k_kick_from_gp's F, wilson.hip)
 __global__ void k_dual_links(const Dual* __restrict__ gp, double* __restrict__ gx, int L) {
@@ -458,8 +458,8 @@ int launch_dual_pack(const double* x, const double* g, Dual* out, size_t n, hipS
     FT_LAUNCH_CHECK();
     return FTHMC_OK;
 }
-int launch_dual_tangent(const Dual* in, double* out, size_t n, hipStream_t s) {
-    hipLaunchKernelGGL(k_dual_tangent, dim3(egrid(n)), dim3(256), 0, s, in, out, n);
+int launch_dual_tangent(const Dual* in, double* out, size_t n, hipStream_t s, double scale) {
+    hipLaunchKernelGGL(k_dual_tangent, dim3(egrid(n)), dim3(256), 0, s, in, out, n, scale);
     FT_LAUNCH_CHECK();
     return FTHMC_OK;
 }

@@ -271,7 +271,46 @@ int launch_gen_seed(const Dual* x, const double* coef, int B, int L, double beta
 // x + eps g as one dual field; the link gradient (adjoint of the plaquette stencil) of the TANGENT of a dual gP field; tangents
 int launch_dual_pack(const double* x, const double* g, Dual* out, size_t n, hipStream_t s);
 int launch_dual_links(const Dual* gp, double* gx, int B, int L, hipStream_t s);
-int launch_dual_tangent(const Dual* in, double* out, size_t n, hipStream_t s);
+int launch_dual_tangent(const Dual* in, double* out, size_t n, hipStream_t s, double scale = 1.0);   // out = scale * tangent
+
+// ---- flow_dual.hip: the default net's coupling layer on dual numbers as fused tile kernels (the force-norm training step,
+// fthmc_train_force_grad): forward x -> y, and the backward from the layer's input with the tangent weight gradients
+struct FlowDualArgs {
+    const Dual* x;           // [B][2][L][L] layer input
+    Dual* y;                 // forward: output field (not x)
+    const double* wint;      // this layer's weights, kernel layout (k_pack_weights)
+    const Dual* up_gp;       // backward: upstream plaquette gradient [B][L][L]
+    Dual* gp_part;           // backward: [B * ntiles][window] partial plaquette gradients (launch_gather_gp_dual adds them onto up_gp)
+    double* gw_part;         // backward: [flow_dual_nparts][FLOW_GW_STRIDE] tangent weight-gradient partials, canonical order
+    double glogj_const;      // backward: d/d logJ
+    int B, L, mu, off, act;
+    int ntj, ntiles, items;  // set by the launcher
+};
+// tile 0: 8 x 8 sites (77.5 KB of LDS in the backward), tile 1: 8 x 16 (132 KB); either backward holds 330 / 416 registers per
+// lane (256 VGPRs + accumulator registers), so ONE workgroup is resident per CU whatever the LDS would allow
+inline FlowGeom flow_dual_geom(int tile) { return tile == 0 ? FlowGeom{8, 8} : FlowGeom{8, 16}; }
+// served: the tile divides the lattice (L = 8: one tile whose window wraps onto itself), item and row counts in int, one
+// workgroup row per chain in the small launches
+inline bool flow_dual_shape(int B, int L, int tile) {
+    const FlowGeom g = flow_dual_geom(tile);
+    return B > 0 && B <= 65535 && L >= 8 && L <= 8192 && L % g.tr == 0 && L % g.tc == 0 && (long)B * g.ntiles(L) < (1L << 30);
+}
+// workgroups of the backward = rows of its partial buffer: two rounds (8 x 8) / one round (8 x 16) of the 256 CUs, fewer for small
+// launches;
+// workgroup k walks the items k, k + rows, ...
+inline int flow_dual_nparts(int B, int L, int tile) {
+    const long items = (long)B * flow_dual_geom(tile).ntiles(L), cap = tile == 0 ? 512 : 256;
+    return (int)(items < cap ? items : cap);
+}
+inline size_t flow_dual_gp_part(int B, int L, int tile) { const FlowGeom g = flow_dual_geom(tile); return (size_t)B * g.ntiles(L) * g.n0(); }   // dual numbers
+int launch_flow_dual_fwd(const FlowDualArgs& a, int tile, hipStream_t s);
+int launch_flow_dual_bwd(const FlowDualArgs& a, int tile, hipStream_t s);
+int launch_gather_gp_dual(const Dual* gp_part, int B, int L, int tile, Dual* gp, hipStream_t s);
+// fthmc_set_dual_path: 0 the generic dual sweep (flow_generic.hip) always, 1 (default) the fused kernels where they serve the call
+// (api.hip force_dual_tile picks the tile), 2 / 3 the fused kernels with 8 x 8 tiles always / 8 x 16 tiles wherever those divide
+// L (the A/B of the tile shapes)
+void set_dual_path(int v);
+int get_dual_path();
 
 // ---- flow_small.hip: L <= 16, one workgroup per chain, whole sequences of the flowed path in one launch
 struct SmallArgs {

@@ -68,8 +68,8 @@ struct Arch {
 
 struct Workspace {
     Tensor buf; size_t bytes;
-    Workspace(const Tensor& like, const fthmc_arch_t* arch, int B, int L, int nl, bool train = false, bool vjp = false) {
-        bytes = vjp ? fthmc_vjp_ws_bytes(arch, B, L, nl) : train ? fthmc_train_ws_bytes(arch, B, L, nl) : fthmc_ws_bytes(arch, B, L, nl);
+    Workspace(const Tensor& like, const fthmc_arch_t* arch, int B, int L, int nl, bool train = false, bool vjp = false, bool force = false) {
+        bytes = force ? fthmc_train_force_ws_bytes(arch, B, L, nl) : vjp ? fthmc_vjp_ws_bytes(arch, B, L, nl) : train ? fthmc_train_ws_bytes(arch, B, L, nl) : fthmc_ws_bytes(arch, B, L, nl);
         TORCH_CHECK(bytes > 0, "unsupported shape (B = ", B, ", L = ", L, ", n_layers = ", nl, ")");
         buf = at::empty({(int64_t)((bytes + 7) / 8)}, like.options());
     }
@@ -248,6 +248,20 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> train_grad(const Tensor& xi_, const T
        "fthmc_train_grad");
     return {x, logq, logp, gw};
 }
+// the force-norm training step (ipynb/ft_hmc.py:253-299): F, sum F_b^2 and d(sum_b |F_b|^2)/dw (none without layers)
+std::tuple<Tensor, Tensor, Tensor> train_force_grad(const Tensor& x_, const Tensor& w_all, int64_t n_layers, double beta, int64_t act,
+                                                    int64_t n_mix, IntList hidden, int64_t kernel_size) {
+    FT_DEVICE_GUARD(x_);
+    Tensor x = field(x_, "x");
+    Arch A(n_mix, hidden, kernel_size);
+    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
+    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
+    Tensor F = at::empty_like(x), fsq = at::empty({B}, x.options()), gw = at::zeros({w.numel()}, x.options());
+    Workspace ws(x, A.ptr(), B, L, nl, false, false, true);
+    ok(fthmc_train_force_grad(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, mp(F), mp(fsq), nl > 0 ? mp(gw) : nullptr, ws.ptr(), ws.bytes,
+                              cur_stream(x)), "fthmc_train_force_grad");
+    return {F, fsq, gw};
+}
 
 }  // namespace
 
@@ -265,6 +279,7 @@ TORCH_LIBRARY(fthmc_hip, m) {
     m.def("train_grad(Tensor xi, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("ft_action_vjp(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor gS, Tensor? glogdet=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
     m.def("ft_force_vjp(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor g, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
+    m.def("train_force_grad(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor)");
 }
 
 // "CUDA" is the dispatch key of HIP devices in PyTorch-ROCm
@@ -282,4 +297,5 @@ TORCH_LIBRARY_IMPL(fthmc_hip, CUDA, m) {
     m.impl("train_grad", &train_grad);
     m.impl("ft_action_vjp", &ft_action_vjp);
     m.impl("ft_force_vjp", &ft_force_vjp);
+    m.impl("train_force_grad", &train_force_grad);
 }

@@ -52,13 +52,24 @@ def vjp_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
     return int(_lib.load().fthmc_vjp_ws_bytes(_arch(arch), B, L, n_layers))
 
 
-def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None, vjp: bool = False):
-    if vjp:
+def train_force_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
+    """Scratch of train_force_grad under the current `set_dual_path` setting; 0 for a refused shape."""
+    return int(_lib.load().fthmc_train_force_ws_bytes(_arch(arch), B, L, n_layers))
+
+
+def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None, vjp: bool = False, force: bool = False):
+    if force:
+        need = train_force_ws_bytes(B, L, nl, arch)
+        if need == 0:
+            raise FthmcError(f'train_force_grad: shape B={B}, L={L}, {nl} layers is refused (fthmc_train_force_ws_bytes = 0)')
+    elif vjp:
         need = vjp_ws_bytes(B, L, nl, arch)
     else:
         need = int(_lib.load().fthmc_train_ws_bytes(_arch(arch), B, L, nl)) if train else ws_bytes(B, L, nl, arch)
     # one workspace per (device, stream): chain groups running on concurrent streams must not share scratch
     key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream)
+    if force:
+        key += ('train_force',)        # a buffer of its own: the dual regions would otherwise stay with every later sampling call
     buf = _WS.get(key)
     if buf is None or buf.numel() * 8 < need:
         if torch.cuda.is_current_stream_capturing():
@@ -211,6 +222,22 @@ def set_small_path(on: bool):
 
 def get_small_path() -> bool:
     return bool(_lib.load().fthmc_get_small_path())
+
+
+def set_dual_path(on):
+    """The dual sweep behind train_force_grad: True / 1 (default) the fused tile kernels where they serve the shape, False / 0
+    the plain dual kernels always, 2 / 3 the fused kernels with 8 x 8 tiles always / 8 x 16 tiles wherever those divide L (the
+    A/B of the tile shapes)."""
+    check(_lib.load().fthmc_set_dual_path(int(on)), 'fthmc_set_dual_path')
+
+
+def get_dual_path() -> int:
+    return int(_lib.load().fthmc_get_dual_path())
+
+
+def train_force_path(B: int, L: int, arch=None) -> int:
+    """1: the fused dual kernels serve a train_force_grad call of this shape under the current setting, 0: the plain ones."""
+    return int(_lib.load().fthmc_train_force_path(_arch(arch), B, L))
 
 
 def act_code(act) -> int:
@@ -820,6 +847,28 @@ def train_grad(xi, w, n_layers: int, beta: float, act='silu', need_gw=True, grou
     check(_lib.load().fthmc_train_grad(_p(xi), _p(w), ap, n_layers, B, L, act_code(act), float(beta), _p(x), _p(logq),
                                        _p(logp), _p(gw), ws, nb, _stream(xi)), 'fthmc_train_grad')
     return {'x': x, 'logq': logq, 'logp': logp, 'gw': gw}
+
+
+def train_force_grad(xi, w, n_layers: int, beta: float, act='silu', need_gw=True, out_gw=None, arch=None):
+    """-> dict(F, force_sq, gw): the force-norm training step's pieces at a fixed field `xi` (C ABI fthmc_train_force_grad,
+    ipynb/ft_hmc.py:253-299): F = d(sum_b S_eff)/dxi [B, 2, L, L] (what ft_force returns), force_sq[b] = sum F_b^2, and
+    gw = d(sum_b force_sq[b])/dw flat like `w` (written into `out_gw` when given, with train_grad's contract: a contiguous
+    float64 device tensor of w.numel() entries, e.g. the flat gradient buffer); gw is None with need_gw=False or no layers."""
+    xi = _field(xi, 'xi'); B, _, L, _ = xi.shape
+    w, ap, a = _wall(w, n_layers, arch)
+    need_gw = bool(need_gw and n_layers)
+    if out_gw is not None and need_gw and (not out_gw.is_cuda or out_gw.dtype != torch.float64 or not out_gw.is_contiguous()
+                                           or out_gw.numel() != w.numel()):
+        raise FthmcError(f'train_force_grad: out_gw must be a contiguous float64 device tensor of {w.numel()} entries')
+    F = torch.empty_like(xi)
+    fsq = torch.empty(B, dtype=xi.dtype, device=xi.device)
+    gw = None
+    if need_gw:
+        gw = _tag(out_gw.reshape(-1) if out_gw is not None else torch.empty(w.numel(), dtype=xi.dtype, device=xi.device), w, a)
+    ws, nb = _ws(xi, B, L, n_layers, arch=a, force=True)
+    check(_lib.load().fthmc_train_force_grad(_p(xi), _p(w), ap, n_layers, B, L, act_code(act), float(beta), _p(F), _p(fsq),
+                                             _p(gw), ws, nb, _stream(xi)), 'fthmc_train_force_grad')
+    return {'F': F, 'force_sq': fsq, 'gw': gw}
 
 
 def time_kernel(kind: str, x, w=None, mu=0, off=0, act='silu', beta=1.0, reps=20) -> float:

@@ -30,6 +30,8 @@ Operators (reference call site each one replaces):
                    d/dx, d/dw of sum_b gS_b S_eff_b + glogdet_b logdet_b        (autograd of qed_helpers.py:212-223)
   ft_force_vjp(x, w_all, n_layers, beta, act, g, n_mix=2, hidden, kernel_size) -> (gx, gw)
                    H g and d/dw <g, F> for the force F                         (autograd of qed_helpers.py:226-242, create_graph)
+  train_force_grad(x, w_all, n_layers, beta, act, n_mix=2, hidden, kernel_size) -> (F, force_sq, gw)
+                   the force, sum_links F_b^2 and d(sum_b |F_b|^2)/dw          ipynb/ft_hmc.py:253-299 (with_force)
 `act` is the integer code of fthmc_hip.h (0 silu/swish, 1 relu, 2 leaky_relu); `mode` 0 = MD
 semantics, 1 = literal reference leapfrog.  The s/t net's shape travels IN the schema, as plain
 integers: `n_mix` mixture components, `hidden` = hidden_sizes (None = the reference default [8, 8]), `kernel_size` --
@@ -161,6 +163,15 @@ if BACKEND == 'python':
         return gx, gw
 
 
+    @torch.library.custom_op('fthmc_hip::train_force_grad', mutates_args=(), device_types=_DEV)
+    def train_force_grad(x: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta: float, act: int,
+                         n_mix: int = 2, hidden: Optional[Sequence[int]] = None,
+                         kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        r = ops.train_force_grad(x, w_all, n_layers, beta, _act(act), arch=_arch(n_mix, hidden, kernel_size))
+        gw = r['gw'] if r['gw'] is not None else x.new_zeros(w_all.numel())
+        return r['F'], r['force_sq'], gw
+
+
 # ---------------------------------------------------------------- shapes for tracing (meta tensors)
 def _b(x):
     return x.new_empty(x.shape[0])
@@ -229,6 +240,11 @@ def _(x, w_all, n_layers, beta, act, gS, glogdet=None, n_mix=2, hidden=None, ker
 @torch.library.register_fake('fthmc_hip::ft_force_vjp')
 def _(x, w_all, n_layers, beta, act, g, n_mix=2, hidden=None, kernel_size=3):
     return torch.empty_like(x), x.new_empty(w_all.numel())
+
+
+@torch.library.register_fake('fthmc_hip::train_force_grad')
+def _(x, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
+    return torch.empty_like(x), _b(x), x.new_empty(w_all.numel())
 
 
 # ---------------------------------------------------------------- autograd formulas
@@ -301,9 +317,9 @@ torch.library.register_autograd('fthmc_hip::ft_action_force', _action_force_back
 if BACKEND == 'compiled':                        # the module's names are the dispatcher's operators themselves
     for _n in ('wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x', 'flow_layer_bwd_w',
                'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad', 'ft_action_vjp',
-               'ft_force_vjp'):
+               'ft_force_vjp', 'train_force_grad'):
         globals()[_n] = getattr(torch.ops.fthmc_hip, _n)
 
 __all__ = ['wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x',
            'flow_layer_bwd_w', 'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad',
-           'ft_action_vjp', 'ft_force_vjp']
+           'ft_action_vjp', 'ft_force_vjp', 'train_force_grad']

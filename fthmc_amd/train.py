@@ -152,8 +152,12 @@ def _metrics_dict(row_host: np.ndarray, B: int) -> dict:
 
 def train_step(model: FlowModel, config: TrainConfig, action: ActionFn, optimizer: optim.Optimizer,
                batch_size: int, scheduler: Any = None, scaler: Any = None, pre_model: FlowModel = None,
-               dkl_factor: float = 1., xi: torch.Tensor = None, fused: bool = True):
+               dkl_factor: float = 1., xi: torch.Tensor = None, fused: bool = True, with_force: bool = False):
     """train.py:162-228.  `batch_size` is this rank's share of the global batch.
+
+    with_force=True: the force-norm step of ipynb/ft_hmc.py:253-299 instead of the reverse-KL step: the loss is
+                 sum_b |F_b|^2 of the flowed force F = d(sum_b S_eff)/dxi at a FIXED xi; see `_force_step`.  A `scaler` is
+                 refused with it (ValueError): the step has no scaled loss.
 
     fused=True : one HIP call computes x, logq, logp and d(loss)/d(weights) (needs `action` to be
                  the Wilson `BatchAction(config.beta)`, which is what train.py:291 passes); the gradient lands in the
@@ -162,6 +166,11 @@ def train_step(model: FlowModel, config: TrainConfig, action: ActionFn, optimize
     `scaler` (a torch GradScaler, train.py:206-209, 321-324): the reference's scale / step / update sequence on the autograd
     route; on the fp64 path it changes nothing but the order of two multiplications (there is no fp16 to protect).
     A whole training loop without any per-step host synchronisation: `GraphTrainer` (what `train` uses)."""
+    if with_force:
+        if scaler is not None:
+            raise ValueError('train_step(with_force=True): a GradScaler does not apply to the force-norm step (its gradient comes from '
+                             'one fused fp64 call, there is no scaled loss to backpropagate); pass scaler=None')
+        return _force_step(model, config, action, optimizer, batch_size, scheduler, pre_model, dkl_factor, xi, fused)
     t0 = time.time()
     if scaler is not None:
         fused = False        # train.py:206-209: scaler.scale(loss).backward() needs the loss as an autograd tensor: the layer-wise route
@@ -214,6 +223,91 @@ def train_step(model: FlowModel, config: TrainConfig, action: ActionFn, optimize
     B = x.shape[0]
     host = torch.cat([loss_dkl.reshape(1), ess.reshape(1), logp.detach(), logq.detach(), q, dq, plaq]).cpu().numpy()
     out = _metrics_dict(host, B)
+    out['dt'] = time.time() - t0
+    return out
+
+
+def _force_step(model: FlowModel, config: TrainConfig, action, optimizer, batch_size: int, scheduler, pre_model, dkl_factor: float,
+                xi, fused: bool):
+    """train_step(with_force=True): one force-norm step (ipynb/ft_hmc.py:253-299: force = ft_force(param, layers, xi, True);
+    loss = sum(force**2); loss.backward(); optimizer.step()).
+
+    xi: the `xi` argument if given, else a draw of the model's prior.  With `pre_model` it follows the NOTEBOOK
+    (ipynb/ft_hmc.py:258-262): the pre-model's prior through the pre-model's layers, then back through the inverse of the
+    model BEING TRAINED -- unlike the reverse-KL branch above, which follows the package's train.py:186-189 and inverts the
+    pre-model's own layers.  The notebook's `assert pre_model != None` is not kept: a prior draw is a legal xi.
+
+    fused (and the Wilson `BatchAction`): ONE ops.train_force_grad call writes d(sum_b |F_b|^2)/d(weights) into the flat
+    gradient buffer (C ABI fthmc_train_force_grad: the first-order force, then one dual-number sweep seeded with it); with a
+    process group the gradients are SUM all-reduced as in the reverse-KL branch.  Otherwise the autograd route:
+    qed.ft_force(..., create_graph=True) and loss.backward().
+    -> the metrics of a reverse-KL step evaluated at the same xi BEFORE the update (no gradient), plus 'force' = 'loss' =
+    sum_b |F_b|^2 summed over the ranks."""
+    t0 = time.time()
+    layers = model.layers
+    if pre_model is not None:
+        pre_xi = pre_model.prior.sample_n(batch_size)
+        x_pre = qed.ft_flow(pre_model.layers, pre_xi)
+        xi = qed.ft_flow_inv(layers, x_pre)
+    if xi is None:
+        xi = model.prior.sample_n(batch_size)
+    xi = xi.detach().to(DTYPE).contiguous()
+    B = xi.shape[0]
+    if fused and isinstance(action, qed.BatchAction):
+        flat = flatten_flow(layers)
+        gflat = flow_grad_buffer(layers)
+        act = flow_activation(layers)
+        # the reverse-KL metrics at this xi, before the weights move
+        r0 = ops.train_grad(xi, flat, len(layers), action.beta, act, need_gw=False)
+        row = ops.train_metrics(xi, r0['x'], r0['logq'], r0['logp'], action.beta, dkl_factor)
+        d = r0['logq'] - r0['logp']
+        r = ops.train_force_grad(xi, flat, len(layers), action.beta, act, out_gw=gflat)
+        fsum = r['force_sq'].sum().reshape(1)
+        if parallel.have_group():
+            world = torch.distributed.get_world_size()
+            n_global = B * world
+            gext = flow_grad_ext(layers)
+            n = gflat.numel()
+            torch.sum(d, dim=0, keepdim=True, out=gext[n:n + 1])
+            parallel.allreduce_grads(gext)
+            row[0] = dkl_factor * gext[n] / n_global
+            row[1] = parallel.global_ess(-d, n_global)
+            torch.distributed.all_reduce(fsum, op=torch.distributed.ReduceOp.SUM)
+        attach_grads(layers)                     # the call overwrites every gradient: no zero_grad pass
+        optimizer.step()
+        host = torch.cat([row, fsum]).cpu().numpy()
+        out = _metrics_dict(host[:-1], B)
+        force = np.asarray(host[-1])
+    else:
+        world = torch.distributed.get_world_size() if parallel.have_group() else 1
+        n_global = B * world
+        with torch.no_grad():
+            x, _, logq = apply_flow_to_prior(model.prior, layers, xi=xi, batch_size=batch_size)
+            logp = (-1.) * action(x)
+            loss_dkl = dkl_factor * parallel.global_mean(logq - logp, n_global)
+            logw = logp - logq
+            ess = torch.exp(2 * parallel.global_logsumexp(logw) - parallel.global_logsumexp(2 * logw)) / n_global
+            qi = qed.batch_charges(xi)
+            q = qed.batch_charges(x)
+            plaq = logp / (config.beta * config.volume)
+            dq = torch.sqrt((q - qi) ** 2)
+        optimizer.zero_grad()
+        F = qed.ft_force(config, layers, xi, create_graph=True)      # the Wilson force at config.beta, attached to autograd
+        loss = (F ** 2).sum()
+        loss.backward()
+        fsum = loss.detach().reshape(1).clone()
+        if parallel.have_group():
+            for p in layers.parameters():
+                parallel.allreduce_grads(p.grad)
+            torch.distributed.all_reduce(fsum, op=torch.distributed.ReduceOp.SUM)
+        optimizer.step()
+        host = torch.cat([loss_dkl.reshape(1), ess.reshape(1), logp, logq, q, dq, plaq, fsum]).cpu().numpy()
+        out = _metrics_dict(host[:-1], B)
+        force = np.asarray(host[-1])
+    out['force'] = force
+    out['loss'] = force
+    if scheduler is not None:
+        scheduler.step(float(force))
     out['dt'] = time.time() - t0
     return out
 
@@ -463,13 +557,28 @@ def train(config: TrainConfig, model: Optional[FlowModel] = None, pre_model: Flo
     """train.py:236-431 without plots / tensorboard: n_era x n_epoch steps, one checkpoint per era
     (save=True).  Returns dict(model, optimizer, history, ckpt_files).
 
+    config.with_force ("Minimize force norm during training"): every epoch runs the reverse-KL step and then a force-norm step
+    (`train_step(with_force=True)`) on a second optimizer of the same kind at base_lr / 100, as flow_train does
+    (ipynb/ft_hmc.py:338-343); the loop then takes the step-by-step route and the history gains 'force'.  The second optimizer
+    comes back as 'optimizer_wf' (a key only such a run has).  Checkpoints (save=True) keep the reference's keys and hold the
+    reverse-KL optimizer only: a resumed run starts the force steps' Adam moments from zero unless the caller saves
+    `optimizer_wf.state_dict()` itself.  With `use_scaler` the GradScaler wraps the reverse-KL step only; the force-norm step
+    runs unscaled (fp64 throughout: there is nothing to protect).
+
     The steps run through `GraphTrainer` (one captured hipGraph per step, metrics kept on the device until the end or
     the next `print_freq` line); `pre_model` (a prior passed through another flow and back) and `use_scaler` (train.py:250,
     321-324: a torch GradScaler around the step) keep the step-by-step `train_step` route."""
     if model is None:
         model = get_model(config)
-    stepwise = pre_model is not None or use_scaler
+    with_force = bool(getattr(config, 'with_force', False))
+    stepwise = pre_model is not None or use_scaler or with_force
     optimizer = make_optimizer(model, config, capturable=not stepwise)
+    # ipynb/ft_hmc.py:321, 338-343: a second optimizer of the same kind at base_lr / 100 takes the force-norm steps
+    optimizer_wf = None
+    if with_force:
+        optimizer_wf = make_optimizer(model, config, capturable=not stepwise)
+        for g in optimizer_wf.param_groups:
+            g['lr'] = config.base_lr / 100.0
     scaler = torch.amp.GradScaler('cuda') if (use_scaler and torch.cuda.is_available()) else None
     scheduler = None
     if scheduler_config is not None:
@@ -492,6 +601,10 @@ def train(config: TrainConfig, model: Optional[FlowModel] = None, pre_model: Flo
                                      pre_model=pre_model, dkl_factor=dkl_factor)
                 for k, v in metrics.items():
                     history.setdefault(k, []).append(v)
+                if with_force:                   # the KL step, then a force-norm step on the second optimizer
+                    mf = train_step(model, config, action, optimizer_wf, config.batch_size, pre_model=pre_model,
+                                    dkl_factor=dkl_factor, with_force=True)
+                    history.setdefault('force', []).append(mf['force'])
             if show:
                 print(f"era {era} epoch {epoch}: loss_dkl={float(metrics['loss_dkl']):.4f} "
                       f"ess={float(metrics['ess']):.4f} plaq={float(np.mean(metrics['plaq'])):.5f}", flush=True)
@@ -504,7 +617,10 @@ def train(config: TrainConfig, model: Optional[FlowModel] = None, pre_model: Flo
     if trainer is not None:
         history = trainer.history()
         history['dt'] = [(time.time() - t0) / max(step, 1)] * step       # per-step wall time: the loop never stops to measure one
-    return {'model': model, 'optimizer': optimizer, 'history': history, 'ckpt_files': ckpts, 'action': action}
+    out = {'model': model, 'optimizer': optimizer, 'history': history, 'ckpt_files': ckpts, 'action': action}
+    if with_force:
+        out['optimizer_wf'] = optimizer_wf
+    return out
 
 
 def transfer_to_new_lattice(L: int, layers: nn.ModuleList, param_init: Param = None):

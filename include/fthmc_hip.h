@@ -275,6 +275,31 @@ int fthmc_ft_force_vjp(const double* x, const double* w, const fthmc_arch_t* arc
                        double beta, const double* g, double* gx, double* gw, void* ws, size_t ws_bytes, void* stream);
 /* Scratch for the two calls above (0 for a refused shape). */
 size_t fthmc_vjp_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers);
+/* Force-norm training (TrainConfig.with_force): the loss sum_b |F_b|^2 of the flowed force F = d(sum_b S_eff)/dx at a fixed x and
+ * its gradient with respect to the weights, in one call.  ipynb/ft_hmc.py:253-299 (force = ft_force(param, layers, xi, True);
+ * loss = sum(force**2); loss.backward()).
+ *   F[B][2][L][L]  the first-order force, from the sweep fthmc_ft_force runs under the current switches (NULL: not wanted)
+ *   force_sq[B]    sum over the links of F_b^2, fixed order
+ *   gw             d(sum_b force_sq[b])/dw, n_layers x fthmc_arch_params(arch) in the canonical layout (NULL: the metrics-only
+ *                  call); = twice the tangent weight gradient of the force sweep on the dual field x + eps F (csrc/dual.h)
+ * The dual sweep of the default net runs on fused tile kernels (csrc/flow_dual.hip) where 8 x 8 tiles divide the lattice
+ * (L % 8 == 0), and on the plain dual kernels of fthmc_ft_force_vjp everywhere else: same results to rounding, fixed summation
+ * order either way.  n_layers = 0: the Wilson force, gw untouched.  ws: fthmc_train_force_ws_bytes(arch, B, L, n_layers), which
+ * is a workspace of fthmc_ft_force (head included: the first-order sweep expands the weights there) with the dual regions behind
+ * it; the size covers the path the current fthmc_set_dual_path setting selects and is 0 for a refused shape. */
+size_t fthmc_train_force_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers);   /* ipynb/ft_hmc.py:253-299 */
+int fthmc_train_force_grad(const double* xi, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
+                           int act, double beta, double* F, double* force_sq, double* gw,
+                           void* ws, size_t ws_bytes, void* stream);                         /* ipynb/ft_hmc.py:253-299 */
+/* Which dual sweep serves fthmc_train_force_grad (ipynb/ft_hmc.py:253-299): 1 (default) the fused kernels where they are built
+ * for the shape (8 x 16 tiles where they divide L and fill the chip, else 8 x 8), 0 the plain dual kernels always, 2 / 3 the
+ * fused kernels with 8 x 8 tiles always / 8 x 16 tiles wherever those divide L (tile A/B).  A process-wide DEBUG switch like
+ * fthmc_set_small_path, read once per call. */
+int fthmc_set_dual_path(int on);
+int fthmc_get_dual_path(void);
+/* 1 if the fused dual kernels serve a fthmc_train_force_grad call of this shape under the current setting, 0 if the plain
+ * dual kernels do, < 0 for a refused arch */
+int fthmc_train_force_path(const fthmc_arch_t* arch, int B, int L);
 /* x_, v_ = leapfrog with ft_force.  ipynb/ft_hmc.py:394-418. */
 int fthmc_ft_leapfrog(const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int n_layers,
                       int B, int L, int act, double beta, double dt, int nstep,
