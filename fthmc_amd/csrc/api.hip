@@ -709,7 +709,14 @@ static int layer_bwd_impl(const double* x, const double* stash, const double* w,
         if (stash) { a.stash = const_cast<double*>(stash); a.stash_h = 1; }
         else {
             a.stash = W.stash; a.stash_h = gw ? 1 : 0;
+            // with weight gradients: the launch of fthmc_flow_layer_fwd_stash (links into W.X, log J partials; nobody reads them) --
+            // on the exact tiles that is the training-sweep instance of the forward, and the instances of one kernel round their
+            // stash differently in the last bit (fp contraction follows the code around it): so this call and the two-call route
+            // give the same bits on every shape.  Without them the workspace holds the force stash only (no h1, h2): another
+            // instance than a caller's stash came from, equal to round-off.
+            if (gw) { a.y = W.X; a.logj_part = W.lj_part; }
             FT_TRY(launch_flow_fwd_mfma(a, s));
+            a.y = nullptr; a.logj_part = nullptr;
         }
         a.gp_out = W.gp;
         FT_TRY(layer_backward_stash(W, a, gw, s));

@@ -33,7 +33,7 @@ def close(a, b, rtol=0.0, atol=0.0):
 
 @pytest.mark.parametrize('B,L,nl,beta', [(1, 32, 8, 2.0),      # 4 items: every workgroup walks one tile; all eight (mu, off)
                                          (3, 64, 8, 6.0),      # 48 items
-                                         (20, 64, 2, 4.0),     # 320 items > 256 workgroups: walks of two items, the last round ragged
+                                         (20, 64, 2, 4.0),     # 320 items > 256 workgroups: every workgroup walks two items
                                          (2, 128, 3, 3.0)])    # 128 items, tiles far from the lattice edge
 def test_fused_training_backward_vs_oracle(B, L, nl, beta):
     """fthmc_train_grad on the tiled-exactly shapes (L a power of two >= 32: csrc/flow_bwd_train.hip) = loss.backward() of
