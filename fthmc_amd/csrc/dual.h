@@ -1,9 +1,12 @@
 // Dual numbers (value, tangent) for the second-order path: the plain kernels of flow_generic.hip instantiated on Dual run the
 // first-order backward on x + eps g, and the eps parts of its outputs are the Hessian-vector product H g and the mixed
 // derivative d/dw <g, F> (fthmc_ft_force_vjp, api.hip).  Every helper the plain kernels call has an overload here.  Value parts
-// go through the double helpers themselves (common.h, flow_common.h), so they are the numbers of the double instances; tangent
-// parts are the analytic derivatives torch's autograd takes of the same functions: the remainders (ft_wrap, ft_wrap_pm_pi)
-// pass the tangent through, relu'' = leaky_relu'' = 0, silu'' = sigma' (2 + z (1 - 2 sigma)), tanh'' = -2 t (1 - t^2).
+// go through the double helpers themselves (common.h, flow_common.h), so they are the numbers of the double instance of the same
+// expression in the same caller, bit for bit (from one caller to another a sum of products may round differently in its last
+// bit, on double as on Dual: flow_transform.h); tangent parts are the analytic derivatives torch's autograd takes of the same
+// functions: the remainders (ft_wrap, ft_wrap_pm_pi) pass the tangent through, relu'' = leaky_relu'' = 0,
+// silu'' = sigma' (2 + z (1 - 2 sigma)), tanh'' = -2 t (1 - t^2).  tests/test_dual_math_gpu.py pins every overload: values against the
+// double helpers bit for bit, tangents against the closed-form derivatives within bounds traced through the expressions below.
 #pragma once
 #include "flow_common.h"
 

@@ -5,8 +5,12 @@
 //     log J = log(sum_k 1/D_k) - log K   (= logsumexp_k(-log D_k) - log K)
 // The pieces are values formed where the caller asks for them: a kernel keeps its own order of loads, stores and barriers.  K is a
 // plain argument (NMIX in the tuned kernels, where it folds); T is double, or Dual (dual.h) in flow_generic.hip.  Results are
-// pinned bit for bit: no expression may change its operand order or its helper.  flow.hip, the VALU variant, deliberately keeps a
-// second statement of the inverse (ocml's math, started at 0).
+// pinned bit for bit: no expression may change its operand order or its helper.  That holds per caller, not from one caller to
+// the next: which product of a sum becomes an FMA is the compiler's choice and follows what else the caller forms.  In
+// tests/hip/device_probe.hip D_k is fma(e^-s, cs^2, round(e^s sn^2)) where Bn() is formed next to it, as a backward stage does, and
+// differs in the last bit from the D_k of the forward form at one input in ten (tests/test_dual_math_gpu.py: 78 of 792, never more
+// than 1 ulp; 2 ulp is the most two such forms can differ).  flow.hip, the VALU variant, deliberately keeps a second statement of
+// the inverse (ocml's math, started at 0).
 #pragma once
 #include "flow_common.h"
 

@@ -1,7 +1,7 @@
-// Test-only device probe (tests/test_device_math_gpu.py, tests/test_rng_gpu.py): the kernels' own fp64 math helpers (common.h,
-// flow_common.h), the tan-mixture transform (flow_transform.h), integer index helpers (flow_mfma_common.h) and the draws of the
-// random streams from raw words (rng_common.h), applied elementwise to arrays, exactly as the headers define them -- nothing is
-// copied.  Built by
+// Test-only device probe (tests/test_device_math_gpu.py, tests/test_dual_math_gpu.py, tests/test_rng_gpu.py): the kernels' own fp64
+// math helpers (common.h, flow_common.h), their dual-number overloads (dual.h), the tan-mixture transform on double and on Dual
+// (flow_transform.h), integer index helpers (flow_mfma_common.h) and the draws of the random streams from raw words
+// (rng_common.h), applied elementwise to arrays, exactly as the headers define them -- nothing is copied.  Built by
 // `make -C fthmc_amd/csrc probe` with the kernels' CXXFLAGS (same FP-contraction policy), never linked into
 // libfthmc_hip.so.  Every launcher takes HOST arrays, copies them in and out, and returns the first HIP error (0 = success).
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include "../../fthmc_amd/csrc/flow_common.h"
 #include "../../fthmc_amd/csrc/flow_mfma_common.h"
 #include "../../fthmc_amd/csrc/flow_transform.h"
+#include "../../fthmc_amd/csrc/dual.h"
 #include "../../fthmc_amd/csrc/rng_common.h"
 
 using namespace fthmc_flow;
@@ -82,6 +83,96 @@ __global__ void k_math(const double* __restrict__ x, const double* __restrict__ 
         o0[t] = m.y();
         o1[t] = m.D;
         o2[t] = m.invD;
+    }
+}
+
+// ---- the dual-number overloads of dual.h and the Dual instances of flow_transform.h.  Planes of n doubles: in[p * n + i] is input
+// plane p of element i, out[q * n + i] output plane q; a dual operand takes two planes (value, tangent).  Operands a, b, c of the
+// arithmetic ops: planes 0-1, 2-3, 4-5 (a scalar operand reads its value plane alone).
+enum {
+    D_MUL = 0, D_DIV_DD, D_DIV_SD, D_FMA_SDD, D_FMA_DDD, D_LOG, D_TANH, D_WRAP, D_WRAP_PM_PI, D_SINCOS, D_EXP, D_RCP, D_ATAN, D_ACT,
+    D_MIXFWD, D_MIXBWD, D_NEW_PLAQ, D_ADJOINT, D_NOPS
+};
+__host__ __device__ constexpr int dual_nin(int op) {
+    return op == D_MUL || op == D_DIV_DD || op == D_DIV_SD || op == D_MIXFWD || op == D_MIXBWD || op == D_NEW_PLAQ ? 4
+         : op == D_FMA_SDD || op == D_FMA_DDD ? 6 : op == D_ADJOINT ? 14 : 2;
+}
+__host__ __device__ constexpr int dual_nout(int op) {
+    return op == D_SINCOS || op == D_ACT ? 4 : op == D_LOG || op == D_TANH || op == D_NEW_PLAQ ? 3 : op == D_MIXFWD ? 9
+         : op == D_MIXBWD ? 24 : op == D_ADJOINT ? 6 : 2;
+}
+
+// One mixture component as the kernels form it, (sn, cs) = ft_sincos(0.5 P) as they take them.  Forward (mix_forward of
+// flow_generic.hip, the transform stage of flow_dual.hip; probe_math's composite on double): y, D, 1 / D.  Backward (the adjoint
+// stages of the same files): sin P = 2.0 * sn * cs, then A, C, B and E as the tuned kernels stash them (Bn, En times invD2), B and
+// E as these backwards form them ((. invD) invD), and the D, 1 / D they rest on.
+template <typename T> struct CompOut { T v[8]; };
+template <typename T> __device__ __forceinline__ CompOut<T> comp_fwd(T P, T s) {
+    T sn, cs;
+    ft_sincos(0.5 * P, &sn, &cs);
+    const MixComp<T> m(s, cs, sn);
+    CompOut<T> o;
+    o.v[0] = m.y(); o.v[1] = m.D; o.v[2] = m.invD;
+    return o;
+}
+template <typename T> __device__ __forceinline__ CompOut<T> comp_bwd(T P, T s, int K) {
+    T sn, cs;
+    ft_sincos(0.5 * P, &sn, &cs);
+    const T sinP = 2.0 * sn * cs;
+    const MixComp<T> m(s, cs, sn);
+    CompOut<T> o;
+    o.v[0] = m.A(sinP, K); o.v[1] = m.C(K); o.v[2] = m.B(m.invD2()); o.v[3] = m.E(sinP, m.invD2());
+    o.v[4] = m.Bn() * m.invD * m.invD; o.v[5] = m.En(sinP) * m.invD * m.invD;
+    o.v[6] = m.D; o.v[7] = m.invD;
+    return o;
+}
+
+template <int OP>
+__global__ void k_dual(const double* __restrict__ in, double* __restrict__ out, int n, int act, int K) {
+    using fthmc::Dual;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t N = (size_t)n;
+    auto dl = [&](int p) { return Dual(in[p * N + i], in[(p + 1) * N + i]); };
+    auto put = [&](int q, Dual r) { out[q * N + i] = r.v; out[(q + 1) * N + i] = r.t; };
+    const Dual a = dl(0);
+    if (OP == D_MUL) put(0, a * dl(2));
+    if (OP == D_DIV_DD) put(0, a / dl(2));
+    if (OP == D_DIV_SD) put(0, a.v / dl(2));
+    if (OP == D_FMA_SDD) put(0, fma(a.v, dl(2), dl(4)));
+    if (OP == D_FMA_DDD) put(0, fma(a, dl(2), dl(4)));
+    if (OP == D_LOG) { put(0, log(a)); out[2 * N + i] = ::log(a.v); }             // plane 2: the double function on the value
+    if (OP == D_TANH) { put(0, tanh(a)); out[2 * N + i] = ::tanh(a.v); }
+    if (OP == D_WRAP) put(0, ft_wrap(a));
+    if (OP == D_WRAP_PM_PI) put(0, ft_wrap_pm_pi(a));
+    if (OP == D_SINCOS) { Dual sn, cs; ft_sincos(a, &sn, &cs); put(0, sn); put(2, cs); }
+    if (OP == D_EXP) put(0, ft_exp(a));
+    if (OP == D_RCP) put(0, ft_rcp(a));
+    if (OP == D_ATAN) put(0, ft_atan(a));
+    if (OP == D_ACT) { Dual h, d; act_eval(a, act, h, d); put(0, h); put(2, d); }
+    if (OP == D_MIXFWD) {
+        // in: P, s; out planes 0-5: y, D, 1 / D of comp_fwd<Dual>, 6-8: the values of comp_fwd<double>
+        const CompOut<Dual> o = comp_fwd<Dual>(a, dl(2));
+        const CompOut<double> od = comp_fwd<double>(a.v, in[2 * N + i]);
+        for (int q = 0; q < 3; ++q) { put(2 * q, o.v[q]); out[(6 + q) * N + i] = od.v[q]; }
+    }
+    if (OP == D_MIXBWD) {
+        // in: P, s; out planes 0-15: the eight results of comp_bwd<Dual>, 16-23: the values of comp_bwd<double>
+        const CompOut<Dual> o = comp_bwd<Dual>(a, dl(2), K);
+        const CompOut<double> od = comp_bwd<double>(a.v, in[2 * N + i], K);
+        for (int q = 0; q < 8; ++q) { put(2 * q, o.v[q]); out[(16 + q) * N + i] = od.v[q]; }
+    }
+    if (OP == D_NEW_PLAQ) {
+        // in: ysum, t; plane 2: the double instance
+        put(0, mix_new_plaq<Dual>(a, K, dl(2)));
+        out[2 * N + i] = mix_new_plaq<double>(a.v, K, in[2 * N + i]);
+    }
+    if (OP == D_ADJOINT) {
+        // in: gd, cbr, csum, esum, A_k, B_k, g; out: gs (0-1), dir_onto (2-3), the double instance's two values (4, 5)
+        const MixAdjoint<Dual> adj(a, dl(2), dl(4), dl(6));
+        put(0, adj.gs(dl(8), dl(10))); put(2, adj.dir_onto(dl(12)));
+        const MixAdjoint<double> ad(a.v, in[2 * N + i], in[4 * N + i], in[6 * N + i]);
+        out[4 * N + i] = ad.gs(in[8 * N + i], in[10 * N + i]); out[5 * N + i] = ad.dir_onto(in[12 * N + i]);
     }
 }
 
@@ -183,6 +274,14 @@ void math_dispatch(int op, std::integer_sequence<int, OPS...>, int n, int act, c
     ((op == OPS ? launch_math<OPS>(n, act, x, s, o0, o1, o2) : void()), ...);
 }
 
+template <int OP> void launch_dual(const double* in, double* out, int n, int act, int K) {
+    hipLaunchKernelGGL(k_dual<OP>, dim3((n + 255) / 256), dim3(256), 0, 0, in, out, n, act, K);
+}
+template <int... OPS>
+void dual_dispatch(int op, std::integer_sequence<int, OPS...>, const double* in, double* out, int n, int act, int K) {
+    ((op == OPS ? launch_dual<OPS>(in, out, n, act, K) : void()), ...);
+}
+
 template <int D> void launch_fdiv(int* out, int n) {
     hipLaunchKernelGGL(k_fdiv<D>, dim3((n + 255) / 256), dim3(256), 0, 0, out, n);
 }
@@ -218,6 +317,23 @@ int probe_math(int op, int act, const double* x, const double* s, double* o0, do
     math_dispatch(op, std::make_integer_sequence<int, P_NOPS>{}, n, act, dx, ds, d0, d1, d2);
     d.launched();
     d.out(o0, d0, N); d.out(o1, d1, N); d.out(o2, d2, N);
+    return (int)d.err;
+}
+
+// The dual-number ops (k_dual): in holds dual_nin(op) planes of n doubles, out dual_nout(op) planes; nin / nout are checked against
+// them.  act: the activation of D_ACT; K: the number of mixture components of D_MIXBWD / D_NEW_PLAQ (>= 1)
+int probe_dual_nops(void) { return D_NOPS; }
+int probe_dual(int op, int act, int K, const double* in, int nin, double* out, int nout, int n) {
+    if (op < 0 || op >= D_NOPS || n <= 0 || !in || !out || K < 1 || act < 0 || act > 2) return (int)hipErrorInvalidValue;
+    if (nin != dual_nin(op) || nout != dual_nout(op)) return (int)hipErrorInvalidValue;
+    Dev d;
+    const size_t N = (size_t)n;
+    const double* di = d.in(in, nin * N);
+    double* dout = d.alloc<double>(nout * N);
+    if (d.err != hipSuccess) return (int)d.err;
+    dual_dispatch(op, std::make_integer_sequence<int, D_NOPS>{}, di, dout, n, act, K);
+    d.launched();
+    d.out(out, dout, nout * N);
     return (int)d.err;
 }
 

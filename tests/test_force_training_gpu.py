@@ -99,6 +99,11 @@ def test_matches_the_oracle_double_backward(i):
     errs = [rel(r['F'], F_r), rel(r['force_sq'], fs_r), rel(r['gw'], gw_r)]
     print(f'L={L} B={B} layers={nl} {act} fused={ops.train_force_path(B, L, arch)}: errors (F, force_sq, gw)', errs)
     assert max(errs) < TOL, errs
+    # the same bound for every layer's every parameter tensor and every chain's force on its own (tests/second_order_cases.py)
+    import second_order_cases as C
+    each = C.per_tensor(C.split(r['gw'], flow), C.split(gw_r, flow))
+    each.update(C.per_chain(r['F'], F_r, 'F'))
+    assert C.hold(each, TOL, 'per tensor') < TOL
 
 
 def test_fused_kernels_agree_with_the_plain_dual_sweep_and_serve_their_shapes():

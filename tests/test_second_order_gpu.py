@@ -95,6 +95,15 @@ def test_vjps_match_the_oracle_double_backward(L, B, nl, act, hidden, k, n_mix, 
     ax, aw = ops.ft_action_vjp(D(x), w, nl, beta, D(gS), D(glogdet), act)
     errs = [rel(hx, hx_r), rel(hw, hw_r), rel(ax, ax_r), rel(aw, aw_r)]
     assert max(errs) < 1e-9, errs
+    # the same bound for every layer's every parameter tensor and every chain on its own (tests/second_order_cases.py): the global
+    # norm above lets a small tensor, a conv bias say, be wrong by its share of the largest
+    import second_order_cases as C
+    each = {}
+    for what, got, ref in (('d/dw <g, F>', hw, hw_r), ('d/dw action', aw, aw_r)):
+        each.update(C.per_tensor(C.split(got, flow), C.split(ref, flow), what))
+    each.update(C.per_chain(hx, hx_r, 'H g'))
+    each.update(C.per_chain(ax, ax_r, 'd/dx action'))
+    assert C.hold(each, 1e-9, 'per tensor') < 1e-9
 
 
 # ---------------------------------------------------------------- public API
