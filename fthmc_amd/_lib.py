@@ -21,6 +21,9 @@ LIB_PATH = os.environ.get('FTHMC_LIB') or os.path.join(_HERE, 'libfthmc_hip.so')
 W_PER_LAYER = 955
 ACT_CODES = {None: 0, 'silu': 0, 'swish': 0, 'relu': 1, 'leaky_relu': 2}
 MODE_MD, MODE_LITERAL = 0, 1
+# the MD integrators (include/fthmc_hip.h FTHMC_INT_*; csrc/integrator.h states them as schedules)
+INTEGRATORS = {'leapfrog': 0, 'omelyan': 1, 'force_gradient': 2}
+STAGE_KICK, STAGE_SHIFT = 0, 1
 
 _D = c_void_p          # device pointer
 _P = c_void_p
@@ -94,6 +97,14 @@ SIGNATURES = {
 # the `_v` twins of the whole-flow entry points: the same arguments + the caller's weight version (include/fthmc_hip.h)
 for _n in ('fthmc_flow_forward', 'fthmc_flow_reverse', 'fthmc_ft_action', 'fthmc_ft_force', 'fthmc_ft_leapfrog', 'fthmc_ft_trajectory'):
     SIGNATURES[_n + '_v'] = SIGNATURES[_n] + [c_uint64]
+# the entry points with the integrator as an argument: the plain ones behind nstep, the flowed `_v` twins before the weight version
+SIGNATURES['fthmc_integrator_forces'] = [c_int, c_int]
+SIGNATURES['fthmc_integrator_schedule'] = [c_int, c_double, c_int, ctypes.POINTER(c_double), ctypes.POINTER(c_int), ctypes.POINTER(c_double),
+                                           ctypes.POINTER(c_double), c_int]
+SIGNATURES['fthmc_md'] = SIGNATURES['fthmc_leapfrog'][:7] + [c_int] + SIGNATURES['fthmc_leapfrog'][7:]
+SIGNATURES['fthmc_hmc_trajectory_int'] = SIGNATURES['fthmc_hmc_trajectory'][:8] + [c_int] + SIGNATURES['fthmc_hmc_trajectory'][8:]
+SIGNATURES['fthmc_ft_md_v'] = SIGNATURES['fthmc_ft_leapfrog'] + [c_int, c_uint64]
+SIGNATURES['fthmc_ft_trajectory_int_v'] = SIGNATURES['fthmc_ft_trajectory'] + [c_int, c_uint64]
 _RESTYPE = {'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None

@@ -363,6 +363,34 @@ int ft_leapfrog_ws(const Ctx& C, const double* x, const double* v, const WS& w, 
     return FTHMC_OK;
 }
 
+// ft_leapfrog_ws generalised over a schedule (integrator.h): x += b0 v, then per stage one force evaluation and KICK(a, b) --
+// the kick kernel as it is -- or SHIFT(c): the shifted field goes to `xshift` and the next stage's force is evaluated there
+// (w.xa and w.va are untouched by it).  nl = 0 is the plain Wilson MD (launch_wilson_gp + kick).  Result in w.xa / w.va; xreg as
+// in ft_leapfrog_ws -- it may be `xshift` itself: nothing reads the shifted field once the kick behind it has its gP.
+int ft_md_ws(const Ctx& C, const double* x, const double* v, const WS& w, int nl, int B, int L, int act, double beta,
+             const Sched& sc, hipStream_t s, double* xshift, double* xreg = nullptr) {
+    FT_TRY(launch_axpy_copy(x, v, sc.b0, w.xa, w.va, w.n2, s));
+    const double* xe = w.xa;                                               // where this stage's force is evaluated
+    for (int it = 0; it < sc.n; ++it) {
+        const SchedStage st = sc.stage(it);
+        FT_TRY(force_gp(C, xe, w, nl, B, L, act, beta, -1.0, nullptr, s));
+        if (st.kind == FT_STAGE_SHIFT) {
+            FT_TRY(launch_shift_from_gp(w.gp, w.xa, xshift, B, L, st.a, s));
+            xe = xshift;
+        } else {
+            FT_TRY(launch_kick_from_gp(w.gp, w.va, w.xa, nullptr, B, L, st.a, st.b, s, it == sc.n - 1 ? xreg : nullptr));
+            xe = w.xa;
+        }
+    }
+    return FTHMC_OK;
+}
+
+// the schedule of an entry point's (integrator, dt, nstep): FTHMC_ERR_UNSUPPORTED for an unknown integrator
+inline int sched_of(int integrator, double dt, int nstep, Sched* sc) {
+    const int n = make_sched(integrator, dt, nstep, sc);
+    return n >= 1 ? FTHMC_OK : (n == -2 ? FTHMC_ERR_UNSUPPORTED : FTHMC_ERR_ARG);
+}
+
 // plain leapfrog; result pointers returned through xo/po (ping-pong inside the workspace)
 int leapfrog_ws(const double* x, const double* p, const WS& w, int B, int L, double beta, double dt,
                 int nstep, double** xo, double** po, hipStream_t s) {
@@ -600,6 +628,54 @@ int fthmc_hmc_trajectory(const double* x, const double* v, const double* u, int 
     FT_TRY(launch_kinetic(po, B, L, K, s));
     FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h1, B, s));
     return launch_metropolis(x, xo, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
+}
+
+int fthmc_integrator_forces(int integrator, int nstep) { return integrator_forces(integrator, nstep); }
+
+int fthmc_integrator_schedule(int integrator, double dt, int nstep, double* b0, int* kind, double* a, double* b, int cap) {
+    return expand_sched(integrator, dt, nstep, b0, kind, a, b, cap);
+}
+
+int fthmc_md(const double* x, const double* p, int B, int L, double beta, double dt, int nstep, int integrator,
+             double* x_out, double* p_out, void* ws, size_t ws_bytes, void* stream) {
+    if (integrator == FTHMC_INT_LEAPFROG) return fthmc_leapfrog(x, p, B, L, beta, dt, nstep, x_out, p_out, ws, ws_bytes, stream);
+    if (!x || !p || !x_out || !p_out || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(nullptr);
+    FT_WS(0, false);
+    FT_TRY(ft_md_ws(C, x, p, W, 0, B, L, 0, beta, sc, s, W.xb));
+    if (hipMemcpyAsync(x_out, W.xa, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(p_out, W.va, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
+    return FTHMC_OK;
+}
+
+int fthmc_hmc_trajectory_int(const double* x, const double* v, const double* u, int B, int L, double beta, double dt, int nstep,
+                             int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                             void* ws, size_t ws_bytes, void* stream) {
+    if (integrator == FTHMC_INT_LEAPFROG)
+        return fthmc_hmc_trajectory(x, v, u, B, L, beta, dt, nstep, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
+    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(nullptr);
+    // L <= 64 (x_new must not alias x): one persistent launch per trajectory, as fthmc_hmc_trajectory
+    if (L <= 64 && C.mfma && x_new != x)
+        return launch_hmc_trajectory_sched(x, v, u, B, L, beta, sc, x_new, dH, acc, H0, H1, s);
+    FT_WS(0, false);
+    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    FT_TRY(launch_action_charge(x, B, L, beta, S, nullptr, nullptr, s));
+    FT_TRY(launch_kinetic(v, B, L, K, s));
+    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h0, B, s));
+    // the flowed schedule with zero layers: the shifted field and then the regularized end point in W.xb
+    FT_TRY(ft_md_ws(C, x, v, W, 0, B, L, 0, beta, sc, s, W.xb, W.xb));
+    FT_TRY(launch_action_charge(W.xb, B, L, beta, S, nullptr, nullptr, s));
+    FT_TRY(launch_kinetic(W.va, B, L, K, s));
+    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h1, B, s));
+    return launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
 }
 
 int fthmc_flow_layer_fwd(const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
@@ -939,6 +1015,86 @@ int fthmc_ft_trajectory_v(const double* x, const double* v, const double* u, con
     FT_TRY(launch_kinetic(vend, B, L, K, s));
     FT_TRY(launch_lincomb(neu, 1.0, K, 0.5, 0.0, h1, B, s));
     // state of x_new without another sweep: select per chain
+    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s));
+    if (plaq && hipMemcpyAsync(plaq, sel + B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
+    if (Q && hipMemcpyAsync(Q, sel + 2 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
+    return FTHMC_OK;
+}
+
+int fthmc_ft_md_v(const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
+                  int act, double beta, double dt, int nstep, double* x_out, double* v_out,
+                  void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version) {
+    if (integrator == FTHMC_INT_LEAPFROG)
+        return fthmc_ft_leapfrog_v(x, v, w, arch, n_layers, B, L, act, beta, dt, nstep, x_out, v_out, ws, ws_bytes, stream, weights_version);
+    FT_TRY(check_flow_call(x && v && x_out && v_out && nstep >= 1, w, n_layers, B, L, act));
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(arch);
+    FT_WS(n_layers, false);
+    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
+    if (C.small(L, n_layers)) {
+        SmallArgs a = small_args(x, W, n_layers, B, act, beta, 2);
+        a.v = v; a.dt = dt; a.nstep = nstep; a.x_out = x_out; a.v_out = v_out;
+        return launch_ft_small_sched(a, sc, L, s);
+    }
+    FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, beta, sc, s, W.xb));
+    if (hipMemcpyAsync(x_out, W.xa, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(v_out, W.va, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
+    return FTHMC_OK;
+}
+
+// fthmc_ft_trajectory_v's MD branches with the MD of a schedule; the energies, the Metropolis step and the chaining are its own
+int fthmc_ft_trajectory_int_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
+                              int B, int L, int act, double beta, double dt, int nstep, int mode, double* x_new,
+                              double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
+                              const double* state_in, double* state_out,
+                              void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version) {
+    if (integrator == FTHMC_INT_LEAPFROG)
+        return fthmc_ft_trajectory_v(x, v, u, w, arch, n_layers, B, L, act, beta, dt, nstep, mode, x_new, dH, acc, H0, H1, plaq, Q,
+                                     state_in, state_out, ws, ws_bytes, stream, weights_version);
+    FT_TRY(check_flow_call(x && v && u && x_new && nstep >= 1, w, n_layers, B, L, act));
+    if (mode != FTHMC_MODE_MD) return FTHMC_ERR_UNSUPPORTED;        // FTHMC_MODE_LITERAL discards the MD: no integrator to choose
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(arch);
+    FT_WS(n_layers, false);
+    double* K = W.scal + (size_t)SC_K * B;
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    double* old = W.scal + (size_t)SC_OLD0 * B;
+    double* neu = W.scal + (size_t)SC_NEW0 * B;
+    double* sel = state_out ? state_out : W.scal + (size_t)SC_S * B;
+    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
+    if (C.small(L, n_layers)) {                                      // the whole trajectory in one launch
+        SmallArgs a = small_args(x, W, n_layers, B, act, beta, 3);
+        a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
+        a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
+        return launch_ft_small_sched(a, sc, L, s);
+    }
+    if (C.A.is_default() && n_layers > 0) {                          // tuned kernels: the shifted field lives in the proposal buffer
+        const int np = flow_fwd_geom(C.mfma).ntiles(L);
+        if (!state_in) FT_TRY(sweep_forward(C, x, W, n_layers, B, L, act, nullptr, s, false, false, true));
+        FT_TRY(launch_traj_energy(phys_field(x, W, n_layers), B, L, beta, W.lj_part, np, n_layers, state_in, v, old, h0, s));
+        FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, beta, sc, s, W.xb, W.xb));
+        FT_TRY(sweep_forward(C, W.xb, W, n_layers, B, L, act, nullptr, s, false, false, true));
+        FT_TRY(launch_traj_energy(phys_field(W.xb, W, n_layers), B, L, beta, W.lj_part, np, n_layers, nullptr, W.va, neu, h1, s));
+        return launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s, plaq, Q);
+    }
+    if (state_in) {
+        if (hipMemcpyAsync(old, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return FTHMC_ERR_LAUNCH;
+    } else {
+        FT_TRY(eval_action(C, x, W, n_layers, B, L, act, beta, old, nullptr, old + B, old + 2 * B, s));
+    }
+    FT_TRY(launch_kinetic(v, B, L, K, s));
+    FT_TRY(launch_lincomb(old, 1.0, K, 0.5, 0.0, h0, B, s));
+    FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, beta, sc, s, W.xb, W.xb));
+    FT_TRY(eval_action(C, W.xb, W, n_layers, B, L, act, beta, neu, nullptr, neu + B, neu + 2 * B, s));
+    FT_TRY(launch_kinetic(W.va, B, L, K, s));
+    FT_TRY(launch_lincomb(neu, 1.0, K, 0.5, 0.0, h1, B, s));
     FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s));
     if (plaq && hipMemcpyAsync(plaq, sel + B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return FTHMC_ERR_LAUNCH;

@@ -130,6 +130,18 @@ __device__ __forceinline__ ColdArgs& cold() {
     return *p;
 }
 
+// The schedule-driven instance (k_ft_small<..., SCHED>) takes the same block with the MD schedule behind it (integrator.h): the other
+// instances' argument block, and with it their code, is what it was
+struct SmallArgsSched : SmallArgs { Sched sched; };
+typedef const __attribute__((address_space(4))) SmallArgsSched ColdSched;
+__device__ __forceinline__ ColdSched& cold_sched() {
+    ColdSched* p = (ColdSched*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+template <bool SCHED> struct SmallArgsOf { typedef SmallArgs type; };
+template <> struct SmallArgsOf<true> { typedef SmallArgsSched type; };
+
 // the stash values a backward pass multiplies by, loaded one pass ahead
 struct BwdPre { double tcv[4 * NMIX], fcs, fsn, d2v[4], d1v[4]; };
 
@@ -725,12 +737,15 @@ enum { SM_ACTION = 0, SM_FORCE = 1, SM_LEAPFROG = 2, SM_TRAJ = 3, SM_TRAIN = 4 }
 //   training:    ONE sweep that is both (fthmc/train.py:191-210): every layer forward with the stash (+ h1, h2) AND log J,
 //                the Wilson action of the flowed field -> x, logq, logp; the seed (beta / B) sin P, every layer backward with
 //                dL/dlogJ = -1 / B, writing each layer's pre-activation gradients for k_flow_wgrad
+//   SCHED:       the leapfrog / trajectory of another integrator (integrator.h): x += b0 v; FORCE sweep `it` is stage `it` of the
+//                schedule -- KICK(a, b): v -= a F; x += b v, or SHIFT(c): the thread keeps c F of its site in two registers and
+//                the NEXT sweep copies XL - shift into X where it copies XL (XL and the momenta are untouched)
 // The sweep loop has ONE call site of the layer bodies (the kernel is register- and code-size-bound otherwise).
 // TRAJ: the launch is a whole trajectory (fthmc_ft_trajectory: the hot entry point of the small lattices): the other entry
 // points' branches leave that instance.  DBG: the stage stamps of tools/small_profile.py (A.dbg) exist in their own instance
 // of the generic kernel only: compiled out, config 2 runs 4 % faster (0.497 -> 0.477 ms per trajectory).
-template <int L, bool TRAIN, bool TRAJ, bool DBG>
-__global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(SmallArgs Aarg) {
+template <int L, bool TRAIN, bool TRAJ, bool DBG, bool SCHED>
+__global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArgsOf<SCHED>::type Aarg) {
     using G = GS<L>;
     constexpr int N = G::N;
     __shared__ __attribute__((aligned(16))) double sm[G::SIZE];
@@ -749,7 +764,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(SmallArgs Aarg) {
     if (hot.dbg && tid < 32) reinterpret_cast<long long*>(sm + G::PROF)[tid] = 0;
     const bool moves = mode == SM_LEAPFROG || mode == SM_TRAJ;
     constexpr bool train = TRAIN;
-    const int nforce = mode == SM_ACTION ? 0 : ((mode == SM_FORCE || train) ? 1 : Aarg.nstep);
+    int nforce = mode == SM_ACTION ? 0 : ((mode == SM_FORCE || train) ? 1 : Aarg.nstep);
+    if constexpr (SCHED) nforce = Aarg.sched.n;                            // one FORCE sweep per stage
+    double sh0 = 0.0, sh1 = 0.0;                                           // SCHED: c F of the own site behind a SHIFT sweep
     // sweeps it = first .. last: it < 0 and it == nforce are EVAL sweeps, 0 <= it < nforce FORCE sweeps
     const int first = (mode == SM_ACTION || (mode == SM_TRAJ && !have_state)) ? -1 : 0;
     const int last = mode == SM_TRAJ ? nforce : (mode == SM_ACTION ? -1 : nforce - 1);
@@ -770,10 +787,17 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(SmallArgs Aarg) {
 
     for (int it = first; it <= last; ++it) {
         const bool force = it >= 0 && it < nforce;
+        if constexpr (SCHED) {
+            if (it == 0 && tid < N) { const double b0 = cold_sched().sched.b0; sm[G::XL + tid] += b0 * v0; sm[G::XL + N + tid] += b0 * v1; }
+        } else
         if (it == 0 && moves && tid < N) { sm[G::XL + tid] += 0.5 * dt * v0; sm[G::XL + N + tid] += 0.5 * dt * v1; }   // own site
         if (it == nforce && mode == SM_TRAJ && tid < N) {                  // end of the MD: regularize (ipynb/ft_hmc.py:426)
             sm[G::XL + tid] = ft_regularize(sm[G::XL + tid]); sm[G::XL + N + tid] = ft_regularize(sm[G::XL + N + tid]);
         }
+        if constexpr (SCHED) {                                             // behind a SHIFT sweep: the shifted field, once
+            if (tid < N) { sm[G::X + tid] = sm[G::XL + tid] - sh0; sm[G::X + N + tid] = sm[G::XL + N + tid] - sh1; }
+            sh0 = 0.0; sh1 = 0.0;
+        } else
         if (tid < N) { sm[G::X + tid] = sm[G::XL + tid]; sm[G::X + N + tid] = sm[G::XL + N + tid]; }
         lds_barrier();
         C.stamp(16);
@@ -808,6 +832,18 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(SmallArgs Aarg) {
             if (tid < N) {
                 double f0, f1;
                 C.site_force(f0, f1);
+                if constexpr (SCHED) {
+                    ColdSched& S = cold_sched();
+                    const int ns = S.sched.n, k = it % S.sched.nper;       // Sched::stage(it), read from the kernarg segment
+                    const __attribute__((address_space(4))) SchedStage* st =
+                        it == ns - 1 ? &S.sched.last : (it == 0 ? &S.sched.first : &S.sched.per[k]);
+                    const double sa = st->a, sb = st->b;
+                    if (st->kind == FT_STAGE_SHIFT) { sh0 = sa * f0; sh1 = sa * f1; }
+                    else {
+                        v0 -= sa * f0; v1 -= sa * f1;
+                        sm[G::XL + tid] += sb * v0; sm[G::XL + N + tid] += sb * v1;
+                    }
+                } else
                 if (mode == SM_FORCE) { double* F = cold().F + (size_t)b * 2 * N; F[tid] = f0; F[N + tid] = f1; }
                 else {
                     v0 -= dt * f0; v1 -= dt * f1;
@@ -885,41 +921,58 @@ int get_small_path() {
 }
 bool ft_small_shape(int L, int nl) { return nl >= 1 && (L == 8 || L == 12 || L == 16); }
 
+// leapfrog / trajectory of a schedule (integrator.h): the SCHED instance, mode at run time
+int launch_ft_small_sched(const SmallArgs& a0, const Sched& sched, int L, hipStream_t s) {
+    const dim3 grid(a0.B), block(NT);
+    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
+    if ((a0.mode != SM_TRAJ && a0.mode != SM_LEAPFROG) || a0.dbg || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
+    SmallArgsSched a;
+    static_cast<SmallArgs&>(a) = a0;
+    a.sched = sched;
+    switch (L) {
+        case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, false, true>), grid, block, 0, s, a); break;
+        case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, false, true>), grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, false, true>), grid, block, 0, s, a); break;
+        default: return FTHMC_ERR_UNSUPPORTED;
+    }
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
+
 int launch_ft_small(const SmallArgs& a, int L, hipStream_t s) {
     const dim3 grid(a.B), block(NT);
     if (!flow_stash_fits32(a.B, L, true)) return FTHMC_ERR_UNSUPPORTED;                  // stash_view: 32-bit plane offsets
     if (a.mode == SM_TRAIN) {
         if (!a.gz) return FTHMC_ERR_ARG;
         switch (L) {
-            case 8: hipLaunchKernelGGL((k_ft_small<8, true, false, false>), grid, block, 0, s, a); break;
-            case 12: hipLaunchKernelGGL((k_ft_small<12, true, false, false>), grid, block, 0, s, a); break;
-            case 16: hipLaunchKernelGGL((k_ft_small<16, true, false, false>), grid, block, 0, s, a); break;
+            case 8: hipLaunchKernelGGL((k_ft_small<8, true, false, false, false>), grid, block, 0, s, a); break;
+            case 12: hipLaunchKernelGGL((k_ft_small<12, true, false, false, false>), grid, block, 0, s, a); break;
+            case 16: hipLaunchKernelGGL((k_ft_small<16, true, false, false, false>), grid, block, 0, s, a); break;
             default: return FTHMC_ERR_UNSUPPORTED;
         }
         FT_LAUNCH_CHECK(); return FTHMC_OK;
     }
     if (a.dbg) {                                            // diagnostic launches: the generic kernel with its stage stamps
         switch (L) {
-            case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, true>), grid, block, 0, s, a); break;
-            case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, true>), grid, block, 0, s, a); break;
-            case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, true>), grid, block, 0, s, a); break;
+            case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, true, false>), grid, block, 0, s, a); break;
+            case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, true, false>), grid, block, 0, s, a); break;
+            case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, true, false>), grid, block, 0, s, a); break;
             default: return FTHMC_ERR_UNSUPPORTED;
         }
         FT_LAUNCH_CHECK(); return FTHMC_OK;
     }
     if (a.mode == SM_TRAJ) {
         switch (L) {
-            case 8: hipLaunchKernelGGL((k_ft_small<8, false, true, false>), grid, block, 0, s, a); break;
-            case 12: hipLaunchKernelGGL((k_ft_small<12, false, true, false>), grid, block, 0, s, a); break;
-            case 16: hipLaunchKernelGGL((k_ft_small<16, false, true, false>), grid, block, 0, s, a); break;
+            case 8: hipLaunchKernelGGL((k_ft_small<8, false, true, false, false>), grid, block, 0, s, a); break;
+            case 12: hipLaunchKernelGGL((k_ft_small<12, false, true, false, false>), grid, block, 0, s, a); break;
+            case 16: hipLaunchKernelGGL((k_ft_small<16, false, true, false, false>), grid, block, 0, s, a); break;
             default: return FTHMC_ERR_UNSUPPORTED;
         }
         FT_LAUNCH_CHECK(); return FTHMC_OK;
     }
     switch (L) {
-        case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, false>), grid, block, 0, s, a); break;
-        case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, false>), grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, false>), grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, false, false>), grid, block, 0, s, a); break;
+        case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, false, false>), grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, false, false>), grid, block, 0, s, a); break;
         default: return FTHMC_ERR_UNSUPPORTED;
     }
     FT_LAUNCH_CHECK(); return FTHMC_OK;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "integrator.h"
 
 namespace fthmc {
 
@@ -34,6 +35,11 @@ int launch_hmc_trajectory_fused(const double* x, const double* v, const double* 
                                 double* H1, hipStream_t s);
 int launch_kick_from_gp(const double* gp, double* v, double* xq, double* Fout, int B, int L,
                         double dt, double a, hipStream_t s, double* xreg = nullptr);   // xreg: also regularize(x') (end of the MD)
+// the SHIFT stage of a schedule (integrator.h): xs = x - c adj(gP); x, v and gP are only read
+int launch_shift_from_gp(const double* gp, const double* x, double* xs, int B, int L, double c, hipStream_t s);
+// plain HMC of a schedule in one launch (L <= 64): launch_hmc_trajectory_fused's twin
+int launch_hmc_trajectory_sched(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sched,
+                                double* x_new, double* dH, double* acc, double* H0, double* H1, hipStream_t s);
 // the scalars of one end of a flowed trajectory in one launch: (S_eff, plaq, Q) of the flowed field (or carried over: state_in)
 // and H = S_eff + sum v^2 / 2
 int launch_traj_energy(const double* xphys, int B, int L, double beta, const double* lj_part, int np, int nsets,
@@ -333,6 +339,7 @@ struct SmallArgs {
 };
 bool ft_small_shape(int L, int n_layers);       // the fused path is built for this lattice size (default net shape, MFMA kernels)
 int launch_ft_small(const SmallArgs& a, int L, hipStream_t s);
+int launch_ft_small_sched(const SmallArgs& a, const Sched& sched, int L, hipStream_t s);   // mode 2 / 3 of a schedule (integrator.h)
 void set_small_path(int v);
 int get_small_path();
 // 0: VALU kernels everywhere; 1 (default): MFMA kernels for forward and backward-wrt-x

@@ -26,3 +26,10 @@ ifneq ($(TORCHDIR),)
 endif
 	@echo "sanitizer runtime to preload: $(SANRT)"
 
+# The schedule header on its own (integrator.h: plain C++): tests/hip/integrator_walk.cpp as a stand-alone program with the
+# sanitizer runtimes linked in (nothing to preload), built where SANWALK says and run by tests/test_integrators.py
+SANWALK ?= $(SANDIR)/integrator_walk
+san_integrator:
+	mkdir -p $(dir $(SANWALK))
+	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	  -I. ../../tests/hip/integrator_walk.cpp -o $(SANWALK)

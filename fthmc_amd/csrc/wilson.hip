@@ -411,6 +411,43 @@ __global__ __launch_bounds__(TR * 32) void k_kick_rows(const double* __restrict_
     }
 }
 
+// The SHIFT stage of a schedule (integrator.h): xs = x - c adj(gP), the field at which the next stage evaluates its force
+// (force-gradient integrator: the gradient term as one shifted re-evaluation).  k_kick_from_gp's walk and per-site arithmetic;
+// x, v and gP are only read.
+__global__ void k_shift_from_gp(const double* __restrict__ gp, const double* __restrict__ x, double* __restrict__ xs, int L, double c) {
+    const int b = blockIdx.y;
+    const int n = L * L;
+    const double* g = gp + (size_t)b * n;
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
+        const int i = s / L, j = s - i * L;
+        const int im = i == 0 ? L - 1 : i - 1, jm = j == 0 ? L - 1 : j - 1;
+        const double gc = g[s];
+        const double f0 = gc - g[i * L + jm];
+        const double f1 = g[im * L + j] - gc;
+        const size_t s0 = (size_t)b * 2 * n + s, s1 = s0 + n;
+        xs[s0] = x[s0] - c * f0; xs[s1] = x[s1] - c * f1;
+    }
+}
+
+// ... on row strips (k_kick_rows' tiling: 16-byte accesses, the left neighbour from the adjacent lane); bit-identical to k_shift_from_gp
+template <int TR>
+__global__ __launch_bounds__(TR * 32) void k_shift_rows(const double* __restrict__ gp, const double* __restrict__ x, double* __restrict__ xs,
+                                                        int L, double c) {
+    typedef double double2_t __attribute__((ext_vector_type(2)));
+    const int b = blockIdx.z, i = blockIdx.y * TR + (threadIdx.x >> 5), q = threadIdx.x & 31, j = blockIdx.x * 64 + 2 * q;
+    const int n = L * L;
+    const double* g = gp + (size_t)b * n;
+    const int im = i == 0 ? L - 1 : i - 1;
+    const double2_t gc = *reinterpret_cast<const double2_t*>(g + i * L + j), gu = *reinterpret_cast<const double2_t*>(g + im * L + j);
+    double gl = __shfl_up(gc.y, 1, 32);                                       // gP[i][j - 1]: the previous lane's second site
+    if (q == 0) gl = g[i * L + (j == 0 ? L - 1 : j - 1)];
+    const double2_t f0 = {gc.x - gl, gc.y - gc.x}, f1 = {gu.x - gc.x, gu.y - gc.y};
+    const size_t s0 = (size_t)b * 2 * n + (size_t)i * L + j, s1 = s0 + n;
+    const double2_t y0 = *reinterpret_cast<const double2_t*>(x + s0), y1 = *reinterpret_cast<const double2_t*>(x + s1);
+    *reinterpret_cast<double2_t*>(xs + s0) = double2_t{y0.x - c * f0.x, y0.y - c * f0.y};
+    *reinterpret_cast<double2_t*>(xs + s1) = double2_t{y1.x - c * f1.x, y1.y - c * f1.y};
+}
+
 // ---------------------------------------------------------------- Metropolis
 // Per chain: H1 = S1 + K1/2, dH = H1 - H0, acc = u < exp(-dH),
 // x_new = acc ? xform(x_prop) : x_old.   xform: 0 none, 1 regularize, 2 wrap.
@@ -632,6 +669,104 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory(const double* __restri
         }
 }
 
+// The same trajectory for any schedule (integrator.h): the same LDS plan and thread-to-site map, x += b0 v and then per stage
+//   beta sin P of the links in LDS;  KICK(a, b): v -= a F, x += b v  |  SHIFT(c): the thread keeps its own links in registers and
+//   puts x - c F in their place for the NEXT stage's beta sin P, whose kick first puts the kept links back: sx itself is as if
+//   never touched (restored bit for bit, not recomputed)
+__global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __restrict__ x, const double* __restrict__ v,
+                                                                const double* __restrict__ u, int L, double beta, fthmc::Sched sched,
+                                                                double* __restrict__ x_new, double* __restrict__ dH,
+                                                                double* __restrict__ acc, double* __restrict__ H0o,
+                                                                double* __restrict__ H1o) {
+    __shared__ double sx[2 * TJ_MAXL * TJ_MAXL];        // links
+    __shared__ double sp[TJ_MAXL * TJ_MAXL];            // beta sin P
+    __shared__ double red[16];
+    const int b = blockIdx.x, tid = threadIdx.x, n = L * L;
+    const double* xb = x + (size_t)b * 2 * n;
+    const double* vb = v + (size_t)b * 2 * n;
+    double v0[TJ_NSITE], v1[TJ_NSITE], k0[TJ_NSITE], k1[TJ_NSITE];
+    int st[TJ_NSITE], sjm[TJ_NSITE], sim[TJ_NSITE], sjp[TJ_NSITE], sip[TJ_NSITE];
+    double kin = 0.0;
+#pragma unroll
+    for (int k = 0; k < TJ_NSITE; ++k) {
+        const int s = tid + k * TJ_NT;
+        st[k] = s < n ? s : -1;
+        v0[k] = v1[k] = k0[k] = k1[k] = 0.0; sjm[k] = sim[k] = sjp[k] = sip[k] = 0;
+        if (s < n) {
+            const int i = s / L, j = s - i * L;
+            sjp[k] = i * L + (j + 1 == L ? 0 : j + 1);  sip[k] = (i + 1 == L ? 0 : i + 1) * L + j;
+            sjm[k] = i * L + (j == 0 ? L - 1 : j - 1);  sim[k] = (i == 0 ? L - 1 : i - 1) * L + j;
+            sx[s] = xb[s]; sx[n + s] = xb[n + s];
+            v0[k] = vb[s]; v1[k] = vb[n + s];
+            kin += v0[k] * v0[k] + v1[k] * v1[k];
+        }
+    }
+    __syncthreads();
+    auto action = [&]() {                                // -beta sum cos P over the chain (summation order of BatchAction)
+        double c = 0.0;
+#pragma unroll
+        for (int k = 0; k < TJ_NSITE; ++k)
+            if (st[k] >= 0) { double sn_, cs_; ft_sincos(sx[st[k]] + sx[n + sip[k]] - sx[sjp[k]] - sx[n + st[k]], &sn_, &cs_); c += cs_; }
+        return (-beta) * ft_block_sum(c, red);
+    };
+    const double h0 = action() + 0.5 * ft_block_sum(kin, red);
+#pragma unroll
+    for (int k = 0; k < TJ_NSITE; ++k)
+        if (st[k] >= 0) { sx[st[k]] += sched.b0 * v0[k]; sx[n + st[k]] += sched.b0 * v1[k]; }
+    bool shifted = false;                                // sx holds the shifted links of the own sites, k0 / k1 the links themselves
+    for (int it = 0; it < sched.n; ++it) {
+        const fthmc::SchedStage sg = sched.stage(it);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < TJ_NSITE; ++k)
+            if (st[k] >= 0) {
+                double sn_, cs_;
+                ft_sincos(sx[st[k]] - sx[n + st[k]] - sx[sjp[k]] + sx[n + sip[k]], &sn_, &cs_);
+                sp[st[k]] = beta * sn_;
+            }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < TJ_NSITE; ++k)
+            if (st[k] >= 0) {
+                const double sc = sp[st[k]];
+                const double f0 = sc - sp[sjm[k]], f1 = sp[sim[k]] - sc;
+                if (sg.kind == fthmc::FT_STAGE_SHIFT) {
+                    k0[k] = sx[st[k]]; k1[k] = sx[n + st[k]];
+                    sx[st[k]] = k0[k] - sg.a * f0; sx[n + st[k]] = k1[k] - sg.a * f1;
+                } else {
+                    v0[k] -= sg.a * f0; v1[k] -= sg.a * f1;
+                    const double y0 = shifted ? k0[k] : sx[st[k]], y1 = shifted ? k1[k] : sx[n + st[k]];
+                    sx[st[k]] = y0 + sg.b * v0[k]; sx[n + st[k]] = y1 + sg.b * v1[k];
+                }
+            }
+        shifted = sg.kind == fthmc::FT_STAGE_SHIFT;
+    }
+    kin = 0.0;
+#pragma unroll
+    for (int k = 0; k < TJ_NSITE; ++k)
+        if (st[k] >= 0) {
+            sx[st[k]] = ft_regularize(sx[st[k]]); sx[n + st[k]] = ft_regularize(sx[n + st[k]]);
+            kin += v0[k] * v0[k] + v1[k] * v1[k];
+        }
+    __syncthreads();
+    const double h1 = action() + 0.5 * ft_block_sum(kin, red);
+    const double d = h1 - h0;
+    const bool ok = u[b] < exp(-d);
+    if (tid == 0) {
+        if (dH) dH[b] = d;
+        if (acc) acc[b] = ok ? 1.0 : 0.0;
+        if (H0o) H0o[b] = h0;
+        if (H1o) H1o[b] = h1;
+    }
+    double* xo = x_new + (size_t)b * 2 * n;
+#pragma unroll
+    for (int k = 0; k < TJ_NSITE; ++k)
+        if (st[k] >= 0) {
+            xo[st[k]] = ok ? sx[st[k]] : xb[st[k]];
+            xo[n + st[k]] = ok ? sx[n + st[k]] : xb[n + st[k]];
+        }
+}
+
 int g_leap_rows = 1;     // FTHMC_LEAP_ROWS=0 in the environment: the 16 x 16-tile kernel for every L (A/B runs)
 
 inline int ew_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 2048 ? 2048 : (g ? g : 1)); }
@@ -738,6 +873,23 @@ int launch_kick_from_gp(const double* gp, double* v, double* xq, double* Fout, i
     }
     int gx = (L * L + 255) / 256; if (gx > 64) gx = 64;
     hipLaunchKernelGGL(k_kick_from_gp, dim3(gx, B), dim3(256), 0, s, gp, v, xq, Fout, L, dt, a, xreg);
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
+int launch_shift_from_gp(const double* gp, const double* x, double* xs, int B, int L, double c, hipStream_t s) {
+    if (L % 64 == 0 && g_leap_rows) {
+        constexpr int TR = 8;
+        hipLaunchKernelGGL(k_shift_rows<TR>, dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, gp, x, xs, L, c);
+        FT_LAUNCH_CHECK(); return FTHMC_OK;
+    }
+    int gx = (L * L + 255) / 256; if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(k_shift_from_gp, dim3(gx, B), dim3(256), 0, s, gp, x, xs, L, c);
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
+int launch_hmc_trajectory_sched(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sched,
+                                double* x_new, double* dH, double* acc, double* H0, double* H1, hipStream_t s) {
+    if (L > TJ_MAXL) return FTHMC_ERR_UNSUPPORTED;
+    if (sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
+    hipLaunchKernelGGL(k_hmc_trajectory_sched, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, beta, sched, x_new, dH, acc, H0, H1);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_traj_energy(const double* xphys, int B, int L, double beta, const double* lj_part, int np, int nsets,

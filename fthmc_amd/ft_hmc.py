@@ -9,6 +9,8 @@ Two reference quirks are explicit switches, defaults = what the m
   energy_mode   = 'per_chain'        H_b = S_eff,b + v_b^2 / 2;
                   'reference_literal' reproduces calc_energy ft_hmc.py:177-178
                                       (no 1/2, kinetic term summed over the whole batch)
+Beyond the reference: integrator = 'leapfrog' (default) | 'omelyan' | 'force_gradient' chooses the MD between the two energies
+(csrc/integrator.h; lfconfig.nstep steps of it cost ops.integrator_forces(integrator, nstep) force evaluations).
 """
 from __future__ import annotations
 
@@ -74,9 +76,12 @@ class LazyHistory(dict):
 
 class FieldTransformation(nn.Module):
     def __init__(self, flow: nn.ModuleList, config: TrainConfig, lfconfig: lfConfig,
-                 leapfrog_mode: str = 'md', energy_mode: str = 'per_chain'):
+                 leapfrog_mode: str = 'md', energy_mode: str = 'per_chain', integrator: str = 'leapfrog'):
         super().__init__()
         assert leapfrog_mode in ('md', 'reference_literal') and energy_mode in ('per_chain', 'reference_literal')
+        if ops.integrator_code(integrator) and leapfrog_mode != 'md':       # (an unknown name: ValueError)
+            raise ValueError(f'leapfrog_mode {leapfrog_mode!r} discards the MD: it goes with integrator=\'leapfrog\' only')
+        self.integrator = integrator
         self.flow = flow
         self.config = config
         self.lfconfig = lfconfig
@@ -165,7 +170,7 @@ class FieldTransformation(nn.Module):
         if self.leapfrog_mode == 'reference_literal':
             return x + 0.5 * self.dt * v, v
         return ops.ft_leapfrog(x, v, self.weights(x.device), len(self.flow), self.config.beta, self.dt,
-                               self.nstep, self._act)
+                               self.nstep, self._act, integrator=self.integrator)
 
     def _mode(self):
         return 'md' if self.leapfrog_mode == 'md' else 'literal'
@@ -189,7 +194,8 @@ class FieldTransformation(nn.Module):
             wkey = self._wkey(w)
             state = self._carried_state(x, wkey)                         # see _batch_hmc
             r = ops.ft_trajectory(x, v, u.reshape(1), w, len(self.flow), self.config.beta,
-                                  self.dt, self.nstep, self._act, mode=self._mode(), state_in=state, wkey=wkey)
+                                  self.dt, self.nstep, self._act, mode=self._mode(), state_in=state, wkey=wkey,
+                                  integrator=self.integrator)
             # the packaged code maps the end point with wrap, the notebook with regularize: same set
             xnew, acc, dh = r['x_new'], r['acc'][0] > 0.5, r['dH'][0]
             self._carry = (xnew, xnew._version, wkey, self.config.beta, r['state'])
@@ -226,7 +232,7 @@ class FieldTransformation(nn.Module):
             state = self._carried_state(x, wkey)
             r = ops.ft_trajectory(x, v, u, w, len(self.flow), self.config.beta, self.dt,
                                   self.nstep, self._act, mode=self._mode(), state_in=state,
-                                  groups=ops.default_groups(x.shape[0], x.shape[-1]), wkey=wkey)
+                                  groups=ops.default_groups(x.shape[0], x.shape[-1]), wkey=wkey, integrator=self.integrator)
             x_, dh, acc = r['x_new'], r['dH'], r['acc']
             x_ = x_.detach()
             self._carry = (x_, x_._version, wkey, self.config.beta, r['state'])
@@ -308,7 +314,7 @@ class FieldTransformation(nn.Module):
         # the weights' content version is part of what a capture is FOR: its launches carry it to the library, which checks
         # it on the device against the stamps in the workspaces (include/fthmc_hip.h "Weight versions")
         sig = (tuple(x.shape), dev, w.data_ptr(), nl, act, mode, beta, self.dt, self.nstep, G, batch,
-               ops.get_variant(), ops.get_small_path(), ops.weights_version(wkey))
+               ops.get_variant(), ops.get_small_path(), ops.weights_version(wkey), self.integrator)
         if self._loop is not None and self._loop.get('pending') is not None:
             self._loop['pending']()                                       # an unread history of the previous run: read it before its ring is reused
             self._loop['pending'] = None
@@ -387,6 +393,7 @@ class FieldTransformation(nn.Module):
 
     def _make_loop(self, x, w, nl, act, mode, beta, G, batch, sig, wkey):
         dev, B = x.device, x.shape[0]
+        integrator = self.integrator                                      # what this capture is for (part of `sig`)
         xs = torch.empty_like(x)
         v = torch.empty_like(x)
         u = torch.empty(B, dtype=torch.float64, device=dev)
@@ -410,7 +417,7 @@ class FieldTransformation(nn.Module):
             u.uniform_()
             # in place: the accepted field replaces x, its (S_eff, plaq, Q) the carried state (both read before they are written)
             ops.ft_trajectory(xs, v, u, w, nl, beta, self.dt, self.nstep, act, mode=mode, out=out, state_in=state, groups=G,
-                              side_streams=sides, wkey=wkey)
+                              side_streams=sides, wkey=wkey, integrator=integrator)
         loop = GraphLoop(enqueue, row, use_graph=True, stream=lstream)
         return {'sig': sig, 'loop': loop, 'x': xs, 'state': state, 'row': row, 'token': None, 'pending': None, 'sides': sides}
 

@@ -12,9 +12,12 @@ from .utils import qed_helpers as qed
 
 
 def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, figsize=None, use_title: bool = True,
-            save_data: bool = False, nplot: int = 10):
+            save_data: bool = False, nplot: int = 10, integrator: str = 'leapfrog'):
     """hmc.py:57-175: `param.nrun` experiments of `param.ntraj` trajectories each.
-    Returns (fields_arr, histories) with the reference's metric keys."""
+    Returns (fields_arr, histories) with the reference's metric keys.
+    integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h)."""
+    from . import ops
+    ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
     action = qed.BatchAction(param.beta)
     histories, fields_arr, run_times = {}, [], []
     for n in range(param.nrun):
@@ -24,7 +27,7 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
         xarr, history = [], {}
         for i in range(param.ntraj):
             t1 = time.time()
-            dH, exp_mdH, acc, x = qed.hmc(param, x, verbose=False)
+            dH, exp_mdH, acc, x = qed.hmc(param, x, verbose=False, integrator=integrator)
             qold = history['q'][-1] if 'q' in history else q
             qnew = qed.batch_charges(x)
             dq = torch.sqrt((qnew - qold) ** 2)

@@ -8,7 +8,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._lib import ACT_CODES, MODE_LITERAL, MODE_MD, W_PER_LAYER, FthmcError, check
+from ._lib import ACT_CODES, INTEGRATORS, MODE_LITERAL, MODE_MD, W_PER_LAYER, FthmcError, check
 
 _WS = {}           # (device index, stream) -> workspace tensor (grown on demand)
 _WS_CAPTURED = set()   # keys whose CURRENT workspace was handed out during a graph capture
@@ -459,17 +459,53 @@ def split_metrics(row, B: int) -> dict:
     return {'loss_dkl': row[0], 'ess': row[1], 'logp': r[0], 'logq': r[1], 'q': r[2], 'dq': r[3], 'plaq': r[4]}
 
 
-def leapfrog(x, p, beta: float, dt: float, nstep: int):
+def integrator_code(name) -> int:
+    """'leapfrog' | 'omelyan' | 'force_gradient' -> FTHMC_INT_* (include/fthmc_hip.h); anything else raises ValueError"""
+    try:
+        return INTEGRATORS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f'integrator: expected one of {sorted(INTEGRATORS)}, got {name!r}') from None
+
+
+def integrator_forces(name, nstep: int) -> int:
+    """force evaluations of one trajectory of `nstep` steps (host only: fthmc_integrator_forces)"""
+    n = _lib.load().fthmc_integrator_forces(integrator_code(name), int(nstep))
+    if n < 0:
+        raise ValueError(f'integrator_forces({name!r}, {nstep}): nstep must be >= 1')
+    return n
+
+
+def integrator_schedule(name, dt: float, nstep: int):
+    """-> (b0, [(kind, a, b), ...]): the MD as the library runs it (csrc/integrator.h) -- x += b0 v, then per stage
+    ('kick', a, b): v -= a g(x*); x += b v, or ('shift', c, 0.0): x* = x - c g(x) for the next stage.  Host only."""
+    import ctypes
+    n = integrator_forces(name, nstep)
+    b0 = ctypes.c_double()
+    kind, a, b = (ctypes.c_int * n)(), (ctypes.c_double * n)(), (ctypes.c_double * n)()
+    m = _lib.load().fthmc_integrator_schedule(integrator_code(name), float(dt), int(nstep), ctypes.byref(b0), kind, a, b, n)
+    if m != n:
+        raise FthmcError(f'fthmc_integrator_schedule: {m} stages where {n} were expected')
+    return b0.value, [('shift' if kind[i] == _lib.STAGE_SHIFT else 'kick', a[i], b[i]) for i in range(n)]
+
+
+def leapfrog(x, p, beta: float, dt: float, nstep: int, integrator='leapfrog'):
+    """the plain Wilson MD -> (x', p'); integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (csrc/integrator.h)"""
+    ic = integrator_code(integrator)
     x = _field(x); p = _field(p, 'p'); B, _, L, _ = x.shape
     xo, po = torch.empty_like(x), torch.empty_like(p)
     ws, nb = _ws(x, B, L, 0)
+    if ic:
+        check(_lib.load().fthmc_md(_p(x), _p(p), B, L, float(beta), float(dt), int(nstep), ic, _p(xo), _p(po),
+                                   ws, nb, _stream(x)), 'fthmc_md')
+        return xo, po
     check(_lib.load().fthmc_leapfrog(_p(x), _p(p), B, L, float(beta), float(dt), int(nstep), _p(xo), _p(po),
                                      ws, nb, _stream(x)), 'fthmc_leapfrog')
     return xo, po
 
 
-def hmc_trajectory(x, v, u, beta: float, dt: float, nstep: int, out=None):
+def hmc_trajectory(x, v, u, beta: float, dt: float, nstep: int, out=None, integrator='leapfrog'):
     """-> dict(x_new, dH, acc, H0, H1), per chain; out: optional dict with any of these to write into (x_new must not be x)."""
+    ic = integrator_code(integrator)
     x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
     if u.numel() != B:
         raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
@@ -480,6 +516,11 @@ def hmc_trajectory(x, v, u, beta: float, dt: float, nstep: int, out=None):
         raise FthmcError('out[\'x_new\']: expected a contiguous device tensor of the shape of x that is not x')
     dH, acc, H0, H1 = (_out_vec(out, k, B, x) for k in ('dH', 'acc', 'H0', 'H1'))
     ws, nb = _ws(x, B, L, 0)
+    if ic:
+        check(_lib.load().fthmc_hmc_trajectory_int(_p(x), _p(v), _p(u), B, L, float(beta), float(dt), int(nstep), ic,
+                                                   _p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x)),
+              'fthmc_hmc_trajectory_int')
+        return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1}
     check(_lib.load().fthmc_hmc_trajectory(_p(x), _p(v), _p(u), B, L, float(beta), float(dt), int(nstep),
                                            _p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x)),
           'fthmc_hmc_trajectory')
@@ -701,11 +742,18 @@ def ft_force_vjp(x, w, n_layers: int, beta: float, g, act='silu', arch=None, nee
     return gx, gw
 
 
-def ft_leapfrog(x, v, w, n_layers: int, beta: float, dt: float, nstep: int, act='silu', arch=None, wkey=None):
+def ft_leapfrog(x, v, w, n_layers: int, beta: float, dt: float, nstep: int, act='silu', arch=None, wkey=None,
+                integrator='leapfrog'):
+    """the MD in the latent field -> (x', v'); integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (csrc/integrator.h)"""
+    ic = integrator_code(integrator)
     x = _field(x); v = _field(v, 'v'); B, _, L, _ = x.shape
     w, ap, a = _wall(w, n_layers, arch)
     xo, vo = torch.empty_like(x), torch.empty_like(v)
     ws, nb = _ws(x, B, L, n_layers, arch=a)
+    if ic:
+        check(_lib.load().fthmc_ft_md_v(_p(x), _p(v), _p(w), ap, n_layers, B, L, act_code(act), float(beta), float(dt),
+                                        int(nstep), _p(xo), _p(vo), ws, nb, _stream(x), ic, weights_version(wkey)), 'fthmc_ft_md')
+        return xo, vo
     check(_lib.load().fthmc_ft_leapfrog_v(_p(x), _p(v), _p(w), ap, n_layers, B, L, act_code(act), float(beta), float(dt),
                                         int(nstep), _p(xo), _p(vo), ws, nb, _stream(x), weights_version(wkey)), 'fthmc_ft_leapfrog')
     return xo, vo
@@ -742,7 +790,7 @@ def _side_streams(device, n: int):
 
 def ft_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int, act='silu', mode='md',
                   out: Optional[dict] = None, state_in: Optional[torch.Tensor] = None, groups: int = 1, arch=None, wkey=None,
-                  side_streams=None):
+                  side_streams=None, integrator='leapfrog'):
     """One ftHMC trajectory per chain -> dict(x_new, dH, acc, H0, H1, plaq, Q, state).
 
     `out` may carry preallocated output tensors (same keys) so that a caller can replay the call
@@ -752,7 +800,13 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int,
     groups > 1 splits the chains into that many contiguous groups (a list gives the group sizes) whose trajectories
     run on concurrent streams (forked from and joined back into the current stream, each with its own workspace):
     chains are independent, and one group's kernels fill the CUs that the other's leave idle in every kernel
-    tail and dispatch gap.  Results do not depend on `groups`."""
+    tail and dispatch gap.  Results do not depend on `groups`.
+
+    integrator: 'leapfrog' | 'omelyan' | 'force_gradient' -- the MD between the two energies (csrc/integrator.h; nstep steps cost
+    integrator_forces(integrator, nstep) force evaluations); mode 'literal' discards the MD and takes 'leapfrog' only."""
+    ic = integrator_code(integrator)
+    if ic and mode not in ('md',):
+        raise ValueError(f'mode {mode!r} discards the MD: it goes with integrator=\'leapfrog\' only, got {integrator!r}')
     x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
     if u.numel() != B:
         raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
@@ -785,7 +839,8 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int,
             with torch.cuda.stream(st):
                 og = {k: t[a:b_] for k, t in out.items() if k != 'state'}
                 sg = state_in[:, a:b_].contiguous() if state_in is not None else None
-                ft_trajectory(x[a:b_], v[a:b_], u[a:b_], w, n_layers, beta, dt, nstep, act, mode, og, sg, arch=arch_, wkey=wkey)   # one group: no side streams
+                ft_trajectory(x[a:b_], v[a:b_], u[a:b_], w, n_layers, beta, dt, nstep, act, mode, og, sg, arch=arch_, wkey=wkey,
+                              integrator=integrator)                    # one group: no side streams
                 out['state'][:, a:b_].copy_(og['state'])
                 parts.append(og)                                        # keep the group's temporaries alive until the join
         for st in sides:
@@ -797,6 +852,13 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int,
             raise FthmcError(f'state_in: expected [3, {B}]')
     m = {'md': MODE_MD, 'literal': MODE_LITERAL, 'reference_literal': MODE_LITERAL}[mode]
     ws, nb = _ws(x, B, L, n_layers, arch=a)
+    if ic:
+        check(_lib.load().fthmc_ft_trajectory_int_v(_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), float(beta),
+                                                    float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']),
+                                                    _p(out['H0']), _p(out['H1']), _p(out['plaq']), _p(out['Q']),
+                                                    _p(state_in), _p(out['state']), ws, nb,
+                                                    _stream(x), ic, weights_version(wkey)), 'fthmc_ft_trajectory_int')
+        return out
     check(_lib.load().fthmc_ft_trajectory_v(_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), float(beta),
                                           float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']),
                                           _p(out['H0']), _p(out['H1']), _p(out['plaq']), _p(out['Q']),

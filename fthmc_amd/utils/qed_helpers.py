@@ -267,13 +267,13 @@ def force(param, x: torch.Tensor):
     return ops.wilson_force(_batched(x), param.beta).reshape(x.shape)
 
 
-def leapfrog(param, x: torch.Tensor, p: torch.Tensor, verbose: bool = True):
-    """qed_helpers.py:275-295."""
-    xo, po = ops.leapfrog(_batched(x), _batched(p), param.beta, param.dt, param.nstep)
+def leapfrog(param, x: torch.Tensor, p: torch.Tensor, verbose: bool = True, integrator: str = 'leapfrog'):
+    """qed_helpers.py:275-295.  integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h)."""
+    xo, po = ops.leapfrog(_batched(x), _batched(p), param.beta, param.dt, param.nstep, integrator=integrator)
     return xo.reshape(x.shape), po.reshape(p.shape)
 
 
-def hmc(param, x, verbose=True, v: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None):
+def hmc(param, x, verbose=True, v: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None, integrator: str = 'leapfrog'):
     """qed_helpers.py:298-311: one trajectory; the whole tensor is ONE system (one H, one
     accept), as in the reference.  `v`, `u` may be supplied for reproducible checks."""
     xb = _batched(x)
@@ -283,12 +283,12 @@ def hmc(param, x, verbose=True, v: Optional[torch.Tensor] = None, u: Optional[to
         u = torch.rand([], dtype=torch.float64, device=x.device)
     vb = _batched(v)
     if xb.shape[0] == 1:
-        r = ops.hmc_trajectory(xb, vb, u.reshape(1), param.beta, param.dt, param.nstep)
+        r = ops.hmc_trajectory(xb, vb, u.reshape(1), param.beta, param.dt, param.nstep, integrator=integrator)
         dH = r['dH'][0]
         acc = r['acc'][0] > 0.5
         return dH, torch.exp(-dH), acc, r['x_new'].reshape(x.shape)
     h0 = ops.wilson_action_charge(xb, param.beta)[0].sum() + 0.5 * ops.kinetic(vb).sum()
-    x_, v_ = ops.leapfrog(xb, vb, param.beta, param.dt, param.nstep)
+    x_, v_ = ops.leapfrog(xb, vb, param.beta, param.dt, param.nstep, integrator=integrator)
     xr = ops.regularize(x_)
     dH = ops.wilson_action_charge(xr, param.beta)[0].sum() + 0.5 * ops.kinetic(v_).sum() - h0
     exp_mdH = torch.exp(-dH)
@@ -297,9 +297,18 @@ def hmc(param, x, verbose=True, v: Optional[torch.Tensor] = None, u: Optional[to
     return dH, exp_mdH, acc, newx.reshape(x.shape)
 
 
+def ft_leapfrog(param, flow, x: torch.Tensor, p: torch.Tensor, integrator: str = 'leapfrog'):
+    """ipynb/ft_hmc.py:394-418: the MD in the latent field with the flowed force -> (x', p').
+    integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h)."""
+    xb = _batched(x)
+    w, nl, act = flow_weights(flow, xb.device), len(flow), flow_activation(flow)
+    xo, po = ops.ft_leapfrog(xb, _batched(p), w, nl, param.beta, param.dt, param.nstep, act, integrator=integrator)
+    return xo.reshape(x.shape), po.reshape(p.shape)
+
+
 # ---------------------------------------------------------------- ftHMC on the physical field
 def ft_hmc(param, flow, field: torch.Tensor, v: Optional[torch.Tensor] = None, u: Optional[torch.Tensor] = None,
-           tol: float = 1e-12):
+           tol: float = 1e-12, integrator: str = 'leapfrog'):
     """ipynb/ft_hmc.py:420-435: one ftHMC trajectory that starts and ends on the PHYSICAL field:
     x = F^-1(field); momenta; leapfrog in the latent field with ft_force (`:394-418`); xr = regularize(x_);
     accept on u < exp(-dH); return F(newx).  Like the notebook the whole tensor is ONE system (one H,
@@ -316,11 +325,11 @@ def ft_hmc(param, flow, field: torch.Tensor, v: Optional[torch.Tensor] = None, u
         u = torch.rand([], dtype=torch.float64, device=x.device)
     vb = _batched(v)
     if x.shape[0] == 1:
-        r = ops.ft_trajectory(x, vb, u.reshape(1), w, nl, param.beta, param.dt, param.nstep, act, mode='md')
+        r = ops.ft_trajectory(x, vb, u.reshape(1), w, nl, param.beta, param.dt, param.nstep, act, mode='md', integrator=integrator)
         dH, acc, newx = r['dH'][0], r['acc'][0] > 0.5, r['x_new']
     else:
         h0 = ops.ft_action(x, w, nl, param.beta, act)[0].sum() + 0.5 * ops.kinetic(vb).sum()
-        x_, v_ = ops.ft_leapfrog(x, vb, w, nl, param.beta, param.dt, param.nstep, act)
+        x_, v_ = ops.ft_leapfrog(x, vb, w, nl, param.beta, param.dt, param.nstep, act, integrator=integrator)
         xr = ops.regularize(x_)
         dH = ops.ft_action(xr, w, nl, param.beta, act)[0].sum() + 0.5 * ops.kinetic(v_).sum() - h0
         acc = u < torch.exp(-dH)
@@ -331,7 +340,7 @@ def ft_hmc(param, flow, field: torch.Tensor, v: Optional[torch.Tensor] = None, u
 
 
 def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[str] = None, verbose: bool = False,
-           use_graph: Optional[bool] = None):
+           use_graph: Optional[bool] = None, integrator: str = 'leapfrog'):
     """ipynb/ft_hmc.py:437-487: `param.nrun` x `param.ntraj` physical-field ftHMC trajectories of one
     configuration [2, L, L].  Returns (field, history) with per-trajectory dH, exp_mdH, acc, plaq, topo
     (the notebook returns the field and keeps the histories in module globals); the status lines it prints
@@ -342,6 +351,7 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
     off): the notebook's loop synchronises five times per trajectory, this one not at all; the histories and the log are
     written when the loop has run.  Same draws, identical numbers."""
     import os
+    ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
     if field is None:
         field = param.initializer()[0]
     history = {k: [] for k in ('dH', 'exp_mdH', 'acc', 'plaq', 'topo')}
@@ -363,7 +373,7 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
         put(f'Initial configuration:  plaq: {float(plaq[0])}  topo: {float(Q[0])} {tuple(field.shape)}\n')
         ntot = param.nrun * param.ntraj
         if use_graph and field.is_cuda and ntot > 0:
-            field, rows = _ft_run_captured(param, flow, field, ntot)
+            field, rows = _ft_run_captured(param, flow, field, ntot, integrator=integrator)
             for k, (dH, acc, plaq_, topo, exp_mdH) in enumerate(rows.tolist()):
                 for key, val in zip(history, (dH, exp_mdH, float(acc > 0.5), plaq_, topo)):
                     history[key].append(val)
@@ -371,7 +381,7 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
         else:
             for n in range(param.nrun):
                 for i in range(param.ntraj):
-                    dH, exp_mdH, acc, field_run = ft_hmc(param, flow, field.reshape((1,) + tuple(field.shape[-3:])))
+                    dH, exp_mdH, acc, field_run = ft_hmc(param, flow, field.reshape((1,) + tuple(field.shape[-3:])), integrator=integrator)
                     field = field_run[0]
                     S, Q, plaq = ops.wilson_action_charge(field_run, param.beta)
                     for k, val in zip(history, (dH, exp_mdH, float(bool(acc)), float(plaq[0]), float(Q[0]))):
@@ -383,7 +393,7 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
     return field, history
 
 
-def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1e-12):
+def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1e-12, integrator: str = 'leapfrog'):
     """the loop of ft_run as one captured sequence per trajectory -> (final field [2, L, L], rows [ntot, 5] on the host:
     dH, acc, plaq, Q, exp(-dH))"""
     from ..graph_loop import GraphLoop
@@ -406,7 +416,7 @@ def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1
         x = ops.flow_reverse(fs, w, nl, act, tol=tol, wkey=wkey)[0]      # x = F^-1(field)
         v.normal_()                                                      # randn_like(x), then rand([]): ipynb/ft_hmc.py:423-424
         u.uniform_()
-        ops.ft_trajectory(x, v, u, w, nl, param.beta, param.dt, param.nstep, act, mode='md', out=res, wkey=wkey)
+        ops.ft_trajectory(x, v, u, w, nl, param.beta, param.dt, param.nstep, act, mode='md', out=res, wkey=wkey, integrator=integrator)
         fs.copy_(ops.flow_forward(res['x_new'], w, nl, act, wkey=wkey)[0])   # newfield = F(newx)
         ops.wilson_action_charge(fs, param.beta, out=obs)
         torch.exp(torch.neg(row[0:1]), out=row[4:5])

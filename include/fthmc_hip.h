@@ -328,6 +328,48 @@ int fthmc_ft_trajectory_v(const double* x, const double* v, const double* u, con
                         const double* state_in, double* state_out,
                         void* ws, size_t ws_bytes, void* stream, uint64_t weights_version);
 
+/* ---- MD integrators ------------------------------------------------------ */
+/* The MD of a trajectory as a schedule (csrc/integrator.h): an initial drift x += b0 v, then stages, each one force evaluation;
+ * g = the gradient of the action (what the kicks subtract):
+ *   KICK(a, b):  v -= a g(x*); x += b v     (x* = x, or the shifted field if a SHIFT stage came just before)
+ *   SHIFT(c):    x~ = x - c g(x)            (the next stage evaluates g at x~; x and v are untouched)
+ * FTHMC_INT_LEAPFROG:        b0 = dt/2; nstep x KICK(dt, dt), the last b = dt/2                              nstep forces
+ * FTHMC_INT_OMELYAN:         2nd-order minimum norm, position version, lambda = 0.1931833275037836: b0 = lambda dt; per step
+ *                            KICK(dt/2, (1 - 2 lambda) dt), KICK(dt/2, 2 lambda dt); the very last b = lambda dt     2 nstep forces
+ * FTHMC_INT_FORCE_GRADIENT:  4th order, B A B_FG A B with the end kicks of neighbouring steps merged and the force-gradient
+ *                            term as one shifted re-evaluation of the force: b0 = 0; KICK(dt/6, dt/2); per step
+ *                            SHIFT(dt^2/24), KICK(2dt/3, dt/2); between steps KICK(dt/3, dt/2); last KICK(dt/6, 0)   3 nstep + 1 forces */
+#define FTHMC_INT_LEAPFROG        0
+#define FTHMC_INT_OMELYAN         1
+#define FTHMC_INT_FORCE_GRADIENT  2
+#define FTHMC_STAGE_KICK          0
+#define FTHMC_STAGE_SHIFT         1
+/* Host only.  Force evaluations (= stages) per trajectory; -2 for an unknown integrator, -1 for nstep < 1 (or a count beyond int). */
+int fthmc_integrator_forces(int integrator, int nstep);
+/* Host only.  The expanded schedule: *b0 and kind[i], a[i], b[i] of stage i (a SHIFT stage: a = c, b = 0); `cap` = length of the
+ * arrays.  Returns the number of stages; fthmc_integrator_forces' codes, or -3 if cap is too small or a pointer is null -- nothing
+ * is written then. */
+int fthmc_integrator_schedule(int integrator, double dt, int nstep, double* b0, int* kind, double* a, double* b, int cap);
+/* fthmc_leapfrog / fthmc_hmc_trajectory with the integrator as an argument.  FTHMC_INT_LEAPFROG delegates to them (bit-identical);
+ * an unknown integrator: FTHMC_ERR_UNSUPPORTED.  ws as theirs. */
+int fthmc_md(const double* x, const double* p, int B, int L, double beta, double dt, int nstep, int integrator,
+             double* x_out, double* p_out, void* ws, size_t ws_bytes, void* stream);
+int fthmc_hmc_trajectory_int(const double* x, const double* v, const double* u, int B, int L, double beta, double dt, int nstep,
+                             int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                             void* ws, size_t ws_bytes, void* stream);
+/* fthmc_ft_leapfrog_v / fthmc_ft_trajectory_v with the integrator as an argument (before weights_version).  FTHMC_INT_LEAPFROG
+ * delegates to them (bit-identical); FTHMC_MODE_LITERAL with another integrator (that mode discards the MD) and an unknown
+ * integrator: FTHMC_ERR_UNSUPPORTED.  ws as theirs: fthmc_ws_bytes. */
+int fthmc_ft_md_v(const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int n_layers,
+                  int B, int L, int act, double beta, double dt, int nstep,
+                  double* x_out, double* v_out, void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version);
+int fthmc_ft_trajectory_int_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch,
+                              int n_layers, int B, int L, int act, double beta, double dt, int nstep,
+                              int mode, double* x_new, double* dH, double* acc,
+                              double* H0, double* H1, double* plaq, double* Q,
+                              const double* state_in, double* state_out,
+                              void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version);
+
 /* ---- training ------------------------------------------------------------ */
 /* Reverse-KL loss pieces and weight gradients for a fixed prior draw xi
  * (fthmc/train.py:191-210, fthmc/utils/samplers.py:40-56):
