@@ -105,6 +105,13 @@ SIGNATURES['fthmc_md'] = SIGNATURES['fthmc_leapfrog'][:7] + [c_int] + SIGNATURES
 SIGNATURES['fthmc_hmc_trajectory_int'] = SIGNATURES['fthmc_hmc_trajectory'][:8] + [c_int] + SIGNATURES['fthmc_hmc_trajectory'][8:]
 SIGNATURES['fthmc_ft_md_v'] = SIGNATURES['fthmc_ft_leapfrog'] + [c_int, c_uint64]
 SIGNATURES['fthmc_ft_trajectory_int_v'] = SIGNATURES['fthmc_ft_trajectory'] + [c_int, c_uint64]
+# per-chain beta and replica exchange: the device array beta_b where the scalar twins take `double beta`
+_i = SIGNATURES['fthmc_ft_trajectory_int_v'].index(c_double)
+SIGNATURES['fthmc_ft_trajectory_pb_v'] = SIGNATURES['fthmc_ft_trajectory_int_v'][:_i] + [_D] + SIGNATURES['fthmc_ft_trajectory_int_v'][_i + 1:]
+_i = SIGNATURES['fthmc_hmc_trajectory_int'].index(c_double)
+SIGNATURES['fthmc_hmc_trajectory_pb'] = SIGNATURES['fthmc_hmc_trajectory_int'][:_i] + [_D] + SIGNATURES['fthmc_hmc_trajectory_int'][_i + 1:]
+SIGNATURES['fthmc_replica_swap'] = [_D, c_int, c_int, c_int, _D, _D, _D, _D, _D, _D, _D, _P]
+SIGNATURES['fthmc_ladder_init'] = [ctypes.POINTER(c_double), c_int, c_int, _D, _D, _D, _D, _P]
 _RESTYPE = {'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None

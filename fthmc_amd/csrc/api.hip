@@ -287,13 +287,14 @@ int eval_action(const Ctx& C, const double* x, const WS& w, int nl, int B, int L
 
 // Plaquette-gradient field of sum_b S_eff (scaled): gp = scale*beta*sin P(F(x)) + sum_l gP_l,
 // with dL/dlogJ = glogj.  gw != null also accumulates weight gradients (training).
+// beta_b (optional): per-chain beta in place of beta_scaled (the per-chain-beta trajectories: fthmc_*_pb)
 int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, int act, double beta_scaled,
-             double glogj, double* gw, hipStream_t s, bool have_forward = false) {
+             double glogj, double* gw, hipStream_t s, bool have_forward = false, const double* beta_b = nullptr) {
     if (C.gen()) {                                // any other net shape (flow_generic.hip)
         if (nl > 0 && !have_forward) FT_TRY(sweep_forward(C, x, w, nl, B, L, act, nullptr, s, true));
         double* gcur = (nl & 1) ? w.gp2 : w.gp;
         double* galt = gcur == w.gp ? w.gp2 : w.gp;
-        FT_TRY(launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gcur, s));
+        FT_TRY(launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gcur, s, beta_b));
         for (int l = nl - 1; l >= 0; --l) {
             GenLayerArgs g = gen_args(C, w, l, B, L, act, true);
             g.up_gp = gcur; g.glogj_const = glogj; g.gp_out = galt;
@@ -313,7 +314,7 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
     // stash path: gather-form backward, gP ping-pongs between two fields and ends in w.gp
     double* gcur = (stash && (nl & 1)) ? w.gp2 : w.gp;
     double* galt = gcur == w.gp ? w.gp2 : w.gp;
-    FT_TRY(launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gcur, s));
+    FT_TRY(launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gcur, s, beta_b));
     // training on the tiled-exactly shapes: the layer's backward and its weight gradients in ONE kernel (flow_bwd_train.hip: the
     // pre-activation gradients never leave LDS), one partial per workgroup
     const bool fused = gw && train && fused_train_bwd(C.A, B, L);
@@ -368,12 +369,12 @@ int ft_leapfrog_ws(const Ctx& C, const double* x, const double* v, const WS& w, 
 // (w.xa and w.va are untouched by it).  nl = 0 is the plain Wilson MD (launch_wilson_gp + kick).  Result in w.xa / w.va; xreg as
 // in ft_leapfrog_ws -- it may be `xshift` itself: nothing reads the shifted field once the kick behind it has its gP.
 int ft_md_ws(const Ctx& C, const double* x, const double* v, const WS& w, int nl, int B, int L, int act, double beta,
-             const Sched& sc, hipStream_t s, double* xshift, double* xreg = nullptr) {
+             const Sched& sc, hipStream_t s, double* xshift, double* xreg = nullptr, const double* beta_b = nullptr) {
     FT_TRY(launch_axpy_copy(x, v, sc.b0, w.xa, w.va, w.n2, s));
     const double* xe = w.xa;                                               // where this stage's force is evaluated
     for (int it = 0; it < sc.n; ++it) {
         const SchedStage st = sc.stage(it);
-        FT_TRY(force_gp(C, xe, w, nl, B, L, act, beta, -1.0, nullptr, s));
+        FT_TRY(force_gp(C, xe, w, nl, B, L, act, beta, -1.0, nullptr, s, false, beta_b));
         if (st.kind == FT_STAGE_SHIFT) {
             FT_TRY(launch_shift_from_gp(w.gp, w.xa, xshift, B, L, st.a, s));
             xe = xshift;
@@ -393,12 +394,12 @@ inline int sched_of(int integrator, double dt, int nstep, Sched* sc) {
 
 // plain leapfrog; result pointers returned through xo/po (ping-pong inside the workspace)
 int leapfrog_ws(const double* x, const double* p, const WS& w, int B, int L, double beta, double dt,
-                int nstep, double** xo, double** po, hipStream_t s) {
+                int nstep, double** xo, double** po, hipStream_t s, const double* beta_b = nullptr) {
     const double* xi = x; const double* pi = p;
     double* xs[2] = {w.xa, w.xb}; double* ps[2] = {w.va, w.vb};
     int cur = 0;
     for (int k = 0; k < nstep; ++k) {
-        FT_TRY(launch_leap_step(xi, pi, xs[cur], ps[cur], B, L, beta, k == 0 ? 0.5 * dt : dt, dt, s));
+        FT_TRY(launch_leap_step(xi, pi, xs[cur], ps[cur], B, L, beta, k == 0 ? 0.5 * dt : dt, dt, s, beta_b));
         xi = xs[cur]; pi = ps[cur]; cur ^= 1;
     }
     // final half drift into the free x buffer
@@ -1101,6 +1102,114 @@ int fthmc_ft_trajectory_int_v(const double* x, const double* v, const double* u,
     if (Q && hipMemcpyAsync(Q, sel + 2 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return FTHMC_ERR_LAUNCH;
     return FTHMC_OK;
+}
+
+// ---------------------------------------------------------------- per-chain beta and replica exchange (no reference counterpart)
+// The beta-free triple (log det J, C = sum cos P, Q) of x into `trip` -- carried over (state_in) or evaluated -- and S_eff of it
+// at beta_b into `seff`: the general branch's eval_action + launch_lincomb with beta read per chain
+static int pb_eval(const Ctx& C, const double* x, const WS& W, int nl, int B, int L, int act, const double* beta_b,
+                   const double* state_in, double* trip, double* seff, hipStream_t s) {
+    if (state_in) {
+        if (hipMemcpyAsync(trip, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    } else {
+        if (nl > 0) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, trip, s));
+        else if (hipMemsetAsync(trip, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+        FT_TRY(launch_action_charge_pb(phys_field(x, W, nl), B, L, beta_b, nullptr, trip + 2 * B, nullptr, trip + B, s, W.act_part));
+    }
+    return launch_pb_from_state(trip, beta_b, B, L, nl > 0, seff, nullptr, s);
+}
+
+int fthmc_ft_trajectory_pb_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
+                             int B, int L, int act, const double* beta_b, double dt, int nstep, int mode, double* x_new,
+                             double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
+                             const double* state_in, double* state_out,
+                             void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version) {
+    FT_TRY(check_flow_call(x && v && u && x_new && beta_b && nstep >= 1, w, n_layers, B, L, act));
+    if (mode != FTHMC_MODE_MD) return FTHMC_ERR_UNSUPPORTED;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(arch);
+    FT_WS(n_layers, false);
+    double* K = W.scal + (size_t)SC_K * B;
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    // per-chain BETA-FREE triples (log det J, sum cos P, Q): of x (old), of the proposal (neu), of x_new (sel)
+    double* old = W.scal + (size_t)SC_OLD0 * B;
+    double* neu = W.scal + (size_t)SC_NEW0 * B;
+    double* sel = state_out ? state_out : W.scal + (size_t)SC_S * B;
+    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
+    if (C.small(L, n_layers)) {                                      // the whole trajectory in one launch
+        SmallArgs a = small_args(x, W, n_layers, B, act, 0.0, 3);
+        a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
+        a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
+        return launch_ft_small_pb(a, sc, beta_b, L, s);
+    }
+    if (C.A.is_default() && n_layers > 0) {                          // tuned kernels: fthmc_ft_trajectory_int_v's sequence
+        const int np = flow_fwd_geom(C.mfma).ntiles(L);
+        if (!state_in) FT_TRY(sweep_forward(C, x, W, n_layers, B, L, act, nullptr, s, false, false, true));
+        FT_TRY(launch_traj_energy(phys_field(x, W, n_layers), B, L, 0.0, W.lj_part, np, n_layers, state_in, v, old, h0, s, beta_b));
+        FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, 0.0, sc, s, W.xb, W.xb, beta_b));
+        FT_TRY(sweep_forward(C, W.xb, W, n_layers, B, L, act, nullptr, s, false, false, true));
+        FT_TRY(launch_traj_energy(phys_field(W.xb, W, n_layers), B, L, 0.0, W.lj_part, np, n_layers, nullptr, W.va, neu, h1, s, beta_b));
+    } else {                                                         // other net shapes, no layers
+        double* seff = W.scal + (size_t)SC_SEFF * B;
+        FT_TRY(pb_eval(C, x, W, n_layers, B, L, act, beta_b, state_in, old, seff, s));
+        FT_TRY(launch_kinetic(v, B, L, K, s));
+        FT_TRY(launch_lincomb(seff, 1.0, K, 0.5, 0.0, h0, B, s));
+        FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, 0.0, sc, s, W.xb, W.xb, beta_b));
+        FT_TRY(pb_eval(C, W.xb, W, n_layers, B, L, act, beta_b, nullptr, neu, seff, s));
+        FT_TRY(launch_kinetic(W.va, B, L, K, s));
+        FT_TRY(launch_lincomb(seff, 1.0, K, 0.5, 0.0, h1, B, s));
+    }
+    // the state of x_new is selected per chain, beta-free; Q is its third row, plaq follows from its second and beta_b
+    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s, nullptr, Q));
+    if (plaq) FT_TRY(launch_pb_from_state(sel, beta_b, B, L, n_layers > 0, nullptr, plaq, s));
+    return FTHMC_OK;
+}
+
+int fthmc_hmc_trajectory_pb(const double* x, const double* v, const double* u, int B, int L, const double* beta_b, double dt, int nstep,
+                            int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                            void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !v || !u || !x_new || !beta_b || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(nullptr);
+    // L <= 64 (x_new must not alias x): one persistent launch per trajectory, the schedule-driven kernel for every integrator
+    if (L <= 64 && C.mfma && x_new != x)
+        return launch_hmc_trajectory_sched(x, v, u, B, L, 0.0, sc, x_new, dH, acc, H0, H1, s, beta_b);
+    FT_WS(0, false);
+    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    FT_TRY(launch_action_charge_pb(x, B, L, beta_b, S, nullptr, nullptr, nullptr, s));
+    FT_TRY(launch_kinetic(v, B, L, K, s));
+    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h0, B, s));
+    double *xo = W.xb, *po = W.va;
+    if (integrator == FTHMC_INT_LEAPFROG) {                          // fthmc_hmc_trajectory's fused steps
+        FT_TRY(leapfrog_ws(x, v, W, B, L, 0.0, dt, nstep, &xo, &po, s, beta_b));
+        FT_TRY(launch_wrap(xo, xo, W.n2, 1, s));
+    } else {
+        FT_TRY(ft_md_ws(C, x, v, W, 0, B, L, 0, 0.0, sc, s, W.xb, W.xb, beta_b));
+    }
+    FT_TRY(launch_action_charge_pb(xo, B, L, beta_b, S, nullptr, nullptr, nullptr, s));
+    FT_TRY(launch_kinetic(po, B, L, K, s));
+    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h1, B, s));
+    return launch_metropolis(x, xo, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
+}
+
+int fthmc_replica_swap(const double* betas, int K, int M, int parity, const double* C, const double* u, double* beta_b, int32_t* rung,
+                       int32_t* chain_of, double* swap_acc, double* d, void* stream) {
+    if (K < 2 || M < 1 || (long long)K * M > FTHMC_MAX_B || (parity != 0 && parity != 1) || !betas || !C || !u || !beta_b || !rung ||
+        !chain_of)
+        return FTHMC_ERR_ARG;
+    return launch_replica_swap(betas, K, M, parity, C, u, beta_b, rung, chain_of, swap_acc, d, ft_stream(stream));
+}
+
+int fthmc_ladder_init(const double* betas_host, int K, int M, double* betas, double* beta_b, int32_t* rung, int32_t* chain_of,
+                      void* stream) {
+    if (K < 2 || M < 1 || (long long)K * M > FTHMC_MAX_B || !betas_host || !betas || !beta_b || !rung || !chain_of) return FTHMC_ERR_ARG;
+    for (int k = 0; k + 1 < K; ++k) if (!(betas_host[k] < betas_host[k + 1])) return FTHMC_ERR_ARG;      // strictly increasing (NaN refused)
+    return launch_ladder_init(betas_host, betas, K, M, beta_b, rung, chain_of, ft_stream(stream));
 }
 
 int fthmc_ft_trajectory(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,

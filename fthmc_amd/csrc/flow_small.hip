@@ -139,8 +139,13 @@ __device__ __forceinline__ ColdSched& cold_sched() {
     asm volatile("" : "+s"(p));
     return *p;
 }
-template <bool SCHED> struct SmallArgsOf { typedef SmallArgs type; };
-template <> struct SmallArgsOf<true> { typedef SmallArgsSched type; };
+// The per-chain-beta instance (k_ft_small<..., SCHED, PB>: replica exchange, fthmc_ft_trajectory_pb_v) takes the schedule-driven block
+// with the device array beta_b[B] behind it: beta is ONE load per workgroup at the chain's index, and state_in / state_out are the
+// beta-free triple (log det J, sum cos P, Q)
+struct SmallArgsPB : SmallArgsSched { const double* beta_b; };
+template <bool SCHED, bool PB = false> struct SmallArgsOf { typedef SmallArgs type; };
+template <> struct SmallArgsOf<true, false> { typedef SmallArgsSched type; };
+template <> struct SmallArgsOf<true, true> { typedef SmallArgsPB type; };
 
 // the stash values a backward pass multiplies by, loaded one pass ahead
 struct BwdPre { double tcv[4 * NMIX], fcs, fsn, d2v[4], d1v[4]; };
@@ -714,6 +719,24 @@ template <int L, bool TRAIN> struct Chain {
         }
         lds_barrier();
     }
+    // action_charge's sums themselves (the per-chain-beta instance keeps C = sum cos P: the beta-free state)
+    __device__ void action_sums(double& Cs, double& Q) {
+        constexpr int N = G::N;
+        const double* sX = sm + G::X;
+        double* red = sm + G::RED;
+        double c = 0.0, q = 0.0;
+        if (tid < N) {
+            const int i = fdiv<L>(tid), j = tid - i * L;
+            const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
+            const double a = sX[tid], bb = sX[N + tid], cc = sX[i * L + jp], d = sX[N + ip * L + j];
+            double sn_, cs_;
+            ft_sincos(a + d - cc - bb, &sn_, &cs_);
+            c = cs_;
+            q = ft_wrap(a - bb - cc + d);
+        }
+        Cs = ft_block_sum(c, red);
+        Q = ft_block_sum(q, red) / FT_TWO_PI;
+    }
     // force of site tid from sGP (adjoint of the plaquette stencil)
     __device__ __forceinline__ void site_force(double& f0, double& f1) const {
         const double* g = sm + G::GP;
@@ -744,8 +767,11 @@ enum { SM_ACTION = 0, SM_FORCE = 1, SM_LEAPFROG = 2, SM_TRAJ = 3, SM_TRAIN = 4 }
 // TRAJ: the launch is a whole trajectory (fthmc_ft_trajectory: the hot entry point of the small lattices): the other entry
 // points' branches leave that instance.  DBG: the stage stamps of tools/small_profile.py (A.dbg) exist in their own instance
 // of the generic kernel only: compiled out, config 2 runs 4 % faster (0.497 -> 0.477 ms per trajectory).
-template <int L, bool TRAIN, bool TRAJ, bool DBG, bool SCHED>
-__global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArgsOf<SCHED>::type Aarg) {
+//   PB:          the SCHED instance with beta = beta_b[b] (one load per workgroup) and the beta-free state: thread 0 keeps
+//                (log det J, sum cos P) of x and of the proposal in the first four doubles of the profiling slots (DBG is off)
+template <int L, bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false>
+__global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArgsOf<SCHED, PB>::type Aarg) {
+    static_assert(!PB || (SCHED && !DBG && !TRAIN), "the per-chain-beta instance is a schedule-driven trajectory");
     using G = GS<L>;
     constexpr int N = G::N;
     __shared__ __attribute__((aligned(16))) double sm[G::SIZE];
@@ -755,7 +781,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
     const int tid = C.tid;
     double* red = sm + G::RED;
     const int mode = TRAIN ? (int)SM_TRAIN : (TRAJ ? (int)SM_TRAJ : Aarg.mode), nl = hot.nl;
-    const double beta = Aarg.beta, dt = Aarg.dt;
+    double beta_ = Aarg.beta;
+    if constexpr (PB) beta_ = Aarg.beta_b[b];
+    const double beta = beta_, dt = Aarg.dt;
     const bool have_state = Aarg.state_in != nullptr;
     {
         const double* xb = cold().x + (size_t)b * 2 * N;
@@ -775,6 +803,15 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
     if (moves && tid < N) { const double* vb = cold().v + (size_t)b * 2 * N; v0 = vb[tid]; v1 = vb[N + tid]; }
     double* stt = sm + G::STT;                                             // thread 0's scalars live in LDS, not in registers of every lane
     if (mode == SM_TRAJ) {
+        if constexpr (PB) {
+            if (have_state && tid == 0) {                                  // (log det J, C, Q) -> the kernel's triple, by the EVAL sweep's expressions
+                const double* si = cold().state_in;
+                const double ld = si[b], c = si[hot.B + b];
+                const double S = (-beta) * c;
+                stt[0] = S - ld; stt[1] = (-S) / (beta * (double)N); stt[2] = si[2 * hot.B + b];
+                sm[G::PROF] = ld; sm[G::PROF + 1] = c;
+            }
+        } else
         if (have_state && tid == 0) { const double* si = cold().state_in; stt[0] = si[b]; stt[1] = si[hot.B + b]; stt[2] = si[2 * hot.B + b]; }
         const double k0 = ft_block_sum(v0 * v0 + v1 * v1, red);
         if (tid == 0) stt[6] = k0;
@@ -852,6 +889,16 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
                 }
             }
             C.stamp(18);
+        } else if constexpr (PB) {
+            double Cs, Q;
+            C.action_sums(Cs, Q);
+            if (tid == 0) {
+                const double S = (-beta) * Cs;
+                double* st = stt + (it < 0 ? 0 : 3);
+                st[0] = S - ld; st[1] = (-S) / (beta * (double)N); st[2] = Q; stt[7] = ld;
+                double* keep = sm + G::PROF + (it < 0 ? 0 : 2);
+                keep[0] = ld; keep[1] = Cs;
+            }
         } else {
             double S, Q;
             C.action_charge(beta, S, Q);
@@ -894,6 +941,10 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
         if (A.H0) A.H0[b] = h0;
         if (A.H1) A.H1[b] = h1;
         const double* sel = stt + (ok ? 3 : 0);
+        if constexpr (PB) {
+            const double* keep = sm + G::PROF + (ok ? 2 : 0);
+            if (A.state_out) { A.state_out[b] = keep[0]; A.state_out[A.B + b] = keep[1]; A.state_out[2 * A.B + b] = sel[2]; }
+        } else
         if (A.state_out) { A.state_out[b] = sel[0]; A.state_out[A.B + b] = sel[1]; A.state_out[2 * A.B + b] = sel[2]; }
         if (A.plaq) A.plaq[b] = sel[1];
         if (A.Q) A.Q[b] = sel[2];
@@ -933,6 +984,24 @@ int launch_ft_small_sched(const SmallArgs& a0, const Sched& sched, int L, hipStr
         case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, false, true>), grid, block, 0, s, a); break;
         case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, false, true>), grid, block, 0, s, a); break;
         case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, false, true>), grid, block, 0, s, a); break;
+        default: return FTHMC_ERR_UNSUPPORTED;
+    }
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
+
+// a trajectory of a schedule with per-chain beta (a0.beta is not read; state_in / state_out: the beta-free triple)
+int launch_ft_small_pb(const SmallArgs& a0, const Sched& sched, const double* beta_b, int L, hipStream_t s) {
+    const dim3 grid(a0.B), block(NT);
+    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
+    if (a0.mode != SM_TRAJ || a0.dbg || !beta_b || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
+    SmallArgsPB a;
+    static_cast<SmallArgs&>(a) = a0;
+    a.sched = sched;
+    a.beta_b = beta_b;
+    switch (L) {
+        case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, false, true, true>), grid, block, 0, s, a); break;
+        case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, false, true, true>), grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, false, true, true>), grid, block, 0, s, a); break;
         default: return FTHMC_ERR_UNSUPPORTED;
     }
     FT_LAUNCH_CHECK(); return FTHMC_OK;

@@ -26,9 +26,11 @@ int launch_stats_accumulate(const double* acc, const double* plaq, const double*
                             double* vec, hipStream_t s);
 int launch_wilson_force(const double* x, int B, int L, double beta, double* F, hipStream_t s);
 void set_leap_rows(int v);      // 1 (default): row-strip leapfrog kernel when L % 64 == 0; 0: 16 x 16 tiles always
+// beta_b (optional, here and below): per-chain beta, a device array [B] read in place of `beta` (the per-chain-beta entry points,
+// fthmc_*_pb); null: the instances and argument lists every other caller has always run
 int launch_leap_step(const double* x, const double* p, double* xo, double* po, int B, int L,
-                     double beta, double a, double dt, hipStream_t s);
-int launch_wilson_gp(const double* x, int B, int L, double beta, double* gp, hipStream_t s);
+                     double beta, double a, double dt, hipStream_t s, const double* beta_b = nullptr);
+int launch_wilson_gp(const double* x, int B, int L, double beta, double* gp, hipStream_t s, const double* beta_b = nullptr);
 // whole plain-HMC trajectory in one launch (L <= 64: links in LDS, momenta in registers)
 int launch_hmc_trajectory_fused(const double* x, const double* v, const double* u, int B, int L, double beta,
                                 double dt, int nstep, double* x_new, double* dH, double* acc, double* H0,
@@ -39,11 +41,23 @@ int launch_kick_from_gp(const double* gp, double* v, double* xq, double* Fout, i
 int launch_shift_from_gp(const double* gp, const double* x, double* xs, int B, int L, double c, hipStream_t s);
 // plain HMC of a schedule in one launch (L <= 64): launch_hmc_trajectory_fused's twin
 int launch_hmc_trajectory_sched(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sched,
-                                double* x_new, double* dH, double* acc, double* H0, double* H1, hipStream_t s);
+                                double* x_new, double* dH, double* acc, double* H0, double* H1, hipStream_t s,
+                                const double* beta_b = nullptr);
 // the scalars of one end of a flowed trajectory in one launch: (S_eff, plaq, Q) of the flowed field (or carried over: state_in)
 // and H = S_eff + sum v^2 / 2
 int launch_traj_energy(const double* xphys, int B, int L, double beta, const double* lj_part, int np, int nsets,
-                       const double* state_in, const double* v, double* trip, double* H, hipStream_t s);
+                       const double* state_in, const double* v, double* trip, double* H, hipStream_t s,
+                       const double* beta_b = nullptr);   // beta_b: trip and state_in are the BETA-FREE triple (log det J, sum cos P, Q)
+// per-chain beta (replica exchange): S_W / Q / plaq as launch_action_charge with beta_b[b], and Csum = sum cos P
+int launch_action_charge_pb(const double* x, int B, int L, const double* beta_b, double* S, double* Q, double* plaq, double* Csum,
+                            hipStream_t s, double* wave_part = nullptr);
+// S_eff (has_ld: minus row 0) and plaq from the beta-free state st[3][B] = (log det J, sum cos P, Q) and beta_b
+int launch_pb_from_state(const double* st, const double* beta_b, int B, int L, int has_ld, double* seff, double* plaq, hipStream_t s);
+// one replica-exchange round of parity 0 / 1 over M ladders of K chains (wilson.hip k_replica_swap); every ladder in order
+int launch_replica_swap(const double* betas, int K, int M, int parity, const double* C, const double* u, double* beta_b, int* rung,
+                        int* chain_of, double* swap_acc, double* d, hipStream_t s);
+// betas_host (host, K doubles) is read DURING the call: it travels to `betas` by value, in kernel arguments
+int launch_ladder_init(const double* betas_host, double* betas, int K, int M, double* beta_b, int* rung, int* chain_of, hipStream_t s);
 int launch_axpy_copy(const double* x, const double* p, double a, double* xo, double* po, size_t n, hipStream_t s);
 int launch_plane_from(const double* g, int B, int L, int mu, double sign, double* out, hipStream_t s);   // out[b][mu][:] = sign * g[b][:]
 int launch_metropolis(const double* x_old, const double* x_prop, const double* u, const double* H0,
@@ -340,6 +354,8 @@ struct SmallArgs {
 bool ft_small_shape(int L, int n_layers);       // the fused path is built for this lattice size (default net shape, MFMA kernels)
 int launch_ft_small(const SmallArgs& a, int L, hipStream_t s);
 int launch_ft_small_sched(const SmallArgs& a, const Sched& sched, int L, hipStream_t s);   // mode 2 / 3 of a schedule (integrator.h)
+// mode 3 of a schedule with per-chain beta beta_b[B] (replica exchange); state_in / state_out: (log det J, sum cos P, Q)
+int launch_ft_small_pb(const SmallArgs& a, const Sched& sched, const double* beta_b, int L, hipStream_t s);
 void set_small_path(int v);
 int get_small_path();
 // 0: VALU kernels everywhere; 1 (default): MFMA kernels for forward and backward-wrt-x

@@ -33,3 +33,14 @@ san_integrator:
 	mkdir -p $(dir $(SANWALK))
 	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	  -I. ../../tests/hip/integrator_walk.cpp -o $(SANWALK)
+
+# The replica-exchange entry points (fthmc_ft_trajectory_pb_v, fthmc_hmc_trajectory_pb, fthmc_replica_swap, fthmc_ladder_init):
+# tests/hip/tempering_walk.cpp as a stand-alone program against the host-side sanitizer build of the library (built first when it
+# is missing or older than a source), the sanitizer runtimes linked in (nothing to preload), run by tests/test_tempering.py
+SANTEMP ?= $(SANDIR)/tempering_walk
+$(SANOUT): $(SRCS) common.h kernels.h integrator.h ../../include/fthmc_hip.h san.mk
+	@$(MAKE) --no-print-directory -f san.mk san_build
+san_tempering: $(SANOUT)
+	mkdir -p $(dir $(SANTEMP))
+	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
+	  ../../tests/hip/tempering_walk.cpp -o $(SANTEMP) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))

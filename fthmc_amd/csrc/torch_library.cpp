@@ -263,6 +263,67 @@ std::tuple<Tensor, Tensor, Tensor> train_force_grad(const Tensor& x_, const Tens
     return {F, fsq, gw};
 }
 
+// ---------------------------------------------------------------- per-chain beta and replica exchange
+Tensor i32(const Tensor& t, int64_t n, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, ": tensor lives on ", t.device(), "; fthmc_hip runs on the MI355X only (no CPU fallback)");
+    TORCH_CHECK(t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() == n, name, ": expected a contiguous int32 tensor of ", n, " entries");
+    return t;
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ft_trajectory_pb(const Tensor& x_, const Tensor& v_, const Tensor& u_, const Tensor& w_all,
+                                                                            int64_t n_layers, const Tensor& beta_b_, double dt, int64_t nstep,
+                                                                            int64_t integrator, int64_t act, const c10::optional<Tensor>& state_in_,
+                                                                            int64_t n_mix, IntList hidden, int64_t kernel_size) {
+    FT_DEVICE_GUARD(x_);
+    Tensor x = field(x_, "x"), v = field(v_, "v");
+    Arch A(n_mix, hidden, kernel_size);
+    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
+    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
+    Tensor u = perchain(u_, B, "u"), beta_b = perchain(beta_b_, B, "beta_b");
+    TORCH_CHECK(v.sizes() == x.sizes(), "v: shaped like x expected");
+    Tensor state_in;
+    if (state_in_.has_value()) {
+        state_in = dev64(*state_in_, "state_in");
+        TORCH_CHECK(state_in.numel() == 3 * (int64_t)B, "state_in: expected [3, ", B, "]");
+    }
+    auto o = x.options();
+    Tensor xn = at::empty_like(x), dH = at::empty({B}, o), acc = at::empty({B}, o), plaq = at::empty({B}, o), Q = at::empty({B}, o),
+           state = at::empty({3, B}, o);
+    Workspace ws(x, A.ptr(), B, L, nl);
+    ok(fthmc_ft_trajectory_pb_v(cp(x), cp(v), cp(u), cp(w), A.ptr(), nl, B, L, (int)act, cp(beta_b), dt, (int)nstep, FTHMC_MODE_MD, mp(xn), mp(dH),
+                                mp(acc), nullptr, nullptr, mp(plaq), mp(Q), state_in.defined() ? cp(state_in) : nullptr, mp(state), ws.ptr(),
+                                ws.bytes, cur_stream(x), (int)integrator, 0), "fthmc_ft_trajectory_pb_v");
+    return {xn, dH, acc, plaq, Q, state};
+}
+std::tuple<Tensor, Tensor, Tensor> hmc_trajectory_pb(const Tensor& x_, const Tensor& v_, const Tensor& u_, const Tensor& beta_b_, double dt,
+                                                     int64_t nstep, int64_t integrator) {
+    FT_DEVICE_GUARD(x_);
+    Tensor x = field(x_, "x"), v = field(v_, "v");
+    const int B = (int)x.size(0), L = (int)x.size(2);
+    Tensor u = perchain(u_, B, "u"), beta_b = perchain(beta_b_, B, "beta_b");
+    TORCH_CHECK(v.sizes() == x.sizes(), "v: shaped like x expected");
+    Tensor xn = at::empty_like(x), dH = at::empty({B}, x.options()), acc = at::empty({B}, x.options());
+    Workspace ws(x, nullptr, B, L, 0);
+    ok(fthmc_hmc_trajectory_pb(cp(x), cp(v), cp(u), B, L, cp(beta_b), dt, (int)nstep, (int)integrator, mp(xn), mp(dH), mp(acc), nullptr, nullptr,
+                               ws.ptr(), ws.bytes, cur_stream(x)), "fthmc_hmc_trajectory_pb");
+    return {xn, dH, acc};
+}
+// beta_b, rung and chain_of are updated in place (the schema says so)
+std::tuple<Tensor, Tensor> replica_swap(const Tensor& betas_, const Tensor& C_, const Tensor& u_, Tensor& beta_b, Tensor& rung, Tensor& chain_of,
+                                        int64_t parity) {
+    FT_DEVICE_GUARD(beta_b);
+    Tensor betas = dev64(betas_, "betas").reshape({-1});
+    const int64_t K = betas.numel(), B = beta_b.numel();
+    TORCH_CHECK(beta_b.is_cuda() && beta_b.scalar_type() == at::kDouble && beta_b.is_contiguous(), "beta_b: expected a contiguous float64 device tensor");
+    TORCH_CHECK(K >= 2 && B > 0 && B % K == 0, "replica_swap: ", B, " chains do not form whole ladders of ", K, " rungs");
+    const int64_t M = B / K;
+    Tensor C = perchain(C_, B, "C"), u = perchain(u_, M * (K - 1), "u");
+    i32(rung, B, "rung"); i32(chain_of, B, "chain_of");
+    Tensor acc = at::empty({M, K - 1}, beta_b.options()), d = at::empty({M, K - 1}, beta_b.options());
+    ok(fthmc_replica_swap(cp(betas), (int)K, (int)M, (int)parity, cp(C), cp(u), mp(beta_b), rung.mutable_data_ptr<int32_t>(),
+                          chain_of.mutable_data_ptr<int32_t>(), mp(acc), mp(d), cur_stream(beta_b)), "fthmc_replica_swap");
+    return {acc, d};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(fthmc_hip, m) {
@@ -280,6 +341,9 @@ TORCH_LIBRARY(fthmc_hip, m) {
     m.def("ft_action_vjp(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor gS, Tensor? glogdet=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
     m.def("ft_force_vjp(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor g, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
     m.def("train_force_grad(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor)");
+    m.def("ft_trajectory_pb(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, Tensor beta_b, float dt, int nstep, int integrator, int act, Tensor? state_in=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+    m.def("hmc_trajectory_pb(Tensor x, Tensor v, Tensor u, Tensor beta_b, float dt, int nstep, int integrator=0) -> (Tensor, Tensor, Tensor)");
+    m.def("replica_swap(Tensor betas, Tensor C, Tensor u, Tensor(a!) beta_b, Tensor(b!) rung, Tensor(c!) chain_of, int parity) -> (Tensor, Tensor)");
 }
 
 // "CUDA" is the dispatch key of HIP devices in PyTorch-ROCm
@@ -298,4 +362,7 @@ TORCH_LIBRARY_IMPL(fthmc_hip, CUDA, m) {
     m.impl("ft_action_vjp", &ft_action_vjp);
     m.impl("ft_force_vjp", &ft_force_vjp);
     m.impl("train_force_grad", &train_force_grad);
+    m.impl("ft_trajectory_pb", &ft_trajectory_pb);
+    m.impl("hmc_trajectory_pb", &hmc_trajectory_pb);
+    m.impl("replica_swap", &replica_swap);
 }

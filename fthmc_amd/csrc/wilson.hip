@@ -8,6 +8,15 @@
 namespace {
 
 constexpr int TS = 16;          // stencil tile (TS x TS sites, 256 threads)
+constexpr int FT_LADDER_CHUNK = 64;
+
+// beta of a launch: ONE double for every chain (the instances every scalar entry point runs: their argument lists and code are
+// what they were), or -- PB, the per-chain-beta entry points (replica exchange: fthmc_*_pb) -- a device array beta_b[B] read once
+// per workgroup at the chain's index
+template <bool PB> struct BetaArg { typedef double type; };
+template <> struct BetaArg<true> { typedef const double* type; };
+__device__ __forceinline__ double beta_at(double beta, int) { return beta; }
+__device__ __forceinline__ double beta_at(const double* beta_b, int b) { return beta_b[b]; }
 
 // ---------------------------------------------------------------- elementwise
 __global__ void k_wrap(const double* __restrict__ x, double* __restrict__ o, size_t n, int reg) {
@@ -120,15 +129,26 @@ __global__ void k_kinetic(const double* __restrict__ v, int n, double* __restric
 //   trip = (S_eff = S_W - log det J, plaq, Q)   -- or copied from state_in when the caller carries it over
 //   H = S_eff + K / 2,  K = sum v^2                                           (k_kinetic's order)
 // Launched with the block size k_action_charge / k_kinetic use for this L, so every sum is bit-identical to theirs.
-__global__ void k_traj_energy(const double* __restrict__ xphys, int L, double beta, const double* __restrict__ lj_part, int np,
+// PB: beta = beta_b[b], and the triple is BETA-FREE: trip = state = (log det J, C = sum cos P, Q).  S_W = (-beta) C, S_eff and plaq are
+// formed from it by the expressions below whether C was just summed or carried over, so a chained call is bit-equal to a
+// stateless one at any beta and a replica exchange (k_replica_swap) never touches the state.
+template <bool PB>
+__global__ void k_traj_energy(const double* __restrict__ xphys, int L, typename BetaArg<PB>::type beta_, const double* __restrict__ lj_part, int np,
                               int nsets, const double* __restrict__ state_in, const double* __restrict__ v,
                               double* __restrict__ trip, double* __restrict__ H, int B) {
     __shared__ double red[16];
     __shared__ double sld;
     const int b = blockIdx.x;
+    const double beta = beta_at(beta_, b);
     double seff, pq, qq;
-    if (state_in) { seff = state_in[b]; pq = state_in[B + b]; qq = state_in[2 * B + b]; }
-    else {
+    if (!PB && state_in) { seff = state_in[b]; pq = state_in[B + b]; qq = state_in[2 * B + b]; }
+    else if (PB && state_in) {
+        const double ld = state_in[b], c = state_in[B + b];
+        const double s = (-beta) * c;
+        seff = 1.0 * s + (nsets > 0 ? -1.0 * ld : 0.0) + 0.0;
+        pq = c; qq = state_in[2 * B + b];
+        if (threadIdx.x == 0) sld = ld;
+    } else {
         if (threadIdx.x < FT_WAVE) {
             double tot = 0.0;
             for (int q = 0; q < nsets; ++q) {
@@ -145,7 +165,7 @@ __global__ void k_traj_energy(const double* __restrict__ xphys, int L, double be
         q = ft_block_sum(q, red);
         const double s = (-beta) * c;
         seff = 1.0 * s + (nsets > 0 ? -1.0 * sld : 0.0) + 0.0;           // k_lincomb(S, 1, logdet, -1, 0)
-        pq = (-s) / (beta * (double)(L * L));
+        pq = PB ? c : (-s) / (beta * (double)(L * L));
         qq = q / FT_TWO_PI;
     }
     const int n = 2 * L * L;
@@ -154,7 +174,7 @@ __global__ void k_traj_energy(const double* __restrict__ xphys, int L, double be
     for (int s = threadIdx.x; s < n; s += blockDim.x) a += vb[s] * vb[s];
     a = ft_block_sum(a, red);
     if (threadIdx.x == 0) {
-        trip[b] = seff; trip[B + b] = pq; trip[2 * B + b] = qq;
+        trip[b] = PB ? (nsets > 0 ? sld : 0.0) : seff; trip[B + b] = pq; trip[2 * B + b] = qq;
         H[b] = 1.0 * seff + 0.5 * a + 0.0;                                // k_lincomb(S_eff, 1, K, 0.5, 0)
     }
 }
@@ -182,12 +202,12 @@ __global__ void k_axpy_copy(const double* __restrict__ x, const double* __restri
 // MODE 0: F = dS/dx of x.
 // MODE 1: fused leapfrog step  x' = x + a p ; p' = p - dt F(x')  (ping-pong buffers)
 // MODE 2: gP = beta sin P (plaquette-gradient field that seeds the flow backward sweep)
-template <int MODE>
+template <int MODE, bool PB = false>
 __global__ __launch_bounds__(256) void k_force(const double* __restrict__ x,
                                                const double* __restrict__ p,
                                                double* __restrict__ o0,   // F | x' | gP
                                                double* __restrict__ o1,   // - | p' | -
-                                               int L, double beta, double a, double dt) {
+                                               int L, typename BetaArg<PB>::type beta_, double a, double dt) {
     // Links are staged through LDS once (x0 on a (TS+1) x (TS+2) window, x1 on (TS+2) x (TS+1), MODE 1:
     // already drifted, x + a p, with p of the window kept for the kick), beta sin P is evaluated once per
     // plaquette of the (TS+1) x (TS+1) window (one extra row above / column to the left), the force of a site
@@ -195,6 +215,7 @@ __global__ __launch_bounds__(256) void k_force(const double* __restrict__ x,
     constexpr int W0C = TS + 2, W1C = TS + 1, NW0 = (TS + 1) * W0C, NW1 = (TS + 2) * W1C, WP = TS + 1;
     __shared__ double sx0[NW0], sx1[NW1], sq0[MODE == 1 ? NW0 : 1], sq1[MODE == 1 ? NW1 : 1], sp[WP * WP];
     const int b = blockIdx.z;
+    const double beta = beta_at(beta_, b);
     const int i0 = blockIdx.y * TS, j0 = blockIdx.x * TS;
     const int n = L * L;
     const double* x0 = x + (size_t)b * 2 * n;
@@ -257,15 +278,16 @@ __global__ __launch_bounds__(256) void k_force(const double* __restrict__ x,
 // never stored; the own momenta stay in registers), beta sin P is evaluated once per plaquette of the (TR + 1) x 65
 // window, the force of a site is two differences of it.  HBM-bound: 64 B per site and launch algorithmically; the halo
 // rows (2.5 of TR + ... per plane pair) are re-reads that the neighbouring workgroup's own loads leave in L2.
-template <int TR>
+template <int TR, bool PB = false>
 __global__ __launch_bounds__(TR * 32) void k_leap_rows(const double* __restrict__ x, const double* __restrict__ p,
                                                        double* __restrict__ xo, double* __restrict__ po,
-                                                       int L, double beta, double a, double dt) {
+                                                       int L, typename BetaArg<PB>::type beta_, double a, double dt) {
     constexpr int TC = 64, WC = TC + 2, NTH = TR * 32;
     typedef double double2_t __attribute__((ext_vector_type(2)));
     // window row r <-> lattice row i0 - 1 + r, window column c <-> lattice column j0 - 1 + c
     __shared__ __attribute__((aligned(16))) double sx0[(TR + 1) * WC], sx1[(TR + 2) * WC], ss[(TR + 1) * WC];
     const int b = blockIdx.z, i0 = blockIdx.y * TR, j0 = blockIdx.x * TC;
+    const double beta = beta_at(beta_, b);
     const int n = L * L, t = threadIdx.x;
     const double* x0 = x + (size_t)b * 2 * n;
     const double* p0 = p + (size_t)b * 2 * n;
@@ -362,10 +384,12 @@ __global__ void k_kick_from_gp(const double* __restrict__ gp, double* __restrict
 // Same arithmetic per site as k_force<2> / k_kick_from_gp: results are bit-identical.
 //
 // gP = beta sin P(x): the seed of the flow's backward sweep (qed_helpers.py:226-242: d S_W / d P)
-template <int TR>
-__global__ __launch_bounds__(TR * 32) void k_gp_rows(const double* __restrict__ x, double* __restrict__ gp, int L, double beta) {
+template <int TR, bool PB = false>
+__global__ __launch_bounds__(TR * 32) void k_gp_rows(const double* __restrict__ x, double* __restrict__ gp, int L,
+                                                     typename BetaArg<PB>::type beta_) {
     typedef double double2_t __attribute__((ext_vector_type(2)));
     const int b = blockIdx.z, i = blockIdx.y * TR + (threadIdx.x >> 5), q = threadIdx.x & 31, j = blockIdx.x * 64 + 2 * q;
+    const double beta = beta_at(beta_, b);
     const int n = L * L;
     const double* x0 = x + (size_t)b * 2 * n;
     const double* x1 = x0 + n;
@@ -673,8 +697,9 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory(const double* __restri
 //   beta sin P of the links in LDS;  KICK(a, b): v -= a F, x += b v  |  SHIFT(c): the thread keeps its own links in registers and
 //   puts x - c F in their place for the NEXT stage's beta sin P, whose kick first puts the kept links back: sx itself is as if
 //   never touched (restored bit for bit, not recomputed)
+template <bool PB>
 __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __restrict__ x, const double* __restrict__ v,
-                                                                const double* __restrict__ u, int L, double beta, fthmc::Sched sched,
+                                                                const double* __restrict__ u, int L, typename BetaArg<PB>::type beta_, fthmc::Sched sched,
                                                                 double* __restrict__ x_new, double* __restrict__ dH,
                                                                 double* __restrict__ acc, double* __restrict__ H0o,
                                                                 double* __restrict__ H1o) {
@@ -682,6 +707,7 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __
     __shared__ double sp[TJ_MAXL * TJ_MAXL];            // beta sin P
     __shared__ double red[16];
     const int b = blockIdx.x, tid = threadIdx.x, n = L * L;
+    const double beta = beta_at(beta_, b);
     const double* xb = x + (size_t)b * 2 * n;
     const double* vb = v + (size_t)b * 2 * n;
     double v0[TJ_NSITE], v1[TJ_NSITE], k0[TJ_NSITE], k1[TJ_NSITE];
@@ -767,6 +793,102 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __
         }
 }
 
+// ---------------------------------------------------------------- per-chain beta: energies from the beta-free state, replica exchange
+// k_action_charge / k_action_charge_fin with beta = beta_b[b]: the same sums by the same threads in the same order; also hands
+// out C = sum cos P itself (the beta-free row of the carried state)
+__global__ void k_action_charge_pb(const double* __restrict__ x, int L, const double* __restrict__ beta_b,
+                                   double* __restrict__ S, double* __restrict__ Q, double* __restrict__ plaq, double* __restrict__ Csum) {
+    __shared__ double red[16];
+    const int b = blockIdx.x;
+    double c, q;
+    chain_action_charge<0>(x + (size_t)b * 2 * L * L, L, c, q);
+    c = ft_block_sum(c, red);
+    q = ft_block_sum(q, red);
+    if (threadIdx.x == 0) {
+        const double beta = beta_b[b];
+        const double s = (-beta) * c;
+        if (S) S[b] = s;
+        if (Q) Q[b] = q / FT_TWO_PI;
+        if (plaq) plaq[b] = (-s) / (beta * (double)(L * L));
+        if (Csum) Csum[b] = c;
+    }
+}
+__global__ void k_action_charge_fin_pb(const double* __restrict__ part, int nw, int B, int L, const double* __restrict__ beta_b,
+                                       double* __restrict__ S, double* __restrict__ Q, double* __restrict__ plaq, double* __restrict__ Csum) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double c = 0.0, q = 0.0;
+    for (int w = 0; w < nw; ++w) { c += part[((size_t)b * nw + w) * 2]; q += part[((size_t)b * nw + w) * 2 + 1]; }
+    const double beta = beta_b[b];
+    const double s = (-beta) * c;
+    if (S) S[b] = s;
+    if (Q) Q[b] = q / FT_TWO_PI;
+    if (plaq) plaq[b] = (-s) / (beta * (double)(L * L));
+    if (Csum) Csum[b] = c;
+}
+
+// S_eff and plaq of a chain from its beta-free state st[3][B] = (log det J, C, Q) and beta_b[b], by k_traj_energy's expressions:
+//   S_W = (-beta) C;  S_eff = S_W - log det J (has_ld: the call has layers), each rounded;  plaq = (-S_W) / (beta L^2)
+__global__ void k_pb_from_state(const double* __restrict__ st, const double* __restrict__ beta_b, int B, int L, int has_ld,
+                                double* __restrict__ seff, double* __restrict__ plaq) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double beta = beta_b[b];
+    // the scalar calls of this branch round S_W on its way through memory (k_action_charge -> k_lincomb): no contraction here either
+    const double s = __dmul_rn(-beta, st[B + b]);
+    if (seff) seff[b] = has_ld ? __dsub_rn(s, st[b]) : s;
+    if (plaq) plaq[b] = (-s) / (beta * (double)(L * L));
+}
+
+// One round of replica exchange (parallel tempering) over M ladders of K consecutive chains each.  rung[b]: the rung chain b sits
+// on; chain_of[m K + k]: the chain (index inside ladder m) that sits on rung k -- the inverse of rung within the ladder.  One
+// thread per (ladder m, pair k): pairs k = parity (mod 2) are attempted,
+//   a = chain on rung k, c = chain on rung k + 1;  d = (beta_k - beta_{k+1}) (C_c - C_a);  accept iff u[m][k] < exp(d)
+// (with ONE flow for every rung the log det J terms of the four S_eff cancel: DESIGN 4.11), and an accepted pair exchanges its
+// rung, beta_b and chain_of entries: the fields never move and the beta-free state stays valid.  The pairs of a round are
+// disjoint: no thread reads what another writes, no atomics, two calls give the same bits.
+__global__ void k_replica_swap(const double* __restrict__ betas, int K, int M, int parity, const double* __restrict__ C,
+                               const double* __restrict__ u, double* __restrict__ beta_b, int* __restrict__ rung,
+                               int* __restrict__ chain_of, double* __restrict__ swap_acc, double* __restrict__ dout) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)M * (K - 1)) return;
+    const int m = (int)(t / (K - 1)), k = (int)(t - (long long)m * (K - 1));
+    const size_t base = (size_t)m * K;
+    int al = -1, cl = -1;
+    if ((k & 1) == parity) { al = chain_of[base + k]; cl = chain_of[base + k + 1]; }   // only an attempted pair reads its two entries
+    if ((unsigned)al >= (unsigned)K || (unsigned)cl >= (unsigned)K) {                   // not attempted in this round
+        if (swap_acc) swap_acc[t] = -1.0;
+        if (dout) dout[t] = 0.0;
+        return;
+    }
+    const size_t a = base + al, c = base + cl;
+    const double bk = betas[k], bk1 = betas[k + 1];
+    const double d = (bk - bk1) * (C[c] - C[a]);
+    const bool ok = u[t] < exp(d);
+    if (swap_acc) swap_acc[t] = ok ? 1.0 : 0.0;
+    if (dout) dout[t] = d;
+    if (ok) {
+        rung[a] = k + 1; rung[c] = k;
+        beta_b[a] = bk1; beta_b[c] = bk;
+        chain_of[base + k] = cl; chain_of[base + k + 1] = al;
+    }
+}
+
+// the ladder itself travels BY VALUE, FT_LADDER_CHUNK doubles per launch: nothing of the host array is read behind the call
+struct LadderChunk { double v[FT_LADDER_CHUNK]; };
+__global__ void k_ladder_set(LadderChunk c, int n, double* __restrict__ betas) {
+    const int k = threadIdx.x;
+    if (k < n) betas[k] = c.v[k];
+}
+// every ladder in order: chain m K + k on rung k at betas[k]
+__global__ void k_ladder_init(const double* __restrict__ betas, int K, long long B, double* __restrict__ beta_b, int* __restrict__ rung,
+                              int* __restrict__ chain_of) {
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int k = (int)(b % K);
+    beta_b[b] = betas[k]; rung[b] = k; chain_of[b] = k;
+}
+
 int g_leap_rows = 1;     // FTHMC_LEAP_ROWS=0 in the environment: the 16 x 16-tile kernel for every L (A/B runs)
 
 inline int ew_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 2048 ? 2048 : (g ? g : 1)); }
@@ -806,6 +928,43 @@ int launch_action_charge(const double* x, int B, int L, double beta, double* S, 
     hipLaunchKernelGGL(k_action_charge, dim3(B), dim3(nt), 0, s, x, L, beta, S, Q, plaq);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
+// launch_action_charge's two forms (the same choice between them) with beta = beta_b[b]; Csum: sum cos P per chain
+int launch_action_charge_pb(const double* x, int B, int L, const double* beta_b, double* S, double* Q, double* plaq, double* Csum,
+                            hipStream_t s, double* wave_part) {
+    const int nt = L * L >= 4096 ? 1024 : (L * L >= 1024 ? 512 : 256);
+    if (wave_part && B < 128 && L >= 128) {
+        const int nw = nt / FT_WAVE;
+        hipLaunchKernelGGL(k_action_charge_waves, dim3(nw, B), dim3(FT_WAVE), 0, s, x, L, wave_part);
+        FT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_action_charge_fin_pb, dim3((B + 63) / 64), dim3(64), 0, s, wave_part, nw, B, L, beta_b, S, Q, plaq, Csum);
+        FT_LAUNCH_CHECK(); return FTHMC_OK;
+    }
+    hipLaunchKernelGGL(k_action_charge_pb, dim3(B), dim3(nt), 0, s, x, L, beta_b, S, Q, plaq, Csum);
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
+int launch_pb_from_state(const double* st, const double* beta_b, int B, int L, int has_ld, double* seff, double* plaq, hipStream_t s) {
+    hipLaunchKernelGGL(k_pb_from_state, dim3((B + 255) / 256), dim3(256), 0, s, st, beta_b, B, L, has_ld, seff, plaq);
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
+int launch_replica_swap(const double* betas, int K, int M, int parity, const double* C, const double* u, double* beta_b, int* rung,
+                        int* chain_of, double* swap_acc, double* d, hipStream_t s) {
+    const long long np = (long long)M * (K - 1);
+    hipLaunchKernelGGL(k_replica_swap, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, betas, K, M, parity, C, u, beta_b, rung,
+                       chain_of, swap_acc, d);
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
+int launch_ladder_init(const double* betas_host, double* betas, int K, int M, double* beta_b, int* rung, int* chain_of, hipStream_t s) {
+    for (int k0 = 0; k0 < K; k0 += FT_LADDER_CHUNK) {
+        LadderChunk c;
+        const int n = K - k0 < FT_LADDER_CHUNK ? K - k0 : FT_LADDER_CHUNK;
+        for (int k = 0; k < FT_LADDER_CHUNK; ++k) c.v[k] = k < n ? betas_host[k0 + k] : 0.0;
+        hipLaunchKernelGGL(k_ladder_set, dim3(1), dim3(FT_LADDER_CHUNK), 0, s, c, n, betas + k0);
+        FT_LAUNCH_CHECK();
+    }
+    const long long B = (long long)M * K;
+    hipLaunchKernelGGL(k_ladder_init, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, betas, K, B, beta_b, rung, chain_of);
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
 int launch_kinetic(const double* v, int B, int L, double* K, hipStream_t s) {
     const int n = 2 * L * L;
     const int nt = n >= 8192 ? 1024 : (n >= 2048 ? 512 : 256);
@@ -839,7 +998,16 @@ int launch_wilson_force(const double* x, int B, int L, double beta, double* F, h
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_leap_step(const double* x, const double* p, double* xo, double* po, int B, int L,
-                     double beta, double a, double dt, hipStream_t s) {
+                     double beta, double a, double dt, hipStream_t s, const double* beta_b) {
+    if (beta_b) {                                // per-chain beta: the same two kernels, beta read at the chain's index
+        if (L % 64 == 0 && g_leap_rows) {
+            constexpr int TR = 8;
+            hipLaunchKernelGGL((k_leap_rows<TR, true>), dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, x, p, xo, po, L, beta_b, a, dt);
+            FT_LAUNCH_CHECK(); return FTHMC_OK;
+        }
+        hipLaunchKernelGGL((k_force<1, true>), tile_grid(B, L), dim3(256), 0, s, x, p, xo, po, L, beta_b, a, dt);
+        FT_LAUNCH_CHECK(); return FTHMC_OK;
+    }
     if (L % 64 == 0 && g_leap_rows) {            // whole 64-site row segments: 16-byte accesses, two sites per thread
         constexpr int TR = 8;
         hipLaunchKernelGGL(k_leap_rows<TR>, dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, x, p, xo, po, L, beta, a, dt);
@@ -855,7 +1023,16 @@ int launch_hmc_trajectory_fused(const double* x, const double* v, const double* 
     hipLaunchKernelGGL(k_hmc_trajectory, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, beta, dt, nstep, x_new, dH, acc, H0, H1);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
-int launch_wilson_gp(const double* x, int B, int L, double beta, double* gp, hipStream_t s) {
+int launch_wilson_gp(const double* x, int B, int L, double beta, double* gp, hipStream_t s, const double* beta_b) {
+    if (beta_b) {                                // per-chain beta: gP[b] = beta_b[b] sin P
+        if (L % 64 == 0 && g_leap_rows) {
+            constexpr int TR = 8;
+            hipLaunchKernelGGL((k_gp_rows<TR, true>), dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, x, gp, L, beta_b);
+            FT_LAUNCH_CHECK(); return FTHMC_OK;
+        }
+        hipLaunchKernelGGL((k_force<2, true>), tile_grid(B, L), dim3(256), 0, s, x, nullptr, gp, nullptr, L, beta_b, 0.0, 0.0);
+        FT_LAUNCH_CHECK(); return FTHMC_OK;
+    }
     if (L % 64 == 0 && g_leap_rows) {
         constexpr int TR = 8;
         hipLaunchKernelGGL(k_gp_rows<TR>, dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, x, gp, L, beta);
@@ -886,16 +1063,18 @@ int launch_shift_from_gp(const double* gp, const double* x, double* xs, int B, i
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_hmc_trajectory_sched(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sched,
-                                double* x_new, double* dH, double* acc, double* H0, double* H1, hipStream_t s) {
+                                double* x_new, double* dH, double* acc, double* H0, double* H1, hipStream_t s, const double* beta_b) {
     if (L > TJ_MAXL) return FTHMC_ERR_UNSUPPORTED;
     if (sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
-    hipLaunchKernelGGL(k_hmc_trajectory_sched, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, beta, sched, x_new, dH, acc, H0, H1);
+    if (beta_b) { hipLaunchKernelGGL(k_hmc_trajectory_sched<true>, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, beta_b, sched, x_new, dH, acc, H0, H1); }
+    else { hipLaunchKernelGGL(k_hmc_trajectory_sched<false>, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, beta, sched, x_new, dH, acc, H0, H1); }
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_traj_energy(const double* xphys, int B, int L, double beta, const double* lj_part, int np, int nsets,
-                       const double* state_in, const double* v, double* trip, double* H, hipStream_t s) {
+                       const double* state_in, const double* v, double* trip, double* H, hipStream_t s, const double* beta_b) {
     const int nt = L * L >= 4096 ? 1024 : (L * L >= 1024 ? 512 : 256);           // = launch_action_charge = launch_kinetic
-    hipLaunchKernelGGL(k_traj_energy, dim3(B), dim3(nt), 0, s, xphys, L, beta, lj_part, np, nsets, state_in, v, trip, H, B);
+    if (beta_b) { hipLaunchKernelGGL(k_traj_energy<true>, dim3(B), dim3(nt), 0, s, xphys, L, beta_b, lj_part, np, nsets, state_in, v, trip, H, B); }
+    else { hipLaunchKernelGGL(k_traj_energy<false>, dim3(B), dim3(nt), 0, s, xphys, L, beta, lj_part, np, nsets, state_in, v, trip, H, B); }
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_plane_from(const double* g, int B, int L, int mu, double sign, double* out, hipStream_t s) {

@@ -503,12 +503,24 @@ def leapfrog(x, p, beta: float, dt: float, nstep: int, integrator='leapfrog'):
     return xo, po
 
 
-def hmc_trajectory(x, v, u, beta: float, dt: float, nstep: int, out=None, integrator='leapfrog'):
-    """-> dict(x_new, dH, acc, H0, H1), per chain; out: optional dict with any of these to write into (x_new must not be x)."""
+def _beta_b(beta, B: int):
+    """beta as the per-chain device array of the `_pb` entry points (a tensor of B doubles, used IN PLACE: a replica exchange
+    updates it between calls), or None for a Python number: the scalar entry points, untouched."""
+    if not isinstance(beta, torch.Tensor):
+        return None
+    if not beta.is_cuda or beta.dtype != torch.float64 or not beta.is_contiguous() or beta.numel() != B:
+        raise FthmcError(f'beta: a per-chain beta is a contiguous float64 device tensor of {B} entries')
+    return beta.view(-1)
+
+
+def hmc_trajectory(x, v, u, beta, dt: float, nstep: int, out=None, integrator='leapfrog'):
+    """-> dict(x_new, dH, acc, H0, H1), per chain; out: optional dict with any of these to write into (x_new must not be x).
+    beta: a number, or a device tensor of B doubles -- per-chain beta (C ABI fthmc_hmc_trajectory_pb)."""
     ic = integrator_code(integrator)
     x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
     if u.numel() != B:
         raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
+    bb = _beta_b(beta, B)
     xn = None if out is None else out.get('x_new')
     if xn is None:
         xn = torch.empty_like(x)
@@ -516,6 +528,11 @@ def hmc_trajectory(x, v, u, beta: float, dt: float, nstep: int, out=None, integr
         raise FthmcError('out[\'x_new\']: expected a contiguous device tensor of the shape of x that is not x')
     dH, acc, H0, H1 = (_out_vec(out, k, B, x) for k in ('dH', 'acc', 'H0', 'H1'))
     ws, nb = _ws(x, B, L, 0)
+    if bb is not None:
+        check(_lib.load().fthmc_hmc_trajectory_pb(_p(x), _p(v), _p(u), B, L, _p(bb), float(dt), int(nstep), ic,
+                                                  _p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x)),
+              'fthmc_hmc_trajectory_pb')
+        return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1}
     if ic:
         check(_lib.load().fthmc_hmc_trajectory_int(_p(x), _p(v), _p(u), B, L, float(beta), float(dt), int(nstep), ic,
                                                    _p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x)),
@@ -525,6 +542,62 @@ def hmc_trajectory(x, v, u, beta: float, dt: float, nstep: int, out=None, integr
                                            _p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x)),
           'fthmc_hmc_trajectory')
     return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1}
+
+
+# ---------------------------------------------------------------- replica exchange (parallel tempering)
+def _i32(t, n: int, name: str):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n:
+        raise FthmcError(f'{name}: expected a contiguous int32 device tensor of {n} entries')
+    return t
+
+
+def ladder_init(betas, n_ladders: int, device=None):
+    """M = n_ladders ladders of K = len(betas) consecutive chains, every ladder in order (C ABI fthmc_ladder_init) ->
+    dict(betas [K], beta_b [M K], rung [M K] int32, chain_of [M K] int32) on the device.  betas: strictly increasing."""
+    import ctypes
+    bl = [float(b) for b in betas]
+    K, M = len(bl), int(n_ladders)
+    if K < 2 or M < 1 or any(not (bl[k] < bl[k + 1]) for k in range(K - 1)):
+        raise ValueError(f'ladder_init: at least two strictly increasing betas and one ladder expected, got {bl}, {M}')
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    r = {'betas': torch.empty(K, dtype=torch.float64, device=dev), 'beta_b': torch.empty(M * K, dtype=torch.float64, device=dev),
+         'rung': torch.empty(M * K, dtype=torch.int32, device=dev), 'chain_of': torch.empty(M * K, dtype=torch.int32, device=dev)}
+    host = (ctypes.c_double * K)(*bl)
+    with torch.cuda.device(dev):
+        check(_lib.load().fthmc_ladder_init(host, K, M, _p(r['betas']), _p(r['beta_b']), _p(r['rung']), _p(r['chain_of']),
+                                            _stream(r['betas'])), 'fthmc_ladder_init')
+    return r
+
+
+def replica_swap(betas, C, u, beta_b, rung, chain_of, parity: int, out: Optional[dict] = None):
+    """One round of replica exchange over the M = B / K ladders of K = len(betas) consecutive chains (C ABI fthmc_replica_swap):
+    for every pair of neighbouring rungs k = parity (mod 2), accept iff u[m, k] < exp((beta_k - beta_{k+1}) (C_c - C_a)), C = sum
+    cos P per chain (row 1 of the beta-free state).  beta_b, rung and chain_of are updated IN PLACE; fields never move.
+    -> dict(swap_acc [M, K - 1] (1, 0, or -1: not attempted in this round), d [M, K - 1]); `out` may carry both."""
+    betas = _dev(betas, 'betas').view(-1); K = betas.numel()
+    if isinstance(beta_b, torch.Tensor) and not beta_b.is_contiguous():
+        raise FthmcError('beta_b: expected a contiguous tensor (it is updated in place)')
+    beta_b = _dev(beta_b, 'beta_b').view(-1); B = beta_b.numel()
+    if K < 2 or B % K != 0 or B == 0:
+        raise FthmcError(f'replica_swap: {B} chains do not form whole ladders of {K} rungs')
+    M = B // K
+    C = _dev(C, 'C').reshape(-1); u = _dev(u, 'u').reshape(-1)
+    if C.numel() != B or u.numel() != M * (K - 1):
+        raise FthmcError(f'replica_swap: expected C [{B}] and u [{M}, {K - 1}]')
+    _i32(rung, B, 'rung'); _i32(chain_of, B, 'chain_of')
+    if int(parity) not in (0, 1):
+        raise ValueError(f'parity: 0 or 1, got {parity!r}')
+    if out is None:
+        out = {}
+    for k in ('swap_acc', 'd'):
+        if k not in out:
+            out[k] = torch.empty(M, K - 1, dtype=torch.float64, device=beta_b.device)
+        elif not out[k].is_cuda or out[k].dtype != torch.float64 or not out[k].is_contiguous() or out[k].numel() != M * (K - 1):
+            raise FthmcError(f'out[{k!r}]: expected a contiguous float64 device tensor of {M * (K - 1)} entries')
+    with torch.cuda.device(beta_b.device):
+        check(_lib.load().fthmc_replica_swap(_p(betas), K, M, int(parity), _p(C), _p(u), _p(beta_b), _p(rung), _p(chain_of),
+                                             _p(out['swap_acc']), _p(out['d']), _stream(beta_b)), 'fthmc_replica_swap')
+    return out
 
 
 # ---------------------------------------------------------------- coupling layer
@@ -788,7 +861,7 @@ def _side_streams(device, n: int):
     return pool[:n]
 
 
-def ft_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int, act='silu', mode='md',
+def ft_trajectory(x, v, u, w, n_layers: int, beta, dt: float, nstep: int, act='silu', mode='md',
                   out: Optional[dict] = None, state_in: Optional[torch.Tensor] = None, groups: int = 1, arch=None, wkey=None,
                   side_streams=None, integrator='leapfrog'):
     """One ftHMC trajectory per chain -> dict(x_new, dH, acc, H0, H1, plaq, Q, state).
@@ -803,13 +876,19 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int,
     tail and dispatch gap.  Results do not depend on `groups`.
 
     integrator: 'leapfrog' | 'omelyan' | 'force_gradient' -- the MD between the two energies (csrc/integrator.h; nstep steps cost
-    integrator_forces(integrator, nstep) force evaluations); mode 'literal' discards the MD and takes 'leapfrog' only."""
+    integrator_forces(integrator, nstep) force evaluations); mode 'literal' discards the MD and takes 'leapfrog' only.
+
+    beta: a number, or a device tensor of B doubles -- per-chain beta (C ABI fthmc_ft_trajectory_pb_v; mode 'md' only), read in
+    place.  `state` is then the BETA-FREE triple [3, B] = (log det J, sum cos P, Q) of x_new, valid as `state_in` under any beta."""
     ic = integrator_code(integrator)
     if ic and mode not in ('md',):
         raise ValueError(f'mode {mode!r} discards the MD: it goes with integrator=\'leapfrog\' only, got {integrator!r}')
     x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
     if u.numel() != B:
         raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
+    bb = _beta_b(beta, B)
+    if bb is not None and mode != 'md':
+        raise ValueError(f'a per-chain beta goes with mode \'md\' only, got {mode!r}')
     w, ap, a = _wall(w, n_layers, arch)
     if out is None:
         out = {'x_new': torch.empty_like(x)}
@@ -839,7 +918,8 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int,
             with torch.cuda.stream(st):
                 og = {k: t[a:b_] for k, t in out.items() if k != 'state'}
                 sg = state_in[:, a:b_].contiguous() if state_in is not None else None
-                ft_trajectory(x[a:b_], v[a:b_], u[a:b_], w, n_layers, beta, dt, nstep, act, mode, og, sg, arch=arch_, wkey=wkey,
+                ft_trajectory(x[a:b_], v[a:b_], u[a:b_], w, n_layers, beta if bb is None else bb[a:b_], dt, nstep, act, mode, og, sg,
+                              arch=arch_, wkey=wkey,
                               integrator=integrator)                    # one group: no side streams
                 out['state'][:, a:b_].copy_(og['state'])
                 parts.append(og)                                        # keep the group's temporaries alive until the join
@@ -852,6 +932,13 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int,
             raise FthmcError(f'state_in: expected [3, {B}]')
     m = {'md': MODE_MD, 'literal': MODE_LITERAL, 'reference_literal': MODE_LITERAL}[mode]
     ws, nb = _ws(x, B, L, n_layers, arch=a)
+    if bb is not None:
+        check(_lib.load().fthmc_ft_trajectory_pb_v(_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), _p(bb),
+                                                   float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']),
+                                                   _p(out['H0']), _p(out['H1']), _p(out['plaq']), _p(out['Q']),
+                                                   _p(state_in), _p(out['state']), ws, nb,
+                                                   _stream(x), ic, weights_version(wkey)), 'fthmc_ft_trajectory_pb')
+        return out
     if ic:
         check(_lib.load().fthmc_ft_trajectory_int_v(_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), float(beta),
                                                     float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']),

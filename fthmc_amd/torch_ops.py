@@ -32,6 +32,12 @@ Operators (reference call site each one replaces):
                    H g and d/dw <g, F> for the force F                         (autograd of qed_helpers.py:226-242, create_graph)
   train_force_grad(x, w_all, n_layers, beta, act, n_mix=2, hidden, kernel_size) -> (F, force_sq, gw)
                    the force, sum_links F_b^2 and d(sum_b |F_b|^2)/dw          ipynb/ft_hmc.py:253-299 (with_force)
+  ft_trajectory_pb(x, v, u, w_all, n_layers, beta_b, dt, nstep, integrator, act, state_in=None, n_mix=2, hidden, kernel_size)
+                   -> (x_new, dH, acc, plaq, Q, state)   per-chain beta (replica exchange; no reference counterpart): state is the
+                   beta-free triple [3, B] = (log det J, sum cos P, Q); integrator 0 leapfrog, 1 omelyan, 2 force_gradient
+  hmc_trajectory_pb(x, v, u, beta_b, dt, nstep, integrator=0) -> (x_new, dH, acc)          plain HMC, per-chain beta
+  replica_swap(betas, C, u, beta_b!, rung!, chain_of!, parity) -> (swap_acc, d)            one exchange round; updates beta_b,
+                   rung, chain_of in place (ops.replica_swap)
 `act` is the integer code of fthmc_hip.h (0 silu/swish, 1 relu, 2 leaky_relu); `mode` 0 = MD
 semantics, 1 = literal reference leapfrog.  The s/t net's shape travels IN the schema, as plain
 integers: `n_mix` mixture components, `hidden` = hidden_sizes (None = the reference default [8, 8]), `kernel_size` --
@@ -172,6 +178,37 @@ if BACKEND == 'python':
         return r['F'], r['force_sq'], gw
 
 
+    _INT = {v: k for k, v in _lib.INTEGRATORS.items()}
+
+
+    @torch.library.custom_op('fthmc_hip::ft_trajectory_pb', mutates_args=(), device_types=_DEV)
+    def ft_trajectory_pb(x: torch.Tensor, v: torch.Tensor, u: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta_b: torch.Tensor,
+                         dt: float, nstep: int, integrator: int, act: int, state_in: Optional[torch.Tensor] = None, n_mix: int = 2,
+                         hidden: Optional[Sequence[int]] = None, kernel_size: int = 3
+                         ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        if integrator not in _INT:
+            raise FthmcError(f'integrator: expected 0, 1 or 2, got {integrator}')
+        r = ops.ft_trajectory(x, v, u, w_all, n_layers, beta_b.contiguous(), dt, nstep, _act(act), 'md', state_in=state_in,
+                              arch=_arch(n_mix, hidden, kernel_size), integrator=_INT[integrator])
+        return r['x_new'], r['dH'], r['acc'], r['plaq'], r['Q'], r['state']
+
+
+    @torch.library.custom_op('fthmc_hip::hmc_trajectory_pb', mutates_args=(), device_types=_DEV)
+    def hmc_trajectory_pb(x: torch.Tensor, v: torch.Tensor, u: torch.Tensor, beta_b: torch.Tensor, dt: float, nstep: int,
+                          integrator: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        if integrator not in _INT:
+            raise FthmcError(f'integrator: expected 0, 1 or 2, got {integrator}')
+        r = ops.hmc_trajectory(x, v, u, beta_b.contiguous(), dt, nstep, integrator=_INT[integrator])
+        return r['x_new'], r['dH'], r['acc']
+
+
+    @torch.library.custom_op('fthmc_hip::replica_swap', mutates_args=('beta_b', 'rung', 'chain_of'), device_types=_DEV)
+    def replica_swap(betas: torch.Tensor, C: torch.Tensor, u: torch.Tensor, beta_b: torch.Tensor, rung: torch.Tensor,
+                     chain_of: torch.Tensor, parity: int) -> tuple[torch.Tensor, torch.Tensor]:
+        r = ops.replica_swap(betas, C, u, beta_b, rung, chain_of, parity)
+        return r['swap_acc'], r['d']
+
+
 # ---------------------------------------------------------------- shapes for tracing (meta tensors)
 def _b(x):
     return x.new_empty(x.shape[0])
@@ -247,6 +284,22 @@ def _(x, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
     return torch.empty_like(x), _b(x), x.new_empty(w_all.numel())
 
 
+@torch.library.register_fake('fthmc_hip::ft_trajectory_pb')
+def _(x, v, u, w_all, n_layers, beta_b, dt, nstep, integrator, act, state_in=None, n_mix=2, hidden=None, kernel_size=3):
+    return torch.empty_like(x), _b(x), _b(x), _b(x), _b(x), x.new_empty(3, x.shape[0])
+
+
+@torch.library.register_fake('fthmc_hip::hmc_trajectory_pb')
+def _(x, v, u, beta_b, dt, nstep, integrator=0):
+    return torch.empty_like(x), _b(x), _b(x)
+
+
+@torch.library.register_fake('fthmc_hip::replica_swap')
+def _(betas, C, u, beta_b, rung, chain_of, parity):
+    M, K = beta_b.numel() // betas.numel(), betas.numel()
+    return beta_b.new_empty(M, K - 1), beta_b.new_empty(M, K - 1)
+
+
 # ---------------------------------------------------------------- autograd formulas
 def _wilson_setup(ctx, inputs, output):
     x, beta = inputs
@@ -317,9 +370,9 @@ torch.library.register_autograd('fthmc_hip::ft_action_force', _action_force_back
 if BACKEND == 'compiled':                        # the module's names are the dispatcher's operators themselves
     for _n in ('wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x', 'flow_layer_bwd_w',
                'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad', 'ft_action_vjp',
-               'ft_force_vjp', 'train_force_grad'):
+               'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap'):
         globals()[_n] = getattr(torch.ops.fthmc_hip, _n)
 
 __all__ = ['wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x',
            'flow_layer_bwd_w', 'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad',
-           'ft_action_vjp', 'ft_force_vjp', 'train_force_grad']
+           'ft_action_vjp', 'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap']

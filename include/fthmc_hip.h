@@ -370,6 +370,43 @@ int fthmc_ft_trajectory_int_v(const double* x, const double* v, const double* u,
                               const double* state_in, double* state_out,
                               void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version);
 
+/* ---- Per-chain beta and replica exchange (parallel tempering).  The reference has no counterpart, as for the integrators: it
+ * samples one beta per run.  B = M K chains form M ladders of K consecutive chains; beta_b[B] (device) holds every chain's beta.
+ *
+ * fthmc_ft_trajectory_pb_v generalises fthmc_ft_trajectory_int_v: the device array beta_b in place of `double beta`, FTHMC_MODE_MD
+ * only (another mode: FTHMC_ERR_UNSUPPORTED), every integrator, every branch of the scalar call (the one-launch kernel of the small
+ * lattices, the tuned kernels, other net shapes / the VALU variant / ragged lattices / n_layers = 0).  With a constant beta_b its
+ * x_new, dH, acc, H0, H1, plaq, Q are those of the scalar call.  The carried state is BETA-FREE:
+ *     state[3][B] = (log det J, C = sum cos P, Q) of the accepted field,
+ * from which a call forms S_W = (-beta_b[b]) C, S_eff = S_W - log det J and plaq = (-S_W) / (beta_b[b] L^2) -- so a chained call
+ * equals a stateless one at ANY beta_b, and an exchange of betas between two chains leaves the state valid.  ws: fthmc_ws_bytes.
+ * fthmc_hmc_trajectory_pb generalises fthmc_hmc_trajectory_int in the same way (plain HMC; no state). */
+int fthmc_ft_trajectory_pb_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch,
+                             int n_layers, int B, int L, int act, const double* beta_b, double dt, int nstep,
+                             int mode, double* x_new, double* dH, double* acc,
+                             double* H0, double* H1, double* plaq, double* Q,
+                             const double* state_in, double* state_out,
+                             void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version);
+int fthmc_hmc_trajectory_pb(const double* x, const double* v, const double* u, int B, int L, const double* beta_b, double dt, int nstep,
+                            int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                            void* ws, size_t ws_bytes, void* stream);
+/* One round of replica exchange.  betas[K]: the ladder, strictly increasing; rung[B]: the rung of every chain; chain_of[B]: per
+ * ladder, the chain (its index INSIDE the ladder, 0 .. K - 1) on every rung -- the inverse of rung within the ladder.  For every
+ * ladder m and every k = parity (mod 2), k + 1 < K: a = chain on rung k, c = chain on rung k + 1,
+ *     d = (beta_k - beta_{k+1}) (C[c] - C[a]);   accept iff u[m (K - 1) + k] < exp(d)
+ * with C[B] = sum cos P of the chains' (flowed) fields, row 1 of the beta-free state: all rungs share ONE flow, so the log det J
+ * terms of the exact ratio cancel.  An accepted pair exchanges its rung, beta_b and chain_of entries; fields never move.
+ * Optional outputs [M][K - 1]: swap_acc = 1 / 0, or -1 for a pair not attempted in this round; d (0 where not attempted).  The pairs
+ * of a round are disjoint: no atomics, two calls give the same bits.  u[M][K - 1]: uniforms on [0, 1), an input as for a trajectory.
+ * K < 2, M < 1, K M > FTHMC_MAX_B, parity not 0 / 1, a null pointer: FTHMC_ERR_ARG. */
+int fthmc_replica_swap(const double* betas, int K, int M, int parity, const double* C, const double* u, double* beta_b, int32_t* rung,
+                       int32_t* chain_of, double* swap_acc, double* d, void* stream);
+/* Every ladder in order: betas <- betas_host (host, K doubles, read DURING the call: they travel in kernel arguments, so the call
+ * only enqueues, can be captured, and the host array may be freed when it returns), and for chain b = m K + k: beta_b = betas[k],
+ * rung = k, chain_of = k.  A ladder that is not strictly increasing: FTHMC_ERR_ARG; sizes and pointers as fthmc_replica_swap. */
+int fthmc_ladder_init(const double* betas_host, int K, int M, double* betas, double* beta_b, int32_t* rung, int32_t* chain_of,
+                      void* stream);
+
 /* ---- training ------------------------------------------------------------ */
 /* Reverse-KL loss pieces and weight gradients for a fixed prior draw xi
  * (fthmc/train.py:191-210, fthmc/utils/samplers.py:40-56):
