@@ -112,7 +112,10 @@ _i = SIGNATURES['fthmc_hmc_trajectory_int'].index(c_double)
 SIGNATURES['fthmc_hmc_trajectory_pb'] = SIGNATURES['fthmc_hmc_trajectory_int'][:_i] + [_D] + SIGNATURES['fthmc_hmc_trajectory_int'][_i + 1:]
 SIGNATURES['fthmc_replica_swap'] = [_D, c_int, c_int, c_int, _D, _D, _D, _D, _D, _D, _D, _P]
 SIGNATURES['fthmc_ladder_init'] = [ctypes.POINTER(c_double), c_int, c_int, _D, _D, _D, _D, _P]
-_RESTYPE = {'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
+# Wilson loops / Polyakov-loop correlators: the table W[B][Rmax][Tmax] and, optionally, its batch mean
+SIGNATURES['fthmc_wilson_loops_ws_bytes'] = [c_int, c_int, c_int, c_int]
+SIGNATURES['fthmc_wilson_loops'] = [_D, c_int, c_int, c_int, c_int, _D, _D, _P, c_size_t, _P]
+_RESTYPE = {'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None
 

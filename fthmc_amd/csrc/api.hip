@@ -1212,6 +1212,22 @@ int fthmc_ladder_init(const double* betas_host, int K, int M, double* betas, dou
     return launch_ladder_init(betas_host, betas, K, M, beta_b, rung, chain_of, ft_stream(stream));
 }
 
+// Wilson loops (loops.hip): the argument checks and the three regions of the workspace; the kernels know nothing of `ws`
+size_t fthmc_wilson_loops_ws_bytes(int B, int L, int Rmax, int Tmax) {
+    if (bad_shape(B, L) || Rmax < 1 || Rmax > L || Tmax < 1 || Tmax > L) return 0;
+    const LoopsGeom g = loops_geom(B, L, Rmax, Tmax);
+    return g.ok ? g.total * sizeof(double) : 0;
+}
+
+int fthmc_wilson_loops(const double* x, int B, int L, int Rmax, int Tmax, double* W, double* Wmean, void* ws, size_t ws_bytes,
+                       void* stream) {
+    if (!x || !W || bad_shape(B, L) || Rmax < 1 || Rmax > L || Tmax < 1 || Tmax > L) return FTHMC_ERR_ARG;
+    const LoopsGeom g = loops_geom(B, L, Rmax, Tmax);
+    if (!g.ok || !ws || ws_bytes / sizeof(double) < g.total) return FTHMC_ERR_WS;
+    double* prefix = static_cast<double*>(ws);
+    return launch_wilson_loops(x, B, L, Rmax, Tmax, W, Wmean, prefix, prefix + g.prefix, prefix + g.prefix + g.part, ft_stream(stream));
+}
+
 int fthmc_ft_trajectory(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
                         int B, int L, int act, double beta, double dt, int nstep, int mode, double* x_new,
                         double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,

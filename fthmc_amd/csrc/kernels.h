@@ -70,6 +70,43 @@ int launch_train_metrics(const double* logq, const double* logp, const double* q
 int launch_adam(double* p, const double* g, double* m, double* v, double* hp, size_t n, double b1, double b2, double eps,
                 double wd, int decoupled, hipStream_t s);       // hp: [t, lr, ticket] on the device
 
+// ---- loops.hip: the table of rectangular Wilson loops W[b][R-1][T-1], R <= Rmax, T <= Tmax (fthmc_wilson_loops)
+constexpr int LP_THREADS = 256;               // threads of a walking workgroup
+constexpr int LP_SITES = 1024;                // sites a workgroup walks at a time: four per thread, 32 KB of LDS planes
+constexpr int LP_LDS_MAXL = 1024;             // beyond it a row of the planes (32 L bytes) lives in global scratch
+constexpr int LP_BIG_WGS = 1024;              // workgroups (and scratch slots) of that path
+// How a call is cut up, and its workspace in doubles: prefix[B][L+1][L] | part[B][Rmax][nblk][Tmax] | scratch (L > LP_LDS_MAXL).
+// ok = false: a size beyond size_t (no workspace can hold it)
+struct LoopsGeom {
+    bool ok, lds;
+    int rows, nblk, nwg;                      // rows per workgroup, partials per (chain, R), workgroups of the large-L path
+    size_t prefix, part, scratch, total;
+};
+inline LoopsGeom loops_geom(int B, int L, int Rmax, int Tmax) {
+    LoopsGeom g{};
+    g.lds = L <= LP_LDS_MAXL;
+    if (g.lds) {
+        g.rows = LP_SITES / L < 1 ? 1 : (LP_SITES / L > L ? L : LP_SITES / L);
+        g.nblk = (L + g.rows - 1) / g.rows;
+    } else {
+        g.rows = 1;
+        g.nblk = L * ((L + LP_SITES - 1) / LP_SITES);
+        const long long items = (long long)B * Rmax * L;
+        g.nwg = items < LP_BIG_WGS ? (int)items : LP_BIG_WGS;
+    }
+    auto pad = [](size_t n) { return (n + 31) / 32 * 32; };    // regions start on 256 B: the planes are read 16 bytes at a time
+    size_t p = 0;
+    g.prefix = pad((size_t)B * (size_t)(L + 1) * (size_t)L);            // < 2^22 2^30: fits
+    g.ok = !__builtin_mul_overflow((size_t)B * (size_t)Rmax, (size_t)g.nblk * (size_t)Tmax, &p) && p < ((size_t)1 << 59);
+    g.part = g.ok ? pad(p) : 0;
+    g.scratch = g.lds ? 0 : pad((size_t)g.nwg * 4 * ((size_t)L + (size_t)Tmax));
+    g.total = g.prefix + g.part + g.scratch;
+    return g;
+}
+// prefix, part, scratch: the three regions of the workspace (api.hip carves them)
+int launch_wilson_loops(const double* x, int B, int L, int Rmax, int Tmax, double* W, double* Wmean, double* prefix, double* part,
+                        double* scratch, hipStream_t s);
+
 // ---- rng.hip
 int launch_random_momenta(const int64_t* seeds, int B, int n, double* v, double* u, hipStream_t s);
 int launch_random_uniform(const int64_t* seeds, int B, int n, double lo, double hi, double* out, hipStream_t s);

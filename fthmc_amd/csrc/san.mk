@@ -44,3 +44,11 @@ san_tempering: $(SANOUT)
 	mkdir -p $(dir $(SANTEMP))
 	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
 	  ../../tests/hip/tempering_walk.cpp -o $(SANTEMP) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
+
+# The Wilson-loop entry points (fthmc_wilson_loops_ws_bytes, fthmc_wilson_loops): tests/hip/loops_walk.cpp in the same way, run
+# by tests/test_wilson_loops.py
+SANLOOPS ?= $(SANDIR)/loops_walk
+san_loops: $(SANOUT)
+	mkdir -p $(dir $(SANLOOPS))
+	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
+	  ../../tests/hip/loops_walk.cpp -o $(SANLOOPS) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))

@@ -103,6 +103,18 @@ Tensor wilson_force(const Tensor& x_, double beta) {
     ok(fthmc_wilson_force(cp(x), (int)x.size(0), (int)x.size(2), beta, mp(F), cur_stream(x)), "fthmc_wilson_force");
     return F;
 }
+// the table of Wilson loops [B, Rmax, Tmax] (no autograd formula: an observable)
+Tensor wilson_loops(const Tensor& x_, int64_t Rmax, int64_t Tmax) {
+    FT_DEVICE_GUARD(x_);
+    Tensor x = field(x_, "x");
+    const int B = (int)x.size(0), L = (int)x.size(2);
+    TORCH_CHECK(Rmax >= 1 && Rmax <= L && Tmax >= 1 && Tmax <= L, "wilson_loops: 1 <= Rmax, Tmax <= L = ", L, " expected, got ", Rmax, ", ", Tmax);
+    const size_t bytes = fthmc_wilson_loops_ws_bytes(B, L, (int)Rmax, (int)Tmax);
+    TORCH_CHECK(bytes > 0, "wilson_loops: unsupported shape (B = ", B, ", L = ", L, ", Rmax = ", Rmax, ", Tmax = ", Tmax, ")");
+    Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, x.options()), W = at::empty({B, Rmax, Tmax}, x.options());
+    ok(fthmc_wilson_loops(cp(x), B, L, (int)Rmax, (int)Tmax, mp(W), nullptr, mp(ws), bytes, cur_stream(x)), "fthmc_wilson_loops");
+    return W;
+}
 std::tuple<Tensor, Tensor, Tensor> hmc_trajectory(const Tensor& x_, const Tensor& v_, const Tensor& u_, double beta, double dt, int64_t nstep) {
     FT_DEVICE_GUARD(x_);
     Tensor x = field(x_, "x"), v = field(v_, "v");
@@ -329,6 +341,7 @@ std::tuple<Tensor, Tensor> replica_swap(const Tensor& betas_, const Tensor& C_, 
 TORCH_LIBRARY(fthmc_hip, m) {
     m.def("wilson_action_charge(Tensor x, float beta) -> (Tensor, Tensor, Tensor)");
     m.def("wilson_force(Tensor x, float beta) -> Tensor");
+    m.def("wilson_loops(Tensor x, int Rmax, int Tmax) -> Tensor");
     m.def("hmc_trajectory(Tensor x, Tensor v, Tensor u, float beta, float dt, int nstep) -> (Tensor, Tensor, Tensor)");
     m.def("flow_layer_fwd(Tensor x, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
     m.def("flow_layer_bwd_x(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> Tensor");
@@ -350,6 +363,7 @@ TORCH_LIBRARY(fthmc_hip, m) {
 TORCH_LIBRARY_IMPL(fthmc_hip, CUDA, m) {
     m.impl("wilson_action_charge", &wilson_action_charge);
     m.impl("wilson_force", &wilson_force);
+    m.impl("wilson_loops", &wilson_loops);
     m.impl("hmc_trajectory", &hmc_trajectory);
     m.impl("flow_layer_fwd", &flow_layer_fwd);
     m.impl("flow_layer_bwd_x", &flow_layer_bwd_x);

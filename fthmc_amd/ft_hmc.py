@@ -11,6 +11,7 @@ Two reference quirks are explicit switches, defaults = what the m
                                       (no 1/2, kinetic term summed over the whole batch)
 Beyond the reference: integrator = 'leapfrog' (default) | 'omelyan' | 'force_gradient' chooses the MD between the two energies
 (csrc/integrator.h; lfconfig.nstep steps of it cost ops.integrator_forces(integrator, nstep) force evaluations).
+`run(..., loops=(Rmax, Tmax))` adds the table of Wilson loops of the PHYSICAL field F(x) to the history ('wloops').
 """
 from __future__ import annotations
 
@@ -262,20 +263,29 @@ class FieldTransformation(nn.Module):
         return {'plaq': p, 'q': q, 'dq': torch.sqrt((q - qold) ** 2)}
 
     def run(self, x: torch.Tensor = None, nprint: int = 25, nplot: int = 25, window: int = 10,
-            num_trajs: int = 1024, writer=None, plotdir: str = None, batch: bool = False, use_graph: bool = None, **kwargs):
+            num_trajs: int = 1024, writer=None, plotdir: str = None, batch: bool = False, use_graph: bool = None,
+            loops=None, loops_every: int = 1, **kwargs):
         """ft_hmc.py:272-346 without plotting: returns the history dict of per-trajectory metrics.
         batch=True advances a batch of independent chains with per-chain accepts.
 
         On the device the trajectory sequence (momenta and uniforms from torch's generator, the fused trajectory with the
         carried state, in place) is captured once in a hipGraph and replayed (`use_graph`, default on; FTHMC_RUN_GRAPH=0
         turns it off): the host issues one graph launch and one small copy per trajectory, the history is read back when it
-        is first looked at.  Same draws and bit-identical histories as the eager loop."""
+        is first looked at.  Same draws and bit-identical histories as the eager loop.
+
+        loops = (Rmax, Tmax) (default None: nothing is measured, nothing changes): after every `loops_every`-th trajectory
+        (0, loops_every, ...) the Wilson loops W(R, T), R <= Rmax, T <= Tmax, of the PHYSICAL field F(x) of the accepted latent
+        field are measured (ops.flow_forward, ops.wilson_loops) and history['wloops'] gains their mean over the chains, one
+        [Rmax, Tmax] table per measured trajectory.  In the captured loop the measurement is a captured sequence of its own
+        behind the trajectory's and the table rides in the loop's row.  utils.observables has the exact values and the analysis."""
         if x is None:
             x = self.initializer()
+        loops = self._loops_arg(loops, x.shape[-1])
+        loops_every = max(1, int(loops_every))
         use_graph = self.use_graph if use_graph is None else bool(use_graph)
         fused = (self.energy_mode == 'per_chain') if batch else (x.shape[0] == 1)
         if use_graph and fused and x.is_cuda and num_trajs > 0:
-            return self._run_captured(x, nprint, num_trajs, batch)
+            return self._run_captured(x, nprint, num_trajs, batch, loops, loops_every)
         history = {}
         q = qed.batch_charges(self.flow_forward(x)[0]) if batch else qed.batch_charges(x)
         for i in range(num_trajs):
@@ -289,10 +299,28 @@ class FieldTransformation(nn.Module):
                 metrics = {**metrics_, **self.lattice_metrics(x_phys, qold)}
             for key, val in metrics.items():
                 history.setdefault(key, []).append(val)
+            if loops is not None and i % loops_every == 0:
+                table = torch.empty(loops, dtype=DTYPE, device=x.device)
+                self._measure_loops(x, self.weights(x.device), loops, None, table)
+                history.setdefault('wloops', []).append(table)
             if nprint and i % nprint == 0:
                 self._print_line(i, metrics['acc'], metrics['dh'], metrics['plaq'], metrics['q'])
         self.x_last = x
         return history
+
+    @staticmethod
+    def _loops_arg(loops, L: int):
+        if loops is None:
+            return None
+        Rmax, Tmax = (int(loops), int(loops)) if isinstance(loops, int) else (int(loops[0]), int(loops[1]))
+        if not (1 <= Rmax <= L and 1 <= Tmax <= L):
+            raise ValueError(f'loops: (Rmax, Tmax) with 1 <= Rmax, Tmax <= L = {L} expected, got {loops!r}')
+        return Rmax, Tmax
+
+    def _measure_loops(self, x, w, loops, W, table, wkey=None):
+        """the loop table of F(x): per chain into W [B, Rmax, Tmax] (or a fresh tensor), its batch mean into `table` [Rmax, Tmax]"""
+        x_phys = ops.flow_forward(x, w, len(self.flow), self._act, wkey=wkey)[0]
+        ops.wilson_loops(x_phys, loops[0], loops[1], out=W, mean_out=table)
 
     @staticmethod
     def _print_line(i, acc, dh, plaq, q):
@@ -301,7 +329,7 @@ class FieldTransformation(nn.Module):
               f"q={float(torch.as_tensor(q).mean()):.3f}", flush=True)
 
     # ---- the captured loop ----------------------------------------------------------
-    def _run_captured(self, x: torch.Tensor, nprint: int, num_trajs: int, batch: bool):
+    def _run_captured(self, x: torch.Tensor, nprint: int, num_trajs: int, batch: bool, loops=None, loops_every: int = 1):
         dev = x.device
         caller = torch.cuda.current_stream(dev)
         B, L = x.shape[0], x.shape[-1]
@@ -314,12 +342,12 @@ class FieldTransformation(nn.Module):
         # the weights' content version is part of what a capture is FOR: its launches carry it to the library, which checks
         # it on the device against the stamps in the workspaces (include/fthmc_hip.h "Weight versions")
         sig = (tuple(x.shape), dev, w.data_ptr(), nl, act, mode, beta, self.dt, self.nstep, G, batch,
-               ops.get_variant(), ops.get_small_path(), ops.weights_version(wkey), self.integrator)
+               ops.get_variant(), ops.get_small_path(), ops.weights_version(wkey), self.integrator, loops, loops_every if loops else 1)
         if self._loop is not None and self._loop.get('pending') is not None:
             self._loop['pending']()                                       # an unread history of the previous run: read it before its ring is reused
             self._loop['pending'] = None
         if self._loop is None or self._loop['sig'] != sig:
-            self._loop = self._make_loop(xd, w, nl, act, mode, beta, G, batch, sig, wkey)
+            self._loop = self._make_loop(xd, w, nl, act, mode, beta, G, batch, sig, wkey, loops, loops_every)
 
         def prepare(lp):
             """start field, start state and the weight expansion on the loop's stream -> (q0, workspace token)"""
@@ -340,7 +368,7 @@ class FieldTransformation(nn.Module):
         q0, token = prepare(self._loop)
         if self._loop['loop'].captured and self._loop['token'] != token:
             # a workspace moved since the capture (grown by another caller of these streams): capture again
-            self._loop = self._make_loop(xd, w, nl, act, mode, beta, G, batch, sig, wkey)
+            self._loop = self._make_loop(xd, w, nl, act, mode, beta, G, batch, sig, wkey, loops, loops_every)
             q0, token = prepare(self._loop)
         lp = self._loop
         loop, xs, state = lp['loop'], lp['x'], lp['state']
@@ -356,7 +384,7 @@ class FieldTransformation(nn.Module):
                 with torch.cuda.stream(loop.stream):
                     lp['token'] = ops.trajectory_workspaces(xs, w, nl, groups=G, side_streams=lp['sides'], wkey=wkey)
             if nprint and i % nprint == 0:
-                r = torch.from_numpy(loop.last()).view(4, B)
+                r = torch.from_numpy(loop.last()[:4 * B]).view(4, B)
                 self._print_line(i, r[0], r[1], r[2], r[3])
         ev1.record(loop.stream)
         with torch.cuda.stream(loop.stream):
@@ -376,7 +404,8 @@ class FieldTransformation(nn.Module):
         lp['pending'] = loop_rows
 
         def fill():
-            H = torch.from_numpy(loop_rows()).to(dev).view(n, 4, B)
+            R_ = torch.from_numpy(loop_rows()).to(dev)
+            H = R_[:, :4 * B].reshape(n, 4, B)
             ev1.synchronize()
             dt = ev0.elapsed_time(ev1) * 1e-3 / n                         # per trajectory, on the device's clock
             qs = torch.cat([q0.reshape(1, -1).to(H.dtype), H[:, 3]], 0)
@@ -388,16 +417,23 @@ class FieldTransformation(nn.Module):
             else:
                 h.update({'acc': [H[i, 0, 0] > 0.5 for i in range(n)], 'dh': [H[i, 1, 0] for i in range(n)]})
             h.update({'plaq': [H[i, 2] for i in range(n)], 'q': [H[i, 3] for i in range(n)], 'dq': [dq[i] for i in range(n)]})
+            if loops is not None:                                         # the row's tail: the table of the last measured trajectory
+                h['wloops'] = [R_[i, 4 * B:].reshape(loops) for i in range(0, n, loops_every)]
             return h
         return LazyHistory(fill)
 
-    def _make_loop(self, x, w, nl, act, mode, beta, G, batch, sig, wkey):
+    def _make_loop(self, x, w, nl, act, mode, beta, G, batch, sig, wkey, loops=None, loops_every: int = 1):
         dev, B = x.device, x.shape[0]
         integrator = self.integrator                                      # what this capture is for (part of `sig`)
         xs = torch.empty_like(x)
         v = torch.empty_like(x)
         u = torch.empty(B, dtype=torch.float64, device=dev)
-        row = torch.empty(4, B, dtype=torch.float64, device=dev)          # acc, dH, plaq, Q of the trajectory
+        # acc, dH, plaq, Q of the trajectory [4, B]; with loops, the batch-mean table [Rmax, Tmax] behind them
+        nlp = loops[0] * loops[1] if loops is not None else 0
+        flat = torch.empty(4 * B + nlp, dtype=torch.float64, device=dev)
+        if nlp:
+            flat[4 * B:].zero_()
+        row = flat[:4 * B].view(4, B)
         state = torch.empty(3, B, dtype=torch.float64, device=dev)
         out = {'x_new': xs, 'acc': row[0], 'dH': row[1], 'plaq': row[2], 'Q': row[3], 'state': state,
                'H0': torch.empty(B, dtype=torch.float64, device=dev), 'H1': torch.empty(B, dtype=torch.float64, device=dev)}
@@ -418,7 +454,14 @@ class FieldTransformation(nn.Module):
             # in place: the accepted field replaces x, its (S_eff, plaq, Q) the carried state (both read before they are written)
             ops.ft_trajectory(xs, v, u, w, nl, beta, self.dt, self.nstep, act, mode=mode, out=out, state_in=state, groups=G,
                               side_streams=sides, wkey=wkey, integrator=integrator)
-        loop = GraphLoop(enqueue, row, use_graph=True, stream=lstream)
+        measure = None
+        if loops is not None:
+            W = torch.empty(B, loops[0], loops[1], dtype=torch.float64, device=dev)
+            table = flat[4 * B:].view(loops)
+
+            def measure():
+                self._measure_loops(xs, w, loops, W, table, wkey=wkey)    # of F(accepted latent field)
+        loop = GraphLoop(enqueue, flat, use_graph=True, stream=lstream, extra=measure, extra_every=loops_every)
         return {'sig': sig, 'loop': loop, 'x': xs, 'state': state, 'row': row, 'token': None, 'pending': None, 'sides': sides}
 
 

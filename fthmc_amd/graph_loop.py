@@ -43,11 +43,16 @@ class GraphLoop:
     The first `step()` runs the sequence eagerly (allocator, workspaces), then captures it -- the capture does not execute,
     so n calls of `step()` are exactly n iterations, with the same random draws as n eager ones (torch's generator takes
     part in the capture).  `stream`: the stream the loop runs on (default: a new one); an owner that re-captures often hands
-    in the same one every time."""
+    in the same one every time.
+
+    `extra` (optional): a second enqueue-only sequence that runs behind `enqueue` in every iteration whose number is a multiple of
+    `extra_every` (a measurement that is not wanted after every trajectory), captured in a graph of its own; it writes into `row`
+    too, whose entries keep their last values in the iterations between."""
 
     def __init__(self, enqueue: Callable[[], None], row: torch.Tensor, chunk: int = 256, use_graph: bool = True,
-                 stream: Optional[torch.cuda.Stream] = None):
+                 stream: Optional[torch.cuda.Stream] = None, extra: Optional[Callable[[], None]] = None, extra_every: int = 1):
         self.enqueue, self.row = enqueue, row
+        self.extra, self.extra_every, self.extra_graph = extra, max(1, int(extra_every)), None
         self.dev = row.device
         self.chunk = max(1, int(chunk))
         self.ring = torch.empty(self.chunk, row.numel(), dtype=row.dtype, device=self.dev)
@@ -63,18 +68,30 @@ class GraphLoop:
         return self.graph is not None
 
     def step(self):
+        measure = self.extra is not None and self.n % self.extra_every == 0
         with torch.cuda.stream(self.stream):
             if self.use_graph and self.graph is None:
                 self.enqueue()
+                if self.extra is not None:
+                    self.extra()                  # iteration 0 of a fresh loop: always a measured one
                 self.stream.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with capture(g, self.stream):
                     self.enqueue()
                 self.graph = g
+                if self.extra is not None:
+                    g = torch.cuda.CUDAGraph()
+                    with capture(g, self.stream):
+                        self.extra()
+                    self.extra_graph = g
             elif self.use_graph:
                 self.graph.replay()
+                if measure:
+                    self.extra_graph.replay()
             else:
                 self.enqueue()
+                if measure:
+                    self.extra()
             self.ring[self.n % self.chunk].copy_(self.row.reshape(-1))
             self.n += 1
             if self.n % self.chunk == 0:

@@ -12,12 +12,20 @@ from .utils import qed_helpers as qed
 
 
 def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, figsize=None, use_title: bool = True,
-            save_data: bool = False, nplot: int = 10, integrator: str = 'leapfrog'):
+            save_data: bool = False, nplot: int = 10, integrator: str = 'leapfrog', loops=None, loops_every: int = 1):
     """hmc.py:57-175: `param.nrun` experiments of `param.ntraj` trajectories each.
     Returns (fields_arr, histories) with the reference's metric keys.
-    integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h)."""
+    integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h).
+    loops = (Rmax, Tmax) (default None: nothing changes): after every `loops_every`-th trajectory of a run the Wilson loops of the
+    field are measured (ops.wilson_loops) and the history gains 'wloops', one [Rmax, Tmax] batch-mean table per measured
+    trajectory (utils.observables.exact_wilson_loop has the exact expectation)."""
     from . import ops
     ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
+    if loops is not None:
+        loops = (int(loops), int(loops)) if isinstance(loops, int) else (int(loops[0]), int(loops[1]))
+        if not (1 <= loops[0] <= param.L and 1 <= loops[1] <= param.L):
+            raise ValueError(f'loops: (Rmax, Tmax) with 1 <= Rmax, Tmax <= L = {param.L} expected, got {loops!r}')
+    loops_every = max(1, int(loops_every))
     action = qed.BatchAction(param.beta)
     histories, fields_arr, run_times = {}, [], []
     for n in range(param.nrun):
@@ -37,6 +45,10 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
                        'plaq': plaq, 'q': qnew, 'dq': dq}
             for k, v in metrics.items():
                 history.setdefault(k, []).append(v)
+            if loops is not None and i % loops_every == 0:
+                table = torch.empty(loops, dtype=DTYPE, device=x.device)
+                ops.wilson_loops(x.reshape((-1,) + tuple(x.shape[-3:])), loops[0], loops[1], mean_out=table)
+                history.setdefault('wloops', []).append(table)
             if param.nprint and (i - 1) % param.nprint == 0:
                 print(f"run {n} traj {i}: acc={float(acc):.0f} dH={float(dH):.4g} plaq={float(plaq):.6f} "
                       f"q={float(qnew):.2f}", flush=True)
@@ -46,6 +58,7 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
     if save_data:
         os.makedirs(param.logdir, exist_ok=True)
         np.savez(os.path.join(param.logdir, 'hmc_histories.npz'),
-                 **{f'run{n}_{k}': np.array([float(torch.as_tensor(v).reshape(-1)[0]) for v in vals])
+                 **{f'run{n}_{k}': (np.stack([v.cpu().numpy() for v in vals]) if k == 'wloops' else
+                                    np.array([float(torch.as_tensor(v).reshape(-1)[0]) for v in vals]))
                     for n, h in histories.items() for k, vals in h.items()})
     return fields_arr, histories

@@ -98,6 +98,8 @@ def release_workspaces():
     _WS.clear()
     _WS_CAPTURED.clear()
     _WS_RETIRED.clear()
+    _LOOPS_WS.clear()
+    _LOOPS_WS_RETIRED.clear()
 
 
 def weights_version(wkey) -> int:
@@ -342,6 +344,53 @@ def wilson_action_charge(x, beta: float, out=None):
     check(_lib.load().fthmc_wilson_action_charge(_p(x), B, L, float(beta), _p(S), _p(Q), _p(plaq), _stream(x)),
           'fthmc_wilson_action_charge')
     return S, Q, plaq
+
+
+_LOOPS_WS = {}     # (device index, stream) -> the workspace of wilson_loops (its own small buffer: never the flow workspaces of _ws)
+_LOOPS_WS_RETIRED = []   # outgrown ones a captured graph may still point into
+
+
+def wilson_loops_ws_bytes(B: int, L: int, Rmax: int, Tmax: int) -> int:
+    """Scratch of wilson_loops; 0 for a refused shape."""
+    return int(_lib.load().fthmc_wilson_loops_ws_bytes(B, L, Rmax, Tmax))
+
+
+def _loops_ws(t: torch.Tensor, need: int):
+    key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream)
+    buf = _LOOPS_WS.get(key)
+    if buf is None or buf.numel() * 8 < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise FthmcError(f'the loop workspace of this stream would have to be {"allocated" if buf is None else "grown"} ({need} bytes) '
+                             f'during graph capture: run the same call once eagerly on this stream first (warm-up), then capture')
+        if buf is not None:
+            _LOOPS_WS_RETIRED.append(buf)
+        buf = torch.empty((need + 7) // 8, dtype=torch.float64, device=t.device)
+        _LOOPS_WS[key] = buf
+    return buf.data_ptr(), buf.numel() * 8
+
+
+def wilson_loops(x, Rmax: int, Tmax: Optional[int] = None, out=None, mean_out=None):
+    """The table of rectangular Wilson loops of every chain (C ABI fthmc_wilson_loops) -> W [B, Rmax, Tmax]:
+    W[b, R-1, T-1] = mean over the L^2 corners of cos(angle of the R x T loop), extent R along x0's direction (axis 2 of x) and T
+    along x1's (axis 3), wrapping around the torus.  W[:, 0, 0] is the mean of cos P; the column T = L is the Polyakov-loop
+    correlator at distance R.  Tmax = None: Rmax.  `out` [B, Rmax, Tmax] and `mean_out` [Rmax, Tmax] (the mean over the chains,
+    added in index order) are written in place when given (contiguous float64 device tensors: a captured loop passes both).
+    Not differentiable: an observable of finished configurations."""
+    x = _field(x); B, _, L, _ = x.shape
+    Rmax = int(Rmax); Tmax = Rmax if Tmax is None else int(Tmax)
+    if not (1 <= Rmax <= L and 1 <= Tmax <= L):
+        raise ValueError(f'wilson_loops: 1 <= Rmax, Tmax <= L = {L} expected, got {Rmax}, {Tmax}')
+    for t, n, name in ((out, B * Rmax * Tmax, 'out'), (mean_out, Rmax * Tmax, 'mean_out')):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n):
+            raise FthmcError(f'{name}: expected a contiguous float64 device tensor of {n} entries')
+    W = torch.empty(B, Rmax, Tmax, dtype=x.dtype, device=x.device) if out is None else out
+    need = wilson_loops_ws_bytes(B, L, Rmax, Tmax)
+    if need == 0:
+        raise FthmcError(f'wilson_loops: shape B={B}, L={L}, Rmax={Rmax}, Tmax={Tmax} is refused (fthmc_wilson_loops_ws_bytes = 0)')
+    with torch.cuda.device(x.device):
+        ws, nb = _loops_ws(x, need)
+        check(_lib.load().fthmc_wilson_loops(_p(x), B, L, Rmax, Tmax, _p(W), _p(mean_out), ws, nb, _stream(x)), 'fthmc_wilson_loops')
+    return W.view(B, Rmax, Tmax)
 
 
 def wilson_force(x, beta: float):

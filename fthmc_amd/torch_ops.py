@@ -17,6 +17,8 @@ Two registrations of the SAME schemas (`BACKEND` says which one this process use
 Operators (reference call site each one replaces):
   wilson_action_charge(x, beta) -> (S, Q, plaq)      qed_helpers.py:94-116,177-186
   wilson_force(x, beta) -> F                         qed_helpers.py:265-272
+  wilson_loops(x, Rmax, Tmax) -> W[B, Rmax, Tmax]    rectangular Wilson loops / Polyakov-loop correlators (ops.wilson_loops; no
+                   reference counterpart).  NOT differentiable: no autograd formula is registered, a backward through it raises
   hmc_trajectory(x, v, u, beta, dt, nstep) -> (x_new, dH, acc)          qed_helpers.py:275-311
   flow_layer_fwd(x, w, mu, off, n_mix, act, hidden=None, kernel_size=3) -> (y, logJ)      layers.py:196-202,348-371
   flow_layer_bwd_x(x, gy, glogJ, w, mu, off, n_mix, act, hidden, kernel_size) -> gx        (autograd of the above)
@@ -83,6 +85,11 @@ if BACKEND == 'python':
     @torch.library.custom_op('fthmc_hip::wilson_force', mutates_args=(), device_types=_DEV)
     def wilson_force(x: torch.Tensor, beta: float) -> torch.Tensor:
         return ops.wilson_force(x, beta)
+
+
+    @torch.library.custom_op('fthmc_hip::wilson_loops', mutates_args=(), device_types=_DEV)
+    def wilson_loops(x: torch.Tensor, Rmax: int, Tmax: int) -> torch.Tensor:
+        return ops.wilson_loops(x, Rmax, Tmax)
 
 
     @torch.library.custom_op('fthmc_hip::hmc_trajectory', mutates_args=(), device_types=_DEV)
@@ -222,6 +229,11 @@ def _(x, beta):
 @torch.library.register_fake('fthmc_hip::wilson_force')
 def _(x, beta):
     return torch.empty_like(x)
+
+
+@torch.library.register_fake('fthmc_hip::wilson_loops')
+def _(x, Rmax, Tmax):
+    return x.new_empty(x.shape[0], Rmax, Tmax)
 
 
 @torch.library.register_fake('fthmc_hip::hmc_trajectory')
@@ -370,9 +382,9 @@ torch.library.register_autograd('fthmc_hip::ft_action_force', _action_force_back
 if BACKEND == 'compiled':                        # the module's names are the dispatcher's operators themselves
     for _n in ('wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x', 'flow_layer_bwd_w',
                'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad', 'ft_action_vjp',
-               'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap'):
+               'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap', 'wilson_loops'):
         globals()[_n] = getattr(torch.ops.fthmc_hip, _n)
 
 __all__ = ['wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x',
            'flow_layer_bwd_w', 'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad',
-           'ft_action_vjp', 'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap']
+           'ft_action_vjp', 'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap', 'wilson_loops']

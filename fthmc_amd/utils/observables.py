@@ -1,5 +1,7 @@
 """Host-side analysis of sampling histories: topological-charge tunnelling versus MD-time lag and the
-topological susceptibility.  numpy only; the histories come from
+topological susceptibility; the exact finite-volume Wilson loops of 2D U(1), Creutz ratios and the
+blocked mean of a history of loop tables (`exact_wilson_loop`, `string_tension_exact`, `creutz_ratios`, `loop_table`:
+beyond the reference, which measures no loops).  numpy only; the histories come from
 `FieldTransformation.run` / `run_hmc` (lists or arrays of per-trajectory charges, optionally per chain).
 
 Reference: ipynb/ft_hmc.py:16-53 (`average`, `sigma`, `sub_avg`, `block_list`, `change_sqr`, `change_sqr_vs_dt`),
@@ -85,3 +87,75 @@ def save_topo_change_sqr(fn: str, q_history: Sequence, drop_len: Optional[int] =
         for lag, mean, sig in rows:
             f.write(f'{lag} {mean} {sig}\n')
     return rows
+
+
+# ---------------------------------------------------------------- Wilson loops: the exact solution and the analysis of a history
+def _log_bessel_ratios(beta: float, nmax: int) -> np.ndarray:
+    """l[n] = log(I_n(beta) / I_0(beta)), n = 0 .. nmax, from the ratios r_n = I_{n+1} / I_n = 1 / (2 (n + 1) / beta + r_{n+1})
+    run DOWNWARD from r_N = 0 far beyond nmax (the recurrence contracts in that direction: every step keeps the relative
+    error at a few ulps).  Logarithms, so that I_n^V of V = 4096 neither overflows nor underflows."""
+    beta = float(beta)
+    if not beta > 0.0:
+        raise ValueError(f'beta > 0 expected, got {beta}')
+    N = nmax + 64 + int(2 * beta)
+    r = np.zeros(N + 1, dtype=np.longdouble)
+    b = np.longdouble(beta)
+    for n in range(N - 1, -1, -1):
+        r[n] = 1 / (2 * np.longdouble(n + 1) / b + r[n + 1])
+    l = np.zeros(nmax + 1, dtype=np.longdouble)
+    l[1:] = np.cumsum(np.log(r[:nmax]))
+    return l
+
+
+def exact_wilson_loop(beta: float, L: int, R: int, T: int, nmax: int = 40) -> float:
+    """<W(R, T)> of 2D U(1) with the Wilson action on the periodic L x L lattice (V = L^2 plaquettes), for a non-self-intersecting
+    R x T rectangle of area A = R T (character expansion; the sum over n runs over the topological sectors):
+        sum_n I_n(beta)^(V - A) I_{n+1}(beta)^A / sum_n I_n(beta)^V .
+    A = 1 is the plaquette; the formula is symmetric under A <-> V - A; T = L makes it the Polyakov-loop correlator at distance R;
+    W(L, L) = 1.  Evaluated in logarithms relative to I_0 (log-sum-exp in extended precision): beta = 6, V = 4096, A = V / 2 gives
+    its 1e-82 to 1e-10 relative."""
+    if not (1 <= R <= L and 1 <= T <= L):
+        raise ValueError(f'1 <= R, T <= L = {L} expected, got {R}, {T}')
+    return exact_loop_of_area(beta, int(L) * int(L), int(R) * int(T), nmax)
+
+
+def exact_loop_of_area(beta: float, V: int, A: int, nmax: int = 40) -> float:
+    """The formula of `exact_wilson_loop` as a function of the enclosed area A, 0 <= A <= V, alone (what it depends on)."""
+    if not 0 <= A <= V:
+        raise ValueError(f'0 <= A <= V = {V} expected, got {A}')
+    l = _log_bessel_ratios(beta, nmax + 1)
+    n = np.arange(-nmax, nmax + 1)
+    ln, ln1 = l[np.abs(n)], l[np.abs(n + 1)]                     # I_{-n} = I_n
+    num = (V - A) * ln + A * ln1
+    den = V * ln
+    m = max(num.max(), den.max())
+    return float(np.exp(num - m).sum() / np.exp(den - m).sum())
+
+
+def string_tension_exact(beta: float) -> float:
+    """sigma = -log(I_1(beta) / I_0(beta)): W(R, T) = exp(-sigma R T) in infinite volume, an exact area law."""
+    return float(-_log_bessel_ratios(beta, 1)[1])
+
+
+def creutz_ratios(W) -> np.ndarray:
+    """chi(R, T) = -log[ W(R, T) W(R - 1, T - 1) / (W(R, T - 1) W(R - 1, T)) ] for R, T >= 2 from a table W[..., R - 1, T - 1]
+    -> [..., Rmax - 1, Tmax - 1] (entry [R - 2, T - 2]); an exact area law gives the string tension everywhere.  NaN where the
+    argument of the logarithm is not positive (a noisy large loop)."""
+    W = np.asarray(W, dtype=np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return -np.log(W[..., 1:, 1:] * W[..., :-1, :-1] / (W[..., 1:, :-1] * W[..., :-1, 1:]))
+
+
+def loop_table(samples, n_block: int = N_BLOCK):
+    """(mean, error) of a history of loop tables `samples` [n, ..., Rmax, Tmax] (axis 0 = trajectory, e.g. history['wloops'];
+    axes between it and the table = chains, averaged): the error of the mean from `n_block` block means, as `change_sqr`."""
+    v = np.asarray([np.asarray(getattr(t, 'cpu', lambda: t)()) for t in samples], dtype=np.float64) if isinstance(samples, (list, tuple)) \
+        else np.asarray(samples, dtype=np.float64)
+    if v.ndim < 3:
+        raise ValueError(f'loop_table: [n, ..., Rmax, Tmax] expected, got {v.shape}')
+    if v.ndim > 3:
+        v = v.reshape(v.shape[0], -1, *v.shape[-2:]).mean(axis=1)
+    bm = block_means(v, n_block)
+    nb = bm.shape[0]
+    err = np.sqrt(bm.var(axis=0) / (nb - 1)) if nb > 1 else np.full(bm.shape[1:], np.nan)
+    return bm.mean(axis=0), err

@@ -79,6 +79,22 @@ def topo_charge(x):
     return batch_charges(x=x)
 
 
+def wilson_loops(x: torch.Tensor, Rmax: int, Tmax: Optional[int] = None):
+    """The table of rectangular Wilson loops of a field [2, L, L] or a batch [B, 2, L, L] -> [B, Rmax, Tmax]
+    (`ops.wilson_loops`: entry [b, R - 1, T - 1], R along axis -2, T along axis -1, wrapping).  Beyond the reference, whose
+    only gauge-invariant observables are the plaquette and the charge; `utils.observables.exact_wilson_loop` is the exact value
+    of its expectation.  Not differentiable."""
+    return ops.wilson_loops(_batched(x), Rmax, Tmax)
+
+
+def polyakov_correlator(x: torch.Tensor, Rmax: Optional[int] = None):
+    """< P(i) P*(i + R) >, R = 1 .. Rmax (default L), of the Polyakov loops P(i) = exp(i sum_j x1[i][j]) -> [B, Rmax]: the column
+    T = L of the loop table, where the two sides along axis -2 cancel."""
+    xb = _batched(x)
+    L = xb.shape[-1]
+    return ops.wilson_loops(xb, L if Rmax is None else Rmax, L)[:, :, L - 1]
+
+
 class _WilsonActionFn(torch.autograd.Function):
     """S_b(x) with its gradient dS_b/dx = fthmc_wilson_force (so flows trained through
     `action(x)` by autograd, train.py:202-210, see the Wilson term)."""

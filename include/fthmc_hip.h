@@ -407,6 +407,20 @@ int fthmc_replica_swap(const double* betas, int K, int M, int parity, const doub
 int fthmc_ladder_init(const double* betas_host, int K, int M, double* betas, double* beta_b, int32_t* rung, int32_t* chain_of,
                       void* stream);
 
+/* ---- Wilson loops and Polyakov-loop correlators.  The reference has no counterpart, as for the integrators and the ladder: its
+ * only gauge-invariant observables are the plaquette and the charge.  With indices mod L, the loop with corner (i, j), extent R
+ * along i and T along j has the angle
+ *     theta = sum_{a<R} x0[i+a][j] + sum_{c<T} x1[i+R][j+c] - sum_{a<R} x0[i+a][j+T] - sum_{c<T} x1[i][j+c]
+ * and W[b][R-1][T-1] = (1 / L^2) sum_{i,j} cos theta, 1 <= R <= Rmax, 1 <= T <= Tmax: R = T = 1 is the mean of cos P with P as
+ * fthmc_plaquettes forms it; the column T = L is the Polyakov-loop correlator < P(i) P*(i + R) >, P(i) = exp(i sum_j x1[i][j]);
+ * W(L, L) = 1.  Wmean[Rmax][Tmax] (optional): the mean over the chains, added in index order.  fp64 throughout; no atomics: two
+ * calls give the same bits.  Enqueue-only, capturable, no allocation: ws holds fthmc_wilson_loops_ws_bytes(B, L, Rmax, Tmax) bytes
+ * (0 for a refused shape or a size beyond size_t).  Null x / W, B or L out of range, Rmax or Tmax outside [1, L]: FTHMC_ERR_ARG; a
+ * short (or null) workspace: FTHMC_ERR_WS. */
+size_t fthmc_wilson_loops_ws_bytes(int B, int L, int Rmax, int Tmax);
+int fthmc_wilson_loops(const double* x, int B, int L, int Rmax, int Tmax, double* W /* [B][Rmax][Tmax] */,
+                       double* Wmean /* [Rmax][Tmax] or NULL */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- training ------------------------------------------------------------ */
 /* Reverse-KL loss pieces and weight gradients for a fixed prior draw xi
  * (fthmc/train.py:191-210, fthmc/utils/samplers.py:40-56):
