@@ -1228,6 +1228,18 @@ int fthmc_wilson_loops(const double* x, int B, int L, int Rmax, int Tmax, double
     return launch_wilson_loops(x, B, L, Rmax, Tmax, W, Wmean, prefix, prefix + g.prefix, prefix + g.prefix + g.part, ft_stream(stream));
 }
 
+// Heatbath / overrelaxation sweeps (local.hip): the argument checks and the choice of the path; no workspace
+int fthmc_local_update(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hb, int n_or,
+                       int nsweep, int64_t sweep0, int classes, double* x_out, void* stream) {
+    if (!x || !x_out || bad_shape(B, L) || n_hb < 0 || n_or < 0 || nsweep < 0 || sweep0 < 0 || classes < 1 || classes > 15) return FTHMC_ERR_ARG;
+    if (n_hb > 0 && !seeds) return FTHMC_ERR_ARG;                                       // overrelaxation draws nothing
+    // the heatbath-sweep index is one 32-bit word of the Philox counter: every index the call uses must fit
+    const long long last = (long long)nsweep * (long long)n_hb;                         // < 2^62
+    if (sweep0 > (1LL << 32) || last > (1LL << 32) - sweep0) return FTHMC_ERR_ARG;
+    const bool resident = L <= LU_MAXL && get_small_path() != 0;
+    return launch_local_update(x, B, L, beta, beta_b, seeds, n_hb, n_or, nsweep, (uint32_t)sweep0, classes, x_out, resident, ft_stream(stream));
+}
+
 int fthmc_ft_trajectory(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
                         int B, int L, int act, double beta, double dt, int nstep, int mode, double* x_new,
                         double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,

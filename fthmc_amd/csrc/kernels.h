@@ -107,6 +107,14 @@ inline LoopsGeom loops_geom(int B, int L, int Rmax, int Tmax) {
 int launch_wilson_loops(const double* x, int B, int L, int Rmax, int Tmax, double* W, double* Wmean, double* prefix, double* part,
                         double* scratch, hipStream_t s);
 
+// ---- local.hip: heatbath / overrelaxation sweeps of the plain Wilson action (fthmc_local_update)
+constexpr int LU_MAXL = 64;                   // up to here a chain's links stay in one workgroup's LDS for the whole call
+constexpr int LU_MAX_ATTEMPTS = 64;           // rejection attempts of one heatbath draw, at most: a link that uses them up keeps its value
+// classes: bit (2 mu + parity) set = that class is updated; sweep0: index of the call's first heatbath sweep in the Philox counter;
+// resident: the one-launch kernel (L <= LU_MAXL), else one launch per class and sweep; beta_b: per-chain beta or null
+int launch_local_update(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hb, int n_or,
+                        int nsweep, uint32_t sweep0, int classes, double* x_out, bool resident, hipStream_t s);
+
 // ---- rng.hip
 int launch_random_momenta(const int64_t* seeds, int B, int n, double* v, double* u, hipStream_t s);
 int launch_random_uniform(const int64_t* seeds, int B, int n, double lo, double hi, double* out, hipStream_t s);

@@ -1,0 +1,253 @@
+// Local updates of 2D U(1) with the plaquette action: heatbath and overrelaxation sweeps (fthmc_local_update).
+// A link sits in two plaquettes, so its conditional weight is exp(kappa cos(x - phi)) with A = exp(i a) + exp(-i b) = |A| e^{-i phi},
+//   x0[i][j]:  a = x1[i+1][j] - x0[i][j+1] - x1[i][j],       b = x0[i][j-1] + x1[i+1][j-1] - x1[i][j-1]
+//   x1[i][j]:  a = -(x0[i][j] + x1[i+1][j] - x0[i][j+1]),    b = -(x0[i-1][j] - x0[i-1][j+1] - x1[i-1][j])
+// and A = 2 cos((a + b) / 2) exp(i (a - b) / 2) in closed form: kappa = 2 beta |cos h|, h = (a + b) / 2, phi = (b - a) / 2 (+ pi where
+// cos h < 0) -- one cosine, no atan2, no square root, and phi is as well conditioned as a and b themselves wherever cos h is away from 0.
+//   overrelaxation: x <- regularize(2 phi - x) = regularize((b - a) - x): no transcendental at all, the two plaquettes exchange angles
+//   heatbath: Best-Fisher rejection for von Mises(kappa), x <- regularize(phi +- acos f), at most LU_MAX_ATTEMPTS attempts
+// x0 links of one parity of j (x1 links of one parity of i) read only links of the other three classes: a class is updated in place.
+// Draws: Philox4x32-10 under the chain's key at counter (site i L + j, heatbath sweep, 3, mu << 8 | attempt) -- nothing of the batch,
+// the launch geometry or the path enters, and both paths run lu_update on the same loaded values: they give the same bits.
+#include "common.h"
+#include "kernels.h"
+#include "rng_common.h"
+
+namespace {
+
+using namespace fthmc_rng;
+using fthmc::LU_MAXL;
+using fthmc::LU_MAX_ATTEMPTS;
+
+// beta of a launch: one double, or (PB) the per-chain array read at the chain's index (wilson.hip BetaArg)
+template <bool PB> struct BetaArg { typedef double type; };
+template <> struct BetaArg<true> { typedef const double* type; };
+__device__ __forceinline__ double beta_at(double beta, int) { return beta; }
+__device__ __forceinline__ double beta_at(const double* beta_b, int b) { return beta_b[b]; }
+
+// below it 1 + 4 kappa^2 and every other place kappa enters round to their kappa = 0 values long since: the draw is the algorithm's
+// own limit r -> inf, f = z, c = 1 (accepted at once): uniform on the circle.  Above it nothing of the setup cancels (rho below)
+constexpr double LU_KAPPA_MIN = 8.673617379884035e-19;      // 2^-60
+
+__device__ __forceinline__ void lu_sincos(double a, double* sn, double* cs) {      // loops.hip lp_sincos: ft_sincos' range is 1e5
+    if (fabs(a) <= 1.0e5) ft_sincos(a, sn, cs);
+    else sincos(a, sn, cs);
+}
+
+// the staple angles from the six neighbours in the order the callers load them (lu_neighbours)
+// (fp contract off in the three functions that hold the update's arithmetic: which products and sums become one FMA must not be left
+// to the optimiser's view of two different kernels -- the two paths promise the same bits)
+__device__ __forceinline__ void lu_staples(int mu, const double* v, double* a, double* b) {
+#pragma clang fp contract(off)
+    if (mu == 0) { *a = (v[0] - v[1]) - v[2]; *b = (v[3] + v[4]) - v[5]; }
+    else { *a = -((v[0] + v[1]) - v[2]); *b = -((v[3] - v[4]) - v[5]); }
+}
+
+__device__ __forceinline__ double lu_overrelax(double x, double a, double b) {
+#pragma clang fp contract(off)
+    return ft_regularize((b - a) - x);
+}
+
+// One heatbath draw.  Best & Fisher (1979): tau = 1 + sqrt(1 + 4 kappa^2), rho = (tau - sqrt(2 tau)) / 2 kappa, r = (1 + rho^2) / 2 rho;
+// rho is formed as 2 kappa / (tau + sqrt(2 tau)) -- the same number ((tau - sqrt(2 tau))(tau + sqrt(2 tau)) = tau (tau - 2) = 4 kappa^2)
+// without the cancellation that costs the textbook form its digits below kappa ~ 1e-6 and makes it 0 / 0 at kappa = 0.
+// The loop is bounded: a link that is never accepted (probability < 0.34^64) keeps xold.
+__device__ __forceinline__ double lu_heatbath(double xold, double a, double b, double beta, uint32_t k0, uint32_t k1, uint32_t site,
+                                              uint32_t mu, uint32_t sweep) {
+#pragma clang fp contract(off)
+    double sn, ch;
+    lu_sincos(0.5 * (a + b), &sn, &ch);
+    const double kappa = 2.0 * beta * fabs(ch);
+    double phi = 0.5 * (b - a);
+    if (ch < 0.0) phi += FT_PI;
+    const bool flat = !(kappa >= LU_KAPPA_MIN);
+    double r = 1.0;
+    if (!flat) {
+        const double tau = 1.0 + sqrt(1.0 + 4.0 * kappa * kappa);
+        const double rho = 2.0 * kappa / (tau + sqrt(2.0 * tau));
+        r = (1.0 + rho * rho) / (2.0 * rho);
+    }
+    double out = xold;
+    for (int t = 0; t < LU_MAX_ATTEMPTS; ++t) {
+        const u4 w = philox4x32_10(u4{site, sweep, 3u, (mu << 8) | (uint32_t)t}, k0, k1);
+        const double u1 = u53(w.x, w.y), u2 = u53(w.z, w.w);
+        double sz, z;
+        ft_sincos(FT_PI * u1, &sz, &z);
+        double f = z;
+        bool take = true;
+        if (!flat) {
+            f = (1.0 + r * z) / (r + z);
+            f = fmin(fmax(f, -1.0), 1.0);                         // r + z = 0 (kappa beyond 1e7, z = -1): 0 / 0 becomes -1
+            const double c = kappa * (r - f);
+            take = c * (2.0 - c) - u2 > 0.0 || log(c / u2) + 1.0 - c >= 0.0;
+        }
+        if (take) {
+            const double th = acos(f);
+            out = ft_regularize((w.y & 1u) ? phi - th : phi + th);
+            break;
+        }
+    }
+    return out;
+}
+
+template <bool HEAT>
+__device__ __forceinline__ double lu_update(double x, int mu, const double* v, double beta, uint32_t k0, uint32_t k1, uint32_t site,
+                                            uint32_t sweep) {
+    double a, b;
+    lu_staples(mu, v, &a, &b);
+    if (HEAT) return lu_heatbath(x, a, b, beta, k0, k1, site, (uint32_t)mu, sweep);
+    return lu_overrelax(x, a, b);
+}
+
+// the six neighbours of link (mu, i, j) as (plane, row, column), in lu_staples' order
+struct LuNb { int pl[6], r[6], c[6]; };
+__device__ __forceinline__ LuNb lu_neighbours(int mu, int i, int j, int L) {
+    const int ip = i + 1 == L ? 0 : i + 1, im = i == 0 ? L - 1 : i - 1, jp = j + 1 == L ? 0 : j + 1, jm = j == 0 ? L - 1 : j - 1;
+    if (mu == 0) return LuNb{{1, 0, 1, 0, 1, 1}, {ip, i, i, i, ip, i}, {j, jp, j, jm, jm, jm}};
+    return LuNb{{0, 1, 0, 0, 0, 1}, {i, ip, i, im, im, im}, {j, j, jp, j, jp, j}};
+}
+
+// link e of class (mu, p): the x0 links of column parity p row by row, the x1 links of row parity p row by row
+__device__ __forceinline__ void lu_link(int mu, int p, int e, int L, int* i, int* j) {
+    if (mu == 0) { const int hl = L >> 1, r = e / hl; *i = r; *j = 2 * (e - r * hl) + p; }
+    else { const int r = e / L; *i = 2 * r + p; *j = e - r * L; }
+}
+
+// ---------------------------------------------------------------- any L: one launch per class, in place, the chain on grid x
+template <bool HEAT, bool PB>
+__global__ __launch_bounds__(256) void k_local_class(double* __restrict__ x, int L, typename BetaArg<PB>::type beta_,
+                                                     const int64_t* __restrict__ seeds, int mu, int p, uint32_t sweep) {
+    const int b = blockIdx.x, n = L * L;
+    const double beta = beta_at(beta_, b);
+    uint32_t k0 = 0u, k1 = 0u;
+    if (HEAT) { const uint64_t sd = (uint64_t)seeds[b]; k0 = (uint32_t)sd; k1 = (uint32_t)(sd >> 32); }
+    double* xb = x + (size_t)b * 2 * n;
+    for (int e = blockIdx.y * 256 + threadIdx.x; e < n / 2; e += gridDim.y * 256) {
+        int i, j;
+        lu_link(mu, p, e, L, &i, &j);
+        const LuNb nb = lu_neighbours(mu, i, j, L);
+        double v[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[q] = xb[(size_t)nb.pl[q] * n + (size_t)nb.r[q] * L + nb.c[q]];
+        double* own = xb + (size_t)mu * n + (size_t)i * L + j;
+        *own = lu_update<HEAT>(*own, mu, v, beta, k0, k1, (uint32_t)(i * L + j), sweep);
+    }
+}
+
+// ---------------------------------------------------------------- L <= LU_MAXL: the whole call in one launch, one workgroup per chain
+// Both planes live in LDS, each split by the PARITY OF THE COLUMN: slot(mu, i, j) = mu 2 H + (j & 1) H + i L / 2 + (j >> 1),
+// H = L^2 / 2 + 16.  Then
+//   * an x0 class owns one half of plane 0, consecutive threads on consecutive slots (reads and writes of the own link), its x0
+//     neighbours (columns j +- 1) are consecutive slots of the other half and its x1 neighbours (columns j, j - 1) consecutive slots
+//     of the two halves of plane 1: every access of a wave is a run of consecutive 8-byte slots, conflict-free, where the row-major
+//     plane would give stride-2 (two-way) reads and writes;
+//   * an x1 class owns whole rows: consecutive threads alternate between the halves, 16 slots each per 32 lanes, and the 16 doubles
+//     of padding in H put the two runs on the two halves of the 64 banks (L >= 32; a smaller lattice has several rows per 32 lanes and
+//     pays a two-way conflict on some of them: its call is launch latency, not LDS).
+// A thread keeps the coordinates of its links (formed once, two divisions per link) and owns the same links of a class throughout.
+// The six neighbour slots are re-formed from them at every update (wrap selects and adds, ~30 integer instructions against ~700 of a
+// heatbath draw): kept, they would be 7 indices x 4 classes x LU_PER links = 56 registers on top of the 121 the kernel holds, beyond
+// the 128 a lane of a 1024-thread workgroup may have.
+constexpr int LU_NT = 1024, LU_PER = LU_MAXL * LU_MAXL / 2 / LU_NT, LU_PAD = 16;
+static_assert(LU_PER * LU_NT * 2 == LU_MAXL * LU_MAXL, "k_local_resident: LU_PER links per thread and class cover L = LU_MAXL");
+
+template <bool PB>
+__global__ __launch_bounds__(LU_NT) void k_local_resident(const double* x, int L, typename BetaArg<PB>::type beta_,
+                                                          const int64_t* __restrict__ seeds, int n_hb, int n_or, int nsweep,
+                                                          uint32_t sweep0, int classes, double* x_out) {     // x_out may be x
+    __shared__ double sx[2 * (LU_MAXL * LU_MAXL + 2 * LU_PAD)];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, n = L * L, hl = L >> 1, H = n / 2 + LU_PAD;
+    const double beta = beta_at(beta_, b);
+    uint32_t k0 = 0u, k1 = 0u;
+    if (n_hb > 0) { const uint64_t sd = (uint64_t)seeds[b]; k0 = (uint32_t)sd; k1 = (uint32_t)(sd >> 32); }
+    auto slot = [&](int mu, int i, int j) { return mu * 2 * H + (j & 1) * H + i * hl + (j >> 1); };
+    const double* xb = x + (size_t)b * 2 * n;
+    for (int s = tid; s < 2 * n; s += nt) {
+        const int mu = s >= n ? 1 : 0, t = s - mu * n, i = t / L, j = t - i * L;
+        sx[slot(mu, i, j)] = xb[s];
+    }
+    int r0[LU_PER], q0[LU_PER], r1[LU_PER], c1[LU_PER];             // link e = tid + k nt: (row, half column) as x0, (half row, column) as x1
+    bool have[LU_PER];
+#pragma unroll
+    for (int k = 0; k < LU_PER; ++k) {
+        const int e = tid + k * nt;
+        have[k] = e < n / 2;
+        const int ee = have[k] ? e : 0;
+        r0[k] = ee / hl; q0[k] = ee - r0[k] * hl;
+        r1[k] = ee / L; c1[k] = ee - r1[k] * L;
+    }
+    __syncthreads();
+    uint32_t sweep = sweep0;
+    for (int sw = 0; sw < nsweep; ++sw)
+        for (int h = 0; h < n_hb + n_or; ++h) {
+            const bool heat = h < n_hb;
+            for (int cl = 0; cl < 4; ++cl) {
+                if (!((classes >> cl) & 1)) continue;               // uniform over the workgroup, as is every loop bound here
+                const int mu = cl >> 1, p = cl & 1;
+#pragma unroll
+                for (int k = 0; k < LU_PER; ++k)
+                    if (have[k]) {
+                        const int i = mu == 0 ? r0[k] : 2 * r1[k] + p, j = mu == 0 ? 2 * q0[k] + p : c1[k];
+                        const LuNb nb = lu_neighbours(mu, i, j, L);
+                        double v[6];
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) v[q] = sx[slot(nb.pl[q], nb.r[q], nb.c[q])];
+                        const int own = slot(mu, i, j);
+                        const uint32_t site = (uint32_t)(i * L + j);
+                        sx[own] = heat ? lu_update<true>(sx[own], mu, v, beta, k0, k1, site, sweep)
+                                       : lu_update<false>(sx[own], mu, v, beta, k0, k1, site, sweep);
+                    }
+                __syncthreads();
+            }
+            if (heat) ++sweep;
+        }
+    double* xo = x_out + (size_t)b * 2 * n;
+    for (int s = tid; s < 2 * n; s += nt) {
+        const int mu = s >= n ? 1 : 0, t = s - mu * n, i = t / L, j = t - i * L;
+        xo[s] = sx[slot(mu, i, j)];
+    }
+}
+
+template <bool HEAT>
+int lu_launch_class(double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int cl, uint32_t sweep, hipStream_t s) {
+    const long long blocks = ((long long)L * L / 2 + 255) / 256;
+    const dim3 grid((unsigned)B, (unsigned)(blocks > 65535 ? 65535 : blocks));
+    if (beta_b) hipLaunchKernelGGL((k_local_class<HEAT, true>), grid, dim3(256), 0, s, x, L, beta_b, seeds, cl >> 1, cl & 1, sweep);
+    else hipLaunchKernelGGL((k_local_class<HEAT, false>), grid, dim3(256), 0, s, x, L, beta, seeds, cl >> 1, cl & 1, sweep);
+    FT_LAUNCH_CHECK();
+    return FTHMC_OK;
+}
+
+}  // namespace
+
+namespace fthmc {
+
+int launch_local_update(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hb, int n_or,
+                        int nsweep, uint32_t sweep0, int classes, double* x_out, bool resident, hipStream_t s) {
+    if (resident) {
+        if (L > LU_MAXL) return FTHMC_ERR_UNSUPPORTED;
+        int nt = (L * L / 2 + FT_WAVE - 1) / FT_WAVE * FT_WAVE;     // a thread per link of a class, whole waves, at most LU_NT
+        if (nt > LU_NT) nt = LU_NT;
+        if (beta_b) hipLaunchKernelGGL(k_local_resident<true>, dim3(B), dim3(nt), 0, s, x, L, beta_b, seeds, n_hb, n_or, nsweep, sweep0, classes, x_out);
+        else hipLaunchKernelGGL(k_local_resident<false>, dim3(B), dim3(nt), 0, s, x, L, beta, seeds, n_hb, n_or, nsweep, sweep0, classes, x_out);
+        FT_LAUNCH_CHECK();
+        return FTHMC_OK;
+    }
+    if (x_out != x && hipMemcpyAsync(x_out, x, (size_t)B * 2 * L * L * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
+    uint32_t sweep = sweep0;
+    for (int sw = 0; sw < nsweep; ++sw)
+        for (int h = 0; h < n_hb + n_or; ++h) {
+            const bool heat = h < n_hb;
+            for (int cl = 0; cl < 4; ++cl) {
+                if (!((classes >> cl) & 1)) continue;
+                const int rc = heat ? lu_launch_class<true>(x_out, B, L, beta, beta_b, seeds, cl, sweep, s)
+                                    : lu_launch_class<false>(x_out, B, L, beta, beta_b, seeds, cl, sweep, s);
+                if (rc != FTHMC_OK) return rc;
+            }
+            if (heat) ++sweep;
+        }
+    return FTHMC_OK;
+}
+
+}  // namespace fthmc

@@ -52,3 +52,10 @@ san_loops: $(SANOUT)
 	mkdir -p $(dir $(SANLOOPS))
 	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
 	  ../../tests/hip/loops_walk.cpp -o $(SANLOOPS) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
+
+# The local-update entry point (fthmc_local_update): tests/hip/local_walk.cpp in the same way, run by tests/test_local_update.py
+SANLOCAL ?= $(SANDIR)/local_walk
+san_local: $(SANOUT)
+	mkdir -p $(dir $(SANLOCAL))
+	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
+	  ../../tests/hip/local_walk.cpp -o $(SANLOCAL) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))

@@ -115,6 +115,26 @@ Tensor wilson_loops(const Tensor& x_, int64_t Rmax, int64_t Tmax) {
     ok(fthmc_wilson_loops(cp(x), B, L, (int)Rmax, (int)Tmax, mp(W), nullptr, mp(ws), bytes, cur_stream(x)), "fthmc_wilson_loops");
     return W;
 }
+// heatbath / overrelaxation sweeps -> the updated field (no autograd formula: a sampler step)
+Tensor local_update(const Tensor& x_, double beta, const c10::optional<Tensor>& beta_b_, const c10::optional<Tensor>& seeds_, int64_t n_hb,
+                    int64_t n_or, int64_t nsweep, int64_t sweep0, int64_t classes) {
+    FT_DEVICE_GUARD(x_);
+    Tensor x = field(x_, "x");
+    const int B = (int)x.size(0), L = (int)x.size(2);
+    TORCH_CHECK(n_hb >= 0 && n_or >= 0 && nsweep >= 0 && n_hb <= INT32_MAX && n_or <= INT32_MAX && nsweep <= INT32_MAX && sweep0 >= 0 &&
+                classes >= 1 && classes <= 15, "local_update: counts >= 0, sweep0 >= 0 and classes in 1 .. 15 expected");
+    Tensor beta_b, seeds;
+    if (beta_b_.has_value()) beta_b = perchain(*beta_b_, B, "beta_b");
+    if (seeds_.has_value()) {
+        seeds = seeds_->contiguous();
+        TORCH_CHECK(seeds.is_cuda() && seeds.scalar_type() == at::kLong && seeds.numel() == B, "seeds: expected ", B, " int64 seeds on the HIP device");
+    }
+    TORCH_CHECK(n_hb == 0 || seeds.defined(), "local_update: heatbath sweeps need seeds");
+    Tensor out = at::empty_like(x);
+    ok(fthmc_local_update(cp(x), B, L, beta, beta_b.defined() ? cp(beta_b) : nullptr, seeds.defined() ? seeds.const_data_ptr<int64_t>() : nullptr,
+                          (int)n_hb, (int)n_or, (int)nsweep, sweep0, (int)classes, mp(out), cur_stream(x)), "fthmc_local_update");
+    return out;
+}
 std::tuple<Tensor, Tensor, Tensor> hmc_trajectory(const Tensor& x_, const Tensor& v_, const Tensor& u_, double beta, double dt, int64_t nstep) {
     FT_DEVICE_GUARD(x_);
     Tensor x = field(x_, "x"), v = field(v_, "v");
@@ -356,6 +376,7 @@ TORCH_LIBRARY(fthmc_hip, m) {
     m.def("train_force_grad(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor)");
     m.def("ft_trajectory_pb(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, Tensor beta_b, float dt, int nstep, int integrator, int act, Tensor? state_in=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("hmc_trajectory_pb(Tensor x, Tensor v, Tensor u, Tensor beta_b, float dt, int nstep, int integrator=0) -> (Tensor, Tensor, Tensor)");
+    m.def("local_update(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hb=1, int n_or=0, int nsweep=1, int sweep0=0, int classes=15) -> Tensor");
     m.def("replica_swap(Tensor betas, Tensor C, Tensor u, Tensor(a!) beta_b, Tensor(b!) rung, Tensor(c!) chain_of, int parity) -> (Tensor, Tensor)");
 }
 
@@ -379,4 +400,5 @@ TORCH_LIBRARY_IMPL(fthmc_hip, CUDA, m) {
     m.impl("ft_trajectory_pb", &ft_trajectory_pb);
     m.impl("hmc_trajectory_pb", &hmc_trajectory_pb);
     m.impl("replica_swap", &replica_swap);
+    m.impl("local_update", &local_update);
 }

@@ -12,13 +12,16 @@ from .utils import qed_helpers as qed
 
 
 def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, figsize=None, use_title: bool = True,
-            save_data: bool = False, nplot: int = 10, integrator: str = 'leapfrog', loops=None, loops_every: int = 1):
+            save_data: bool = False, nplot: int = 10, integrator: str = 'leapfrog', loops=None, loops_every: int = 1,
+            overrelax: int = 0):
     """hmc.py:57-175: `param.nrun` experiments of `param.ntraj` trajectories each.
     Returns (fields_arr, histories) with the reference's metric keys.
     integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h).
     loops = (Rmax, Tmax) (default None: nothing changes): after every `loops_every`-th trajectory of a run the Wilson loops of the
     field are measured (ops.wilson_loops) and the history gains 'wloops', one [Rmax, Tmax] batch-mean table per measured
-    trajectory (utils.observables.exact_wilson_loop has the exact expectation)."""
+    trajectory (utils.observables.exact_wilson_loop has the exact expectation).
+    overrelax = k (default 0: nothing changes): k overrelaxation sweeps (qed_helpers.overrelax) behind every trajectory, before it is
+    measured; they leave the action where the trajectory put it and move the non-topological modes."""
     from . import ops
     ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
     if loops is not None:
@@ -26,6 +29,9 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
         if not (1 <= loops[0] <= param.L and 1 <= loops[1] <= param.L):
             raise ValueError(f'loops: (Rmax, Tmax) with 1 <= Rmax, Tmax <= L = {param.L} expected, got {loops!r}')
     loops_every = max(1, int(loops_every))
+    overrelax = int(overrelax)
+    if overrelax < 0:
+        raise ValueError(f'overrelax: a number of sweeps >= 0 expected, got {overrelax}')
     action = qed.BatchAction(param.beta)
     histories, fields_arr, run_times = {}, [], []
     for n in range(param.nrun):
@@ -36,6 +42,8 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
         for i in range(param.ntraj):
             t1 = time.time()
             dH, exp_mdH, acc, x = qed.hmc(param, x, verbose=False, integrator=integrator)
+            if overrelax:
+                x = qed.overrelax(param, x, overrelax)
             qold = history['q'][-1] if 'q' in history else q
             qnew = qed.batch_charges(x)
             dq = torch.sqrt((qnew - qold) ** 2)

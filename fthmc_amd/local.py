@@ -1,0 +1,82 @@
+"""Local-update sampler of 2D U(1): heatbath sweeps, optionally mixed with overrelaxation (beyond the reference, which updates by
+molecular dynamics only: fthmc/hmc.py, fthmc/ft_hmc.py know leapfrog).
+
+A heatbath sweep draws every link from its conditional von Mises distribution exactly -- no step size, acceptance 1; an
+overrelaxation sweep reflects every link about its conditional mode and leaves the action unchanged (csrc/local.hip).
+The sampler shares no kernel with the MD path (no force, no integrator, no Metropolis step), so it is an independent check of the
+same exact numbers (utils.observables.exact_wilson_loop).  It does NOT cure topological freezing: a local update changes the
+charge no faster than HMC does; that stays with the flow and the beta ladder (tempering.py)."""
+from __future__ import annotations
+
+import os
+import time
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .config import DTYPE, Param
+from .graph_loop import GraphLoop
+
+
+def run_local(param: Param, x: Optional[torch.Tensor] = None, n_overrelax: int = 0, sweeps_per_traj: int = 1, loops=None,
+              loops_every: int = 1, use_graph: Optional[bool] = None):
+    """`param.nrun` runs of `param.ntraj` updates each; one update ("trajectory") is `sweeps_per_traj` compound sweeps of one
+    heatbath sweep followed by `n_overrelax` overrelaxation sweeps, at param.beta (param.tau / nstep are not used: there is no MD).
+    x: the start of every run, [2, L, L] or a batch [B, 2, L, L] (default param.initializer()).
+    -> (fields_arr, histories): fields_arr[n] is the last field of run n; histories[n] has run_hmc's keys except 'dH' -- 'traj',
+    'dt', 'acc' (identically 1), 'plaq', 'q', 'dq', one entry per update, per chain -- and 'wloops' where loops = (Rmax, Tmax) is
+    given (one batch-mean table per `loops_every`-th update, as run_hmc).
+    The seeds of update t are ops.chain_seeds(param.seed, chain, t), formed on the device; the sequence of one update is captured
+    once (graph_loop) and replayed (`use_graph`, default on; FTHMC_RUN_GRAPH=0 turns it off): the same bits either way."""
+    from . import ops
+    from .config import device
+    n_overrelax, sweeps_per_traj, loops_every = int(n_overrelax), int(sweeps_per_traj), max(1, int(loops_every))
+    if n_overrelax < 0 or sweeps_per_traj < 1:
+        raise ValueError(f'run_local: n_overrelax >= 0 and sweeps_per_traj >= 1 expected, got {n_overrelax}, {sweeps_per_traj}')
+    if loops is not None:
+        loops = (int(loops), int(loops)) if isinstance(loops, int) else (int(loops[0]), int(loops[1]))
+        if not (1 <= loops[0] <= param.L and 1 <= loops[1] <= param.L):
+            raise ValueError(f'loops: (Rmax, Tmax) with 1 <= Rmax, Tmax <= L = {param.L} expected, got {loops!r}')
+    if use_graph is None:
+        use_graph = os.environ.get('FTHMC_RUN_GRAPH', '1') not in ('', '0')
+    x0 = param.initializer() if x is None else x
+    x0 = (x0 if x0.dim() == 4 else x0[None]).to(device=device(), dtype=DTYPE).contiguous()
+    dev, B = x0.device, x0.shape[0]
+    nl = 0 if loops is None else loops[0] * loops[1]
+    histories, fields_arr = {}, []
+    for n in range(param.nrun):
+        t0 = time.time()
+        xs = x0.clone()
+        seeds = torch.empty(B, dtype=torch.int64, device=dev)
+        counter = torch.full((1,), n * param.ntraj, dtype=torch.int64, device=dev)      # update t of the whole experiment
+        row = torch.zeros(2 * B + nl, dtype=DTYPE, device=dev)
+        obs = {'plaq': row[0:B], 'Q': row[B:2 * B]}
+        q0 = ops.wilson_action_charge(xs, param.beta)[1].cpu().numpy()
+
+        def enqueue():
+            ops.chain_seeds(param.seed, 0, B, 0, counter=counter, advance=True, out=seeds)
+            ops.local_update(xs, param.beta, seeds, n_hb=1, n_or=n_overrelax, nsweep=sweeps_per_traj, out=xs)
+            ops.wilson_action_charge(xs, param.beta, out=obs)
+
+        def measure():
+            ops.wilson_loops(xs, loops[0], loops[1], mean_out=row[2 * B:])
+        loop = GraphLoop(enqueue, row, use_graph=use_graph, extra=measure if loops is not None else None, extra_every=loops_every)
+        for _ in range(param.ntraj):
+            loop.step()
+        rows = loop.rows()
+        loop.join()
+        dt = (time.time() - t0) / max(1, param.ntraj)
+        history = {k: [] for k in ('traj', 'dt', 'acc', 'plaq', 'q', 'dq')}
+        qold = q0
+        for i in range(param.ntraj):
+            plaq, q = rows[i, 0:B], rows[i, B:2 * B]
+            for k, v in (('traj', n * param.ntraj + i + 1), ('dt', dt), ('acc', torch.ones(B, dtype=DTYPE)), ('plaq', torch.from_numpy(plaq.copy())),
+                         ('q', torch.from_numpy(q.copy())), ('dq', torch.from_numpy(np.sqrt((q - qold) ** 2)))):
+                history[k].append(v)
+            if loops is not None and i % loops_every == 0:
+                history.setdefault('wloops', []).append(torch.from_numpy(rows[i, 2 * B:].reshape(loops).copy()))
+            qold = q
+        histories[n] = history
+        fields_arr.append(xs.clone())
+    return fields_arr, histories

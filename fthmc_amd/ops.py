@@ -393,6 +393,35 @@ def wilson_loops(x, Rmax: int, Tmax: Optional[int] = None, out=None, mean_out=No
     return W.view(B, Rmax, Tmax)
 
 
+def local_update(x, beta, seeds=None, n_hb: int = 1, n_or: int = 0, nsweep: int = 1, sweep0: int = 0, classes: int = 0xF, out=None):
+    """Heatbath and overrelaxation sweeps of the plain Wilson action (C ABI fthmc_local_update) -> the updated field: `nsweep`
+    compound sweeps, each `n_hb` heatbath sweeps (an exact draw of every link from its conditional von Mises distribution) followed by
+    `n_or` overrelaxation sweeps (the reflection of every link about its conditional mode: the action does not change).
+    beta: a number, or a device tensor of B doubles -- per-chain beta.  seeds: int64 [B] on the device (ops.chain_seeds), needed for
+    heatbath only; `sweep0` is the index of the call's first heatbath sweep in the random stream: a caller that keeps one seed per
+    chain moves it on by nsweep * n_hb per call, one that draws fresh seeds per call leaves it 0.  classes: mask of the link classes
+    (bit 2 mu + parity) a sweep touches.  out: written in place when given (may be x).  Not differentiable."""
+    x = _field(x); B, _, L, _ = x.shape
+    n_hb, n_or, nsweep, sweep0, classes = int(n_hb), int(n_or), int(nsweep), int(sweep0), int(classes)
+    if min(n_hb, n_or, nsweep, sweep0) < 0 or not 1 <= classes <= 15:
+        raise ValueError(f'local_update: counts and sweep0 >= 0 and classes in 1 .. 15 expected, got n_hb={n_hb}, n_or={n_or}, '
+                         f'nsweep={nsweep}, sweep0={sweep0}, classes={classes}')
+    if n_hb > 0 and seeds is None:
+        raise ValueError('local_update: heatbath sweeps need per-chain seeds')
+    if seeds is not None:
+        if not seeds.is_cuda or seeds.dtype != torch.int64 or seeds.numel() != B:
+            raise FthmcError(f'seeds: expected an int64 tensor of {B} entries on the HIP device')
+        seeds = seeds.contiguous()
+    bb = _beta_b(beta, B)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_cuda or not out.is_contiguous():
+        raise FthmcError('out: expected a contiguous device tensor of the shape of x')
+    check(_lib.load().fthmc_local_update(_p(x), B, L, 0.0 if bb is not None else float(beta), _p(bb), _p(seeds), n_hb, n_or, nsweep,
+                                         sweep0, classes, _p(out), _stream(x)), 'fthmc_local_update')
+    return out
+
+
 def wilson_force(x, beta: float):
     x = _field(x); B, _, L, _ = x.shape
     F = torch.empty_like(x)

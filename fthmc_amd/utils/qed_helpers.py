@@ -313,6 +313,22 @@ def hmc(param, x, verbose=True, v: Optional[torch.Tensor] = None, u: Optional[to
     return dH, exp_mdH, acc, newx.reshape(x.shape)
 
 
+# ---------------------------------------------------------------- local updates (beyond the reference, which updates by MD only)
+def heatbath(param, x: torch.Tensor, seeds: Optional[torch.Tensor] = None):
+    """One heatbath sweep at param.beta: every link drawn from its conditional von Mises distribution (ops.local_update; no step
+    size, acceptance 1).  seeds: int64 per chain (ops.chain_seeds); None: drawn from torch's generator."""
+    xb = _batched(x)
+    if seeds is None:
+        seeds = torch.randint(0, 2 ** 63 - 1, (xb.shape[0],), dtype=torch.int64, device=xb.device)
+    return ops.local_update(xb, param.beta, seeds, n_hb=1, n_or=0).reshape(x.shape)
+
+
+def overrelax(param, x: torch.Tensor, n: int = 1):
+    """`n` overrelaxation sweeps: every link reflected about its conditional mode; the action is unchanged (to rounding), nothing is
+    drawn.  Not ergodic on its own: mixed with heatbath or HMC (run_local, run_hmc(overrelax=n))."""
+    return ops.local_update(_batched(x), param.beta, None, n_hb=0, n_or=int(n)).reshape(x.shape)
+
+
 def ft_leapfrog(param, flow, x: torch.Tensor, p: torch.Tensor, integrator: str = 'leapfrog'):
     """ipynb/ft_hmc.py:394-418: the MD in the latent field with the flowed force -> (x', p').
     integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h)."""

@@ -421,6 +421,30 @@ size_t fthmc_wilson_loops_ws_bytes(int B, int L, int Rmax, int Tmax);
 int fthmc_wilson_loops(const double* x, int B, int L, int Rmax, int Tmax, double* W /* [B][Rmax][Tmax] */,
                        double* Wmean /* [Rmax][Tmax] or NULL */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Local updates: heatbath and overrelaxation sweeps of the plain Wilson action.  The reference has no counterpart: it updates
+ * by molecular dynamics only.  With P(i,j) = x0[i][j] + x1[i+1][j] - x0[i][j+1] - x1[i][j] a link sits in two plaquettes and its
+ * conditional weight is exp(kappa cos(x - phi)), kappa = beta |A|, phi = -arg A, A = exp(i a) + exp(-i b) with
+ *     x0[i][j]:  a = x1[i+1][j] - x0[i][j+1] - x1[i][j],          b = x0[i][j-1] + x1[i+1][j-1] - x1[i][j-1]
+ *     x1[i][j]:  a = -(x0[i][j] + x1[i+1][j] - x0[i][j+1]),       b = -(x0[i-1][j] - x0[i-1][j+1] - x1[i-1][j])
+ * i.e. kappa = 2 beta |cos((a + b) / 2)|, phi = (b - a) / 2 (+ pi where that cosine is negative).  The four classes (mu, parity) --
+ * x0 links by the parity of j, x1 links by the parity of i -- are updated in place in the order (0,0), (0,1), (1,0), (1,1);
+ * `classes` is the mask of those a sweep touches (bit 2 mu + parity; 15 = a full sweep), every other link is copied.
+ *   overrelaxation: x <- regularize(2 phi - x) = regularize((b - a) - x): the link's two plaquettes exchange their angles, the
+ *     action is unchanged, nothing is drawn;
+ *   heatbath: x <- regularize(phi +- acos f) by Best-Fisher rejection for the von Mises distribution: at most 64 attempts (a link
+ *     that uses them up, probability < 1e-30, keeps its value); kappa < 2^-60 takes the algorithm's limit, the uniform draw f = z.
+ * The call runs nsweep compound sweeps, each n_hb heatbath sweeps followed by n_or overrelaxation sweeps.  Attempt t of the link
+ * (mu, i, j) in heatbath sweep k = sweep0 + (compound sweep) n_hb + (heatbath sweep inside it) reads the Philox4x32-10 block at
+ * counter (i L + j, k, 3, mu << 8 | t) under the key of seeds[b]: u1 from words (0, 1), u2 from words (2, 3), the sign of the
+ * angle from bit 0 of word 1.  A link's draws depend on nothing else: nsweep = 2 equals two calls with sweep0, sweep0 + n_hb; a
+ * full sweep equals its four classes one call each; chain b of a batch equals the chain alone; fthmc_set_small_path(0 / 1)
+ * (one launch per class / the whole call in one launch with the chain's links in LDS, L <= 64) gives the same bits.
+ * beta_b (nullable): per-chain beta [B], read in place of `beta`.  x_out may be x.  Enqueue-only, capturable, no workspace.
+ * A null x / x_out (seeds: with n_hb > 0), B or L out of range, a negative count or sweep0, classes outside 1 .. 15, or
+ * sweep0 + nsweep n_hb > 2^32: FTHMC_ERR_ARG. */
+int fthmc_local_update(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hb, int n_or,
+                       int nsweep, int64_t sweep0, int classes, double* x_out, void* stream);
+
 /* ---- training ------------------------------------------------------------ */
 /* Reverse-KL loss pieces and weight gradients for a fixed prior draw xi
  * (fthmc/train.py:191-210, fthmc/utils/samplers.py:40-56):
