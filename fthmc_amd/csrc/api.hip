@@ -186,6 +186,14 @@ inline SmallArgs small_args(const double* x, const WS& w, int nl, int B, int act
 }
 
 #define FT_TRY(expr) do { int rc_ = (expr); if (rc_ != FTHMC_OK) return rc_; } while (0)
+// the call's context (shape from `arch`, the debug switches, the stream), then its workspace view
+#define FT_CTX(arch_)                                                               \
+    (void)hipGetLastError();   /* drop stale (non-sticky) errors left by the host framework */ \
+    Ctx C; { const int rc_ = make_ctx((arch_), stream, &C); if (rc_ != FTHMC_OK) return rc_; } \
+    hipStream_t s = C.s; (void)s
+#define FT_WS(nl, train)                                                            \
+    if (!ws || ws_bytes < ws_doubles(C.A, B, L, (nl), (train)) * sizeof(double)) return FTHMC_ERR_WS; \
+    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, (nl), (train))
 
 // Argument checks of the entry points, in the precedence every one of them keeps: FTHMC_ERR_ARG, then FTHMC_ERR_UNSUPPORTED
 // (then the workspace: FT_WS).  ptrs_ok: the call's own pointers and counts.
@@ -351,23 +359,11 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
     return FTHMC_OK;
 }
 
-// leapfrog in the latent field; result in w.xa / w.va
-// xreg (optional): regularize(result x), written by the last kick (the end point of a trajectory, ipynb/ft_hmc.py:426)
-int ft_leapfrog_ws(const Ctx& C, const double* x, const double* v, const WS& w, int nl, int B, int L, int act,
-                   double beta, double dt, int nstep, hipStream_t s, double* xreg = nullptr) {
-    FT_TRY(launch_axpy_copy(x, v, 0.5 * dt, w.xa, w.va, w.n2, s));       // first half drift + the working copy of the momenta
-    for (int k = 0; k < nstep; ++k) {
-        FT_TRY(force_gp(C, w.xa, w, nl, B, L, act, beta, -1.0, nullptr, s));
-        FT_TRY(launch_kick_from_gp(w.gp, w.va, w.xa, nullptr, B, L, dt, k == nstep - 1 ? 0.5 * dt : dt, s,
-                                   k == nstep - 1 ? xreg : nullptr));
-    }
-    return FTHMC_OK;
-}
-
-// ft_leapfrog_ws generalised over a schedule (integrator.h): x += b0 v, then per stage one force evaluation and KICK(a, b) --
-// the kick kernel as it is -- or SHIFT(c): the shifted field goes to `xshift` and the next stage's force is evaluated there
-// (w.xa and w.va are untouched by it).  nl = 0 is the plain Wilson MD (launch_wilson_gp + kick).  Result in w.xa / w.va; xreg as
-// in ft_leapfrog_ws -- it may be `xshift` itself: nothing reads the shifted field once the kick behind it has its gP.
+// The MD of a schedule (integrator.h) in the latent field: x += b0 v, then per stage one force evaluation and KICK(a, b), or
+// SHIFT(c): the shifted field goes to `xshift` and the next stage's force is evaluated there (w.xa and w.va are untouched by
+// it; the leapfrog has no such stage and reads no `xshift`).  nl = 0 is the plain Wilson MD (launch_wilson_gp + kick).  Result
+// in w.xa / w.va.  xreg (optional): regularize(result x), written by the last kick (the end point of a trajectory,
+// ipynb/ft_hmc.py:426) -- it may be `xshift` itself: nothing reads the shifted field once the kick behind it has its gP.
 int ft_md_ws(const Ctx& C, const double* x, const double* v, const WS& w, int nl, int B, int L, int act, double beta,
              const Sched& sc, hipStream_t s, double* xshift, double* xreg = nullptr, const double* beta_b = nullptr) {
     FT_TRY(launch_axpy_copy(x, v, sc.b0, w.xa, w.va, w.n2, s));
@@ -447,6 +443,186 @@ template <class Ref> int mean_stamps(const long long* dbg, size_t nrec, int nslo
     return FTHMC_OK;
 }
 
+// the result pair of an MD entry point
+inline int copy_pair(double* x_out, const double* xo, double* v_out, const double* vo, size_t n2, hipStream_t s) {
+    if (hipMemcpyAsync(x_out, xo, n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(v_out, vo, n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
+    return FTHMC_OK;
+}
+
+// The bare MD behind fthmc_leapfrog / fthmc_md (`plain`: no flow, no weights, never the one-launch path) and fthmc_ft_leapfrog_v /
+// fthmc_ft_md_v.  fthmc_leapfrog keeps the fused launch_leap_step steps (leapfrog_ws); everything else is ft_md_ws.
+int md_call(bool plain, const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int nl, int B, int L, int act,
+            double beta, double dt, int nstep, int integrator, double* x_out, double* v_out, void* ws, size_t ws_bytes,
+            void* stream, uint64_t wver) {
+    FT_TRY(check_flow_call(x && v && x_out && v_out && nstep >= 1, w, nl, B, L, act));
+    const bool leap = integrator == FTHMC_INT_LEAPFROG;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(arch);
+    FT_WS(nl, false);
+    if (plain && leap) {
+        double *xo, *po;
+        FT_TRY(leapfrog_ws(x, v, W, B, L, beta, dt, nstep, &xo, &po, s));
+        return copy_pair(x_out, xo, v_out, po, W.n2, s);
+    }
+    if (!plain) {
+        FT_TRY(use_weights(C, w, nl, W, s, wver));
+        if (C.small(L, nl)) {                                            // the whole MD in one launch
+            SmallArgs a = small_args(x, W, nl, B, act, beta, 2);
+            a.v = v; a.dt = dt; a.nstep = nstep; a.x_out = x_out; a.v_out = v_out;
+            return leap ? launch_ft_small(a, L, s) : launch_ft_small_sched(a, sc, L, s);
+        }
+    }
+    FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb));
+    return copy_pair(x_out, W.xa, v_out, W.va, W.n2, s);
+}
+
+// Plain HMC: H0, MD, H1, Metropolis -- the one sequence behind fthmc_hmc_trajectory, _int and _pb.  beta_b: per-chain beta
+// (null: the scalar `beta`; the kernels that take beta_b are handed beta = 0.0 beside it).
+int hmc_trajectory_call(const double* x, const double* v, const double* u, int B, int L, double beta, const double* beta_b, double dt,
+                        int nstep, int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                        void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
+    const bool pb = beta_b != nullptr, leap = integrator == FTHMC_INT_LEAPFROG;
+    if (pb) beta = 0.0;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(nullptr);
+    // L <= 64 (x_new must not alias x): one persistent launch per trajectory, state in LDS / registers.  The scalar-beta leapfrog
+    // has a kernel of its own, the schedule-driven one serves every other integrator and per-chain beta with every integrator.
+    if (L <= 64 && C.mfma && x_new != x)
+        return leap && !pb ? launch_hmc_trajectory_fused(x, v, u, B, L, beta, dt, nstep, x_new, dH, acc, H0, H1, s)
+                           : launch_hmc_trajectory_sched(x, v, u, B, L, beta, sc, x_new, dH, acc, H0, H1, s, beta_b);
+    FT_WS(0, false);
+    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
+    auto energy = [&](const double* xf, const double* vf, double* h) {     // h = S_W(xf) + K(vf) / 2
+        FT_TRY(pb ? launch_action_charge_pb(xf, B, L, beta_b, S, nullptr, nullptr, nullptr, s)
+                  : launch_action_charge(xf, B, L, beta, S, nullptr, nullptr, s));
+        FT_TRY(launch_kinetic(vf, B, L, K, s));
+        return launch_lincomb(S, 1.0, K, 0.5, 0.0, h, B, s);
+    };
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    FT_TRY(energy(x, v, h0));
+    double *xo = W.xb, *po = W.va;
+    if (leap) {                                                      // the fused launch_leap_step steps, then xr = regularize(x_)
+        FT_TRY(leapfrog_ws(x, v, W, B, L, beta, dt, nstep, &xo, &po, s, beta_b));
+        FT_TRY(launch_wrap(xo, xo, W.n2, 1, s));
+    } else {                                                         // the flowed schedule with zero layers: the shifted field
+        FT_TRY(ft_md_ws(C, x, v, W, 0, B, L, 0, beta, sc, s, W.xb, W.xb, beta_b));      // and then the regularized end point in W.xb
+    }
+    FT_TRY(energy(xo, po, h1));
+    return launch_metropolis(x, xo, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
+}
+
+// ---------------------------------------------------------------- per-chain beta and replica exchange (no reference counterpart)
+// The beta-free triple (log det J, C = sum cos P, Q) of x into `trip` -- carried over (state_in) or evaluated -- and S_eff of it
+// at beta_b into `seff`: the general branch's eval_action + launch_lincomb with beta read per chain
+int pb_eval(const Ctx& C, const double* x, const WS& W, int nl, int B, int L, int act, const double* beta_b,
+            const double* state_in, double* trip, double* seff, hipStream_t s) {
+    if (state_in) {
+        if (hipMemcpyAsync(trip, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    } else {
+        if (nl > 0) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, trip, s));
+        else if (hipMemsetAsync(trip, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+        FT_TRY(launch_action_charge_pb(phys_field(x, W, nl), B, L, beta_b, nullptr, trip + 2 * B, nullptr, trip + B, s, W.act_part));
+    }
+    return launch_pb_from_state(trip, beta_b, B, L, nl > 0, seff, nullptr, s);
+}
+
+// The flowed trajectory: H0, MD, H1, Metropolis, plaq / Q of x_new -- the one sequence behind fthmc_ft_trajectory_v, _int_v and
+// _pb_v.  beta_b: per-chain beta (null: the scalar `beta`); the state triples are then BETA-FREE (log det J, sum cos P, Q)
+// instead of (S_eff, plaq, Q), and the kernels that take beta_b are handed beta = 0.0 beside it.
+int ft_trajectory_call(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int nl, int B,
+                       int L, int act, double beta, const double* beta_b, double dt, int nstep, int integrator, int mode,
+                       double* x_new, double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
+                       const double* state_in, double* state_out, void* ws, size_t ws_bytes, void* stream, uint64_t wver) {
+    FT_TRY(check_flow_call(x && v && u && x_new && nstep >= 1, w, nl, B, L, act));
+    const bool pb = beta_b != nullptr, leap = integrator == FTHMC_INT_LEAPFROG;
+    if (pb) beta = 0.0;
+    if (mode != FTHMC_MODE_MD && mode != FTHMC_MODE_LITERAL) return FTHMC_ERR_UNSUPPORTED;
+    // FTHMC_MODE_LITERAL discards the MD: no integrator to choose, and no per-chain form of it
+    if (mode == FTHMC_MODE_LITERAL && (!leap || pb)) return FTHMC_ERR_UNSUPPORTED;
+    const bool md = mode == FTHMC_MODE_MD;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    FT_CTX(arch);
+    FT_WS(nl, false);
+    double* K = W.scal + (size_t)SC_K * B;
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    // per-chain state triples: of x (old), of the proposal (neu), of x_new (sel)
+    double* old = W.scal + (size_t)SC_OLD0 * B;      // slots SC_OLD0.. : 3 consecutive
+    double* neu = W.scal + (size_t)SC_NEW0 * B;
+    double* sel = state_out ? state_out : W.scal + (size_t)SC_S * B;
+    FT_TRY(use_weights(C, w, nl, W, s, wver));
+    if (md && C.small(L, nl)) {                                      // the whole trajectory in one launch
+        SmallArgs a = small_args(x, W, nl, B, act, beta, 3);
+        a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
+        a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
+        // three instances of k_ft_small: per-chain beta runs the schedule-driven one with every integrator, the leapfrog included
+        if (pb) return launch_ft_small_pb(a, sc, beta_b, L, s);
+        return leap ? launch_ft_small(a, L, s) : launch_ft_small_sched(a, sc, L, s);
+    }
+    const bool tuned = md && C.A.is_default() && nl > 0;
+    if (tuned) {
+        // tuned kernels: the scalars of either end of the trajectory come from ONE launch each (launch_traj_energy: log det J
+        // from the sweep's partials, S_W / Q / plaq of the flowed field, the kinetic term, H), the first drift and the copy of
+        // the momenta are one pass, the last kick also writes the regularized end point, the Metropolis kernel hands plaq / Q
+        // out itself: 5 small launches per trajectory where there were 15.  A schedule's shifted field lives in the proposal
+        // buffer (xshift = xreg = W.xb); the leapfrog has no SHIFT stage and reads no shift buffer.
+        const int np = flow_fwd_geom(C.mfma).ntiles(L);
+        if (!state_in) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, nullptr, s, false, false, true));
+        FT_TRY(launch_traj_energy(phys_field(x, W, nl), B, L, beta, W.lj_part, np, nl, state_in, v, old, h0, s, beta_b));
+        FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b));
+        FT_TRY(sweep_forward(C, W.xb, W, nl, B, L, act, nullptr, s, false, false, true));
+        FT_TRY(launch_traj_energy(phys_field(W.xb, W, nl), B, L, beta, W.lj_part, np, nl, nullptr, W.va, neu, h1, s, beta_b));
+    } else {                                                         // other net shapes, no layers, FTHMC_MODE_LITERAL
+        double* seff = W.scal + (size_t)SC_SEFF * B;                 // per-chain beta: S_eff beside the beta-free triple
+        if (pb) {
+            FT_TRY(pb_eval(C, x, W, nl, B, L, act, beta_b, state_in, old, seff, s));
+        } else if (state_in) {    // chained trajectories: S_eff and observables of x are the previous call's state_out
+            if (hipMemcpyAsync(old, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+                return FTHMC_ERR_LAUNCH;
+        } else {
+            FT_TRY(eval_action(C, x, W, nl, B, L, act, beta, old, nullptr, old + B, old + 2 * B, s));
+        }
+        FT_TRY(launch_kinetic(v, B, L, K, s));
+        FT_TRY(launch_lincomb(pb ? seff : old, 1.0, K, 0.5, 0.0, h0, B, s));
+        const double* vend = W.va;
+        if (!md) {
+            FT_TRY(launch_axpy(x, v, 0.5 * dt, W.xa, W.n2, s));       // ft_hmc.py:187 (Q2)
+            FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 0, s));              // wrap (ft_hmc.py:208)
+            vend = v;
+        } else if (leap && !pb) {                                     // scalar-beta leapfrog: the last kick writes no xreg,
+            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, nullptr));
+            FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 1, s));              // a launch of its own regularizes (ipynb/ft_hmc.py:426)
+        } else {                                                      // schedules and per-chain beta: xreg inside the last kick
+            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b));
+        }
+        if (pb) FT_TRY(pb_eval(C, W.xb, W, nl, B, L, act, beta_b, nullptr, neu, seff, s));
+        else FT_TRY(eval_action(C, W.xb, W, nl, B, L, act, beta, neu, nullptr, neu + B, neu + 2 * B, s));
+        FT_TRY(launch_kinetic(vend, B, L, K, s));
+        FT_TRY(launch_lincomb(pb ? seff : neu, 1.0, K, 0.5, 0.0, h1, B, s));
+    }
+    // The state of x_new without another sweep: selected per chain.  Who hands plaq / Q out: the Metropolis kernel both on the
+    // tuned branch; per-chain beta: Q (the triple's third row) from the kernel on either branch, plaq from the triple's second
+    // row and beta_b; the scalar general branch: two copies out of `sel`.
+    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s, tuned && !pb ? plaq : nullptr,
+                             tuned || pb ? Q : nullptr));
+    if (pb) {
+        if (plaq) FT_TRY(launch_pb_from_state(sel, beta_b, B, L, nl > 0, nullptr, plaq, s));
+    } else if (!tuned) {
+        if (plaq && hipMemcpyAsync(plaq, sel + B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return FTHMC_ERR_LAUNCH;
+        if (Q && hipMemcpyAsync(Q, sel + 2 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return FTHMC_ERR_LAUNCH;
+    }
+    return FTHMC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -507,15 +683,6 @@ size_t fthmc_train_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers
     if (B <= 0 || L <= 0 || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
     return ws_doubles(C.A, B, L, n_layers, true) * sizeof(double);
 }
-
-// the call's context (shape from `arch`, the debug switches, the stream), then its workspace view
-#define FT_CTX(arch_)                                                               \
-    (void)hipGetLastError();   /* drop stale (non-sticky) errors left by the host framework */ \
-    Ctx C; { const int rc_ = make_ctx((arch_), stream, &C); if (rc_ != FTHMC_OK) return rc_; } \
-    hipStream_t s = C.s; (void)s
-#define FT_WS(nl, train)                                                            \
-    if (!ws || ws_bytes < ws_doubles(C.A, B, L, (nl), (train)) * sizeof(double)) return FTHMC_ERR_WS; \
-    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, (nl), (train))
 
 int fthmc_wrap(const double* x, double* out, size_t n, void* stream) {
     if (!x || !out) return FTHMC_ERR_ARG;
@@ -596,39 +763,13 @@ int fthmc_adam_step(double* w, const double* gw, double* exp_avg, double* exp_av
 
 int fthmc_leapfrog(const double* x, const double* p, int B, int L, double beta, double dt, int nstep,
                    double* x_out, double* p_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !p || !x_out || !p_out || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
-    FT_CTX(nullptr);
-    FT_WS(0, false);
-    double *xo, *po;
-    FT_TRY(leapfrog_ws(x, p, W, B, L, beta, dt, nstep, &xo, &po, s));
-    if (hipMemcpyAsync(x_out, xo, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(p_out, po, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    return FTHMC_OK;
+    return md_call(true, x, p, nullptr, nullptr, 0, B, L, 0, beta, dt, nstep, FTHMC_INT_LEAPFROG, x_out, p_out, ws, ws_bytes, stream, 0);
 }
 
 int fthmc_hmc_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta,
                          double dt, int nstep, double* x_new, double* dH, double* acc, double* H0,
                          double* H1, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
-    FT_CTX(nullptr);
-    // L <= 64 (x_new must not alias x): one persistent launch per trajectory, state in LDS / registers
-    if (L <= 64 && C.mfma && x_new != x)
-        return launch_hmc_trajectory_fused(x, v, u, B, L, beta, dt, nstep, x_new, dH, acc, H0, H1, s);
-    FT_WS(0, false);
-    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    FT_TRY(launch_action_charge(x, B, L, beta, S, nullptr, nullptr, s));
-    FT_TRY(launch_kinetic(v, B, L, K, s));
-    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h0, B, s));
-    double *xo, *po;
-    FT_TRY(leapfrog_ws(x, v, W, B, L, beta, dt, nstep, &xo, &po, s));
-    FT_TRY(launch_wrap(xo, xo, W.n2, 1, s));                       // xr = regularize(x_)
-    FT_TRY(launch_action_charge(xo, B, L, beta, S, nullptr, nullptr, s));
-    FT_TRY(launch_kinetic(po, B, L, K, s));
-    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h1, B, s));
-    return launch_metropolis(x, xo, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
+    return hmc_trajectory_call(x, v, u, B, L, beta, nullptr, dt, nstep, FTHMC_INT_LEAPFROG, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
 }
 
 int fthmc_integrator_forces(int integrator, int nstep) { return integrator_forces(integrator, nstep); }
@@ -639,44 +780,13 @@ int fthmc_integrator_schedule(int integrator, double dt, int nstep, double* b0, 
 
 int fthmc_md(const double* x, const double* p, int B, int L, double beta, double dt, int nstep, int integrator,
              double* x_out, double* p_out, void* ws, size_t ws_bytes, void* stream) {
-    if (integrator == FTHMC_INT_LEAPFROG) return fthmc_leapfrog(x, p, B, L, beta, dt, nstep, x_out, p_out, ws, ws_bytes, stream);
-    if (!x || !p || !x_out || !p_out || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
-    Sched sc;
-    FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(nullptr);
-    FT_WS(0, false);
-    FT_TRY(ft_md_ws(C, x, p, W, 0, B, L, 0, beta, sc, s, W.xb));
-    if (hipMemcpyAsync(x_out, W.xa, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(p_out, W.va, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    return FTHMC_OK;
+    return md_call(true, x, p, nullptr, nullptr, 0, B, L, 0, beta, dt, nstep, integrator, x_out, p_out, ws, ws_bytes, stream, 0);
 }
 
 int fthmc_hmc_trajectory_int(const double* x, const double* v, const double* u, int B, int L, double beta, double dt, int nstep,
                              int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
                              void* ws, size_t ws_bytes, void* stream) {
-    if (integrator == FTHMC_INT_LEAPFROG)
-        return fthmc_hmc_trajectory(x, v, u, B, L, beta, dt, nstep, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
-    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
-    Sched sc;
-    FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(nullptr);
-    // L <= 64 (x_new must not alias x): one persistent launch per trajectory, as fthmc_hmc_trajectory
-    if (L <= 64 && C.mfma && x_new != x)
-        return launch_hmc_trajectory_sched(x, v, u, B, L, beta, sc, x_new, dH, acc, H0, H1, s);
-    FT_WS(0, false);
-    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    FT_TRY(launch_action_charge(x, B, L, beta, S, nullptr, nullptr, s));
-    FT_TRY(launch_kinetic(v, B, L, K, s));
-    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h0, B, s));
-    // the flowed schedule with zero layers: the shifted field and then the regularized end point in W.xb
-    FT_TRY(ft_md_ws(C, x, v, W, 0, B, L, 0, beta, sc, s, W.xb, W.xb));
-    FT_TRY(launch_action_charge(W.xb, B, L, beta, S, nullptr, nullptr, s));
-    FT_TRY(launch_kinetic(W.va, B, L, K, s));
-    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h1, B, s));
-    return launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
+    return hmc_trajectory_call(x, v, u, B, L, beta, nullptr, dt, nstep, integrator, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
 }
 
 int fthmc_flow_layer_fwd(const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
@@ -936,20 +1046,8 @@ int fthmc_ft_force(const double* x, const double* w, const fthmc_arch_t* arch, i
 int fthmc_ft_leapfrog_v(const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
                       int act, double beta, double dt, int nstep, double* x_out, double* v_out,
                       void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    FT_TRY(check_flow_call(x && v && x_out && v_out && nstep >= 1, w, n_layers, B, L, act));
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
-    if (C.small(L, n_layers)) {
-        SmallArgs a = small_args(x, W, n_layers, B, act, beta, 2);
-        a.v = v; a.dt = dt; a.nstep = nstep; a.x_out = x_out; a.v_out = v_out;
-        return launch_ft_small(a, L, s);
-    }
-    FT_TRY(ft_leapfrog_ws(C, x, v, W, n_layers, B, L, act, beta, dt, nstep, s));
-    if (hipMemcpyAsync(x_out, W.xa, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(v_out, W.va, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    return FTHMC_OK;
+    return md_call(false, x, v, w, arch, n_layers, B, L, act, beta, dt, nstep, FTHMC_INT_LEAPFROG, x_out, v_out, ws, ws_bytes, stream,
+                   weights_version);
 }
 
 int fthmc_ft_leapfrog(const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
@@ -963,238 +1061,42 @@ int fthmc_ft_trajectory_v(const double* x, const double* v, const double* u, con
                         double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
                         const double* state_in, double* state_out,
                         void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    FT_TRY(check_flow_call(x && v && u && x_new && nstep >= 1, w, n_layers, B, L, act));
-    if (mode != FTHMC_MODE_MD && mode != FTHMC_MODE_LITERAL) return FTHMC_ERR_UNSUPPORTED;
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    double* K = W.scal + (size_t)SC_K * B;
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    // per-chain state triples [S_eff, plaq, Q]: of x (old), of the proposal (neu), of x_new (sel)
-    double* old = W.scal + (size_t)SC_OLD0 * B;      // slots SC_OLD0.. : 3 consecutive
-    double* neu = W.scal + (size_t)SC_NEW0 * B;
-    double* sel = state_out ? state_out : W.scal + (size_t)SC_S * B;
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
-    if (mode == FTHMC_MODE_MD && C.small(L, n_layers)) {          // the whole trajectory in one launch
-        SmallArgs a = small_args(x, W, n_layers, B, act, beta, 3);
-        a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
-        a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
-        return launch_ft_small(a, L, s);
-    }
-    if (mode == FTHMC_MODE_MD && C.A.is_default() && n_layers > 0) {
-        // tuned kernels: the scalars of either end of the trajectory come from ONE launch each (launch_traj_energy: log det J
-        // from the sweep's partials, S_W / Q / plaq of the flowed field, the kinetic term, H), the first drift and the copy of
-        // the momenta are one pass, the last kick also writes the regularized end point, the Metropolis kernel hands plaq / Q
-        // out itself: 5 small launches per trajectory where there were 15
-        const int np = flow_fwd_geom(C.mfma).ntiles(L);
-        if (!state_in) FT_TRY(sweep_forward(C, x, W, n_layers, B, L, act, nullptr, s, false, false, true));
-        FT_TRY(launch_traj_energy(phys_field(x, W, n_layers), B, L, beta, W.lj_part, np, n_layers, state_in, v, old, h0, s));
-        FT_TRY(ft_leapfrog_ws(C, x, v, W, n_layers, B, L, act, beta, dt, nstep, s, W.xb));
-        FT_TRY(sweep_forward(C, W.xb, W, n_layers, B, L, act, nullptr, s, false, false, true));
-        FT_TRY(launch_traj_energy(phys_field(W.xb, W, n_layers), B, L, beta, W.lj_part, np, n_layers, nullptr, W.va, neu, h1, s));
-        return launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s, plaq, Q);
-    }
-    if (state_in) {       // chained trajectories: S_eff and observables of x are the previous call's state_out
-        if (hipMemcpyAsync(old, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return FTHMC_ERR_LAUNCH;
-    } else {
-        FT_TRY(eval_action(C, x, W, n_layers, B, L, act, beta, old, nullptr, old + B, old + 2 * B, s));
-    }
-    FT_TRY(launch_kinetic(v, B, L, K, s));
-    FT_TRY(launch_lincomb(old, 1.0, K, 0.5, 0.0, h0, B, s));
-    const double* vend;
-    if (mode == FTHMC_MODE_MD) {
-        FT_TRY(ft_leapfrog_ws(C, x, v, W, n_layers, B, L, act, beta, dt, nstep, s));
-        FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 1, s));              // regularize (ipynb/ft_hmc.py:426)
-        vend = W.va;
-    } else {
-        FT_TRY(launch_axpy(x, v, 0.5 * dt, W.xa, W.n2, s));       // ft_hmc.py:187 (Q2)
-        FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 0, s));              // wrap (ft_hmc.py:208)
-        vend = v;
-    }
-    FT_TRY(eval_action(C, W.xb, W, n_layers, B, L, act, beta, neu, nullptr, neu + B, neu + 2 * B, s));
-    FT_TRY(launch_kinetic(vend, B, L, K, s));
-    FT_TRY(launch_lincomb(neu, 1.0, K, 0.5, 0.0, h1, B, s));
-    // state of x_new without another sweep: select per chain
-    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s));
-    if (plaq && hipMemcpyAsync(plaq, sel + B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    if (Q && hipMemcpyAsync(Q, sel + 2 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    return FTHMC_OK;
+    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, nullptr, dt, nstep, FTHMC_INT_LEAPFROG, mode, x_new, dH, acc,
+                              H0, H1, plaq, Q, state_in, state_out, ws, ws_bytes, stream, weights_version);
 }
 
 int fthmc_ft_md_v(const double* x, const double* v, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
                   int act, double beta, double dt, int nstep, double* x_out, double* v_out,
                   void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version) {
-    if (integrator == FTHMC_INT_LEAPFROG)
-        return fthmc_ft_leapfrog_v(x, v, w, arch, n_layers, B, L, act, beta, dt, nstep, x_out, v_out, ws, ws_bytes, stream, weights_version);
-    FT_TRY(check_flow_call(x && v && x_out && v_out && nstep >= 1, w, n_layers, B, L, act));
-    Sched sc;
-    FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
-    if (C.small(L, n_layers)) {
-        SmallArgs a = small_args(x, W, n_layers, B, act, beta, 2);
-        a.v = v; a.dt = dt; a.nstep = nstep; a.x_out = x_out; a.v_out = v_out;
-        return launch_ft_small_sched(a, sc, L, s);
-    }
-    FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, beta, sc, s, W.xb));
-    if (hipMemcpyAsync(x_out, W.xa, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(v_out, W.va, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    return FTHMC_OK;
+    return md_call(false, x, v, w, arch, n_layers, B, L, act, beta, dt, nstep, integrator, x_out, v_out, ws, ws_bytes, stream,
+                   weights_version);
 }
 
-// fthmc_ft_trajectory_v's MD branches with the MD of a schedule; the energies, the Metropolis step and the chaining are its own
 int fthmc_ft_trajectory_int_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
                               int B, int L, int act, double beta, double dt, int nstep, int mode, double* x_new,
                               double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
                               const double* state_in, double* state_out,
                               void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version) {
-    if (integrator == FTHMC_INT_LEAPFROG)
-        return fthmc_ft_trajectory_v(x, v, u, w, arch, n_layers, B, L, act, beta, dt, nstep, mode, x_new, dH, acc, H0, H1, plaq, Q,
-                                     state_in, state_out, ws, ws_bytes, stream, weights_version);
-    FT_TRY(check_flow_call(x && v && u && x_new && nstep >= 1, w, n_layers, B, L, act));
-    if (mode != FTHMC_MODE_MD) return FTHMC_ERR_UNSUPPORTED;        // FTHMC_MODE_LITERAL discards the MD: no integrator to choose
-    Sched sc;
-    FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    double* K = W.scal + (size_t)SC_K * B;
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    double* old = W.scal + (size_t)SC_OLD0 * B;
-    double* neu = W.scal + (size_t)SC_NEW0 * B;
-    double* sel = state_out ? state_out : W.scal + (size_t)SC_S * B;
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
-    if (C.small(L, n_layers)) {                                      // the whole trajectory in one launch
-        SmallArgs a = small_args(x, W, n_layers, B, act, beta, 3);
-        a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
-        a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
-        return launch_ft_small_sched(a, sc, L, s);
-    }
-    if (C.A.is_default() && n_layers > 0) {                          // tuned kernels: the shifted field lives in the proposal buffer
-        const int np = flow_fwd_geom(C.mfma).ntiles(L);
-        if (!state_in) FT_TRY(sweep_forward(C, x, W, n_layers, B, L, act, nullptr, s, false, false, true));
-        FT_TRY(launch_traj_energy(phys_field(x, W, n_layers), B, L, beta, W.lj_part, np, n_layers, state_in, v, old, h0, s));
-        FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, beta, sc, s, W.xb, W.xb));
-        FT_TRY(sweep_forward(C, W.xb, W, n_layers, B, L, act, nullptr, s, false, false, true));
-        FT_TRY(launch_traj_energy(phys_field(W.xb, W, n_layers), B, L, beta, W.lj_part, np, n_layers, nullptr, W.va, neu, h1, s));
-        return launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s, plaq, Q);
-    }
-    if (state_in) {
-        if (hipMemcpyAsync(old, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return FTHMC_ERR_LAUNCH;
-    } else {
-        FT_TRY(eval_action(C, x, W, n_layers, B, L, act, beta, old, nullptr, old + B, old + 2 * B, s));
-    }
-    FT_TRY(launch_kinetic(v, B, L, K, s));
-    FT_TRY(launch_lincomb(old, 1.0, K, 0.5, 0.0, h0, B, s));
-    FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, beta, sc, s, W.xb, W.xb));
-    FT_TRY(eval_action(C, W.xb, W, n_layers, B, L, act, beta, neu, nullptr, neu + B, neu + 2 * B, s));
-    FT_TRY(launch_kinetic(W.va, B, L, K, s));
-    FT_TRY(launch_lincomb(neu, 1.0, K, 0.5, 0.0, h1, B, s));
-    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s));
-    if (plaq && hipMemcpyAsync(plaq, sel + B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    if (Q && hipMemcpyAsync(Q, sel + 2 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    return FTHMC_OK;
+    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, nullptr, dt, nstep, integrator, mode, x_new, dH, acc,
+                              H0, H1, plaq, Q, state_in, state_out, ws, ws_bytes, stream, weights_version);
 }
 
-// ---------------------------------------------------------------- per-chain beta and replica exchange (no reference counterpart)
-// The beta-free triple (log det J, C = sum cos P, Q) of x into `trip` -- carried over (state_in) or evaluated -- and S_eff of it
-// at beta_b into `seff`: the general branch's eval_action + launch_lincomb with beta read per chain
-static int pb_eval(const Ctx& C, const double* x, const WS& W, int nl, int B, int L, int act, const double* beta_b,
-                   const double* state_in, double* trip, double* seff, hipStream_t s) {
-    if (state_in) {
-        if (hipMemcpyAsync(trip, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-    } else {
-        if (nl > 0) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, trip, s));
-        else if (hipMemsetAsync(trip, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-        FT_TRY(launch_action_charge_pb(phys_field(x, W, nl), B, L, beta_b, nullptr, trip + 2 * B, nullptr, trip + B, s, W.act_part));
-    }
-    return launch_pb_from_state(trip, beta_b, B, L, nl > 0, seff, nullptr, s);
-}
-
+// per-chain beta (replica exchange): a null beta_b would mean "scalar beta" to the sequencers, so it is refused here
 int fthmc_ft_trajectory_pb_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
                              int B, int L, int act, const double* beta_b, double dt, int nstep, int mode, double* x_new,
                              double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
                              const double* state_in, double* state_out,
                              void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version) {
-    FT_TRY(check_flow_call(x && v && u && x_new && beta_b && nstep >= 1, w, n_layers, B, L, act));
-    if (mode != FTHMC_MODE_MD) return FTHMC_ERR_UNSUPPORTED;
-    Sched sc;
-    FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    double* K = W.scal + (size_t)SC_K * B;
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    // per-chain BETA-FREE triples (log det J, sum cos P, Q): of x (old), of the proposal (neu), of x_new (sel)
-    double* old = W.scal + (size_t)SC_OLD0 * B;
-    double* neu = W.scal + (size_t)SC_NEW0 * B;
-    double* sel = state_out ? state_out : W.scal + (size_t)SC_S * B;
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
-    if (C.small(L, n_layers)) {                                      // the whole trajectory in one launch
-        SmallArgs a = small_args(x, W, n_layers, B, act, 0.0, 3);
-        a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
-        a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
-        return launch_ft_small_pb(a, sc, beta_b, L, s);
-    }
-    if (C.A.is_default() && n_layers > 0) {                          // tuned kernels: fthmc_ft_trajectory_int_v's sequence
-        const int np = flow_fwd_geom(C.mfma).ntiles(L);
-        if (!state_in) FT_TRY(sweep_forward(C, x, W, n_layers, B, L, act, nullptr, s, false, false, true));
-        FT_TRY(launch_traj_energy(phys_field(x, W, n_layers), B, L, 0.0, W.lj_part, np, n_layers, state_in, v, old, h0, s, beta_b));
-        FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, 0.0, sc, s, W.xb, W.xb, beta_b));
-        FT_TRY(sweep_forward(C, W.xb, W, n_layers, B, L, act, nullptr, s, false, false, true));
-        FT_TRY(launch_traj_energy(phys_field(W.xb, W, n_layers), B, L, 0.0, W.lj_part, np, n_layers, nullptr, W.va, neu, h1, s, beta_b));
-    } else {                                                         // other net shapes, no layers
-        double* seff = W.scal + (size_t)SC_SEFF * B;
-        FT_TRY(pb_eval(C, x, W, n_layers, B, L, act, beta_b, state_in, old, seff, s));
-        FT_TRY(launch_kinetic(v, B, L, K, s));
-        FT_TRY(launch_lincomb(seff, 1.0, K, 0.5, 0.0, h0, B, s));
-        FT_TRY(ft_md_ws(C, x, v, W, n_layers, B, L, act, 0.0, sc, s, W.xb, W.xb, beta_b));
-        FT_TRY(pb_eval(C, W.xb, W, n_layers, B, L, act, beta_b, nullptr, neu, seff, s));
-        FT_TRY(launch_kinetic(W.va, B, L, K, s));
-        FT_TRY(launch_lincomb(seff, 1.0, K, 0.5, 0.0, h1, B, s));
-    }
-    // the state of x_new is selected per chain, beta-free; Q is its third row, plaq follows from its second and beta_b
-    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s, nullptr, Q));
-    if (plaq) FT_TRY(launch_pb_from_state(sel, beta_b, B, L, n_layers > 0, nullptr, plaq, s));
-    return FTHMC_OK;
+    if (!beta_b) return FTHMC_ERR_ARG;
+    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, 0.0, beta_b, dt, nstep, integrator, mode, x_new, dH, acc,
+                              H0, H1, plaq, Q, state_in, state_out, ws, ws_bytes, stream, weights_version);
 }
 
 int fthmc_hmc_trajectory_pb(const double* x, const double* v, const double* u, int B, int L, const double* beta_b, double dt, int nstep,
                             int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
                             void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !v || !u || !x_new || !beta_b || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
-    Sched sc;
-    FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(nullptr);
-    // L <= 64 (x_new must not alias x): one persistent launch per trajectory, the schedule-driven kernel for every integrator
-    if (L <= 64 && C.mfma && x_new != x)
-        return launch_hmc_trajectory_sched(x, v, u, B, L, 0.0, sc, x_new, dH, acc, H0, H1, s, beta_b);
-    FT_WS(0, false);
-    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    FT_TRY(launch_action_charge_pb(x, B, L, beta_b, S, nullptr, nullptr, nullptr, s));
-    FT_TRY(launch_kinetic(v, B, L, K, s));
-    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h0, B, s));
-    double *xo = W.xb, *po = W.va;
-    if (integrator == FTHMC_INT_LEAPFROG) {                          // fthmc_hmc_trajectory's fused steps
-        FT_TRY(leapfrog_ws(x, v, W, B, L, 0.0, dt, nstep, &xo, &po, s, beta_b));
-        FT_TRY(launch_wrap(xo, xo, W.n2, 1, s));
-    } else {
-        FT_TRY(ft_md_ws(C, x, v, W, 0, B, L, 0, 0.0, sc, s, W.xb, W.xb, beta_b));
-    }
-    FT_TRY(launch_action_charge_pb(xo, B, L, beta_b, S, nullptr, nullptr, nullptr, s));
-    FT_TRY(launch_kinetic(po, B, L, K, s));
-    FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h1, B, s));
-    return launch_metropolis(x, xo, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
+    if (!beta_b) return FTHMC_ERR_ARG;
+    return hmc_trajectory_call(x, v, u, B, L, 0.0, beta_b, dt, nstep, integrator, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
 }
 
 int fthmc_replica_swap(const double* betas, int K, int M, int parity, const double* C, const double* u, double* beta_b, int32_t* rung,

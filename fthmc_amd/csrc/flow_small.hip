@@ -972,79 +972,46 @@ int get_small_path() {
 }
 bool ft_small_shape(int L, int nl) { return nl >= 1 && (L == 8 || L == 12 || L == 16); }
 
-// leapfrog / trajectory of a schedule (integrator.h): the SCHED instance, mode at run time
-int launch_ft_small_sched(const SmallArgs& a0, const Sched& sched, int L, hipStream_t s) {
-    const dim3 grid(a0.B), block(NT);
-    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
-    if ((a0.mode != SM_TRAJ && a0.mode != SM_LEAPFROG) || a0.dbg || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
-    SmallArgsSched a;
-    static_cast<SmallArgs&>(a) = a0;
-    a.sched = sched;
+// one workgroup per chain: the instance of k_ft_small with these flags for the lattice size
+template <bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false>
+static int launch_instance(const typename SmallArgsOf<SCHED, PB>::type& a, int L, hipStream_t s) {
+    const dim3 grid(a.B), block(NT);
     switch (L) {
-        case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, false, true>), grid, block, 0, s, a); break;
-        case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, false, true>), grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, false, true>), grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((k_ft_small<8, TRAIN, TRAJ, DBG, SCHED, PB>), grid, block, 0, s, a); break;
+        case 12: hipLaunchKernelGGL((k_ft_small<12, TRAIN, TRAJ, DBG, SCHED, PB>), grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((k_ft_small<16, TRAIN, TRAJ, DBG, SCHED, PB>), grid, block, 0, s, a); break;
         default: return FTHMC_ERR_UNSUPPORTED;
     }
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 
+// leapfrog / trajectory of a schedule (integrator.h): the SCHED instance, mode at run time
+int launch_ft_small_sched(const SmallArgs& a0, const Sched& sched, int L, hipStream_t s) {
+    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
+    if ((a0.mode != SM_TRAJ && a0.mode != SM_LEAPFROG) || a0.dbg || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
+    SmallArgsSched a;
+    static_cast<SmallArgs&>(a) = a0;
+    a.sched = sched;
+    return launch_instance<false, false, false, true>(a, L, s);
+}
+
 // a trajectory of a schedule with per-chain beta (a0.beta is not read; state_in / state_out: the beta-free triple)
 int launch_ft_small_pb(const SmallArgs& a0, const Sched& sched, const double* beta_b, int L, hipStream_t s) {
-    const dim3 grid(a0.B), block(NT);
     if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
     if (a0.mode != SM_TRAJ || a0.dbg || !beta_b || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
     SmallArgsPB a;
     static_cast<SmallArgs&>(a) = a0;
     a.sched = sched;
     a.beta_b = beta_b;
-    switch (L) {
-        case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, false, true, true>), grid, block, 0, s, a); break;
-        case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, false, true, true>), grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, false, true, true>), grid, block, 0, s, a); break;
-        default: return FTHMC_ERR_UNSUPPORTED;
-    }
-    FT_LAUNCH_CHECK(); return FTHMC_OK;
+    return launch_instance<false, false, false, true, true>(a, L, s);
 }
 
 int launch_ft_small(const SmallArgs& a, int L, hipStream_t s) {
-    const dim3 grid(a.B), block(NT);
     if (!flow_stash_fits32(a.B, L, true)) return FTHMC_ERR_UNSUPPORTED;                  // stash_view: 32-bit plane offsets
-    if (a.mode == SM_TRAIN) {
-        if (!a.gz) return FTHMC_ERR_ARG;
-        switch (L) {
-            case 8: hipLaunchKernelGGL((k_ft_small<8, true, false, false, false>), grid, block, 0, s, a); break;
-            case 12: hipLaunchKernelGGL((k_ft_small<12, true, false, false, false>), grid, block, 0, s, a); break;
-            case 16: hipLaunchKernelGGL((k_ft_small<16, true, false, false, false>), grid, block, 0, s, a); break;
-            default: return FTHMC_ERR_UNSUPPORTED;
-        }
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    if (a.dbg) {                                            // diagnostic launches: the generic kernel with its stage stamps
-        switch (L) {
-            case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, true, false>), grid, block, 0, s, a); break;
-            case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, true, false>), grid, block, 0, s, a); break;
-            case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, true, false>), grid, block, 0, s, a); break;
-            default: return FTHMC_ERR_UNSUPPORTED;
-        }
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    if (a.mode == SM_TRAJ) {
-        switch (L) {
-            case 8: hipLaunchKernelGGL((k_ft_small<8, false, true, false, false>), grid, block, 0, s, a); break;
-            case 12: hipLaunchKernelGGL((k_ft_small<12, false, true, false, false>), grid, block, 0, s, a); break;
-            case 16: hipLaunchKernelGGL((k_ft_small<16, false, true, false, false>), grid, block, 0, s, a); break;
-            default: return FTHMC_ERR_UNSUPPORTED;
-        }
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    switch (L) {
-        case 8: hipLaunchKernelGGL((k_ft_small<8, false, false, false, false>), grid, block, 0, s, a); break;
-        case 12: hipLaunchKernelGGL((k_ft_small<12, false, false, false, false>), grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_ft_small<16, false, false, false, false>), grid, block, 0, s, a); break;
-        default: return FTHMC_ERR_UNSUPPORTED;
-    }
-    FT_LAUNCH_CHECK(); return FTHMC_OK;
+    if (a.mode == SM_TRAIN) return a.gz ? launch_instance<true, false, false, false>(a, L, s) : FTHMC_ERR_ARG;
+    if (a.dbg) return launch_instance<false, false, true, false>(a, L, s);   // diagnostic launches: the generic kernel with its stage stamps
+    if (a.mode == SM_TRAJ) return launch_instance<false, true, false, false>(a, L, s);
+    return launch_instance<false, false, false, false>(a, L, s);
 }
 
 }  // namespace fthmc

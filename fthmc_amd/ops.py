@@ -572,12 +572,11 @@ def leapfrog(x, p, beta: float, dt: float, nstep: int, integrator='leapfrog'):
     x = _field(x); p = _field(p, 'p'); B, _, L, _ = x.shape
     xo, po = torch.empty_like(x), torch.empty_like(p)
     ws, nb = _ws(x, B, L, 0)
-    if ic:
-        check(_lib.load().fthmc_md(_p(x), _p(p), B, L, float(beta), float(dt), int(nstep), ic, _p(xo), _p(po),
-                                   ws, nb, _stream(x)), 'fthmc_md')
-        return xo, po
-    check(_lib.load().fthmc_leapfrog(_p(x), _p(p), B, L, float(beta), float(dt), int(nstep), _p(xo), _p(po),
-                                     ws, nb, _stream(x)), 'fthmc_leapfrog')
+    lib, head, tail = _lib.load(), (_p(x), _p(p), B, L, float(beta), float(dt), int(nstep)), (_p(xo), _p(po), ws, nb, _stream(x))
+    if ic:                                        # 'leapfrog' keeps its own entry point (the fused leap steps)
+        check(lib.fthmc_md(*head, ic, *tail), 'fthmc_md')
+    else:
+        check(lib.fthmc_leapfrog(*head, *tail), 'fthmc_leapfrog')
     return xo, po
 
 
@@ -606,19 +605,15 @@ def hmc_trajectory(x, v, u, beta, dt: float, nstep: int, out=None, integrator='l
         raise FthmcError('out[\'x_new\']: expected a contiguous device tensor of the shape of x that is not x')
     dH, acc, H0, H1 = (_out_vec(out, k, B, x) for k in ('dH', 'acc', 'H0', 'H1'))
     ws, nb = _ws(x, B, L, 0)
+    lib, head, step = _lib.load(), (_p(x), _p(v), _p(u), B, L), (float(dt), int(nstep))
+    tail = (_p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x))
+    # the entry point decides which kernel instance runs: a tensor beta -> _pb, 'leapfrog' with a number -> the old one, else _int
     if bb is not None:
-        check(_lib.load().fthmc_hmc_trajectory_pb(_p(x), _p(v), _p(u), B, L, _p(bb), float(dt), int(nstep), ic,
-                                                  _p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x)),
-              'fthmc_hmc_trajectory_pb')
-        return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1}
-    if ic:
-        check(_lib.load().fthmc_hmc_trajectory_int(_p(x), _p(v), _p(u), B, L, float(beta), float(dt), int(nstep), ic,
-                                                   _p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x)),
-              'fthmc_hmc_trajectory_int')
-        return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1}
-    check(_lib.load().fthmc_hmc_trajectory(_p(x), _p(v), _p(u), B, L, float(beta), float(dt), int(nstep),
-                                           _p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x)),
-          'fthmc_hmc_trajectory')
+        check(lib.fthmc_hmc_trajectory_pb(*head, _p(bb), *step, ic, *tail), 'fthmc_hmc_trajectory_pb')
+    elif ic:
+        check(lib.fthmc_hmc_trajectory_int(*head, float(beta), *step, ic, *tail), 'fthmc_hmc_trajectory_int')
+    else:
+        check(lib.fthmc_hmc_trajectory(*head, float(beta), *step, *tail), 'fthmc_hmc_trajectory')
     return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1}
 
 
@@ -901,12 +896,12 @@ def ft_leapfrog(x, v, w, n_layers: int, beta: float, dt: float, nstep: int, act=
     w, ap, a = _wall(w, n_layers, arch)
     xo, vo = torch.empty_like(x), torch.empty_like(v)
     ws, nb = _ws(x, B, L, n_layers, arch=a)
-    if ic:
-        check(_lib.load().fthmc_ft_md_v(_p(x), _p(v), _p(w), ap, n_layers, B, L, act_code(act), float(beta), float(dt),
-                                        int(nstep), _p(xo), _p(vo), ws, nb, _stream(x), ic, weights_version(wkey)), 'fthmc_ft_md')
-        return xo, vo
-    check(_lib.load().fthmc_ft_leapfrog_v(_p(x), _p(v), _p(w), ap, n_layers, B, L, act_code(act), float(beta), float(dt),
-                                        int(nstep), _p(xo), _p(vo), ws, nb, _stream(x), weights_version(wkey)), 'fthmc_ft_leapfrog')
+    lib, wv = _lib.load(), weights_version(wkey)
+    args = (_p(x), _p(v), _p(w), ap, n_layers, B, L, act_code(act), float(beta), float(dt), int(nstep), _p(xo), _p(vo), ws, nb, _stream(x))
+    if ic:                                        # 'leapfrog' keeps its own entry point (another instance of the one-launch kernel)
+        check(lib.fthmc_ft_md_v(*args, ic, wv), 'fthmc_ft_md')
+    else:
+        check(lib.fthmc_ft_leapfrog_v(*args, wv), 'fthmc_ft_leapfrog')
     return xo, vo
 
 
@@ -1010,25 +1005,17 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta, dt: float, nstep: int, act='s
             raise FthmcError(f'state_in: expected [3, {B}]')
     m = {'md': MODE_MD, 'literal': MODE_LITERAL, 'reference_literal': MODE_LITERAL}[mode]
     ws, nb = _ws(x, B, L, n_layers, arch=a)
+    lib, wv = _lib.load(), weights_version(wkey)
+    head = (_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act))
+    tail = (float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']), _p(out['H0']), _p(out['H1']), _p(out['plaq']),
+            _p(out['Q']), _p(state_in), _p(out['state']), ws, nb, _stream(x))
+    # the entry point decides which kernel instance runs: a tensor beta -> _pb, 'leapfrog' with a number -> the old one, else _int
     if bb is not None:
-        check(_lib.load().fthmc_ft_trajectory_pb_v(_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), _p(bb),
-                                                   float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']),
-                                                   _p(out['H0']), _p(out['H1']), _p(out['plaq']), _p(out['Q']),
-                                                   _p(state_in), _p(out['state']), ws, nb,
-                                                   _stream(x), ic, weights_version(wkey)), 'fthmc_ft_trajectory_pb')
-        return out
-    if ic:
-        check(_lib.load().fthmc_ft_trajectory_int_v(_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), float(beta),
-                                                    float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']),
-                                                    _p(out['H0']), _p(out['H1']), _p(out['plaq']), _p(out['Q']),
-                                                    _p(state_in), _p(out['state']), ws, nb,
-                                                    _stream(x), ic, weights_version(wkey)), 'fthmc_ft_trajectory_int')
-        return out
-    check(_lib.load().fthmc_ft_trajectory_v(_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), float(beta),
-                                          float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']),
-                                          _p(out['H0']), _p(out['H1']), _p(out['plaq']), _p(out['Q']),
-                                          _p(state_in), _p(out['state']), ws, nb,
-                                          _stream(x), weights_version(wkey)), 'fthmc_ft_trajectory')
+        check(lib.fthmc_ft_trajectory_pb_v(*head, _p(bb), *tail, ic, wv), 'fthmc_ft_trajectory_pb')
+    elif ic:
+        check(lib.fthmc_ft_trajectory_int_v(*head, float(beta), *tail, ic, wv), 'fthmc_ft_trajectory_int')
+    else:
+        check(lib.fthmc_ft_trajectory_v(*head, float(beta), *tail, wv), 'fthmc_ft_trajectory')
     return out
 
 

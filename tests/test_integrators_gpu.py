@@ -110,6 +110,29 @@ def test_plain_hmc_in_place_takes_the_multi_launch_path(name, nstep):
     check_plain({'dH': dH, 'acc': acc, 'x_new': xd}, res)
 
 
+@pytest.mark.parametrize('entry', ['hmc_trajectory', 'hmc_trajectory_pb'])
+def test_plain_leapfrog_in_place_takes_the_multi_launch_path(entry):
+    """the same with the leapfrog: fthmc_hmc_trajectory and fthmc_hmc_trajectory_pb (a constant beta_b) with x_new aliasing x at
+    L = 8 run the fused leap steps, the regularizing pass and the separate energies, and are held to the oracle as above"""
+    from fthmc_amd import _lib
+    nstep = 3
+    s, x, v, u, res = plain_case(11, 3, 8, 'leapfrog', nstep)
+    B, L = 3, 8
+    xd, vd, ud = x.cuda(), v.cuda(), u.cuda()
+    dH, acc = torch.empty(B, dtype=torch.float64, device='cuda'), torch.empty(B, dtype=torch.float64, device='cuda')
+    ws, nb = ops._ws(xd, B, L, 0)
+    p = ops._p
+    if entry == 'hmc_trajectory':
+        rc = _lib.load().fthmc_hmc_trajectory(p(xd), p(vd), p(ud), B, L, BETA_PLAIN, TAU / nstep, nstep, p(xd), p(dH), p(acc), None, None,
+                                              ws, nb, ops._stream(xd))
+    else:
+        bb = torch.full((B,), BETA_PLAIN, dtype=torch.float64, device='cuda')
+        rc = _lib.load().fthmc_hmc_trajectory_pb(p(xd), p(vd), p(ud), B, L, p(bb), TAU / nstep, nstep, _lib.INTEGRATORS['leapfrog'],
+                                                 p(xd), p(dH), p(acc), None, None, ws, nb, ops._stream(xd))
+    assert rc == 0
+    check_plain({'dH': dH, 'acc': acc, 'x_new': xd}, res)
+
+
 @pytest.mark.parametrize('name,nstep', INTEGRATORS)
 def test_plain_md_vs_oracle(name, nstep):
     x, p, _ = IC.draw(21, 3, 8)
@@ -240,6 +263,32 @@ def test_chained_state_equals_stateless(L, nl, name, nstep):
         u = torch.rand(B, generator=gen, dtype=torch.float64).cuda()
         ra = ops.ft_trajectory(xa, v, u, w, nl, BETA_FT, TAU / nstep, nstep, integrator=name)
         rb = ops.ft_trajectory(xb, v, u, w, nl, BETA_FT, TAU / nstep, nstep, integrator=name, state_in=state)
+        _same(ra, rb)
+        xa, xb, state = ra['x_new'].clone(), rb['x_new'].clone(), rb['state'].clone()
+
+
+# (id, integrator, nstep, per-chain beta)
+GENERAL_SETTINGS = [('leapfrog', 'leapfrog', 3, False), ('omelyan', 'omelyan', 3, False), ('force_gradient-ladder', 'force_gradient', 2, True)]
+
+
+@pytest.mark.parametrize('setting', GENERAL_SETTINGS, ids=[c[0] for c in GENERAL_SETTINGS])
+@pytest.mark.parametrize('nl,arch', [(2, ((4,), 3, 1)), (0, None)], ids=['net-4-3-1', 'no-layers'])
+def test_chained_state_equals_stateless_on_the_general_branch(nl, arch, setting):
+    """Another net shape and a flow without layers take the general branch of the sequencer (energies, MD and Metropolis as
+    separate launches) at L = 8: state_out -> state_in over 2 trajectories changes nothing, with a number as beta (the state is
+    copied into the old triple) and with a per-chain ladder (the beta-free state: pb_eval copies it)"""
+    _, name, nstep, ladder = setting
+    B, L = 3, 8
+    w = ops.pack_weights(flow_of(46, nl, arch), device='cuda') if nl else None
+    beta = torch.tensor([1.5, 2.0, 3.0], dtype=torch.float64, device='cuda') if ladder else BETA_FT
+    gen = torch.Generator().manual_seed(46)
+    x = ((torch.rand(B, 2, L, L, generator=gen, dtype=torch.float64) * 2 - 1) * math.pi).cuda()
+    xa, xb, state = x.clone(), x.clone(), None
+    for t in range(2):
+        v = torch.randn(B, 2, L, L, generator=gen, dtype=torch.float64).cuda()
+        u = torch.rand(B, generator=gen, dtype=torch.float64).cuda()
+        ra = ops.ft_trajectory(xa, v, u, w, nl, beta, TAU / nstep, nstep, integrator=name)
+        rb = ops.ft_trajectory(xb, v, u, w, nl, beta, TAU / nstep, nstep, integrator=name, state_in=state)
         _same(ra, rb)
         xa, xb, state = ra['x_new'].clone(), rb['x_new'].clone(), rb['state'].clone()
 
