@@ -498,8 +498,7 @@ int hmc_trajectory_call(const double* x, const double* v, const double* u, int B
     FT_WS(0, false);
     double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
     auto energy = [&](const double* xf, const double* vf, double* h) {     // h = S_W(xf) + K(vf) / 2
-        FT_TRY(pb ? launch_action_charge_pb(xf, B, L, beta_b, S, nullptr, nullptr, nullptr, s)
-                  : launch_action_charge(xf, B, L, beta, S, nullptr, nullptr, s));
+        FT_TRY(launch_action_charge(xf, B, L, beta, S, nullptr, nullptr, s, nullptr, beta_b));
         FT_TRY(launch_kinetic(vf, B, L, K, s));
         return launch_lincomb(S, 1.0, K, 0.5, 0.0, h, B, s);
     };
@@ -527,7 +526,7 @@ int pb_eval(const Ctx& C, const double* x, const WS& W, int nl, int B, int L, in
     } else {
         if (nl > 0) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, trip, s));
         else if (hipMemsetAsync(trip, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-        FT_TRY(launch_action_charge_pb(phys_field(x, W, nl), B, L, beta_b, nullptr, trip + 2 * B, nullptr, trip + B, s, W.act_part));
+        FT_TRY(launch_action_charge(phys_field(x, W, nl), B, L, 0.0, nullptr, trip + 2 * B, nullptr, s, W.act_part, beta_b, trip + B));
     }
     return launch_pb_from_state(trip, beta_b, B, L, nl > 0, seff, nullptr, s);
 }

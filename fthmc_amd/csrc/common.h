@@ -27,6 +27,16 @@ namespace fthmc { void note_hip_error(hipError_t e, const char* file, int line);
 #define FT_LAUNCH_CHECK() do { } while (0)
 #endif
 
+// beta of a launch: ONE double for every chain (the instances every scalar entry point runs: their argument lists and code are
+// what they were), or -- PB, the per-chain-beta entry points (replica exchange: fthmc_*_pb) -- a device array beta_b[B] read once
+// per workgroup at the chain's index.  (In an unnamed namespace, as the kernels that take it are: BetaArg is part of their symbols.)
+namespace {
+template <bool PB> struct BetaArg { typedef double type; };
+template <> struct BetaArg<true> { typedef const double* type; };
+__device__ __forceinline__ double beta_at(double beta, int) { return beta; }
+__device__ __forceinline__ double beta_at(const double* beta_b, int b) { return beta_b[b]; }
+}  // namespace
+
 // torch.remainder(x + pi, 2 pi) - pi   (fmod is exact; sign fix as ATen does)
 // Within three periods of the principal range the remainder is one exact subtraction (Sterbenz) or
 // the same rounded addition ATen performs, so the short path is bit-identical to fmod's.

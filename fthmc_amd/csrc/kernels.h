@@ -17,8 +17,12 @@ int launch_axpy(const double* x, const double* p, double a, double* o, size_t n,
 int launch_plaq(const double* x, double* P, int B, int L, hipStream_t s);
 // wave_part (optional): 32 B doubles of scratch; with it a few chains of a large lattice (B < 128, L >= 128) run one wave per
 // workgroup instead of one workgroup per chain -- the same sums in the same order, bit-identical
+// beta_b (optional, here and below): per-chain beta, a device array [B] read in place of `beta` (the per-chain-beta entry points,
+// fthmc_*_pb); null: the instances and argument lists every other caller has always run
+// Csum (optional, with beta_b only): sum cos P per chain, the beta-free row of the carried state
 int launch_action_charge(const double* x, int B, int L, double beta, double* S, double* Q,
-                         double* plaq, hipStream_t s, double* wave_part = nullptr);
+                         double* plaq, hipStream_t s, double* wave_part = nullptr, const double* beta_b = nullptr,
+                         double* Csum = nullptr);
 int launch_kinetic(const double* v, int B, int L, double* K, hipStream_t s);
 int launch_lincomb(const double* a, double ca, const double* b, double cb, double c0, double* out,
                    int B, hipStream_t s);
@@ -26,8 +30,6 @@ int launch_stats_accumulate(const double* acc, const double* plaq, const double*
                             double* vec, hipStream_t s);
 int launch_wilson_force(const double* x, int B, int L, double beta, double* F, hipStream_t s);
 void set_leap_rows(int v);      // 1 (default): row-strip leapfrog kernel when L % 64 == 0; 0: 16 x 16 tiles always
-// beta_b (optional, here and below): per-chain beta, a device array [B] read in place of `beta` (the per-chain-beta entry points,
-// fthmc_*_pb); null: the instances and argument lists every other caller has always run
 int launch_leap_step(const double* x, const double* p, double* xo, double* po, int B, int L,
                      double beta, double a, double dt, hipStream_t s, const double* beta_b = nullptr);
 int launch_wilson_gp(const double* x, int B, int L, double beta, double* gp, hipStream_t s, const double* beta_b = nullptr);
@@ -48,9 +50,6 @@ int launch_hmc_trajectory_sched(const double* x, const double* v, const double* 
 int launch_traj_energy(const double* xphys, int B, int L, double beta, const double* lj_part, int np, int nsets,
                        const double* state_in, const double* v, double* trip, double* H, hipStream_t s,
                        const double* beta_b = nullptr);   // beta_b: trip and state_in are the BETA-FREE triple (log det J, sum cos P, Q)
-// per-chain beta (replica exchange): S_W / Q / plaq as launch_action_charge with beta_b[b], and Csum = sum cos P
-int launch_action_charge_pb(const double* x, int B, int L, const double* beta_b, double* S, double* Q, double* plaq, double* Csum,
-                            hipStream_t s, double* wave_part = nullptr);
 // S_eff (has_ld: minus row 0) and plaq from the beta-free state st[3][B] = (log det J, sum cos P, Q) and beta_b
 int launch_pb_from_state(const double* st, const double* beta_b, int B, int L, int has_ld, double* seff, double* plaq, hipStream_t s);
 // one replica-exchange round of parity 0 / 1 over M ladders of K chains (wilson.hip k_replica_swap); every ladder in order

@@ -19,12 +19,6 @@ using namespace fthmc_rng;
 using fthmc::LU_MAXL;
 using fthmc::LU_MAX_ATTEMPTS;
 
-// beta of a launch: one double, or (PB) the per-chain array read at the chain's index (wilson.hip BetaArg)
-template <bool PB> struct BetaArg { typedef double type; };
-template <> struct BetaArg<true> { typedef const double* type; };
-__device__ __forceinline__ double beta_at(double beta, int) { return beta; }
-__device__ __forceinline__ double beta_at(const double* beta_b, int b) { return beta_b[b]; }
-
 // below it 1 + 4 kappa^2 and every other place kappa enters round to their kappa = 0 values long since: the draw is the algorithm's
 // own limit r -> inf, f = z, c = 1 (accepted at once): uniform on the circle.  Above it nothing of the setup cancels (rho below)
 constexpr double LU_KAPPA_MIN = 8.673617379884035e-19;      // 2^-60

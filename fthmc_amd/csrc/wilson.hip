@@ -4,19 +4,17 @@
 // [B][2][L][L] field are contiguous in j) and shares plaquettes through LDS.
 #include "common.h"
 #include "kernels.h"
+#include <type_traits>
 
 namespace {
 
 constexpr int TS = 16;          // stencil tile (TS x TS sites, 256 threads)
 constexpr int FT_LADDER_CHUNK = 64;
 
-// beta of a launch: ONE double for every chain (the instances every scalar entry point runs: their argument lists and code are
-// what they were), or -- PB, the per-chain-beta entry points (replica exchange: fthmc_*_pb) -- a device array beta_b[B] read once
-// per workgroup at the chain's index
-template <bool PB> struct BetaArg { typedef double type; };
-template <> struct BetaArg<true> { typedef const double* type; };
-__device__ __forceinline__ double beta_at(double beta, int) { return beta; }
-__device__ __forceinline__ double beta_at(const double* beta_b, int b) { return beta_b[b]; }
+typedef double double2_t __attribute__((ext_vector_type(2)));   // two adjacent sites of a row: one 16-byte access
+
+// the periodic neighbour above / to the right of a coordinate
+__device__ __forceinline__ int next_of(int i, int L) { return i + 1 == L ? 0 : i + 1; }
 
 // ---------------------------------------------------------------- elementwise
 __global__ void k_wrap(const double* __restrict__ x, double* __restrict__ o, size_t n, int reg) {
@@ -40,7 +38,7 @@ __global__ void k_plaq(const double* __restrict__ x, double* __restrict__ P, int
     const double* x1 = x0 + n;
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
         const int i = s / L, j = s - i * L;
-        const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
+        const int ip = next_of(i, L), jp = next_of(j, L);
         P[(size_t)b * n + s] = x0[s] - x1[s] - x0[i * L + jp] + x1[ip * L + j];
     }
 }
@@ -57,7 +55,7 @@ __device__ __forceinline__ void chain_action_charge(const double* __restrict__ x
     double c = 0.0, q = 0.0;
     for (int s = tid; s < n; s += nthr) {
         const int i = s / L, j = s - i * L;
-        const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
+        const int ip = next_of(i, L), jp = next_of(j, L);
         double a = x0[s], bb = x1[s], cc = x0[i * L + jp], d = x1[ip * L + j];
         if (XFORM) { a = ft_regularize(a); bb = ft_regularize(bb); cc = ft_regularize(cc); d = ft_regularize(d); }
         c += cos(a + d - cc - bb);           // summation order of BatchAction._u1_plaq
@@ -71,21 +69,37 @@ __device__ __forceinline__ void chain_action_charge(const double* __restrict__ x
     chain_action_charge<XFORM>(x0, L, (int)threadIdx.x, (int)blockDim.x, csum, qsum);
 }
 
-__global__ void k_action_charge(const double* __restrict__ x, int L, double beta,
-                                double* __restrict__ S, double* __restrict__ Q,
-                                double* __restrict__ plaq) {
+// The scalars of chain b from its two sums c = sum cos P, q = sum wrap(P), each wherever the caller wants it:
+//   S = (-beta) c,  Q = q / 2 pi,  plaq = (-S) / (beta L^2),  Csum = c (the beta-free row of the carried state)
+// beta_: the launch's double, or the per-chain array (read here, by the one thread that stores)
+template <class Beta>
+__device__ __forceinline__ void chain_scalars(int b, double c, double q, int L, Beta beta_, double* __restrict__ S,
+                                              double* __restrict__ Q, double* __restrict__ plaq, double* __restrict__ Csum) {
+    const double beta = beta_at(beta_, b);
+    const double s = (-beta) * c;
+    if (S) S[b] = s;
+    if (Q) Q[b] = q / FT_TWO_PI;
+    if (plaq) plaq[b] = (-s) / (beta * (double)(L * L));
+    if (Csum) Csum[b] = c;
+}
+
+// one workgroup per chain: the block sums, thread 0 stores
+template <class Beta>
+__device__ __forceinline__ void action_charge_chain(const double* __restrict__ x, int L, Beta beta_, double* __restrict__ S,
+                                                    double* __restrict__ Q, double* __restrict__ plaq, double* __restrict__ Csum) {
     __shared__ double red[16];
     const int b = blockIdx.x;
     double c, q;
     chain_action_charge<0>(x + (size_t)b * 2 * L * L, L, c, q);
     c = ft_block_sum(c, red);
     q = ft_block_sum(q, red);
-    if (threadIdx.x == 0) {
-        const double s = (-beta) * c;
-        if (S) S[b] = s;
-        if (Q) Q[b] = q / FT_TWO_PI;
-        if (plaq) plaq[b] = (-s) / (beta * (double)(L * L));
-    }
+    if (threadIdx.x == 0) chain_scalars(b, c, q, L, beta_, S, Q, plaq, Csum);
+}
+
+__global__ void k_action_charge(const double* __restrict__ x, int L, double beta,
+                                double* __restrict__ S, double* __restrict__ Q,
+                                double* __restrict__ plaq) {
+    action_charge_chain(x, L, beta, S, Q, plaq, nullptr);
 }
 
 // The same sums by the same threads in the same order, for a FEW chains of a LARGE lattice (a training shard: 32 chains of
@@ -100,16 +114,19 @@ __global__ __launch_bounds__(FT_WAVE) void k_action_charge_waves(const double* _
     q = ft_wave_sum(q);
     if (threadIdx.x == 0) { part[((size_t)b * nw + w) * 2] = c; part[((size_t)b * nw + w) * 2 + 1] = q; }
 }
-__global__ void k_action_charge_fin(const double* __restrict__ part, int nw, int B, int L, double beta, double* __restrict__ S,
-                                    double* __restrict__ Q, double* __restrict__ plaq) {
+template <class Beta>
+__device__ __forceinline__ void action_charge_fin(const double* __restrict__ part, int nw, int B, int L, Beta beta_,
+                                                  double* __restrict__ S, double* __restrict__ Q, double* __restrict__ plaq,
+                                                  double* __restrict__ Csum) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     double c = 0.0, q = 0.0;
     for (int w = 0; w < nw; ++w) { c += part[((size_t)b * nw + w) * 2]; q += part[((size_t)b * nw + w) * 2 + 1]; }
-    const double s = (-beta) * c;
-    if (S) S[b] = s;
-    if (Q) Q[b] = q / FT_TWO_PI;
-    if (plaq) plaq[b] = (-s) / (beta * (double)(L * L));
+    chain_scalars(b, c, q, L, beta_, S, Q, plaq, Csum);
+}
+__global__ void k_action_charge_fin(const double* __restrict__ part, int nw, int B, int L, double beta, double* __restrict__ S,
+                                    double* __restrict__ Q, double* __restrict__ plaq) {
+    action_charge_fin(part, nw, B, L, beta, S, Q, plaq, nullptr);
 }
 
 __global__ void k_kinetic(const double* __restrict__ v, int n, double* __restrict__ K) {
@@ -202,6 +219,9 @@ __global__ void k_axpy_copy(const double* __restrict__ x, const double* __restri
 // MODE 0: F = dS/dx of x.
 // MODE 1: fused leapfrog step  x' = x + a p ; p' = p - dt F(x')  (ping-pong buffers)
 // MODE 2: gP = beta sin P (plaquette-gradient field that seeds the flow backward sweep)
+// u / W, exact for 0 <= u < 2^20 / W (an index into a window of W columns; the windows here hold ~300 entries): one 24-bit multiply
+template <int W> __device__ __forceinline__ int div_small(int u) { return (int)(__umul24((unsigned)u, ((1u << 20) + W - 1) / W) >> 20); }
+
 template <int MODE, bool PB = false>
 __global__ __launch_bounds__(256) void k_force(const double* __restrict__ x,
                                                const double* __restrict__ p,
@@ -226,8 +246,7 @@ __global__ __launch_bounds__(256) void k_force(const double* __restrict__ x,
     for (int t = threadIdx.x; t < NW0 + NW1; t += blockDim.x) {
         const bool second = t >= NW0;
         const int u = second ? t - NW0 : t;
-        const int r = second ? (int)(__umul24((unsigned)u, ((1u << 20) + W1C - 1) / W1C) >> 20)
-                             : (int)(__umul24((unsigned)u, ((1u << 20) + W0C - 1) / W0C) >> 20);
+        const int r = second ? div_small<W1C>(u) : div_small<W0C>(u);
         const int c = u - r * (second ? W1C : W0C);
         int wi = i0 - 1 + r, wj = j0 - 1 + c;
         if (fastw) {
@@ -245,7 +264,7 @@ __global__ __launch_bounds__(256) void k_force(const double* __restrict__ x,
     }
     __syncthreads();
     for (int t = threadIdx.x; t < WP * WP; t += blockDim.x) {
-        const int r = (int)(__umul24((unsigned)t, ((1u << 20) + WP - 1) / WP) >> 20), c = t - r * WP;
+        const int r = div_small<WP>(t), c = t - r * WP;
         double sn, cs;
         ft_sincos(sx0[r * W0C + c] - sx1[r * W1C + c] - sx0[r * W0C + c + 1] + sx1[(r + 1) * W1C + c], &sn, &cs);
         sp[t] = beta * sn;
@@ -283,7 +302,6 @@ __global__ __launch_bounds__(TR * 32) void k_leap_rows(const double* __restrict_
                                                        double* __restrict__ xo, double* __restrict__ po,
                                                        int L, typename BetaArg<PB>::type beta_, double a, double dt) {
     constexpr int TC = 64, WC = TC + 2, NTH = TR * 32;
-    typedef double double2_t __attribute__((ext_vector_type(2)));
     // window row r <-> lattice row i0 - 1 + r, window column c <-> lattice column j0 - 1 + c
     __shared__ __attribute__((aligned(16))) double sx0[(TR + 1) * WC], sx1[(TR + 2) * WC], ss[(TR + 1) * WC];
     const int b = blockIdx.z, i0 = blockIdx.y * TR, j0 = blockIdx.x * TC;
@@ -348,8 +366,17 @@ __global__ __launch_bounds__(TR * 32) void k_leap_rows(const double* __restrict_
     }
 }
 
-// v' = v - dt * adj(gP)   (adjoint of the plaquette stencil applied to a plaquette-
-// gradient field; closes one flowed leapfrog kick), optionally followed by the
+// adj(gP): the adjoint of the plaquette stencil applied to one chain's plaquette-gradient field g, at site s -- the gradients
+// of the site's two links:  f0 = g - g[left],  f1 = g[up] - g
+__device__ __forceinline__ void adj_gp_site(const double* __restrict__ g, int L, int s, double& f0, double& f1) {
+    const int i = s / L, j = s - i * L;
+    const int im = i == 0 ? L - 1 : i - 1, jm = j == 0 ? L - 1 : j - 1;
+    const double gc = g[s];
+    f0 = gc - g[i * L + jm];
+    f1 = g[im * L + j] - gc;
+}
+
+// v' = v - dt * adj(gP)   (closes one flowed leapfrog kick), optionally followed by the
 // drift x' = x + a v'.  In place on v (and x): every thread touches its own site only.
 __global__ void k_kick_from_gp(const double* __restrict__ gp, double* __restrict__ v,
                                double* __restrict__ xq, double* __restrict__ Fout,
@@ -358,11 +385,8 @@ __global__ void k_kick_from_gp(const double* __restrict__ gp, double* __restrict
     const int n = L * L;
     const double* g = gp + (size_t)b * n;
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
-        const int i = s / L, j = s - i * L;
-        const int im = i == 0 ? L - 1 : i - 1, jm = j == 0 ? L - 1 : j - 1;
-        const double gc = g[s];
-        const double f0 = gc - g[i * L + jm];
-        const double f1 = g[im * L + j] - gc;
+        double f0, f1;
+        adj_gp_site(g, L, s, f0, f1);
         const size_t s0 = (size_t)b * 2 * n + s, s1 = s0 + n;
         if (Fout) { Fout[s0] = f0; Fout[s1] = f1; }
         if (v) {
@@ -382,18 +406,33 @@ __global__ void k_kick_from_gp(const double* __restrict__ gp, double* __restrict
 // plane is one 16-byte load / store per lane; the left / right neighbour of a lane's pair comes from the neighbouring lane
 // (the 32 lanes of a row segment are one half-wave), only the segment's edge lanes load it.  No LDS, no barrier.
 // Same arithmetic per site as k_force<2> / k_kick_from_gp: results are bit-identical.
-//
+
+// the strip coordinates of a thread: chain b, row i, lane q of the row segment, first column j of its pair
+struct Strip { int b, i, q, j; };
+template <int TR> __device__ __forceinline__ Strip strip_of() {
+    const int q = threadIdx.x & 31;
+    return Strip{(int)blockIdx.z, (int)(blockIdx.y * TR + (threadIdx.x >> 5)), q, (int)(blockIdx.x * 64 + 2 * q)};
+}
+
+// adj(gP) of the pair (i, j), (i, j + 1): adj_gp_site's differences, the pair's left neighbour gP[i][j - 1] from the previous lane
+__device__ __forceinline__ void adj_gp_pair(const double* __restrict__ g, int L, int i, int q, int j, double2_t& f0, double2_t& f1) {
+    const int im = i == 0 ? L - 1 : i - 1;
+    const double2_t gc = *reinterpret_cast<const double2_t*>(g + i * L + j), gu = *reinterpret_cast<const double2_t*>(g + im * L + j);
+    double gl = __shfl_up(gc.y, 1, 32);                                       // the previous lane's second site
+    if (q == 0) gl = g[i * L + (j == 0 ? L - 1 : j - 1)];
+    f0 = double2_t{gc.x - gl, gc.y - gc.x}; f1 = double2_t{gu.x - gc.x, gu.y - gc.y};
+}
+
 // gP = beta sin P(x): the seed of the flow's backward sweep (qed_helpers.py:226-242: d S_W / d P)
 template <int TR, bool PB = false>
 __global__ __launch_bounds__(TR * 32) void k_gp_rows(const double* __restrict__ x, double* __restrict__ gp, int L,
                                                      typename BetaArg<PB>::type beta_) {
-    typedef double double2_t __attribute__((ext_vector_type(2)));
-    const int b = blockIdx.z, i = blockIdx.y * TR + (threadIdx.x >> 5), q = threadIdx.x & 31, j = blockIdx.x * 64 + 2 * q;
+    const auto [b, i, q, j] = strip_of<TR>();
     const double beta = beta_at(beta_, b);
     const int n = L * L;
     const double* x0 = x + (size_t)b * 2 * n;
     const double* x1 = x0 + n;
-    const int ip = i + 1 == L ? 0 : i + 1;
+    const int ip = next_of(i, L);
     const double2_t a0 = *reinterpret_cast<const double2_t*>(x0 + i * L + j), a1 = *reinterpret_cast<const double2_t*>(x1 + i * L + j);
     const double2_t d1 = *reinterpret_cast<const double2_t*>(x1 + ip * L + j);
     double r0 = __shfl_down(a0.x, 1, 32);                                     // x0[i][j + 2]: the next lane's first site
@@ -408,15 +447,11 @@ __global__ __launch_bounds__(TR * 32) void k_gp_rows(const double* __restrict__ 
 template <int TR>
 __global__ __launch_bounds__(TR * 32) void k_kick_rows(const double* __restrict__ gp, double* __restrict__ v, double* __restrict__ xq,
                                                        double* __restrict__ Fout, int L, double dt, double a, double* __restrict__ xreg) {
-    typedef double double2_t __attribute__((ext_vector_type(2)));
-    const int b = blockIdx.z, i = blockIdx.y * TR + (threadIdx.x >> 5), q = threadIdx.x & 31, j = blockIdx.x * 64 + 2 * q;
+    const auto [b, i, q, j] = strip_of<TR>();
     const int n = L * L;
     const double* g = gp + (size_t)b * n;
-    const int im = i == 0 ? L - 1 : i - 1;
-    const double2_t gc = *reinterpret_cast<const double2_t*>(g + i * L + j), gu = *reinterpret_cast<const double2_t*>(g + im * L + j);
-    double gl = __shfl_up(gc.y, 1, 32);                                       // gP[i][j - 1]: the previous lane's second site
-    if (q == 0) gl = g[i * L + (j == 0 ? L - 1 : j - 1)];
-    const double2_t f0 = {gc.x - gl, gc.y - gc.x}, f1 = {gu.x - gc.x, gu.y - gc.y};
+    double2_t f0, f1;
+    adj_gp_pair(g, L, i, q, j, f0, f1);
     const size_t s0 = (size_t)b * 2 * n + (size_t)i * L + j, s1 = s0 + n;
     if (Fout) { *reinterpret_cast<double2_t*>(Fout + s0) = f0; *reinterpret_cast<double2_t*>(Fout + s1) = f1; }
     if (v) {
@@ -443,11 +478,8 @@ __global__ void k_shift_from_gp(const double* __restrict__ gp, const double* __r
     const int n = L * L;
     const double* g = gp + (size_t)b * n;
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < n; s += gridDim.x * blockDim.x) {
-        const int i = s / L, j = s - i * L;
-        const int im = i == 0 ? L - 1 : i - 1, jm = j == 0 ? L - 1 : j - 1;
-        const double gc = g[s];
-        const double f0 = gc - g[i * L + jm];
-        const double f1 = g[im * L + j] - gc;
+        double f0, f1;
+        adj_gp_site(g, L, s, f0, f1);
         const size_t s0 = (size_t)b * 2 * n + s, s1 = s0 + n;
         xs[s0] = x[s0] - c * f0; xs[s1] = x[s1] - c * f1;
     }
@@ -457,15 +489,11 @@ __global__ void k_shift_from_gp(const double* __restrict__ gp, const double* __r
 template <int TR>
 __global__ __launch_bounds__(TR * 32) void k_shift_rows(const double* __restrict__ gp, const double* __restrict__ x, double* __restrict__ xs,
                                                         int L, double c) {
-    typedef double double2_t __attribute__((ext_vector_type(2)));
-    const int b = blockIdx.z, i = blockIdx.y * TR + (threadIdx.x >> 5), q = threadIdx.x & 31, j = blockIdx.x * 64 + 2 * q;
+    const auto [b, i, q, j] = strip_of<TR>();
     const int n = L * L;
     const double* g = gp + (size_t)b * n;
-    const int im = i == 0 ? L - 1 : i - 1;
-    const double2_t gc = *reinterpret_cast<const double2_t*>(g + i * L + j), gu = *reinterpret_cast<const double2_t*>(g + im * L + j);
-    double gl = __shfl_up(gc.y, 1, 32);                                       // gP[i][j - 1]: the previous lane's second site
-    if (q == 0) gl = g[i * L + (j == 0 ? L - 1 : j - 1)];
-    const double2_t f0 = {gc.x - gl, gc.y - gc.x}, f1 = {gu.x - gc.x, gu.y - gc.y};
+    double2_t f0, f1;
+    adj_gp_pair(g, L, i, q, j, f0, f1);
     const size_t s0 = (size_t)b * 2 * n + (size_t)i * L + j, s1 = s0 + n;
     const double2_t y0 = *reinterpret_cast<const double2_t*>(x + s0), y1 = *reinterpret_cast<const double2_t*>(x + s1);
     *reinterpret_cast<double2_t*>(xs + s0) = double2_t{y0.x - c * f0.x, y0.y - c * f0.y};
@@ -798,33 +826,11 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __
 // out C = sum cos P itself (the beta-free row of the carried state)
 __global__ void k_action_charge_pb(const double* __restrict__ x, int L, const double* __restrict__ beta_b,
                                    double* __restrict__ S, double* __restrict__ Q, double* __restrict__ plaq, double* __restrict__ Csum) {
-    __shared__ double red[16];
-    const int b = blockIdx.x;
-    double c, q;
-    chain_action_charge<0>(x + (size_t)b * 2 * L * L, L, c, q);
-    c = ft_block_sum(c, red);
-    q = ft_block_sum(q, red);
-    if (threadIdx.x == 0) {
-        const double beta = beta_b[b];
-        const double s = (-beta) * c;
-        if (S) S[b] = s;
-        if (Q) Q[b] = q / FT_TWO_PI;
-        if (plaq) plaq[b] = (-s) / (beta * (double)(L * L));
-        if (Csum) Csum[b] = c;
-    }
+    action_charge_chain(x, L, beta_b, S, Q, plaq, Csum);
 }
 __global__ void k_action_charge_fin_pb(const double* __restrict__ part, int nw, int B, int L, const double* __restrict__ beta_b,
                                        double* __restrict__ S, double* __restrict__ Q, double* __restrict__ plaq, double* __restrict__ Csum) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    double c = 0.0, q = 0.0;
-    for (int w = 0; w < nw; ++w) { c += part[((size_t)b * nw + w) * 2]; q += part[((size_t)b * nw + w) * 2 + 1]; }
-    const double beta = beta_b[b];
-    const double s = (-beta) * c;
-    if (S) S[b] = s;
-    if (Q) Q[b] = q / FT_TWO_PI;
-    if (plaq) plaq[b] = (-s) / (beta * (double)(L * L));
-    if (Csum) Csum[b] = c;
+    action_charge_fin(part, nw, B, L, beta_b, S, Q, plaq, Csum);
 }
 
 // S_eff and plaq of a chain from its beta-free state st[3][B] = (log det J, C, Q) and beta_b[b], by k_traj_energy's expressions:
@@ -891,8 +897,26 @@ __global__ void k_ladder_init(const double* __restrict__ betas, int K, long long
 
 int g_leap_rows = 1;     // FTHMC_LEAP_ROWS=0 in the environment: the 16 x 16-tile kernel for every L (A/B runs)
 
+// ---- the launch shapes
 inline int ew_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 2048 ? 2048 : (g ? g : 1)); }
 inline dim3 tile_grid(int B, int L) { return dim3((L + TS - 1) / TS, (L + TS - 1) / TS, B); }
+// one workgroup per chain: its size for an L x L lattice.  Every chain sum (action, charge, kinetic energy, k_traj_energy) is launched
+// with it, so that the same sum is bit-identical wherever it is formed
+inline int chain_threads(int L) { return L * L >= 4096 ? 1024 : (L * L >= 1024 ? 512 : 256); }
+// grid-stride walk over a chain's sites, 256 threads a workgroup, at most 64 workgroups per chain
+inline dim3 stride_grid(int B, int L) { const int gx = (L * L + 255) / 256; return dim3(gx > 64 ? 64 : gx, B); }
+// row strips: whole 64-site row segments (16-byte accesses, two sites per thread), TR rows to a workgroup
+constexpr int TR = 8;
+inline bool row_strips(int L) { return L % 64 == 0 && g_leap_rows; }
+inline dim3 strip_grid(int B, int L) { return dim3(L / 64, L / TR, B); }
+constexpr int STRIP_THREADS = TR * 32;
+
+// The scalar / per-chain-beta split of a launcher: f(PB, beta of the launch) with PB = std::false_type and the double, or
+// std::true_type and the device array
+template <class F> inline void with_beta(double beta, const double* beta_b, F f) {
+    if (beta_b) f(std::true_type{}, beta_b);
+    else f(std::false_type{}, beta);
+}
 
 }  // namespace
 
@@ -911,35 +935,20 @@ int launch_axpy(const double* x, const double* p, double a, double* o, size_t n,
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_plaq(const double* x, double* P, int B, int L, hipStream_t s) {
-    int gx = (L * L + 255) / 256; if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(k_plaq, dim3(gx, B), dim3(256), 0, s, x, P, L);
+    hipLaunchKernelGGL(k_plaq, stride_grid(B, L), dim3(256), 0, s, x, P, L);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_action_charge(const double* x, int B, int L, double beta, double* S, double* Q,
-                         double* plaq, hipStream_t s, double* wave_part) {
-    const int nt = L * L >= 4096 ? 1024 : (L * L >= 1024 ? 512 : 256);
+                         double* plaq, hipStream_t s, double* wave_part, const double* beta_b, double* Csum) {
+    const int nt = chain_threads(L);
     if (wave_part && B < 128 && L >= 128) {                 // fewer workgroups than half the CUs, each busy for tens of us
         const int nw = nt / FT_WAVE;
         hipLaunchKernelGGL(k_action_charge_waves, dim3(nw, B), dim3(FT_WAVE), 0, s, x, L, wave_part);
         FT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_action_charge_fin, dim3((B + 63) / 64), dim3(64), 0, s, wave_part, nw, B, L, beta, S, Q, plaq);
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    hipLaunchKernelGGL(k_action_charge, dim3(B), dim3(nt), 0, s, x, L, beta, S, Q, plaq);
-    FT_LAUNCH_CHECK(); return FTHMC_OK;
-}
-// launch_action_charge's two forms (the same choice between them) with beta = beta_b[b]; Csum: sum cos P per chain
-int launch_action_charge_pb(const double* x, int B, int L, const double* beta_b, double* S, double* Q, double* plaq, double* Csum,
-                            hipStream_t s, double* wave_part) {
-    const int nt = L * L >= 4096 ? 1024 : (L * L >= 1024 ? 512 : 256);
-    if (wave_part && B < 128 && L >= 128) {
-        const int nw = nt / FT_WAVE;
-        hipLaunchKernelGGL(k_action_charge_waves, dim3(nw, B), dim3(FT_WAVE), 0, s, x, L, wave_part);
-        FT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_action_charge_fin_pb, dim3((B + 63) / 64), dim3(64), 0, s, wave_part, nw, B, L, beta_b, S, Q, plaq, Csum);
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    hipLaunchKernelGGL(k_action_charge_pb, dim3(B), dim3(nt), 0, s, x, L, beta_b, S, Q, plaq, Csum);
+        if (beta_b) hipLaunchKernelGGL(k_action_charge_fin_pb, dim3((B + 63) / 64), dim3(64), 0, s, wave_part, nw, B, L, beta_b, S, Q, plaq, Csum);
+        else hipLaunchKernelGGL(k_action_charge_fin, dim3((B + 63) / 64), dim3(64), 0, s, wave_part, nw, B, L, beta, S, Q, plaq);
+    } else if (beta_b) hipLaunchKernelGGL(k_action_charge_pb, dim3(B), dim3(nt), 0, s, x, L, beta_b, S, Q, plaq, Csum);
+    else hipLaunchKernelGGL(k_action_charge, dim3(B), dim3(nt), 0, s, x, L, beta, S, Q, plaq);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_pb_from_state(const double* st, const double* beta_b, int B, int L, int has_ld, double* seff, double* plaq, hipStream_t s) {
@@ -966,9 +975,7 @@ int launch_ladder_init(const double* betas_host, double* betas, int K, int M, do
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_kinetic(const double* v, int B, int L, double* K, hipStream_t s) {
-    const int n = 2 * L * L;
-    const int nt = n >= 8192 ? 1024 : (n >= 2048 ? 512 : 256);
-    hipLaunchKernelGGL(k_kinetic, dim3(B), dim3(nt), 0, s, v, n, K);
+    hipLaunchKernelGGL(k_kinetic, dim3(B), dim3(chain_threads(L)), 0, s, v, 2 * L * L, K);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_lincomb(const double* a, double ca, const double* b, double cb, double c0, double* out,
@@ -999,21 +1006,11 @@ int launch_wilson_force(const double* x, int B, int L, double beta, double* F, h
 }
 int launch_leap_step(const double* x, const double* p, double* xo, double* po, int B, int L,
                      double beta, double a, double dt, hipStream_t s, const double* beta_b) {
-    if (beta_b) {                                // per-chain beta: the same two kernels, beta read at the chain's index
-        if (L % 64 == 0 && g_leap_rows) {
-            constexpr int TR = 8;
-            hipLaunchKernelGGL((k_leap_rows<TR, true>), dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, x, p, xo, po, L, beta_b, a, dt);
-            FT_LAUNCH_CHECK(); return FTHMC_OK;
-        }
-        hipLaunchKernelGGL((k_force<1, true>), tile_grid(B, L), dim3(256), 0, s, x, p, xo, po, L, beta_b, a, dt);
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    if (L % 64 == 0 && g_leap_rows) {            // whole 64-site row segments: 16-byte accesses, two sites per thread
-        constexpr int TR = 8;
-        hipLaunchKernelGGL(k_leap_rows<TR>, dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, x, p, xo, po, L, beta, a, dt);
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    hipLaunchKernelGGL(k_force<1>, tile_grid(B, L), dim3(256), 0, s, x, p, xo, po, L, beta, a, dt);
+    with_beta(beta, beta_b, [&](auto pb, auto bt) {
+        constexpr bool PB = decltype(pb)::value;
+        if (row_strips(L)) hipLaunchKernelGGL((k_leap_rows<TR, PB>), strip_grid(B, L), dim3(STRIP_THREADS), 0, s, x, p, xo, po, L, bt, a, dt);
+        else hipLaunchKernelGGL((k_force<1, PB>), tile_grid(B, L), dim3(256), 0, s, x, p, xo, po, L, bt, a, dt);
+    });
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_hmc_trajectory_fused(const double* x, const double* v, const double* u, int B, int L, double beta,
@@ -1024,62 +1021,43 @@ int launch_hmc_trajectory_fused(const double* x, const double* v, const double* 
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_wilson_gp(const double* x, int B, int L, double beta, double* gp, hipStream_t s, const double* beta_b) {
-    if (beta_b) {                                // per-chain beta: gP[b] = beta_b[b] sin P
-        if (L % 64 == 0 && g_leap_rows) {
-            constexpr int TR = 8;
-            hipLaunchKernelGGL((k_gp_rows<TR, true>), dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, x, gp, L, beta_b);
-            FT_LAUNCH_CHECK(); return FTHMC_OK;
-        }
-        hipLaunchKernelGGL((k_force<2, true>), tile_grid(B, L), dim3(256), 0, s, x, nullptr, gp, nullptr, L, beta_b, 0.0, 0.0);
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    if (L % 64 == 0 && g_leap_rows) {
-        constexpr int TR = 8;
-        hipLaunchKernelGGL(k_gp_rows<TR>, dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, x, gp, L, beta);
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    hipLaunchKernelGGL(k_force<2>, tile_grid(B, L), dim3(256), 0, s, x, nullptr, gp, nullptr, L, beta, 0.0, 0.0);
+    with_beta(beta, beta_b, [&](auto pb, auto bt) {
+        constexpr bool PB = decltype(pb)::value;
+        if (row_strips(L)) hipLaunchKernelGGL((k_gp_rows<TR, PB>), strip_grid(B, L), dim3(STRIP_THREADS), 0, s, x, gp, L, bt);
+        else hipLaunchKernelGGL((k_force<2, PB>), tile_grid(B, L), dim3(256), 0, s, x, nullptr, gp, nullptr, L, bt, 0.0, 0.0);
+    });
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_kick_from_gp(const double* gp, double* v, double* xq, double* Fout, int B, int L,
                         double dt, double a, hipStream_t s, double* xreg) {
-    if (L % 64 == 0 && g_leap_rows) {
-        constexpr int TR = 8;
-        hipLaunchKernelGGL(k_kick_rows<TR>, dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, gp, v, xq, Fout, L, dt, a, xreg);
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    int gx = (L * L + 255) / 256; if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(k_kick_from_gp, dim3(gx, B), dim3(256), 0, s, gp, v, xq, Fout, L, dt, a, xreg);
+    if (row_strips(L)) hipLaunchKernelGGL(k_kick_rows<TR>, strip_grid(B, L), dim3(STRIP_THREADS), 0, s, gp, v, xq, Fout, L, dt, a, xreg);
+    else hipLaunchKernelGGL(k_kick_from_gp, stride_grid(B, L), dim3(256), 0, s, gp, v, xq, Fout, L, dt, a, xreg);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_shift_from_gp(const double* gp, const double* x, double* xs, int B, int L, double c, hipStream_t s) {
-    if (L % 64 == 0 && g_leap_rows) {
-        constexpr int TR = 8;
-        hipLaunchKernelGGL(k_shift_rows<TR>, dim3(L / 64, L / TR, B), dim3(TR * 32), 0, s, gp, x, xs, L, c);
-        FT_LAUNCH_CHECK(); return FTHMC_OK;
-    }
-    int gx = (L * L + 255) / 256; if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(k_shift_from_gp, dim3(gx, B), dim3(256), 0, s, gp, x, xs, L, c);
+    if (row_strips(L)) hipLaunchKernelGGL(k_shift_rows<TR>, strip_grid(B, L), dim3(STRIP_THREADS), 0, s, gp, x, xs, L, c);
+    else hipLaunchKernelGGL(k_shift_from_gp, stride_grid(B, L), dim3(256), 0, s, gp, x, xs, L, c);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_hmc_trajectory_sched(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sched,
                                 double* x_new, double* dH, double* acc, double* H0, double* H1, hipStream_t s, const double* beta_b) {
     if (L > TJ_MAXL) return FTHMC_ERR_UNSUPPORTED;
     if (sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
-    if (beta_b) { hipLaunchKernelGGL(k_hmc_trajectory_sched<true>, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, beta_b, sched, x_new, dH, acc, H0, H1); }
-    else { hipLaunchKernelGGL(k_hmc_trajectory_sched<false>, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, beta, sched, x_new, dH, acc, H0, H1); }
+    with_beta(beta, beta_b, [&](auto pb, auto bt) {
+        hipLaunchKernelGGL(k_hmc_trajectory_sched<decltype(pb)::value>, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, bt, sched, x_new, dH, acc, H0, H1);
+    });
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_traj_energy(const double* xphys, int B, int L, double beta, const double* lj_part, int np, int nsets,
                        const double* state_in, const double* v, double* trip, double* H, hipStream_t s, const double* beta_b) {
-    const int nt = L * L >= 4096 ? 1024 : (L * L >= 1024 ? 512 : 256);           // = launch_action_charge = launch_kinetic
-    if (beta_b) { hipLaunchKernelGGL(k_traj_energy<true>, dim3(B), dim3(nt), 0, s, xphys, L, beta_b, lj_part, np, nsets, state_in, v, trip, H, B); }
-    else { hipLaunchKernelGGL(k_traj_energy<false>, dim3(B), dim3(nt), 0, s, xphys, L, beta, lj_part, np, nsets, state_in, v, trip, H, B); }
+    with_beta(beta, beta_b, [&](auto pb, auto bt) {
+        hipLaunchKernelGGL(k_traj_energy<decltype(pb)::value>, dim3(B), dim3(chain_threads(L)), 0, s, xphys, L, bt, lj_part, np, nsets, state_in,
+                           v, trip, H, B);
+    });
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_plane_from(const double* g, int B, int L, int mu, double sign, double* out, hipStream_t s) {
-    int gx = (L * L + 255) / 256; if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(k_plane_from, dim3(gx, B), dim3(256), 0, s, g, L * L, mu, sign, out);
+    hipLaunchKernelGGL(k_plane_from, stride_grid(B, L), dim3(256), 0, s, g, L * L, mu, sign, out);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_axpy_copy(const double* x, const double* p, double a, double* xo, double* po, size_t n, hipStream_t s) {
