@@ -22,7 +22,7 @@
 //
 // Reference: autograd of GaugeEquivCouplingLayer.forward (fthmc/utils/layers.py:196-202,348-371)
 // as used by ft_force (qed_helpers.py:226-242) and train_step (train.py:162-228).
-#include "flow_mfma_common.h"
+#include "flow_bwd_common.h"
 #include "flow_transform.h"
 
 namespace {
@@ -30,22 +30,11 @@ namespace {
 using namespace fthmc;
 using namespace fthmc_flow;
 
-constexpr int cmax_(int a, int b) { return a > b ? a : b; }
 constexpr unsigned BWD_HAS_UPLINK = 1u << 16, BWD_HAS_GLOGJ = 1u << 17, BWD_HAS_GZ = 1u << 18, BWD_HAS_DBG = 1u << 19;   // flags in the hoa word
 
-template <int TR, int TC> struct SmemG {
-    static constexpr int W3R = TR + 6, W3C = TC + 6, N3W = W3R * W3C;   // g_out window (active sites only)
-    static constexpr int W2R = TR + 4, W2C = TC + 4, N2W = W2R * W2C;   // act'(z2) -> gz2
-    static constexpr int W1R = TR + 2, W1C = TC + 2, N1W = W1R * W1C;   // act'(z1) -> gz1; cos/sin
-    static constexpr int N3 = TR * TC;
-    // gz2 rows are RS2 apart in LDS: odd, so that the 16 lanes of a conv2^T operand read (one per window row, below)
-    // fall into 16 different banks
-    static constexpr int RS2 = W2C + 1;
-    static constexpr int PS2 = ps_round16(W2R * RS2), PS1 = ps_round(N1W);   // gz2: MFMA operand; gz1: read by four channel lanes per site
-    // active lines of the g_out window: every 4th column (mu = 0) or row (mu = 1)
-    static constexpr int NLC = (W3C + 3) / 4, NLR = (W3R + 3) / 4;
-    static constexpr int NSLOT = cmax_(W3R * NLC, NLR * W3C);           // transform tasks
-    static constexpr int NTT = (NSLOT + 63) / 64 * 64;                  // threads that run them (last waves)
+template <int TR, int TC> struct SmemG : BwdWindows<TR, TC> {
+    using W = BwdWindows<TR, TC>;
+    static constexpr int N3W = W::N3W, W1R = W::W1R, N1W = W::N1W, N3 = W::N3, PS1 = W::PS1, PS2 = W::PS2, NTT = W::NTT;
     static constexpr int GO = 0;                                        // [3][N3W] g(s0, s1, t)
     static constexpr int GZ2 = GO + 3 * N3W;                            // [8][PS2] gz2
     static constexpr int D1 = GZ2 + 8 * PS2;                            // [8][PS1] gz1
@@ -107,13 +96,12 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 4) void k_flow_bwd_gather(const doub
     __builtin_assume(i0 >= 0 && i0 < L && j0 >= 0 && j0 < L && b >= 0 && b < (1 << 20) && A.B > 0 && A.B <= (1 << 20));
     const int rmax = EXACT ? TR : min(TR, L - i0), cmax = EXACT ? TC : min(TC, L - j0);    // own sites inside the lattice
     const double* __restrict__ w = A.wint;
-    const Stash sv = stash_view(A.stash, A.B, b, n);
     // stash planes of this chain (struct Stash), as kernel-argument base + uniform offset
     const unsigned bn = (unsigned)b * (unsigned)n, Bn = (unsigned)A.B * (unsigned)n;       // 32-bit plane offsets: uniform_at()
-    const double* __restrict__ st1 = uniform_at(A.stash, 8u * bn);
-    const double* __restrict__ stc = uniform_at(A.stash, 16u * Bn + 2u * bn);
-    const double* __restrict__ scs = uniform_at(A.stash, 18u * Bn + bn);
-    (void)sv;
+    const StashOff<unsigned> so = stash_off(Bn, bn);
+    const double* __restrict__ st1 = uniform_at(A.stash, so.d1);
+    const double* __restrict__ stc = uniform_at(A.stash, so.tc);
+    const double* __restrict__ scs = uniform_at(A.stash, so.cs);
     // training outputs of this chain (kernels.h: FlowLayerArgs::gz)
     double* const gz2o = has_gz ? A0.gz + (size_t)b * 17 * n : nullptr;
     double* const gz1o = has_gz ? gz2o + (size_t)8 * n : nullptr;
@@ -140,29 +128,15 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 4) void k_flow_bwd_gather(const doub
     // (1) transform tasks on the last waves: active site `a` of the tile+3 window, both mixture components
     const int ta = tid - (NT - S::NTT);
     const int c0 = (off - (j0 - 3)) & 3, r0 = (off - (i0 - 3)) & 3;    // first active column / row of the window
-    int tr3 = 0, tc3 = 0;
-    bool ttask = false;
-    if (ta >= 0) {
-        if (mu == 0) { tr3 = fdiv<S::NLC>(ta); tc3 = c0 + 4 * (ta - tr3 * S::NLC); ttask = tr3 < S::W3R && tc3 < W3C; }
-        else { const int m = fdiv<W3C>(ta); tc3 = ta - m * W3C; tr3 = r0 + 4 * m; ttask = tr3 < S::W3R; }
-        if (!ttask) { tr3 = 3; tc3 = 3; }                                // any valid site
-    } else { tr3 = 3; tc3 = 3; }
-    typedef double double2_t __attribute__((ext_vector_type(2)));
-    auto ldu2 = [](const double* base, unsigned idx) {               // 16-byte load, scalar base + 32-bit element offset
-        const double2_t* p = reinterpret_cast<const double2_t*>(reinterpret_cast<const char*>(base) + idx * 8u);
-        return *p;
-    };
+    int tr3, tc3;
+    const bool ttask = transform_task<S>(ta, mu, c0, r0, tr3, tc3);
     double tcv[4 * NMIX], ag[2];
     const double cb = has_glogj ? A0.glogj[b] : A.glogj_const;
     {
         const int i = wi(tr3 - 3), j = WJ(tc3 - 3);
         // wave-uniform base + 32-bit per-lane offset everywhere: the address costs no VALU op per load
         const unsigned ia = (unsigned)stash_active_idx(i, j, L, mu);
-#pragma unroll
-        for (int q = 0; q < 4 * NMIX; q += 2) {                             // [k][n/4][A B C E] (struct Stash): 16 bytes per load
-            const double2_t t2 = ldu2(stc + (size_t)(q >> 2) * n, ia * 4u + (q & 3));
-            tcv[q] = t2.x; tcv[q + 1] = t2.y;
-        }
+        transform_coeffs(stc, n, ia, tcv);
         // upstream gradient: a link field (first layer of a standalone call) or the plaquette-gradient field
         const double* gsrc = uniform_at(A.up_gp, bn);
         if (has_uplink) {                      // a real branch (the empty asm keeps it one): the rarely used pointer is fetched from the
@@ -223,44 +197,29 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 4) void k_flow_bwd_gather(const doub
         const int goA = !c3live ? 0 : mu == 0 ? mul24(wi(c3r - 2), 3 * (L >> 2)) + lx : mul24(lx, L) + WJ(c3c - 2);
         const int goB = !c3live ? 0 : mu == 0 ? mul24(wi(c3r + W2R / 2 - 2), 3 * (L >> 2)) + lx : mul24(lx, L) + WJ(c3c + W2C / 2 - 2);
         // channel-minor stash (struct Stash): the task's four channels of a site are 32 contiguous bytes
-        const double* pl = uniform_at(A.stash, 8u * (Bn + bn) + (unsigned)(c3half * 4));
+        const double* pl = uniform_at(A.stash, so.d2 + (unsigned)(c3half * 4));
         const unsigned oA = ft_off32((unsigned)goA * 8u), oB = ft_off32((unsigned)goB * 8u);       // byte offsets of the two records
-        auto ldu2o = [](const double* base, unsigned o) {
-            const double2_t* p = reinterpret_cast<const double2_t*>(reinterpret_cast<const char*>(base) + o);
-            return *p;
-        };
 #pragma unroll
         for (int k = 0; k < 4; k += 2) {
             const double2_t va = ldu2o(pl + k, oA), vb = ldu2o(pl + k, oB);
             d2v[0][k] = va.x; d2v[0][k + 1] = va.y; d2v[1][k] = vb.x; d2v[1][k + 1] = vb.y;
         }
     }
-    // conv2^T pairs its output sites ACROSS the stripe lines -- columns (c, c + 1) of one row for mu = 0, rows (r, r + 1)
-    // of one column for mu = 1 -- so the pair's input window is four consecutive lines of gz2, exactly one of which is
-    // dead (conv3^T wrote zeros there): its six K steps are skipped, 18 of 24 remain.  Which of the four it is depends on
-    // the parity of the pair's position u across the lines only, so an MFMA tile holds pairs of ONE parity:
-    //     tiles 0 .. NU-1:  u = tile, positions v = 0 .. 15 along the lines        (NU = 9 pairs across, NV = 18 along)
-    //     tiles NU, NU+1:   the remaining v = 16, 17 of the even / of the odd u
-    // The epilogue's lane (g = lane >> 4, i = lane & 15) of tile T = wave + 8 it owns pair i of the tile, channels
-    // 2 g and 2 g + 1, both sites of the pair.
-    static_assert(TR == 16 && TC == 16, "conv2^T tile map: 16 positions along the lines + 2");
-    constexpr int NU = W1C / 2, NTILE1 = NU + 2, NIT1 = (NTILE1 + NW - 1) / NW;
-    static_assert(NIT1 == 2 && W1R == W1C, "two rounds of conv2^T tiles");
-    int pu[NIT1], pv[NIT1];                                              // pair position (across, along); rows / columns of site 0:
-    bool pok[NIT1];                                                      //   mu = 0: (pv, 2 pu)   mu = 1: (2 pu, pv)   in tile+1 coordinates
+    // conv2^T tile map, the act'(z1) of its epilogue lanes (flow_bwd_common.h Conv2TMap)
+    static_assert(TR == 16 && TC == 16 && W1R == W1C, "conv2^T tile map: 16 positions along the lines + 2");
+    using C2 = Conv2TMap<W1C>;
+    constexpr int NTILE1 = C2::NTILE1, NIT1 = C2::NIT1;
+    int pu[NIT1], pv[NIT1];
+    bool pok[NIT1];
     double d1v[NIT1][4];
 #pragma unroll
     for (int it = 0; it < NIT1; ++it) {
-        const int T = wave + NW * it, i = lane & 15;
-        if (T < NU) { pu[it] = T; pv[it] = i; pok[it] = true; }
-        else { pu[it] = 2 * (i >> 1) + (T - NU); pv[it] = 16 + (i & 1); pok[it] = T < NTILE1 && pu[it] < NU; if (!pok[it]) { pu[it] = 0; pv[it] = 0; } }
+        C2::pair(wave, lane, it, pu[it], pv[it], pok[it]);
         const int ra = mu == 0 ? pv[it] : 2 * pu[it], ca = mu == 0 ? 2 * pu[it] : pv[it];
         // mu = 0: the act'(z1) plane is stored transposed (flow_mfma_common.h): site index j L + i
         const int ga = mu == 0 ? mul24(WJ(ca - 1), L) + wi(ra - 1) : WI(ra - 1) + WJ(ca - 1);
         const int gb = mu == 0 ? mul24(WJ(ca), L) + wi(ra - 1) : WI(ra) + WJ(ca - 1);
-        const unsigned og = 2u * (unsigned)(lane >> 4);                      // channels 2 g, 2 g + 1: one 16-byte load per site
-        const double2_t va = ldu2(st1, (unsigned)ga * 8u + og), vb = ldu2(st1, (unsigned)gb * 8u + og);
-        d1v[it][0] = va.x; d1v[it][1] = va.y; d1v[it][2] = vb.x; d1v[it][3] = vb.y;
+        conv2t_d1_load(st1, ga, gb, lane, d1v[it]);
     }
     __builtin_amdgcn_sched_barrier(0);
 
@@ -366,24 +325,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 4) void k_flow_bwd_gather(const doub
         for (int it = 0; it < NIT1; ++it) {
             const int T = wave + NW * it;
             if (T >= NTILE1) break;
-            const int kd = (kd0 + 2 * (T < NU ? T & 1 : T - NU)) & 3;              // wave-uniform
+            const int kd = C2::dead_line(kd0, T);                                  // wave-uniform
             const double* a0 = sGZ2 + g * PS2 + (mu == 0 ? pv[it] * RS2 + 2 * pu[it] : 2 * pu[it] * RS2 + pv[it]);
-            double4_t acc;
-            if (mu == 0) {
-                switch (kd) {
-                    case 0: acc = conv2t_tile<KConv2Col, 4, 0, RS2, PS2>(wp, a0); break;
-                    case 1: acc = conv2t_tile<KConv2Col, 4, 1, RS2, PS2>(wp, a0); break;
-                    case 2: acc = conv2t_tile<KConv2Col, 4, 2, RS2, PS2>(wp, a0); break;
-                    default: acc = conv2t_tile<KConv2Col, 4, 3, RS2, PS2>(wp, a0); break;
-                }
-            } else {
-                switch (kd) {
-                    case 0: acc = conv2t_tile<KConv2Row, 3, 0, RS2, PS2>(wp, a0); break;
-                    case 1: acc = conv2t_tile<KConv2Row, 3, 1, RS2, PS2>(wp, a0); break;
-                    case 2: acc = conv2t_tile<KConv2Row, 3, 2, RS2, PS2>(wp, a0); break;
-                    default: acc = conv2t_tile<KConv2Row, 3, 3, RS2, PS2>(wp, a0); break;
-                }
-            }
+            const double4_t acc = conv2t_dead_line<RS2, PS2>(mu, kd, wp, a0);
 #ifdef FT_DIAG      // slots 6..9: wave 0 after the MFMAs / the epilogue of its two tiles; 10, 11: wave 4 (one tile)
             if (dbg && (wave == 0 || wave == 4)) { asm volatile("" :: "v"(acc[0]), "v"(acc[1]), "v"(acc[2]), "v"(acc[3])); stampx(dbg + (wave == 0 ? 6 + 2 * it : 10)); }
 #endif
@@ -406,19 +350,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 4) void k_flow_bwd_gather(const doub
 #endif
         }
     }
-    // conv1^T's 18 weights of this wave's hidden channel: scalar loads from the weight block (constant address space)
-    typedef const double __attribute__((address_space(4))) * cdptr;
+    // conv1^T's 18 weights of this wave's hidden channel: scalar loads from the weight block
     double w0s[18];
-    {
-        cdptr wq = (cdptr)(size_t)(w + (mu == 0 ? WBWD1 : WBWD) + LB_W0 + wave * 18);
-        // wide scalar loads written out (8 + 8 + 2 doubles): the merging pass is off for this kernel (FT_LDS_B64)
-        typedef double double8c_t __attribute__((ext_vector_type(8)));
-        typedef const double8c_t __attribute__((address_space(4))) * cd8ptr;
-        const double8c_t va = *(cd8ptr)(wq), vb = *(cd8ptr)(wq + 8);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { w0s[k] = va[k]; w0s[8 + k] = vb[k]; }
-        w0s[16] = wq[16]; w0s[17] = wq[17];
-    }
+    conv1t_weights(w + (mu == 0 ? WBWD1 : WBWD) + LB_W0 + wave * 18, w0s);
     lds_barrier();
     STAMP(3);
 #ifdef FT_DIAG
@@ -430,21 +364,15 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 4) void k_flow_bwd_gather(const doub
     // (scalar loads, requested ahead of the barrier above) and the gz1 reads of a wave stay inside ONE plane; the sum
     // over the channels goes through LDS (the gz2 planes are free by now)
     static_assert(NW == 8 && N3 / 2 == 2 * 64 && 8 * 2 * (N3 / 2) <= 8 * PS2, "one wave per hidden channel, two sites per lane");
+    // (k_flow_bwd_train carries the same stage: see there)
     double* sPart = sGZ2;                                                // [8 co][2: cos, sin][N3 / 2]
-    auto frozen_site = [&](int f, int& r, int& c) {
-        // mu = 0: 16 rows x 8 frozen columns, f = row + 16 h (a 32-lane group then holds an odd and an even column of 16
-        // rows: 32 different banks at row stride 18); mu = 1: 8 frozen rows x 16 columns, f = column + 16 hh
-        const int h = f >> 4, q = f & 15;
-        if (mu == 0) { r = q; c = 4 * (h >> 1) + ((off + 1 + (h & 1)) & 3); }
-        else { c = q; r = 4 * (h >> 1) + ((off + 1 + (h & 1)) & 3); }
-    };
     {
         const int co = wave;
 #pragma unroll
         for (int sx = 0; sx < 2; ++sx) {
             const int f = lane + 64 * sx;
             int r, c;
-            frozen_site(f, r, c);
+            frozen_site<TC>(f, mu, off, r, c);
             const double* gz = sD1 + co * PS1 + r * W1C + c;            // window coordinates (r + 2 - ky, c + 2 - kx)
             double gv[9], gc = 0.0, gs = 0.0;
 #pragma unroll
@@ -458,7 +386,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 4) void k_flow_bwd_gather(const doub
     lds_barrier();
     if (tid < N3 / 2) {
         int r, c;
-        frozen_site(tid, r, c);
+        frozen_site<TC>(tid, mu, off, r, c);
         double gct = 0.0, gst = 0.0;
 #pragma unroll
         for (int co = 0; co < 8; ++co) { gct += sPart[(co * 2 + 0) * (N3 / 2) + tid]; gst += sPart[(co * 2 + 1) * (N3 / 2) + tid]; }

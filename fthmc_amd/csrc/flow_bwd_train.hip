@@ -44,7 +44,7 @@
 // Built for the tiled-exactly shapes (L a power of two >= 32: every BASELINE training shape); anything else keeps the
 // two-kernel form.  Reference: loss.backward() of fthmc/train.py:191-210 through GaugeEquivCouplingLayer.forward
 // (fthmc/utils/layers.py:196-202,348-371) and make_conv_net (:138-167).
-#include "flow_mfma_common.h"
+#include "flow_bwd_common.h"
 #include "flow_transform.h"
 
 namespace {
@@ -52,23 +52,11 @@ namespace {
 using namespace fthmc;
 using namespace fthmc_flow;
 
-typedef double double2_t __attribute__((ext_vector_type(2)));
-constexpr int cmax_(int a, int b) { return a > b ? a : b; }
-
-template <int TR, int TC> struct SmemT {
-    // the backward's windows (flow_bwd_gather.hip SmemG)
-    static constexpr int W3R = TR + 6, W3C = TC + 6, N3W = W3R * W3C;   // g_out window (active sites only)
-    static constexpr int W2R = TR + 4, W2C = TC + 4, N2W = W2R * W2C;   // act'(z2) -> gz2
-    static constexpr int W1R = TR + 2, W1C = TC + 2, N1W = W1R * W1C;   // act'(z1) -> gz1; h1, h2, (cos, sin)
-    static constexpr int N3 = TR * TC, NA = N3 / 4;
-    static constexpr int RS2 = W2C + 1;
-    static constexpr int PS2 = ps_round16(W2R * RS2), PS1 = ps_round(N1W);
-    // h1 / h2 / net-input planes on tile+1 (+ one row of slack): stride = 12 (mod 32) as in k_flow_wgrad (its B operand reads
-    // and the fill's writes are free of bank conflicts)
-    static constexpr int NH = N1W, PSH = ((NH + W1C - 12 + 31) / 32) * 32 + 12;
-    static constexpr int NLC = (W3C + 3) / 4, NLR = (W3R + 3) / 4;
-    static constexpr int NSLOT = cmax_(W3R * NLC, NLR * W3C);           // transform tasks
-    static constexpr int NTT = (NSLOT + 63) / 64 * 64;                  // threads that run them (last waves)
+template <int TR, int TC> struct SmemT : BwdWindows<TR, TC>, WalkRed {
+    using W = BwdWindows<TR, TC>;
+    static constexpr int N3W = W::N3W, W1R = W::W1R, W1C = W::W1C, N1W = W::N1W, N3 = W::N3, NA = N3 / 4, PS1 = W::PS1, PS2 = W::PS2, NTT = W::NTT;
+    // h1 / h2 / net-input planes on tile+1 (+ one row of slack), stride as in k_flow_wgrad (psh_round)
+    static constexpr int NH = N1W, PSH = psh_round(NH, W1C);
     static constexpr int GO = 0;                                        // [3][N3W] g(s0, s1, t) on the tile+3 window
     static constexpr int GOC = GO + 3 * N3W;                            // [2][3][NA] the same at the own active sites, task order; one buffer per item parity
     static constexpr int GZ2 = GOC + 2 * 3 * NA;                        // [8][PS2] gz2; later conv1^T's channel partials
@@ -80,38 +68,11 @@ template <int TR, int TC> struct SmemT {
     static constexpr int HA1 = T3 + LT3_SIZE;                           // [8][PSH] h1 window
     static constexpr int HA2 = HA1 + 8 * PSH;                           // [8][PSH] h2 window
     static constexpr int WALK = HA2 + 8 * PSH;
-    // after the walk, over the planes: the waves' accumulators [8][4 tiles][4][64], bias lane sums [8][2][8], conv3 sums [432]
-    static constexpr int RED = 0, RBS = RED + 8 * 4 * 4 * 64, RC3 = RBS + 8 * 2 * 8, RSIZE = RC3 + 432;
-    static constexpr int SIZE = WALK > RSIZE ? WALK : RSIZE;
+    static constexpr int SIZE = WALK > RSIZE ? WALK : RSIZE;                 // after the walk the reduction's buffers lie over the planes (WalkRed)
     static_assert(TR == 16 && TC == 16 && NA == 64, "thread maps: conv2^T tile map, K split of the weight-gradient GEMMs, one wave per g_out plane");
     static_assert(W1R % 2 == 0 && NTT <= NT && 2 * N3 <= NT && N1W <= NT && GOC % 2 == 0, "thread maps");
     static_assert(SIZE * 8 <= 160 * 1024, "one workgroup per CU (160 KB of LDS on gfx950)");
 };
-
-// conv3 (8 -> 3, active sites only) weight gradient: thread = (output (co, ci, tap), half of the active sites); the 32 sites of
-// the half at compile-time offsets from the thread's base (k_flow_wgrad's loop)
-template <int MU, int TC, int W1C>
-__device__ __forceinline__ void conv3_acc(const double* __restrict__ pg, const double* __restrict__ ph, double (&acc)[4]) {
-    // in batches of eight sites: the eight h2 reads and the four 16-byte g_out reads of a batch are issued together, then its
-    // eight FMAs (left to itself the scheduler of the mu = 0 instance put a full LDS wait behind every single read: 2.2 k cycles
-    // for this loop against 1.0 k in the mu = 1 instance with the same instructions)
-#pragma unroll
-    for (int a0 = 0; a0 < 32; a0 += 8) {
-        double2_t g2[4];
-        double hv[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) g2[e] = *reinterpret_cast<const double2_t*>(pg + a0 + 2 * e);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int aa = a0 + e;
-            hv[e] = ph[MU == 0 ? (aa / (TC / 4)) * W1C + 4 * (aa % (TC / 4)) : 4 * (aa / TC) * W1C + aa % TC];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e & 3] = fma((e & 1) ? g2[e >> 1].y : g2[e >> 1].x, hv[e], acc[e & 3]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 template <int TR, int TC, int MU>
 __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerArgs A) {
@@ -136,24 +97,14 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
     const int nti_ = L / TR, ntj_ = L / TC, ntiles = nti_ * ntj_;
     (void)nti_;
 
-    // ---- the walk (k_flow_wgrad's): the ns workgroups resident together on an XCD stand on ns consecutive items at every step
-    //      and move on by ns, so that the halo lines neighbouring tiles share are fetched once into the XCD's L2.
-    //      grid: x = 8 XCDs (blockIdx.x % 8) x rounds x ns; round kr = xcd * R + r covers items [kr * tpw * ns, (kr + 1) * tpw * ns)
-    const int items = A.B * ntiles, tpw = A.tpw, ns = A.wg_ns;
-    const int KR = (items + tpw * ns - 1) / (tpw * ns), R = (KR + 7) >> 3;
-    const int idx = (int)blockIdx.x >> 3, r_ = idx / ns, s_ = idx - r_ * ns, kr = ((int)blockIdx.x & 7) * R + r_;
-    const int first = kr * tpw * ns + s_;
-    if (r_ >= R || first >= items) return;
-    const int grp = kr * ns + s_;                                         // valid groups are a prefix of this numbering
-    const int nwalk = min(tpw, (items - first + ns - 1) / ns);
+    // ---- the walk (flow_bwd_common.h walk_of_block): nwalk items from `first` on, ns apart; row grp of the partials
+    Walk wk;
+    if (!walk_of_block(A, ntiles, wk)) return;
+    const int first = wk.first, grp = wk.grp, nwalk = wk.nwalk, ns = wk.ns;
     double* gw0 = A.gw_part + (size_t)grp * FLOW_GW_STRIDE;              // the group's partial
     const double* __restrict__ w = A.wint;
     const double cb = A.glogj_const;
     const unsigned Bn = (unsigned)A.B * (unsigned)n;
-    auto ldu2 = [](const double* base, unsigned idx_) {                  // 16-byte load, scalar base + 32-bit element offset
-        const double2_t* p = reinterpret_cast<const double2_t*>(reinterpret_cast<const char*>(base) + idx_ * 8u);
-        return *p;
-    };
 
     // ---- once per walk: the layer's backward weight block, the zeros behind the windows (read by discarded ky = 3 columns only)
     {
@@ -180,29 +131,21 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
     // k_flow_bwd_gather, two workgroups per CU on a saturated DP pipe, the same change LOST 1 %: profiles/r06_ab_bwd_conv3t_mfma.txt)
     using C3 = Conv3T<mu, W2R>;
     static_assert(W2R == W2C && C3::NIT == 2 && N2W <= NT, "square window, two rounds of conv3^T tiles");
-    // conv2^T tile map (flow_bwd_gather.hip): tiles 0 .. NU-1: u = tile, v = 0 .. 15; tiles NU, NU+1: v = 16, 17 of the even / odd u
-    constexpr int NU = W1C / 2, NTILE1 = NU + 2, NIT1 = (NTILE1 + NW - 1) / NW;
-    static_assert(NIT1 == 2 && W1R == W1C, "two rounds of conv2^T tiles");
+    // conv2^T tile map (flow_bwd_common.h Conv2TMap)
+    using C2 = Conv2TMap<W1C>;
+    constexpr int NTILE1 = C2::NTILE1, NIT1 = C2::NIT1;
+    static_assert(W1R == W1C, "square window");
     int pu[NIT1], pv[NIT1];
     bool pok[NIT1];
 #pragma unroll
-    for (int it = 0; it < NIT1; ++it) {
-        const int T = wave + NW * it, i = lane & 15;
-        if (T < NU) { pu[it] = T; pv[it] = i; pok[it] = true; }
-        else { pu[it] = 2 * (i >> 1) + (T - NU); pv[it] = 16 + (i & 1); pok[it] = T < NTILE1 && pu[it] < NU; if (!pok[it]) { pu[it] = 0; pv[it] = 0; } }
-    }
+    for (int it = 0; it < NIT1; ++it) C2::pair(wave, lane, it, pu[it], pv[it], pok[it]);
     // h1 / h2 windows: tasks (window site, channel quad) in two rounds; the (cos, sin) window: thread = window site
-    constexpr int NITH = 2 * NH, NRH = (NITH + NT - 1) / NT;
-    int hwr[NRH], hwc[NRH], hwq[NRH], hls[NRH];
-#pragma unroll
-    for (int k = 0; k < NRH; ++k) {
-        const int t = min(tid + k * NT, NITH - 1), ws = t >> 1;
-        hwq[k] = t & 1; hwr[k] = fdiv<W1C>(ws); hwc[k] = ws - hwr[k] * W1C;
-        hls[k] = tid + k * NT < NITH ? (4 * hwq[k]) * PSH + hwr[k] * W1C + hwc[k] : -1;
-    }
-    const int fwr = fdiv<W1C>(min(tid, NH - 1)), fwc = min(tid, NH - 1) - fwr * W1C;
-    const bool fwtask = tid < NH;
-    const bool fwfrozen = fwtask && ((((mu == 0 ? fwc : fwr) - 1 - off) & 3) == 1 || (((mu == 0 ? fwc : fwr) - 1 - off) & 3) == 2);   // tile origins are multiples of 4
+    using HW = HWindow<W1C, NH, PSH>;
+    constexpr int NRH = HW::NRH;
+    const HW hw(tid);
+    int fwr, fwc;
+    bool fwtask, fwfrozen;
+    netin_task<W1C, NH>(tid, mu, off, fwr, fwc, fwtask, fwfrozen);
     // own sites (final store)
     const int orr = fdiv<TC>(tid), occ = tid - orr * TC;
     const bool ovalid = tid < N3;
@@ -210,8 +153,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
     const int wg_ = lane >> 4, wi_ = lane & 15, wco = wi_ & 7, wdy = wi_ >> 3;
     // conv1 (row pairs, all sixteen columns of a walk row in four K steps):
     const int pa1 = wco * PS1 + (1 - wdy) * W1C + 1 + wg_;                // gz1 of the tile's site (walk row - dy, 4 cs + g) in the tile+1 plane
-    auto pbf = [&](int ncol, int ncols) { const int nc = ncol < ncols ? ncol : 0, ci = nc / 6, kx = (nc % 6) >> 1, kyb = nc & 1; return ci * PSH + 2 * kyb * W1C + kx + wg_; };
-    const int pb3 = pbf(wi_, 12);
+    const int pb3 = wgrad_bcol<W1C, PSH>(wi_, 12, wg_);
     // conv2: gz2 is an exact 0 on every fourth stripe line (no active site within reach), so its GEMM walks the LIVE lines
     // only -- twelve of a tile's sixteen, three K steps where the dense walk takes four (153 MFMAs per item instead of 204) --
     // and pairs the shifted copies of gz2 ALONG the lines, so that the K lanes run across them: mu = 0 (lines = columns) as
@@ -235,13 +177,8 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
 
     // ---- what does not depend on the item: tile origins are multiples of 16, so the stripe phase of every window is the layer's
     const int c0 = (off + 3) & 3, r0 = c0;                                 // first active column / row of the tile+3 window
-    int tr3 = 3, tc3 = 3;                                                  // transform task: active site (tr3, tc3) of the tile+3 window
-    bool ttask = false;
-    if (ta >= 0) {
-        if (mu == 0) { tr3 = fdiv<S::NLC>(ta); tc3 = c0 + 4 * (ta - tr3 * S::NLC); ttask = tr3 < S::W3R && tc3 < W3C; }
-        else { const int m = fdiv<W3C>(ta); tc3 = ta - m * W3C; tr3 = r0 + 4 * m; ttask = tr3 < S::W3R; }
-        if (!ttask) { tr3 = 3; tc3 = 3; }                                    // any valid site
-    }
+    int tr3, tc3;                                                          // transform task: active site (tr3, tc3) of the tile+3 window
+    const bool ttask = transform_task<S>(ta, mu, c0, r0, tr3, tc3);
     const unsigned wmagic = (unsigned)(L - 1);
 
     // ---- an item's operands, in registers.  Every load is unconditional, from a clamped address; each GROUP of them is issued for
@@ -257,25 +194,23 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
     auto item_at = [&](int k) {                                            // uniform: scalar divisions
         const int item = first + (k < nwalk ? k : nwalk - 1) * ns;
         Item q;
-        q.b = item / ntiles;
-        const int tl = item - q.b * ntiles, ti = tl / ntj_;
-        q.i0 = ti * TR; q.j0 = (tl - ti * ntj_) * TC;
+        int ti, tj;
+        item_coords(item, ntiles, ntj_, q.b, ti, tj);
+        q.i0 = ti * TR; q.j0 = tj * TC;
         return q;
     };
 #define WI_(q, k) mul24(wrap_line<true, true>((q).i0 + (k), L, wmagic), L)
 #define wi_(q, k) wrap_line<true, true>((q).i0 + (k), L, wmagic)
 #define WJ_(q, k) wrap_line<true, true>((q).j0 + (k), L, wmagic)
+    auto planes_of = [&](const Item& q) { return stash_off(Bn, (unsigned)q.b * (unsigned)n); };   // struct Stash
     auto issue_A = [&](const Item& q) {
+        const StashOff<unsigned> so = planes_of(q);
         const unsigned bn = (unsigned)q.b * (unsigned)n;
-        const double* __restrict__ stc = uniform_at(A.stash, 16u * Bn + 2u * bn);
-        const double* __restrict__ scs = uniform_at(A.stash, 18u * Bn + bn);
+        const double* __restrict__ stc = uniform_at(A.stash, so.tc);
+        const double* __restrict__ scs = uniform_at(A.stash, so.cs);
         const int i = wi_(q, tr3 - 3), j = WJ_(q, tc3 - 3);
         const unsigned ia = (unsigned)stash_active_idx(i, j, L, mu);
-#pragma unroll
-        for (int e = 0; e < 4 * NMIX; e += 2) {                              // [k][n/4][A B C E] (struct Stash): 16 bytes per load
-            const double2_t t2 = ldu2(stc + (size_t)(e >> 2) * n, ia * 4u + (e & 3));
-            tcv[e] = t2.x; tcv[e + 1] = t2.y;
-        }
+        transform_coeffs(stc, n, ia, tcv);
         const double* gsrc = uniform_at(A.up_gp, bn);                        // upstream gradient: the plaquette-gradient field
         const int iL = mul24(i, L);
         ag[0] = ldu(gsrc, (unsigned)(iL + j));
@@ -288,20 +223,17 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
     auto issue_G = [&](const Item& q) {
         gpin = ldu_j(uniform_at(A.up_gp, (unsigned)q.b * (unsigned)n), ovalid ? (unsigned)(mul24(q.i0 + orr, L) + q.j0 + occ) : 0u);
     };
-    auto issue_H = [&](const Item& q, int plane, double2_t (&hv)[NRH][2]) {  // plane 19: h1, 27: h2 (struct Stash)
+    // own statement of the h1 / h2 plane bases (stash_off's .h1, .h2: through it this kernel spilled two more SGPRs): plane 19: h1, 27: h2
+    auto issue_H = [&](const Item& q, int plane, double2_t (&hv)[NRH][2]) {
         const double* __restrict__ sh = uniform_at(A.stash, (unsigned)plane * Bn + 8u * (unsigned)q.b * (unsigned)n);
 #pragma unroll
         for (int k = 0; k < NRH; ++k) {
-            const unsigned hat = (unsigned)(WI_(q, hwr[k] - 1) + WJ_(q, hwc[k] - 1)) * 8u + 4u * (unsigned)hwq[k];
+            const unsigned hat = (unsigned)(WI_(q, hw.hwr[k] - 1) + WJ_(q, hw.hwc[k] - 1)) * 8u + 4u * (unsigned)hw.hwq[k];
             hv[k][0] = ldu2(sh, hat); hv[k][1] = ldu2(sh, hat + 2);
         }
     };
     auto issue_D2 = [&](const Item& q) {
-        const double* pl = uniform_at(A.stash, 8u * (Bn + (unsigned)q.b * (unsigned)n));
-        auto ldu2o = [](const double* base, unsigned o) {
-            const double2_t* p = reinterpret_cast<const double2_t*>(reinterpret_cast<const char*>(base) + o);
-            return *p;
-        };
+        const double* pl = uniform_at(A.stash, planes_of(q).d2);
 #pragma unroll
         for (int e = 0; e < C3::NIT; ++e) {
             const C3 P(wave + NW * e, lane, c0);
@@ -317,16 +249,14 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
         }
     };
     auto issue_D1 = [&](const Item& q) {
-        const double* __restrict__ st1 = uniform_at(A.stash, 8u * (unsigned)q.b * (unsigned)n);
+        const double* __restrict__ st1 = uniform_at(A.stash, planes_of(q).d1);
 #pragma unroll
         for (int e = 0; e < NIT1; ++e) {
             const int ra = mu == 0 ? pv[e] : 2 * pu[e], ca = mu == 0 ? 2 * pu[e] : pv[e];
             // mu = 0: the act'(z1) plane is stored transposed (flow_mfma_common.h): site index j L + i
             const int ga = mu == 0 ? mul24(WJ_(q, ca - 1), L) + wi_(q, ra - 1) : WI_(q, ra - 1) + WJ_(q, ca - 1);
             const int gb = mu == 0 ? mul24(WJ_(q, ca), L) + wi_(q, ra - 1) : WI_(q, ra) + WJ_(q, ca - 1);
-            const unsigned og = 2u * (unsigned)(lane >> 4);                  // channels 2 g, 2 g + 1: one 16-byte load per site
-            const double2_t va = ldu2(st1, (unsigned)ga * 8u + og), vb = ldu2(st1, (unsigned)gb * 8u + og);
-            d1v[e][0] = va.x; d1v[e][1] = va.y; d1v[e][2] = vb.x; d1v[e][3] = vb.y;
+            conv2t_d1_load(st1, ga, gb, lane, d1v[e]);
         }
     };
     {
@@ -337,21 +267,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
     // conv3's weight gradient of an item (VALU; g_out at the own active sites and the h2 window): runs in the FIRST stage of
     // the next item, beside the transform adjoint that keeps three of the eight waves busy there (its planes outlive the item:
     // g_out compact per item parity, the h2 window until the next item's third stage)
-    auto conv3_wgrad = [&](const double* sGOCi) {
-        if (tid < 432) {                                                 // gw2[co][ci][tap] += sum over the own active sites of g_out[co] h2[ci][site + tap]
-            const int hf = tid >= 216 ? 1 : 0, t = tid - 216 * hf;
-            const int co = fdiv<9>(fdiv<8>(t)), ci = fdiv<9>(t) & 7, tap = t - fdiv<9>(t) * 9, ky = fdiv<3>(tap), kx = tap - 3 * ky;
-            const double* pg = sGOCi + co * NA + hf * (NA / 2);
-            const double* ph = sHA2 + ci * PSH + ky * W1C + kx;          // h2 at own (r, c) + (ky - 1, kx - 1): window index (r + ky) W1C + c + kx
-            double c3[4] = {0.0, 0.0, 0.0, 0.0};
-            if (mu == 0) conv3_acc<0, TC, W1C>(pg, ph + hf * (NA / 2 / (TC / 4)) * W1C + off, c3);
-            else         conv3_acc<1, TC, W1C>(pg, ph + (off + 4 * hf * (NA / 2 / TC)) * W1C, c3);
-            acc3[0] += (c3[0] + c3[1]) + (c3[2] + c3[3]);
-        } else if (tid >= 448) {                                         // b3: the eighth wave sums the three g_out planes
-#pragma unroll
-            for (int k = 0; k < 3; ++k) acc3[k] += sGOCi[k * NA + lane];
-        }
-    };
+    auto conv3_wgrad = [&](const double* sGOCi) { conv3_wgrad_task<TC, W1C, PSH, NA, true>(sGOCi, sHA2, tid, lane, mu, off, acc3); };
 #ifdef FT_BT_STAMPS       // measurement builds only: cycles per stage, summed over the walk, printed by two workgroups
     long long stc_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, stl_ = (long long)__builtin_readcyclecounter();
 #define BT_STAMP(k) do { const long long t_ = (long long)__builtin_readcyclecounter(); stc_[k] += t_ - stl_; stl_ = t_; } while (0)
@@ -416,7 +332,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
         }
 #pragma unroll
         for (int k = 0; k < NRH; ++k)
-            if (hls[k] >= 0) { double* p1 = sHA1 + hls[k]; p1[0] = hv1[k][0].x; p1[PSH] = hv1[k][0].y; p1[2 * PSH] = hv1[k][1].x; p1[3 * PSH] = hv1[k][1].y; }
+            if (hw.hls[k] >= 0) h_quad_store<PSH>(sHA1 + hw.hls[k], hv1[k]);
         __builtin_amdgcn_sched_barrier(0);
         issue_D2(nxt); issue_H(nxt, 19, hv1);
         lds_barrier();
@@ -431,24 +347,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
             for (int q = 0; q < NIT1; ++q) {
                 const int T = wave + NW * q;
                 if (T >= NTILE1) break;
-                const int kd = (kd0 + 2 * (T < NU ? T & 1 : T - NU)) & 3;              // wave-uniform
+                const int kd = C2::dead_line(kd0, T);                                  // wave-uniform
                 const double* a0 = sGZ2 + g * PS2 + (mu == 0 ? pv[q] * RS2 + 2 * pu[q] : 2 * pu[q] * RS2 + pv[q]);
-                double4_t ac;
-                if (mu == 0) {
-                    switch (kd) {
-                        case 0: ac = conv2t_tile<KConv2Col, 4, 0, RS2, PS2>(wp, a0); break;
-                        case 1: ac = conv2t_tile<KConv2Col, 4, 1, RS2, PS2>(wp, a0); break;
-                        case 2: ac = conv2t_tile<KConv2Col, 4, 2, RS2, PS2>(wp, a0); break;
-                        default: ac = conv2t_tile<KConv2Col, 4, 3, RS2, PS2>(wp, a0); break;
-                    }
-                } else {
-                    switch (kd) {
-                        case 0: ac = conv2t_tile<KConv2Row, 3, 0, RS2, PS2>(wp, a0); break;
-                        case 1: ac = conv2t_tile<KConv2Row, 3, 1, RS2, PS2>(wp, a0); break;
-                        case 2: ac = conv2t_tile<KConv2Row, 3, 2, RS2, PS2>(wp, a0); break;
-                        default: ac = conv2t_tile<KConv2Row, 3, 3, RS2, PS2>(wp, a0); break;
-                    }
-                }
+                const double4_t ac = conv2t_dead_line<RS2, PS2>(mu, kd, wp, a0);
                 if (pok[q]) {
                     const int ra = mu == 0 ? pv[q] : 2 * pu[q], ca = mu == 0 ? 2 * pu[q] : pv[q];   // site 0; site 1 = next column / row
                     const int ds = mu == 0 ? 1 : W1C;
@@ -489,21 +390,12 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
         }
 #pragma unroll
         for (int k = 0; k < NRH; ++k)
-            if (hls[k] >= 0) { double* p2 = sHA2 + hls[k]; p2[0] = hv2[k][0].x; p2[PSH] = hv2[k][0].y; p2[2 * PSH] = hv2[k][1].x; p2[3 * PSH] = hv2[k][1].y; }
+            if (hw.hls[k] >= 0) h_quad_store<PSH>(sHA2 + hw.hls[k], hv2[k]);
         __builtin_amdgcn_sched_barrier(0);
         issue_H(nxt, 27, hv2);
-        // conv1^T's 18 weights of this wave's hidden channel: scalar loads from the weight block (constant address space)
-        typedef const double __attribute__((address_space(4))) * cdptr;
+        // conv1^T's 18 weights of this wave's hidden channel: scalar loads from the weight block
         double w0s[18];
-        {
-            cdptr wq = (cdptr)(size_t)(w + (mu == 0 ? WBWD1 : WBWD) + LB_W0 + wave * 18);
-            typedef double double8c_t __attribute__((ext_vector_type(8)));
-            typedef const double8c_t __attribute__((address_space(4))) * cd8ptr;
-            const double8c_t va = *(cd8ptr)(wq), vb = *(cd8ptr)(wq + 8);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { w0s[k] = va[k]; w0s[8 + k] = vb[k]; }
-            w0s[16] = wq[16]; w0s[17] = wq[17];
-        }
+        conv1t_weights(w + (mu == 0 ? WBWD1 : WBWD) + LB_W0 + wave * 18, w0s);
         lds_barrier();
         BT_STAMP(3);
 
@@ -511,19 +403,15 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
         //      over the gz2 planes, free by now); conv1's weight gradient (MFMA) from gz1 and the net-input window; conv3's
         //      (VALU) from g_out and the h2 window ----------------------------------------------------------------------
         static_assert(NW == 8 && N3 / 2 == 2 * 64 && 8 * 2 * (N3 / 2) <= 8 * PS2, "one wave per hidden channel, two sites per lane");
+        // (k_flow_bwd_gather's stage, written out in both: as a shared function it cost this kernel six more spilled SGPRs)
         double* sPart = sGZ2;                                                // [8 co][2: cos, sin][N3 / 2]
-        auto frozen_site = [&](int f, int& r, int& c) {
-            const int h = f >> 4, q = f & 15;
-            if (mu == 0) { r = q; c = 4 * (h >> 1) + ((off + 1 + (h & 1)) & 3); }
-            else { c = q; r = 4 * (h >> 1) + ((off + 1 + (h & 1)) & 3); }
-        };
         {
             const int co = wave;
 #pragma unroll
             for (int sx = 0; sx < 2; ++sx) {
                 const int f = lane + 64 * sx;
                 int r, c;
-                frozen_site(f, r, c);
+                frozen_site<TC>(f, mu, off, r, c);
                 const double* gz = sD1 + co * PS1 + r * W1C + c;            // window coordinates (r + 2 - ky, c + 2 - kx)
                 double gv[9], gc = 0.0, gs = 0.0;
 #pragma unroll
@@ -591,53 +479,8 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_flow_bwd_train(FlowLayerAr
 #undef wi_
 #undef WJ_
 
-    // ---- the group's partial: the waves' K slices summed through LDS in a fixed order (k_flow_wgrad's epilogue)
-    lds_barrier();
-    {
-        double* Rr = sm + S::RED; double* BS = sm + S::RBS; double* C3 = sm + S::RC3;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) Rr[((wave * 4 + nt) * 4 + q) * 64 + lane] = acc[nt][q];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {                                    // A rows (co, dy = 0): lanes co + 16 g
-            double v = bsum[k];
-            v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
-            if (lane < 8) BS[(wave * 2 + k) * 8 + lane] = v;
-        }
-        if (tid < 432) C3[tid] = acc3[0];
-        else if (tid >= 448) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double v = ft_wave_sum(acc3[k]);
-                if (lane == 0) gw0[CB2 + k] = v;
-            }
-        }
-        lds_barrier();
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {                                    // element e = (nt, q, lane) = D_nt[row g + 4 q][col i]
-            const int e = tid + NT * h, nt = e >> 8, q = (e >> 6) & 3, ln = e & 63;
-            double v = 0.0;
-#pragma unroll
-            for (int wv = 0; wv < 8; ++wv) v += Rr[wv * 1024 + e];
-            const int g = ln >> 4, i = ln & 15, m = g + 4 * q, co = m & 7, dy = m >> 3;
-            const int ncol = (nt < 3 ? nt * 16 : 0) + i;
-            if (ncol < (nt < 3 ? 48 : 12)) {
-                // conv1 (nt = 3) and conv2 of a mu = 0 layer: columns (ci, kx, kyb), ky = 2 kyb + d; conv2 of a mu = 1 layer: (ci, ky, kxb), kx = 2 kxb + d
-                const bool tr = nt < 3 && mu == 1;
-                const int ci = ncol / 6, ka = (ncol % 6) >> 1, kb2 = 2 * (ncol & 1) + dy;
-                const int ky = tr ? ka : kb2, kx = tr ? kb2 : ka;
-                if (kb2 <= 2) gw0[(nt < 3 ? CW1 + (co * 8 + ci) * 9 : CW0 + (co * 2 + ci) * 9) + ky * 3 + kx] = v;
-            }
-        }
-        if (tid < 16) {
-            double v = 0.0;
-#pragma unroll
-            for (int wv = 0; wv < 8; ++wv) v += BS[wv * 16 + tid];
-            gw0[(tid < 8 ? CB1 : CB0) + (tid & 7)] = v;
-        }
-        if (tid < 216) gw0[CW2 + tid] = C3[tid] + C3[216 + tid];
-    }
+    // ---- the group's partial: the waves' K slices summed through LDS in a fixed order
+    walk_partial<S, mu == 1>(sm, gw0, acc, bsum, acc3, tid, wave);
 }
 
 }  // namespace
@@ -651,9 +494,7 @@ int launch_flow_bwd_train(const FlowLayerArgs& a, hipStream_t s) {
     FlowLayerArgs b = a;
     b.tpw = flow_bwd_train_tpw(a.B, a.L);
     b.wg_ns = flow_bwd_train_ns(a.B, a.L, b.tpw);
-    const int items = a.B * FlowGeom{MG_TR, MG_TC}.ntiles(a.L);
-    const int KR = (items + b.tpw * b.wg_ns - 1) / (b.tpw * b.wg_ns), R = (KR + 7) / 8;
-    const dim3 grid(8 * R * b.wg_ns, 1, 1);
+    const dim3 grid((unsigned)walk_grid_x(walk_items(a.B, a.L), b.tpw, b.wg_ns), 1, 1);
     if (a.mu == 0) hipLaunchKernelGGL((k_flow_bwd_train<MG_TR, MG_TC, 0>), grid, dim3(NT), 0, s, b);
     else hipLaunchKernelGGL((k_flow_bwd_train<MG_TR, MG_TC, 1>), grid, dim3(NT), 0, s, b);
     FT_LAUNCH_CHECK(); return FTHMC_OK;

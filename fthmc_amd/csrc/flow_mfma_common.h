@@ -1,5 +1,5 @@
-// Building blocks shared by the MFMA coupling-layer kernels (flow_fwd.hip, flow_bwd_gather.hip):
-// tile geometry, the implicit-GEMM conv stage, the XCD-aware block map.
+// Building blocks shared by the MFMA coupling-layer kernels (flow_fwd.hip, flow_bwd_gather.hip, flow_bwd_train.hip, flow_wgrad.hip,
+// flow_small.hip): tile geometry, the stash layout, the implicit-GEMM conv stage, the XCD-aware block map.
 #pragma once
 #include "flow_common.h"
 
@@ -46,6 +46,8 @@ namespace fthmc_flow {
 constexpr size_t NT_MIN_BYTES = (size_t)128 << 20;
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
+typedef double double2_t __attribute__((ext_vector_type(2)));
+constexpr int cmax_(int a, int b) { return a > b ? a : b; }
 
 constexpr int NT = 512;                 // threads per workgroup (8 waves)
 constexpr int NW = NT / 64;
@@ -91,6 +93,13 @@ template <class T> __device__ __forceinline__ T* uniform_at(T* base, unsigned of
 #define FT_G __attribute__((address_space(1)))                    // global memory, said in the pointer type (see flow_small.hip: gld / gst)
 __device__ __forceinline__ double ldu(const double* base, unsigned idx) {
     return *(const FT_G double*)((const FT_G char*)base + idx * 8u);
+}
+// 16-byte loads, scalar base + 32-bit element offset (ldu2) / byte offset (ldu2o)
+__device__ __forceinline__ double2_t ldu2(const double* base, unsigned idx) {
+    return *reinterpret_cast<const double2_t*>(reinterpret_cast<const char*>(base) + idx * 8u);
+}
+__device__ __forceinline__ double2_t ldu2o(const double* base, unsigned o) {
+    return *reinterpret_cast<const double2_t*>(reinterpret_cast<const char*>(base) + o);
 }
 // the same for an index that comes out of a branch (idle lanes read element 0): hipcc otherwise carries the ZERO-EXTENDED offset
 // through the join and forms a 64-bit VGPR address per load (v_mov 0 + v_lshl_add_u64); the empty asm pins the 32-bit byte offset
@@ -184,9 +193,11 @@ template <int TR, int TC, int MU = 0, bool AL = false> struct Geom {
 //   h1, h2 [n][8]  hidden activations, channel-minor (training only)
 // = 16 + 2 + 1 = 19 doubles per site and layer (35 with h1, h2): kernels.h flow_stash_doubles().
 struct Stash { double *d1, *d2, *tc, *cs, *h1, *h2; };
-__device__ __forceinline__ Stash stash_view(double* base, int B, int b, int n) {
-    const unsigned bn = (unsigned)b * (unsigned)n, Bn = (unsigned)B * (unsigned)n;     // 35 B n < 2^32: checked by the launchers
-    Stash v;
+// the plane bases of chain b, Bn = B n, bn = b n: the ONE statement of the layout above, as pointers (stash_view) or as element
+// offsets (stash_off: U = unsigned for uniform_at() where the launcher has checked 35 B n < 2^32, size_t for uniform_ptr() elsewhere)
+template <class U> struct StashOff { U d1, d2, tc, cs, h1, h2; };
+template <class V, class T, class U> __device__ __forceinline__ V stash_planes(T base, U Bn, U bn) {
+    V v;
     v.d1 = base + (size_t)(8u * bn);
     v.d2 = base + (size_t)(8u * (Bn + bn));
     v.tc = base + (size_t)(16u * Bn + 2u * bn);
@@ -195,6 +206,10 @@ __device__ __forceinline__ Stash stash_view(double* base, int B, int b, int n) {
     v.h2 = base + (size_t)(27u * Bn + 8u * bn);
     return v;
 }
+__device__ __forceinline__ Stash stash_view(double* base, int B, int b, int n) {
+    return stash_planes<Stash>(base, (unsigned)B * (unsigned)n, (unsigned)b * (unsigned)n);   // 35 B n < 2^32: checked by the launchers
+}
+template <class U> __device__ __forceinline__ StashOff<U> stash_off(U Bn, U bn) { return stash_planes<StashOff<U>>((size_t)0, Bn, bn); }
 // compact index of an active site (i, j): every 4th column (mu = 0) or row (mu = 1)
 __device__ __forceinline__ int stash_active_idx(int i, int j, int L, int mu) {
     // unsigned 24-bit multiply-adds (coordinates are lattice sites): the signed form came out as v_bfe_i32 + the quarter-rate v_mad_u64_u32

@@ -17,7 +17,7 @@
 //
 // Reference: GaugeEquivCouplingLayer.forward (fthmc/utils/layers.py:196-202, 348-371), ft_action / ft_force
 // (fthmc/utils/qed_helpers.py:212-242), the leapfrog and accept step of ipynb/ft_hmc.py:394-435.
-#include "flow_mfma_common.h"
+#include "flow_bwd_common.h"
 #include "flow_transform.h"
 #include <stdlib.h>
 
@@ -26,7 +26,6 @@ namespace {
 using namespace fthmc;
 using namespace fthmc_flow;
 
-typedef double double2_t __attribute__((ext_vector_type(2)));
 
 // timing-only builds (results wrong): bit 0 no stash stores, 1 no border duplicates, 2 identity activation, 3 no weight loads,
 // 4 no stash loads in the backward.  tools/small_knobs.sh builds and times them; the product build has FT_KNOB = 0.
@@ -220,11 +219,6 @@ template <int L, bool TRAIN> struct Chain {
     static __device__ __forceinline__ void active_site(int a, int mu, int off, int& i, int& j) {
         if (mu == 0) { i = fdiv<L / 4>(a); j = off + 4 * (a - i * (L / 4)); }
         else { const int m = fdiv<L>(a); j = a - m * L; i = off + 4 * m; }
-    }
-    // frozen site f in [0, N / 2): line q along the stripes, h-th frozen line across them
-    static __device__ __forceinline__ void frozen_site(int f, int mu, int off, int& r, int& c) {
-        const int h = fdiv<L>(f), q = f - h * L, x = 4 * (h >> 1) + ((off + 1 + (h & 1)) & 3);
-        if (mu == 0) { r = q; c = x; } else { c = q; r = x; }
     }
     // Pairs ACROSS the stripe lines (conv1 forward, conv2^T): tile `wave` = pair position u across the lines, lane i = position
     // v along them; site 0 = (v, 2 u) for mu = 0 (site 1 = next column), (2 u, v) for mu = 1 (site 1 = next row).  A tile
@@ -475,7 +469,7 @@ template <int L, bool TRAIN> struct Chain {
         const int mu = l & 1, off = (l >> 1) & 3;
         const Stash sv = stash_view(stash(l), A.B, chain(), N);
         int fr, fc;
-        frozen_site(tid < NF ? tid : 0, mu, off, fr, fc);                  // cos / sin of frozen site tid
+        frozen_site<L>(tid < NF ? tid : 0, mu, off, fr, fc);                  // cos / sin of frozen site tid
         const int ic = stash_frozen_idx(fr, fc, L, mu, off);
         if (FT_KNOB & 16) { q.fcs = 0.6; q.fsn = 0.8; } else { q.fcs = gld(sv.cs + ic); q.fsn = gld(sv.cs + (N >> 1) + ic); }
     }
@@ -525,7 +519,7 @@ template <int L, bool TRAIN> struct Chain {
         const bool ttask = tid < NA, ftask = tid < NF, c3task = tid < 2 * N;
         const int c3half = tid >= N ? 1 : 0, c3s = tid - c3half * N;
         int fr = 0, fc = 0;
-        frozen_site(ftask ? tid : 0, mu, off, fr, fc);
+        frozen_site<L>(ftask ? tid : 0, mu, off, fr, fc);
         int pr_ = 0, pc_ = 0;
         const bool pok = pair_site(lane, mu, pr_, pc_);
         __builtin_amdgcn_sched_barrier(0);
@@ -611,36 +605,12 @@ template <int L, bool TRAIN> struct Chain {
             const int kd = (off + 3 - 2 * u) & 3;
             const double* wp = sWc + LB_T2 + KConv2Row::wlane(g, i & 7, i >> 3);
             const double* a0 = sGZ2 + g * PSZ + pr_ * RS + pc_;             // padded origin of the pair window = site 0 - (1, 1)
-            double4_t acc;
-            if (mu == 0) {
-                switch (kd) {
-                    case 0: acc = conv2t_tile<KConv2Col, 4, 0, RS, PSZ>(wp, a0); break;
-                    case 1: acc = conv2t_tile<KConv2Col, 4, 1, RS, PSZ>(wp, a0); break;
-                    case 2: acc = conv2t_tile<KConv2Col, 4, 2, RS, PSZ>(wp, a0); break;
-                    default: acc = conv2t_tile<KConv2Col, 4, 3, RS, PSZ>(wp, a0); break;
-                }
-            } else {
-                switch (kd) {
-                    case 0: acc = conv2t_tile<KConv2Row, 3, 0, RS, PSZ>(wp, a0); break;
-                    case 1: acc = conv2t_tile<KConv2Row, 3, 1, RS, PSZ>(wp, a0); break;
-                    case 2: acc = conv2t_tile<KConv2Row, 3, 2, RS, PSZ>(wp, a0); break;
-                    default: acc = conv2t_tile<KConv2Row, 3, 3, RS, PSZ>(wp, a0); break;
-                }
-            }
+            const double4_t acc = conv2t_dead_line<RS, PSZ>(mu, kd, wp, a0);
             double z4[4] = {acc[0], acc[1], acc[2], acc[3]};
             epi(g, 0, pok, z4, 0);
         }
-        typedef const double __attribute__((address_space(4))) * cdptr;
         double w0s[18];
-        {
-            cdptr wq = (cdptr)(size_t)(block_of(A.wint, true, l) + LB_W0 + wave * 18);
-            typedef double double8c_t __attribute__((ext_vector_type(8)));                   // wide scalar loads (8 + 8 + 2), as above
-            typedef const double8c_t __attribute__((address_space(4))) * cd8ptr;
-            const double8c_t va = *(cd8ptr)(wq), vb = *(cd8ptr)(wq + 8);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { w0s[k] = va[k]; w0s[8 + k] = vb[k]; }
-            w0s[16] = wq[16]; w0s[17] = wq[17];
-        }
+        conv1t_weights(block_of(A.wint, true, l) + LB_W0 + wave * 18, w0s);
         if (refill) issue_d1(lane, nl_, pre);
         lds_barrier();
         stamp(10);
@@ -648,7 +618,7 @@ template <int L, bool TRAIN> struct Chain {
         // ---- conv1^T at the frozen sites: wave = hidden channel, the sum over the channels through LDS
         for (int f = lane; f < NF; f += 64) {
             int r, c;
-            frozen_site(f, mu, off, r, c);
+            frozen_site<L>(f, mu, off, r, c);
             const double* gz = sD1 + wave * PSZ;                           // source site (r + 1 - ky, c + 1 - kx), wrapped
             int ro[3], co_[3];
             wrap3<L>(r, ro); wrap3<L>(c, co_);

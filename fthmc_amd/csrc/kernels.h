@@ -227,48 +227,46 @@ int launch_flow_bwd_gather(const FlowLayerArgs& a, hipStream_t s);
 int launch_flow_wgrad(const FlowLayerArgs& a, hipStream_t s);
 inline size_t flow_gz_doubles(int B, int L) { return (size_t)B * 17 * L * L; }
 inline int flow_wgrad_parts(int L) { return 2 * FlowGeom{MG_TR, MG_TC}.ntiles(L); }          // per chain at one item per workgroup: sizes the workspace
-// items per workgroup: as many as leave one workgroup for each of the 512 slots of the chip (two per CU), at most 8
-inline int flow_wgrad_tpw(int B, int L, int nlayers) {
-    const long items = (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L) * (nlayers > 0 ? nlayers : 1);
-    const long t = items / 512;
-    return t < 1 ? 1 : t > 8 ? 8 : (int)t;
+// How the (chain, 16 x 16 tile) items of a launch are shared among workgroups that WALK several of them (k_flow_wgrad,
+// k_flow_bwd_train; the kernels' side: flow_bwd_common.h walk_of_block).  tpw: items per workgroup -- as many as leave one
+// workgroup for each of the chip's `slots`, at most max_tpw (round_up: no slot takes more than one workgroup); ns: workgroups
+// of one XCD that walk side by side, one per slot of the XCD (fewer when the launch is smaller than the chip), at most max_ns;
+// nparts: the workgroups that walk at least one item = the rows of partials the launch writes (the kernels number those 0, 1,
+// 2, ...); grid.x = 8 XCDs x rounds x ns.  All in 64-bit arithmetic, for the callers that ask before they check the shape (ws_layout).
+struct WalkPlan { int slots, max_tpw, max_ns; bool round_up; };
+constexpr WalkPlan WALK_WGRAD = {512, 8, 64, false};        // two workgroups per CU: 512 slots, 32 CUs x 2 per XCD
+constexpr WalkPlan WALK_BWD_TRAIN = {256, 64, 32, true};    // one workgroup per CU: 256 slots, 32 per XCD
+inline long walk_items(int B, int L) { return (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L); }
+inline int walk_tpw(const WalkPlan& p, long items) {
+    const long t = (items + (p.round_up ? p.slots - 1 : 0)) / p.slots;
+    return t < 1 ? 1 : t > p.max_tpw ? p.max_tpw : (int)t;
 }
-// workgroups of one XCD that walk side by side (one per slot: 32 CUs x 2; fewer when the launch is smaller than the chip)
-inline int flow_wgrad_ns(int B, int L, int tpw) {
-    const int items = B * FlowGeom{MG_TR, MG_TC}.ntiles(L), n = (items + 8 * tpw - 1) / (8 * tpw);
-    return n < 1 ? 1 : n > 64 ? 64 : n;
+inline int walk_ns(const WalkPlan& p, long items, int tpw) {
+    const long n = (items + 8 * tpw - 1) / (8 * tpw);
+    return n < 1 ? 1 : n > p.max_ns ? p.max_ns : (int)n;
 }
-// partials of a launch: one per workgroup that has an item (k_flow_wgrad numbers those 0, 1, 2, ...)
-inline int flow_wgrad_nparts(int B, int L, int tpw) {
-    const int items = B * FlowGeom{MG_TR, MG_TC}.ntiles(L), ns = flow_wgrad_ns(B, L, tpw);
-    const int k0 = items / (tpw * ns), rem = items - k0 * tpw * ns;
+inline long walk_nparts(const WalkPlan& p, long items, int tpw) {
+    const long ns = walk_ns(p, items, tpw), k0 = items / (tpw * ns), rem = items - k0 * tpw * ns;
     return k0 * ns + (rem < ns ? rem : ns);
 }
+inline long walk_grid_x(long items, int tpw, int ns) {
+    const long KR = (items + (long)tpw * ns - 1) / ((long)tpw * ns), R = (KR + 7) / 8;
+    return 8 * R * ns;
+}
+// k_flow_wgrad: tpw counts the items of every layer of the launch (blockIdx.y), ns and the partials those of one layer
+inline int flow_wgrad_tpw(int B, int L, int nlayers) { return walk_tpw(WALK_WGRAD, walk_items(B, L) * (nlayers > 0 ? nlayers : 1)); }
+inline int flow_wgrad_ns(int B, int L, int tpw) { return walk_ns(WALK_WGRAD, walk_items(B, L), tpw); }
+inline int flow_wgrad_nparts(int B, int L, int tpw) { return (int)walk_nparts(WALK_WGRAD, walk_items(B, L), tpw); }
 // flow_bwd_train.hip: the training backward WITH the layer's weight gradients in one kernel (the pre-activation gradients never
 // leave LDS): one workgroup per CU walks (chain, tile) items and writes ONE 955-entry partial to a.gw_part
 // [flow_bwd_train_nparts(B, L)][FLOW_GW_STRIDE]; a.gp_out as launch_flow_bwd_gather.  Built for the shapes 16 x 16 tiles divide with
 // L a power of two (flow_bwd_train_shape); FTHMC_ERR_UNSUPPORTED otherwise: the caller keeps the two-kernel form.
 int launch_flow_bwd_train(const FlowLayerArgs& a, hipStream_t s);
 inline bool flow_bwd_train_shape(int L) { return L >= 32 && (L & (L - 1)) == 0; }
-// items per workgroup: as many as leave one workgroup per CU (256), at most 64
-inline int flow_bwd_train_tpw(int B, int L) {
-    const long items = (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L);
-    const long t = (items + 255) / 256;
-    return t < 1 ? 1 : t > 64 ? 64 : (int)t;
-}
-// workgroups of one XCD that walk side by side (one per CU: 32; fewer when the launch is smaller than the chip)
-inline int flow_bwd_train_ns(int B, int L, int tpw) {
-    const long items = (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L), n = (items + 8 * tpw - 1) / (8 * tpw);
-    return n < 1 ? 1 : n > 32 ? 32 : (int)n;
-}
-// partials of one launch (= its workgroups that walk at least one item); the launcher serves flow_stash_fits32 shapes only, where
-// this fits an int with room to spare -- the arithmetic is 64-bit for the callers that ask before they check (ws_layout)
-inline long flow_bwd_train_nparts(int B, int L) {
-    const int tpw = flow_bwd_train_tpw(B, L), ns = flow_bwd_train_ns(B, L, tpw);
-    const long items = (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L);
-    const long k0 = items / ((long)tpw * ns), rem = items - k0 * tpw * ns;
-    return k0 * ns + (rem < ns ? rem : ns);
-}
+inline int flow_bwd_train_tpw(int B, int L) { return walk_tpw(WALK_BWD_TRAIN, walk_items(B, L)); }
+inline int flow_bwd_train_ns(int B, int L, int tpw) { return walk_ns(WALK_BWD_TRAIN, walk_items(B, L), tpw); }
+// the launcher serves flow_stash_fits32 shapes only, where this fits an int with room to spare
+inline long flow_bwd_train_nparts(int B, int L) { return walk_nparts(WALK_BWD_TRAIN, walk_items(B, L), flow_bwd_train_tpw(B, L)); }
 // doubles per layer of the stash (layout: flow_mfma_common.h struct Stash): 19 per site, 35 with h1, h2 (training)
 inline size_t flow_stash_doubles(int B, int L, bool train = false) { return (size_t)B * (train ? 35 : 19) * L * L; }
 // the tuned kernels form a chain's plane offsets inside one layer's stash in 32 bits (flow_mfma_common.h: uniform_at, stash_view)

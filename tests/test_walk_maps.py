@@ -3,7 +3,8 @@ of a launch among their workgroups, and the rows the host reserves for what they
 
 A workgroup of either kernel WALKS several items and writes one row of partial weight gradients; the host sizes those rows, the
 layer stride of the small path's one launch and the reduction from flow_wgrad_tpw / _ns / _nparts and flow_bwd_train_tpw / _ns /
-_nparts (csrc/kernels.h) without asking the kernel.  tests/walk_model.py restates both sides; here
+_nparts (csrc/kernels.h: one WalkPlan computation with two sets of constants) without asking the kernel.  tests/walk_model.py
+restates both sides; here
   * the restated lines are pinned to the source text (an edit there fails until the model follows),
   * over a sweep of shapes every item is walked exactly once, nothing beyond the items is walked, and the rows the workgroups
     write are exactly 0 .. nparts - 1 (the claim "valid groups are a prefix of this numbering"),
@@ -28,35 +29,35 @@ def src(name):
 
 # ---------------------------------------------------------------- the model is the source
 KERNELS_H_BODIES = (
-    '''inline int flow_wgrad_tpw(int B, int L, int nlayers) {
-    const long items = (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L) * (nlayers > 0 ? nlayers : 1);
-    const long t = items / 512;
-    return t < 1 ? 1 : t > 8 ? 8 : (int)t;
+    # the one computation ...
+    '''inline long walk_items(int B, int L) { return (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L); }''',
+    '''inline int walk_tpw(const WalkPlan& p, long items) {
+    const long t = (items + (p.round_up ? p.slots - 1 : 0)) / p.slots;
+    return t < 1 ? 1 : t > p.max_tpw ? p.max_tpw : (int)t;
 }''',
-    '''inline int flow_wgrad_ns(int B, int L, int tpw) {
-    const int items = B * FlowGeom{MG_TR, MG_TC}.ntiles(L), n = (items + 8 * tpw - 1) / (8 * tpw);
-    return n < 1 ? 1 : n > 64 ? 64 : n;
+    '''inline int walk_ns(const WalkPlan& p, long items, int tpw) {
+    const long n = (items + 8 * tpw - 1) / (8 * tpw);
+    return n < 1 ? 1 : n > p.max_ns ? p.max_ns : (int)n;
 }''',
-    '''inline int flow_wgrad_nparts(int B, int L, int tpw) {
-    const int items = B * FlowGeom{MG_TR, MG_TC}.ntiles(L), ns = flow_wgrad_ns(B, L, tpw);
-    const int k0 = items / (tpw * ns), rem = items - k0 * tpw * ns;
+    '''inline long walk_nparts(const WalkPlan& p, long items, int tpw) {
+    const long ns = walk_ns(p, items, tpw), k0 = items / (tpw * ns), rem = items - k0 * tpw * ns;
     return k0 * ns + (rem < ns ? rem : ns);
 }''',
-    '''inline int flow_bwd_train_tpw(int B, int L) {
-    const long items = (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L);
-    const long t = (items + 255) / 256;
-    return t < 1 ? 1 : t > 64 ? 64 : (int)t;
+    '''inline long walk_grid_x(long items, int tpw, int ns) {
+    const long KR = (items + (long)tpw * ns - 1) / ((long)tpw * ns), R = (KR + 7) / 8;
+    return 8 * R * ns;
 }''',
-    '''inline int flow_bwd_train_ns(int B, int L, int tpw) {
-    const long items = (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L), n = (items + 8 * tpw - 1) / (8 * tpw);
-    return n < 1 ? 1 : n > 32 ? 32 : (int)n;
-}''',
-    '''inline long flow_bwd_train_nparts(int B, int L) {
-    const int tpw = flow_bwd_train_tpw(B, L), ns = flow_bwd_train_ns(B, L, tpw);
-    const long items = (long)B * FlowGeom{MG_TR, MG_TC}.ntiles(L);
-    const long k0 = items / ((long)tpw * ns), rem = items - k0 * tpw * ns;
-    return k0 * ns + (rem < ns ? rem : ns);
-}''',
+    # ... its two sets of constants { slots, max_tpw, max_ns, round_up } (walk_model.py spells them out as numbers) ...
+    'struct WalkPlan { int slots, max_tpw, max_ns; bool round_up; };',
+    'constexpr WalkPlan WALK_WGRAD = {512, 8, 64, false};',
+    'constexpr WalkPlan WALK_BWD_TRAIN = {256, 64, 32, true};',
+    # ... and the six names the callers use
+    'inline int flow_wgrad_tpw(int B, int L, int nlayers) { return walk_tpw(WALK_WGRAD, walk_items(B, L) * (nlayers > 0 ? nlayers : 1)); }',
+    'inline int flow_wgrad_ns(int B, int L, int tpw) { return walk_ns(WALK_WGRAD, walk_items(B, L), tpw); }',
+    'inline int flow_wgrad_nparts(int B, int L, int tpw) { return (int)walk_nparts(WALK_WGRAD, walk_items(B, L), tpw); }',
+    'inline int flow_bwd_train_tpw(int B, int L) { return walk_tpw(WALK_BWD_TRAIN, walk_items(B, L)); }',
+    'inline int flow_bwd_train_ns(int B, int L, int tpw) { return walk_ns(WALK_BWD_TRAIN, walk_items(B, L), tpw); }',
+    'inline long flow_bwd_train_nparts(int B, int L) { return walk_nparts(WALK_BWD_TRAIN, walk_items(B, L), flow_bwd_train_tpw(B, L)); }',
 )
 KERNELS_H_LINES = (
     'int nti(int L) const { return (L + tr - 1) / tr; }',
@@ -76,31 +77,37 @@ KERNELS_H_LINES = (
     return (nparts + chunk - 1) / chunk;
 }''',
 )
-# the same in k_flow_wgrad and k_flow_bwd_train
+# the walk of k_flow_wgrad and k_flow_bwd_train, stated once (csrc/flow_bwd_common.h walk_of_block)
 KERNEL_MAP_LINES = (
     'const int items = A.B * ntiles, tpw = A.tpw, ns = A.wg_ns;',
     'const int KR = (items + tpw * ns - 1) / (tpw * ns), R = (KR + 7) >> 3;',
     'const int idx = (int)blockIdx.x >> 3, r_ = idx / ns, s_ = idx - r_ * ns, kr = ((int)blockIdx.x & 7) * R + r_;',
     'const int first = kr * tpw * ns + s_;',
-    'if (r_ >= R || first >= items) return;',
+    'if (r_ >= R || first >= items) return false;',
     'const int grp = kr * ns + s_;',
     'const int nwalk = min(tpw, (items - first + ns - 1) / ns);',
-    # the launchers
-    'const int items = a.B * FlowGeom{MG_TR, MG_TC}.ntiles(a.L);',
-    'const int KR = (items + b.tpw * b.wg_ns - 1) / (b.tpw * b.wg_ns), R = (KR + 7) / 8;',
+)
+# both kernels take their walk from it
+KERNEL_USE_LINES = (
+    'if (!walk_of_block(A, ntiles, wk)) return;',
+    'const int first = wk.first, grp = wk.grp, nwalk = wk.nwalk, ns = wk.ns;',
 )
 WGRAD_LINES = (
     'const int nti_ = (L + TR - 1) / TR, ntj_ = (L + TC - 1) / TC, ntiles = nti_ * ntj_;',
-    'item_coords(first + (it + 1 < nwalk ? it + 1 : it) * ns, nb, nti, ntj);',           # the walk's stride
+    'item_coords(first + (it + 1 < nwalk ? it + 1 : it) * ns, ntiles, ntj_, nb, nti, ntj);',   # the walk's stride
     'double* gw0 = A.gw_part + (size_t)lz * A.gwp_lstride + (size_t)grp * FLOW_GW_STRIDE;',
     'b.tpw = a.tpw > 0 ? a.tpw : 1;',
     'b.wg_ns = flow_wgrad_ns(a.B, a.L, b.tpw);',
-    'const dim3 grid(8 * R * b.wg_ns, a.nlb > 0 ? a.nlb : 1, 1);',
+    'const dim3 grid((unsigned)walk_grid_x(walk_items(a.B, a.L), b.tpw, b.wg_ns), a.nlb > 0 ? a.nlb : 1, 1);',
 )
 FUSED_LINES = (
     'b.tpw = flow_bwd_train_tpw(a.B, a.L);',
     'b.wg_ns = flow_bwd_train_ns(a.B, a.L, b.tpw);',
-    'const dim3 grid(8 * R * b.wg_ns, 1, 1);',
+    'const int nti_ = L / TR, ntj_ = L / TC, ntiles = nti_ * ntj_;',
+    'const int item = first + (k < nwalk ? k : nwalk - 1) * ns;',                                 # the walk's stride
+    'item_coords(item, ntiles, ntj_, q.b, ti, tj);',
+    'double* gw0 = A.gw_part + (size_t)grp * FLOW_GW_STRIDE;',
+    'const dim3 grid((unsigned)walk_grid_x(walk_items(a.B, a.L), b.tpw, b.wg_ns), 1, 1);',
 )
 API_LINES = (
     'const size_t nt = flow_ntiles_max(L);',
@@ -136,11 +143,12 @@ def test_the_restated_functions_are_the_ones_in_kernels_h():
 
 @pytest.mark.parametrize('name,own', [('flow_wgrad.hip', WGRAD_LINES), ('flow_bwd_train.hip', FUSED_LINES)])
 def test_the_restated_walk_is_the_one_in_the_kernel(name, own):
-    text = src(name)
-    assert missing_lines(text, KERNEL_MAP_LINES) == []
+    text, shared = src(name), src('flow_bwd_common.h')
+    assert missing_lines(shared, KERNEL_MAP_LINES) == []
+    assert missing_lines(text, KERNEL_USE_LINES) == []
     assert missing_lines(text, own) == []
-    for line in KERNEL_MAP_LINES[:7]:                      # once each: no second map the model would not know of
-        assert text.count(line) == 1, line
+    for line in KERNEL_MAP_LINES:                          # once, in the shared header: no second map the model would not know of
+        assert shared.count(line) == 1 and line not in text, line
 
 
 def test_the_restated_workspace_rows_are_the_ones_in_ws_layout():
@@ -155,7 +163,7 @@ def test_the_restated_workspace_rows_are_the_ones_in_ws_layout():
 
 def test_a_pin_notices_an_edit():
     """the pins compare text: one character of a pinned line changed, and the line counts as missing"""
-    text = src('flow_wgrad.hip')
+    text = src('flow_bwd_common.h')
     line = 'const int nwalk = min(tpw, (items - first + ns - 1) / ns);'
     assert missing_lines(text.replace(line, line.replace('ns - 1', 'ns')), KERNEL_MAP_LINES) == [line]
 

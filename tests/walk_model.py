@@ -1,9 +1,11 @@
 """Pure Python restatement of how the two weight-gradient kernels share (chain, tile) items among their workgroups.
 
   * csrc/kernels.h: flow_wgrad_tpw / _ns / _nparts (k_flow_wgrad, csrc/flow_wgrad.hip) and flow_bwd_train_tpw / _ns / _nparts
-    (k_flow_bwd_train, csrc/flow_bwd_train.hip): items a workgroup walks, workgroups of one XCD that walk side by side, rows of the
-    partial buffer;
-  * both kernels: blockIdx.x -> (r_, s_, kr, first, grp, nwalk) with the early return, and the launchers' grid = 8 * R * ns;
+    (k_flow_bwd_train, csrc/flow_bwd_train.hip) -- there walk_tpw / _ns / _nparts with the plans WALK_WGRAD = {512, 8, 64, round
+    down} and WALK_BWD_TRAIN = {256, 64, 32, round up}, here the two parameter sets spelled out as numbers: items a workgroup
+    walks, workgroups of one XCD that walk side by side, rows of the partial buffer;
+  * both kernels (csrc/flow_bwd_common.h walk_of_block): blockIdx.x -> (r_, s_, kr, first, grp, nwalk) with the early return, and
+    the launchers' grid = 8 * R * ns (csrc/kernels.h walk_grid_x);
   * csrc/api.hip ws_layout / csrc/kernels.h: the rows a training workspace has for the partials and for the reduction.
 
 tests/test_walk_maps.py pins every line restated here to the source text and checks the properties the host code relies on;
@@ -67,9 +69,9 @@ def flow_bwd_train_nparts(B, L):
     return k0 * ns + (rem if rem < ns else ns)
 
 
-# ---- the kernels' own map (the same lines in both)
+# ---- the kernels' own map (walk_of_block: one statement for both)
 def grid_x(items, tpw, ns):
-    """launch_flow_wgrad / launch_flow_bwd_train: grid.x = 8 * R * ns"""
+    """launch_flow_wgrad / launch_flow_bwd_train through walk_grid_x: grid.x = 8 * R * ns"""
     KR = (items + tpw * ns - 1) // (tpw * ns)
     R = (KR + 7) // 8
     return 8 * R * ns
