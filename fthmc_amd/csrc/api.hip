@@ -191,7 +191,10 @@ inline SmallArgs small_args(const double* x, const WS& w, int nl, int B, int act
     (void)hipGetLastError();   /* drop stale (non-sticky) errors left by the host framework */ \
     Ctx C; { const int rc_ = make_ctx((arch_), stream, &C); if (rc_ != FTHMC_OK) return rc_; } \
     hipStream_t s = C.s; (void)s
+// (first the chain count the default net's kernels take, flow_shape_ok's B <= 2^20 (kernels.h, fthmc_hip.h): their launchers
+// refuse it too, but only behind the weight expansion -- here nothing has been enqueued yet)
 #define FT_WS(nl, train)                                                            \
+    if (C.A.is_default() && (nl) > 0 && B > (1 << 20)) return FTHMC_ERR_ARG;        \
     if (!ws || ws_bytes < ws_doubles(C.A, B, L, (nl), (train)) * sizeof(double)) return FTHMC_ERR_WS; \
     const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, (nl), (train))
 

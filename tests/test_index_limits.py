@@ -162,3 +162,25 @@ def test_plain_lattice_entry_points_refuse_shapes_past_their_limits():
     assert lib.fthmc_random_momenta(p, BMAX + 1, 32, p, p, None) == -1
     assert lib.fthmc_random_momenta(p, 1, 2 * LMAX * LMAX + 1, p, p, None) == -1
     assert lib.fthmc_random_momenta(p, 1, 2 ** 31 - 1, p, p, None) == -1
+
+
+def test_flow_entry_points_refuse_the_first_chain_count_past_their_limit():
+    """B = 2^20 + 1 with the default net (flow_shape_ok; include/fthmc_hip.h: B <= 2^20, else FTHMC_ERR_ARG): every flow entry
+    point refuses before anything is enqueued, the weight expansion included (the pointers are never dereferenced; on a machine
+    without a device a launch would be FTHMC_ERR_LAUNCH).  tests/test_limits_gpu.py runs B = 2^20."""
+    import ctypes
+    from fthmc_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(64)
+    B, L, nl, big = (1 << 20) + 1, 4, 2, 1 << 50
+    assert flow_shape_ok(B - 1, L) and not flow_shape_ok(B, L) and flow_stash_fits32(B, L, True)
+    assert 'B <= 2^20, else FTHMC_ERR_ARG' in open(os.path.join(ROOT, 'include', 'fthmc_hip.h')).read()
+    assert lib.fthmc_flow_layer_fwd(p, p, None, B, L, 0, 0, 0, p, p, p, big, None) == -1
+    assert lib.fthmc_flow_layer_rev(p, p, None, B, L, 0, 0, 0, 1e-12, p, p, p, big, None) == -1
+    assert lib.fthmc_flow_layer_bwd(p, p, None, p, p, B, L, 0, 0, 0, p, p, p, big, None) == -1
+    assert lib.fthmc_flow_forward(p, p, None, nl, B, L, 0, p, p, p, big, None) == -1
+    assert lib.fthmc_flow_reverse(p, p, None, nl, B, L, 0, 1e-12, p, p, p, big, None) == -1
+    assert lib.fthmc_ft_action(p, p, None, nl, B, L, 0, 1.0, p, p, p, p, p, big, None) == -1
+    assert lib.fthmc_ft_force(p, p, None, nl, B, L, 0, 1.0, p, p, big, None) == -1
+    assert lib.fthmc_ft_leapfrog(p, p, p, None, nl, B, L, 0, 1.0, 0.1, 1, p, p, p, big, None) == -1
+    assert lib.fthmc_train_grad(p, p, None, nl, B, L, 0, 1.0, p, p, p, p, p, big, None) == -1

@@ -106,6 +106,60 @@ def _flow(nl=2):
     return ops.pack_weights(flow, device='cuda'), nl
 
 
+def _same_in_every_chain(big, small, what):
+    assert torch.equal(big, small.expand_as(big)), what
+
+
+def test_generic_flow_kernels_at_large_chain_counts(release):
+    """B = 65537 identical chains of L = 4 through csrc/flow_generic.hip (hidden = (2,), k = 3, two components, two layers): its
+    launches carry the chain index in gridDim.y / gridDim.z (k_gen_transform: gridDim.x), past 65535 here.  Every chain of
+    flow_forward, ft_action, ft_force and of ft_force_vjp's H g is the B = 1 result; train_grad returns the gradient of the MEAN
+    over the chains, the chain sum (B times the single gradient) over B: the single one, to `close`"""
+    from fthmc_amd import _lib, ops
+    from oracle import ref_cpu as R
+    B, L, nl, beta, arch = 65537, 4, 2, 2.0, ((2,), 3, 2)
+    flow = R.default_flow(nl, torch.Generator().manual_seed(25), hidden=arch[0], k=arch[1], n_mix=arch[2])
+    w = ops.pack_weights(flow, device='cuda')
+    assert ops.arch_of(w) == arch != ops.DEFAULT_ARCH and B > 65535
+    need_memory(int(_lib.load().fthmc_train_ws_bytes(ops._arch(arch), B, L, nl)) + ops.vjp_ws_bytes(B, L, nl, arch)
+                + 8 * B * 2 * L * L * 8, f'generic net, B = {B}')
+    x1 = field(1, L, 27)
+    g1 = torch.randn(1, 2, L, L, generator=torch.Generator().manual_seed(28), dtype=torch.float64).cuda()
+    xB, gB = x1.expand(B, -1, -1, -1).contiguous(), g1.expand(B, -1, -1, -1).contiguous()
+    for a, b, k in zip(ops.flow_forward(xB, w, nl), ops.flow_forward(x1, w, nl), ('y', 'logdet')):
+        _same_in_every_chain(a, b, 'flow_forward ' + k)
+    for a, b, k in zip(ops.ft_action(xB, w, nl, beta), ops.ft_action(x1, w, nl, beta), ('S_eff', 'logdet', 'plaq', 'Q')):
+        _same_in_every_chain(a, b, 'ft_action ' + k)
+    _same_in_every_chain(ops.ft_force(xB, w, nl, beta), ops.ft_force(x1, w, nl, beta), 'ft_force')
+    _same_in_every_chain(ops.ft_force_vjp(xB, w, nl, beta, gB, need_gw=False)[0], ops.ft_force_vjp(x1, w, nl, beta, g1, need_gw=False)[0],
+                         'ft_force_vjp Hg')
+    rB, r1 = ops.train_grad(xB, w, nl, beta), ops.train_grad(x1, w, nl, beta)
+    for k in ('x', 'logq', 'logp'):
+        _same_in_every_chain(rB[k], r1[k], 'train_grad ' + k)
+    print('train_grad gw, B = %d against B = 1: %.1e' % (B, float((rB['gw'] - r1['gw']).abs().max() / r1['gw'].abs().max())))
+    assert close(rB['gw'], r1['gw'], 1.0)
+    torch.cuda.synchronize()
+
+
+def test_tuned_flow_kernels_at_the_largest_chain_count(release):
+    """B = 2^20 identical chains of L = 4, the largest B flow_shape_ok accepts (the tuned launches carry (B + 7) / 8 = 131072 in
+    gridDim.z): every chain of flow_forward, ft_action and ft_force is the B = 1 result.  tests/test_index_limits.py has the first
+    refused B."""
+    from fthmc_amd import ops
+    w, nl = _flow()
+    B, L, beta = 1 << 20, 4, 2.0
+    assert ops.arch_of(w) == ops.DEFAULT_ARCH and ops.get_variant() == 1
+    need_memory(ops.ws_bytes(B, L, nl) + 4 * B * 2 * L * L * 8, f'default net, B = {B}')
+    x1 = field(1, L, 29)
+    xB = x1.expand(B, -1, -1, -1).contiguous()
+    for a, b, k in zip(ops.flow_forward(xB, w, nl), ops.flow_forward(x1, w, nl), ('y', 'logdet')):
+        _same_in_every_chain(a, b, 'flow_forward ' + k)
+    for a, b, k in zip(ops.ft_action(xB, w, nl, beta), ops.ft_action(x1, w, nl, beta), ('S_eff', 'logdet', 'plaq', 'Q')):
+        _same_in_every_chain(a, b, 'ft_action ' + k)
+    _same_in_every_chain(ops.ft_force(xB, w, nl, beta), ops.ft_force(x1, w, nl, beta), 'ft_force')
+    torch.cuda.synchronize()
+
+
 def test_flow_refuses_the_first_lattice_past_its_limit(release):
     """L = 8196: the tuned kernels' launchers refuse with FTHMC_ERR_ARG (flow_shape_ok: the stash planes' byte offsets)"""
     from fthmc_amd import ops
