@@ -117,7 +117,10 @@ SIGNATURES['fthmc_wilson_loops_ws_bytes'] = [c_int, c_int, c_int, c_int]
 SIGNATURES['fthmc_wilson_loops'] = [_D, c_int, c_int, c_int, c_int, _D, _D, _P, c_size_t, _P]
 # heatbath / overrelaxation sweeps: x, B, L, beta, beta_b, seeds, n_hb, n_or, nsweep, sweep0, classes, x_out, stream
 SIGNATURES['fthmc_local_update'] = [_D, c_int, c_int, c_double, _D, _D, c_int, c_int, c_int, ctypes.c_int64, c_int, _D, _P]
-_RESTYPE = {'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
+# instanton hits: x, B, L, beta, beta_b, seeds, n_hit, hit0, path, x_out, k_out, nacc_out, cs_out, ws, ws_bytes, stream
+SIGNATURES['fthmc_instanton_ws_bytes'] = [c_int, c_int, c_int]
+SIGNATURES['fthmc_instanton_hit'] = [_D, c_int, c_int, c_double, _D, _D, c_int, ctypes.c_int64, c_int, _D, _D, _D, _D, _P, c_size_t, _P]
+_RESTYPE = {'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None
 

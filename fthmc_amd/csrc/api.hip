@@ -4,6 +4,7 @@
 // trajectory can be captured into a hipGraph by the caller.
 #include "common.h"
 #include "kernels.h"
+#include "topo_int.h"
 #include "dual.h"
 #include <math.h>
 
@@ -1142,6 +1143,31 @@ int fthmc_local_update(const double* x, int B, int L, double beta, const double*
     if (sweep0 > (1LL << 32) || last > (1LL << 32) - sweep0) return FTHMC_ERR_ARG;
     const bool resident = L <= LU_MAXL && get_small_path() != 0;
     return launch_local_update(x, B, L, beta, beta_b, seeds, n_hb, n_or, nsweep, (uint32_t)sweep0, classes, x_out, resident, ft_stream(stream));
+}
+
+// Instanton hits (topo.hip): the argument checks, the choice of the launch shape and the workspace of the split one:
+// part[B][nw][2] doubles | k[B] int32
+static bool instanton_split(int B, int L, int path) { return path == 2 || (path == 0 && B < 64 && L >= 128); }
+size_t fthmc_instanton_ws_bytes(int B, int L, int path) {
+    if (bad_shape(B, L) || path < 0 || path > 2 || !instanton_split(B, L, path)) return 0;
+    return instanton_part_doubles(B, L) * sizeof(double) + ((size_t)B * sizeof(int32_t) + 7) / 8 * 8;
+}
+int fthmc_instanton_hit(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hit, int64_t hit0,
+                        int path, double* x_out, int32_t* k_out, int32_t* nacc_out, double* cs_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !x_out || bad_shape(B, L) || n_hit < 0 || n_hit > IT_MAX_HITS || path < 0 || path > 2) return FTHMC_ERR_ARG;
+    if (n_hit > 0 && !seeds) return FTHMC_ERR_ARG;                                       // no hit draws nothing
+    // the hit index is one 32-bit word of the Philox counter: every index the call uses must fit
+    if (hit0 < 0 || hit0 > (1LL << 32) - n_hit) return FTHMC_ERR_ARG;
+    const bool split = instanton_split(B, L, path);
+    double* part = nullptr;
+    int32_t* kbuf = nullptr;
+    if (split) {
+        if (!ws || ws_bytes < fthmc_instanton_ws_bytes(B, L, path)) return FTHMC_ERR_WS;
+        part = static_cast<double*>(ws);
+        kbuf = reinterpret_cast<int32_t*>(part + instanton_part_doubles(B, L));
+    }
+    return launch_instanton(x, B, L, beta, beta_b, seeds, n_hit, (uint32_t)hit0, split, x_out, k_out, nacc_out, cs_out, part, kbuf,
+                            ft_stream(stream));
 }
 
 int fthmc_ft_trajectory(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,

@@ -11,6 +11,10 @@ namespace fthmc {
 // much before the backward returns to it -- the 256 MB Infinity Cache over two chain groups, each writing and reading back
 constexpr size_t STASH_FAR_BYTES = (size_t)64 << 20;
 
+// one workgroup per chain: its size for an L x L lattice.  Every chain sum (action, charge, kinetic energy, k_traj_energy, the instanton
+// hit's C and Sn) is launched with it, so that the same sum is bit-identical wherever it is formed
+inline int chain_threads(int L) { return L * L >= 4096 ? 1024 : (L * L >= 1024 ? 512 : 256); }
+
 // ---- wilson.hip
 int launch_wrap(const double* x, double* o, size_t n, int reg, hipStream_t s);
 int launch_axpy(const double* x, const double* p, double a, double* o, size_t n, hipStream_t s);
@@ -113,6 +117,13 @@ constexpr int LU_MAX_ATTEMPTS = 64;           // rejection attempts of one heatb
 // resident: the one-launch kernel (L <= LU_MAXL), else one launch per class and sweep; beta_b: per-chain beta or null
 int launch_local_update(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hb, int n_or,
                         int nsweep, uint32_t sweep0, int classes, double* x_out, bool resident, hipStream_t s);
+
+// ---- topo.hip: instanton hits, the Metropolis update across topological sectors (fthmc_instanton_hit)
+// split: one wave per workgroup + decision + apply (part: [B][chain_threads(L) / 64][2] doubles, kbuf: [B] int32) in place of one
+// workgroup per chain (part, kbuf unused); k_out, nacc_out, cs_out: optional; x_out may be x
+inline size_t instanton_part_doubles(int B, int L) { return (size_t)B * (size_t)(chain_threads(L) / 64) * 2; }
+int launch_instanton(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hit, uint32_t hit0,
+                     bool split, double* x_out, int32_t* k_out, int32_t* nacc_out, double* cs_out, double* part, int32_t* kbuf, hipStream_t s);
 
 // ---- rng.hip
 int launch_random_momenta(const int64_t* seeds, int B, int n, double* v, double* u, hipStream_t s);

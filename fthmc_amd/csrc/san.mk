@@ -38,7 +38,7 @@ san_integrator:
 # tests/hip/tempering_walk.cpp as a stand-alone program against the host-side sanitizer build of the library (built first when it
 # is missing or older than a source), the sanitizer runtimes linked in (nothing to preload), run by tests/test_tempering.py
 SANTEMP ?= $(SANDIR)/tempering_walk
-$(SANOUT): $(SRCS) common.h kernels.h integrator.h ../../include/fthmc_hip.h san.mk
+$(SANOUT): $(SRCS) common.h kernels.h integrator.h topo_int.h ../../include/fthmc_hip.h san.mk
 	@$(MAKE) --no-print-directory -f san.mk san_build
 san_tempering: $(SANOUT)
 	mkdir -p $(dir $(SANTEMP))
@@ -59,3 +59,11 @@ san_local: $(SANOUT)
 	mkdir -p $(dir $(SANLOCAL))
 	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
 	  ../../tests/hip/local_walk.cpp -o $(SANLOCAL) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
+
+# The instanton-hit entry points (fthmc_instanton_hit, fthmc_instanton_ws_bytes) and the integer reductions of topo_int.h:
+# tests/hip/instanton_walk.cpp in the same way, run by tests/test_instanton.py
+SANINST ?= $(SANDIR)/instanton_walk
+san_instanton: $(SANOUT)
+	mkdir -p $(dir $(SANINST))
+	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
+	  ../../tests/hip/instanton_walk.cpp -o $(SANINST) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))

@@ -135,6 +135,31 @@ Tensor local_update(const Tensor& x_, double beta, const c10::optional<Tensor>& 
                           (int)n_hb, (int)n_or, (int)nsweep, sweep0, (int)classes, mp(out), cur_stream(x)), "fthmc_local_update");
     return out;
 }
+// instanton hits -> (the updated field, the applied charge k, the accepted steps), k and nacc int32 [B] (no autograd formula: a
+// sampler step); the library chooses the launch shape
+std::tuple<Tensor, Tensor, Tensor> instanton_hit(const Tensor& x_, double beta, const c10::optional<Tensor>& beta_b_, const c10::optional<Tensor>& seeds_,
+                                                 int64_t n_hit, int64_t hit0) {
+    FT_DEVICE_GUARD(x_);
+    Tensor x = field(x_, "x");
+    const int B = (int)x.size(0), L = (int)x.size(2);
+    TORCH_CHECK(n_hit >= 0 && n_hit <= 1024 && hit0 >= 0 && hit0 <= ((int64_t)1 << 32) - n_hit,
+                "instanton_hit: n_hit in 0 .. 1024 and hit0 >= 0 with hit0 + n_hit <= 2^32 expected");
+    Tensor beta_b, seeds;
+    if (beta_b_.has_value()) beta_b = perchain(*beta_b_, B, "beta_b");
+    if (seeds_.has_value()) {
+        seeds = seeds_->contiguous();
+        TORCH_CHECK(seeds.is_cuda() && seeds.scalar_type() == at::kLong && seeds.numel() == B, "seeds: expected ", B, " int64 seeds on the HIP device");
+    }
+    TORCH_CHECK(n_hit == 0 || seeds.defined(), "instanton_hit: hits need seeds");
+    Tensor out = at::empty_like(x), k = at::empty({B}, x.options().dtype(at::kInt)), nacc = at::empty({B}, x.options().dtype(at::kInt));
+    const size_t bytes = fthmc_instanton_ws_bytes(B, L, 0);
+    Tensor ws;
+    if (bytes > 0) ws = at::empty({(int64_t)((bytes + 7) / 8)}, x.options());
+    ok(fthmc_instanton_hit(cp(x), B, L, beta, beta_b.defined() ? cp(beta_b) : nullptr, seeds.defined() ? seeds.const_data_ptr<int64_t>() : nullptr,
+                           (int)n_hit, hit0, 0, mp(out), k.mutable_data_ptr<int32_t>(), nacc.mutable_data_ptr<int32_t>(), nullptr,
+                           bytes > 0 ? mp(ws) : nullptr, bytes, cur_stream(x)), "fthmc_instanton_hit");
+    return {out, k, nacc};
+}
 std::tuple<Tensor, Tensor, Tensor> hmc_trajectory(const Tensor& x_, const Tensor& v_, const Tensor& u_, double beta, double dt, int64_t nstep) {
     FT_DEVICE_GUARD(x_);
     Tensor x = field(x_, "x"), v = field(v_, "v");
@@ -377,6 +402,7 @@ TORCH_LIBRARY(fthmc_hip, m) {
     m.def("ft_trajectory_pb(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, Tensor beta_b, float dt, int nstep, int integrator, int act, Tensor? state_in=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
     m.def("hmc_trajectory_pb(Tensor x, Tensor v, Tensor u, Tensor beta_b, float dt, int nstep, int integrator=0) -> (Tensor, Tensor, Tensor)");
     m.def("local_update(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hb=1, int n_or=0, int nsweep=1, int sweep0=0, int classes=15) -> Tensor");
+    m.def("instanton_hit(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hit=1, int hit0=0) -> (Tensor, Tensor, Tensor)");
     m.def("replica_swap(Tensor betas, Tensor C, Tensor u, Tensor(a!) beta_b, Tensor(b!) rung, Tensor(c!) chain_of, int parity) -> (Tensor, Tensor)");
 }
 
@@ -401,4 +427,5 @@ TORCH_LIBRARY_IMPL(fthmc_hip, CUDA, m) {
     m.impl("hmc_trajectory_pb", &hmc_trajectory_pb);
     m.impl("replica_swap", &replica_swap);
     m.impl("local_update", &local_update);
+    m.impl("instanton_hit", &instanton_hit);
 }

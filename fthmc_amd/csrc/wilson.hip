@@ -900,9 +900,6 @@ int g_leap_rows = 1;     // FTHMC_LEAP_ROWS=0 in the environment: the 16 x 16-ti
 // ---- the launch shapes
 inline int ew_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 2048 ? 2048 : (g ? g : 1)); }
 inline dim3 tile_grid(int B, int L) { return dim3((L + TS - 1) / TS, (L + TS - 1) / TS, B); }
-// one workgroup per chain: its size for an L x L lattice.  Every chain sum (action, charge, kinetic energy, k_traj_energy) is launched
-// with it, so that the same sum is bit-identical wherever it is formed
-inline int chain_threads(int L) { return L * L >= 4096 ? 1024 : (L * L >= 1024 ? 512 : 256); }
 // grid-stride walk over a chain's sites, 256 threads a workgroup, at most 64 workgroups per chain
 inline dim3 stride_grid(int B, int L) { const int gx = (L * L + 255) / 256; return dim3(gx > 64 ? 64 : gx, B); }
 // row strips: whole 64-site row segments (16-byte accesses, two sites per thread), TR rows to a workgroup

@@ -13,7 +13,7 @@ from .utils import qed_helpers as qed
 
 def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, figsize=None, use_title: bool = True,
             save_data: bool = False, nplot: int = 10, integrator: str = 'leapfrog', loops=None, loops_every: int = 1,
-            overrelax: int = 0):
+            overrelax: int = 0, instanton: int = 0):
     """hmc.py:57-175: `param.nrun` experiments of `param.ntraj` trajectories each.
     Returns (fields_arr, histories) with the reference's metric keys.
     integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h).
@@ -21,7 +21,10 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
     field are measured (ops.wilson_loops) and the history gains 'wloops', one [Rmax, Tmax] batch-mean table per measured
     trajectory (utils.observables.exact_wilson_loop has the exact expectation).
     overrelax = k (default 0: nothing changes): k overrelaxation sweeps (qed_helpers.overrelax) behind every trajectory, before it is
-    measured; they leave the action where the trajectory put it and move the non-topological modes."""
+    measured; they leave the action where the trajectory put it and move the non-topological modes.
+    instanton = k (default 0: nothing changes): k instanton hits (qed_helpers.instanton_hit) behind every trajectory and behind the
+    overrelaxation sweeps, before the measurement: Metropolis steps across topological sectors, which the molecular dynamics does
+    not cross at large beta.  The history gains 'inst_acc' (accepted / k per chain) and 'inst_dq' (the applied charge per chain)."""
     from . import ops
     ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
     if loops is not None:
@@ -32,6 +35,9 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
     overrelax = int(overrelax)
     if overrelax < 0:
         raise ValueError(f'overrelax: a number of sweeps >= 0 expected, got {overrelax}')
+    instanton = int(instanton)
+    if not 0 <= instanton <= 1024:
+        raise ValueError(f'instanton: a number of hits in 0 .. 1024 expected, got {instanton}')
     action = qed.BatchAction(param.beta)
     histories, fields_arr, run_times = {}, [], []
     for n in range(param.nrun):
@@ -44,6 +50,8 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
             dH, exp_mdH, acc, x = qed.hmc(param, x, verbose=False, integrator=integrator)
             if overrelax:
                 x = qed.overrelax(param, x, overrelax)
+            if instanton:
+                x, inst_k, inst_na = qed.instanton_hit(param, x, instanton)
             qold = history['q'][-1] if 'q' in history else q
             qnew = qed.batch_charges(x)
             dq = torch.sqrt((qnew - qold) ** 2)
@@ -51,6 +59,8 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
             xarr.append(x)
             metrics = {'traj': n * param.ntraj + i + 1, 'dt': time.time() - t1, 'acc': acc.to(DTYPE), 'dH': dH,
                        'plaq': plaq, 'q': qnew, 'dq': dq}
+            if instanton:
+                metrics.update(inst_acc=inst_na.to(DTYPE) / instanton, inst_dq=inst_k)
             for k, v in metrics.items():
                 history.setdefault(k, []).append(v)
             if loops is not None and i % loops_every == 0:

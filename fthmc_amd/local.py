@@ -5,7 +5,8 @@ A heatbath sweep draws every link from its conditional von Mises distribution ex
 overrelaxation sweep reflects every link about its conditional mode and leaves the action unchanged (csrc/local.hip).
 The sampler shares no kernel with the MD path (no force, no integrator, no Metropolis step), so it is an independent check of the
 same exact numbers (utils.observables.exact_wilson_loop).  It does NOT cure topological freezing: a local update changes the
-charge no faster than HMC does; that stays with the flow and the beta ladder (tempering.py)."""
+charge no faster than HMC does; that stays with the flow and the beta ladder (tempering.py) -- and, for the plain action, with the
+instanton hit (csrc/topo.hip), which does: run_local(instanton=k) puts k hits behind every update."""
 from __future__ import annotations
 
 import os
@@ -20,7 +21,7 @@ from .graph_loop import GraphLoop
 
 
 def run_local(param: Param, x: Optional[torch.Tensor] = None, n_overrelax: int = 0, sweeps_per_traj: int = 1, loops=None,
-              loops_every: int = 1, use_graph: Optional[bool] = None):
+              loops_every: int = 1, use_graph: Optional[bool] = None, instanton: int = 0):
     """`param.nrun` runs of `param.ntraj` updates each; one update ("trajectory") is `sweeps_per_traj` compound sweeps of one
     heatbath sweep followed by `n_overrelax` overrelaxation sweeps, at param.beta (param.tau / nstep are not used: there is no MD).
     x: the start of every run, [2, L, L] or a batch [B, 2, L, L] (default param.initializer()).
@@ -28,10 +29,15 @@ def run_local(param: Param, x: Optional[torch.Tensor] = None, n_overrelax: int =
     'dt', 'acc' (identically 1), 'plaq', 'q', 'dq', one entry per update, per chain -- and 'wloops' where loops = (Rmax, Tmax) is
     given (one batch-mean table per `loops_every`-th update, as run_hmc).
     The seeds of update t are ops.chain_seeds(param.seed, chain, t), formed on the device; the sequence of one update is captured
-    once (graph_loop) and replayed (`use_graph`, default on; FTHMC_RUN_GRAPH=0 turns it off): the same bits either way."""
+    once (graph_loop) and replayed (`use_graph`, default on; FTHMC_RUN_GRAPH=0 turns it off): the same bits either way.
+    instanton = k (default 0: nothing changes): k instanton hits (ops.instanton_hit) behind the sweeps of every update, inside the
+    captured sequence, under the update's seeds (hit0 = 0: the seeds are fresh per update; the hit's counter plane is its own).  The
+    history gains 'inst_acc' (accepted / k per chain) and 'inst_dq' (the applied charge per chain)."""
     from . import ops
     from .config import device
-    n_overrelax, sweeps_per_traj, loops_every = int(n_overrelax), int(sweeps_per_traj), max(1, int(loops_every))
+    n_overrelax, sweeps_per_traj, loops_every, instanton = int(n_overrelax), int(sweeps_per_traj), max(1, int(loops_every)), int(instanton)
+    if not 0 <= instanton <= 1024:
+        raise ValueError(f'run_local: instanton: a number of hits in 0 .. 1024 expected, got {instanton}')
     if n_overrelax < 0 or sweeps_per_traj < 1:
         raise ValueError(f'run_local: n_overrelax >= 0 and sweeps_per_traj >= 1 expected, got {n_overrelax}, {sweeps_per_traj}')
     if loops is not None:
@@ -50,17 +56,23 @@ def run_local(param: Param, x: Optional[torch.Tensor] = None, n_overrelax: int =
         xs = x0.clone()
         seeds = torch.empty(B, dtype=torch.int64, device=dev)
         counter = torch.full((1,), n * param.ntraj, dtype=torch.int64, device=dev)      # update t of the whole experiment
-        row = torch.zeros(2 * B + nl, dtype=DTYPE, device=dev)
+        row = torch.zeros(2 * B + nl + (2 * B if instanton else 0), dtype=DTYPE, device=dev)
         obs = {'plaq': row[0:B], 'Q': row[B:2 * B]}
         q0 = ops.wilson_action_charge(xs, param.beta)[1].cpu().numpy()
+        if instanton:
+            iout = {'x': xs, 'k': torch.empty(B, dtype=torch.int32, device=dev), 'nacc': torch.empty(B, dtype=torch.int32, device=dev)}
 
         def enqueue():
             ops.chain_seeds(param.seed, 0, B, 0, counter=counter, advance=True, out=seeds)
             ops.local_update(xs, param.beta, seeds, n_hb=1, n_or=n_overrelax, nsweep=sweeps_per_traj, out=xs)
+            if instanton:
+                ops.instanton_hit(xs, param.beta, seeds, n_hit=instanton, out=iout)
+                row[2 * B + nl:3 * B + nl].copy_(iout['k'])
+                row[3 * B + nl:].copy_(iout['nacc'])
             ops.wilson_action_charge(xs, param.beta, out=obs)
 
         def measure():
-            ops.wilson_loops(xs, loops[0], loops[1], mean_out=row[2 * B:])
+            ops.wilson_loops(xs, loops[0], loops[1], mean_out=row[2 * B:2 * B + nl])
         loop = GraphLoop(enqueue, row, use_graph=use_graph, extra=measure if loops is not None else None, extra_every=loops_every)
         for _ in range(param.ntraj):
             loop.step()
@@ -75,7 +87,10 @@ def run_local(param: Param, x: Optional[torch.Tensor] = None, n_overrelax: int =
                          ('q', torch.from_numpy(q.copy())), ('dq', torch.from_numpy(np.sqrt((q - qold) ** 2)))):
                 history[k].append(v)
             if loops is not None and i % loops_every == 0:
-                history.setdefault('wloops', []).append(torch.from_numpy(rows[i, 2 * B:].reshape(loops).copy()))
+                history.setdefault('wloops', []).append(torch.from_numpy(rows[i, 2 * B:2 * B + nl].reshape(loops).copy()))
+            if instanton:
+                history.setdefault('inst_acc', []).append(torch.from_numpy(rows[i, 3 * B + nl:] / instanton))
+                history.setdefault('inst_dq', []).append(torch.from_numpy(rows[i, 2 * B + nl:3 * B + nl].astype(np.int32)))
             qold = q
         histories[n] = history
         fields_arr.append(xs.clone())

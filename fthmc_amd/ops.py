@@ -100,6 +100,8 @@ def release_workspaces():
     _WS_RETIRED.clear()
     _LOOPS_WS.clear()
     _LOOPS_WS_RETIRED.clear()
+    _INST_WS.clear()
+    _INST_WS_RETIRED.clear()
 
 
 def weights_version(wkey) -> int:
@@ -420,6 +422,90 @@ def local_update(x, beta, seeds=None, n_hb: int = 1, n_or: int = 0, nsweep: int 
     check(_lib.load().fthmc_local_update(_p(x), B, L, 0.0 if bb is not None else float(beta), _p(bb), _p(seeds), n_hb, n_or, nsweep,
                                          sweep0, classes, _p(out), _stream(x)), 'fthmc_local_update')
     return out
+
+
+_INST_WS = {}      # (device index, stream) -> the workspace of instanton_hit's split path (a small buffer of its own, as _LOOPS_WS)
+_INST_WS_RETIRED = []
+
+
+def instanton_ws_bytes(B: int, L: int, path: int = 0) -> int:
+    """Scratch of instanton_hit: 0 where the path that (B, L, path) selects needs none."""
+    return int(_lib.load().fthmc_instanton_ws_bytes(B, L, path))
+
+
+def _inst_ws(t: torch.Tensor, need: int):
+    if need == 0:
+        return None, 0
+    key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream)
+    buf = _INST_WS.get(key)
+    if buf is None or buf.numel() * 8 < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise FthmcError(f'the instanton workspace of this stream would have to be {"allocated" if buf is None else "grown"} ({need} '
+                             f'bytes) during graph capture: run the same call once eagerly on this stream first (warm-up), then capture')
+        if buf is not None:
+            _INST_WS_RETIRED.append(buf)
+        buf = torch.empty((need + 7) // 8, dtype=torch.float64, device=t.device)
+        _INST_WS[key] = buf
+    return buf.data_ptr(), buf.numel() * 8
+
+
+def _instanton_call(x, beta, seeds, n_hit, hit0, path, out, want_cs):
+    x = _field(x); B, _, L, _ = x.shape
+    n_hit, hit0, path = int(n_hit), int(hit0), int(path)
+    if not 0 <= n_hit <= 1024 or hit0 < 0 or hit0 + n_hit > 2 ** 32 or path not in (0, 1, 2):
+        raise ValueError(f'instanton_hit: n_hit in 0 .. 1024, hit0 >= 0 with hit0 + n_hit <= 2^32 and path in 0 .. 2 expected, got '
+                         f'n_hit={n_hit}, hit0={hit0}, path={path}')
+    if n_hit > 0 and seeds is None:
+        raise ValueError('instanton_hit: hits need per-chain seeds')
+    if seeds is not None:
+        if not seeds.is_cuda or seeds.dtype != torch.int64 or seeds.numel() != B:
+            raise FthmcError(f'seeds: expected an int64 tensor of {B} entries on the HIP device')
+        seeds = seeds.contiguous()
+    bb = _beta_b(beta, B)
+    if isinstance(out, torch.Tensor):
+        out = {'x': out}
+    out = {} if out is None else out
+    xo = out.get('x')
+    if xo is None:
+        xo = torch.empty_like(x)
+    elif xo.shape != x.shape or xo.dtype != x.dtype or not xo.is_cuda or not xo.is_contiguous():
+        raise FthmcError('out: expected a contiguous device tensor of the shape of x')
+    ints = []
+    for key in ('k', 'nacc'):
+        t = out.get(key)
+        if t is None:
+            t = torch.empty(B, dtype=torch.int32, device=x.device)
+        elif not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != B:
+            raise FthmcError(f'out[{key!r}]: expected a contiguous int32 device vector of {B} entries')
+        ints.append(t)
+    cs = out.get('cs')
+    if cs is None and want_cs:
+        cs = torch.empty(B, 2, dtype=x.dtype, device=x.device)
+    elif cs is not None and (not cs.is_cuda or cs.dtype != torch.float64 or not cs.is_contiguous() or cs.numel() != 2 * B):
+        raise FthmcError(f"out['cs']: expected a contiguous float64 device tensor of {2 * B} entries")
+    with torch.cuda.device(x.device):
+        ws, nb = _inst_ws(x, instanton_ws_bytes(B, L, path))
+        check(_lib.load().fthmc_instanton_hit(_p(x), B, L, 0.0 if bb is not None else float(beta), _p(bb), _p(seeds), n_hit, hit0, path,
+                                              _p(xo), _p(ints[0]), _p(ints[1]), _p(cs), ws, nb, _stream(x)), 'fthmc_instanton_hit')
+    return xo, ints[0], ints[1], cs
+
+
+def instanton_hit(x, beta, seeds, n_hit: int = 1, hit0: int = 0, path: int = 0, out=None):
+    """`n_hit` instanton hits of the plain Wilson action (C ABI fthmc_instanton_hit) -> (x_new, k, nacc): Metropolis steps k -> k +- 1
+    in the net charge of the proposal x + k A, A the constant-field-strength configuration of charge 1, accepted with
+    min(1, exp(-dS)), dS in closed form from sum cos P and sum sin P of x; then x + k A for the k the steps end with (int32 [B]);
+    nacc (int32 [B]): the accepted steps.  The update that changes the topological charge where HMC and local updates freeze.
+    beta: a number, or a device tensor of B doubles -- per-chain beta.  seeds: int64 [B] on the device (ops.chain_seeds; None with
+    n_hit = 0); `hit0` is the index of the call's first hit in the random stream: a caller that keeps one seed per chain moves it on by
+    n_hit per call, one that draws fresh seeds per call leaves it 0.  path: 0 the library chooses, 1 one workgroup per chain, 2 the
+    split form for a few chains of a large lattice; the same bits.  out: the field to write (may be x), or a dict with any of 'x',
+    'k', 'nacc', 'cs' ([B, 2]: sum cos P, sum sin P of x) to write into.  Not differentiable."""
+    return _instanton_call(x, beta, seeds, n_hit, hit0, path, out, False)[:3]
+
+
+def instanton_sums(x, path: int = 0):
+    """(sum cos P, sum sin P) per chain as instanton_hit reduces them -> [B, 2] (the cs_out of an n_hit = 0 call)."""
+    return _instanton_call(x, 0.0, None, 0, 0, path, None, True)[3]
 
 
 def wilson_force(x, beta: float):

@@ -43,6 +43,9 @@ Operators (reference call site each one replaces):
   local_update(x, beta, beta_b, seeds, n_hb=1, n_or=0, nsweep=1, sweep0=0, classes=15) -> x_new   heatbath / overrelaxation sweeps
                    of the plain Wilson action (ops.local_update; no reference counterpart); beta_b: per-chain beta or None; seeds:
                    int64 [B], None with n_hb = 0.  NOT differentiable
+  instanton_hit(x, beta, beta_b, seeds, n_hit=1, hit0=0) -> (x_new, k, nacc)                  instanton hits of the plain Wilson
+                   action, the Metropolis update across topological sectors (ops.instanton_hit; no reference counterpart); k, nacc:
+                   int32 [B]; beta_b: per-chain beta or None; seeds: int64 [B], None with n_hit = 0.  NOT differentiable
 `act` is the integer code of fthmc_hip.h (0 silu/swish, 1 relu, 2 leaky_relu); `mode` 0 = MD
 semantics, 1 = literal reference leapfrog.  The s/t net's shape travels IN the schema, as plain
 integers: `n_mix` mixture components, `hidden` = hidden_sizes (None = the reference default [8, 8]), `kernel_size` --
@@ -99,6 +102,12 @@ if BACKEND == 'python':
     def local_update(x: torch.Tensor, beta: float, beta_b: Optional[torch.Tensor], seeds: Optional[torch.Tensor], n_hb: int = 1, n_or: int = 0,
                      nsweep: int = 1, sweep0: int = 0, classes: int = 15) -> torch.Tensor:
         return ops.local_update(x, beta if beta_b is None else beta_b, seeds, n_hb, n_or, nsweep, sweep0, classes)
+
+
+    @torch.library.custom_op('fthmc_hip::instanton_hit', mutates_args=(), device_types=_DEV)
+    def instanton_hit(x: torch.Tensor, beta: float, beta_b: Optional[torch.Tensor], seeds: Optional[torch.Tensor], n_hit: int = 1,
+                      hit0: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return ops.instanton_hit(x, beta if beta_b is None else beta_b, seeds, n_hit, hit0)
 
 
     @torch.library.custom_op('fthmc_hip::hmc_trajectory', mutates_args=(), device_types=_DEV)
@@ -250,6 +259,11 @@ def _(x, beta, beta_b, seeds, n_hb=1, n_or=0, nsweep=1, sweep0=0, classes=15):
     return torch.empty_like(x)
 
 
+@torch.library.register_fake('fthmc_hip::instanton_hit')
+def _(x, beta, beta_b, seeds, n_hit=1, hit0=0):
+    return torch.empty_like(x), x.new_empty(x.shape[0], dtype=torch.int32), x.new_empty(x.shape[0], dtype=torch.int32)
+
+
 @torch.library.register_fake('fthmc_hip::hmc_trajectory')
 def _(x, v, u, beta, dt, nstep):
     return torch.empty_like(x), _b(x), _b(x)
@@ -396,10 +410,11 @@ torch.library.register_autograd('fthmc_hip::ft_action_force', _action_force_back
 if BACKEND == 'compiled':                        # the module's names are the dispatcher's operators themselves
     for _n in ('wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x', 'flow_layer_bwd_w',
                'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad', 'ft_action_vjp',
-               'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap', 'wilson_loops', 'local_update'):
+               'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap', 'wilson_loops', 'local_update',
+               'instanton_hit'):
         globals()[_n] = getattr(torch.ops.fthmc_hip, _n)
 
 __all__ = ['wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x',
            'flow_layer_bwd_w', 'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad',
            'ft_action_vjp', 'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap', 'wilson_loops',
-           'local_update']
+           'local_update', 'instanton_hit']

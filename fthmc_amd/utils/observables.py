@@ -1,7 +1,8 @@
 """Host-side analysis of sampling histories: topological-charge tunnelling versus MD-time lag and the
 topological susceptibility; the exact finite-volume Wilson loops of 2D U(1), Creutz ratios and the
 blocked mean of a history of loop tables (`exact_wilson_loop`, `string_tension_exact`, `creutz_ratios`, `loop_table`:
-beyond the reference, which measures no loops).  numpy only; the histories come from
+beyond the reference, which measures no loops); the exact finite-volume distribution of the topological charge
+(`exact_charge_distribution`, `exact_charge_moment`).  numpy only; the histories come from
 `FieldTransformation.run` / `run_hmc` (lists or arrays of per-trajectory charges, optionally per chain).
 
 Reference: ipynb/ft_hmc.py:16-53 (`average`, `sigma`, `sub_avg`, `block_list`, `change_sqr`, `change_sqr_vs_dt`),
@@ -159,3 +160,46 @@ def loop_table(samples, n_block: int = N_BLOCK):
     nb = bm.shape[0]
     err = np.sqrt(bm.var(axis=0) / (nb - 1)) if nb > 1 else np.full(bm.shape[1:], np.nan)
     return bm.mean(axis=0), err
+
+
+# ---------------------------------------------------------------- the topological charge: its exact finite-volume distribution
+def exact_charge_distribution(beta: float, L: int, qmax: int, nmax: int = 12, nodes: int = 200) -> np.ndarray:
+    """P(Q), Q = -qmax .. qmax, of the geometric charge Q = sum wrap(P) / 2 pi of 2D U(1) with the Wilson action on the periodic
+    L x L lattice (V = L^2 plaquettes) -> [2 qmax + 1] float64.  With a theta term the plaquettes decouple sector by sector,
+        Z(theta) = sum_n c_n(theta)^V,     c_n(theta) = int_{-pi}^{pi} dP / 2 pi  e^{beta cos P} cos((theta / 2 pi - n) P),
+    and P(Q) = int_0^{2 pi} d theta / 2 pi  e^{-i theta Q} Z(theta) / Z(0).  c_n by Gauss-Legendre (`nodes` points: the integrand is
+    entire), n = -nmax .. nmax (c_n / c_0 falls like e^{-beta} / (pi n I_0(beta)), taken to the power V), theta by the periodic
+    trapezoid rule on N = max(4 qmax + 4, 256) points (Z is 2 pi-periodic and even: spectrally accurate; the charges the rule
+    aliases onto |Q| <= qmax lie beyond 3 qmax).  V log|c_n| with the common maximum taken out: V = 4096 neither overflows nor
+    underflows.  The caller chooses qmax wide enough for its purpose: the sum of the result is 1 minus the tail beyond qmax
+    (L = 64, beta = 6 needs qmax >= 30 for 1e-10; exact_charge_moment chooses its own)."""
+    beta, V, qmax = float(beta), int(L) * int(L), int(qmax)
+    if not beta > 0.0 or V < 1 or qmax < 0:
+        raise ValueError(f'beta > 0, L >= 1 and qmax >= 0 expected, got {beta}, {L}, {qmax}')
+    LD = np.longdouble
+    g, wg = np.polynomial.legendre.leggauss(int(nodes))
+    P = (LD(np.pi) * g.astype(LD))                                       # nodes on (-pi, pi); the weights carry pi / 2 pi = 1 / 2
+    wP = (wg.astype(LD) * LD(0.5)) * np.exp(LD(beta) * (np.cos(P) - 1))  # e^{-beta} taken out of every c_n: cancels in Z / Z(0)
+    N = max(4 * qmax + 4, 256)
+    a = (np.arange(N, dtype=LD) / N)[:, None] - np.arange(-nmax, nmax + 1, dtype=LD)[None, :]      # theta / 2 pi - n
+    c = (np.cos(a[:, :, None] * P[None, None, :]) * wP).sum(axis=2)
+    logc = V * np.log(np.abs(c))
+    sign = np.where((c < 0) & (V % 2 == 1), LD(-1), LD(1))
+    m = logc.max()
+    Z = (sign * np.exp(logc - m)).sum(axis=1)
+    ratio = Z / Z[0]
+    Q = np.arange(-qmax, qmax + 1)
+    k = np.arange(N)
+    ph = (np.outer(Q, k) % N).astype(LD) * (2 * LD(np.pi) / N)           # the phase reduced in integers first
+    return ((np.cos(ph) * ratio[None, :]).sum(axis=1) / N).astype(np.float64)
+
+
+def exact_charge_moment(beta: float, L: int, power: int = 2) -> float:
+    """<Q^power> of `exact_charge_distribution`, over a range of charges wide enough that the tail beyond it is below 1e-15
+    (eight standard deviations of the wider of the large-beta form V / 4 pi^2 beta and the beta = 0 limit V / 12)."""
+    V = int(L) * int(L)
+    sig2 = V * min(1.0 / 12.0, 1.5 / (4 * np.pi ** 2 * float(beta)))
+    qmax = int(8 * np.sqrt(sig2)) + 6
+    p = exact_charge_distribution(beta, L, qmax)
+    Q = np.arange(-qmax, qmax + 1, dtype=np.float64)
+    return float((Q ** int(power) * p).sum())

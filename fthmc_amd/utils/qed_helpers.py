@@ -329,6 +329,18 @@ def overrelax(param, x: torch.Tensor, n: int = 1):
     return ops.local_update(_batched(x), param.beta, None, n_hb=0, n_or=int(n)).reshape(x.shape)
 
 
+def instanton_hit(param, x: torch.Tensor, n_hit: int = 1, seeds: Optional[torch.Tensor] = None):
+    """`n_hit` instanton hits at param.beta (ops.instanton_hit): Metropolis steps in the net charge k of the proposal x + k A, A the
+    constant-field-strength configuration of charge 1 -> (x_new, k, nacc), k and nacc int32 per chain.  The update that moves the
+    topological charge where HMC and the local updates freeze; exact for the plain Wilson action.  seeds: int64 per chain
+    (ops.chain_seeds); None: drawn from torch's generator."""
+    xb = _batched(x)
+    if seeds is None:
+        seeds = torch.randint(0, 2 ** 63 - 1, (xb.shape[0],), dtype=torch.int64, device=xb.device)
+    xn, k, nacc = ops.instanton_hit(xb, param.beta, seeds, n_hit=int(n_hit))
+    return xn.reshape(x.shape), k, nacc
+
+
 def ft_leapfrog(param, flow, x: torch.Tensor, p: torch.Tensor, integrator: str = 'leapfrog'):
     """ipynb/ft_hmc.py:394-418: the MD in the latent field with the flowed force -> (x', p').
     integrator: 'leapfrog' | 'omelyan' | 'force_gradient' (beyond the reference: csrc/integrator.h)."""
@@ -372,7 +384,7 @@ def ft_hmc(param, flow, field: torch.Tensor, v: Optional[torch.Tensor] = None, u
 
 
 def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[str] = None, verbose: bool = False,
-           use_graph: Optional[bool] = None, integrator: str = 'leapfrog'):
+           use_graph: Optional[bool] = None, integrator: str = 'leapfrog', instanton: int = 0):
     """ipynb/ft_hmc.py:437-487: `param.nrun` x `param.ntraj` physical-field ftHMC trajectories of one
     configuration [2, L, L].  Returns (field, history) with per-trajectory dH, exp_mdH, acc, plaq, topo
     (the notebook returns the field and keeps the histories in module globals); the status lines it prints
@@ -381,9 +393,18 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
     On the device the trajectory sequence (inverse flow, momenta and the uniform from torch's generator, the fused trajectory,
     forward flow, observables) is captured once in a hipGraph and replayed (`use_graph`, default on; FTHMC_RUN_GRAPH=0 turns it
     off): the notebook's loop synchronises five times per trajectory, this one not at all; the histories and the log are
-    written when the loop has run.  Same draws, identical numbers."""
+    written when the loop has run.  Same draws, identical numbers.
+
+    instanton = k (default 0: nothing changes): k instanton hits (instanton_hit) behind every trajectory, before it is measured; the
+    history gains 'inst_acc' (accepted / k) and 'inst_dq' (the applied charge).  The chain's state here is the PHYSICAL field, and
+    the flow only changes how the molecular dynamics proposes: the target density of that field is exp(-S_W).  The hit's proposal
+    x -> x +- A is symmetric and volume-preserving in that field, so its acceptance with the plain Wilson action is exact between
+    flowed trajectories; no Jacobian of the flow enters."""
     import os
     ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
+    instanton = int(instanton)
+    if not 0 <= instanton <= 1024:
+        raise ValueError(f'instanton: a number of hits in 0 .. 1024 expected, got {instanton}')
     if field is None:
         field = param.initializer()[0]
     history = {k: [] for k in ('dH', 'exp_mdH', 'acc', 'plaq', 'topo')}
@@ -405,15 +426,22 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
         put(f'Initial configuration:  plaq: {float(plaq[0])}  topo: {float(Q[0])} {tuple(field.shape)}\n')
         ntot = param.nrun * param.ntraj
         if use_graph and field.is_cuda and ntot > 0:
-            field, rows = _ft_run_captured(param, flow, field, ntot, integrator=integrator)
-            for k, (dH, acc, plaq_, topo, exp_mdH) in enumerate(rows.tolist()):
+            field, rows = _ft_run_captured(param, flow, field, ntot, integrator=integrator, instanton=instanton)
+            for k, (dH, acc, plaq_, topo, exp_mdH, *inst) in enumerate(rows.tolist()):
                 for key, val in zip(history, (dH, exp_mdH, float(acc > 0.5), plaq_, topo)):
                     history[key].append(val)
+                if instanton:
+                    history.setdefault('inst_dq', []).append(int(inst[0]))
+                    history.setdefault('inst_acc', []).append(inst[1] / instanton)
                 put(line(k + 1, dH, exp_mdH, acc > 0.5, plaq_, topo))
         else:
             for n in range(param.nrun):
                 for i in range(param.ntraj):
                     dH, exp_mdH, acc, field_run = ft_hmc(param, flow, field.reshape((1,) + tuple(field.shape[-3:])), integrator=integrator)
+                    if instanton:
+                        field_run, ik, ina = instanton_hit(param, field_run, instanton)
+                        history.setdefault('inst_dq', []).append(int(ik[0]))
+                        history.setdefault('inst_acc', []).append(int(ina[0]) / instanton)
                     field = field_run[0]
                     S, Q, plaq = ops.wilson_action_charge(field_run, param.beta)
                     for k, val in zip(history, (dH, exp_mdH, float(bool(acc)), float(plaq[0]), float(Q[0]))):
@@ -425,9 +453,10 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
     return field, history
 
 
-def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1e-12, integrator: str = 'leapfrog'):
-    """the loop of ft_run as one captured sequence per trajectory -> (final field [2, L, L], rows [ntot, 5] on the host:
-    dH, acc, plaq, Q, exp(-dH))"""
+def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1e-12, integrator: str = 'leapfrog', instanton: int = 0):
+    """the loop of ft_run as one captured sequence per trajectory -> (final field [2, L, L], rows [ntot, 5 or 7] on the host).
+    Row layout: dH, acc, plaq, Q, exp(-dH) -- 5 columns with instanton = 0; with instanton > 0 columns 5 and 6 follow: the applied
+    charge k and the accepted hits."""
     from ..graph_loop import GraphLoop
     dev = field.device
     fs = field.detach().reshape((1,) + tuple(field.shape[-3:])).clone()
@@ -438,7 +467,10 @@ def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1
     wkey = ('ft_run', id(flow), w.data_ptr(), w._version, weights_generation(w), time.monotonic_ns())
     v = torch.empty_like(fs)
     u = torch.empty(1, dtype=torch.float64, device=dev)
-    row = torch.empty(5, dtype=torch.float64, device=dev)
+    row = torch.empty(7 if instanton else 5, dtype=torch.float64, device=dev)
+    if instanton:
+        iseeds = torch.empty(1, dtype=torch.int64, device=dev)
+        iout = {'x': fs, 'k': torch.empty(1, dtype=torch.int32, device=dev), 'nacc': torch.empty(1, dtype=torch.int32, device=dev)}
     res = {'x_new': torch.empty_like(fs), 'dH': row[0:1], 'acc': row[1:2], 'plaq': torch.empty(1, dtype=torch.float64, device=dev),
            'Q': torch.empty(1, dtype=torch.float64, device=dev), 'H0': torch.empty(1, dtype=torch.float64, device=dev),
            'H1': torch.empty(1, dtype=torch.float64, device=dev)}
@@ -450,6 +482,11 @@ def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1
         u.uniform_()
         ops.ft_trajectory(x, v, u, w, nl, param.beta, param.dt, param.nstep, act, mode='md', out=res, wkey=wkey, integrator=integrator)
         fs.copy_(ops.flow_forward(res['x_new'], w, nl, act, wkey=wkey)[0])   # newfield = F(newx)
+        if instanton:
+            torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, device=dev, out=iseeds)
+            ops.instanton_hit(fs, param.beta, iseeds, n_hit=instanton, out=iout)
+            row[5:6].copy_(iout['k'])
+            row[6:7].copy_(iout['nacc'])
         ops.wilson_action_charge(fs, param.beta, out=obs)
         torch.exp(torch.neg(row[0:1]), out=row[4:5])
     loop = GraphLoop(enqueue, row, use_graph=True)

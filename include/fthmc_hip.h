@@ -445,6 +445,33 @@ int fthmc_wilson_loops(const double* x, int B, int L, int Rmax, int Tmax, double
 int fthmc_local_update(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hb, int n_or,
                        int nsweep, int64_t sweep0, int classes, double* x_out, void* stream);
 
+/* ---- Instanton hits: a Metropolis update of the plain Wilson action across topological sectors.  The reference has no counterpart:
+ * it updates by leapfrog molecular dynamics only.  With A the constant-field-strength configuration of charge 1,
+ *     A1[i][j] = (2 pi / L^2) i,      A0[L-1][j] = -(2 pi / L) j,      A0[i][j] = 0 for i < L - 1,
+ * x + k A moves every plaquette by k w, w = 2 pi / L^2 (the one at (L-1, L-1) by k w - 2 pi k).  A call runs n_hit Metropolis steps
+ * in the net charge k, from k = 0, and applies the k it ends with.  Step h = 0 .. n_hit - 1 of chain b reads the Philox4x32-10 block
+ * at counter (hit0 + h, 0, 4, 0) under the key of seeds[b]: u = 1 - u53(words 0, 1) in [0, 1), s = +1 where bit 0 of word 2 is set,
+ * else -1; it accepts k -> k + s iff u < exp(-dS),
+ *     dS = 2 beta s sin(pi / L^2) [C sin theta + Sn cos theta],      theta = ((2 k + s) mod 2 L^2) pi / L^2,
+ * where C = sum cos P and Sn = sum sin P are the sums of the field the call RECEIVED, P(i,j) = x0[i][j] + x1[i+1][j] - x0[i][j+1] -
+ * x1[i][j] (they are not reduced again inside a call).  The net charge is applied as
+ *     x1[i][j]   <- regularize(x1[i][j]   + 2 pi ((k i) mod L^2) / L^2)
+ *     x0[L-1][j] <- regularize(x0[L-1][j] - 2 pi ((k j) mod L) / L)
+ * with the mathematical (non-negative) remainder in 64-bit integers: a shift lies in [0, 2 pi) whatever k, and a link whose reduced
+ * integer is 0 -- all of x0 above its last row, row 0 of x1, column 0 of the last row of x0, everything when k = 0 -- is copied bit
+ * for bit.  beta_b (nullable): per-chain beta [B], read in place of `beta`.  Outputs (each nullable): k_out[B] the applied charge,
+ * nacc_out[B] the accepted steps, cs_out[B][2] = (C, Sn).  x_out may be x.  n_hit = 0 copies the field and writes k = nacc = 0.
+ * path: 1 = one workgroup per chain, the whole call in one launch, no workspace; 2 = a few chains of a large lattice: one wave per
+ * workgroup for the sums, a decision kernel, an apply kernel, workspace fthmc_instanton_ws_bytes; 0 = the library chooses: 2 when
+ * B < 64 and L >= 128, else 1.  Both give the same bits in every output; chain b of a batch equals the chain alone.
+ * fthmc_instanton_ws_bytes is 0 where the path that (B, L, path) selects needs no workspace (and for refused arguments).
+ * Enqueue-only, capturable.  A null x / x_out (seeds: with n_hit > 0), B or L out of range, n_hit outside 0 .. 1024, hit0 < 0 or
+ * hit0 + n_hit > 2^32, path outside 0 .. 2: FTHMC_ERR_ARG; a short (or null) workspace where one is needed: FTHMC_ERR_WS. */
+size_t fthmc_instanton_ws_bytes(int B, int L, int path);
+int fthmc_instanton_hit(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hit, int64_t hit0,
+                        int path, double* x_out, int32_t* k_out /* [B] or NULL */, int32_t* nacc_out /* [B] or NULL */,
+                        double* cs_out /* [B][2] or NULL */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- training ------------------------------------------------------------ */
 /* Reverse-KL loss pieces and weight gradients for a fixed prior draw xi
  * (fthmc/train.py:191-210, fthmc/utils/samplers.py:40-56):
