@@ -1150,7 +1150,8 @@ int fthmc_local_update(const double* x, int B, int L, double beta, const double*
 static bool instanton_split(int B, int L, int path) { return path == 2 || (path == 0 && B < 64 && L >= 128); }
 size_t fthmc_instanton_ws_bytes(int B, int L, int path) {
     if (bad_shape(B, L) || path < 0 || path > 2 || !instanton_split(B, L, path)) return 0;
-    return instanton_part_doubles(B, L) * sizeof(double) + ((size_t)B * sizeof(int32_t) + 7) / 8 * 8;
+    // rounded like every other workspace size (a multiple of 256 bytes), so that a caller may carve one allocation into workspaces
+    return up(instanton_part_doubles(B, L) + ((size_t)B * sizeof(int32_t) + 7) / 8) * sizeof(double);
 }
 int fthmc_instanton_hit(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hit, int64_t hit0,
                         int path, double* x_out, int32_t* k_out, int32_t* nacc_out, double* cs_out, void* ws, size_t ws_bytes, void* stream) {

@@ -464,7 +464,8 @@ int fthmc_local_update(const double* x, int B, int L, double beta, const double*
  * path: 1 = one workgroup per chain, the whole call in one launch, no workspace; 2 = a few chains of a large lattice: one wave per
  * workgroup for the sums, a decision kernel, an apply kernel, workspace fthmc_instanton_ws_bytes; 0 = the library chooses: 2 when
  * B < 64 and L >= 128, else 1.  Both give the same bits in every output; chain b of a batch equals the chain alone.
- * fthmc_instanton_ws_bytes is 0 where the path that (B, L, path) selects needs no workspace (and for refused arguments).
+ * fthmc_instanton_ws_bytes is 0 where the path that (B, L, path) selects needs no workspace (and for refused arguments), else
+ * a multiple of 256 bytes like every workspace size of this header.
  * Enqueue-only, capturable.  A null x / x_out (seeds: with n_hit > 0), B or L out of range, n_hit outside 0 .. 1024, hit0 < 0 or
  * hit0 + n_hit > 2^32, path outside 0 .. 2: FTHMC_ERR_ARG; a short (or null) workspace where one is needed: FTHMC_ERR_WS. */
 size_t fthmc_instanton_ws_bytes(int B, int L, int path);

@@ -104,11 +104,12 @@ int main() {
     }
     const int badP[5] = {-1, 3, 255, 2147483647, -2147483647 - 1};
     for (int k = 0; k < 5; ++k) { Call c; c.path = badP[k]; WANT(c, FTHMC_ERR_ARG, "path outside 0 .. 2 not refused"); }
-    // ---- the workspace rule
+    // ---- the workspace rule (sizes are rounded up to a multiple of 256 bytes, like every workspace size of the header)
+    auto up256 = [](size_t n) { return (n + 255) / 256 * 256; };
     if (fthmc_instanton_ws_bytes(2, 8, 1) != 0 || fthmc_instanton_ws_bytes(2, 8, 0) != 0 || fthmc_instanton_ws_bytes(64, 128, 0) != 0 ||
         fthmc_instanton_ws_bytes(63, 128, 0) == 0 || fthmc_instanton_ws_bytes(63, 128, 0) != fthmc_instanton_ws_bytes(63, 128, 2) ||
-        fthmc_instanton_ws_bytes(2, 8, 2) != 2 * 4 * 2 * sizeof(double) + 8 || fthmc_instanton_ws_bytes(0, 8, 2) != 0 ||
-        fthmc_instanton_ws_bytes(2, 8, 3) != 0 || fthmc_instanton_ws_bytes(FTHMC_MAX_B, FTHMC_MAX_L, 2) != (size_t)FTHMC_MAX_B * 16 * 2 * 8 + ((size_t)FTHMC_MAX_B * 4 + 7) / 8 * 8) {
+        fthmc_instanton_ws_bytes(2, 8, 2) != up256(2 * 4 * 2 * sizeof(double) + 8) || fthmc_instanton_ws_bytes(0, 8, 2) != 0 ||
+        fthmc_instanton_ws_bytes(2, 8, 3) != 0 || fthmc_instanton_ws_bytes(FTHMC_MAX_B, FTHMC_MAX_L, 2) != up256((size_t)FTHMC_MAX_B * 16 * 2 * 8 + ((size_t)FTHMC_MAX_B * 4 + 7) / 8 * 8)) {
         fprintf(stderr, "instanton_walk: fthmc_instanton_ws_bytes\n");
         return 1;
     }

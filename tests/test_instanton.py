@@ -83,7 +83,10 @@ def test_refusals_refuse_and_the_workspace_rule():
     # B < 64 and L >= 128
     wsb = lib.fthmc_instanton_ws_bytes
     assert wsb(2, 8, 1) == 0 and wsb(2, 128, 1) == 0 and wsb(2, 8, 0) == 0 and wsb(64, 128, 0) == 0 and wsb(2, 124, 0) == 0
-    assert wsb(2, 8, 2) == 2 * 4 * 2 * 8 + 8 and wsb(3, 128, 0) == wsb(3, 128, 2) == 3 * 16 * 2 * 8 + 16 and wsb(63, 128, 0) > 0
+    # (rounded up to a multiple of 256 bytes, like every workspace size: tests/test_workspace_contract.py)
+    up = lambda n: (n + 255) // 256 * 256
+    assert wsb(2, 8, 2) == up(2 * 4 * 2 * 8 + 8) == 256 and wsb(3, 128, 0) == wsb(3, 128, 2) == up(3 * 16 * 2 * 8 + 16) == 1024
+    assert wsb(63, 128, 0) > 0
     assert wsb(0, 8, 2) == 0 and wsb(2, 6, 2) == 0 and wsb(2, 8, 3) == 0 and wsb(2, 8, -1) == 0
     need = wsb(2, 8, 2)
     assert call(path=2) == WS and call(path=2, ws=W, nb=need - 1) == WS and call(path=2, ws=None, nb=need) == WS
