@@ -3,6 +3,7 @@ include/fthmc_hip.h).  Inputs must be fp64 tensors on a HIP device; PyTorch only
 provides device memory and the current stream."""
 from __future__ import annotations
 
+import math
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -10,9 +11,11 @@ import torch
 from . import _lib
 from ._lib import ACT_CODES, INTEGRATORS, MODE_LITERAL, MODE_MD, W_PER_LAYER, FthmcError, check
 
-_WS = {}           # (device index, stream) -> workspace tensor (grown on demand)
-_WS_CAPTURED = set()   # keys whose CURRENT workspace was handed out during a graph capture
-_WS_RETIRED = []   # superseded workspaces a captured hipGraph may still point into, kept alive
+# The one scratch cache: (device index, stream) -> the flow workspace, (device index, stream, family) -> the buffer of a call
+# family that keeps its own ('train_force', 'loops', 'instanton'); all grown on demand by _stream_buffer
+_WS = {}
+_WS_CAPTURED = set()   # keys whose CURRENT buffer was handed out during a graph capture
+_WS_RETIRED = []   # superseded buffers a captured hipGraph may still point into, kept alive
 
 
 def _dev(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -43,6 +46,37 @@ def _stream(t: torch.Tensor):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _expect(t, n: int, name: str, dtype=torch.float64):
+    """a caller-supplied tensor the library reads or writes IN PLACE: on the device, contiguous, of `dtype`, n entries"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() != n:
+        raise FthmcError(f'{name}: expected a contiguous {dtype} device tensor of {n} entries')
+    return t
+
+
+def _out(t, shape: tuple, name: str, device, dtype=torch.float64):
+    """the caller's output tensor `t` after the check (written in place: no copy launches behind the kernel in a captured
+    loop), or a fresh one of `shape`"""
+    return torch.empty(shape, dtype=dtype, device=device) if t is None else _expect(t, math.prod(shape), name, dtype)
+
+
+def _out_like(t, x, name: str):
+    """as _out for an output that has the shape of the field `x`"""
+    if t is None:
+        return torch.empty_like(x)
+    if t.shape != x.shape:
+        raise FthmcError(f'{name}: expected the shape of x {tuple(x.shape)}, got {tuple(t.shape)}')
+    return _expect(t, x.numel(), name)
+
+
+def _seeds(seeds, B: int):
+    """per-chain seeds as the library reads them: int64 [B] on the device, made contiguous; None stays None"""
+    if seeds is None:
+        return None
+    if not seeds.is_cuda or seeds.dtype != torch.int64 or seeds.numel() != B:
+        raise FthmcError(f'seeds: expected an int64 tensor of {B} entries on the HIP device')
+    return seeds.contiguous()
+
+
 def ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
     return int(_lib.load().fthmc_ws_bytes(_arch(arch), B, L, n_layers))
 
@@ -57,6 +91,35 @@ def train_force_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
     return int(_lib.load().fthmc_train_force_ws_bytes(_arch(arch), B, L, n_layers))
 
 
+def _stream_buffer(t: torch.Tensor, need: int, family=None, zero_head: bool = False):
+    """-> (pointer, bytes) of the scratch of the current stream of t's device that serves `need` bytes, grown where it is too
+    small.  One buffer per (device, stream): chain groups running on concurrent streams must not share scratch; a `family`
+    keeps a buffer of its own beside the flow workspace.  zero_head: the first fthmc_ws_head_bytes() of a fresh buffer are
+    zeroed."""
+    key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream) + (() if family is None else (family,))
+    buf, capturing = _WS.get(key), torch.cuda.is_current_stream_capturing()
+    if buf is None or buf.numel() * 8 < need:
+        if capturing:
+            # an allocation made here would come from the graph's private pool and the pointer would be
+            # baked into the graph while later eager calls keep using (or replace) the buffer
+            raise FthmcError(f'the {family or "flow"} workspace of this stream would have to be '
+                             f'{"allocated" if buf is None else "grown"} ({need} bytes) during graph capture: run the same call '
+                             f'once eagerly on this stream first (warm-up), then capture')
+        if buf is not None and key in _WS_CAPTURED:
+            _WS_RETIRED.append(buf)        # a graph captured on this stream replays into it: keep it alive
+        # (a buffer no capture ever saw is simply dropped: the allocator orders its reuse behind this stream's work)
+        _WS_CAPTURED.discard(key)
+        buf = torch.empty((need + 7) // 8, dtype=torch.float64, device=t.device)
+        if zero_head:
+            # the head holds the weight expansions and their stamps (include/fthmc_hip.h, "Weight versions"): fresh memory
+            # may carry the stamps of an earlier life of the same address
+            buf[:min(buf.numel(), int(_lib.load().fthmc_ws_head_bytes()) // 8)].zero_()
+        _WS[key] = buf
+    if capturing:
+        _WS_CAPTURED.add(key)
+    return buf.data_ptr(), buf.numel() * 8
+
+
 def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None, vjp: bool = False, force: bool = False):
     if force:
         need = train_force_ws_bytes(B, L, nl, arch)
@@ -66,42 +129,16 @@ def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None
         need = vjp_ws_bytes(B, L, nl, arch)
     else:
         need = int(_lib.load().fthmc_train_ws_bytes(_arch(arch), B, L, nl)) if train else ws_bytes(B, L, nl, arch)
-    # one workspace per (device, stream): chain groups running on concurrent streams must not share scratch
-    key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream)
-    if force:
-        key += ('train_force',)        # a buffer of its own: the dual regions would otherwise stay with every later sampling call
-    buf = _WS.get(key)
-    if buf is None or buf.numel() * 8 < need:
-        if torch.cuda.is_current_stream_capturing():
-            # an allocation made here would come from the graph's private pool and the pointer would be
-            # baked into the graph while later eager calls keep using (or replace) the buffer
-            raise FthmcError(f'the workspace of this stream would have to be {"allocated" if buf is None else "grown"} '
-                             f'({need} bytes) during graph capture: run the same call once eagerly on this stream '
-                             f'first (warm-up), then capture')
-        if buf is not None and key in _WS_CAPTURED:
-            _WS_RETIRED.append(buf)        # a graph captured on this stream replays into it: keep it alive
-        # (a buffer no capture ever saw is simply dropped: the allocator orders its reuse behind this stream's work)
-        _WS_CAPTURED.discard(key)
-        buf = torch.empty((need + 7) // 8, dtype=torch.float64, device=t.device)
-        # the head holds the weight expansions and their stamps (include/fthmc_hip.h, "Weight versions"): fresh memory may
-        # carry the stamps of an earlier life of the same address
-        buf[:min(buf.numel(), int(_lib.load().fthmc_ws_head_bytes()) // 8)].zero_()
-        _WS[key] = buf
-    if torch.cuda.is_current_stream_capturing():
-        _WS_CAPTURED.add(key)
-    return buf.data_ptr(), buf.numel() * 8
+    # train_force: a buffer of its own, the dual regions would otherwise stay with every later sampling call
+    return _stream_buffer(t, need, 'train_force' if force else None, zero_head=True)
 
 
 def release_workspaces():
-    """Drop every cached workspace (current and superseded).  Only when no captured graph that used them will
-    be replayed again."""
+    """Drop every cached workspace (current and superseded, of every family).  Only when no captured graph that used them
+    will be replayed again."""
     _WS.clear()
     _WS_CAPTURED.clear()
     _WS_RETIRED.clear()
-    _LOOPS_WS.clear()
-    _LOOPS_WS_RETIRED.clear()
-    _INST_WS.clear()
-    _INST_WS_RETIRED.clear()
 
 
 def weights_version(wkey) -> int:
@@ -130,20 +167,11 @@ def trajectory_workspaces(x: torch.Tensor, w, n_layers: int, groups=1, arch=None
     (the current stream and the side streams of the chain groups) exists at its final size, holding the expansion of `w`
     -> a token (the workspaces' addresses): a captured sequence stays valid while the token does."""
     x = _field(x); B, _, L, _ = x.shape
-    edges = _group_edges(groups, B)
-    G = len(edges) - 1
-    main = torch.cuda.current_stream(x.device)
-    sides = (list(side_streams)[:G - 1] if side_streams is not None else _side_streams(x.device, G - 1)) if G > 1 else []
-    for st in sides:
-        st.wait_stream(main)
     token = []
-    for gi in list(range(1, G)) + [0]:
-        st = main if gi == 0 else sides[gi - 1]
+    for lo, hi, st in _chain_groups(x.device, _group_edges(groups, B), side_streams):
         with torch.cuda.stream(st):
-            pack_workspace(x, w, n_layers, edges[gi + 1] - edges[gi], L, wkey=wkey, arch=arch)
+            pack_workspace(x, w, n_layers, hi - lo, L, wkey=wkey, arch=arch)
             token.append(_WS[(x.device.index, st.cuda_stream)].data_ptr())
-    for st in sides:
-        main.wait_stream(st)
     return tuple(token)
 
 
@@ -328,15 +356,11 @@ def plaquettes(x):
     return P
 
 
-def _out_vec(out, key, B, like):
-    """out[key] when the caller supplies it (a contiguous float64 device vector of B entries, written in place: no copy
-    launches behind the kernel in a captured loop), else a fresh one"""
+def _out_vec(out, key, B, like, dtype=torch.float64):
+    """out[key] when the caller supplies it (a vector of B entries), else a fresh one; on the path of every eager call: no
+    name is formatted where nothing is wrong"""
     t = None if out is None else out.get(key)
-    if t is None:
-        return torch.empty(B, dtype=like.dtype, device=like.device)
-    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != B:
-        raise FthmcError(f'out[{key!r}]: expected a contiguous float64 device vector of {B} entries')
-    return t
+    return torch.empty(B, dtype=dtype, device=like.device) if t is None else _expect(t, B, f'out[{key!r}]', dtype)
 
 
 def wilson_action_charge(x, beta: float, out=None):
@@ -348,27 +372,13 @@ def wilson_action_charge(x, beta: float, out=None):
     return S, Q, plaq
 
 
-_LOOPS_WS = {}     # (device index, stream) -> the workspace of wilson_loops (its own small buffer: never the flow workspaces of _ws)
-_LOOPS_WS_RETIRED = []   # outgrown ones a captured graph may still point into
-
-
 def wilson_loops_ws_bytes(B: int, L: int, Rmax: int, Tmax: int) -> int:
     """Scratch of wilson_loops; 0 for a refused shape."""
     return int(_lib.load().fthmc_wilson_loops_ws_bytes(B, L, Rmax, Tmax))
 
 
 def _loops_ws(t: torch.Tensor, need: int):
-    key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream)
-    buf = _LOOPS_WS.get(key)
-    if buf is None or buf.numel() * 8 < need:
-        if torch.cuda.is_current_stream_capturing():
-            raise FthmcError(f'the loop workspace of this stream would have to be {"allocated" if buf is None else "grown"} ({need} bytes) '
-                             f'during graph capture: run the same call once eagerly on this stream first (warm-up), then capture')
-        if buf is not None:
-            _LOOPS_WS_RETIRED.append(buf)
-        buf = torch.empty((need + 7) // 8, dtype=torch.float64, device=t.device)
-        _LOOPS_WS[key] = buf
-    return buf.data_ptr(), buf.numel() * 8
+    return _stream_buffer(t, need, 'loops')           # a small buffer of its own: never the flow workspaces of _ws
 
 
 def wilson_loops(x, Rmax: int, Tmax: Optional[int] = None, out=None, mean_out=None):
@@ -382,10 +392,9 @@ def wilson_loops(x, Rmax: int, Tmax: Optional[int] = None, out=None, mean_out=No
     Rmax = int(Rmax); Tmax = Rmax if Tmax is None else int(Tmax)
     if not (1 <= Rmax <= L and 1 <= Tmax <= L):
         raise ValueError(f'wilson_loops: 1 <= Rmax, Tmax <= L = {L} expected, got {Rmax}, {Tmax}')
-    for t, n, name in ((out, B * Rmax * Tmax, 'out'), (mean_out, Rmax * Tmax, 'mean_out')):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n):
-            raise FthmcError(f'{name}: expected a contiguous float64 device tensor of {n} entries')
-    W = torch.empty(B, Rmax, Tmax, dtype=x.dtype, device=x.device) if out is None else out
+    W = _out(out, (B, Rmax, Tmax), 'out', x.device)
+    if mean_out is not None:
+        _expect(mean_out, Rmax * Tmax, 'mean_out')
     need = wilson_loops_ws_bytes(B, L, Rmax, Tmax)
     if need == 0:
         raise FthmcError(f'wilson_loops: shape B={B}, L={L}, Rmax={Rmax}, Tmax={Tmax} is refused (fthmc_wilson_loops_ws_bytes = 0)')
@@ -410,22 +419,10 @@ def local_update(x, beta, seeds=None, n_hb: int = 1, n_or: int = 0, nsweep: int 
                          f'nsweep={nsweep}, sweep0={sweep0}, classes={classes}')
     if n_hb > 0 and seeds is None:
         raise ValueError('local_update: heatbath sweeps need per-chain seeds')
-    if seeds is not None:
-        if not seeds.is_cuda or seeds.dtype != torch.int64 or seeds.numel() != B:
-            raise FthmcError(f'seeds: expected an int64 tensor of {B} entries on the HIP device')
-        seeds = seeds.contiguous()
-    bb = _beta_b(beta, B)
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_cuda or not out.is_contiguous():
-        raise FthmcError('out: expected a contiguous device tensor of the shape of x')
+    seeds, bb, out = _seeds(seeds, B), _beta_b(beta, B), _out_like(out, x, 'out')
     check(_lib.load().fthmc_local_update(_p(x), B, L, 0.0 if bb is not None else float(beta), _p(bb), _p(seeds), n_hb, n_or, nsweep,
                                          sweep0, classes, _p(out), _stream(x)), 'fthmc_local_update')
     return out
-
-
-_INST_WS = {}      # (device index, stream) -> the workspace of instanton_hit's split path (a small buffer of its own, as _LOOPS_WS)
-_INST_WS_RETIRED = []
 
 
 def instanton_ws_bytes(B: int, L: int, path: int = 0) -> int:
@@ -434,19 +431,8 @@ def instanton_ws_bytes(B: int, L: int, path: int = 0) -> int:
 
 
 def _inst_ws(t: torch.Tensor, need: int):
-    if need == 0:
-        return None, 0
-    key = (t.device.index, torch.cuda.current_stream(t.device).cuda_stream)
-    buf = _INST_WS.get(key)
-    if buf is None or buf.numel() * 8 < need:
-        if torch.cuda.is_current_stream_capturing():
-            raise FthmcError(f'the instanton workspace of this stream would have to be {"allocated" if buf is None else "grown"} ({need} '
-                             f'bytes) during graph capture: run the same call once eagerly on this stream first (warm-up), then capture')
-        if buf is not None:
-            _INST_WS_RETIRED.append(buf)
-        buf = torch.empty((need + 7) // 8, dtype=torch.float64, device=t.device)
-        _INST_WS[key] = buf
-    return buf.data_ptr(), buf.numel() * 8
+    """the scratch of instanton_hit's split path (a small buffer of its own, as _loops_ws); no scratch where none is needed"""
+    return _stream_buffer(t, need, 'instanton') if need else (None, 0)
 
 
 def _instanton_call(x, beta, seeds, n_hit, hit0, path, out, want_cs):
@@ -457,37 +443,20 @@ def _instanton_call(x, beta, seeds, n_hit, hit0, path, out, want_cs):
                          f'n_hit={n_hit}, hit0={hit0}, path={path}')
     if n_hit > 0 and seeds is None:
         raise ValueError('instanton_hit: hits need per-chain seeds')
-    if seeds is not None:
-        if not seeds.is_cuda or seeds.dtype != torch.int64 or seeds.numel() != B:
-            raise FthmcError(f'seeds: expected an int64 tensor of {B} entries on the HIP device')
-        seeds = seeds.contiguous()
-    bb = _beta_b(beta, B)
+    seeds, bb = _seeds(seeds, B), _beta_b(beta, B)
     if isinstance(out, torch.Tensor):
         out = {'x': out}
     out = {} if out is None else out
-    xo = out.get('x')
-    if xo is None:
-        xo = torch.empty_like(x)
-    elif xo.shape != x.shape or xo.dtype != x.dtype or not xo.is_cuda or not xo.is_contiguous():
-        raise FthmcError('out: expected a contiguous device tensor of the shape of x')
-    ints = []
-    for key in ('k', 'nacc'):
-        t = out.get(key)
-        if t is None:
-            t = torch.empty(B, dtype=torch.int32, device=x.device)
-        elif not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != B:
-            raise FthmcError(f'out[{key!r}]: expected a contiguous int32 device vector of {B} entries')
-        ints.append(t)
+    xo = _out_like(out.get('x'), x, 'out')
+    k, nacc = (_out_vec(out, key, B, x, torch.int32) for key in ('k', 'nacc'))
     cs = out.get('cs')
-    if cs is None and want_cs:
-        cs = torch.empty(B, 2, dtype=x.dtype, device=x.device)
-    elif cs is not None and (not cs.is_cuda or cs.dtype != torch.float64 or not cs.is_contiguous() or cs.numel() != 2 * B):
-        raise FthmcError(f"out['cs']: expected a contiguous float64 device tensor of {2 * B} entries")
+    if cs is not None or want_cs:
+        cs = _out(cs, (B, 2), "out['cs']", x.device)
     with torch.cuda.device(x.device):
         ws, nb = _inst_ws(x, instanton_ws_bytes(B, L, path))
         check(_lib.load().fthmc_instanton_hit(_p(x), B, L, 0.0 if bb is not None else float(beta), _p(bb), _p(seeds), n_hit, hit0, path,
-                                              _p(xo), _p(ints[0]), _p(ints[1]), _p(cs), ws, nb, _stream(x)), 'fthmc_instanton_hit')
-    return xo, ints[0], ints[1], cs
+                                              _p(xo), _p(k), _p(nacc), _p(cs), ws, nb, _stream(x)), 'fthmc_instanton_hit')
+    return xo, k, nacc, cs
 
 
 def instanton_hit(x, beta, seeds, n_hit: int = 1, hit0: int = 0, path: int = 0, out=None):
@@ -525,9 +494,8 @@ def kinetic(v):
 def stats_accumulate(acc, plaq, Q, qold, dH, vec):
     """vec[8] += sums over the chains of (1, acc, plaq, Q, Q^2, |Q - qold|, dH, exp(-dH)); qold <- Q (in place)."""
     B = acc.numel()
-    for t, n in ((acc, B), (plaq, B), (Q, B), (qold, B), (dH, B), (vec, 8)):
-        if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n:
-            raise FthmcError('stats_accumulate: contiguous float64 device tensors of B (vec: 8) elements expected')
+    for t, n, name in ((acc, B, 'acc'), (plaq, B, 'plaq'), (Q, B, 'Q'), (qold, B, 'qold'), (dH, B, 'dH'), (vec, 8, 'vec')):
+        _expect(t, n, 'stats_accumulate: ' + name)
     check(_lib.load().fthmc_stats_accumulate(_p(acc), _p(plaq), _p(Q), _p(qold), _p(dH), B, _p(vec), _stream(acc)),
           'fthmc_stats_accumulate')
 
@@ -535,20 +503,11 @@ def stats_accumulate(acc, plaq, Q, qold, dH, vec):
 def random_momenta(seeds, shape, need_u=True, out_v=None, out_u=None):
     """v ~ N(0,1) of `shape` = (B, 2, L, L) and u ~ U[0,1) [B] from per-chain int64 seeds
     (written into out_v / out_u when given: contiguous float64 device tensors of those shapes)."""
-    if not seeds.is_cuda or seeds.dtype != torch.int64:
-        raise FthmcError('seeds: expected an int64 tensor on the HIP device')
-    seeds = seeds.contiguous()
-    B = int(shape[0]); n = 1
-    for d in shape[1:]:
-        n *= int(d)
-    if seeds.numel() != B:
-        raise FthmcError(f'seeds: expected {B}, got {seeds.numel()}')
-    for t, want in ((out_v, B * n), (out_u, B)):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != want):
-            raise FthmcError('random_momenta: out tensors must be contiguous float64 device tensors of the result shapes')
-    v = out_v if out_v is not None else torch.empty(tuple(shape), dtype=torch.float64, device=seeds.device)
-    u = out_u if out_u is not None else (torch.empty(B, dtype=torch.float64, device=seeds.device) if need_u else None)
-    check(_lib.load().fthmc_random_momenta(_p(seeds), B, n, _p(v), _p(u), _stream(v)), 'fthmc_random_momenta')
+    shape = tuple(int(d) for d in shape); B = shape[0]
+    seeds = _seeds(seeds, B)
+    v = _out(out_v, shape, 'random_momenta: out_v', seeds.device)
+    u = _out(out_u, (B,), 'random_momenta: out_u', seeds.device) if need_u or out_u is not None else None
+    check(_lib.load().fthmc_random_momenta(_p(seeds), B, math.prod(shape[1:]), _p(v), _p(u), _stream(v)), 'fthmc_random_momenta')
     return v, u
 
 
@@ -557,12 +516,11 @@ def chain_seeds(seed: int, lo: int, B: int, traj: int = 0, counter: Optional[tor
     """Per-chain int64 seeds of trajectory / step `traj (+ counter[0])` for the global chain ids lo .. lo + B - 1, formed on
     the device (C ABI fthmc_chain_seeds): the same numbers as parallel.chain_seeds.  `counter`: a device int64 scalar added
     to `traj`; advance=True adds 1 to it behind the read, so that a captured launch draws fresh seeds at every replay."""
-    if out is None:
+    if out is None:                     # checked like a caller's: `device` may name the host
         out = torch.empty(B, dtype=torch.int64, device=device if device is not None else counter.device)
-    if not out.is_cuda or out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != B:
-        raise FthmcError(f'chain_seeds: out must be a contiguous int64 device tensor of {B} entries')
-    if counter is not None and (not counter.is_cuda or counter.dtype != torch.int64 or counter.numel() != 1):
-        raise FthmcError('chain_seeds: counter must be one int64 on the HIP device')
+    _expect(out, B, 'chain_seeds: out', torch.int64)
+    if counter is not None:
+        _expect(counter, 1, 'chain_seeds: counter', torch.int64)
     check(_lib.load().fthmc_chain_seeds(int(seed), int(lo), int(B), int(traj), _p(counter), int(bool(advance)), _p(out),
                                         _stream(out)), 'fthmc_chain_seeds')
     return out
@@ -572,19 +530,11 @@ def random_uniform(seeds, shape, lo: float, hi: float, out=None):
     """U[lo, hi) of `shape` = (B, ...) from per-chain int64 seeds: the prior draw of a training step on the device.
     Half-open on (0, 1) and (-pi, pi); on a range whose width is not above |hi| the last rounding can return hi itself
     (include/fthmc_hip.h, fthmc_random_uniform)."""
-    if not seeds.is_cuda or seeds.dtype != torch.int64:
-        raise FthmcError('seeds: expected an int64 tensor on the HIP device')
-    seeds = seeds.contiguous()
-    B = int(shape[0]); n = 1
-    for d in shape[1:]:
-        n *= int(d)
-    if seeds.numel() != B:
-        raise FthmcError(f'seeds: expected {B}, got {seeds.numel()}')
-    if out is None:
-        out = torch.empty(tuple(shape), dtype=torch.float64, device=seeds.device)
-    elif not out.is_cuda or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != B * n:
-        raise FthmcError('random_uniform: out must be a contiguous float64 device tensor of the result shape')
-    check(_lib.load().fthmc_random_uniform(_p(seeds), B, n, float(lo), float(hi), _p(out), _stream(out)), 'fthmc_random_uniform')
+    shape = tuple(int(d) for d in shape); B = shape[0]
+    seeds = _seeds(seeds, B)
+    out = _out(out, shape, 'random_uniform: out', seeds.device)
+    check(_lib.load().fthmc_random_uniform(_p(seeds), B, math.prod(shape[1:]), float(lo), float(hi), _p(out), _stream(out)),
+          'fthmc_random_uniform')
     return out
 
 
@@ -595,10 +545,7 @@ def train_metrics(xi, x, logq, logp, beta: float, dkl_factor: float = 1.0, out=N
     logq = _dev(logq, 'logq').reshape(-1); logp = _dev(logp, 'logp').reshape(-1)
     if logq.numel() != B or logp.numel() != B or xi.shape != x.shape:
         raise FthmcError(f'train_metrics: expected logq, logp of {B} entries and xi shaped like x')
-    if out is None:
-        out = torch.empty(2 + 5 * B, dtype=torch.float64, device=x.device)
-    elif not out.is_cuda or out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 + 5 * B:
-        raise FthmcError(f'train_metrics: out must be a contiguous float64 device tensor of {2 + 5 * B} entries')
+    out = _out(out, (2 + 5 * B,), 'train_metrics: out', x.device)
     ws, nb = _ws(x, B, L, 0)
     check(_lib.load().fthmc_train_metrics(_p(xi), _p(x), _p(logq), _p(logp), B, L, float(beta), float(dkl_factor),
                                           _p(out), ws, nb, _stream(x)), 'fthmc_train_metrics')
@@ -610,9 +557,8 @@ def adam_step(w, gw, exp_avg, exp_avg_sq, hyper, betas=(0.9, 0.999), eps: float 
     """One Adam (AdamW: decoupled=True) step on flat fp64 device buffers, in place, ONE launch (C ABI fthmc_adam_step).
     `hyper` = [steps taken, learning rate, 0] on the device: the launch reads both from there and moves the count on."""
     n = w.numel()
-    for t, want in ((w, n), (gw, n), (exp_avg, n), (exp_avg_sq, n), (hyper, 3)):
-        if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != want:
-            raise FthmcError('adam_step: contiguous float64 device tensors expected (w, gw, exp_avg, exp_avg_sq alike; hyper: 3)')
+    for t, want, name in ((w, n, 'w'), (gw, n, 'gw'), (exp_avg, n, 'exp_avg'), (exp_avg_sq, n, 'exp_avg_sq'), (hyper, 3, 'hyper')):
+        _expect(t, want, 'adam_step: ' + name)
     check(_lib.load().fthmc_adam_step(_p(w), _p(gw), _p(exp_avg), _p(exp_avg_sq), _p(hyper), n, float(betas[0]), float(betas[1]),
                                       float(eps), float(weight_decay), int(bool(decoupled)), _stream(w)), 'fthmc_adam_step')
 
@@ -669,11 +615,7 @@ def leapfrog(x, p, beta: float, dt: float, nstep: int, integrator='leapfrog'):
 def _beta_b(beta, B: int):
     """beta as the per-chain device array of the `_pb` entry points (a tensor of B doubles, used IN PLACE: a replica exchange
     updates it between calls), or None for a Python number: the scalar entry points, untouched."""
-    if not isinstance(beta, torch.Tensor):
-        return None
-    if not beta.is_cuda or beta.dtype != torch.float64 or not beta.is_contiguous() or beta.numel() != B:
-        raise FthmcError(f'beta: a per-chain beta is a contiguous float64 device tensor of {B} entries')
-    return beta.view(-1)
+    return _expect(beta, B, 'beta (per chain)').view(-1) if isinstance(beta, torch.Tensor) else None
 
 
 def hmc_trajectory(x, v, u, beta, dt: float, nstep: int, out=None, integrator='leapfrog'):
@@ -684,11 +626,9 @@ def hmc_trajectory(x, v, u, beta, dt: float, nstep: int, out=None, integrator='l
     if u.numel() != B:
         raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
     bb = _beta_b(beta, B)
-    xn = None if out is None else out.get('x_new')
-    if xn is None:
-        xn = torch.empty_like(x)
-    elif xn.shape != x.shape or xn.dtype != x.dtype or not xn.is_cuda or not xn.is_contiguous() or xn.data_ptr() == x.data_ptr():
-        raise FthmcError('out[\'x_new\']: expected a contiguous device tensor of the shape of x that is not x')
+    xn = _out_like(None if out is None else out.get('x_new'), x, "out['x_new']")
+    if xn.data_ptr() == x.data_ptr():
+        raise FthmcError("out['x_new']: must not be x")
     dH, acc, H0, H1 = (_out_vec(out, k, B, x) for k in ('dH', 'acc', 'H0', 'H1'))
     ws, nb = _ws(x, B, L, 0)
     lib, head, step = _lib.load(), (_p(x), _p(v), _p(u), B, L), (float(dt), int(nstep))
@@ -704,12 +644,6 @@ def hmc_trajectory(x, v, u, beta, dt: float, nstep: int, out=None, integrator='l
 
 
 # ---------------------------------------------------------------- replica exchange (parallel tempering)
-def _i32(t, n: int, name: str):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n:
-        raise FthmcError(f'{name}: expected a contiguous int32 device tensor of {n} entries')
-    return t
-
-
 def ladder_init(betas, n_ladders: int, device=None):
     """M = n_ladders ladders of K = len(betas) consecutive chains, every ladder in order (C ABI fthmc_ladder_init) ->
     dict(betas [K], beta_b [M K], rung [M K] int32, chain_of [M K] int32) on the device.  betas: strictly increasing."""
@@ -743,16 +677,13 @@ def replica_swap(betas, C, u, beta_b, rung, chain_of, parity: int, out: Optional
     C = _dev(C, 'C').reshape(-1); u = _dev(u, 'u').reshape(-1)
     if C.numel() != B or u.numel() != M * (K - 1):
         raise FthmcError(f'replica_swap: expected C [{B}] and u [{M}, {K - 1}]')
-    _i32(rung, B, 'rung'); _i32(chain_of, B, 'chain_of')
+    _expect(rung, B, 'rung', torch.int32); _expect(chain_of, B, 'chain_of', torch.int32)
     if int(parity) not in (0, 1):
         raise ValueError(f'parity: 0 or 1, got {parity!r}')
     if out is None:
         out = {}
     for k in ('swap_acc', 'd'):
-        if k not in out:
-            out[k] = torch.empty(M, K - 1, dtype=torch.float64, device=beta_b.device)
-        elif not out[k].is_cuda or out[k].dtype != torch.float64 or not out[k].is_contiguous() or out[k].numel() != M * (K - 1):
-            raise FthmcError(f'out[{k!r}]: expected a contiguous float64 device tensor of {M * (K - 1)} entries')
+        out[k] = _out(out.get(k), (M, K - 1), f'out[{k!r}]', beta_b.device)
     with torch.cuda.device(beta_b.device):
         check(_lib.load().fthmc_replica_swap(_p(betas), K, M, int(parity), _p(C), _p(u), _p(beta_b), _p(rung), _p(chain_of),
                                              _p(out['swap_acc']), _p(out['d']), _stream(beta_b)), 'fthmc_replica_swap')
@@ -801,10 +732,7 @@ def flow_layer_fwd_stash(x, w, mu: int, off: int, act='silu', arch=None, inplace
     if nbytes == 0:
         return (*flow_layer_fwd(x, w, mu, off, act, arch=a, inplace=inplace), None)
     y = x if inplace else torch.empty_like(x); logJ = torch.empty(B, dtype=x.dtype, device=x.device)
-    if stash is None:
-        stash = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
-    elif stash.dtype != torch.float64 or not stash.is_cuda or not stash.is_contiguous() or stash.numel() != nbytes // 8:
-        raise FthmcError(f'stash: expected a contiguous float64 device tensor of {nbytes // 8} entries')
+    stash = _out(stash, (nbytes // 8,), 'stash', x.device)
     ws, nb = _ws(x, B, L, 1, arch=a)
     check(_lib.load().fthmc_flow_layer_fwd_stash(_p(x), _p(w), ap, B, L, int(mu), int(off), act_code(act), _p(y), _p(logJ),
                                                  _p(stash), ws, nb, _stream(x)), 'fthmc_flow_layer_fwd_stash')
@@ -1020,6 +948,25 @@ def _side_streams(device, n: int):
     return pool[:n]
 
 
+def _chain_groups(device, edges, side_streams=None):
+    """The fork and join of a call that runs the chain groups lo .. hi - 1 of `edges` (_group_edges) on concurrent streams.  A
+    generator: the side streams (the caller's `side_streams`, else this device's pool) wait for the current stream before
+    anything of the call is on it; then (lo, hi, stream) of the groups 1 .. G - 1 on the side streams and of group 0, last, on
+    the current stream -- the caller enqueues a group's work under torch.cuda.stream(stream) --; behind the last group the current
+    stream waits for the side streams."""
+    G = len(edges) - 1
+    main = torch.cuda.current_stream(device)
+    sides = [] if G == 1 else list(side_streams)[:G - 1] if side_streams is not None else _side_streams(device, G - 1)
+    if len(sides) != G - 1:
+        raise FthmcError(f'side_streams: {G - 1} streams needed for {G} chain groups')
+    for st in sides:
+        st.wait_stream(main)
+    for gi in list(range(1, G)) + [0]:
+        yield edges[gi], edges[gi + 1], main if gi == 0 else sides[gi - 1]
+    for st in sides:
+        main.wait_stream(st)
+
+
 def ft_trajectory(x, v, u, w, n_layers: int, beta, dt: float, nstep: int, act='silu', mode='md',
                   out: Optional[dict] = None, state_in: Optional[torch.Tensor] = None, groups: int = 1, arch=None, wkey=None,
                   side_streams=None, integrator='leapfrog'):
@@ -1055,40 +1002,23 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta, dt: float, nstep: int, act='s
             out[k] = torch.empty(B, dtype=x.dtype, device=x.device)
     if 'state' not in out:
         out['state'] = torch.empty(3, B, dtype=x.dtype, device=x.device)
-    edges = _group_edges(groups, B)                                     # an int, or explicit group sizes (chains per group)
-    G = len(edges) - 1
-    if G > 1:
-        arch_ = a
-        if state_in is not None:
-            state_in = _dev(state_in, 'state_in')
-            if state_in.numel() != 3 * B:
-                raise FthmcError(f'state_in: expected [3, {B}]')
-            state_in = state_in.reshape(3, B)
-        main = torch.cuda.current_stream(x.device)
-        sides = list(side_streams)[:G - 1] if side_streams is not None else _side_streams(x.device, G - 1)
-        if len(sides) != G - 1:
-            raise FthmcError(f'side_streams: {G - 1} streams needed for {G} chain groups')
-        parts = []
-        for st in sides:                                                # fork before anything of this call is on `main`
-            st.wait_stream(main)
-        for gi in list(range(1, G)) + [0]:
-            a, b_ = edges[gi], edges[gi + 1]
-            st = main if gi == 0 else sides[gi - 1]
-            with torch.cuda.stream(st):
-                og = {k: t[a:b_] for k, t in out.items() if k != 'state'}
-                sg = state_in[:, a:b_].contiguous() if state_in is not None else None
-                ft_trajectory(x[a:b_], v[a:b_], u[a:b_], w, n_layers, beta if bb is None else bb[a:b_], dt, nstep, act, mode, og, sg,
-                              arch=arch_, wkey=wkey,
-                              integrator=integrator)                    # one group: no side streams
-                out['state'][:, a:b_].copy_(og['state'])
-                parts.append(og)                                        # keep the group's temporaries alive until the join
-        for st in sides:
-            main.wait_stream(st)
-        return out
     if state_in is not None:
         state_in = _dev(state_in, 'state_in')
         if state_in.numel() != 3 * B:
             raise FthmcError(f'state_in: expected [3, {B}]')
+        state_in = state_in.reshape(3, B)
+    edges = _group_edges(groups, B)                                     # an int, or explicit group sizes (chains per group)
+    if len(edges) > 2:
+        parts = []
+        for lo, hi, st in _chain_groups(x.device, edges, side_streams):
+            with torch.cuda.stream(st):
+                og = {k: t[lo:hi] for k, t in out.items() if k != 'state'}
+                sg = state_in[:, lo:hi].contiguous() if state_in is not None else None
+                ft_trajectory(x[lo:hi], v[lo:hi], u[lo:hi], w, n_layers, beta if bb is None else bb[lo:hi], dt, nstep, act, mode, og,
+                              sg, arch=a, wkey=wkey, integrator=integrator)    # one group: no side streams
+                out['state'][:, lo:hi].copy_(og['state'])
+                parts.append(og)                                        # keep the group's temporaries alive until the join
+        return out
     m = {'md': MODE_MD, 'literal': MODE_LITERAL, 'reference_literal': MODE_LITERAL}[mode]
     ws, nb = _ws(x, B, L, n_layers, arch=a)
     lib, wv = _lib.load(), weights_version(wkey)
@@ -1110,33 +1040,25 @@ def train_grad(xi, w, n_layers: int, beta: float, act='silu', need_gw=True, grou
     mean_b (logq - logp) wrt the packed weights (written into `out_gw` when given: a contiguous float64 device tensor
     of w.numel() entries, e.g. the flat gradient buffer the conv parameters' .grad are views of).
 
-    groups > 1: the chains are split into contiguous groups that run on concurrent streams (as in
+    groups > 1: the chains are split into contiguous groups (a list gives the group sizes) that run on concurrent streams (as in
     ft_trajectory); the groups' weight gradients are combined with weights B_g / B."""
     xi = _field(xi, 'xi'); B, _, L, _ = xi.shape
     w, ap, arch_ = _wall(w, n_layers, arch)
-    G = max(1, min(int(groups), B))
-    if out_gw is not None and (not out_gw.is_cuda or out_gw.dtype != torch.float64 or not out_gw.is_contiguous()
-                               or out_gw.numel() != w.numel()):
-        raise FthmcError(f'train_grad: out_gw must be a contiguous float64 device tensor of {w.numel()} entries')
+    if out_gw is not None:
+        _expect(out_gw, w.numel(), 'train_grad: out_gw')
     if _out is None:
         x = torch.empty_like(xi)
         logq, logp = (torch.empty(B, dtype=xi.dtype, device=xi.device) for _ in range(2))
     else:
         x, logq, logp = _out
-    if G > 1:
-        gws = torch.empty(G, w.numel(), dtype=xi.dtype, device=xi.device) if need_gw else None
-        main = torch.cuda.current_stream(xi.device)
-        sides = _side_streams(xi.device, G - 1)
-        for st in sides:
-            st.wait_stream(main)
-        for gi in list(range(1, G)) + [0]:
-            a, b_ = gi * B // G, (gi + 1) * B // G
-            with torch.cuda.stream(main if gi == 0 else sides[gi - 1]):
-                r = train_grad(xi[a:b_], w, n_layers, beta, act, need_gw, 1, (x[a:b_], logq[a:b_], logp[a:b_]), arch=arch_)
+    edges = _group_edges(groups, B)
+    if len(edges) > 2:
+        gws = torch.empty(len(edges) - 1, w.numel(), dtype=xi.dtype, device=xi.device) if need_gw else None
+        for lo, hi, st in _chain_groups(xi.device, edges):
+            with torch.cuda.stream(st):
+                r = train_grad(xi[lo:hi], w, n_layers, beta, act, need_gw, 1, (x[lo:hi], logq[lo:hi], logp[lo:hi]), arch=arch_)
                 if need_gw:
-                    torch.mul(r['gw'], (b_ - a) / B, out=gws[gi])
-        for st in sides:
-            main.wait_stream(st)
+                    torch.mul(r['gw'], (hi - lo) / B, out=gws[edges.index(lo)])    # row g for group g: the sum below adds in group order
         if need_gw and out_gw is not None:
             torch.sum(gws, 0, out=out_gw)
         return {'x': x, 'logq': logq, 'logp': logp,
@@ -1157,9 +1079,8 @@ def train_force_grad(xi, w, n_layers: int, beta: float, act='silu', need_gw=True
     xi = _field(xi, 'xi'); B, _, L, _ = xi.shape
     w, ap, a = _wall(w, n_layers, arch)
     need_gw = bool(need_gw and n_layers)
-    if out_gw is not None and need_gw and (not out_gw.is_cuda or out_gw.dtype != torch.float64 or not out_gw.is_contiguous()
-                                           or out_gw.numel() != w.numel()):
-        raise FthmcError(f'train_force_grad: out_gw must be a contiguous float64 device tensor of {w.numel()} entries')
+    if out_gw is not None and need_gw:
+        _expect(out_gw, w.numel(), 'train_force_grad: out_gw')
     F = torch.empty_like(xi)
     fsq = torch.empty(B, dtype=xi.dtype, device=xi.device)
     gw = None
