@@ -1,18 +1,12 @@
-// extern "C" entry points of libfthmc_hip.so (include/fthmc_hip.h) and the host-side
-// kernel sequencing behind them.  Every function only enqueues work on the caller's
-// stream; scratch comes from the caller's workspace, so the whole sequence of a
-// trajectory can be captured into a hipGraph by the caller.
-#include "common.h"
-#include "kernels.h"
+// extern "C" entry points of libfthmc_hip.so (include/fthmc_hip.h), first order, and the host-side kernel sequencing behind them.
+// Every function only enqueues work on the caller's stream; scratch comes from the caller's workspace, so the whole sequence of a
+// trajectory can be captured into a hipGraph by the caller.  How a call is opened: api_call.h; the second order and force
+// training: api_second_order.hip; the timers and profilers: api_diag.hip.
+#include "api_call.h"
 #include "topo_int.h"
-#include "dual.h"
 #include <math.h>
-
 #include <stdio.h>
 #include <stdlib.h>
-#include <utility>
-
-using namespace fthmc;
 
 namespace fthmc {
 static thread_local char g_last_error[256] = "";
@@ -23,199 +17,18 @@ void note_hip_error(hipError_t e, const char* file, int line) {
 
 namespace {
 
-constexpr size_t ALIGN = 32;   // doubles (256 B)
-inline size_t up(size_t n) { return (n + ALIGN - 1) / ALIGN * ALIGN; }
-
-struct WS {
-    double *wint, *X, *gp, *gp2, *gp_part, *lj_part, *scal, *act_part, *xa, *va, *xb, *vb, *gw_part, *gw_tmp, *stash, *gz;
-    double *hbuf, *gbuf;   // generic net shapes (flow_generic.hip): activation scratch, gradient ping-pong
-    size_t n2;       // doubles per field batch: B * 2 * L * L
-    size_t gw_rows, gw_tmp_rows;   // rows of FLOW_GW_STRIDE doubles in gw_part / gw_tmp
-    size_t total;    // doubles
-};
-
-// scal slots, each B doubles
-enum { SC_S = 0, SC_Q, SC_PLAQ, SC_LOGDET, SC_K, SC_H0, SC_H1, SC_OLD0, SC_OLD1, SC_OLD2, SC_NEW0, SC_NEW1, SC_NEW2, SC_SEFF, SC_N };
-
-// What a call runs with: the net's shape (an ARGUMENT of the call: fthmc_arch_t), the two process-wide debug switches read
-// ONCE per call, the caller's canonical weights and stream.  Nothing below reads a global.
-struct Ctx {
-    FlowArch A;
-    bool mfma;               // fthmc_set_variant: MFMA kernels (default) / VALU kernels
-    bool small_on;           // fthmc_set_small_path
-    const double* wcan;      // the caller's canonical weights (generic net shapes read them as they are)
-    hipStream_t s;
-    bool gen() const { return !A.is_default(); }
-    bool small(int L, int nl) const { return small_on && mfma && A.is_default() && ft_small_shape(L, nl); }
-};
-inline int make_ctx(const fthmc_arch_t* arch, void* stream, Ctx* c) {
-    c->A = flow_arch_default();
-    if (arch) { int rc = make_flow_arch(arch->n_hidden, arch->hidden, arch->kernel_size, arch->n_mix, arch->final_tanh, &c->A); if (rc != FTHMC_OK) return rc; }
-    c->mfma = get_flow_variant() == 1;
-    c->small_on = get_small_path() != 0;
-    c->wcan = nullptr;
-    c->s = ft_stream(stream);
-    return FTHMC_OK;
-}
-
-// The calls whose training backward computes the layer's weight gradients itself (flow_bwd_train.hip) and leaves every layer's
-// partials side by side: ws_layout sizes the rows force_gp then finds
-inline bool fused_train_bwd(const FlowArch& A, int B, int L) { return A.is_default() && flow_bwd_train_shape(L) && flow_stash_fits32(B, L, true); }
-
-WS ws_layout(const FlowArch& A, double* base, int B, int L, int nl, bool train = false) {
-    WS w{};
-    const size_t n1 = (size_t)B * L * L, n2 = 2 * n1;
-    const size_t nt = flow_ntiles_max(L);
-    size_t o = 0;
-    auto take = [&](size_t n) { double* p = base ? base + o : nullptr; o += up(n); return p; };
-    w.n2 = n2;
-    // the weight expansions: a FIXED head of FLOW_WHEAD_LAYERS layer regions in every layout (kernels.h: no call of any shape puts
-    // another region there, so the stamps of k_pack_weights vouch for what sits behind them), longer for deeper flows
-    w.wint = take((size_t)(nl > FLOW_WHEAD_LAYERS ? nl : FLOW_WHEAD_LAYERS) * FLOW_WINT);
-    w.X = take((size_t)nl * n2);
-    w.gp = take(n1);
-    w.gp2 = take(nl > 0 ? n1 : 0);                       // second plaquette-gradient field (gather-form backward)
-    w.gp_part = take(nl > 0 ? (size_t)B * flow_gp_part_max(L) : 0);
-    w.lj_part = take((size_t)(nl > 0 ? nl : 1) * B * nt);               // logJ partials [layer][chain][tile] of a sweep
-    w.scal = take((size_t)SC_N * B);
-    w.act_part = take((size_t)32 * B);                   // launch_action_charge's wave sums (few chains of a large lattice)
-    w.xa = take(n2); w.va = take(n2); w.xb = take(n2); w.vb = take(n2);
-    // small lattices in training: the weight-gradient partials (and reduction rows) of ALL layers at once
-    const size_t nlw = train && A.is_default() && ft_small_shape(L, nl) ? (size_t)nl : 1;
-    w.gw_rows = nl > 0 ? nlw * B * nt : 0;
-    w.gw_tmp_rows = nl > 0 ? nlw * FLOW_REDUCE_GROUPS : 0;
-    if (train && nl > 0 && fused_train_bwd(A, B, L)) {                    // ONE reduction behind the sweep
-        const size_t np = (size_t)flow_bwd_train_nparts(B, L), ng = (size_t)flow_reduce_groups((int)np);
-        if (w.gw_rows < (size_t)nl * np) w.gw_rows = (size_t)nl * np;
-        if (w.gw_tmp_rows < (size_t)nl * ng) w.gw_tmp_rows = (size_t)nl * ng;
-    }
-    w.gw_part = take(w.gw_rows * FLOW_GW_STRIDE);
-    w.gw_tmp = take(w.gw_tmp_rows * FLOW_GW_STRIDE);
-    const bool gen = !A.is_default();
-    // activation stash of a force evaluation (generic shapes: every layer's planes, at least one region as scratch)
-    w.stash = take(gen ? (size_t)(nl > 0 ? nl : 1) * A.stash_doubles(B, L) : (size_t)nl * flow_stash_doubles(B, L, train));
-    // training: pre-activation gradients of the layer in flight; small lattices (flow_small.hip: one launch runs all layers
-    // forward and backward): of every layer
-    w.gz = take(train && nl > 0 && !gen ? flow_gz_doubles(B, L) * (ft_small_shape(L, nl) ? (size_t)nl : 1) : 0);
-    w.hbuf = take(gen ? (size_t)B * A.cmax() * L * L : 0);
-    w.gbuf = take(gen ? (size_t)2 * B * A.cmax() * L * L : 0);
-    w.total = o;
-    return w;
-}
-
-// Workspace of the second-order entry points (fthmc_ft_action_vjp, fthmc_ft_force_vjp): the head of every layout (the weight
-// expansions and their stamps, fthmc_ws_head_bytes()) is skipped and never written; behind it, regions sized in dual numbers (the
-// action VJP runs the double kernels in their first halves): the dual input x + eps g, every layer's output and activation
-// stash, the generic kernels' scratch, the gP ping-pong, the dual weight gradients and the per-chain log J coefficients.
-// total = 0: the sizes overflow size_t.
-struct VWS { Dual *xd, *X, *stash, *hbuf, *gbuf, *gp, *gp2, *gw; double* glj; size_t total; };
-// o0: where the regions start (fthmc_train_force_grad puts them behind a whole force workspace)
-VWS vjp_layout(const FlowArch& A, double* base, int B, int L, int nl, size_t o0 = up((size_t)FLOW_WHEAD_LAYERS * FLOW_WINT)) {
-    VWS w{};
-    bool ovf = false;
-    auto mul = [&](size_t a, size_t b) { size_t r = 0; ovf |= __builtin_mul_overflow(a, b, &r); return r; };
-    size_t o = o0;
-    auto take = [&](size_t nd) {                                   // nd dual numbers
-        Dual* p = base && !ovf ? reinterpret_cast<Dual*>(base + o) : nullptr;
-        ovf |= __builtin_add_overflow(o, up(mul(nd, 2)), &o);
-        return p;
-    };
-    const size_t n1 = (size_t)B * L * L, n2 = 2 * n1, nh = nl > 0 ? mul((size_t)B * L * L, A.cmax()) : 0;
-    w.xd = take(n2);
-    w.X = take(mul((size_t)nl, n2));
-    w.stash = take(nl > 0 ? mul((size_t)nl, A.stash_doubles(B, L)) : 0);
-    w.hbuf = take(nh);
-    w.gbuf = take(mul(nh, 2));
-    w.gp = take(n1);
-    w.gp2 = take(n1);
-    w.gw = take(mul((size_t)nl, (size_t)A.params()));
-    w.glj = reinterpret_cast<double*>(take(B));
-    w.total = ovf || o > SIZE_MAX / sizeof(double) ? 0 : o;
-    return w;
-}
-
-// which kernel family serves a call, and with it the tile geometry of its partial buffers
-inline int flow_rev(const Ctx& C, const FlowLayerArgs& a, hipStream_t s) {
-    return C.mfma ? launch_flow_rev_mfma(a, s) : launch_flow_rev(a, s);
-}
-inline int flow_fwd(const Ctx& C, const FlowLayerArgs& a, hipStream_t s) {
-    return C.mfma ? launch_flow_fwd_mfma(a, s) : launch_flow_fwd(a, s);
-}
-inline size_t ws_doubles(const FlowArch& A, int B, int L, int nl, bool train = false) { return ws_layout(A, nullptr, B, L, nl, train).total; }
-
-// FTHMC_MAX_B / FTHMC_MAX_L (fthmc_hip.h): the plain-lattice kernels (wilson.hip, rng.hip) hold the site count of a chain's
-// field, 2 L^2, in int (launch_kinetic, launch_metropolis and its (2 L^2 + 2047) / 2048, k_leap_rows' plane offsets), and
-// k_metropolis walks s < 2 L^2 with s += its y extent min(that / 2048, 16) * 256 <= 4096: all below 2^31 for L <= 32764, the
-// last multiple of 4 before 2 L^2 reaches 2^31.  A chain is one workgroup of up to 1024 threads along x (k_action_charge,
-// k_kinetic, k_traj_energy), whose extent in work-items must stay below 2^32
-inline bool bad_shape(int B, int L) { return B <= 0 || B > FTHMC_MAX_B || L < 4 || L > FTHMC_MAX_L || (L % 4) != 0; }
-
-// The caller's canonical weights: the tuned kernels read their own expansion (k_pack_weights -> W.wint), the kernels for
-// other net shapes (flow_generic.hip) read the canonical layout itself.
-// wver: the caller's statement of the weights' content version (the `_v` entry points; 0 = none: expand).  The library keeps
-// nothing between calls: the launch compares the token of (version, address of w) with the stamps the last expansion left in
-// the workspace and expands the layers whose stamps differ -- a stale or wrong version costs an expansion, never a result.
-inline unsigned long long weights_token(const double* w, uint64_t wver) {
-    if (wver == 0) return 0ull;
-    unsigned long long z = (unsigned long long)wver ^ ((unsigned long long)(uintptr_t)w * 0xD6E8FEB86659FD93ull);
-    z ^= z >> 32; z *= 0xD6E8FEB86659FD93ull; z ^= z >> 32;            // a 64-bit mix: versions 1, 2, 3 ... do not look alike
-    return z | 2ull;                                                     // never 0
-}
-inline int use_weights(Ctx& C, const double* w, int nl, const WS& W, hipStream_t s, uint64_t wver = 0) {
-    C.wcan = w;
-    return C.A.is_default() ? launch_pack_weights(w, nl, W.wint, s, weights_token(w, wver)) : FTHMC_OK;
-}
-// layer l of a sweep on the plain kernels (T: double, or Dual in the second-order sweeps): weights, scratch and stripe
-template <typename T>
-GenLayerArgsT<T> gen_layer(const Ctx& C, int l, int B, int L, int act, T* stash, T* hbuf, T* gbuf) {
-    GenLayerArgsT<T> g{};
-    g.arch = C.A;
-    g.w = C.wcan + (size_t)l * C.A.params();
-    g.stash = stash; g.hbuf = hbuf; g.gbuf = gbuf;
-    g.B = B; g.L = L; g.mu = layer_mu(l); g.off = layer_off(l); g.act = act;
+// one layer on the plain kernels for the fields and stripe of `a`, the first stash region its scratch; l: its place in the caller's weights
+GenLayerArgs gen_one_layer(const Ctx& C, const WS& W, int l, const FlowLayerArgs& a) {
+    GenLayerArgs g = gen_args(C, gen_ws(C, W, a.B, a.L), l, a.B, a.L, a.act, false);
+    g.mu = a.mu; g.off = a.off; g.x = a.pin ? nullptr : a.x; g.pin = a.pin; g.y = a.y; g.pout = a.pout; g.tol = a.tol;
     return g;
-}
-inline GenLayerArgs gen_args(const Ctx& C, const WS& w, int l, int B, int L, int act, bool own_region) {
-    return gen_layer<double>(C, l, B, L, act, w.stash + (own_region ? (size_t)l * C.A.stash_doubles(B, L) : 0), w.hbuf, w.gbuf);
-}
-
-// small lattices: the fused single-launch path (flow_small.hip)
-inline SmallArgs small_args(const double* x, const WS& w, int nl, int B, int act, double beta, int mode) {
-    SmallArgs a{};
-    a.x = x; a.wint = w.wint; a.stash = w.stash; a.beta = beta; a.mode = mode; a.B = B; a.nl = nl; a.act = act;
-    return a;
-}
-
-#define FT_TRY(expr) do { int rc_ = (expr); if (rc_ != FTHMC_OK) return rc_; } while (0)
-// the call's context (shape from `arch`, the debug switches, the stream), then its workspace view
-#define FT_CTX(arch_)                                                               \
-    (void)hipGetLastError();   /* drop stale (non-sticky) errors left by the host framework */ \
-    Ctx C; { const int rc_ = make_ctx((arch_), stream, &C); if (rc_ != FTHMC_OK) return rc_; } \
-    hipStream_t s = C.s; (void)s
-// (first the chain count the default net's kernels take, flow_shape_ok's B <= 2^20 (kernels.h, fthmc_hip.h): their launchers
-// refuse it too, but only behind the weight expansion -- here nothing has been enqueued yet)
-#define FT_WS(nl, train)                                                            \
-    if (C.A.is_default() && (nl) > 0 && B > (1 << 20)) return FTHMC_ERR_ARG;        \
-    if (!ws || ws_bytes < ws_doubles(C.A, B, L, (nl), (train)) * sizeof(double)) return FTHMC_ERR_WS; \
-    const WS W = ws_layout(C.A, static_cast<double*>(ws), B, L, (nl), (train))
-
-// Argument checks of the entry points, in the precedence every one of them keeps: FTHMC_ERR_ARG, then FTHMC_ERR_UNSUPPORTED
-// (then the workspace: FT_WS).  ptrs_ok: the call's own pointers and counts.
-inline int check_layer_call(bool ptrs_ok, int B, int L, int mu, int off, int act) {            // one layer (mu, off)
-    if (!ptrs_ok || bad_shape(B, L) || mu < 0 || mu > 1 || off < 0 || off > 3) return FTHMC_ERR_ARG;
-    return act < 0 || act > 2 ? FTHMC_ERR_UNSUPPORTED : FTHMC_OK;
-}
-inline int check_flow_call(bool ptrs_ok, const double* w, int nl, int B, int L, int act) {     // a whole flow of nl layers
-    if (!ptrs_ok || (nl > 0 && !w) || bad_shape(B, L) || nl < 0) return FTHMC_ERR_ARG;
-    return act < 0 || act > 2 ? FTHMC_ERR_UNSUPPORTED : FTHMC_OK;
 }
 
 // One layer forward (rev: inverse) and the sum of its log J partials: logJ[b] = (accumulate ? logJ[b] : 0) + sum over the tiles
 // (logJ null: no sum).  `a` carries the fields, weights and stripe; l: the layer's place in the caller's weights.
 int layer_forward(const Ctx& C, const WS& W, int l, FlowLayerArgs a, bool rev, double* logJ, int accumulate = 0) {
     if (C.gen()) {                                // any other net shape (flow_generic.hip)
-        GenLayerArgs g = gen_args(C, W, l, a.B, a.L, a.act, false);
-        g.mu = a.mu; g.off = a.off; g.x = a.pin ? nullptr : a.x; g.pin = a.pin; g.y = a.y; g.pout = a.pout; g.tol = a.tol;
+        GenLayerArgs g = gen_one_layer(C, W, l, a);
         g.logj = logJ; g.logj_accumulate = accumulate;
         if (a.stash) g.stash = a.stash;
         return launch_gen_fwd(g, rev, C.s);
@@ -240,6 +53,33 @@ int layer_backward_stash(const WS& W, FlowLayerArgs a, double* gw, hipStream_t s
     return FTHMC_OK;
 }
 
+// VJP of one layer (plain or MFMA kernels), seeded by a.up_link and a.glogj, into W.gp: the layer's plaquette gradient alone (no upstream
+// gP field); gw (optional): its weight gradient.  stash: the caller's activation stash; null: the layer runs forward once first (a.x / a.pin)
+int layer_vjp(const Ctx& C, const WS& W, FlowLayerArgs a, const double* stash, double* gw) {
+    if (C.gen()) {
+        GenLayerArgs g = gen_one_layer(C, W, 0, a);
+        if (stash) g.stash = const_cast<double*>(stash);
+        else FT_TRY(launch_gen_fwd(g, false, C.s));               // fills the layer's planes
+        g.up_link = a.up_link; g.glogj = a.glogj; g.gp_out = W.gp; g.gw = gw;
+        return launch_gen_bwd(g, C.s);
+    }
+    a.gw_part = W.gw_part;
+    if (stash) { a.stash = const_cast<double*>(stash); a.stash_h = 1; }
+    else {                                                        // forward with the stash (no link update, no log J)
+        a.stash = W.stash; a.stash_h = gw ? 1 : 0;
+        // link level with weight gradients: the launch of fthmc_flow_layer_fwd_stash (links into W.X, log J partials; nobody reads them)
+        // -- on the exact tiles that is the training-sweep instance of the forward, and the instances of one kernel round their
+        // stash differently in the last bit (fp contraction follows the code around it): so this call and the two-call route
+        // give the same bits on every shape.  Without them the workspace holds the force stash only (no h1, h2): another
+        // instance than a caller's stash came from, equal to round-off.
+        if (gw && !a.pin) { a.y = W.X; a.logj_part = W.lj_part; }
+        FT_TRY(launch_flow_fwd_mfma(a, C.s));
+        a.y = nullptr; a.logj_part = nullptr;
+    }
+    a.gp_out = W.gp;
+    return layer_backward_stash(W, a, gw, C.s);
+}
+
 // a forward layer whose output field IS its input field updates only the links it changes, where the kernel has that instance
 inline bool layer_inplace(const Ctx& C, int L, int act) { return C.mfma && !C.gen() && flow_fwd_inplace_ok(L, act); }
 
@@ -253,16 +93,8 @@ inline bool layer_inplace(const Ctx& C, int L, int act) { return C.mfma && !C.ge
 // caller folds them into its own reduction: launch_traj_energy); tuned kernels only.
 int sweep_forward(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, int act, double* logdet,
                   hipStream_t s, bool stash = false, bool train = false, bool parts_only = false) {
-    if (C.gen()) {                                // any other net shape: plain kernels, one stash region per layer
-        for (int l = 0; l < nl; ++l) {
-            GenLayerArgs g = gen_args(C, w, l, B, L, act, stash);
-            g.x = l == 0 ? x : w.X + (size_t)(l - 1) * w.n2;
-            g.y = w.X + (size_t)l * w.n2;
-            g.logj = logdet; g.logj_accumulate = l > 0;
-            FT_TRY(launch_gen_fwd(g, false, s));
-        }
-        return FTHMC_OK;
-    }
+    // any other net shape: plain kernels, one stash region per layer
+    if (C.gen()) return gen_forward<double>(C, gen_ws(C, w, B, L), x, nl, B, L, act, stash, logdet);
     const bool inplace = layer_inplace(C, L, act);
     for (int l = 0; l < nl; ++l) {
         FlowLayerArgs a(w.wint, l, B, L, act);
@@ -282,9 +114,7 @@ int sweep_forward(const Ctx& C, const double* x, const WS& w, int nl, int B, int
     return FTHMC_OK;
 }
 
-inline const double* phys_field(const double* x, const WS& w, int nl) {
-    return nl == 0 ? x : w.X + (size_t)(nl - 1) * w.n2;
-}
+inline const double* phys_field(const double* x, const WS& w, int nl) { return flowed_field<double>(x, w.X, nl, w.n2); }
 
 // S_eff (and friends) of x; leaves the flowed field (phys_field) in w.X
 int eval_action(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, int act, double beta,
@@ -304,17 +134,9 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
              double glogj, double* gw, hipStream_t s, bool have_forward = false, const double* beta_b = nullptr) {
     if (C.gen()) {                                // any other net shape (flow_generic.hip)
         if (nl > 0 && !have_forward) FT_TRY(sweep_forward(C, x, w, nl, B, L, act, nullptr, s, true));
-        double* gcur = (nl & 1) ? w.gp2 : w.gp;
-        double* galt = gcur == w.gp ? w.gp2 : w.gp;
-        FT_TRY(launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gcur, s, beta_b));
-        for (int l = nl - 1; l >= 0; --l) {
-            GenLayerArgs g = gen_args(C, w, l, B, L, act, true);
-            g.up_gp = gcur; g.glogj_const = glogj; g.gp_out = galt;
-            g.gw = gw ? gw + (size_t)l * C.A.params() : nullptr;
-            FT_TRY(launch_gen_bwd(g, s));
-            std::swap(gcur, galt);
-        }
-        return FTHMC_OK;
+        return gen_backward<double>(C, gen_ws(C, w, B, L), nl, B, L, act, nullptr, glogj, gw, [&](double* gp) {
+            return launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gp, s, beta_b);
+        });
     }
     // MFMA path without weight gradients: the forward sweep stashes act'(z1), act'(z2), s per site
     // and the backward kernels read them back instead of recomputing the network
@@ -408,45 +230,6 @@ int leapfrog_ws(const double* x, const double* p, const WS& w, int B, int L, dou
     return FTHMC_OK;
 }
 
-// Event timing of `reps` calls of launch() behind two untimed warm-up calls: *ms_avg = milliseconds per call.  The events are
-// created here, after the caller's last early return, and destroyed on every path.
-template <class Launch> int time_launches(int reps, hipStream_t s, double* ms_avg, Launch launch) {
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess) return FTHMC_ERR_LAUNCH;
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return FTHMC_ERR_LAUNCH; }
-    int rc = FTHMC_OK;
-    for (int it = -2; it < reps && rc == FTHMC_OK; ++it) {
-        if (it == 0) (void)hipEventRecord(e0, s);
-        rc = launch();
-    }
-    (void)hipEventRecord(e1, s);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *ms_avg = (double)ms / reps;
-    return rc;
-}
-
-// Cycle stamps of a profiled launch, read back and averaged: dbg = nrec records of nslot stamps on the device;
-// out[k] = sum over the records of (stamp k - stamp ref(k)) / denom, where both were written (ref(k) < 0: stamp k itself), k >= k0
-template <class Ref> int mean_stamps(const long long* dbg, size_t nrec, int nslot, int k0, size_t denom, hipStream_t s, double* out, Ref ref) {
-    const size_t bytes = nrec * nslot * sizeof(long long);
-    long long* h = (long long*)malloc(bytes);
-    if (!h) return FTHMC_ERR_ARG;
-    if (hipMemcpyAsync(h, dbg, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) { free(h); return FTHMC_ERR_LAUNCH; }
-    for (int k = 0; k < nslot; ++k) out[k] = 0.0;
-    for (size_t r = 0; r < nrec; ++r)
-        for (int k = k0; k < nslot; ++k) {
-            const int q = ref(k);
-            const long long t = h[r * nslot + k], t0 = q < 0 ? 0 : h[r * nslot + q];
-            if (t && (q < 0 || t0)) out[k] += (double)(t - t0) / denom;
-        }
-    free(h);
-    return FTHMC_OK;
-}
-
 // the result pair of an MD entry point
 inline int copy_pair(double* x_out, const double* xo, double* v_out, const double* vo, size_t n2, hipStream_t s) {
     if (hipMemcpyAsync(x_out, xo, n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess ||
@@ -464,15 +247,16 @@ int md_call(bool plain, const double* x, const double* v, const double* w, const
     const bool leap = integrator == FTHMC_INT_LEAPFROG;
     Sched sc;
     FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(arch);
-    FT_WS(nl, false);
+    Ctx C; WS W; FT_TRY(open_call(arch, stream, &C));
+    FT_TRY(open_ws(C, ws, ws_bytes, B, L, nl, false, &W));
+    const hipStream_t s = C.s;
     if (plain && leap) {
         double *xo, *po;
         FT_TRY(leapfrog_ws(x, v, W, B, L, beta, dt, nstep, &xo, &po, s));
         return copy_pair(x_out, xo, v_out, po, W.n2, s);
     }
     if (!plain) {
-        FT_TRY(use_weights(C, w, nl, W, s, wver));
+        FT_TRY(use_weights(C, w, nl, W.wint, wver));
         if (C.small(L, nl)) {                                            // the whole MD in one launch
             SmallArgs a = small_args(x, W, nl, B, act, beta, 2);
             a.v = v; a.dt = dt; a.nstep = nstep; a.x_out = x_out; a.v_out = v_out;
@@ -493,13 +277,14 @@ int hmc_trajectory_call(const double* x, const double* v, const double* u, int B
     if (pb) beta = 0.0;
     Sched sc;
     FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(nullptr);
+    Ctx C; WS W; FT_TRY(open_call(nullptr, stream, &C));
+    const hipStream_t s = C.s;
     // L <= 64 (x_new must not alias x): one persistent launch per trajectory, state in LDS / registers.  The scalar-beta leapfrog
     // has a kernel of its own, the schedule-driven one serves every other integrator and per-chain beta with every integrator.
     if (L <= 64 && C.mfma && x_new != x)
         return leap && !pb ? launch_hmc_trajectory_fused(x, v, u, B, L, beta, dt, nstep, x_new, dH, acc, H0, H1, s)
                            : launch_hmc_trajectory_sched(x, v, u, B, L, beta, sc, x_new, dH, acc, H0, H1, s, beta_b);
-    FT_WS(0, false);
+    FT_TRY(open_ws(C, ws, ws_bytes, B, L, 0, false, &W));
     double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
     auto energy = [&](const double* xf, const double* vf, double* h) {     // h = S_W(xf) + K(vf) / 2
         FT_TRY(launch_action_charge(xf, B, L, beta, S, nullptr, nullptr, s, nullptr, beta_b));
@@ -551,8 +336,8 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
     const bool md = mode == FTHMC_MODE_MD;
     Sched sc;
     FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    FT_CTX(arch);
-    FT_WS(nl, false);
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &W));
+    const hipStream_t s = C.s;
     double* K = W.scal + (size_t)SC_K * B;
     double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
     double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
@@ -560,7 +345,6 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
     double* old = W.scal + (size_t)SC_OLD0 * B;      // slots SC_OLD0.. : 3 consecutive
     double* neu = W.scal + (size_t)SC_NEW0 * B;
     double* sel = state_out ? state_out : W.scal + (size_t)SC_S * B;
-    FT_TRY(use_weights(C, w, nl, W, s, wver));
     if (md && C.small(L, nl)) {                                      // the whole trajectory in one launch
         SmallArgs a = small_args(x, W, nl, B, act, beta, 3);
         a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
@@ -675,17 +459,13 @@ const char* fthmc_strerror(int code) {
     }
 }
 
-size_t fthmc_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
-    Ctx C;
+static size_t ws_bytes_of(const fthmc_arch_t* arch, int B, int L, int n_layers, bool train) {
+    Ctx C; Carver c;
     if (B <= 0 || L <= 0 || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
-    return ws_doubles(C.A, B, L, n_layers) * sizeof(double);
+    return ws_layout(C.A, c, B, L, n_layers, train).total * sizeof(double);
 }
-
-size_t fthmc_train_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
-    Ctx C;
-    if (B <= 0 || L <= 0 || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
-    return ws_doubles(C.A, B, L, n_layers, true) * sizeof(double);
-}
+size_t fthmc_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) { return ws_bytes_of(arch, B, L, n_layers, false); }
+size_t fthmc_train_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) { return ws_bytes_of(arch, B, L, n_layers, true); }
 
 int fthmc_wrap(const double* x, double* out, size_t n, void* stream) {
     if (!x || !out) return FTHMC_ERR_ARG;
@@ -725,15 +505,17 @@ int fthmc_random_momenta(const int64_t* seeds, int B, int n_per_chain, double* v
     return launch_random_momenta(seeds, B, n_per_chain, v, u, ft_stream(stream));
 }
 
-size_t fthmc_ws_head_bytes(void) { return up((size_t)FLOW_WHEAD_LAYERS * FLOW_WINT) * sizeof(double); }
+size_t fthmc_ws_head_bytes(void) { return Carver().up(wint_doubles(0)) * sizeof(double); }
 
 int fthmc_pack_weights(const double* w, const fthmc_arch_t* arch, int n_layers, uint64_t weights_version, void* ws, size_t ws_bytes,
                        void* stream) {
     if (!w || n_layers <= 0) return FTHMC_ERR_ARG;
-    FT_CTX(arch);
-    if (!ws || ws_bytes < up((size_t)(n_layers > FLOW_WHEAD_LAYERS ? n_layers : FLOW_WHEAD_LAYERS) * FLOW_WINT) * sizeof(double)) return FTHMC_ERR_WS;
-    const WS W = ws_layout(C.A, static_cast<double*>(ws), 1, 4, n_layers);      // the expansion is the workspace's first region whatever B, L
-    return use_weights(C, w, n_layers, W, s, weights_version);
+    Ctx C;
+    FT_TRY(open_call(arch, stream, &C));
+    Carver c(ws, ws_bytes);
+    double* wint = c.take(wint_doubles(n_layers));        // the expansion is the first region of every first-order layout whatever B, L
+    FT_TRY(check_ws(c.total(), ws, ws_bytes));
+    return use_weights(C, w, n_layers, wint, weights_version);
 }
 
 int fthmc_chain_seeds(int64_t seed, int64_t lo, int B, int64_t traj, int64_t* counter, int advance, int64_t* seeds, void* stream) {
@@ -749,8 +531,9 @@ int fthmc_random_uniform(const int64_t* seeds, int B, int n_per_chain, double lo
 int fthmc_train_metrics(const double* xi, const double* x, const double* logq, const double* logp, int B, int L,
                         double beta, double dkl_factor, double* row, void* ws, size_t ws_bytes, void* stream) {
     if (!xi || !x || !logq || !logp || !row || bad_shape(B, L) || !(beta != 0.0)) return FTHMC_ERR_ARG;
-    FT_CTX(nullptr);
-    FT_WS(0, false);
+    Ctx C; WS W; FT_TRY(open_call(nullptr, stream, &C));
+    FT_TRY(open_ws(C, ws, ws_bytes, B, L, 0, false, &W));
+    const hipStream_t s = C.s;
     double* q = W.scal + (size_t)SC_Q * B; double* qi = W.scal + (size_t)SC_OLD0 * B;
     FT_TRY(launch_action_charge(x, B, L, beta, nullptr, q, nullptr, s, W.act_part));
     FT_TRY(launch_action_charge(xi, B, L, beta, nullptr, qi, nullptr, s, W.act_part));
@@ -795,9 +578,7 @@ int fthmc_hmc_trajectory_int(const double* x, const double* v, const double* u, 
 int fthmc_flow_layer_fwd(const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
                          double* y, double* logJ, void* ws, size_t ws_bytes, void* stream) {
     FT_TRY(check_layer_call(x && w && y, B, L, mu, off, act));
-    FT_CTX(arch);
-    FT_WS(1, false);
-    FT_TRY(use_weights(C, w, 1, W, s));
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, 1, B, L, false, 0, &C, &W));
     FlowLayerArgs a(W.wint, B, L, mu, off, act);
     a.x = x; a.y = y;
     a.inplace = y == x && layer_inplace(C, L, act);
@@ -807,9 +588,7 @@ int fthmc_flow_layer_fwd(const double* x, const double* w, const fthmc_arch_t* a
 int fthmc_flow_layer_rev(const double* y, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
                          double tol, double* x, double* logJ, void* ws, size_t ws_bytes, void* stream) {
     FT_TRY(check_layer_call(y && w && x, B, L, mu, off, act));
-    FT_CTX(arch);
-    FT_WS(1, false);
-    FT_TRY(use_weights(C, w, 1, W, s));
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, 1, B, L, false, 0, &C, &W));
     FlowLayerArgs a(W.wint, B, L, mu, off, act);
     a.x = y; a.y = x; a.tol = tol;
     return layer_forward(C, W, 0, a, true, logJ);
@@ -819,10 +598,10 @@ int fthmc_flow_layer_rev(const double* y, const double* w, const fthmc_arch_t* a
 static int plaq_coupling(const double* P, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act, double tol,
                          bool rev, double* out, double* logJ, void* ws, size_t ws_bytes, void* stream) {
     FT_TRY(check_layer_call(P && w && out, B, L, mu, off, act));
-    FT_CTX(arch);
+    Ctx C; WS W; FT_TRY(open_call(arch, stream, &C));
     if (!C.mfma && C.A.is_default()) return FTHMC_ERR_UNSUPPORTED;
-    FT_WS(1, false);
-    FT_TRY(use_weights(C, w, 1, W, s));
+    FT_TRY(open_ws(C, ws, ws_bytes, B, L, 1, false, &W));
+    FT_TRY(use_weights(C, w, 1, W.wint));
     FlowLayerArgs a(W.wint, B, L, mu, off, act);
     a.x = P; a.pin = P; a.pout = out; a.tol = tol;
     return layer_forward(C, W, 0, a, rev, logJ);
@@ -846,28 +625,16 @@ int fthmc_plaq_coupling_rev(const double* fP, const double* w, const fthmc_arch_
 int fthmc_plaq_coupling_bwd(const double* P, const double* w, const fthmc_arch_t* arch, const double* gfP, const double* glogJ,
                             int B, int L, int mu, int off, int act, double* gP, double* gw, void* ws, size_t ws_bytes, void* stream) {
     FT_TRY(check_layer_call(P && w && gfP && glogJ && gP, B, L, mu, off, act));
-    FT_CTX(arch);
+    Ctx C; WS W; FT_TRY(open_call(arch, stream, &C));
     if (!C.mfma && C.A.is_default()) return FTHMC_ERR_UNSUPPORTED;          // as fthmc_plaq_coupling_fwd: MFMA kernels (or the plain ones)
-    FT_WS(1, gw != nullptr);
-    FT_TRY(use_weights(C, w, 1, W, s));
+    FT_TRY(open_ws(C, ws, ws_bytes, B, L, 1, gw != nullptr, &W));
+    FT_TRY(use_weights(C, w, 1, W.wint));
     double* fake = W.xa;                                                     // [B][2][L][L]: only plane mu is read
-    FT_TRY(launch_plane_from(gfP, B, L, mu, mu == 0 ? 1.0 : -1.0, fake, s));
-    const size_t n1 = (size_t)B * L * L;
-    if (C.gen()) {
-        GenLayerArgs g = gen_args(C, W, 0, B, L, act, false);
-        g.mu = mu; g.off = off; g.pin = P;
-        FT_TRY(launch_gen_fwd(g, false, s));
-        g.up_link = fake; g.glogj = glogJ; g.gp_out = W.gp; g.gw = gw;
-        FT_TRY(launch_gen_bwd(g, s));
-        return launch_axpy(W.gp, gfP, 1.0, gP, n1, s);
-    }
+    FT_TRY(launch_plane_from(gfP, B, L, mu, mu == 0 ? 1.0 : -1.0, fake, C.s));
     FlowLayerArgs a(W.wint, B, L, mu, off, act);
     a.x = P; a.pin = P; a.up_link = fake; a.glogj = glogJ;
-    a.gw_part = W.gw_part; a.stash = W.stash; a.stash_h = gw ? 1 : 0;
-    FT_TRY(launch_flow_fwd_mfma(a, s));                                      // fills the stash (no output field, no log J)
-    a.gp_out = W.gp;
-    FT_TRY(layer_backward_stash(W, a, gw, s));
-    return launch_axpy(W.gp, gfP, 1.0, gP, n1, s);
+    FT_TRY(layer_vjp(C, W, a, nullptr, gw));
+    return launch_axpy(W.gp, gfP, 1.0, gP, (size_t)B * L * L, C.s);
 }
 
 // VJP of one layer.  `stash` != null: the forward's activation stash (fthmc_flow_layer_fwd_stash) -- nothing is recomputed;
@@ -875,44 +642,20 @@ int fthmc_plaq_coupling_bwd(const double* P, const double* w, const fthmc_arch_t
 static int layer_bwd_impl(const double* x, const double* stash, const double* w, const fthmc_arch_t* arch, const double* gy, const double* glogJ,
                           int B, int L, int mu, int off, int act, double* gx, double* gw, void* ws, size_t ws_bytes, void* stream) {
     FT_TRY(check_layer_call((x || stash) && w && gy && glogJ && gx, B, L, mu, off, act));
-    FT_CTX(arch);
+    Ctx C; WS W; FT_TRY(open_call(arch, stream, &C));
     const bool mfma = C.mfma;
     if (stash && !mfma && C.A.is_default()) return FTHMC_ERR_UNSUPPORTED;      // the VALU variant has no stash
-    FT_WS(1, gw != nullptr && mfma);
-    FT_TRY(use_weights(C, w, 1, W, s));
-    if (C.gen()) {
-        // the adjoint seeded by the link gradient; W.gp holds the layer's plaquette gradient alone
-        GenLayerArgs g = gen_args(C, W, 0, B, L, act, false);
-        g.mu = mu; g.off = off; g.x = x;
-        if (stash) g.stash = const_cast<double*>(stash);
-        else FT_TRY(launch_gen_fwd(g, false, s));                 // forward once: fills the layer's planes
-        g.up_link = gy; g.glogj = glogJ; g.gp_out = W.gp; g.gw = gw;
-        FT_TRY(launch_gen_bwd(g, s));
-        return launch_adj_add(W.gp, gy, B, L, gx, s);
-    }
+    FT_TRY(open_ws(C, ws, ws_bytes, B, L, 1, gw != nullptr && mfma, &W));
+    FT_TRY(use_weights(C, w, 1, W.wint));
+    const hipStream_t s = C.s;
     FlowLayerArgs a(W.wint, B, L, mu, off, act);
     a.x = x; a.up_link = gy; a.glogj = glogJ;
     a.gp_part = W.gp_part; a.gw_part = W.gw_part;
-    if (mfma) {
-        // the gather-form backward seeded by the link gradient; gP_out holds the layer's plaquette gradient alone (no
-        // upstream gP field).  Without a caller's stash: forward once with the stash (no link update, no log J).
-        if (stash) { a.stash = const_cast<double*>(stash); a.stash_h = 1; }
-        else {
-            a.stash = W.stash; a.stash_h = gw ? 1 : 0;
-            // with weight gradients: the launch of fthmc_flow_layer_fwd_stash (links into W.X, log J partials; nobody reads them) --
-            // on the exact tiles that is the training-sweep instance of the forward, and the instances of one kernel round their
-            // stash differently in the last bit (fp contraction follows the code around it): so this call and the two-call route
-            // give the same bits on every shape.  Without them the workspace holds the force stash only (no h1, h2): another
-            // instance than a caller's stash came from, equal to round-off.
-            if (gw) { a.y = W.X; a.logj_part = W.lj_part; }
-            FT_TRY(launch_flow_fwd_mfma(a, s));
-            a.y = nullptr; a.logj_part = nullptr;
-        }
-        a.gp_out = W.gp;
-        FT_TRY(layer_backward_stash(W, a, gw, s));
+    if (C.gen() || mfma) {                                        // the plain kernels, or the gather-form backward on a stash
+        FT_TRY(layer_vjp(C, W, a, stash, gw));
         return launch_adj_add(W.gp, gy, B, L, gx, s);
     }
-    FT_TRY(launch_flow_bwd(a, gw != nullptr, s));
+    FT_TRY(launch_flow_bwd(a, gw != nullptr, s));                 // VALU variant: scatter form + gather
     if (gw) FT_TRY(launch_reduce_gw(W.gw_part, B * flow_geom(false).ntiles(L), 1.0, 0, gw, W.gw_tmp, s));
     FT_TRY(launch_gather_gp(W.gp_part, B, L, flow_geom(false), 0, W.gp, s));
     return launch_adj_add(W.gp, gy, B, L, gx, s);
@@ -936,9 +679,7 @@ int fthmc_flow_layer_fwd_stash(const double* x, const double* w, const fthmc_arc
                                double* logJ, double* stash, void* ws, size_t ws_bytes, void* stream) {
     FT_TRY(check_layer_call(x && w && y && stash, B, L, mu, off, act));
     if (fthmc_layer_stash_bytes(arch, B, L) == 0) return FTHMC_ERR_UNSUPPORTED;        // the VALU variant has no stash
-    FT_CTX(arch);
-    FT_WS(1, false);
-    FT_TRY(use_weights(C, w, 1, W, s));
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, 1, B, L, false, 0, &C, &W));
     FlowLayerArgs a(W.wint, B, L, mu, off, act);
     a.x = x; a.y = y; a.stash = stash; a.stash_h = 1;
     a.inplace = y == x && layer_inplace(C, L, act);
@@ -954,9 +695,8 @@ int fthmc_flow_layer_bwd_stash(const double* stash, const double* w, const fthmc
 int fthmc_flow_forward_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
                        double* y, double* logdet, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
     FT_TRY(check_flow_call(x != nullptr, w, n_layers, B, L, act));
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, false, weights_version, &C, &W));
+    const hipStream_t s = C.s;
     double* ld = logdet ? logdet : W.scal + (size_t)SC_LOGDET * B;
     if (n_layers == 0 && hipMemsetAsync(ld, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     if (C.small(L, n_layers)) {
@@ -978,9 +718,8 @@ int fthmc_flow_forward(const double* x, const double* w, const fthmc_arch_t* arc
 int fthmc_flow_reverse_v(const double* y, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double tol,
                        double* x, double* logdet, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
     FT_TRY(check_flow_call(y && x, w, n_layers, B, L, act));
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, false, weights_version, &C, &W));
+    const hipStream_t s = C.s;
     double* ld = logdet ? logdet : W.scal + (size_t)SC_LOGDET * B;
     if (hipMemsetAsync(ld, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     // The last layer maps y -> x, the others run in place on x.  In place is safe: a layer only rewrites its ACTIVE links,
@@ -1008,9 +747,8 @@ int fthmc_ft_action_v(const double* x, const double* w, const fthmc_arch_t* arch
                     double* S_eff, double* logdet, double* plaq, double* Q, void* ws, size_t ws_bytes,
                     void* stream, uint64_t weights_version) {
     FT_TRY(check_flow_call(x != nullptr, w, n_layers, B, L, act));
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, false, weights_version, &C, &W));
+    const hipStream_t s = C.s;
     if (n_layers == 0 && logdet && hipMemsetAsync(logdet, 0, (size_t)B * sizeof(double), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     if (C.small(L, n_layers)) {
         SmallArgs a = small_args(x, W, n_layers, B, act, beta, 0);
@@ -1029,9 +767,8 @@ int fthmc_ft_action(const double* x, const double* w, const fthmc_arch_t* arch, 
 int fthmc_ft_force_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
                    double* F, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
     FT_TRY(check_flow_call(x && F, w, n_layers, B, L, act));
-    FT_CTX(arch);
-    FT_WS(n_layers, false);
-    FT_TRY(use_weights(C, w, n_layers, W, s, weights_version));
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, false, weights_version, &C, &W));
+    const hipStream_t s = C.s;
     if (C.small(L, n_layers)) {
         SmallArgs a = small_args(x, W, n_layers, B, act, beta, 1);
         a.F = F;
@@ -1151,7 +888,7 @@ static bool instanton_split(int B, int L, int path) { return path == 2 || (path 
 size_t fthmc_instanton_ws_bytes(int B, int L, int path) {
     if (bad_shape(B, L) || path < 0 || path > 2 || !instanton_split(B, L, path)) return 0;
     // rounded like every other workspace size (a multiple of 256 bytes), so that a caller may carve one allocation into workspaces
-    return up(instanton_part_doubles(B, L) + ((size_t)B * sizeof(int32_t) + 7) / 8) * sizeof(double);
+    return Carver().up(instanton_part_doubles(B, L) + ((size_t)B * sizeof(int32_t) + 7) / 8) * sizeof(double);
 }
 int fthmc_instanton_hit(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hit, int64_t hit0,
                         int path, double* x_out, int32_t* k_out, int32_t* nacc_out, double* cs_out, void* ws, size_t ws_bytes, void* stream) {
@@ -1183,9 +920,8 @@ int fthmc_train_grad(const double* xi, const double* w, const fthmc_arch_t* arch
                      double* x, double* logq, double* logp, double* gw, void* ws, size_t ws_bytes,
                      void* stream) {
     FT_TRY(check_flow_call(xi && w && n_layers >= 1, w, n_layers, B, L, act));
-    FT_CTX(arch);
-    FT_WS(n_layers, true);
-    FT_TRY(use_weights(C, w, n_layers, W, s));
+    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, true, 0, &C, &W));
+    const hipStream_t s = C.s;
     if (gw && C.small(L, n_layers)) {
         // small lattices: ONE launch runs the forward sweep (stash + h1, h2 + log J), the loss pieces and the backward sweep of
         // every chain (flow_small.hip, training sweep); then the weight gradients layer by layer from the gz it left behind
@@ -1218,349 +954,6 @@ int fthmc_train_grad(const double* xi, const double* w, const fthmc_arch_t* arch
     if (gw) {
         // d mean_b(S_W - logdet) / dw : seed beta/B on the Wilson term, -1/B on every logJ
         FT_TRY(force_gp(C, xi, W, n_layers, B, L, act, beta / B, -1.0 / B, gw, s, /*have_forward=*/true));
-    }
-    return FTHMC_OK;
-}
-
-int fthmc_time_kernel(int kind, const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
-                      double beta, int reps, double* ms_avg_host, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !ms_avg_host || bad_shape(B, L) || reps < 1 || kind < 0 || kind > 3) return FTHMC_ERR_ARG;
-    if (kind < 2 && !w) return FTHMC_ERR_ARG;
-    FT_CTX(arch);
-    if (C.gen() && kind < 2) return FTHMC_ERR_UNSUPPORTED;         // the tuned kernels serve the default net shape
-    FT_WS(1, false);
-    FlowLayerArgs a{};
-    if (kind < 2) {
-        FT_TRY(use_weights(C, w, 1, W, s));
-        FT_TRY(launch_wilson_gp(x, B, L, beta, W.gp, s));
-        a = FlowLayerArgs(W.wint, B, L, mu, off, act);
-        a.x = x; a.y = W.X; a.logj_part = W.lj_part;
-        a.up_gp = W.gp; a.glogj_const = -1.0; a.gp_part = W.gp_part; a.gp_out = W.gp2;
-#ifdef FT_DIAG
-        if (const char* e = getenv("FTHMC_DBG_STOP")) a.dbg_stop = atoi(e);
-#endif
-        if (C.mfma) {            // the hot path: forward stashes, backward reads the stash
-            a.stash = W.stash;
-            a.logj_part = nullptr;       // ... and asks for no log J: exactly what a layer of a force sweep launches (the SWEEP / FS instances)
-            FT_TRY(launch_flow_fwd_mfma(a, s));
-            // the forward as layers 1 .. nl - 1 of a sweep launch it: in place on the work buffer (sweep_forward)
-            if (kind == 0 && flow_fwd_inplace_ok(L, act)) {
-                if (hipMemcpyAsync(W.X, x, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-                a.x = W.X; a.inplace = 1;
-            }
-        }
-    } else {
-        int64_t* seeds = reinterpret_cast<int64_t*>(W.scal);             // B int64 seeds = 0 .. (any values do)
-        if (hipMemsetAsync(seeds, 0, (size_t)B * sizeof(int64_t), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-        FT_TRY(launch_random_momenta(seeds, B, 2 * L * L, W.va, nullptr, s));
-    }
-    return time_launches(reps, s, ms_avg_host, [&] {
-        if (kind == 0) return flow_fwd(C, a, s);
-        if (kind == 1) return a.stash ? launch_flow_bwd_gather(a, s) : launch_flow_bwd(a, false, s);
-        if (kind == 2) return launch_leap_step(x, W.va, W.xa, W.vb, B, L, beta, 0.05, 0.1, s);
-        return launch_hmc_trajectory_fused(x, W.va, W.scal + B, B, L, beta, 0.1, 10, W.xa, nullptr, nullptr, nullptr, nullptr, s);
-    });
-}
-
-int fthmc_time_small(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
-                     double beta, double dt, int nstep, int reps, double* ms_avg_host, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !v || !u || !w || !ms_avg_host || bad_shape(B, L) || n_layers < 1 || nstep < 1 || reps < 1) return FTHMC_ERR_ARG;
-    FT_CTX(arch);
-    if (!C.small(L, n_layers)) return FTHMC_ERR_UNSUPPORTED;
-    FT_WS(n_layers, false);
-    FT_TRY(use_weights(C, w, n_layers, W, s));
-    SmallArgs a = small_args(x, W, n_layers, B, act, beta, 3);
-    a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = W.xb;
-    // H0 is evaluated in the launch (no state_in): nstep force sweeps + 2 action sweeps
-    return time_launches(reps, s, ms_avg_host, [&] { return launch_ft_small(a, L, s); });
-}
-
-int fthmc_small_profile(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
-                        int act, double beta, double dt, int nstep, double* cycles_host32, void* ws, size_t ws_bytes,
-                        void* stream) {
-    if (!x || !v || !u || !w || !cycles_host32 || bad_shape(B, L) || n_layers < 1 || nstep < 1) return FTHMC_ERR_ARG;
-    FT_CTX(arch);
-    if (!C.small(L, n_layers)) return FTHMC_ERR_UNSUPPORTED;
-    FT_WS(n_layers, false);
-    long long* dbg = reinterpret_cast<long long*>(W.gw_part);            // unused by the force path; B * 32 stamps fit
-    if (hipMemsetAsync(dbg, 0, (size_t)B * 32 * sizeof(long long), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-    FT_TRY(use_weights(C, w, n_layers, W, s));
-    SmallArgs a = small_args(x, W, n_layers, B, act, beta, 3);
-    a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = W.xb; a.dbg = dbg;
-    FT_TRY(launch_ft_small(a, L, s));
-    return mean_stamps(dbg, (size_t)B, 32, 0, (size_t)B, s, cycles_host32, [](int) { return -1; });
-}
-
-int fthmc_profile_stages(int kind, const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
-                         double beta, double* cycles_host16, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !w || !cycles_host16 || bad_shape(B, L) || kind < 0 || kind > 3) return FTHMC_ERR_ARG;
-    FT_CTX(arch);
-    if (C.gen()) return FTHMC_ERR_UNSUPPORTED;                     // the tuned kernels serve the default net shape
-    const bool train = kind >= 2;                                  // kind 2: the backward in training mode (also writes A.gz); 3: k_flow_wgrad behind it
-    FT_WS(1, train);
-    const size_t nrec = (size_t)B * (kind >= 1 ? flow_gather_geom() : flow_fwd_geom(true)).ntiles(L);
-    // stamp buffer: a workspace region the profiled launch does not write (B * ntiles * 16 stamps fit in either)
-    long long* dbg = reinterpret_cast<long long*>(train ? W.gp_part : W.gw_part);
-    if (hipMemsetAsync(dbg, 0, nrec * 16 * sizeof(long long), s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-    FT_TRY(use_weights(C, w, 1, W, s));
-    FT_TRY(launch_wilson_gp(x, B, L, beta, W.gp, s));
-    FlowLayerArgs a(W.wint, B, L, mu, off, act);
-    a.x = x; a.y = W.X; a.logj_part = train ? W.lj_part : nullptr;                       // kind 0, 1: the launch of a force sweep
-    a.up_gp = W.gp; a.glogj_const = -1.0; a.gp_part = W.gp_part; a.gp_out = W.gp2; a.dbg = dbg;
-    if (kind == 0) a.stash = W.stash;             // the forward as a force sweep launches it: with the activation stash, without log J
-    if (kind == 0 && flow_fwd_inplace_ok(L, act)) {                // ... in place on the work buffer, as layers 1 .. nl - 1 are
-        if (hipMemcpyAsync(W.X, x, W.n2 * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-        a.x = W.X; a.inplace = 1;
-    }
-    if (kind >= 1) {                              // stash backward needs the forward's stash first
-        a.stash = W.stash; a.stash_h = train ? 1 : 0; a.gw_part = W.gw_part; a.gz = train ? W.gz : nullptr; a.dbg = nullptr;
-        FT_TRY(launch_flow_fwd_mfma(a, s));
-        a.dbg = kind == 3 ? nullptr : dbg;
-    }
-    FT_TRY(kind == 0 ? launch_flow_fwd_mfma(a, s) : launch_flow_bwd_gather(a, s));
-    size_t nused = nrec;                                           // records the profiled launch stamps
-    if (kind == 3) { a.dbg = dbg; a.tpw = flow_wgrad_tpw(B, L, 1); nused = (size_t)flow_wgrad_nparts(B, L, a.tpw); FT_TRY(launch_flow_wgrad(a, s)); }
-    // forward 7..12 (-DFT_DIAG builds): inside conv1 / conv2; backward, slots 6..13: per-wave arrival at the first barrier
-    return mean_stamps(dbg, nrec, 16, 1, nused, s, cycles_host16, [kind](int k) {
-        return k == 15 ? 14 : kind == 3 ? k - 1 : (kind >= 1 && k >= 6) ? 0 : (kind == 0 && k == 7) ? 1 : (kind == 0 && k == 11) ? 2 : k - 1;
-    });
-}
-
-}  // extern "C"
-
-// ---- second order: the VJPs of S_eff / log det J (plain kernels) and of the force (the same kernels on dual numbers)
-namespace {
-// shared argument checks and the workspace view of both entry points
-int vjp_begin(const double* x, const double* w, const fthmc_arch_t* arch, int nl, int B, int L, int act, const double* cot,
-              const double* gx, const double* gw, void* ws, size_t ws_bytes, void* stream, Ctx* C, VWS* W) {
-    (void)hipGetLastError();
-    FT_TRY(check_flow_call(x && cot && (gx || gw), w, nl, B, L, act));
-    FT_TRY(make_ctx(arch, stream, C));
-    if (nl > 0 && C->A.k / 2 > L) return FTHMC_ERR_UNSUPPORTED;
-    const VWS v = vjp_layout(C->A, nullptr, B, L, nl);
-    if (v.total == 0) return FTHMC_ERR_UNSUPPORTED;
-    if (!ws || ws_bytes < v.total * sizeof(double)) return FTHMC_ERR_WS;
-    *W = vjp_layout(C->A, static_cast<double*>(ws), B, L, nl);
-    C->wcan = w;
-    return FTHMC_OK;
-}
-template <typename T>
-GenLayerArgsT<T> vjp_args(const Ctx& C, const VWS& V, int l, int B, int L, int act) {
-    return gen_layer<T>(C, l, B, L, act, reinterpret_cast<T*>(V.stash) + (size_t)l * C.A.stash_doubles(B, L),
-                        reinterpret_cast<T*>(V.hbuf), reinterpret_cast<T*>(V.gbuf));
-}
-// The sweeps of both entry points, on T = double (the action's VJP) or Dual (the force's: the first-order sweep of force_gp on the
-// dual field x + eps g).  Forward: x -> X[0 .. nl - 1], every layer's activations kept; returns the flowed field.
-template <typename T>
-int vjp_forward(const Ctx& C, const VWS& V, const T* x, int nl, int B, int L, int act, const T** xphys) {
-    const size_t n2 = (size_t)B * 2 * L * L;
-    T* X = reinterpret_cast<T*>(V.X);
-    for (int l = 0; l < nl; ++l) {
-        GenLayerArgsT<T> g = vjp_args<T>(C, V, l, B, L, act);
-        g.x = l == 0 ? x : X + (size_t)(l - 1) * n2;
-        g.y = X + (size_t)l * n2;
-        FT_TRY(launch_gen_fwd(g, false, C.s));
-    }
-    *xphys = nl == 0 ? x : X + (size_t)(nl - 1) * n2;
-    return FTHMC_OK;
-}
-// Backward: the seed coef[b] beta sin P at the flowed field, then layer by layer; d/d logJ = glogj[b] (null: glogj_const); gw
-// (optional): every layer's weight gradient.  Returns the plaquette gradient at x.
-template <typename T>
-int vjp_backward(const Ctx& C, const VWS& V, const T* xphys, int nl, int B, int L, int act, double beta, const double* coef,
-                 const double* glogj, double glogj_const, T* gw, T** gp) {
-    T* gcur = reinterpret_cast<T*>(V.gp);
-    T* galt = reinterpret_cast<T*>(V.gp2);
-    FT_TRY(launch_gen_seed(xphys, coef, B, L, beta, gcur, C.s));
-    for (int l = nl - 1; l >= 0; --l) {
-        GenLayerArgsT<T> g = vjp_args<T>(C, V, l, B, L, act);
-        g.up_gp = gcur; g.glogj = glogj; g.glogj_const = glogj_const; g.gp_out = galt;
-        g.gw = gw ? gw + (size_t)l * C.A.params() : nullptr;
-        FT_TRY(launch_gen_bwd(g, C.s));
-        std::swap(gcur, galt);
-    }
-    *gp = gcur;
-    return FTHMC_OK;
-}
-}  // namespace
-
-extern "C" {
-
-size_t fthmc_vjp_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
-    Ctx C;
-    if (bad_shape(B, L) || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
-    if (n_layers > 0 && C.A.k / 2 > L) return 0;
-    return vjp_layout(C.A, nullptr, B, L, n_layers).total * sizeof(double);
-}
-
-int fthmc_ft_action_vjp(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
-                        double beta, const double* gS, const double* glogdet, double* gx, double* gw,
-                        void* ws, size_t ws_bytes, void* stream) {
-    Ctx C; VWS V;
-    FT_TRY(vjp_begin(x, w, arch, n_layers, B, L, act, gS, gx, gw, ws, ws_bytes, stream, &C, &V));
-    const hipStream_t s = C.s;
-    const double* xphys;
-    FT_TRY(vjp_forward<double>(C, V, x, n_layers, B, L, act, &xphys));
-    // d/d logJ of every layer, per chain: glogdet[b] - gS[b]
-    if (n_layers > 0) FT_TRY(glogdet ? launch_lincomb(glogdet, 1.0, gS, -1.0, 0.0, V.glj, B, s)
-                                     : launch_lincomb(gS, -1.0, nullptr, 0.0, 0.0, V.glj, B, s));
-    double* gp;
-    FT_TRY(vjp_backward<double>(C, V, xphys, n_layers, B, L, act, beta, gS, V.glj, 0.0, gw, &gp));
-    return gx ? launch_kick_from_gp(gp, nullptr, nullptr, gx, B, L, 0.0, 0.0, s) : FTHMC_OK;
-}
-
-int fthmc_ft_force_vjp(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act,
-                       double beta, const double* g, double* gx, double* gw, void* ws, size_t ws_bytes, void* stream) {
-    Ctx C; VWS V;
-    FT_TRY(vjp_begin(x, w, arch, n_layers, B, L, act, g, gx, gw, ws, ws_bytes, stream, &C, &V));
-    const hipStream_t s = C.s;
-    const size_t n2 = (size_t)B * 2 * L * L;
-    // the eps parts of the dual sweep's link and weight gradients are H g and d/dw <g, F>
-    FT_TRY(launch_dual_pack(x, g, V.xd, n2, s));
-    const Dual* xphys;
-    FT_TRY(vjp_forward<Dual>(C, V, V.xd, n_layers, B, L, act, &xphys));
-    Dual* gp;
-    FT_TRY(vjp_backward<Dual>(C, V, xphys, n_layers, B, L, act, beta, nullptr, nullptr, -1.0, gw ? V.gw : nullptr, &gp));
-    if (gw && n_layers > 0) FT_TRY(launch_dual_tangent(V.gw, gw, (size_t)n_layers * C.A.params(), s));
-    return gx ? launch_dual_links(gp, gx, B, L, s) : FTHMC_OK;
-}
-
-// ---- force-norm training: sum_b |F_b|^2 and its weight gradient (ipynb/ft_hmc.py:253-299).  With xi fixed and F = d(sum S_eff)/dxi,
-// d/dw sum_b |F_b|^2 = 2 d/dw <g, F> at g = F: one first-order force, then the dual sweep of fthmc_ft_force_vjp seeded with it.
-int fthmc_set_dual_path(int on) {
-    if (on < 0 || on > 3) return FTHMC_ERR_ARG;
-    set_dual_path(on);
-    return FTHMC_OK;
-}
-int fthmc_get_dual_path(void) { return get_dual_path(); }
-
-}  // extern "C"
-
-namespace {
-int g_dual_path = 1;
-// the tile of the fused dual kernels that serves a call (flow_dual.hip), -1: the plain dual kernels
-inline int force_dual_tile(const FlowArch& A, int B, int L, int path) {
-    if (path == 0 || !A.is_default()) return -1;
-    // 8 x 16 tiles where they divide the lattice and give every CU a workgroup (measured: config 3 9.6 vs 11.8 ms, config-5 shard
-    // 75 vs 92 ms; config 2, 64 such tiles on 256 CUs: 0.41 vs 0.33 ms), 8 x 8 tiles otherwise
-    const bool wide = flow_dual_shape(B, L, 1) && (path == 3 || (path == 1 && (long)B * flow_dual_geom(1).ntiles(L) >= 256));
-    if (wide) return 1;
-    return flow_dual_shape(B, L, 0) ? 0 : -1;
-}
-// Workspace of fthmc_train_force_grad: a whole workspace of fthmc_ft_force first (the head with the weight expansions included:
-// the first-order sweep runs there as in any force call), behind it the force itself and the regions of the dual sweep -- the
-// fused kernels' (dual input, checkpoint chain, plaquette gradient, its partial windows, the weight-gradient partial rows and
-// the reduction's rows) or the plain kernels' (vjp_layout).  total = 0: the sizes overflow size_t.
-struct FWS { size_t first; double* F; Dual *xd, *X, *gp, *gpp; double *gwp, *gwt; VWS V; size_t total; };
-FWS force_layout(const FlowArch& A, double* base, int B, int L, int nl, int tile) {
-    FWS w{};
-    // ws_layout (the first-order workspace) adds its regions unchecked: it is asked only where the plain dual layout, which is
-    // larger region by region and IS checked, stays far from the end of size_t.  Everything this function adds itself is checked.
-    const size_t bound = vjp_layout(A, nullptr, B, L, nl, 0).total;
-    if (bound == 0 || bound > SIZE_MAX / 64) return w;
-    bool ovf = false;
-    auto mul = [&](size_t a, size_t b) { size_t r = 0; ovf |= __builtin_mul_overflow(a, b, &r); return r; };
-    w.first = up(ws_doubles(A, B, L, nl));
-    size_t o = w.first;
-    auto take = [&](size_t n) {                                    // n doubles
-        double* p = base && !ovf ? base + o : nullptr;
-        size_t padded = 0;
-        ovf |= __builtin_add_overflow(n, ALIGN - 1, &padded);
-        ovf |= __builtin_add_overflow(o, padded / ALIGN * ALIGN, &o);
-        return p;
-    };
-    const size_t n1 = mul(mul((size_t)B, (size_t)L), (size_t)L), n2 = mul(2, n1);
-    w.F = take(n2);
-    if (tile < 0) {
-        if (ovf) return w;
-        w.V = vjp_layout(A, base, B, L, nl, o);
-        w.total = w.V.total;
-        return w;
-    }
-    w.xd = reinterpret_cast<Dual*>(take(mul(2, n2)));
-    w.X = reinterpret_cast<Dual*>(take(mul(mul(2, (size_t)nl), n2)));
-    w.gp = reinterpret_cast<Dual*>(take(mul(2, n1)));
-    const FlowGeom g = flow_dual_geom(tile);
-    w.gpp = reinterpret_cast<Dual*>(take(nl > 0 ? mul(2, mul(mul((size_t)B, (size_t)g.ntiles(L)), (size_t)g.n0())) : 0));
-    w.gwp = take(nl > 0 ? mul((size_t)flow_dual_nparts(B, L, tile), FLOW_GW_STRIDE) : 0);
-    w.gwt = take(nl > 0 ? mul((size_t)FLOW_REDUCE_GROUPS, FLOW_GW_STRIDE) : 0);
-    w.total = ovf || o > SIZE_MAX / sizeof(double) ? 0 : o;
-    if (w.total == 0) w = FWS{};
-    return w;
-}
-}  // namespace
-
-namespace fthmc {
-void set_dual_path(int v) { g_dual_path = v; }
-int get_dual_path() { return g_dual_path; }
-}  // namespace fthmc
-
-extern "C" {
-
-int fthmc_train_force_path(const fthmc_arch_t* arch, int B, int L) {
-    Ctx C;
-    if (make_ctx(arch, nullptr, &C) != FTHMC_OK) return FTHMC_ERR_UNSUPPORTED;
-    return force_dual_tile(C.A, B, L, get_dual_path()) >= 0 ? 1 : 0;
-}
-
-size_t fthmc_train_force_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
-    Ctx C;
-    if (bad_shape(B, L) || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
-    if (n_layers > 0 && C.A.k / 2 > L) return 0;
-    return force_layout(C.A, nullptr, B, L, n_layers, force_dual_tile(C.A, B, L, get_dual_path())).total * sizeof(double);
-}
-
-int fthmc_train_force_grad(const double* xi, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L,
-                           int act, double beta, double* F, double* force_sq, double* gw,
-                           void* ws, size_t ws_bytes, void* stream) {
-    (void)hipGetLastError();
-    FT_TRY(check_flow_call(xi && force_sq, w, n_layers, B, L, act));
-    Ctx C;
-    FT_TRY(make_ctx(arch, stream, &C));
-    if (n_layers > 0 && C.A.k / 2 > L) return FTHMC_ERR_UNSUPPORTED;
-    const hipStream_t s = C.s;
-    const int nl = n_layers, tile = force_dual_tile(C.A, B, L, get_dual_path());
-    if (force_layout(C.A, nullptr, B, L, nl, tile).total == 0) return FTHMC_ERR_UNSUPPORTED;
-    const FWS W = force_layout(C.A, static_cast<double*>(ws), B, L, nl, tile);
-    if (!ws || ws_bytes < W.total * sizeof(double)) return FTHMC_ERR_WS;
-    // the first-order force, as fthmc_ft_force computes it, in the front part of the workspace
-    double* Fo = F ? F : W.F;
-    FT_TRY(fthmc_ft_force_v(xi, w, arch, nl, B, L, act, beta, Fo, ws, W.first * sizeof(double), stream, 0));
-    FT_TRY(launch_kinetic(Fo, B, L, force_sq, s));                       // sum over the links of F^2, one workgroup per chain
-    if (!gw || nl == 0) return FTHMC_OK;
-    const size_t n1 = (size_t)B * L * L, n2 = 2 * n1;
-    if (tile < 0) {                                                      // the plain dual kernels: fthmc_ft_force_vjp's sweep at g = F
-        C.wcan = w;
-        FT_TRY(launch_dual_pack(xi, Fo, W.V.xd, n2, s));
-        const Dual* xphys;
-        FT_TRY(vjp_forward<Dual>(C, W.V, W.V.xd, nl, B, L, act, &xphys));
-        Dual* gp;
-        FT_TRY(vjp_backward<Dual>(C, W.V, xphys, nl, B, L, act, beta, nullptr, nullptr, -1.0, W.V.gw, &gp));
-        return launch_dual_tangent(W.V.gw, gw, (size_t)nl * C.A.params(), s, 2.0);
-    }
-    // the fused dual kernels (flow_dual.hip) on the weight expansion the force call has just left in the head
-    const double* wint = static_cast<const double*>(ws);
-    FT_TRY(launch_dual_pack(xi, Fo, W.xd, n2, s));
-    auto layer = [&](int l) {
-        FlowDualArgs a{};
-        a.x = l == 0 ? W.xd : W.X + (size_t)(l - 1) * n2;
-        a.wint = wint + (size_t)l * FLOW_WINT;
-        a.B = B; a.L = L; a.mu = layer_mu(l); a.off = layer_off(l); a.act = act;
-        return a;
-    };
-    for (int l = 0; l < nl; ++l) {
-        FlowDualArgs a = layer(l);
-        a.y = W.X + (size_t)l * n2;
-        FT_TRY(launch_flow_dual_fwd(a, tile, s));
-    }
-    FT_TRY(launch_gen_seed(W.X + (size_t)(nl - 1) * n2, nullptr, B, L, beta, W.gp, s));
-    const int np = flow_dual_nparts(B, L, tile);
-    for (int l = nl - 1; l >= 0; --l) {
-        FlowDualArgs a = layer(l);
-        a.up_gp = W.gp; a.gp_part = W.gpp; a.gw_part = W.gwp; a.glogj_const = -1.0;
-        FT_TRY(launch_flow_dual_bwd(a, tile, s));
-        FT_TRY(launch_reduce_gw(W.gwp, np, 2.0, 0, gw + (size_t)l * FTHMC_W_PER_LAYER, W.gwt, s));
-        if (l > 0) FT_TRY(launch_gather_gp_dual(W.gpp, B, L, tile, W.gp, s));      // nothing reads the plaquette gradient at xi
     }
     return FTHMC_OK;
 }

@@ -38,7 +38,7 @@ san_integrator:
 # tests/hip/tempering_walk.cpp as a stand-alone program against the host-side sanitizer build of the library (built first when it
 # is missing or older than a source), the sanitizer runtimes linked in (nothing to preload), run by tests/test_tempering.py
 SANTEMP ?= $(SANDIR)/tempering_walk
-$(SANOUT): $(SRCS) common.h kernels.h integrator.h topo_int.h ../../include/fthmc_hip.h san.mk
+$(SANOUT): $(SRCS) common.h kernels.h integrator.h topo_int.h api_call.h ../../include/fthmc_hip.h san.mk
 	@$(MAKE) --no-print-directory -f san.mk san_build
 san_tempering: $(SANOUT)
 	mkdir -p $(dir $(SANTEMP))
@@ -67,3 +67,15 @@ san_instanton: $(SANOUT)
 	mkdir -p $(dir $(SANINST))
 	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
 	  ../../tests/hip/instanton_walk.cpp -o $(SANINST) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
+
+# The workspace layouts of api_call.h (ws_layout, vjp_layout, force_layout on one carver): tests/hip/layout_walk.cpp includes the
+# header itself (hipcc's host pass: the header pulls in the HIP headers) with the unsigned-overflow check on top, and asks the
+# library's size queries in the same way; run by tests/test_ws_sizes.py
+SANLAYOUT ?= $(SANDIR)/layout_walk
+san_layout: $(SANOUT)
+	mkdir -p $(dir $(SANLAYOUT))
+	$(HIPCC) -std=c++17 --offload-arch=$(ARCH) --offload-host-only -x hip -O1 -g -fno-omit-frame-pointer -Wno-unused -I. \
+	  -fsanitize=address,undefined,unsigned-integer-overflow -fno-sanitize-recover=undefined,unsigned-integer-overflow \
+	  -c ../../tests/hip/layout_walk.cpp -o $(SANLAYOUT).o
+	$(ROCM)/lib/llvm/bin/clang++ -fsanitize=address,undefined -shared-libsan $(SANLAYOUT).o -o $(SANLAYOUT) \
+	  -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))

@@ -8,7 +8,7 @@ restates both sides; here
   * the restated lines are pinned to the source text (an edit there fails until the model follows),
   * over a sweep of shapes every item is walked exactly once, nothing beyond the items is walked, and the rows the workgroups
     write are exactly 0 .. nparts - 1 (the claim "valid groups are a prefix of this numbering"),
-  * those rows and the reduction's fit the workspace (csrc/api.hip ws_layout),
+  * those rows and the reduction's fit the workspace (csrc/api_call.h ws_layout),
   * the shapes of tests/test_walked_wgrad_gpu.py walk as that module says -- a change of the heuristics that takes the walks
     out of a GPU case fails here, without a GPU.
 """
@@ -24,7 +24,8 @@ CSRC = os.path.join(ROOT, 'fthmc_amd', 'csrc')
 
 
 def src(name):
-    return open(os.path.join(CSRC, name)).read()
+    """a source's text; api.hip: with api_call.h in front of it, where its layouts live"""
+    return ''.join(open(os.path.join(CSRC, n)).read() for n in (('api_call.h', name) if name == 'api.hip' else (name,)))
 
 
 # ---------------------------------------------------------------- the model is the source

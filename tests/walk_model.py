@@ -6,7 +6,7 @@
     walks, workgroups of one XCD that walk side by side, rows of the partial buffer;
   * both kernels (csrc/flow_bwd_common.h walk_of_block): blockIdx.x -> (r_, s_, kr, first, grp, nwalk) with the early return, and
     the launchers' grid = 8 * R * ns (csrc/kernels.h walk_grid_x);
-  * csrc/api.hip ws_layout / csrc/kernels.h: the rows a training workspace has for the partials and for the reduction.
+  * csrc/api_call.h ws_layout / csrc/kernels.h: the rows a training workspace has for the partials and for the reduction.
 
 tests/test_walk_maps.py pins every line restated here to the source text and checks the properties the host code relies on;
 tests/test_walked_wgrad_gpu.py asserts through this model that each of its shapes (LAYER_SHAPES, TRAIN_SHAPES below) walks as
@@ -125,7 +125,7 @@ def fused_histogram(B, L):
     return histogram(items, tpw, ns)
 
 
-# ---- the rows of a training workspace (api.hip ws_layout, default net shape)
+# ---- the rows of a training workspace (api_call.h ws_layout, default net shape)
 def flow_ntiles_max(L):
     a, b = ntiles(L), 2 * ntiles(L)
     return a if a > b else b

@@ -1,5 +1,5 @@
 """The scratch contract of include/fthmc_hip.h as a table: every entry point that takes a workspace, the shapes at which each
-kernel family, layout branch and launch shape of csrc/api.hip ws_layout / vjp_layout / force_layout is reached, and the guarded
+kernel family, layout branch and launch shape of csrc/api_call.h ws_layout / vjp_layout / force_layout is reached, and the guarded
 buffers the calls run in.  Shared by tests/test_workspace_contract.py (CPU: the size queries, and that the table reaches what it
 claims) and tests/test_workspace_contract_gpu.py (the calls).  A plain module: nothing here touches a GPU at import.
 
