@@ -22,21 +22,29 @@
 namespace {
 
 using at::Tensor;
+using OptTensor = c10::optional<Tensor>;
 using IntList = c10::optional<at::IntArrayRef>;
+using Tensor2 = std::tuple<Tensor, Tensor>;
+using Tensor3 = std::tuple<Tensor, Tensor, Tensor>;
+using DeviceGuard = c10::hip::OptionalHIPGuardMasqueradingAsCUDA;
 
-// every operator runs with its first tensor's device current: the workspace and the outputs are allocated there and the launch
-// goes to THAT device's current stream, whatever device the calling thread had selected (several GPUs in one process)
-#define FT_DEVICE_GUARD(t) const c10::hip::OptionalHIPGuardMasqueradingAsCUDA device_guard_((t).device())
-
-void* cur_stream(const Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
-
+// ---------------------------------------------------------------- checked inputs
 const double* cp(const Tensor& t) { return t.const_data_ptr<double>(); }
+const double* cp_or_null(const Tensor& t) { return t.defined() ? cp(t) : nullptr; }
 double* mp(Tensor& t) { return t.mutable_data_ptr<double>(); }
 
-Tensor dev64(const Tensor& t, const char* name) {
+void on_device(const Tensor& t, const char* name) {
     TORCH_CHECK(t.is_cuda(), name, ": tensor lives on ", t.device(), "; fthmc_hip runs on the MI355X only (no CPU fallback)");
+}
+Tensor dev64(const Tensor& t, const char* name) {
+    on_device(t, name);
     TORCH_CHECK(t.scalar_type() == at::kDouble, name, ": dtype ", t.scalar_type(), "; the HIP path computes in float64");
     return t.contiguous();
+}
+Tensor i32(const Tensor& t, int64_t n, const char* name) {
+    on_device(t, name);
+    TORCH_CHECK(t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() == n, name, ": expected a contiguous int32 tensor of ", n, " entries");
+    return t;
 }
 Tensor field(const Tensor& t, const char* name) {
     Tensor f = dev64(t, name);
@@ -44,6 +52,32 @@ Tensor field(const Tensor& t, const char* name) {
     TORCH_CHECK(f.size(2) % 4 == 0, name, ": L = ", f.size(2), " must be a multiple of 4 (stripe masks have period 4)");
     return f;
 }
+// a second field of a call (momenta, a cotangent)
+Tensor shaped_like(const Tensor& x, const Tensor& t, const char* name) {
+    Tensor f = field(t, name);
+    TORCH_CHECK(f.sizes() == x.sizes(), name, ": shaped like x expected");
+    return f;
+}
+Tensor weights(const Tensor& w, int64_t expect, const char* name) {
+    Tensor f = dev64(w, name).reshape({-1});
+    TORCH_CHECK(f.numel() == expect, name, ": expected ", expect, " doubles for this net shape, got ", f.numel());
+    return f;
+}
+Tensor perchain(const Tensor& t, int64_t B, const char* name) {
+    Tensor f = dev64(t, name).reshape({-1});
+    TORCH_CHECK(f.numel() == B, name, ": expected ", B, " entries, got ", f.numel());
+    return f;
+}
+// an absent optional tensor is an undefined Tensor (cp_or_null hands the library a null pointer for it)
+Tensor optional_perchain(const OptTensor& t, int64_t B, const char* name) { return t.has_value() ? perchain(*t, B, name) : Tensor(); }
+Tensor seeds64(const OptTensor& t, int64_t B) {
+    if (!t.has_value()) return Tensor();
+    Tensor seeds = t->contiguous();
+    TORCH_CHECK(seeds.is_cuda() && seeds.scalar_type() == at::kLong && seeds.numel() == B, "seeds: expected ", B, " int64 seeds on the HIP device");
+    return seeds;
+}
+const int64_t* seeds_or_null(const Tensor& seeds) { return seeds.defined() ? seeds.const_data_ptr<int64_t>() : nullptr; }
+
 void ok(int rc, const char* what) {
     TORCH_CHECK(rc == FTHMC_OK, what, " failed: ", fthmc_strerror(rc), " (code ", rc, ") ", rc == FTHMC_ERR_LAUNCH ? fthmc_last_error() : "");
 }
@@ -66,140 +100,138 @@ struct Arch {
     int64_t params() const { const int p = fthmc_arch_params(ptr()); TORCH_CHECK(p > 0, "net shape beyond the limits of the HIP kernels"); return p; }
 };
 
+// ---------------------------------------------------------------- the per-call scratch, allocated by torch
+Tensor scratch(size_t bytes, const Tensor& like) { return at::empty({(int64_t)((bytes + 7) / 8)}, like.options()); }
+
+enum class Ws { plain, train, vjp, train_force };     // which size query of the C ABI a call's workspace answers to
+
 struct Workspace {
     Tensor buf; size_t bytes;
-    Workspace(const Tensor& like, const fthmc_arch_t* arch, int B, int L, int nl, bool train = false, bool vjp = false, bool force = false) {
-        bytes = force ? fthmc_train_force_ws_bytes(arch, B, L, nl) : vjp ? fthmc_vjp_ws_bytes(arch, B, L, nl) : train ? fthmc_train_ws_bytes(arch, B, L, nl) : fthmc_ws_bytes(arch, B, L, nl);
+    Workspace(Ws kind, const Tensor& like, const fthmc_arch_t* arch, int B, int L, int nl) {
+        switch (kind) {
+            case Ws::plain: bytes = fthmc_ws_bytes(arch, B, L, nl); break;
+            case Ws::train: bytes = fthmc_train_ws_bytes(arch, B, L, nl); break;
+            case Ws::vjp: bytes = fthmc_vjp_ws_bytes(arch, B, L, nl); break;
+            case Ws::train_force: bytes = fthmc_train_force_ws_bytes(arch, B, L, nl); break;
+        }
         TORCH_CHECK(bytes > 0, "unsupported shape (B = ", B, ", L = ", L, ", n_layers = ", nl, ")");
-        buf = at::empty({(int64_t)((bytes + 7) / 8)}, like.options());
+        buf = scratch(bytes, like);
     }
     void* ptr() { return buf.mutable_data_ptr<double>(); }
 };
 
-Tensor weights(const Tensor& w, int64_t expect, const char* name) {
-    Tensor f = dev64(w, name).reshape({-1});
-    TORCH_CHECK(f.numel() == expect, name, ": expected ", expect, " doubles for this net shape, got ", f.numel());
-    return f;
-}
-Tensor perchain(const Tensor& t, int64_t B, const char* name) {
-    Tensor f = dev64(t, name).reshape({-1});
-    TORCH_CHECK(f.numel() == B, name, ": expected ", B, " entries, got ", f.numel());
-    return f;
-}
+// ---------------------------------------------------------------- the prologue of every operator
+// A call on a field: it runs with that tensor's device current -- the workspace and the outputs are allocated there and the launch
+// goes to THAT device's current stream, whatever device the calling thread had selected (several GPUs in one process).
+struct FieldCall {
+    const DeviceGuard guard;
+    const Tensor x;                     // checked and contiguous
+    const int B, L;
+    void* const stream;
+    explicit FieldCall(const Tensor& x_, const char* name = "x")
+        : guard(x_.device()), x(field(x_, name)), B((int)x.size(0)), L((int)x.size(2)),
+          stream(c10::hip::getCurrentHIPStream(x.device().index()).stream()) {}
+    Tensor like_x() const { return at::empty_like(x); }
+    Tensor per_chain(at::ScalarType dtype = at::kDouble) const { return at::empty({B}, x.options().dtype(dtype)); }
+    Workspace workspace() const { return Workspace(Ws::plain, x, nullptr, B, L, 0); }
+};
+// A call through the flow: the net shape from the schema's integers, and the weights of one layer ("w", n_layers = 1) or of all
+// n_layers ("w_all") checked against it.
+struct FlowCall : FieldCall {
+    const Arch A;
+    const Tensor w;
+    const int nl;
+    FlowCall(const Tensor& x_, const char* xname, const Tensor& w_, const char* wname, int64_t n_layers, int64_t n_mix, IntList hidden,
+             int64_t kernel_size)
+        : FieldCall(x_, xname), A(n_mix, hidden, kernel_size), w(weights(w_, n_layers * A.params(), wname)), nl((int)n_layers) {}
+    Tensor like_w() const { return at::empty({w.numel()}, x.options()); }
+    // a weight gradient that the library skips without layers: zeroed, and handed over only where there are layers
+    Tensor zero_gw() const { return at::zeros({w.numel()}, x.options()); }
+    double* gw_ptr(Tensor& gw) const { return nl > 0 ? mp(gw) : nullptr; }
+    Workspace workspace(Ws kind = Ws::plain) const { return Workspace(kind, x, A.ptr(), B, L, nl); }
+};
 
 // ---------------------------------------------------------------- Wilson
-std::tuple<Tensor, Tensor, Tensor> wilson_action_charge(const Tensor& x_, double beta) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    const int B = (int)x.size(0), L = (int)x.size(2);
-    Tensor S = at::empty({B}, x.options()), Q = at::empty({B}, x.options()), plaq = at::empty({B}, x.options());
-    ok(fthmc_wilson_action_charge(cp(x), B, L, beta, mp(S), mp(Q), mp(plaq), cur_stream(x)), "fthmc_wilson_action_charge");
+Tensor3 wilson_action_charge(const Tensor& x, double beta) {
+    FieldCall c(x);
+    Tensor S = c.per_chain(), Q = c.per_chain(), plaq = c.per_chain();
+    ok(fthmc_wilson_action_charge(cp(c.x), c.B, c.L, beta, mp(S), mp(Q), mp(plaq), c.stream), "fthmc_wilson_action_charge");
     return {S, Q, plaq};
 }
-Tensor wilson_force(const Tensor& x_, double beta) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    Tensor F = at::empty_like(x);
-    ok(fthmc_wilson_force(cp(x), (int)x.size(0), (int)x.size(2), beta, mp(F), cur_stream(x)), "fthmc_wilson_force");
+Tensor wilson_force(const Tensor& x, double beta) {
+    FieldCall c(x);
+    Tensor F = c.like_x();
+    ok(fthmc_wilson_force(cp(c.x), c.B, c.L, beta, mp(F), c.stream), "fthmc_wilson_force");
     return F;
 }
 // the table of Wilson loops [B, Rmax, Tmax] (no autograd formula: an observable)
-Tensor wilson_loops(const Tensor& x_, int64_t Rmax, int64_t Tmax) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    const int B = (int)x.size(0), L = (int)x.size(2);
-    TORCH_CHECK(Rmax >= 1 && Rmax <= L && Tmax >= 1 && Tmax <= L, "wilson_loops: 1 <= Rmax, Tmax <= L = ", L, " expected, got ", Rmax, ", ", Tmax);
-    const size_t bytes = fthmc_wilson_loops_ws_bytes(B, L, (int)Rmax, (int)Tmax);
-    TORCH_CHECK(bytes > 0, "wilson_loops: unsupported shape (B = ", B, ", L = ", L, ", Rmax = ", Rmax, ", Tmax = ", Tmax, ")");
-    Tensor ws = at::empty({(int64_t)((bytes + 7) / 8)}, x.options()), W = at::empty({B, Rmax, Tmax}, x.options());
-    ok(fthmc_wilson_loops(cp(x), B, L, (int)Rmax, (int)Tmax, mp(W), nullptr, mp(ws), bytes, cur_stream(x)), "fthmc_wilson_loops");
+Tensor wilson_loops(const Tensor& x, int64_t Rmax, int64_t Tmax) {
+    FieldCall c(x);
+    TORCH_CHECK(Rmax >= 1 && Rmax <= c.L && Tmax >= 1 && Tmax <= c.L, "wilson_loops: 1 <= Rmax, Tmax <= L = ", c.L, " expected, got ", Rmax, ", ", Tmax);
+    const size_t bytes = fthmc_wilson_loops_ws_bytes(c.B, c.L, (int)Rmax, (int)Tmax);
+    TORCH_CHECK(bytes > 0, "wilson_loops: unsupported shape (B = ", c.B, ", L = ", c.L, ", Rmax = ", Rmax, ", Tmax = ", Tmax, ")");
+    Tensor ws = scratch(bytes, c.x), W = at::empty({c.B, Rmax, Tmax}, c.x.options());
+    ok(fthmc_wilson_loops(cp(c.x), c.B, c.L, (int)Rmax, (int)Tmax, mp(W), nullptr, mp(ws), bytes, c.stream), "fthmc_wilson_loops");
     return W;
 }
 // heatbath / overrelaxation sweeps -> the updated field (no autograd formula: a sampler step)
-Tensor local_update(const Tensor& x_, double beta, const c10::optional<Tensor>& beta_b_, const c10::optional<Tensor>& seeds_, int64_t n_hb,
-                    int64_t n_or, int64_t nsweep, int64_t sweep0, int64_t classes) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    const int B = (int)x.size(0), L = (int)x.size(2);
+Tensor local_update(const Tensor& x, double beta, const OptTensor& beta_b_, const OptTensor& seeds_, int64_t n_hb, int64_t n_or, int64_t nsweep,
+                    int64_t sweep0, int64_t classes) {
+    FieldCall c(x);
     TORCH_CHECK(n_hb >= 0 && n_or >= 0 && nsweep >= 0 && n_hb <= INT32_MAX && n_or <= INT32_MAX && nsweep <= INT32_MAX && sweep0 >= 0 &&
                 classes >= 1 && classes <= 15, "local_update: counts >= 0, sweep0 >= 0 and classes in 1 .. 15 expected");
-    Tensor beta_b, seeds;
-    if (beta_b_.has_value()) beta_b = perchain(*beta_b_, B, "beta_b");
-    if (seeds_.has_value()) {
-        seeds = seeds_->contiguous();
-        TORCH_CHECK(seeds.is_cuda() && seeds.scalar_type() == at::kLong && seeds.numel() == B, "seeds: expected ", B, " int64 seeds on the HIP device");
-    }
+    Tensor beta_b = optional_perchain(beta_b_, c.B, "beta_b"), seeds = seeds64(seeds_, c.B);
     TORCH_CHECK(n_hb == 0 || seeds.defined(), "local_update: heatbath sweeps need seeds");
-    Tensor out = at::empty_like(x);
-    ok(fthmc_local_update(cp(x), B, L, beta, beta_b.defined() ? cp(beta_b) : nullptr, seeds.defined() ? seeds.const_data_ptr<int64_t>() : nullptr,
-                          (int)n_hb, (int)n_or, (int)nsweep, sweep0, (int)classes, mp(out), cur_stream(x)), "fthmc_local_update");
+    Tensor out = c.like_x();
+    ok(fthmc_local_update(cp(c.x), c.B, c.L, beta, cp_or_null(beta_b), seeds_or_null(seeds), (int)n_hb, (int)n_or, (int)nsweep, sweep0,
+                          (int)classes, mp(out), c.stream), "fthmc_local_update");
     return out;
 }
 // instanton hits -> (the updated field, the applied charge k, the accepted steps), k and nacc int32 [B] (no autograd formula: a
 // sampler step); the library chooses the launch shape
-std::tuple<Tensor, Tensor, Tensor> instanton_hit(const Tensor& x_, double beta, const c10::optional<Tensor>& beta_b_, const c10::optional<Tensor>& seeds_,
-                                                 int64_t n_hit, int64_t hit0) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    const int B = (int)x.size(0), L = (int)x.size(2);
+Tensor3 instanton_hit(const Tensor& x, double beta, const OptTensor& beta_b_, const OptTensor& seeds_, int64_t n_hit, int64_t hit0) {
+    FieldCall c(x);
     TORCH_CHECK(n_hit >= 0 && n_hit <= 1024 && hit0 >= 0 && hit0 <= ((int64_t)1 << 32) - n_hit,
                 "instanton_hit: n_hit in 0 .. 1024 and hit0 >= 0 with hit0 + n_hit <= 2^32 expected");
-    Tensor beta_b, seeds;
-    if (beta_b_.has_value()) beta_b = perchain(*beta_b_, B, "beta_b");
-    if (seeds_.has_value()) {
-        seeds = seeds_->contiguous();
-        TORCH_CHECK(seeds.is_cuda() && seeds.scalar_type() == at::kLong && seeds.numel() == B, "seeds: expected ", B, " int64 seeds on the HIP device");
-    }
+    Tensor beta_b = optional_perchain(beta_b_, c.B, "beta_b"), seeds = seeds64(seeds_, c.B);
     TORCH_CHECK(n_hit == 0 || seeds.defined(), "instanton_hit: hits need seeds");
-    Tensor out = at::empty_like(x), k = at::empty({B}, x.options().dtype(at::kInt)), nacc = at::empty({B}, x.options().dtype(at::kInt));
-    const size_t bytes = fthmc_instanton_ws_bytes(B, L, 0);
+    Tensor out = c.like_x(), k = c.per_chain(at::kInt), nacc = c.per_chain(at::kInt);
+    const size_t bytes = fthmc_instanton_ws_bytes(c.B, c.L, 0);
     Tensor ws;
-    if (bytes > 0) ws = at::empty({(int64_t)((bytes + 7) / 8)}, x.options());
-    ok(fthmc_instanton_hit(cp(x), B, L, beta, beta_b.defined() ? cp(beta_b) : nullptr, seeds.defined() ? seeds.const_data_ptr<int64_t>() : nullptr,
-                           (int)n_hit, hit0, 0, mp(out), k.mutable_data_ptr<int32_t>(), nacc.mutable_data_ptr<int32_t>(), nullptr,
-                           bytes > 0 ? mp(ws) : nullptr, bytes, cur_stream(x)), "fthmc_instanton_hit");
+    if (bytes > 0) ws = scratch(bytes, c.x);
+    ok(fthmc_instanton_hit(cp(c.x), c.B, c.L, beta, cp_or_null(beta_b), seeds_or_null(seeds), (int)n_hit, hit0, 0, mp(out),
+                           k.mutable_data_ptr<int32_t>(), nacc.mutable_data_ptr<int32_t>(), nullptr, bytes > 0 ? mp(ws) : nullptr, bytes, c.stream),
+       "fthmc_instanton_hit");
     return {out, k, nacc};
 }
-std::tuple<Tensor, Tensor, Tensor> hmc_trajectory(const Tensor& x_, const Tensor& v_, const Tensor& u_, double beta, double dt, int64_t nstep) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x"), v = field(v_, "v");
-    const int B = (int)x.size(0), L = (int)x.size(2);
-    Tensor u = perchain(u_, B, "u");
-    TORCH_CHECK(v.sizes() == x.sizes(), "v: shaped like x expected");
-    Tensor xn = at::empty_like(x), dH = at::empty({B}, x.options()), acc = at::empty({B}, x.options());
-    Workspace ws(x, nullptr, B, L, 0);
-    ok(fthmc_hmc_trajectory(cp(x), cp(v), cp(u), B, L, beta, dt, (int)nstep, mp(xn), mp(dH), mp(acc), nullptr, nullptr, ws.ptr(), ws.bytes,
-                            cur_stream(x)), "fthmc_hmc_trajectory");
+Tensor3 hmc_trajectory(const Tensor& x, const Tensor& v_, const Tensor& u_, double beta, double dt, int64_t nstep) {
+    FieldCall c(x);
+    Tensor v = shaped_like(c.x, v_, "v"), u = perchain(u_, c.B, "u");
+    Tensor xn = c.like_x(), dH = c.per_chain(), acc = c.per_chain();
+    Workspace ws = c.workspace();
+    ok(fthmc_hmc_trajectory(cp(c.x), cp(v), cp(u), c.B, c.L, beta, dt, (int)nstep, mp(xn), mp(dH), mp(acc), nullptr, nullptr, ws.ptr(), ws.bytes,
+                            c.stream), "fthmc_hmc_trajectory");
     return {xn, dH, acc};
 }
 
 // ---------------------------------------------------------------- one coupling layer
-std::tuple<Tensor, Tensor> flow_layer_fwd(const Tensor& x_, const Tensor& w_, int64_t mu, int64_t off, int64_t n_mix, int64_t act,
-                                          IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_, A.params(), "w");
-    const int B = (int)x.size(0), L = (int)x.size(2);
-    Tensor y = at::empty_like(x), logJ = at::empty({B}, x.options());
-    Workspace ws(x, A.ptr(), B, L, 1);
-    ok(fthmc_flow_layer_fwd(cp(x), cp(w), A.ptr(), B, L, (int)mu, (int)off, (int)act, mp(y), mp(logJ), ws.ptr(), ws.bytes, cur_stream(x)),
+Tensor2 flow_layer_fwd(const Tensor& x, const Tensor& w, int64_t mu, int64_t off, int64_t n_mix, int64_t act, IntList hidden, int64_t kernel_size) {
+    FlowCall c(x, "x", w, "w", 1, n_mix, hidden, kernel_size);
+    Tensor y = c.like_x(), logJ = c.per_chain();
+    Workspace ws = c.workspace();
+    ok(fthmc_flow_layer_fwd(cp(c.x), cp(c.w), c.A.ptr(), c.B, c.L, (int)mu, (int)off, (int)act, mp(y), mp(logJ), ws.ptr(), ws.bytes, c.stream),
        "fthmc_flow_layer_fwd");
     return {y, logJ};
 }
-std::tuple<Tensor, Tensor> layer_bwd(const Tensor& x_, const Tensor& gy_, const Tensor& glogJ_, const Tensor& w_, int64_t mu, int64_t off,
-                                     int64_t n_mix, int64_t act, IntList hidden, int64_t kernel_size, bool need_gw) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x"), gy = field(gy_, "gy");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_, A.params(), "w");
-    const int B = (int)x.size(0), L = (int)x.size(2);
-    Tensor glogJ = perchain(glogJ_, B, "glogJ");
-    TORCH_CHECK(gy.sizes() == x.sizes(), "gy: shaped like x expected");
-    Tensor gx = at::empty_like(x), gw = need_gw ? at::empty({w.numel()}, x.options()) : Tensor();
-    Workspace ws(x, A.ptr(), B, L, 1, need_gw);
-    ok(fthmc_flow_layer_bwd(cp(x), cp(w), A.ptr(), cp(gy), cp(glogJ), B, L, (int)mu, (int)off, (int)act, mp(gx), need_gw ? mp(gw) : nullptr,
-                            ws.ptr(), ws.bytes, cur_stream(x)), "fthmc_flow_layer_bwd");
+// the three backward schemas over one launch: gw is computed (and its larger workspace taken) only where asked for
+Tensor2 layer_bwd(const Tensor& x, const Tensor& gy_, const Tensor& glogJ_, const Tensor& w, int64_t mu, int64_t off, int64_t n_mix, int64_t act,
+                  IntList hidden, int64_t kernel_size, bool need_gw) {
+    FlowCall c(x, "x", w, "w", 1, n_mix, hidden, kernel_size);
+    Tensor gy = shaped_like(c.x, gy_, "gy"), glogJ = perchain(glogJ_, c.B, "glogJ");
+    Tensor gx = c.like_x(), gw = need_gw ? c.like_w() : Tensor();
+    Workspace ws = c.workspace(need_gw ? Ws::train : Ws::plain);
+    ok(fthmc_flow_layer_bwd(cp(c.x), cp(c.w), c.A.ptr(), cp(gy), cp(glogJ), c.B, c.L, (int)mu, (int)off, (int)act, mp(gx),
+                            need_gw ? mp(gw) : nullptr, ws.ptr(), ws.bytes, c.stream), "fthmc_flow_layer_bwd");
     return {gx, gw};
 }
 Tensor flow_layer_bwd_x(const Tensor& x, const Tensor& gy, const Tensor& glogJ, const Tensor& w, int64_t mu, int64_t off, int64_t n_mix,
@@ -210,164 +242,116 @@ Tensor flow_layer_bwd_w(const Tensor& x, const Tensor& gy, const Tensor& glogJ, 
                         int64_t act, IntList hidden, int64_t kernel_size) {
     return std::get<1>(layer_bwd(x, gy, glogJ, w, mu, off, n_mix, act, hidden, kernel_size, true));
 }
-std::tuple<Tensor, Tensor> flow_layer_bwd(const Tensor& x, const Tensor& gy, const Tensor& glogJ, const Tensor& w, int64_t mu, int64_t off,
-                                          int64_t n_mix, int64_t act, IntList hidden, int64_t kernel_size) {
+Tensor2 flow_layer_bwd(const Tensor& x, const Tensor& gy, const Tensor& glogJ, const Tensor& w, int64_t mu, int64_t off, int64_t n_mix,
+                       int64_t act, IntList hidden, int64_t kernel_size) {
     return layer_bwd(x, gy, glogJ, w, mu, off, n_mix, act, hidden, kernel_size, true);
 }
-std::tuple<Tensor, Tensor> flow_layer_rev(const Tensor& y_, const Tensor& w_, int64_t mu, int64_t off, int64_t n_mix, int64_t act, double tol,
-                                          IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(y_);
-    Tensor y = field(y_, "y");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_, A.params(), "w");
-    const int B = (int)y.size(0), L = (int)y.size(2);
-    Tensor x = at::empty_like(y), logJ = at::empty({B}, y.options());
-    Workspace ws(y, A.ptr(), B, L, 1);
-    ok(fthmc_flow_layer_rev(cp(y), cp(w), A.ptr(), B, L, (int)mu, (int)off, (int)act, tol, mp(x), mp(logJ), ws.ptr(), ws.bytes, cur_stream(y)),
+Tensor2 flow_layer_rev(const Tensor& y, const Tensor& w, int64_t mu, int64_t off, int64_t n_mix, int64_t act, double tol, IntList hidden,
+                       int64_t kernel_size) {
+    FlowCall c(y, "y", w, "w", 1, n_mix, hidden, kernel_size);      // c.x is y here
+    Tensor x = c.like_x(), logJ = c.per_chain();
+    Workspace ws = c.workspace();
+    ok(fthmc_flow_layer_rev(cp(c.x), cp(c.w), c.A.ptr(), c.B, c.L, (int)mu, (int)off, (int)act, tol, mp(x), mp(logJ), ws.ptr(), ws.bytes, c.stream),
        "fthmc_flow_layer_rev");
     return {x, logJ};
 }
 
 // ---------------------------------------------------------------- whole flow
-std::tuple<Tensor, Tensor, Tensor> ft_action_force(const Tensor& x_, const Tensor& w_all, int64_t n_layers, double beta, int64_t act,
-                                                   int64_t n_mix, IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
-    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
-    Tensor S = at::empty({B}, x.options()), logdet = at::empty({B}, x.options()), F = at::empty_like(x);
-    Workspace ws(x, A.ptr(), B, L, nl);
-    ok(fthmc_ft_action(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, mp(S), mp(logdet), nullptr, nullptr, ws.ptr(), ws.bytes, cur_stream(x)),
+Tensor3 ft_action_force(const Tensor& x, const Tensor& w_all, int64_t n_layers, double beta, int64_t act, int64_t n_mix, IntList hidden,
+                        int64_t kernel_size) {
+    FlowCall c(x, "x", w_all, "w_all", n_layers, n_mix, hidden, kernel_size);
+    Tensor S = c.per_chain(), logdet = c.per_chain(), F = c.like_x();
+    Workspace ws = c.workspace();
+    ok(fthmc_ft_action(cp(c.x), cp(c.w), c.A.ptr(), c.nl, c.B, c.L, (int)act, beta, mp(S), mp(logdet), nullptr, nullptr, ws.ptr(), ws.bytes, c.stream),
        "fthmc_ft_action");
-    ok(fthmc_ft_force(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, mp(F), ws.ptr(), ws.bytes, cur_stream(x)), "fthmc_ft_force");
+    ok(fthmc_ft_force(cp(c.x), cp(c.w), c.A.ptr(), c.nl, c.B, c.L, (int)act, beta, mp(F), ws.ptr(), ws.bytes, c.stream), "fthmc_ft_force");
     return {S, logdet, F};
 }
 // second order (the autograd formula of ft_action_force, torch_ops.py): gw has n_layers * params entries (none without layers)
-std::tuple<Tensor, Tensor> ft_action_vjp(const Tensor& x_, const Tensor& w_all, int64_t n_layers, double beta, int64_t act, const Tensor& gS_,
-                                         const c10::optional<Tensor>& glogdet_, int64_t n_mix, IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
-    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
-    Tensor gS = perchain(gS_, B, "gS");
-    Tensor glogdet = glogdet_.has_value() ? perchain(*glogdet_, B, "glogdet") : Tensor();
-    Tensor gx = at::empty_like(x), gw = at::zeros({w.numel()}, x.options());
-    Workspace ws(x, A.ptr(), B, L, nl, false, true);
-    ok(fthmc_ft_action_vjp(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, cp(gS), glogdet.defined() ? cp(glogdet) : nullptr, mp(gx),
-                           nl > 0 ? mp(gw) : nullptr, ws.ptr(), ws.bytes, cur_stream(x)), "fthmc_ft_action_vjp");
+Tensor2 ft_action_vjp(const Tensor& x, const Tensor& w_all, int64_t n_layers, double beta, int64_t act, const Tensor& gS_, const OptTensor& glogdet_,
+                      int64_t n_mix, IntList hidden, int64_t kernel_size) {
+    FlowCall c(x, "x", w_all, "w_all", n_layers, n_mix, hidden, kernel_size);
+    Tensor gS = perchain(gS_, c.B, "gS"), glogdet = optional_perchain(glogdet_, c.B, "glogdet");
+    Tensor gx = c.like_x(), gw = c.zero_gw();
+    Workspace ws = c.workspace(Ws::vjp);
+    ok(fthmc_ft_action_vjp(cp(c.x), cp(c.w), c.A.ptr(), c.nl, c.B, c.L, (int)act, beta, cp(gS), cp_or_null(glogdet), mp(gx), c.gw_ptr(gw), ws.ptr(),
+                           ws.bytes, c.stream), "fthmc_ft_action_vjp");
     return {gx, gw};
 }
-std::tuple<Tensor, Tensor> ft_force_vjp(const Tensor& x_, const Tensor& w_all, int64_t n_layers, double beta, int64_t act, const Tensor& g_,
-                                        int64_t n_mix, IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x"), g = field(g_, "g");
-    TORCH_CHECK(g.sizes() == x.sizes(), "g: shaped like x expected");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
-    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
-    Tensor gx = at::empty_like(x), gw = at::zeros({w.numel()}, x.options());
-    Workspace ws(x, A.ptr(), B, L, nl, false, true);
-    ok(fthmc_ft_force_vjp(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, cp(g), mp(gx), nl > 0 ? mp(gw) : nullptr, ws.ptr(), ws.bytes,
-                          cur_stream(x)), "fthmc_ft_force_vjp");
+Tensor2 ft_force_vjp(const Tensor& x, const Tensor& w_all, int64_t n_layers, double beta, int64_t act, const Tensor& g_, int64_t n_mix,
+                     IntList hidden, int64_t kernel_size) {
+    FlowCall c(x, "x", w_all, "w_all", n_layers, n_mix, hidden, kernel_size);
+    Tensor g = shaped_like(c.x, g_, "g");
+    Tensor gx = c.like_x(), gw = c.zero_gw();
+    Workspace ws = c.workspace(Ws::vjp);
+    ok(fthmc_ft_force_vjp(cp(c.x), cp(c.w), c.A.ptr(), c.nl, c.B, c.L, (int)act, beta, cp(g), mp(gx), c.gw_ptr(gw), ws.ptr(), ws.bytes, c.stream),
+       "fthmc_ft_force_vjp");
     return {gx, gw};
 }
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> fthmc_trajectory(const Tensor& x_, const Tensor& v_, const Tensor& u_, const Tensor& w_all,
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> fthmc_trajectory(const Tensor& x, const Tensor& v_, const Tensor& u_, const Tensor& w_all,
                                                                     int64_t n_layers, double beta, double dt, int64_t nstep, int64_t mode,
                                                                     int64_t act, int64_t n_mix, IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(x_);
     TORCH_CHECK(mode == FTHMC_MODE_MD || mode == FTHMC_MODE_LITERAL, "mode: expected 0 (md) or 1 (literal), got ", mode);
-    Tensor x = field(x_, "x"), v = field(v_, "v");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
-    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
-    Tensor u = perchain(u_, B, "u");
-    TORCH_CHECK(v.sizes() == x.sizes(), "v: shaped like x expected");
-    auto o = x.options();
-    Tensor xn = at::empty_like(x), dH = at::empty({B}, o), acc = at::empty({B}, o), plaq = at::empty({B}, o), Q = at::empty({B}, o);
-    Workspace ws(x, A.ptr(), B, L, nl);
-    ok(fthmc_ft_trajectory(cp(x), cp(v), cp(u), cp(w), A.ptr(), nl, B, L, (int)act, beta, dt, (int)nstep, (int)mode, mp(xn), mp(dH), mp(acc),
-                           nullptr, nullptr, mp(plaq), mp(Q), nullptr, nullptr, ws.ptr(), ws.bytes, cur_stream(x)), "fthmc_ft_trajectory");
+    FlowCall c(x, "x", w_all, "w_all", n_layers, n_mix, hidden, kernel_size);
+    Tensor v = shaped_like(c.x, v_, "v"), u = perchain(u_, c.B, "u");
+    Tensor xn = c.like_x(), dH = c.per_chain(), acc = c.per_chain(), plaq = c.per_chain(), Q = c.per_chain();
+    Workspace ws = c.workspace();
+    ok(fthmc_ft_trajectory(cp(c.x), cp(v), cp(u), cp(c.w), c.A.ptr(), c.nl, c.B, c.L, (int)act, beta, dt, (int)nstep, (int)mode, mp(xn), mp(dH),
+                           mp(acc), nullptr, nullptr, mp(plaq), mp(Q), nullptr, nullptr, ws.ptr(), ws.bytes, c.stream), "fthmc_ft_trajectory");
     return {xn, dH, acc, plaq, Q};
 }
-std::tuple<Tensor, Tensor, Tensor, Tensor> train_grad(const Tensor& xi_, const Tensor& w_all, int64_t n_layers, double beta, int64_t act,
+std::tuple<Tensor, Tensor, Tensor, Tensor> train_grad(const Tensor& xi, const Tensor& w_all, int64_t n_layers, double beta, int64_t act,
                                                       int64_t n_mix, IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(xi_);
-    Tensor xi = field(xi_, "xi");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
-    const int B = (int)xi.size(0), L = (int)xi.size(2), nl = (int)n_layers;
-    auto o = xi.options();
-    Tensor x = at::empty_like(xi), logq = at::empty({B}, o), logp = at::empty({B}, o), gw = at::empty({w.numel()}, o);
-    Workspace ws(xi, A.ptr(), B, L, nl, true);
-    ok(fthmc_train_grad(cp(xi), cp(w), A.ptr(), nl, B, L, (int)act, beta, mp(x), mp(logq), mp(logp), mp(gw), ws.ptr(), ws.bytes, cur_stream(xi)),
+    FlowCall c(xi, "xi", w_all, "w_all", n_layers, n_mix, hidden, kernel_size);      // c.x is xi here
+    Tensor x = c.like_x(), logq = c.per_chain(), logp = c.per_chain(), gw = c.like_w();
+    Workspace ws = c.workspace(Ws::train);
+    ok(fthmc_train_grad(cp(c.x), cp(c.w), c.A.ptr(), c.nl, c.B, c.L, (int)act, beta, mp(x), mp(logq), mp(logp), mp(gw), ws.ptr(), ws.bytes, c.stream),
        "fthmc_train_grad");
     return {x, logq, logp, gw};
 }
 // the force-norm training step (ipynb/ft_hmc.py:253-299): F, sum F_b^2 and d(sum_b |F_b|^2)/dw (none without layers)
-std::tuple<Tensor, Tensor, Tensor> train_force_grad(const Tensor& x_, const Tensor& w_all, int64_t n_layers, double beta, int64_t act,
-                                                    int64_t n_mix, IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
-    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
-    Tensor F = at::empty_like(x), fsq = at::empty({B}, x.options()), gw = at::zeros({w.numel()}, x.options());
-    Workspace ws(x, A.ptr(), B, L, nl, false, false, true);
-    ok(fthmc_train_force_grad(cp(x), cp(w), A.ptr(), nl, B, L, (int)act, beta, mp(F), mp(fsq), nl > 0 ? mp(gw) : nullptr, ws.ptr(), ws.bytes,
-                              cur_stream(x)), "fthmc_train_force_grad");
+Tensor3 train_force_grad(const Tensor& x, const Tensor& w_all, int64_t n_layers, double beta, int64_t act, int64_t n_mix, IntList hidden,
+                         int64_t kernel_size) {
+    FlowCall c(x, "x", w_all, "w_all", n_layers, n_mix, hidden, kernel_size);
+    Tensor F = c.like_x(), fsq = c.per_chain(), gw = c.zero_gw();
+    Workspace ws = c.workspace(Ws::train_force);
+    ok(fthmc_train_force_grad(cp(c.x), cp(c.w), c.A.ptr(), c.nl, c.B, c.L, (int)act, beta, mp(F), mp(fsq), c.gw_ptr(gw), ws.ptr(), ws.bytes, c.stream),
+       "fthmc_train_force_grad");
     return {F, fsq, gw};
 }
 
 // ---------------------------------------------------------------- per-chain beta and replica exchange
-Tensor i32(const Tensor& t, int64_t n, const char* name) {
-    TORCH_CHECK(t.is_cuda(), name, ": tensor lives on ", t.device(), "; fthmc_hip runs on the MI355X only (no CPU fallback)");
-    TORCH_CHECK(t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() == n, name, ": expected a contiguous int32 tensor of ", n, " entries");
-    return t;
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ft_trajectory_pb(const Tensor& x_, const Tensor& v_, const Tensor& u_, const Tensor& w_all,
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> ft_trajectory_pb(const Tensor& x, const Tensor& v_, const Tensor& u_, const Tensor& w_all,
                                                                             int64_t n_layers, const Tensor& beta_b_, double dt, int64_t nstep,
-                                                                            int64_t integrator, int64_t act, const c10::optional<Tensor>& state_in_,
+                                                                            int64_t integrator, int64_t act, const OptTensor& state_in_,
                                                                             int64_t n_mix, IntList hidden, int64_t kernel_size) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x"), v = field(v_, "v");
-    Arch A(n_mix, hidden, kernel_size);
-    Tensor w = weights(w_all, n_layers * A.params(), "w_all");
-    const int B = (int)x.size(0), L = (int)x.size(2), nl = (int)n_layers;
-    Tensor u = perchain(u_, B, "u"), beta_b = perchain(beta_b_, B, "beta_b");
-    TORCH_CHECK(v.sizes() == x.sizes(), "v: shaped like x expected");
+    FlowCall c(x, "x", w_all, "w_all", n_layers, n_mix, hidden, kernel_size);
+    Tensor v = shaped_like(c.x, v_, "v"), u = perchain(u_, c.B, "u"), beta_b = perchain(beta_b_, c.B, "beta_b");
     Tensor state_in;
     if (state_in_.has_value()) {
         state_in = dev64(*state_in_, "state_in");
-        TORCH_CHECK(state_in.numel() == 3 * (int64_t)B, "state_in: expected [3, ", B, "]");
+        TORCH_CHECK(state_in.numel() == 3 * (int64_t)c.B, "state_in: expected [3, ", c.B, "]");
     }
-    auto o = x.options();
-    Tensor xn = at::empty_like(x), dH = at::empty({B}, o), acc = at::empty({B}, o), plaq = at::empty({B}, o), Q = at::empty({B}, o),
-           state = at::empty({3, B}, o);
-    Workspace ws(x, A.ptr(), B, L, nl);
-    ok(fthmc_ft_trajectory_pb_v(cp(x), cp(v), cp(u), cp(w), A.ptr(), nl, B, L, (int)act, cp(beta_b), dt, (int)nstep, FTHMC_MODE_MD, mp(xn), mp(dH),
-                                mp(acc), nullptr, nullptr, mp(plaq), mp(Q), state_in.defined() ? cp(state_in) : nullptr, mp(state), ws.ptr(),
-                                ws.bytes, cur_stream(x), (int)integrator, 0), "fthmc_ft_trajectory_pb_v");
+    Tensor xn = c.like_x(), dH = c.per_chain(), acc = c.per_chain(), plaq = c.per_chain(), Q = c.per_chain(),
+           state = at::empty({3, c.B}, c.x.options());
+    Workspace ws = c.workspace();
+    ok(fthmc_ft_trajectory_pb_v(cp(c.x), cp(v), cp(u), cp(c.w), c.A.ptr(), c.nl, c.B, c.L, (int)act, cp(beta_b), dt, (int)nstep, FTHMC_MODE_MD,
+                                mp(xn), mp(dH), mp(acc), nullptr, nullptr, mp(plaq), mp(Q), cp_or_null(state_in), mp(state), ws.ptr(), ws.bytes,
+                                c.stream, (int)integrator, 0), "fthmc_ft_trajectory_pb_v");
     return {xn, dH, acc, plaq, Q, state};
 }
-std::tuple<Tensor, Tensor, Tensor> hmc_trajectory_pb(const Tensor& x_, const Tensor& v_, const Tensor& u_, const Tensor& beta_b_, double dt,
-                                                     int64_t nstep, int64_t integrator) {
-    FT_DEVICE_GUARD(x_);
-    Tensor x = field(x_, "x"), v = field(v_, "v");
-    const int B = (int)x.size(0), L = (int)x.size(2);
-    Tensor u = perchain(u_, B, "u"), beta_b = perchain(beta_b_, B, "beta_b");
-    TORCH_CHECK(v.sizes() == x.sizes(), "v: shaped like x expected");
-    Tensor xn = at::empty_like(x), dH = at::empty({B}, x.options()), acc = at::empty({B}, x.options());
-    Workspace ws(x, nullptr, B, L, 0);
-    ok(fthmc_hmc_trajectory_pb(cp(x), cp(v), cp(u), B, L, cp(beta_b), dt, (int)nstep, (int)integrator, mp(xn), mp(dH), mp(acc), nullptr, nullptr,
-                               ws.ptr(), ws.bytes, cur_stream(x)), "fthmc_hmc_trajectory_pb");
+Tensor3 hmc_trajectory_pb(const Tensor& x, const Tensor& v_, const Tensor& u_, const Tensor& beta_b_, double dt, int64_t nstep, int64_t integrator) {
+    FieldCall c(x);
+    Tensor v = shaped_like(c.x, v_, "v"), u = perchain(u_, c.B, "u"), beta_b = perchain(beta_b_, c.B, "beta_b");
+    Tensor xn = c.like_x(), dH = c.per_chain(), acc = c.per_chain();
+    Workspace ws = c.workspace();
+    ok(fthmc_hmc_trajectory_pb(cp(c.x), cp(v), cp(u), c.B, c.L, cp(beta_b), dt, (int)nstep, (int)integrator, mp(xn), mp(dH), mp(acc), nullptr, nullptr,
+                               ws.ptr(), ws.bytes, c.stream), "fthmc_hmc_trajectory_pb");
     return {xn, dH, acc};
 }
-// beta_b, rung and chain_of are updated in place (the schema says so)
-std::tuple<Tensor, Tensor> replica_swap(const Tensor& betas_, const Tensor& C_, const Tensor& u_, Tensor& beta_b, Tensor& rung, Tensor& chain_of,
-                                        int64_t parity) {
-    FT_DEVICE_GUARD(beta_b);
+// no field in this call: it runs on beta_b's device.  beta_b, rung and chain_of are updated in place (the schema says so)
+Tensor2 replica_swap(const Tensor& betas_, const Tensor& C_, const Tensor& u_, Tensor& beta_b, Tensor& rung, Tensor& chain_of, int64_t parity) {
+    const DeviceGuard guard(beta_b.device());
     Tensor betas = dev64(betas_, "betas").reshape({-1});
     const int64_t K = betas.numel(), B = beta_b.numel();
     TORCH_CHECK(beta_b.is_cuda() && beta_b.scalar_type() == at::kDouble && beta_b.is_contiguous(), "beta_b: expected a contiguous float64 device tensor");
@@ -377,55 +361,46 @@ std::tuple<Tensor, Tensor> replica_swap(const Tensor& betas_, const Tensor& C_, 
     i32(rung, B, "rung"); i32(chain_of, B, "chain_of");
     Tensor acc = at::empty({M, K - 1}, beta_b.options()), d = at::empty({M, K - 1}, beta_b.options());
     ok(fthmc_replica_swap(cp(betas), (int)K, (int)M, (int)parity, cp(C), cp(u), mp(beta_b), rung.mutable_data_ptr<int32_t>(),
-                          chain_of.mutable_data_ptr<int32_t>(), mp(acc), mp(d), cur_stream(beta_b)), "fthmc_replica_swap");
+                          chain_of.mutable_data_ptr<int32_t>(), mp(acc), mp(d), c10::hip::getCurrentHIPStream(beta_b.device().index()).stream()),
+       "fthmc_replica_swap");
     return {acc, d};
 }
 
 }  // namespace
 
+// The operators, each named once: X(function, "(arguments) -> returns").  fthmc_amd/torch_ops.py carries the same schema text in its
+// table (tests/test_torch_boundary.py holds the two lists to each other).
+#define FTHMC_OPERATORS(X) \
+    X(wilson_action_charge, "(Tensor x, float beta) -> (Tensor, Tensor, Tensor)") \
+    X(wilson_force, "(Tensor x, float beta) -> Tensor") \
+    X(hmc_trajectory, "(Tensor x, Tensor v, Tensor u, float beta, float dt, int nstep) -> (Tensor, Tensor, Tensor)") \
+    X(flow_layer_fwd, "(Tensor x, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)") \
+    X(flow_layer_bwd_x, "(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> Tensor") \
+    X(flow_layer_bwd_w, "(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> Tensor") \
+    X(flow_layer_bwd, "(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)") \
+    X(flow_layer_rev, "(Tensor y, Tensor w, int mu, int off, int n_mix, int act, float tol, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)") \
+    X(ft_action_force, "(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor)") \
+    X(fthmc_trajectory, "(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, float beta, float dt, int nstep, int mode, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor)") \
+    X(train_grad, "(Tensor xi, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor)") \
+    X(ft_action_vjp, "(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor gS, Tensor? glogdet=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)") \
+    X(ft_force_vjp, "(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor g, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)") \
+    X(train_force_grad, "(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor)") \
+    X(ft_trajectory_pb, "(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, Tensor beta_b, float dt, int nstep, int integrator, int act, Tensor? state_in=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)") \
+    X(hmc_trajectory_pb, "(Tensor x, Tensor v, Tensor u, Tensor beta_b, float dt, int nstep, int integrator=0) -> (Tensor, Tensor, Tensor)") \
+    X(replica_swap, "(Tensor betas, Tensor C, Tensor u, Tensor(a!) beta_b, Tensor(b!) rung, Tensor(c!) chain_of, int parity) -> (Tensor, Tensor)") \
+    X(wilson_loops, "(Tensor x, int Rmax, int Tmax) -> Tensor") \
+    X(local_update, "(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hb=1, int n_or=0, int nsweep=1, int sweep0=0, int classes=15) -> Tensor") \
+    X(instanton_hit, "(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hit=1, int hit0=0) -> (Tensor, Tensor, Tensor)")
+
 TORCH_LIBRARY(fthmc_hip, m) {
-    m.def("wilson_action_charge(Tensor x, float beta) -> (Tensor, Tensor, Tensor)");
-    m.def("wilson_force(Tensor x, float beta) -> Tensor");
-    m.def("wilson_loops(Tensor x, int Rmax, int Tmax) -> Tensor");
-    m.def("hmc_trajectory(Tensor x, Tensor v, Tensor u, float beta, float dt, int nstep) -> (Tensor, Tensor, Tensor)");
-    m.def("flow_layer_fwd(Tensor x, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
-    m.def("flow_layer_bwd_x(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> Tensor");
-    m.def("flow_layer_bwd_w(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> Tensor");
-    m.def("flow_layer_bwd(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
-    m.def("flow_layer_rev(Tensor y, Tensor w, int mu, int off, int n_mix, int act, float tol, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
-    m.def("ft_action_force(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor)");
-    m.def("fthmc_trajectory(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, float beta, float dt, int nstep, int mode, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
-    m.def("train_grad(Tensor xi, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor)");
-    m.def("ft_action_vjp(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor gS, Tensor? glogdet=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
-    m.def("ft_force_vjp(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor g, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)");
-    m.def("train_force_grad(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor)");
-    m.def("ft_trajectory_pb(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, Tensor beta_b, float dt, int nstep, int integrator, int act, Tensor? state_in=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
-    m.def("hmc_trajectory_pb(Tensor x, Tensor v, Tensor u, Tensor beta_b, float dt, int nstep, int integrator=0) -> (Tensor, Tensor, Tensor)");
-    m.def("local_update(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hb=1, int n_or=0, int nsweep=1, int sweep0=0, int classes=15) -> Tensor");
-    m.def("instanton_hit(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hit=1, int hit0=0) -> (Tensor, Tensor, Tensor)");
-    m.def("replica_swap(Tensor betas, Tensor C, Tensor u, Tensor(a!) beta_b, Tensor(b!) rung, Tensor(c!) chain_of, int parity) -> (Tensor, Tensor)");
+#define FTHMC_DEF(name, schema) m.def(#name schema);
+    FTHMC_OPERATORS(FTHMC_DEF)
+#undef FTHMC_DEF
 }
 
 // "CUDA" is the dispatch key of HIP devices in PyTorch-ROCm
 TORCH_LIBRARY_IMPL(fthmc_hip, CUDA, m) {
-    m.impl("wilson_action_charge", &wilson_action_charge);
-    m.impl("wilson_force", &wilson_force);
-    m.impl("wilson_loops", &wilson_loops);
-    m.impl("hmc_trajectory", &hmc_trajectory);
-    m.impl("flow_layer_fwd", &flow_layer_fwd);
-    m.impl("flow_layer_bwd_x", &flow_layer_bwd_x);
-    m.impl("flow_layer_bwd_w", &flow_layer_bwd_w);
-    m.impl("flow_layer_bwd", &flow_layer_bwd);
-    m.impl("flow_layer_rev", &flow_layer_rev);
-    m.impl("ft_action_force", &ft_action_force);
-    m.impl("fthmc_trajectory", &fthmc_trajectory);
-    m.impl("train_grad", &train_grad);
-    m.impl("ft_action_vjp", &ft_action_vjp);
-    m.impl("ft_force_vjp", &ft_force_vjp);
-    m.impl("train_force_grad", &train_force_grad);
-    m.impl("ft_trajectory_pb", &ft_trajectory_pb);
-    m.impl("hmc_trajectory_pb", &hmc_trajectory_pb);
-    m.impl("replica_swap", &replica_swap);
-    m.impl("local_update", &local_update);
-    m.impl("instanton_hit", &instanton_hit);
+#define FTHMC_IMPL(name, schema) m.impl(#name, &name);
+    FTHMC_OPERATORS(FTHMC_IMPL)
+#undef FTHMC_IMPL
 }

@@ -7,7 +7,10 @@ registered: a CPU tensor raises NotImplementedError from the dispatcher (there i
 The differentiable operators carry autograd formulas that call the hand-written backward kernels,
 so `loss.backward()` through `torch.ops.fthmc_hip.flow_layer_fwd` never builds an ATen graph.
 
-Two registrations of the SAME schemas (`BACKEND` says which one this process uses):
+Two registrations of the same schemas (`BACKEND` says which one this process uses).  The schema text of an operator stands once
+per side -- in csrc/torch_library.cpp's operator list and in the table `OPS` below -- and the Python registration is made from
+that text (custom_op(schema=...)), not inferred from annotations; tests/test_torch_boundary.py holds the two lists and both
+processes' `str(op._schema)` to each other:
   'compiled': `libfthmc_torch.so` -- a compiled TORCH_LIBRARY(fthmc_hip) (csrc/torch_library.cpp, built by csrc/Makefile next to
               libfthmc_hip.so): definitions and device implementations in C++, straight onto the C ABI; this module attaches
               the shape functions for tracing and the autograd formulas to them.  Used whenever the library is there.
@@ -18,7 +21,8 @@ Operators (reference call site each one replaces):
   wilson_action_charge(x, beta) -> (S, Q, plaq)      qed_helpers.py:94-116,177-186
   wilson_force(x, beta) -> F                         qed_helpers.py:265-272
   wilson_loops(x, Rmax, Tmax) -> W[B, Rmax, Tmax]    rectangular Wilson loops / Polyakov-loop correlators (ops.wilson_loops; no
-                   reference counterpart).  NOT differentiable: no autograd formula is registered, a backward through it raises
+                   reference counterpart).  NOT differentiable: no autograd formula is registered (a backward through such an
+                   operator raises under the Python registration; under the compiled one torch's fallback only warns)
   hmc_trajectory(x, v, u, beta, dt, nstep) -> (x_new, dH, acc)          qed_helpers.py:275-311
   flow_layer_fwd(x, w, mu, off, n_mix, act, hidden=None, kernel_size=3) -> (y, logJ)      layers.py:196-202,348-371
   flow_layer_bwd_x(x, gy, glogJ, w, mu, off, n_mix, act, hidden, kernel_size) -> gx        (autograd of the above)
@@ -52,7 +56,7 @@ integers: `n_mix` mixture components, `hidden` = hidden_sizes (None = the refere
 the C ABI's fthmc_arch_t of the call; a weight tensor is a plain tensor here and carries no shape of its own.
 """
 import os
-from typing import Optional, Sequence
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -82,262 +86,187 @@ def _arch(n_mix: int, hidden, kernel_size: int):
     return (tuple(int(h) for h in hidden) if hidden is not None else (8, 8), int(kernel_size), int(n_mix))
 
 
-if BACKEND == 'python':
-    @torch.library.custom_op('fthmc_hip::wilson_action_charge', mutates_args=(), device_types=_DEV)
-    def wilson_action_charge(x: torch.Tensor, beta: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        return ops.wilson_action_charge(x, beta)
+_INT = {v: k for k, v in _lib.INTEGRATORS.items()}
 
 
-    @torch.library.custom_op('fthmc_hip::wilson_force', mutates_args=(), device_types=_DEV)
-    def wilson_force(x: torch.Tensor, beta: float) -> torch.Tensor:
-        return ops.wilson_force(x, beta)
+def _integrator(code: int) -> str:
+    if code not in _INT:
+        raise FthmcError(f'integrator: expected 0, 1 or 2, got {code}')
+    return _INT[code]
 
 
-    @torch.library.custom_op('fthmc_hip::wilson_loops', mutates_args=(), device_types=_DEV)
-    def wilson_loops(x: torch.Tensor, Rmax: int, Tmax: int) -> torch.Tensor:
-        return ops.wilson_loops(x, Rmax, Tmax)
+# ---------------------------------------------------------------- the Python backend's implementations, over `ops`
+def _local_update(x, beta, beta_b, seeds, n_hb=1, n_or=0, nsweep=1, sweep0=0, classes=15):
+    return ops.local_update(x, beta if beta_b is None else beta_b, seeds, n_hb, n_or, nsweep, sweep0, classes)
 
 
-    @torch.library.custom_op('fthmc_hip::local_update', mutates_args=(), device_types=_DEV)
-    def local_update(x: torch.Tensor, beta: float, beta_b: Optional[torch.Tensor], seeds: Optional[torch.Tensor], n_hb: int = 1, n_or: int = 0,
-                     nsweep: int = 1, sweep0: int = 0, classes: int = 15) -> torch.Tensor:
-        return ops.local_update(x, beta if beta_b is None else beta_b, seeds, n_hb, n_or, nsweep, sweep0, classes)
+def _instanton_hit(x, beta, beta_b, seeds, n_hit=1, hit0=0):
+    return ops.instanton_hit(x, beta if beta_b is None else beta_b, seeds, n_hit, hit0)
 
 
-    @torch.library.custom_op('fthmc_hip::instanton_hit', mutates_args=(), device_types=_DEV)
-    def instanton_hit(x: torch.Tensor, beta: float, beta_b: Optional[torch.Tensor], seeds: Optional[torch.Tensor], n_hit: int = 1,
-                      hit0: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        return ops.instanton_hit(x, beta if beta_b is None else beta_b, seeds, n_hit, hit0)
+def _hmc_trajectory(x, v, u, beta, dt, nstep):
+    r = ops.hmc_trajectory(x, v, u, beta, dt, nstep)
+    return r['x_new'], r['dH'], r['acc']
 
 
-    @torch.library.custom_op('fthmc_hip::hmc_trajectory', mutates_args=(), device_types=_DEV)
-    def hmc_trajectory(x: torch.Tensor, v: torch.Tensor, u: torch.Tensor, beta: float, dt: float,
-                       nstep: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        r = ops.hmc_trajectory(x, v, u, beta, dt, nstep)
-        return r['x_new'], r['dH'], r['acc']
+def _flow_layer_fwd(x, w, mu, off, n_mix, act, hidden=None, kernel_size=3):
+    return ops.flow_layer_fwd(x, w, mu, off, _act(act), arch=_arch(n_mix, hidden, kernel_size))
 
 
-    @torch.library.custom_op('fthmc_hip::flow_layer_fwd', mutates_args=(), device_types=_DEV)
-    def flow_layer_fwd(x: torch.Tensor, w: torch.Tensor, mu: int, off: int, n_mix: int, act: int,
-                       hidden: Optional[Sequence[int]] = None, kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
-        return ops.flow_layer_fwd(x, w, mu, off, _act(act), arch=_arch(n_mix, hidden, kernel_size))
+def _layer_bwd(need_gw, pick):
+    """the three backward schemas over ops.flow_layer_bwd: `pick` chooses what one of them returns from (gx, gw)"""
+    def impl(x, gy, glogJ, w, mu, off, n_mix, act, hidden=None, kernel_size=3):
+        gx, gw = ops.flow_layer_bwd(x, w, gy, glogJ, mu, off, _act(act), need_gw=need_gw, arch=_arch(n_mix, hidden, kernel_size))
+        return pick(gx, gw)
+    return impl
 
 
-    @torch.library.custom_op('fthmc_hip::flow_layer_bwd_x', mutates_args=(), device_types=_DEV)
-    def flow_layer_bwd_x(x: torch.Tensor, gy: torch.Tensor, glogJ: torch.Tensor, w: torch.Tensor, mu: int, off: int,
-                         n_mix: int, act: int, hidden: Optional[Sequence[int]] = None, kernel_size: int = 3) -> torch.Tensor:
-        return ops.flow_layer_bwd(x, w, gy, glogJ, mu, off, _act(act), need_gw=False, arch=_arch(n_mix, hidden, kernel_size))[0]
+def _flow_layer_rev(y, w, mu, off, n_mix, act, tol, hidden=None, kernel_size=3):
+    return ops.flow_layer_rev(y, w, mu, off, _act(act), tol, arch=_arch(n_mix, hidden, kernel_size))
 
 
-    @torch.library.custom_op('fthmc_hip::flow_layer_bwd_w', mutates_args=(), device_types=_DEV)
-    def flow_layer_bwd_w(x: torch.Tensor, gy: torch.Tensor, glogJ: torch.Tensor, w: torch.Tensor, mu: int, off: int,
-                         n_mix: int, act: int, hidden: Optional[Sequence[int]] = None, kernel_size: int = 3) -> torch.Tensor:
-        return ops.flow_layer_bwd(x, w, gy, glogJ, mu, off, _act(act), need_gw=True, arch=_arch(n_mix, hidden, kernel_size))[1]
+def _ft_action_force(x, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
+    a = _arch(n_mix, hidden, kernel_size)
+    S, logdet, _, _ = ops.ft_action(x, w_all, n_layers, beta, _act(act), arch=a)
+    return S, logdet, ops.ft_force(x, w_all, n_layers, beta, _act(act), arch=a)
 
 
-    @torch.library.custom_op('fthmc_hip::flow_layer_bwd', mutates_args=(), device_types=_DEV)
-    def flow_layer_bwd(x: torch.Tensor, gy: torch.Tensor, glogJ: torch.Tensor, w: torch.Tensor, mu: int, off: int,
-                       n_mix: int, act: int, hidden: Optional[Sequence[int]] = None,
-                       kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
-        """Both gradients from one launch (what the autograd formula of flow_layer_fwd uses)."""
-        gx, gw = ops.flow_layer_bwd(x, w, gy, glogJ, mu, off, _act(act), need_gw=True, arch=_arch(n_mix, hidden, kernel_size))
-        return gx, gw
+def _fthmc_trajectory(x, v, u, w_all, n_layers, beta, dt, nstep, mode, act, n_mix=2, hidden=None, kernel_size=3):
+    if mode not in _MODE:
+        raise FthmcError(f'mode: expected 0 (md) or 1 (literal), got {mode}')
+    r = ops.ft_trajectory(x, v, u, w_all, n_layers, beta, dt, nstep, _act(act), _MODE[mode], arch=_arch(n_mix, hidden, kernel_size))
+    return r['x_new'], r['dH'], r['acc'], r['plaq'], r['Q']
 
 
-    @torch.library.custom_op('fthmc_hip::flow_layer_rev', mutates_args=(), device_types=_DEV)
-    def flow_layer_rev(y: torch.Tensor, w: torch.Tensor, mu: int, off: int, n_mix: int, act: int, tol: float,
-                       hidden: Optional[Sequence[int]] = None, kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
-        return ops.flow_layer_rev(y, w, mu, off, _act(act), tol, arch=_arch(n_mix, hidden, kernel_size))
+def _train_grad(xi, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
+    r = ops.train_grad(xi, w_all, n_layers, beta, _act(act), arch=_arch(n_mix, hidden, kernel_size))
+    return r['x'], r['logq'], r['logp'], r['gw']
 
 
-    @torch.library.custom_op('fthmc_hip::ft_action_force', mutates_args=(), device_types=_DEV)
-    def ft_action_force(x: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta: float, act: int, n_mix: int = 2,
-                        hidden: Optional[Sequence[int]] = None,
-                        kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        a = _arch(n_mix, hidden, kernel_size)
-        S, logdet, _, _ = ops.ft_action(x, w_all, n_layers, beta, _act(act), arch=a)
-        return S, logdet, ops.ft_force(x, w_all, n_layers, beta, _act(act), arch=a)
+def _ft_action_vjp(x, w_all, n_layers, beta, act, gS, glogdet=None, n_mix=2, hidden=None, kernel_size=3):
+    gx, gw = ops.ft_action_vjp(x, w_all, n_layers, beta, gS, glogdet, _act(act), arch=_arch(n_mix, hidden, kernel_size))
+    return gx, gw
 
 
-    @torch.library.custom_op('fthmc_hip::fthmc_trajectory', mutates_args=(), device_types=_DEV)
-    def fthmc_trajectory(x: torch.Tensor, v: torch.Tensor, u: torch.Tensor, w_all: torch.Tensor, n_layers: int,
-                         beta: float, dt: float, nstep: int, mode: int, act: int, n_mix: int = 2,
-                         hidden: Optional[Sequence[int]] = None,
-                         kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-        if mode not in _MODE:
-            raise FthmcError(f'mode: expected 0 (md) or 1 (literal), got {mode}')
-        r = ops.ft_trajectory(x, v, u, w_all, n_layers, beta, dt, nstep, _act(act), _MODE[mode], arch=_arch(n_mix, hidden, kernel_size))
-        return r['x_new'], r['dH'], r['acc'], r['plaq'], r['Q']
+def _ft_force_vjp(x, w_all, n_layers, beta, act, g, n_mix=2, hidden=None, kernel_size=3):
+    gx, gw = ops.ft_force_vjp(x, w_all, n_layers, beta, g, _act(act), arch=_arch(n_mix, hidden, kernel_size))
+    return gx, gw
 
 
-    @torch.library.custom_op('fthmc_hip::train_grad', mutates_args=(), device_types=_DEV)
-    def train_grad(xi: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta: float, act: int, n_mix: int = 2,
-                   hidden: Optional[Sequence[int]] = None,
-                   kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-        r = ops.train_grad(xi, w_all, n_layers, beta, _act(act), arch=_arch(n_mix, hidden, kernel_size))
-        return r['x'], r['logq'], r['logp'], r['gw']
+def _train_force_grad(x, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
+    r = ops.train_force_grad(x, w_all, n_layers, beta, _act(act), arch=_arch(n_mix, hidden, kernel_size))
+    gw = r['gw'] if r['gw'] is not None else x.new_zeros(w_all.numel())
+    return r['F'], r['force_sq'], gw
 
 
-    @torch.library.custom_op('fthmc_hip::ft_action_vjp', mutates_args=(), device_types=_DEV)
-    def ft_action_vjp(x: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta: float, act: int, gS: torch.Tensor,
-                      glogdet: Optional[torch.Tensor] = None, n_mix: int = 2, hidden: Optional[Sequence[int]] = None,
-                      kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
-        gx, gw = ops.ft_action_vjp(x, w_all, n_layers, beta, gS, glogdet, _act(act), arch=_arch(n_mix, hidden, kernel_size))
-        return gx, gw
+def _ft_trajectory_pb(x, v, u, w_all, n_layers, beta_b, dt, nstep, integrator, act, state_in=None, n_mix=2, hidden=None, kernel_size=3):
+    r = ops.ft_trajectory(x, v, u, w_all, n_layers, beta_b.contiguous(), dt, nstep, _act(act), 'md', state_in=state_in,
+                          arch=_arch(n_mix, hidden, kernel_size), integrator=_integrator(integrator))
+    return r['x_new'], r['dH'], r['acc'], r['plaq'], r['Q'], r['state']
 
 
-    @torch.library.custom_op('fthmc_hip::ft_force_vjp', mutates_args=(), device_types=_DEV)
-    def ft_force_vjp(x: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta: float, act: int, g: torch.Tensor,
-                     n_mix: int = 2, hidden: Optional[Sequence[int]] = None,
-                     kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
-        gx, gw = ops.ft_force_vjp(x, w_all, n_layers, beta, g, _act(act), arch=_arch(n_mix, hidden, kernel_size))
-        return gx, gw
+def _hmc_trajectory_pb(x, v, u, beta_b, dt, nstep, integrator=0):
+    r = ops.hmc_trajectory(x, v, u, beta_b.contiguous(), dt, nstep, integrator=_integrator(integrator))
+    return r['x_new'], r['dH'], r['acc']
 
 
-    @torch.library.custom_op('fthmc_hip::train_force_grad', mutates_args=(), device_types=_DEV)
-    def train_force_grad(x: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta: float, act: int,
-                         n_mix: int = 2, hidden: Optional[Sequence[int]] = None,
-                         kernel_size: int = 3) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        r = ops.train_force_grad(x, w_all, n_layers, beta, _act(act), arch=_arch(n_mix, hidden, kernel_size))
-        gw = r['gw'] if r['gw'] is not None else x.new_zeros(w_all.numel())
-        return r['F'], r['force_sq'], gw
+def _replica_swap(betas, C, u, beta_b, rung, chain_of, parity):
+    r = ops.replica_swap(betas, C, u, beta_b, rung, chain_of, parity)
+    return r['swap_acc'], r['d']
 
 
-    _INT = {v: k for k, v in _lib.INTEGRATORS.items()}
+# ---------------------------------------------------------------- the operator table
+class _Op(NamedTuple):
+    name: str
+    schema: str                 # '(arguments) -> returns': character for character the text of csrc/torch_library.cpp's list
+    fake: Callable              # the outputs' shapes from the call's arguments (tracing, meta tensors)
+    impl: Callable              # the Python backend's implementation
+    mutates: tuple = ()         # the arguments updated in place (the schema's alias annotations say the same)
 
 
-    @torch.library.custom_op('fthmc_hip::ft_trajectory_pb', mutates_args=(), device_types=_DEV)
-    def ft_trajectory_pb(x: torch.Tensor, v: torch.Tensor, u: torch.Tensor, w_all: torch.Tensor, n_layers: int, beta_b: torch.Tensor,
-                         dt: float, nstep: int, integrator: int, act: int, state_in: Optional[torch.Tensor] = None, n_mix: int = 2,
-                         hidden: Optional[Sequence[int]] = None, kernel_size: int = 3
-                         ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-        if integrator not in _INT:
-            raise FthmcError(f'integrator: expected 0, 1 or 2, got {integrator}')
-        r = ops.ft_trajectory(x, v, u, w_all, n_layers, beta_b.contiguous(), dt, nstep, _act(act), 'md', state_in=state_in,
-                              arch=_arch(n_mix, hidden, kernel_size), integrator=_INT[integrator])
-        return r['x_new'], r['dH'], r['acc'], r['plaq'], r['Q'], r['state']
+_like = torch.empty_like
 
 
-    @torch.library.custom_op('fthmc_hip::hmc_trajectory_pb', mutates_args=(), device_types=_DEV)
-    def hmc_trajectory_pb(x: torch.Tensor, v: torch.Tensor, u: torch.Tensor, beta_b: torch.Tensor, dt: float, nstep: int,
-                          integrator: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        if integrator not in _INT:
-            raise FthmcError(f'integrator: expected 0, 1 or 2, got {integrator}')
-        r = ops.hmc_trajectory(x, v, u, beta_b.contiguous(), dt, nstep, integrator=_INT[integrator])
-        return r['x_new'], r['dH'], r['acc']
-
-
-    @torch.library.custom_op('fthmc_hip::replica_swap', mutates_args=('beta_b', 'rung', 'chain_of'), device_types=_DEV)
-    def replica_swap(betas: torch.Tensor, C: torch.Tensor, u: torch.Tensor, beta_b: torch.Tensor, rung: torch.Tensor,
-                     chain_of: torch.Tensor, parity: int) -> tuple[torch.Tensor, torch.Tensor]:
-        r = ops.replica_swap(betas, C, u, beta_b, rung, chain_of, parity)
-        return r['swap_acc'], r['d']
-
-
-# ---------------------------------------------------------------- shapes for tracing (meta tensors)
 def _b(x):
     return x.new_empty(x.shape[0])
 
 
-@torch.library.register_fake('fthmc_hip::wilson_action_charge')
-def _(x, beta):
-    return _b(x), _b(x), _b(x)
-
-
-@torch.library.register_fake('fthmc_hip::wilson_force')
-def _(x, beta):
-    return torch.empty_like(x)
-
-
-@torch.library.register_fake('fthmc_hip::wilson_loops')
-def _(x, Rmax, Tmax):
-    return x.new_empty(x.shape[0], Rmax, Tmax)
-
-
-@torch.library.register_fake('fthmc_hip::local_update')
-def _(x, beta, beta_b, seeds, n_hb=1, n_or=0, nsweep=1, sweep0=0, classes=15):
-    return torch.empty_like(x)
-
-
-@torch.library.register_fake('fthmc_hip::instanton_hit')
-def _(x, beta, beta_b, seeds, n_hit=1, hit0=0):
-    return torch.empty_like(x), x.new_empty(x.shape[0], dtype=torch.int32), x.new_empty(x.shape[0], dtype=torch.int32)
-
-
-@torch.library.register_fake('fthmc_hip::hmc_trajectory')
-def _(x, v, u, beta, dt, nstep):
-    return torch.empty_like(x), _b(x), _b(x)
-
-
-@torch.library.register_fake('fthmc_hip::flow_layer_fwd')
-def _(x, w, mu, off, n_mix, act, hidden=None, kernel_size=3):
-    return torch.empty_like(x), _b(x)
-
-
-@torch.library.register_fake('fthmc_hip::flow_layer_bwd_x')
-def _(x, gy, glogJ, w, mu, off, n_mix, act, hidden=None, kernel_size=3):
-    return torch.empty_like(x)
-
-
-@torch.library.register_fake('fthmc_hip::flow_layer_bwd_w')
-def _(x, gy, glogJ, w, mu, off, n_mix, act, hidden=None, kernel_size=3):
+def _gw(x, w):
     return x.new_empty(w.numel())
 
 
-@torch.library.register_fake('fthmc_hip::flow_layer_bwd')
-def _(x, gy, glogJ, w, mu, off, n_mix, act, hidden=None, kernel_size=3):
-    return torch.empty_like(x), x.new_empty(w.numel())
+def _swap_shape(betas, beta_b):
+    return beta_b.new_empty(beta_b.numel() // betas.numel(), betas.numel() - 1)
 
 
-@torch.library.register_fake('fthmc_hip::flow_layer_rev')
-def _(y, w, mu, off, n_mix, act, tol, hidden=None, kernel_size=3):
-    return torch.empty_like(y), _b(y)
+OPS = (
+    _Op('wilson_action_charge', '(Tensor x, float beta) -> (Tensor, Tensor, Tensor)',
+        lambda x, *_: (_b(x), _b(x), _b(x)), ops.wilson_action_charge),
+    _Op('wilson_force', '(Tensor x, float beta) -> Tensor',
+        lambda x, *_: _like(x), ops.wilson_force),
+    _Op('hmc_trajectory', '(Tensor x, Tensor v, Tensor u, float beta, float dt, int nstep) -> (Tensor, Tensor, Tensor)',
+        lambda x, *_: (_like(x), _b(x), _b(x)), _hmc_trajectory),
+    _Op('flow_layer_fwd', '(Tensor x, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)',
+        lambda x, *_: (_like(x), _b(x)), _flow_layer_fwd),
+    _Op('flow_layer_bwd_x', '(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, '
+        'int kernel_size=3) -> Tensor',
+        lambda x, *_: _like(x), _layer_bwd(False, lambda gx, gw: gx)),
+    _Op('flow_layer_bwd_w', '(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, '
+        'int kernel_size=3) -> Tensor',
+        lambda x, gy, glogJ, w, *_: _gw(x, w), _layer_bwd(True, lambda gx, gw: gw)),
+    # both gradients from one launch (what the autograd formula of flow_layer_fwd uses)
+    _Op('flow_layer_bwd', '(Tensor x, Tensor gy, Tensor glogJ, Tensor w, int mu, int off, int n_mix, int act, int[]? hidden=None, '
+        'int kernel_size=3) -> (Tensor, Tensor)',
+        lambda x, gy, glogJ, w, *_: (_like(x), _gw(x, w)), _layer_bwd(True, lambda gx, gw: (gx, gw))),
+    _Op('flow_layer_rev', '(Tensor y, Tensor w, int mu, int off, int n_mix, int act, float tol, int[]? hidden=None, int kernel_size=3) '
+        '-> (Tensor, Tensor)',
+        lambda y, *_: (_like(y), _b(y)), _flow_layer_rev),
+    _Op('ft_action_force', '(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) '
+        '-> (Tensor, Tensor, Tensor)',
+        lambda x, *_: (_b(x), _b(x), _like(x)), _ft_action_force),
+    _Op('fthmc_trajectory', '(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, float beta, float dt, int nstep, int mode, int act, '
+        'int n_mix=2, int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor, Tensor, Tensor, Tensor)',
+        lambda x, *_: (_like(x), _b(x), _b(x), _b(x), _b(x)), _fthmc_trajectory),
+    _Op('train_grad', '(Tensor xi, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) '
+        '-> (Tensor, Tensor, Tensor, Tensor)',
+        lambda xi, w_all, *_: (_like(xi), _b(xi), _b(xi), _gw(xi, w_all)), _train_grad),
+    _Op('ft_action_vjp', '(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor gS, Tensor? glogdet=None, int n_mix=2, '
+        'int[]? hidden=None, int kernel_size=3) -> (Tensor, Tensor)',
+        lambda x, w_all, *_: (_like(x), _gw(x, w_all)), _ft_action_vjp),
+    _Op('ft_force_vjp', '(Tensor x, Tensor w_all, int n_layers, float beta, int act, Tensor g, int n_mix=2, int[]? hidden=None, '
+        'int kernel_size=3) -> (Tensor, Tensor)',
+        lambda x, w_all, *_: (_like(x), _gw(x, w_all)), _ft_force_vjp),
+    _Op('train_force_grad', '(Tensor x, Tensor w_all, int n_layers, float beta, int act, int n_mix=2, int[]? hidden=None, int kernel_size=3) '
+        '-> (Tensor, Tensor, Tensor)',
+        lambda x, w_all, *_: (_like(x), _b(x), _gw(x, w_all)), _train_force_grad),
+    _Op('ft_trajectory_pb', '(Tensor x, Tensor v, Tensor u, Tensor w_all, int n_layers, Tensor beta_b, float dt, int nstep, int integrator, '
+        'int act, Tensor? state_in=None, int n_mix=2, int[]? hidden=None, int kernel_size=3) '
+        '-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)',
+        lambda x, *_: (_like(x), _b(x), _b(x), _b(x), _b(x), x.new_empty(3, x.shape[0])), _ft_trajectory_pb),
+    _Op('hmc_trajectory_pb', '(Tensor x, Tensor v, Tensor u, Tensor beta_b, float dt, int nstep, int integrator=0) -> (Tensor, Tensor, Tensor)',
+        lambda x, *_: (_like(x), _b(x), _b(x)), _hmc_trajectory_pb),
+    _Op('replica_swap', '(Tensor betas, Tensor C, Tensor u, Tensor(a!) beta_b, Tensor(b!) rung, Tensor(c!) chain_of, int parity) '
+        '-> (Tensor, Tensor)',
+        lambda betas, C, u, beta_b, *_: (_swap_shape(betas, beta_b), _swap_shape(betas, beta_b)), _replica_swap,
+        mutates=('beta_b', 'rung', 'chain_of')),
+    _Op('wilson_loops', '(Tensor x, int Rmax, int Tmax) -> Tensor',
+        lambda x, Rmax, Tmax: x.new_empty(x.shape[0], Rmax, Tmax), ops.wilson_loops),
+    _Op('local_update', '(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hb=1, int n_or=0, int nsweep=1, int sweep0=0, '
+        'int classes=15) -> Tensor',
+        lambda x, *_: _like(x), _local_update),
+    _Op('instanton_hit', '(Tensor x, float beta, Tensor? beta_b, Tensor? seeds, int n_hit=1, int hit0=0) -> (Tensor, Tensor, Tensor)',
+        lambda x, *_: (_like(x), x.new_empty(x.shape[0], dtype=torch.int32), x.new_empty(x.shape[0], dtype=torch.int32)), _instanton_hit),
+)
 
-
-@torch.library.register_fake('fthmc_hip::ft_action_force')
-def _(x, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
-    return _b(x), _b(x), torch.empty_like(x)
-
-
-@torch.library.register_fake('fthmc_hip::fthmc_trajectory')
-def _(x, v, u, w_all, n_layers, beta, dt, nstep, mode, act, n_mix=2, hidden=None, kernel_size=3):
-    return torch.empty_like(x), _b(x), _b(x), _b(x), _b(x)
-
-
-@torch.library.register_fake('fthmc_hip::train_grad')
-def _(xi, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
-    return torch.empty_like(xi), _b(xi), _b(xi), xi.new_empty(w_all.numel())
-
-
-@torch.library.register_fake('fthmc_hip::ft_action_vjp')
-def _(x, w_all, n_layers, beta, act, gS, glogdet=None, n_mix=2, hidden=None, kernel_size=3):
-    return torch.empty_like(x), x.new_empty(w_all.numel())
-
-
-@torch.library.register_fake('fthmc_hip::ft_force_vjp')
-def _(x, w_all, n_layers, beta, act, g, n_mix=2, hidden=None, kernel_size=3):
-    return torch.empty_like(x), x.new_empty(w_all.numel())
-
-
-@torch.library.register_fake('fthmc_hip::train_force_grad')
-def _(x, w_all, n_layers, beta, act, n_mix=2, hidden=None, kernel_size=3):
-    return torch.empty_like(x), _b(x), x.new_empty(w_all.numel())
-
-
-@torch.library.register_fake('fthmc_hip::ft_trajectory_pb')
-def _(x, v, u, w_all, n_layers, beta_b, dt, nstep, integrator, act, state_in=None, n_mix=2, hidden=None, kernel_size=3):
-    return torch.empty_like(x), _b(x), _b(x), _b(x), _b(x), x.new_empty(3, x.shape[0])
-
-
-@torch.library.register_fake('fthmc_hip::hmc_trajectory_pb')
-def _(x, v, u, beta_b, dt, nstep, integrator=0):
-    return torch.empty_like(x), _b(x), _b(x)
-
-
-@torch.library.register_fake('fthmc_hip::replica_swap')
-def _(betas, C, u, beta_b, rung, chain_of, parity):
-    M, K = beta_b.numel() // betas.numel(), betas.numel()
-    return beta_b.new_empty(M, K - 1), beta_b.new_empty(M, K - 1)
+# the module's names are the dispatcher's operators themselves: the compiled library's, or defined here with its schema text
+for _op in OPS:
+    if BACKEND == 'python':
+        globals()[_op.name] = torch.library.custom_op('fthmc_hip::' + _op.name, _op.impl, mutates_args=_op.mutates, device_types=_DEV,
+                                                      schema=_op.schema)
+    else:
+        globals()[_op.name] = getattr(torch.ops.fthmc_hip, _op.name)
+    torch.library.register_fake('fthmc_hip::' + _op.name, _op.fake)
+__all__ = [_op.name for _op in OPS]
 
 
 # ---------------------------------------------------------------- autograd formulas
@@ -406,15 +335,3 @@ def _action_force_backward(ctx, gS, glogdet, gF):
 
 
 torch.library.register_autograd('fthmc_hip::ft_action_force', _action_force_backward, setup_context=_action_force_setup)
-
-if BACKEND == 'compiled':                        # the module's names are the dispatcher's operators themselves
-    for _n in ('wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x', 'flow_layer_bwd_w',
-               'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad', 'ft_action_vjp',
-               'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap', 'wilson_loops', 'local_update',
-               'instanton_hit'):
-        globals()[_n] = getattr(torch.ops.fthmc_hip, _n)
-
-__all__ = ['wilson_action_charge', 'wilson_force', 'hmc_trajectory', 'flow_layer_fwd', 'flow_layer_bwd_x',
-           'flow_layer_bwd_w', 'flow_layer_bwd', 'flow_layer_rev', 'ft_action_force', 'fthmc_trajectory', 'train_grad',
-           'ft_action_vjp', 'ft_force_vjp', 'train_force_grad', 'ft_trajectory_pb', 'hmc_trajectory_pb', 'replica_swap', 'wilson_loops',
-           'local_update', 'instanton_hit']
