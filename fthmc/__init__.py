@@ -61,3 +61,9 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 
 if not any(isinstance(f, _AliasFinder) for f in sys.meta_path):
     sys.meta_path.insert(0, _AliasFinder())
+
+
+def __getattr__(name):            # what fthmc_amd exports itself (MetaPotential, run_meta), under this name too
+    if name in fthmc_amd.__all__:
+        return getattr(fthmc_amd, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -120,7 +120,15 @@ SIGNATURES['fthmc_local_update'] = [_D, c_int, c_int, c_double, _D, _D, c_int, c
 # instanton hits: x, B, L, beta, beta_b, seeds, n_hit, hit0, path, x_out, k_out, nacc_out, cs_out, ws, ws_bytes, stream
 SIGNATURES['fthmc_instanton_ws_bytes'] = [c_int, c_int, c_int]
 SIGNATURES['fthmc_instanton_hit'] = [_D, c_int, c_int, c_double, _D, _D, c_int, ctypes.c_int64, c_int, _D, _D, _D, _D, _P, c_size_t, _P]
-_RESTYPE = {'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
+# metadynamics HMC: the table travels as (vtab, G, nb, qmax, wall)
+#   trajectory: x, v, u, B, L, beta, dt, nstep, integrator, <table>, path, x_new, dH, acc, H0, H1, qm_out, vb_out, ws, ws_bytes, stream
+_MT = [_D, c_int, c_int, c_double, c_double]
+SIGNATURES['fthmc_meta_ws_bytes'] = [c_int, c_int, c_int]
+SIGNATURES['fthmc_meta_trajectory'] = [_D, _D, _D, c_int, c_int, c_double, c_double, c_int, c_int] + _MT + [c_int, _D, _D, _D, _D, _D, _D, _D, _P, c_size_t, _P]
+SIGNATURES['fthmc_meta_deposit'] = [_D, c_int, c_int, c_int, c_double, c_double, _D, _P]      # qm, B, G, nb, qmax, w, vtab, stream
+SIGNATURES['fthmc_meta_force'] = [_D, c_int, c_int, c_double] + _MT + [_D, _P]                # x, B, L, beta, <table>, F, stream
+SIGNATURES['fthmc_meta_action'] = [_D, c_int, c_int, c_double] + _MT + [_D, _D, _D, _P]       # ..., S, qm, vb, stream
+_RESTYPE = {'fthmc_meta_ws_bytes': c_size_t, 'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None
 

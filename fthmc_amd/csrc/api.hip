@@ -305,6 +305,68 @@ int hmc_trajectory_call(const double* x, const double* v, const double* u, int B
     return launch_metropolis(x, xo, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
 }
 
+// ---------------------------------------------------------------- metadynamics HMC (meta.hip; no reference counterpart)
+// what every fthmc_meta_* call refuses about the table
+inline bool bad_meta_table(const double* vtab, int B, int G, int nb, double qmax) {
+    return !vtab || G < 1 || B % G != 0 || nb < 2 || nb > 65536 || !isfinite(qmax) || !(qmax > 0.0);
+}
+inline bool bad_meta_weight(double w) { return !isfinite(w) || !(w >= 0.0); }      // the wall's stiffness, a hill's height
+
+// the sequenced path launches the plain kernels' shapes (launch_kick_from_gp, launch_shift_from_gp, k_meta_gp: the chain on grid y)
+constexpr int META_SEQ_MAX_B = 65535;
+
+// The workspace of the sequenced path: a first-order layout without layers, behind it sums[B][2] and the (Q_m, V) pairs of the
+// two ends and of the selected one, [2][B] each
+struct MWS { WS W; double *sums, *qv_old, *qv_new, *qv_sel; size_t total; };
+MWS meta_layout(Carver& c, int B, int L) {
+    MWS m{};
+    m.W = ws_layout(flow_arch_default(), c, B, L, 0);
+    if (m.W.total == 0) return m;
+    m.sums = c.take((size_t)2 * B);
+    m.qv_old = c.take((size_t)2 * B); m.qv_new = c.take((size_t)2 * B); m.qv_sel = c.take((size_t)2 * B);
+    m.total = c.total();
+    return m;
+}
+
+// The biased trajectory, sequenced: hmc_trajectory_call's H0, MD, H1, Metropolis with ft_md_ws' stages, the force of a stage from
+// the chain sums (launch_meta_sums) and the biased plaquette gradient (launch_meta_gp) in place of launch_wilson_gp, and V(Q_m)
+// added to either energy.  Any L; x_new may be x.
+int meta_trajectory_seq(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sc, const MetaTab& T,
+                        double* x_new, double* dH, double* acc, double* H0, double* H1, double* qm_out, double* vb_out,
+                        const MWS& M, hipStream_t s) {
+    const WS& W = M.W;
+    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
+    auto energy = [&](const double* xf, const double* vf, double* h, double* qv) {      // h = S_W(xf) + K(vf) / 2 + V(Q_m(xf))
+        FT_TRY(launch_action_charge(xf, B, L, beta, S, nullptr, nullptr, s));
+        FT_TRY(launch_kinetic(vf, B, L, K, s));
+        FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h, B, s));
+        FT_TRY(launch_meta_sums(xf, B, L, M.sums, s));
+        return launch_meta_energy(M.sums, B, T, h, qv, s);
+    };
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    FT_TRY(energy(x, v, h0, M.qv_old));
+    FT_TRY(launch_axpy_copy(x, v, sc.b0, W.xa, W.va, W.n2, s));
+    const double* xe = W.xa;                                               // where this stage's force is evaluated
+    for (int it = 0; it < sc.n; ++it) {
+        const SchedStage st = sc.stage(it);
+        FT_TRY(launch_meta_sums(xe, B, L, M.sums, s));
+        FT_TRY(launch_meta_gp(xe, B, L, beta, M.sums, T, W.gp, s));
+        if (st.kind == FT_STAGE_SHIFT) {
+            FT_TRY(launch_shift_from_gp(W.gp, W.xa, W.xb, B, L, st.a, s));
+            xe = W.xb;
+        } else {                                                           // the last kick leaves the regularized end point in W.xb
+            FT_TRY(launch_kick_from_gp(W.gp, W.va, W.xa, nullptr, B, L, st.a, st.b, s, it == sc.n - 1 ? W.xb : nullptr));
+            xe = W.xa;
+        }
+    }
+    FT_TRY(energy(W.xb, W.va, h1, M.qv_new));
+    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, M.qv_old, M.qv_new, M.qv_sel, 2, s));
+    if (qm_out && hipMemcpyAsync(qm_out, M.qv_sel, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    if (vb_out && hipMemcpyAsync(vb_out, M.qv_sel + B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    return FTHMC_OK;
+}
+
 // ---------------------------------------------------------------- per-chain beta and replica exchange (no reference counterpart)
 // The beta-free triple (log det J, C = sum cos P, Q) of x into `trip` -- carried over (state_in) or evaluated -- and S_eff of it
 // at beta_b into `seff`: the general branch's eval_action + launch_lincomb with beta read per chain
@@ -906,6 +968,47 @@ int fthmc_instanton_hit(const double* x, int B, int L, double beta, const double
     }
     return launch_instanton(x, B, L, beta, beta_b, seeds, n_hit, (uint32_t)hit0, split, x_out, k_out, nacc_out, cs_out, part, kbuf,
                             ft_stream(stream));
+}
+
+// Metadynamics HMC (meta.hip): the argument checks, the choice of the path and the workspace of the sequenced one
+size_t fthmc_meta_ws_bytes(int B, int L, int path) {
+    if (bad_shape(B, L) || path < 0 || path > 2 || path == 1) return 0;             // the one-launch path needs none
+    if (B > META_SEQ_MAX_B) return 0;                                               // the sequenced path does not serve it
+    Carver c;
+    return meta_layout(c, B, L).total * sizeof(double);
+}
+int fthmc_meta_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta, double dt, int nstep, int integrator,
+                          const double* vtab, int G, int nb, double qmax, double wall, int path, double* x_new, double* dH, double* acc,
+                          double* H0, double* H1, double* qm_out, double* vb_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1 || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall) ||
+        path < 0 || path > 2)
+        return FTHMC_ERR_ARG;
+    if (path == 1 && (L > 64 || x_new == x)) return FTHMC_ERR_ARG;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    Ctx C; FT_TRY(open_call(nullptr, stream, &C));
+    const MetaTab T{vtab, B / G, nb, qmax, wall};
+    if (path == 1 || (path == 0 && L <= 64 && C.mfma && x_new != x))
+        return launch_meta_trajectory(x, v, u, B, L, beta, sc, T, x_new, dH, acc, H0, H1, qm_out, vb_out, C.s);
+    if (B > META_SEQ_MAX_B) return FTHMC_ERR_UNSUPPORTED;
+    Carver c(ws, ws_bytes);
+    const MWS M = meta_layout(c, B, L);
+    FT_TRY(check_ws(M.total, ws, ws_bytes));
+    return meta_trajectory_seq(x, v, u, B, L, beta, sc, T, x_new, dH, acc, H0, H1, qm_out, vb_out, M, C.s);
+}
+int fthmc_meta_deposit(const double* qm, int B, int G, int nb, double qmax, double w, double* vtab, void* stream) {
+    if (!qm || B <= 0 || B > FTHMC_MAX_B || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(w)) return FTHMC_ERR_ARG;
+    return launch_meta_deposit(qm, B, G, nb, qmax, w, vtab, ft_stream(stream));
+}
+int fthmc_meta_force(const double* x, int B, int L, double beta, const double* vtab, int G, int nb, double qmax, double wall, double* F,
+                     void* stream) {
+    if (!x || !F || bad_shape(B, L) || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall)) return FTHMC_ERR_ARG;
+    return launch_meta_force(x, B, L, beta, MetaTab{vtab, B / G, nb, qmax, wall}, F, ft_stream(stream));
+}
+int fthmc_meta_action(const double* x, int B, int L, double beta, const double* vtab, int G, int nb, double qmax, double wall, double* S,
+                      double* qm, double* vb, void* stream) {
+    if (!x || bad_shape(B, L) || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall)) return FTHMC_ERR_ARG;
+    return launch_meta_action(x, B, L, beta, MetaTab{vtab, B / G, nb, qmax, wall}, S, qm, vb, ft_stream(stream));
 }
 
 int fthmc_ft_trajectory(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,

@@ -125,6 +125,22 @@ inline size_t instanton_part_doubles(int B, int L) { return (size_t)B * (size_t)
 int launch_instanton(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hit, uint32_t hit0,
                      bool split, double* x_out, int32_t* k_out, int32_t* nacc_out, double* cs_out, double* part, int32_t* kbuf, hipStream_t s);
 
+// ---- meta.hip: metadynamics HMC, plain HMC under a bias potential in the continuous charge (fthmc_meta_*)
+// the table of a call: v[G][nb] on the nodes -qmax + i 2 qmax / (nb - 1), chain b reads row b / cpr (cpr = B / G), the wall outside
+struct MetaTab { const double* v; int cpr, nb; double qmax, wall; };
+// the whole biased trajectory in one launch (L <= 64): launch_hmc_trajectory_sched's twin; qm_out, vb_out: of the field x_new holds
+int launch_meta_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sched, const MetaTab& T,
+                           double* x_new, double* dH, double* acc, double* H0, double* H1, double* qm_out, double* vb_out, hipStream_t s);
+// the sequenced path: sums[B][2] = (sum sin P, sum cos P); gP = beta sin P + c_b cos P; H[b] += V(Q_m), qv[2][B] = (Q_m, V)
+int launch_meta_sums(const double* x, int B, int L, double* sums, hipStream_t s);
+int launch_meta_gp(const double* x, int B, int L, double beta, const double* sums, const MetaTab& T, double* gp, hipStream_t s);
+int launch_meta_energy(const double* sums, int B, const MetaTab& T, double* H, double* qv, hipStream_t s);
+// the bias on its own
+int launch_meta_force(const double* x, int B, int L, double beta, const MetaTab& T, double* F, hipStream_t s);
+int launch_meta_action(const double* x, int B, int L, double beta, const MetaTab& T, double* S, double* qm, double* vb, hipStream_t s);
+// one hill of height w per walker at qm[b], added to the table in chain order (in place)
+int launch_meta_deposit(const double* qm, int B, int G, int nb, double qmax, double w, double* vtab, hipStream_t s);
+
 // ---- rng.hip
 int launch_random_momenta(const int64_t* seeds, int B, int n, double* v, double* u, hipStream_t s);
 int launch_random_uniform(const int64_t* seeds, int B, int n, double lo, double hi, double* out, hipStream_t s);

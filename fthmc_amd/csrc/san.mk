@@ -79,3 +79,11 @@ san_layout: $(SANOUT)
 	  -c ../../tests/hip/layout_walk.cpp -o $(SANLAYOUT).o
 	$(ROCM)/lib/llvm/bin/clang++ -fsanitize=address,undefined -shared-libsan $(SANLAYOUT).o -o $(SANLAYOUT) \
 	  -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
+
+# The metadynamics entry points (fthmc_meta_ws_bytes, fthmc_meta_trajectory, fthmc_meta_deposit, fthmc_meta_force, fthmc_meta_action):
+# tests/hip/meta_walk.cpp in the same way, run by tests/test_meta.py
+SANMETA ?= $(SANDIR)/meta_walk
+san_meta: $(SANOUT)
+	mkdir -p $(dir $(SANMETA))
+	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
+	  ../../tests/hip/meta_walk.cpp -o $(SANMETA) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))

@@ -1,0 +1,174 @@
+"""Metadynamics HMC of 2D U(1) (beyond the reference, which samples the unbiased action only): HMC under a history-dependent bias
+potential V(Q_m) in the continuous charge Q_m = sum sin P / 2 pi (csrc/meta.hip).
+
+While the potential is built, every trajectory is followed by a deposit: each walker adds a hill of height w to the table at its
+Q_m, so the barriers between the topological sectors fill up.  Under the frozen table the chain samples exp(-S - V(Q_m)) and
+    <O> = sum O e^{V(Q_m)} / sum e^{V(Q_m)}          (utils.observables.reweighted_mean)
+is the unbiased expectation value.  Laio & Parrinello 2002; Laio, Martinelli & Sanfilippo 2016 for topology; Eichhorn, Hoelbling
+et al. 2021-23 compare it in 2D U(1) with the instanton update (csrc/topo.hip) and tempering (tempering.py) this tree also has."""
+from __future__ import annotations
+
+import math
+import os
+import time
+from typing import Optional
+
+import numpy as np
+
+from .config import DTYPE, Param
+
+
+class MetaPotential:
+    """The bias potential: a table V[groups][nb] on the nodes q_i = -qmax + i delta, delta = 2 qmax / (nb - 1), linear between the
+    nodes, and outside them V_edge + wall d^2 / 2, d = |q| - qmax.  `groups` rows: chain b of a batch of B reads row
+    b // (B // groups) -- 1: all walkers share one potential, B: one per chain.
+    `table` is the device tensor the kernels read and ops.meta_deposit updates in place (made on first use); value / slope evaluate
+    the same definitions on the host in numpy (float64)."""
+
+    def __init__(self, nb: int, qmax: float, wall: float, groups: int = 1):
+        nb, groups, qmax, wall = int(nb), int(groups), float(qmax), float(wall)
+        if not 2 <= nb <= 65536 or groups < 1 or not (math.isfinite(qmax) and qmax > 0) or not (math.isfinite(wall) and wall >= 0):
+            raise ValueError(f'MetaPotential: 2 <= nb <= 65536, groups >= 1, finite qmax > 0 and wall >= 0 expected, got nb={nb}, '
+                             f'groups={groups}, qmax={qmax}, wall={wall}')
+        self.nb, self.qmax, self.wall, self.groups = nb, qmax, wall, groups
+        self._host = np.zeros((groups, nb))
+        self._table = None
+
+    @property
+    def delta(self) -> float:
+        return (2.0 * self.qmax) / float(self.nb - 1)
+
+    @property
+    def nodes(self) -> np.ndarray:
+        return -self.qmax + np.arange(self.nb) * self.delta
+
+    @property
+    def table(self):
+        """float64 [groups, nb] on the device"""
+        if self._table is None:
+            import torch
+            from .config import device
+            self._table = torch.from_numpy(self._host).to(device=device(), dtype=DTYPE).contiguous()
+        return self._table
+
+    def numpy(self) -> np.ndarray:
+        """the table on the host, [groups, nb] (synchronises when it lives on the device)"""
+        return self._host.copy() if self._table is None else self._table.detach().cpu().numpy()
+
+    def _locate(self, q):
+        q = np.asarray(q, dtype=np.float64)
+        t = (q + self.qmax) / self.delta
+        fl = np.floor(t)
+        inside = (t >= 0.0) & (fl <= self.nb - 2)
+        i = np.where(inside, fl, 0).astype(np.int64)
+        return q, inside, i, t - fl
+
+    def value(self, q, group: int = 0) -> np.ndarray:
+        """V(q) of row `group`"""
+        V = self.numpy()[group]
+        q, inside, i, f = self._locate(q)
+        d = np.abs(q) - self.qmax
+        edge = np.where(q < 0.0, V[0], V[-1])
+        return np.where(inside, V[i] + f * (V[i + 1] - V[i]), edge + ((0.5 * self.wall) * d) * d)
+
+    def slope(self, q, group: int = 0) -> np.ndarray:
+        """V'(q) of row `group`"""
+        V = self.numpy()[group]
+        q, inside, i, _ = self._locate(q)
+        d = np.abs(q) - self.qmax
+        return np.where(inside, (V[i + 1] - V[i]) / self.delta, np.where(q < 0.0, -(self.wall * d), self.wall * d))
+
+    def state_dict(self) -> dict:
+        return {'nb': self.nb, 'qmax': self.qmax, 'wall': self.wall, 'groups': self.groups, 'table': self.numpy()}
+
+    def load_state_dict(self, state: dict):
+        shape = (int(state['groups']), int(state['nb']))
+        tab = np.asarray(state['table'], dtype=np.float64)
+        if shape != (self.groups, self.nb) or tab.shape != shape:
+            raise ValueError(f'MetaPotential.load_state_dict: a table of shape {(self.groups, self.nb)} expected, got {tab.shape}')
+        self.qmax, self.wall = float(state['qmax']), float(state['wall'])
+        self._host = tab.copy()
+        if self._table is not None:
+            import torch
+            self._table.copy_(torch.from_numpy(self._host))
+        return self
+
+
+def run_meta(param: Param, x=None, potential: Optional[MetaPotential] = None, n_build: int = 0, w: float = 0.0,
+             integrator: str = 'leapfrog', use_graph: Optional[bool] = None):
+    """`param.nrun` runs of `param.ntraj` HMC trajectories each under the bias `potential` (default: a zero table on
+    |Q_m| <= L^2 / 2 pi, which no field leaves: plain HMC).  The first `n_build` trajectories of the experiment (counted through the
+    runs) are each followed by a deposit of height `w` per walker at its Q_m (ops.meta_deposit); the rest run on the frozen table.
+    x: the start of every run, [2, L, L] or a batch [B, 2, L, L] (default param.initializer()).
+    -> (fields_arr, histories, potential): fields_arr[n] is the last field of run n; histories[n] has run_hmc's keys -- 'traj', 'dt',
+    'acc', 'dH', 'plaq', 'q', 'dq' -- plus 'qm' and 'vbias' (Q_m and V(Q_m) of the trajectory's field under the table the
+    trajectory ran on: the weights of utils.observables.reweighted_mean are exp(vbias)) and 'build' (whether a deposit followed).
+    The seeds of trajectory t are ops.chain_seeds(param.seed, chain, t), formed on the device; momenta and accept uniforms come
+    from ops.random_momenta; trajectory, deposit and measurement are captured once per phase (graph_loop) and replayed
+    (`use_graph`, default on; FTHMC_RUN_GRAPH=0 turns it off): the same bits either way."""
+    import torch
+    from . import ops
+    from .config import device
+    from .graph_loop import GraphLoop
+    ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
+    n_build, w = int(n_build), float(w)
+    if n_build < 0 or not (math.isfinite(w) and w >= 0):
+        raise ValueError(f'run_meta: n_build >= 0 and a finite w >= 0 expected, got {n_build}, {w}')
+    if use_graph is None:
+        use_graph = os.environ.get('FTHMC_RUN_GRAPH', '1') not in ('', '0')
+    x0 = param.initializer() if x is None else x
+    x0 = (x0 if x0.dim() == 4 else x0[None]).to(device=device(), dtype=DTYPE).contiguous()
+    dev, B = x0.device, x0.shape[0]
+    if potential is None:
+        potential = MetaPotential(2, param.L * param.L / (2 * math.pi) + 1.0, 0.0)
+    if B % potential.groups:
+        raise ValueError(f'run_meta: the potential has {potential.groups} rows, which do not divide the {B} chains')
+    table = potential.table
+    histories, fields_arr = {}, []
+    for n in range(param.nrun):
+        t0 = time.time()
+        xs, xn, v = x0.clone(), torch.empty_like(x0), torch.empty_like(x0)
+        seeds = torch.empty(B, dtype=torch.int64, device=dev)
+        u = torch.empty(B, dtype=DTYPE, device=dev)
+        counter = torch.full((1,), n * param.ntraj, dtype=torch.int64, device=dev)      # trajectory t of the whole experiment
+        row = torch.zeros(6 * B, dtype=DTYPE, device=dev)
+        out = {'x_new': xn, 'acc': row[0:B], 'dH': row[B:2 * B], 'qm': row[4 * B:5 * B], 'vbias': row[5 * B:6 * B]}
+        obs = {'plaq': row[2 * B:3 * B], 'Q': row[3 * B:4 * B]}
+        q0 = ops.wilson_action_charge(xs, param.beta)[1].cpu().numpy()
+
+        def enqueue(deposit):
+            ops.chain_seeds(param.seed, 0, B, 0, counter=counter, advance=True, out=seeds)
+            ops.random_momenta(seeds, xs.shape, out_v=v, out_u=u)
+            ops.meta_trajectory(xs, v, u, param.beta, param.dt, param.nstep, table, potential.qmax, potential.wall, integrator=integrator,
+                                out=out)
+            xs.copy_(xn)
+            if deposit:
+                ops.meta_deposit(out['qm'], table, potential.qmax, w)
+            ops.wilson_action_charge(xs, param.beta, out=obs)
+        nbuild = min(max(n_build - n * param.ntraj, 0), param.ntraj)
+        stream = torch.cuda.Stream(device=dev)
+        parts = []
+        for count, deposit in ((nbuild, True), (param.ntraj - nbuild, False)):       # one captured sequence per phase
+            if count == 0:
+                continue
+            loop = GraphLoop(lambda deposit=deposit: enqueue(deposit), row, use_graph=use_graph, stream=stream)
+            for _ in range(count):
+                loop.step()
+            parts.append(loop.rows())
+            loop.join()
+        rows = np.concatenate(parts, axis=0) if parts else np.zeros((0, 6 * B))
+        dt = (time.time() - t0) / max(1, param.ntraj)
+        history = {k: [] for k in ('traj', 'dt', 'acc', 'dH', 'plaq', 'q', 'dq', 'qm', 'vbias', 'build')}
+        qold = q0
+        for i in range(param.ntraj):
+            r = rows[i].reshape(6, B)
+            q = r[3]
+            for k, val in (('traj', n * param.ntraj + i + 1), ('dt', dt), ('acc', torch.from_numpy(r[0].copy())),
+                           ('dH', torch.from_numpy(r[1].copy())), ('plaq', torch.from_numpy(r[2].copy())), ('q', torch.from_numpy(q.copy())),
+                           ('dq', torch.from_numpy(np.sqrt((q - qold) ** 2))), ('qm', torch.from_numpy(r[4].copy())),
+                           ('vbias', torch.from_numpy(r[5].copy())), ('build', i < nbuild)):
+                history[k].append(val)
+            qold = q
+        histories[n] = history
+        fields_arr.append(xs.clone())
+    return fields_arr, histories, potential

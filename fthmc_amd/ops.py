@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import ACT_CODES, INTEGRATORS, MODE_LITERAL, MODE_MD, W_PER_LAYER, FthmcError, check
 
 # The one scratch cache: (device index, stream) -> the flow workspace, (device index, stream, family) -> the buffer of a call
-# family that keeps its own ('train_force', 'loops', 'instanton'); all grown on demand by _stream_buffer
+# family that keeps its own ('train_force', 'loops', 'instanton', 'meta'); all grown on demand by _stream_buffer
 _WS = {}
 _WS_CAPTURED = set()   # keys whose CURRENT buffer was handed out during a graph capture
 _WS_RETIRED = []   # superseded buffers a captured hipGraph may still point into, kept alive
@@ -475,6 +475,90 @@ def instanton_hit(x, beta, seeds, n_hit: int = 1, hit0: int = 0, path: int = 0, 
 def instanton_sums(x, path: int = 0):
     """(sum cos P, sum sin P) per chain as instanton_hit reduces them -> [B, 2] (the cs_out of an n_hit = 0 call)."""
     return _instanton_call(x, 0.0, None, 0, 0, path, None, True)[3]
+
+
+# ---------------------------------------------------------------- metadynamics HMC (csrc/meta.hip, DESIGN 4.15)
+def meta_ws_bytes(B: int, L: int, path: int = 0) -> int:
+    """Scratch of meta_trajectory: 0 for path 1 (the one-launch path needs none)."""
+    return int(_lib.load().fthmc_meta_ws_bytes(B, L, path))
+
+
+def _meta_ws(t: torch.Tensor, need: int):
+    """the scratch of meta_trajectory's sequenced path (a buffer of its own, as _loops_ws); no scratch where none is needed"""
+    return _stream_buffer(t, need, 'meta') if need else (None, 0)
+
+
+def _meta_table(table, B: int, qmax, wall):
+    """the bias table as the library reads it -> (pointer, G, nb, qmax, wall): a contiguous float64 device tensor [G, nb] (or [nb]:
+    G = 1), used IN PLACE (meta_deposit updates it between calls)"""
+    if not isinstance(table, torch.Tensor) or table.dim() not in (1, 2):
+        raise FthmcError('table: expected a device tensor [G, nb] (or [nb])')
+    G, nb = (1, table.shape[0]) if table.dim() == 1 else table.shape
+    _expect(table, G * nb, 'table')
+    qmax, wall = float(qmax), float(wall)
+    if G < 1 or B % G or not 2 <= nb <= 65536 or not (math.isfinite(qmax) and qmax > 0) or not (math.isfinite(wall) and wall >= 0):
+        raise ValueError(f'meta table: G dividing B = {B}, 2 <= nb <= 65536, finite qmax > 0 and wall >= 0 expected, got G={G}, nb={nb}, '
+                         f'qmax={qmax}, wall={wall}')
+    return (_p(table), int(G), int(nb), qmax, wall)
+
+
+def meta_trajectory(x, v, u, beta: float, dt: float, nstep: int, table, qmax: float, wall: float = 0.0, integrator='leapfrog',
+                    path: int = 0, out=None):
+    """One HMC trajectory under the bias potential V(Q_m), Q_m = sum sin P / 2 pi (C ABI fthmc_meta_trajectory) -> dict(x_new, dH,
+    acc, H0, H1, qm, vbias) per chain; qm, vbias: Q_m and V(Q_m) of the field x_new holds.  table: V on the nodes
+    -qmax .. qmax, a float64 device tensor [G, nb] read in place (chain b reads row b // (B // G)); wall: the stiffness of the
+    quadratic wall outside.  path: 0 the library chooses, 1 one launch per trajectory (L <= 64, x_new must not be x), 2 the
+    sequenced path (any L; out['x_new'] may be x).  out: optional dict with any of the result keys to write into.  With an all-zero
+    table and wall = 0 the result is hmc_trajectory's.  Not differentiable."""
+    ic = integrator_code(integrator)
+    x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
+    path = int(path)
+    if u.numel() != B:
+        raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
+    if path not in (0, 1, 2) or int(nstep) < 1:
+        raise ValueError(f'meta_trajectory: path in 0 .. 2 and nstep >= 1 expected, got path={path}, nstep={nstep}')
+    tab = _meta_table(table, B, qmax, wall)
+    xn = _out_like(None if out is None else out.get('x_new'), x, "out['x_new']")
+    if path == 1 and (L > 64 or xn.data_ptr() == x.data_ptr()):
+        raise ValueError("meta_trajectory: path 1 serves L <= 64 with out['x_new'] other than x")
+    dH, acc, H0, H1, qm, vb = (_out_vec(out, k, B, x) for k in ('dH', 'acc', 'H0', 'H1', 'qm', 'vbias'))
+    with torch.cuda.device(x.device):
+        # path 0 takes the one-launch kernel where fthmc_meta_trajectory says it does: no scratch is asked for there
+        seq = path == 2 or (path == 0 and (L > 64 or xn.data_ptr() == x.data_ptr() or get_variant() != 1))
+        ws, nb = _meta_ws(x, meta_ws_bytes(B, L, 2) if seq else 0)
+        check(_lib.load().fthmc_meta_trajectory(_p(x), _p(v), _p(u), B, L, float(beta), float(dt), int(nstep), ic, *tab, path, _p(xn),
+                                                _p(dH), _p(acc), _p(H0), _p(H1), _p(qm), _p(vb), ws, nb, _stream(x)), 'fthmc_meta_trajectory')
+    return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1, 'qm': qm, 'vbias': vb}
+
+
+def meta_deposit(qm, table, qmax: float, w: float):
+    """One hill of height w per walker at qm[b], added to `table` IN PLACE (C ABI fthmc_meta_deposit): inside the table node i
+    gains w (1 - f) and node i + 1 gains w f, outside nothing; the walkers of a row are added in chain order.  -> table"""
+    B = qm.numel() if isinstance(qm, torch.Tensor) else 0
+    _expect(qm, max(B, 1), 'qm')
+    w = float(w)
+    if not (math.isfinite(w) and w >= 0):
+        raise ValueError(f'meta_deposit: a finite w >= 0 expected, got {w}')
+    ptr, G, nb, qmax, _ = _meta_table(table, B, qmax, 0.0)
+    check(_lib.load().fthmc_meta_deposit(_p(qm), B, G, nb, qmax, w, ptr, _stream(qm)), 'fthmc_meta_deposit')
+    return table
+
+
+def meta_force(x, beta: float, table, qmax: float, wall: float = 0.0):
+    """F = dS_b / dx of the biased action S_b = -beta sum cos P + V(Q_m) (C ABI fthmc_meta_force), wilson_force's sign"""
+    x = _field(x); B, _, L, _ = x.shape
+    F = torch.empty_like(x)
+    check(_lib.load().fthmc_meta_force(_p(x), B, L, float(beta), *_meta_table(table, B, qmax, wall), _p(F), _stream(x)), 'fthmc_meta_force')
+    return F
+
+
+def meta_action(x, beta: float, table, qmax: float, wall: float = 0.0, out=None):
+    """-> (S_b, Q_m, V(Q_m)) per chain (C ABI fthmc_meta_action); out: optional dict with any of 'S', 'qm', 'vbias' to write into"""
+    x = _field(x); B, _, L, _ = x.shape
+    S, qm, vb = (_out_vec(out, k, B, x) for k in ('S', 'qm', 'vbias'))
+    check(_lib.load().fthmc_meta_action(_p(x), B, L, float(beta), *_meta_table(table, B, qmax, wall), _p(S), _p(qm), _p(vb), _stream(x)),
+          'fthmc_meta_action')
+    return S, qm, vb
 
 
 def wilson_force(x, beta: float):

@@ -203,3 +203,27 @@ def exact_charge_moment(beta: float, L: int, power: int = 2) -> float:
     p = exact_charge_distribution(beta, L, qmax)
     Q = np.arange(-qmax, qmax + 1, dtype=np.float64)
     return float((Q ** int(power) * p).sum())
+
+
+def reweighted_mean(values, vbias, n_block: int = N_BLOCK):
+    """Unbiased mean of an observable sampled under a frozen metadynamics bias (meta.run_meta):
+        <O> = sum O e^{V} / sum e^{V},      V = `vbias`, the bias potential at each sample's Q_m
+    -> (mean, jackknife error).  values, vbias: arrays of one shape, [samples] or [trajectories, chains].  The common maximum of
+    vbias is subtracted before exponentiating (it cancels in the ratio).  The independent units -- the chains of a 2-D history
+    (every chain's weighted sums over its trajectories), the samples of a 1-D one -- are dealt into `n_block` blocks (at most one
+    per unit) and the error is that of the delete-one-block jackknife of the ratio."""
+    o, vb = np.asarray(values, dtype=np.float64), np.asarray(vbias, dtype=np.float64)
+    if o.shape != vb.shape or o.ndim not in (1, 2) or o.size == 0:
+        raise ValueError(f'reweighted_mean: values and vbias of one shape, [samples] or [trajectories, chains], expected; got {o.shape}, {vb.shape}')
+    wgt = np.exp(vb - vb.max())
+    num, den = wgt * o, wgt
+    if o.ndim == 2:
+        num, den = num.sum(axis=0), den.sum(axis=0)
+    nb = max(1, min(int(n_block), num.size))
+    nums = np.array([c.sum() for c in np.array_split(num, nb)])
+    dens = np.array([c.sum() for c in np.array_split(den, nb)])
+    mean = float(nums.sum() / dens.sum())
+    if nb < 2:
+        return mean, float('nan')
+    jk = (nums.sum() - nums) / (dens.sum() - dens)
+    return mean, float(np.sqrt((nb - 1) * np.mean((jk - jk.mean()) ** 2)))

@@ -473,6 +473,53 @@ int fthmc_instanton_hit(const double* x, int B, int L, double beta, const double
                         int path, double* x_out, int32_t* k_out /* [B] or NULL */, int32_t* nacc_out /* [B] or NULL */,
                         double* cs_out /* [B][2] or NULL */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Metadynamics HMC: plain HMC under a history-dependent bias potential V(Q_m) in the continuous charge
+ *     Q_m(x) = (1 / 2 pi) sum sin P,      P(i,j) = x0[i][j] + x1[i+1][j] - x0[i][j+1] - x1[i][j].
+ * The reference has no counterpart to any of the five entry points below: it samples the unbiased action only.
+ * The table vtab[G][nb] (device doubles) holds V on the nodes q_i = -qmax + i delta, delta = 2 qmax / (nb - 1); chain b reads row
+ * b / (B / G): G = 1 one potential for all walkers, G = B one per chain.  Lookup at q: t = (q + qmax) / delta, i = floor(t),
+ * f = t - i; inside (t >= 0 and i <= nb - 2) V = V_i + f (V_{i+1} - V_i) and V' = (V_{i+1} - V_i) / delta; outside, with
+ * d = |q| - qmax and V_edge the nearer end node, V = V_edge + wall d^2 / 2 and V' = sign(q) wall d (q = +qmax lands here, d = 0).
+ * Biased action S_b = -beta sum cos P + V(Q_m), H = S_b + sum v^2 / 2; the force is the plain stencil on
+ *     gP = beta sin P + c cos P,  c = V'(Q_m) / 2 pi:   F0 = gP(i,j) - gP(i,j-1),  F1 = gP(i-1,j) - gP(i,j)
+ * (fthmc_wilson_force's sign).  Under a frozen table <O> = sum O e^{V(Q_m)} / sum e^{V(Q_m)} is the unbiased expectation value. */
+
+/* No reference counterpart.  Scratch of fthmc_meta_trajectory: 0 for path 1 (the one-launch path needs none) and for refused
+ * arguments, else the sequenced path's (path 0 may take it: x_new == x, L > 64), a multiple of 256 bytes. */
+size_t fthmc_meta_ws_bytes(int B, int L, int path);
+
+/* No reference counterpart.  One biased HMC trajectory of every chain: H0 = S_b(x) + v^2 / 2, the MD of (integrator, dt, nstep)
+ * (FTHMC_INT_*) under the biased force, the end point regularized, H1, accept iff u[b] < exp(-(H1 - H0)).  x_new, dH, acc, H0,
+ * H1 as fthmc_hmc_trajectory_int; qm_out[B], vb_out[B]: Q_m and V(Q_m) of the field x_new holds.  dH .. vb_out may be NULL.
+ * path: 1 = one launch per trajectory, one workgroup per chain (L <= 64, x_new must not be x, no workspace); 2 = the sequenced
+ * path (any L, x_new may be x, workspace fthmc_meta_ws_bytes); 0 = the library chooses: 1 when L <= 64, the MFMA variant is
+ * set and x_new != x, as fthmc_hmc_trajectory_int chooses.  With an all-zero table and no wall path 1 gives the bits of
+ * fthmc_hmc_trajectory_int's one-launch kernels and path 2 those of its sequenced form.  A chain's result does not depend on B or
+ * on its place in the batch (G = B).  Enqueue-only, capturable.  The sequenced path launches the plain kernels' shapes, which put the
+ * chain on grid y: it serves B <= 65535 (beyond: FTHMC_ERR_UNSUPPORTED, and fthmc_meta_ws_bytes is 0); the one-launch path,
+ * fthmc_meta_deposit, fthmc_meta_force and fthmc_meta_action take B up to FTHMC_MAX_B.
+ * A null x / v / u / x_new / vtab, B or L out of range, nstep < 1, G < 1 or B % G != 0, nb < 2 or nb > 65536, a qmax that is not
+ * finite and positive, a wall that is not finite and >= 0, path outside 0 .. 2, path 1 with L > 64 or x_new == x: FTHMC_ERR_ARG;
+ * an unknown integrator, B > 65535 on the sequenced path: FTHMC_ERR_UNSUPPORTED; a short (or null) workspace where one is needed:
+ * FTHMC_ERR_WS. */
+int fthmc_meta_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta, double dt, int nstep,
+                          int integrator, const double* vtab, int G, int nb, double qmax, double wall, int path,
+                          double* x_new, double* dH, double* acc, double* H0, double* H1, double* qm_out /* [B] or NULL */,
+                          double* vb_out /* [B] or NULL */, void* ws, size_t ws_bytes, void* stream);
+
+/* No reference counterpart.  One hill per walker, added to the table IN PLACE: for qm[b] inside the table (the lookup's rule) node i
+ * of the chain's row gains w (1 - f) and node i + 1 gains w f, each product rounded before it is added; outside nothing is added.
+ * The walkers of one row are added in chain order, without atomics: a node's value is ((V + h_b1) + h_b2) + ... over the chains
+ * b1 < b2 < ... that touch it.  Refusals as above (w: finite and >= 0; a null qm). */
+int fthmc_meta_deposit(const double* qm, int B, int G, int nb, double qmax, double w, double* vtab /* in place */, void* stream);
+
+/* No reference counterpart.  The bias on its own, for tests and measurements: F[B][2][L][L] = dS_b / dx, and per chain S = S_b,
+ * qm = Q_m, vb = V(Q_m) (each of the three may be NULL).  Refusals as above. */
+int fthmc_meta_force(const double* x, int B, int L, double beta, const double* vtab, int G, int nb, double qmax, double wall,
+                     double* F, void* stream);
+int fthmc_meta_action(const double* x, int B, int L, double beta, const double* vtab, int G, int nb, double qmax, double wall,
+                      double* S, double* qm, double* vb, void* stream);
+
 /* ---- training ------------------------------------------------------------ */
 /* Reverse-KL loss pieces and weight gradients for a fixed prior draw xi
  * (fthmc/train.py:191-210, fthmc/utils/samplers.py:40-56):
