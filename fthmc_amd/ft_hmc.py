@@ -15,64 +15,35 @@ Beyond the reference: integrator = 'leapfrog' (default) | 'omelyan' | 'force_gra
 """
 from __future__ import annotations
 
+import functools
 import time
+from dataclasses import dataclass
 from math import pi as PI
-from typing import Optional
+from typing import Callable, Optional
 
 import torch
 import torch.nn as nn
 
-import os
-
 from . import ops
 from .config import DTYPE, TrainConfig, device, lfConfig
-from .graph_loop import GraphLoop
+from .graph_loop import GraphLoop, LazyHistory, Row, loops_arg, run_graph_default     # (LazyHistory is imported from here too)
 from .utils import qed_helpers as qed
 from .utils.layers import flow_activation, flow_weights, weights_generation
 
 TWO_PI = 2. * PI
 
 
-class LazyHistory(dict):
-    """The history dict of a captured run: {metric: [per-trajectory tensors]} as the eager loop builds it, filled from the
-    device ring the first time anybody looks -- `run()` itself returns when everything is ENQUEUED."""
-
-    def __init__(self, fill):
-        super().__init__()
-        self._fill_fn = fill
-
-    def _fill(self):
-        if self._fill_fn is not None:
-            fn, self._fill_fn = self._fill_fn, None
-            super().update(fn())
-
-    # every way of looking at, copying or changing a dict fills first: a caller written against the reference's plain history dict
-    # (ft_hmc.py:272-346) never sees (or overwrites) an empty one
-    def __getitem__(self, k): self._fill(); return super().__getitem__(k)
-    def __setitem__(self, k, v): self._fill(); return super().__setitem__(k, v)
-    def __delitem__(self, k): self._fill(); return super().__delitem__(k)
-    def __contains__(self, k): self._fill(); return super().__contains__(k)
-    def __iter__(self): self._fill(); return super().__iter__()
-    def __reversed__(self): self._fill(); return super().__reversed__()
-    def __len__(self): self._fill(); return super().__len__()
-    def __bool__(self): self._fill(); return super().__len__() > 0
-    def __or__(self, other): self._fill(); return dict(super().items()) | dict(other)
-    def __ror__(self, other): self._fill(); return dict(other) | dict(super().items())
-    def __ior__(self, other): self._fill(); super().update(other); return self
-    def get(self, k, d=None): self._fill(); return super().get(k, d)
-    def keys(self): self._fill(); return super().keys()
-    def values(self): self._fill(); return super().values()
-    def items(self): self._fill(); return super().items()
-    def setdefault(self, k, d=None): self._fill(); return super().setdefault(k, d)
-    def pop(self, *a): self._fill(); return super().pop(*a)
-    def popitem(self): self._fill(); return super().popitem()
-    def update(self, *a, **kw): self._fill(); return super().update(*a, **kw)
-    def clear(self): self._fill_fn = None; return super().clear()
-    def copy(self): self._fill(); return dict(super().items())
-    def __repr__(self): self._fill(); return super().__repr__()
-    def __eq__(self, other): self._fill(); return super().__eq__(other)
-    __hash__ = None
-    def __reduce__(self): self._fill(); return (dict, (dict(super().items()),))     # pickles / copies as the plain dict it stands for
+@dataclass
+class _CapturedRun:
+    """the captured run loop of a FieldTransformation and what it was captured for"""
+    sig: tuple                            # everything the capture depends on (see _run_captured)
+    loop: GraphLoop
+    x: torch.Tensor                       # the field the trajectory advances in place
+    state: torch.Tensor                   # its carried (S_eff, plaq, Q) [3, B]
+    row: Row
+    sides: list                           # the chain groups' side streams
+    token: object = None                  # the workspaces the capture saw (ops.trajectory_workspaces)
+    pending: Optional[Callable] = None    # reads the history of the last run while the ring still holds it
 
 
 class FieldTransformation(nn.Module):
@@ -96,9 +67,9 @@ class FieldTransformation(nn.Module):
         # (field tensor, its version, weight key, beta, state [3, B]) of the last trajectory's result
         self._carry = None
         self._last_obs = None         # (plaq, Q) of the flowed accepted field of the last trajectory (run() reads them)
-        self._loop = None             # the captured run loop (GraphLoop) and what it was captured for
+        self._loop = None             # the captured run loop (_CapturedRun)
         self._loop_streams = None     # its stream and the chain groups' side streams: made once, reused by every re-capture
-        self.use_graph = os.environ.get('FTHMC_RUN_GRAPH', '1') not in ('', '0')
+        self.use_graph = run_graph_default()
 
     # ---- weights: packed once, refreshed when a parameter changed in place -----------
     def weights(self, dev) -> torch.Tensor:
@@ -176,31 +147,36 @@ class FieldTransformation(nn.Module):
     def _mode(self):
         return 'md' if self.leapfrog_mode == 'md' else 'literal'
 
+    def _trajectory(self, x, v, u, groups: int = 1):
+        """The fused trajectory of hmc() and _batch_hmc() -> (accepted field, the results of ops.ft_trajectory).
+        (S_eff, plaq, Q) of x is carried over when x IS the field the previous call returned, untouched, under the same
+        weights (by content: _wkey) and beta: that call's H1 sweep computed exactly what this call's H0 sweep would
+        (bit-identical; bench.py's `stateless` figure is the price of recomputing it, as the reference does at ft_hmc.py:205).
+        plaq / Q of the flowed accepted field come with the trajectory: run() need not flow x again for its metrics
+        (kept out of the returned metrics: those are the reference's keys, ft_hmc.py:244-257)."""
+        w = self.weights(x.device)
+        wkey = self._wkey(w)
+        r = ops.ft_trajectory(x, v, u, w, len(self.flow), self.config.beta, self.dt, self.nstep, self._act, mode=self._mode(),
+                              state_in=self._carried_state(x, wkey), groups=groups, wkey=wkey, integrator=self.integrator)
+        xnew = r['x_new'].detach()
+        self._carry = (xnew, xnew._version, wkey, self.config.beta, r['state'])
+        self._last_obs = (r['plaq'], r['Q'])
+        return xnew, r
+
     def hmc(self, x: torch.Tensor, step: int = None, v: Optional[torch.Tensor] = None,
             u: Optional[torch.Tensor] = None):
         """ft_hmc.py:190-224: the tensor is one system (one scalar H, one accept).  For the usual
         [1, 2, L, L] field this is a single fused trajectory launch sequence."""
         x = x.to(device()) if not x.is_cuda else x
         t0 = time.time()
-        metrics = {}
-        if step is not None:
-            metrics['traj'] = step
-        if v is None:
-            v = torch.randn_like(x)
-        if u is None:
-            u = torch.rand([], dtype=torch.float64, device=x.device)
+        metrics = {} if step is None else {'traj': step}
+        v = torch.randn_like(x) if v is None else v
+        u = torch.rand([], dtype=torch.float64, device=x.device) if u is None else u
         self._last_obs = None
         if x.shape[0] == 1:
-            w = self.weights(x.device)
-            wkey = self._wkey(w)
-            state = self._carried_state(x, wkey)                         # see _batch_hmc
-            r = ops.ft_trajectory(x, v, u.reshape(1), w, len(self.flow), self.config.beta,
-                                  self.dt, self.nstep, self._act, mode=self._mode(), state_in=state, wkey=wkey,
-                                  integrator=self.integrator)
             # the packaged code maps the end point with wrap, the notebook with regularize: same set
-            xnew, acc, dh = r['x_new'], r['acc'][0] > 0.5, r['dH'][0]
-            self._carry = (xnew, xnew._version, wkey, self.config.beta, r['state'])
-            self._last_obs = (r['plaq'], r['Q'])
+            xnew, r = self._trajectory(x, v, u.reshape(1))
+            acc, dh = r['acc'][0] > 0.5, r['dH'][0]
         else:
             h0 = self._action(x).sum() + 0.5 * ops.kinetic(v).sum()
             x_, v_ = self.leapfrog(x, v)
@@ -216,30 +192,13 @@ class FieldTransformation(nn.Module):
         """ft_hmc.py:226-257: independent chains, per-chain accept (dead code in the reference
         for B > 1 because its force only works for B = 1)."""
         t0 = time.time()
-        metrics = {}
-        if step is not None:
-            metrics['traj'] = step
-        if v is None:
-            v = torch.randn_like(x)
-        if u is None:
-            u = torch.rand(x.shape[0], dtype=torch.float64, device=x.device)
+        metrics = {} if step is None else {'traj': step}
+        v = torch.randn_like(x) if v is None else v
+        u = torch.rand(x.shape[0], dtype=torch.float64, device=x.device) if u is None else u
         self._last_obs = None
         if self.energy_mode == 'per_chain':
-            # (S_eff, plaq, Q) of x is carried over when x IS the field the previous call returned, untouched, under the same
-            # weights (by content: _wkey) and beta: that call's H1 sweep computed exactly what this call's H0 sweep would
-            # (bit-identical; bench.py's `stateless` figure is the price of recomputing it, as the reference does at ft_hmc.py:205)
-            w = self.weights(x.device)
-            wkey = self._wkey(w)
-            state = self._carried_state(x, wkey)
-            r = ops.ft_trajectory(x, v, u, w, len(self.flow), self.config.beta, self.dt,
-                                  self.nstep, self._act, mode=self._mode(), state_in=state,
-                                  groups=ops.default_groups(x.shape[0], x.shape[-1]), wkey=wkey, integrator=self.integrator)
-            x_, dh, acc = r['x_new'], r['dH'], r['acc']
-            x_ = x_.detach()
-            self._carry = (x_, x_._version, wkey, self.config.beta, r['state'])
-            # plaq / Q of the flowed accepted field come with the trajectory: run() need not flow x again for its metrics
-            # (kept out of the returned metrics: those are the reference's keys, ft_hmc.py:244-257)
-            self._last_obs = (r['plaq'], r['Q'])
+            x_, r = self._trajectory(x, v, u, groups=ops.default_groups(x.shape[0], x.shape[-1]))
+            dh, acc = r['dH'], r['acc']
         else:
             h = self.calc_energy(x, v)
             xp, v_ = self.leapfrog(x, v)
@@ -308,14 +267,7 @@ class FieldTransformation(nn.Module):
         self.x_last = x
         return history
 
-    @staticmethod
-    def _loops_arg(loops, L: int):
-        if loops is None:
-            return None
-        Rmax, Tmax = (int(loops), int(loops)) if isinstance(loops, int) else (int(loops[0]), int(loops[1]))
-        if not (1 <= Rmax <= L and 1 <= Tmax <= L):
-            raise ValueError(f'loops: (Rmax, Tmax) with 1 <= Rmax, Tmax <= L = {L} expected, got {loops!r}')
-        return Rmax, Tmax
+    _loops_arg = staticmethod(loops_arg)
 
     def _measure_loops(self, x, w, loops, W, table, wkey=None):
         """the loop table of F(x): per chain into W [B, Rmax, Tmax] (or a fresh tensor), its batch mean into `table` [Rmax, Tmax]"""
@@ -329,6 +281,11 @@ class FieldTransformation(nn.Module):
               f"q={float(torch.as_tensor(q).mean()):.3f}", flush=True)
 
     # ---- the captured loop ----------------------------------------------------------
+    @property
+    def captured(self) -> bool:
+        """whether run() holds a captured loop (it has run through the graph at least once)"""
+        return self._loop is not None and self._loop.loop.captured
+
     def _run_captured(self, x: torch.Tensor, nprint: int, num_trajs: int, batch: bool, loops=None, loops_every: int = 1):
         dev = x.device
         caller = torch.cuda.current_stream(dev)
@@ -343,36 +300,32 @@ class FieldTransformation(nn.Module):
         # it on the device against the stamps in the workspaces (include/fthmc_hip.h "Weight versions")
         sig = (tuple(x.shape), dev, w.data_ptr(), nl, act, mode, beta, self.dt, self.nstep, G, batch,
                ops.get_variant(), ops.get_small_path(), ops.weights_version(wkey), self.integrator, loops, loops_every if loops else 1)
-        if self._loop is not None and self._loop.get('pending') is not None:
-            self._loop['pending']()                                       # an unread history of the previous run: read it before its ring is reused
-            self._loop['pending'] = None
-        if self._loop is None or self._loop['sig'] != sig:
-            self._loop = self._make_loop(xd, w, nl, act, mode, beta, G, batch, sig, wkey, loops, loops_every)
-
-        def prepare(lp):
-            """start field, start state and the weight expansion on the loop's stream -> (q0, workspace token)"""
-            loop = lp['loop']
-            loop.stream.wait_stream(caller)
-            with torch.cuda.stream(loop.stream):
+        lp = self._loop
+        if lp is not None and lp.pending is not None:
+            lp.pending()                              # an unread history of the previous run: read it before its ring is reused
+            lp.pending = None
+        while True:
+            if lp is None or lp.sig != sig:
+                lp = self._loop = self._make_loop(xd, w, wkey, sig, G, loops, loops_every)
+            # start field, start state and the weight expansion on the loop's stream
+            lp.loop.stream.wait_stream(caller)
+            with torch.cuda.stream(lp.loop.stream):
                 if carried is not None:
-                    lp['state'].copy_(carried.reshape(3, B))
+                    lp.state.copy_(carried.reshape(3, B))
                 else:
                     S, _, p_, q_ = ops.ft_action(xd, w, nl, beta, act)
-                    torch.stack([S, p_, q_], out=lp['state'])
+                    torch.stack([S, p_, q_], out=lp.state)
                 # the start of the q history: Q of the flowed start field for a batch (ft_hmc.py:311-313), of the field itself otherwise
-                q0_ = lp['state'][2].clone() if batch else qed.batch_charges(xd)
-                lp['x'].copy_(xd)
+                q0 = lp.state[2].clone() if batch else qed.batch_charges(xd)
+                lp.x.copy_(xd)
                 # the workspaces of the loop's streams at their final size, holding the expansion of these weights: the
                 # replays' own expansion launches find the stamps and leave at once
-                return q0_, ops.trajectory_workspaces(lp['x'], w, nl, groups=G, side_streams=lp['sides'], wkey=wkey)
-        q0, token = prepare(self._loop)
-        if self._loop['loop'].captured and self._loop['token'] != token:
-            # a workspace moved since the capture (grown by another caller of these streams): capture again
-            self._loop = self._make_loop(xd, w, nl, act, mode, beta, G, batch, sig, wkey, loops, loops_every)
-            q0, token = prepare(self._loop)
-        lp = self._loop
-        loop, xs, state = lp['loop'], lp['x'], lp['state']
-        lp['token'] = token
+                token = ops.trajectory_workspaces(lp.x, w, nl, groups=G, side_streams=lp.sides, wkey=wkey)
+            if not (lp.loop.captured and lp.token != token):
+                break
+            lp = None                   # a workspace moved since the capture (grown by another caller of these streams): capture again
+        loop, xs, state, row = lp.loop, lp.x, lp.state, lp.row
+        lp.token = token
         loop.reset_history()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record(loop.stream)
@@ -382,60 +335,47 @@ class FieldTransformation(nn.Module):
             if loop.captured and not was_captured:
                 # the eager first step may have grown a workspace: the capture that followed saw the final ones
                 with torch.cuda.stream(loop.stream):
-                    lp['token'] = ops.trajectory_workspaces(xs, w, nl, groups=G, side_streams=lp['sides'], wkey=wkey)
+                    lp.token = ops.trajectory_workspaces(xs, w, nl, groups=G, side_streams=lp.sides, wkey=wkey)
             if nprint and i % nprint == 0:
-                r = torch.from_numpy(loop.last()[:4 * B]).view(4, B)
-                self._print_line(i, r[0], r[1], r[2], r[3])
+                loop.stream.synchronize()
+                r = row.split(row.flat.cpu())
+                self._print_line(i, r['acc'], r['dH'], r['plaq'], r['Q'])
         ev1.record(loop.stream)
         with torch.cuda.stream(loop.stream):
-            x_out = xs.clone()
-            st_out = state.clone()
+            x_out, st_out = xs.clone(), state.clone()
         loop.join()
         self._carry = (x_out, x_out._version, wkey, beta, st_out)
         self._last_obs = None
         self.x_last = x_out
-        n = num_trajs
-        rows_cache = [None]
-
-        def loop_rows():
-            if rows_cache[0] is None:
-                rows_cache[0] = loop.rows()
-            return rows_cache[0]
-        lp['pending'] = loop_rows
+        lp.pending = loop_rows = functools.cache(loop.rows)               # read once: by the history or before the ring is reused
 
         def fill():
-            R_ = torch.from_numpy(loop_rows()).to(dev)
-            H = R_[:, :4 * B].reshape(n, 4, B)
+            c = row.split(torch.from_numpy(loop_rows()).to(dev))
             ev1.synchronize()
-            dt = ev0.elapsed_time(ev1) * 1e-3 / n                         # per trajectory, on the device's clock
-            qs = torch.cat([q0.reshape(1, -1).to(H.dtype), H[:, 3]], 0)
+            dt = ev0.elapsed_time(ev1) * 1e-3 / num_trajs                 # per trajectory, on the device's clock
+            qs = torch.cat([q0.reshape(1, -1).to(c['Q'].dtype), c['Q']], 0)
             dq = torch.sqrt((qs[1:] - qs[:-1]) ** 2)
-            h = {'traj': list(range(n)), 'dt': [dt] * n}
+            h = {'traj': list(range(num_trajs)), 'dt': [dt] * num_trajs}
             if batch:
-                h.update({'acc': [H[i, 0] for i in range(n)], 'dh': [H[i, 1] for i in range(n)],
-                          'exp_mdh': [torch.exp(-H[i, 1]) for i in range(n)]})
+                h.update({'acc': list(c['acc']), 'dh': list(c['dH']), 'exp_mdh': [torch.exp(-dh) for dh in c['dH']]})
             else:
-                h.update({'acc': [H[i, 0, 0] > 0.5 for i in range(n)], 'dh': [H[i, 1, 0] for i in range(n)]})
-            h.update({'plaq': [H[i, 2] for i in range(n)], 'q': [H[i, 3] for i in range(n)], 'dq': [dq[i] for i in range(n)]})
-            if loops is not None:                                         # the row's tail: the table of the last measured trajectory
-                h['wloops'] = [R_[i, 4 * B:].reshape(loops) for i in range(0, n, loops_every)]
+                h.update({'acc': [a[0] > 0.5 for a in c['acc']], 'dh': [dh[0] for dh in c['dH']]})
+            h.update({'plaq': list(c['plaq']), 'q': list(c['Q']), 'dq': list(dq)})
+            if loops is not None:                                         # the table of the last measured trajectory
+                h['wloops'] = list(c['wloops'][::loops_every])
             return h
         return LazyHistory(fill)
 
-    def _make_loop(self, x, w, nl, act, mode, beta, G, batch, sig, wkey, loops=None, loops_every: int = 1):
+    def _make_loop(self, x, w, wkey, sig, G, loops, loops_every) -> _CapturedRun:
         dev, B = x.device, x.shape[0]
-        integrator = self.integrator                                      # what this capture is for (part of `sig`)
-        xs = torch.empty_like(x)
-        v = torch.empty_like(x)
+        # what this capture is for (all part of `sig`)
+        nl, act, mode, beta, integrator = len(self.flow), self._act, self._mode(), self.config.beta, self.integrator
+        xs, v = torch.empty_like(x), torch.empty_like(x)
         u = torch.empty(B, dtype=torch.float64, device=dev)
-        # acc, dH, plaq, Q of the trajectory [4, B]; with loops, the batch-mean table [Rmax, Tmax] behind them
-        nlp = loops[0] * loops[1] if loops is not None else 0
-        flat = torch.empty(4 * B + nlp, dtype=torch.float64, device=dev)
-        if nlp:
-            flat[4 * B:].zero_()
-        row = flat[:4 * B].view(4, B)
+        # acc, dH, plaq, Q of the trajectory; with loops, the batch-mean table [Rmax, Tmax] behind them
+        row = Row(dev, acc=B, dH=B, plaq=B, Q=B, wloops=loops)
         state = torch.empty(3, B, dtype=torch.float64, device=dev)
-        out = {'x_new': xs, 'acc': row[0], 'dH': row[1], 'plaq': row[2], 'Q': row[3], 'state': state,
+        out = {'x_new': xs, 'acc': row['acc'], 'dH': row['dH'], 'plaq': row['plaq'], 'Q': row['Q'], 'state': state,
                'H0': torch.empty(B, dtype=torch.float64, device=dev), 'H1': torch.empty(B, dtype=torch.float64, device=dev)}
 
         # the loop's own streams (its own and one per chain group beyond the first), made once per FieldTransformation and
@@ -457,12 +397,11 @@ class FieldTransformation(nn.Module):
         measure = None
         if loops is not None:
             W = torch.empty(B, loops[0], loops[1], dtype=torch.float64, device=dev)
-            table = flat[4 * B:].view(loops)
 
             def measure():
-                self._measure_loops(xs, w, loops, W, table, wkey=wkey)    # of F(accepted latent field)
-        loop = GraphLoop(enqueue, flat, use_graph=True, stream=lstream, extra=measure, extra_every=loops_every)
-        return {'sig': sig, 'loop': loop, 'x': xs, 'state': state, 'row': row, 'token': None, 'pending': None, 'sides': sides}
+                self._measure_loops(xs, w, loops, W, row['wloops'], wkey=wkey)    # of F(accepted latent field)
+        loop = GraphLoop(enqueue, row.flat, use_graph=True, stream=lstream, extra=measure, extra_every=loops_every)
+        return _CapturedRun(sig, loop, xs, state, row, sides)
 
 
 def run_ftHMC(flow: torch.nn.Module, config: TrainConfig, tau: float, nstep: int, num_trajs: int = 1024,

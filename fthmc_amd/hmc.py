@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from .config import DTYPE, Param
+from .graph_loop import instanton_arg, loops_arg
 from .utils import qed_helpers as qed
 
 
@@ -27,17 +28,12 @@ def run_hmc(param: Param, x: torch.Tensor = None, plot_metrics: bool = False, fi
     not cross at large beta.  The history gains 'inst_acc' (accepted / k per chain) and 'inst_dq' (the applied charge per chain)."""
     from . import ops
     ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
-    if loops is not None:
-        loops = (int(loops), int(loops)) if isinstance(loops, int) else (int(loops[0]), int(loops[1]))
-        if not (1 <= loops[0] <= param.L and 1 <= loops[1] <= param.L):
-            raise ValueError(f'loops: (Rmax, Tmax) with 1 <= Rmax, Tmax <= L = {param.L} expected, got {loops!r}')
+    loops = loops_arg(loops, param.L)
     loops_every = max(1, int(loops_every))
     overrelax = int(overrelax)
     if overrelax < 0:
         raise ValueError(f'overrelax: a number of sweeps >= 0 expected, got {overrelax}')
-    instanton = int(instanton)
-    if not 0 <= instanton <= 1024:
-        raise ValueError(f'instanton: a number of hits in 0 .. 1024 expected, got {instanton}')
+    instanton = instanton_arg(instanton)
     action = qed.BatchAction(param.beta)
     histories, fields_arr, run_times = {}, [], []
     for n in range(param.nrun):

@@ -9,15 +9,14 @@ charge no faster than HMC does; that stays with the flow and the beta ladder (te
 instanton hit (csrc/topo.hip), which does: run_local(instanton=k) puts k hits behind every update."""
 from __future__ import annotations
 
-import os
 import time
 from typing import Optional
 
 import numpy as np
 import torch
 
-from .config import DTYPE, Param
-from .graph_loop import GraphLoop
+from .config import Param
+from .graph_loop import GraphLoop, Row, batched_start, chain_history, instanton_arg, loops_arg, run_graph_default
 
 
 def run_local(param: Param, x: Optional[torch.Tensor] = None, n_overrelax: int = 0, sweeps_per_traj: int = 1, loops=None,
@@ -34,30 +33,21 @@ def run_local(param: Param, x: Optional[torch.Tensor] = None, n_overrelax: int =
     captured sequence, under the update's seeds (hit0 = 0: the seeds are fresh per update; the hit's counter plane is its own).  The
     history gains 'inst_acc' (accepted / k per chain) and 'inst_dq' (the applied charge per chain)."""
     from . import ops
-    from .config import device
-    n_overrelax, sweeps_per_traj, loops_every, instanton = int(n_overrelax), int(sweeps_per_traj), max(1, int(loops_every)), int(instanton)
-    if not 0 <= instanton <= 1024:
-        raise ValueError(f'run_local: instanton: a number of hits in 0 .. 1024 expected, got {instanton}')
+    n_overrelax, sweeps_per_traj, loops_every = int(n_overrelax), int(sweeps_per_traj), max(1, int(loops_every))
+    instanton = instanton_arg(instanton, 'run_local')
     if n_overrelax < 0 or sweeps_per_traj < 1:
         raise ValueError(f'run_local: n_overrelax >= 0 and sweeps_per_traj >= 1 expected, got {n_overrelax}, {sweeps_per_traj}')
-    if loops is not None:
-        loops = (int(loops), int(loops)) if isinstance(loops, int) else (int(loops[0]), int(loops[1]))
-        if not (1 <= loops[0] <= param.L and 1 <= loops[1] <= param.L):
-            raise ValueError(f'loops: (Rmax, Tmax) with 1 <= Rmax, Tmax <= L = {param.L} expected, got {loops!r}')
-    if use_graph is None:
-        use_graph = os.environ.get('FTHMC_RUN_GRAPH', '1') not in ('', '0')
-    x0 = param.initializer() if x is None else x
-    x0 = (x0 if x0.dim() == 4 else x0[None]).to(device=device(), dtype=DTYPE).contiguous()
+    loops = loops_arg(loops, param.L)
+    use_graph = run_graph_default() if use_graph is None else use_graph
+    x0 = batched_start(param, x)
     dev, B = x0.device, x0.shape[0]
-    nl = 0 if loops is None else loops[0] * loops[1]
     histories, fields_arr = {}, []
     for n in range(param.nrun):
         t0 = time.time()
         xs = x0.clone()
         seeds = torch.empty(B, dtype=torch.int64, device=dev)
         counter = torch.full((1,), n * param.ntraj, dtype=torch.int64, device=dev)      # update t of the whole experiment
-        row = torch.zeros(2 * B + nl + (2 * B if instanton else 0), dtype=DTYPE, device=dev)
-        obs = {'plaq': row[0:B], 'Q': row[B:2 * B]}
+        row = Row(dev, plaq=B, Q=B, wloops=loops, k=B if instanton else 0, nacc=B if instanton else 0)
         q0 = ops.wilson_action_charge(xs, param.beta)[1].cpu().numpy()
         if instanton:
             iout = {'x': xs, 'k': torch.empty(B, dtype=torch.int32, device=dev), 'nacc': torch.empty(B, dtype=torch.int32, device=dev)}
@@ -67,31 +57,20 @@ def run_local(param: Param, x: Optional[torch.Tensor] = None, n_overrelax: int =
             ops.local_update(xs, param.beta, seeds, n_hb=1, n_or=n_overrelax, nsweep=sweeps_per_traj, out=xs)
             if instanton:
                 ops.instanton_hit(xs, param.beta, seeds, n_hit=instanton, out=iout)
-                row[2 * B + nl:3 * B + nl].copy_(iout['k'])
-                row[3 * B + nl:].copy_(iout['nacc'])
-            ops.wilson_action_charge(xs, param.beta, out=obs)
+                row['k'].copy_(iout['k'])
+                row['nacc'].copy_(iout['nacc'])
+            ops.wilson_action_charge(xs, param.beta, out={'plaq': row['plaq'], 'Q': row['Q']})
 
         def measure():
-            ops.wilson_loops(xs, loops[0], loops[1], mean_out=row[2 * B:2 * B + nl])
-        loop = GraphLoop(enqueue, row, use_graph=use_graph, extra=measure if loops is not None else None, extra_every=loops_every)
+            ops.wilson_loops(xs, loops[0], loops[1], mean_out=row['wloops'])
+        loop = GraphLoop(enqueue, row.flat, use_graph=use_graph, extra=measure if loops is not None else None, extra_every=loops_every)
         for _ in range(param.ntraj):
             loop.step()
-        rows = loop.rows()
+        c = row.split(loop.rows())
         loop.join()
         dt = (time.time() - t0) / max(1, param.ntraj)
-        history = {k: [] for k in ('traj', 'dt', 'acc', 'plaq', 'q', 'dq')}
-        qold = q0
-        for i in range(param.ntraj):
-            plaq, q = rows[i, 0:B], rows[i, B:2 * B]
-            for k, v in (('traj', n * param.ntraj + i + 1), ('dt', dt), ('acc', torch.ones(B, dtype=DTYPE)), ('plaq', torch.from_numpy(plaq.copy())),
-                         ('q', torch.from_numpy(q.copy())), ('dq', torch.from_numpy(np.sqrt((q - qold) ** 2)))):
-                history[k].append(v)
-            if loops is not None and i % loops_every == 0:
-                history.setdefault('wloops', []).append(torch.from_numpy(rows[i, 2 * B:2 * B + nl].reshape(loops).copy()))
-            if instanton:
-                history.setdefault('inst_acc', []).append(torch.from_numpy(rows[i, 3 * B + nl:] / instanton))
-                history.setdefault('inst_dq', []).append(torch.from_numpy(rows[i, 2 * B + nl:3 * B + nl].astype(np.int32)))
-            qold = q
-        histories[n] = history
+        late = {'inst_acc': c['nacc'] / instanton, 'inst_dq': c['k'].astype(np.int32)} if instanton else None
+        histories[n] = chain_history(n * param.ntraj + 1, dt, q0, {'acc': np.ones_like(c['plaq']), 'plaq': c['plaq'], 'q': c['Q']},
+                                     wloops=c.get('wloops'), loops_every=loops_every, late=late)
         fields_arr.append(xs.clone())
     return fields_arr, histories

@@ -9,7 +9,6 @@ et al. 2021-23 compare it in 2D U(1) with the instanton update (csrc/topo.hip) a
 from __future__ import annotations
 
 import math
-import os
 import time
 from typing import Optional
 
@@ -108,16 +107,13 @@ def run_meta(param: Param, x=None, potential: Optional[MetaPotential] = None, n_
     (`use_graph`, default on; FTHMC_RUN_GRAPH=0 turns it off): the same bits either way."""
     import torch
     from . import ops
-    from .config import device
-    from .graph_loop import GraphLoop
+    from .graph_loop import GraphLoop, Row, batched_start, chain_history, run_graph_default
     ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
     n_build, w = int(n_build), float(w)
     if n_build < 0 or not (math.isfinite(w) and w >= 0):
         raise ValueError(f'run_meta: n_build >= 0 and a finite w >= 0 expected, got {n_build}, {w}')
-    if use_graph is None:
-        use_graph = os.environ.get('FTHMC_RUN_GRAPH', '1') not in ('', '0')
-    x0 = param.initializer() if x is None else x
-    x0 = (x0 if x0.dim() == 4 else x0[None]).to(device=device(), dtype=DTYPE).contiguous()
+    use_graph = run_graph_default() if use_graph is None else use_graph
+    x0 = batched_start(param, x)
     dev, B = x0.device, x0.shape[0]
     if potential is None:
         potential = MetaPotential(2, param.L * param.L / (2 * math.pi) + 1.0, 0.0)
@@ -131,9 +127,8 @@ def run_meta(param: Param, x=None, potential: Optional[MetaPotential] = None, n_
         seeds = torch.empty(B, dtype=torch.int64, device=dev)
         u = torch.empty(B, dtype=DTYPE, device=dev)
         counter = torch.full((1,), n * param.ntraj, dtype=torch.int64, device=dev)      # trajectory t of the whole experiment
-        row = torch.zeros(6 * B, dtype=DTYPE, device=dev)
-        out = {'x_new': xn, 'acc': row[0:B], 'dH': row[B:2 * B], 'qm': row[4 * B:5 * B], 'vbias': row[5 * B:6 * B]}
-        obs = {'plaq': row[2 * B:3 * B], 'Q': row[3 * B:4 * B]}
+        row = Row(dev, acc=B, dH=B, plaq=B, Q=B, qm=B, vbias=B)
+        out = {'x_new': xn, 'acc': row['acc'], 'dH': row['dH'], 'qm': row['qm'], 'vbias': row['vbias']}
         q0 = ops.wilson_action_charge(xs, param.beta)[1].cpu().numpy()
 
         def enqueue(deposit):
@@ -144,31 +139,22 @@ def run_meta(param: Param, x=None, potential: Optional[MetaPotential] = None, n_
             xs.copy_(xn)
             if deposit:
                 ops.meta_deposit(out['qm'], table, potential.qmax, w)
-            ops.wilson_action_charge(xs, param.beta, out=obs)
+            ops.wilson_action_charge(xs, param.beta, out={'plaq': row['plaq'], 'Q': row['Q']})
         nbuild = min(max(n_build - n * param.ntraj, 0), param.ntraj)
         stream = torch.cuda.Stream(device=dev)
         parts = []
         for count, deposit in ((nbuild, True), (param.ntraj - nbuild, False)):       # one captured sequence per phase
             if count == 0:
                 continue
-            loop = GraphLoop(lambda deposit=deposit: enqueue(deposit), row, use_graph=use_graph, stream=stream)
+            loop = GraphLoop(lambda deposit=deposit: enqueue(deposit), row.flat, use_graph=use_graph, stream=stream)
             for _ in range(count):
                 loop.step()
             parts.append(loop.rows())
             loop.join()
-        rows = np.concatenate(parts, axis=0) if parts else np.zeros((0, 6 * B))
+        c = row.split(np.concatenate(parts + [np.zeros((0, row.width))], axis=0))
         dt = (time.time() - t0) / max(1, param.ntraj)
-        history = {k: [] for k in ('traj', 'dt', 'acc', 'dH', 'plaq', 'q', 'dq', 'qm', 'vbias', 'build')}
-        qold = q0
-        for i in range(param.ntraj):
-            r = rows[i].reshape(6, B)
-            q = r[3]
-            for k, val in (('traj', n * param.ntraj + i + 1), ('dt', dt), ('acc', torch.from_numpy(r[0].copy())),
-                           ('dH', torch.from_numpy(r[1].copy())), ('plaq', torch.from_numpy(r[2].copy())), ('q', torch.from_numpy(q.copy())),
-                           ('dq', torch.from_numpy(np.sqrt((q - qold) ** 2))), ('qm', torch.from_numpy(r[4].copy())),
-                           ('vbias', torch.from_numpy(r[5].copy())), ('build', i < nbuild)):
-                history[k].append(val)
-            qold = q
-        histories[n] = history
+        cols = {'acc': c['acc'], 'dH': c['dH'], 'plaq': c['plaq'], 'q': c['Q'], 'qm': c['qm'], 'vbias': c['vbias'],
+                'build': [i < nbuild for i in range(param.ntraj)]}
+        histories[n] = chain_history(n * param.ntraj + 1, dt, q0, cols)
         fields_arr.append(xs.clone())
     return fields_arr, histories, potential

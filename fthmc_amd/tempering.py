@@ -29,8 +29,7 @@ import torch
 
 from . import ops
 from .config import DTYPE, Param, device
-from .ft_hmc import LazyHistory
-from .graph_loop import GraphLoop
+from .graph_loop import GraphLoop, LazyHistory, Row
 from .parallel import shard_range, world
 
 # key domains of the driver's own streams: a seed of another domain is the run's seed moved by a fixed odd offset, so the
@@ -119,9 +118,8 @@ def run_tempered(param: Param, flow, betas: Sequence[float], n_ladders: int, ntr
     lad = ops.ladder_init(bl, M, device=dev)
     beta_b, rung, chain_of, dbetas = lad['beta_b'], lad['rung'], lad['chain_of'], lad['betas']
     P = 2 * int(swap_every)                                              # one period: both parities once
-    NS = M * (K - 1)
-    R = 5 * B + NS                                                       # acc, dH, plaq, Q, rung | swap_acc of the round behind it
-    rows = torch.empty(P, R, dtype=torch.float64, device=dev)
+    layout = Row(None, acc=B, dH=B, plaq=B, Q=B, rung=B, swap_acc=(M, K - 1))     # swap_acc: of the round behind the trajectory
+    rows = torch.empty(P, layout.width, dtype=torch.float64, device=dev)
     v = torch.empty_like(xs)
     u = torch.empty(B, dtype=torch.float64, device=dev)
     us = torch.empty(M, K - 1, dtype=torch.float64, device=dev)
@@ -136,16 +134,16 @@ def run_tempered(param: Param, flow, betas: Sequence[float], n_ladders: int, ntr
 
     def one(j: int):
         """trajectory j of a period (and the swap round behind it) -> rows[j]"""
-        row = rows[j]
-        out = {'x_new': xs, 'acc': row[0:B], 'dH': row[B:2 * B], 'plaq': row[2 * B:3 * B], 'Q': row[3 * B:4 * B], 'state': state,
+        row = layout.over(rows[j])
+        out = {'x_new': xs, 'acc': row['acc'], 'dH': row['dH'], 'plaq': row['plaq'], 'Q': row['Q'], 'state': state,
                'H0': scratch['H0'], 'H1': scratch['H1']}
         ops.chain_seeds(seed, lo, B, 0, counter=t_cnt, advance=True, out=seeds)
         ops.random_momenta(seeds, (B, 2, L, L), out_v=v, out_u=u)
         ops.ft_trajectory(xs, v, u, w, nl, beta_b, dt, nstep, act, mode='md', out=out, state_in=state if have_state[0] else None,
                           groups=groups, integrator=integrator)
         have_state[0] = True
-        row[4 * B:5 * B].copy_(rung)                                     # the rung this trajectory ran on
-        sw = row[5 * B:].view(M, K - 1)
+        row['rung'].copy_(rung)                                          # the rung this trajectory ran on
+        sw = row['swap_acc']
         if (j + 1) % swap_every == 0:
             parity = ((j + 1) // swap_every - 1) % 2
             ops.chain_seeds(swap_seed(seed), ladder_lo, M, 0, counter=r_cnt, advance=True, out=sseeds)
@@ -162,7 +160,7 @@ def run_tempered(param: Param, flow, betas: Sequence[float], n_ladders: int, ntr
     caller = torch.cuda.current_stream(dev)
     stream = torch.cuda.Stream(device=dev)
     stream.wait_stream(caller)
-    tail = torch.empty(max(rem, 1), R, dtype=torch.float64, device=dev)
+    tail = torch.empty(max(rem, 1), layout.width, dtype=torch.float64, device=dev)
     loop = GraphLoop(period, rows, chunk=max(1, 256 // P), use_graph=bool(captured), stream=stream)
     for _ in range(n_full):
         loop.step()
@@ -174,19 +172,18 @@ def run_tempered(param: Param, flow, betas: Sequence[float], n_ladders: int, ntr
     loop.join()
 
     def fill():
-        H = loop.rows().reshape(n_full * P, R)
+        H = loop.rows().reshape(n_full * P, layout.width)
         if rem:
             stream.synchronize()
             H = np.concatenate([H, tail[:rem].cpu().numpy()], axis=0)
-        n = H.shape[0]
-        rg = np.rint(H[:, 4 * B:5 * B]).astype(np.int64)                                  # [n, B]
+        n, c = H.shape[0], layout.split(H)
+        rg = np.rint(c['rung']).astype(np.int64)                                          # [n, B]
         # chain on rung k of ladder m at trajectory t: the inverse permutation of rg within every ladder
         order = np.argsort(rg.reshape(n, M, K), axis=2) + (np.arange(M) * K)[None, :, None]   # [n, M, K] -> chain index
         h = {}
-        for i, key in enumerate(('acc', 'dH', 'plaq', 'Q')):
-            series = H[:, i * B:(i + 1) * B]
-            h[key] = np.take_along_axis(series, order.reshape(n, B), axis=1).reshape(n, M, K).transpose(0, 2, 1)   # [n, K, M]
-        sw = H[:, 5 * B:].reshape(n, M, K - 1)
+        for key in ('acc', 'dH', 'plaq', 'Q'):
+            h[key] = np.take_along_axis(c[key], order.reshape(n, B), axis=1).reshape(n, M, K).transpose(0, 2, 1)   # [n, K, M]
+        sw = c['swap_acc']
         tried = (sw >= 0).sum(axis=(0, 1))
         h['swap_tried'] = tried
         h['swap_acc'] = np.where(tried > 0, (sw > 0.5).sum(axis=(0, 1)) / np.maximum(tried, 1), np.nan)

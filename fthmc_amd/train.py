@@ -339,10 +339,7 @@ class GraphTrainer:
         self.counter = torch.zeros(1, dtype=torch.int64, device=self.dev)      # steps taken, on the device: keys the step's draws
         self.xi = torch.empty(self.B, 2, L, L, dtype=DTYPE, device=self.dev)
         self.row = torch.empty(2 + 5 * self.B, dtype=DTYPE, device=self.dev)
-        self.chunk = max(1, int(chunk))
-        self.hist_dev = torch.empty(self.chunk, self.row.numel(), dtype=DTYPE, device=self.dev)
-        self.hist_host = []                                            # flushed chunks (numpy)
-        self.nstep = 0
+        self.ring = graph_loop.RowRing(self.row.numel(), chunk, self.dev, DTYPE)     # the metrics rows of every step so far
         self.graph = None
         self.stream = torch.cuda.Stream(device=self.dev)
         flatten_flow(model.layers); flow_grad_buffer(model.layers); attach_grads(model.layers)
@@ -403,11 +400,6 @@ class GraphTrainer:
     def captured(self) -> bool:
         return self.graph is not None
 
-    def _flush(self):
-        k = self.nstep % self.chunk or (self.chunk if self.nstep else 0)
-        if k:
-            self.hist_host.append(self.hist_dev[:k].cpu().numpy())
-
     def step(self):
         """enqueue one training step; returns nothing and waits for nothing (unless a scheduler is attached)"""
         with torch.cuda.stream(self.stream):
@@ -429,10 +421,7 @@ class GraphTrainer:
                 self._enqueue()
                 attach_grads(self.model.layers)
             bump_weights_generation(flatten_flow(self.model.layers))     # a replay writes the weights behind every version counter
-            self.hist_dev[self.nstep % self.chunk].copy_(self.row)
-            self.nstep += 1
-            if self.nstep % self.chunk == 0:
-                self._flush()
+            self.ring.push(self.row)
             if self.scheduler is not None:
                 self.scheduler.step(float(self.row[0]))
 
@@ -448,19 +437,8 @@ class GraphTrainer:
     def history(self) -> dict:
         """{key: [per-step arrays]} of every step so far (synchronises)"""
         self.stream.synchronize()
-        chunks = list(self.hist_host)
-        k = self.nstep % self.chunk
-        if k:
-            chunks.append(self.hist_dev[:k].cpu().numpy())
-        if not chunks:
-            return {k_: [] for k_ in METRIC_KEYS}
-        allrows = np.concatenate(chunks, axis=0)
-        out = {k_: [] for k_ in METRIC_KEYS}
-        for r in allrows:
-            m = _metrics_dict(r, self.B)
-            for k_ in METRIC_KEYS:
-                out[k_].append(m[k_])
-        return out
+        steps = [_metrics_dict(r, self.B) for r in self.ring.rows()]
+        return {k_: [m[k_] for m in steps] for k_ in METRIC_KEYS}
 
 
 class FlatAdam(optim.Adam):

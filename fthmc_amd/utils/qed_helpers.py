@@ -400,17 +400,14 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
     the flow only changes how the molecular dynamics proposes: the target density of that field is exp(-S_W).  The hit's proposal
     x -> x +- A is symmetric and volume-preserving in that field, so its acceptance with the plain Wilson action is exact between
     flowed trajectories; no Jacobian of the flow enters."""
-    import os
+    from ..graph_loop import instanton_arg, run_graph_default
     ops.integrator_code(integrator)                                      # an unknown name raises before anything runs
-    instanton = int(instanton)
-    if not 0 <= instanton <= 1024:
-        raise ValueError(f'instanton: a number of hits in 0 .. 1024 expected, got {instanton}')
+    instanton = instanton_arg(instanton)
     if field is None:
         field = param.initializer()[0]
     history = {k: [] for k in ('dH', 'exp_mdH', 'acc', 'plaq', 'topo')}
     out = open(logfile, 'w') if logfile else None
-    if use_graph is None:
-        use_graph = os.environ.get('FTHMC_RUN_GRAPH', '1') not in ('', '0')
+    use_graph = run_graph_default() if use_graph is None else use_graph
 
     def put(s):
         if out is not None:
@@ -418,35 +415,35 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
         if verbose:
             print(s, end='', flush=True)
 
-    def line(k, dH, exp_mdH, acc, plaq, topo):
-        return (f'Traj: {k:4}  {"ACCEPT" if acc else "REJECT"}  dH: {dH:< 12.8}  '
-                f'exp(-dH): {exp_mdH:< 12.8}  plaq: {plaq:< 12.8}  topo: {topo:< 3.3}\n')
+    def record(k, dH, exp_mdH, acc, plaq, topo, hits=None):
+        """trajectory k into the history and the log; hits: (applied charge, accepted hits) of the instanton hits behind it"""
+        for key, val in zip(history, (dH, exp_mdH, float(acc), plaq, topo)):
+            history[key].append(val)
+        if hits is not None:
+            history.setdefault('inst_dq', []).append(int(hits[0]))
+            history.setdefault('inst_acc', []).append(hits[1] / instanton)
+        put(f'Traj: {k:4}  {"ACCEPT" if acc else "REJECT"}  dH: {dH:< 12.8}  '
+            f'exp(-dH): {exp_mdH:< 12.8}  plaq: {plaq:< 12.8}  topo: {topo:< 3.3}\n')
     try:
         S, Q, plaq = ops.wilson_action_charge(_batched(field), param.beta)
         put(f'Initial configuration:  plaq: {float(plaq[0])}  topo: {float(Q[0])} {tuple(field.shape)}\n')
         ntot = param.nrun * param.ntraj
         if use_graph and field.is_cuda and ntot > 0:
-            field, rows = _ft_run_captured(param, flow, field, ntot, integrator=integrator, instanton=instanton)
-            for k, (dH, acc, plaq_, topo, exp_mdH, *inst) in enumerate(rows.tolist()):
-                for key, val in zip(history, (dH, exp_mdH, float(acc > 0.5), plaq_, topo)):
-                    history[key].append(val)
-                if instanton:
-                    history.setdefault('inst_dq', []).append(int(inst[0]))
-                    history.setdefault('inst_acc', []).append(inst[1] / instanton)
-                put(line(k + 1, dH, exp_mdH, acc > 0.5, plaq_, topo))
+            field, cols = _ft_run_captured(param, flow, field, ntot, integrator=integrator, instanton=instanton)
+            c = {name: col.reshape(-1).tolist() for name, col in cols.items()}
+            for k in range(ntot):
+                record(k + 1, c['dH'][k], c['exp_mdH'][k], c['acc'][k] > 0.5, c['plaq'][k], c['Q'][k],
+                       (c['k'][k], c['nacc'][k]) if instanton else None)
         else:
-            for n in range(param.nrun):
-                for i in range(param.ntraj):
-                    dH, exp_mdH, acc, field_run = ft_hmc(param, flow, field.reshape((1,) + tuple(field.shape[-3:])), integrator=integrator)
-                    if instanton:
-                        field_run, ik, ina = instanton_hit(param, field_run, instanton)
-                        history.setdefault('inst_dq', []).append(int(ik[0]))
-                        history.setdefault('inst_acc', []).append(int(ina[0]) / instanton)
-                    field = field_run[0]
-                    S, Q, plaq = ops.wilson_action_charge(field_run, param.beta)
-                    for k, val in zip(history, (dH, exp_mdH, float(bool(acc)), float(plaq[0]), float(Q[0]))):
-                        history[k].append(val)
-                    put(line(n * param.ntraj + i + 1, dH, exp_mdH, bool(acc), float(plaq[0]), float(Q[0])))
+            for k in range(ntot):
+                dH, exp_mdH, acc, field_run = ft_hmc(param, flow, field.reshape((1,) + tuple(field.shape[-3:])), integrator=integrator)
+                hits = None
+                if instanton:
+                    field_run, ik, ina = instanton_hit(param, field_run, instanton)
+                    hits = (ik[0], int(ina[0]))
+                field = field_run[0]
+                S, Q, plaq = ops.wilson_action_charge(field_run, param.beta)
+                record(k + 1, dH, exp_mdH, bool(acc), float(plaq[0]), float(Q[0]), hits)
     finally:
         if out is not None:
             out.close()
@@ -454,10 +451,9 @@ def ft_run(param, flow, field: Optional[torch.Tensor] = None, logfile: Optional[
 
 
 def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1e-12, integrator: str = 'leapfrog', instanton: int = 0):
-    """the loop of ft_run as one captured sequence per trajectory -> (final field [2, L, L], rows [ntot, 5 or 7] on the host).
-    Row layout: dH, acc, plaq, Q, exp(-dH) -- 5 columns with instanton = 0; with instanton > 0 columns 5 and 6 follow: the applied
-    charge k and the accepted hits."""
-    from ..graph_loop import GraphLoop
+    """the loop of ft_run as one captured sequence per trajectory -> (final field [2, L, L], {name: [ntot, 1]} on the host) of the
+    row dH, acc, plaq, Q, exp_mdH and, with instanton > 0, the applied charge k and the accepted hits nacc."""
+    from ..graph_loop import GraphLoop, Row
     dev = field.device
     fs = field.detach().reshape((1,) + tuple(field.shape[-3:])).clone()
     L = fs.shape[-1]
@@ -467,14 +463,13 @@ def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1
     wkey = ('ft_run', id(flow), w.data_ptr(), w._version, weights_generation(w), time.monotonic_ns())
     v = torch.empty_like(fs)
     u = torch.empty(1, dtype=torch.float64, device=dev)
-    row = torch.empty(7 if instanton else 5, dtype=torch.float64, device=dev)
+    row = Row(dev, dH=1, acc=1, plaq=1, Q=1, exp_mdH=1, k=1 if instanton else 0, nacc=1 if instanton else 0)
     if instanton:
         iseeds = torch.empty(1, dtype=torch.int64, device=dev)
         iout = {'x': fs, 'k': torch.empty(1, dtype=torch.int32, device=dev), 'nacc': torch.empty(1, dtype=torch.int32, device=dev)}
-    res = {'x_new': torch.empty_like(fs), 'dH': row[0:1], 'acc': row[1:2], 'plaq': torch.empty(1, dtype=torch.float64, device=dev),
-           'Q': torch.empty(1, dtype=torch.float64, device=dev), 'H0': torch.empty(1, dtype=torch.float64, device=dev),
-           'H1': torch.empty(1, dtype=torch.float64, device=dev)}
-    obs = {'S': torch.empty(1, dtype=torch.float64, device=dev), 'Q': row[3:4], 'plaq': row[2:3]}
+    res = {'x_new': torch.empty_like(fs), 'dH': row['dH'], 'acc': row['acc'],
+           **{k: torch.empty(1, dtype=torch.float64, device=dev) for k in ('plaq', 'Q', 'H0', 'H1')}}
+    obs = {'S': torch.empty(1, dtype=torch.float64, device=dev), 'Q': row['Q'], 'plaq': row['plaq']}
 
     def enqueue():
         x = ops.flow_reverse(fs, w, nl, act, tol=tol, wkey=wkey)[0]      # x = F^-1(field)
@@ -485,16 +480,16 @@ def _ft_run_captured(param, flow, field: torch.Tensor, ntot: int, tol: float = 1
         if instanton:
             torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, device=dev, out=iseeds)
             ops.instanton_hit(fs, param.beta, iseeds, n_hit=instanton, out=iout)
-            row[5:6].copy_(iout['k'])
-            row[6:7].copy_(iout['nacc'])
+            row['k'].copy_(iout['k'])
+            row['nacc'].copy_(iout['nacc'])
         ops.wilson_action_charge(fs, param.beta, out=obs)
-        torch.exp(torch.neg(row[0:1]), out=row[4:5])
-    loop = GraphLoop(enqueue, row, use_graph=True)
+        torch.exp(torch.neg(row['dH']), out=row['exp_mdH'])
+    loop = GraphLoop(enqueue, row.flat, use_graph=True)
     for k in range(ntot):
         loop.step()
-    rows = loop.rows()
+    cols = row.split(loop.rows())
     loop.join()
-    return fs[0].clone(), rows
+    return fs[0].clone(), cols
 
 
 def flow_resize(flow: nn.ModuleList, lat_new):

@@ -338,7 +338,7 @@ def test_captured_run_equals_the_eager_loop():
         ft = _ft(L, nl, 'force_gradient', B=B)
         torch.manual_seed(5); torch.cuda.manual_seed(5)
         h = ft.run(x0.clone(), nprint=0, num_trajs=n, batch=True, use_graph=(mode == 'graph'))
-        assert (ft._loop is not None and ft._loop['loop'].captured) == (mode == 'graph')
+        assert ft.captured == (mode == 'graph')
         out[mode] = ({k: [t.clone() for t in h[k]] for k in ('acc', 'dh', 'exp_mdh', 'plaq', 'q', 'dq')}, ft.x_last.clone())
     for k, a in out['graph'][0].items():
         b = out['eager'][0][k]

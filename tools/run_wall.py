@@ -30,5 +30,5 @@ for L, beta, nl, B, n in shapes:
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     acc = float(torch.stack([torch.as_tensor(t, dtype=torch.float64).mean() for t in h['acc']]).mean())
     print(json.dumps({'L': L, 'beta': beta, 'n_layers': nl, 'chains': B, 'trajectories': n, 'ms_per_trajectory': round(dt / n * 1e3, 4), 'host_ms_per_trajectory': round(host_idle * 1e3, 4),
-                      'host_ms_per_trajectory_queue_full': round(host / n * 1e3, 4), 'captured': bool(ft._loop is not None and ft._loop['loop'].captured),
+                      'host_ms_per_trajectory_queue_full': round(host / n * 1e3, 4), 'captured': ft.captured,
                       'chain_steps_per_s': round(B * 10 * n / dt, 1), 'acceptance': round(acc, 3)}), flush=True)
