@@ -128,7 +128,14 @@ SIGNATURES['fthmc_meta_trajectory'] = [_D, _D, _D, c_int, c_int, c_double, c_dou
 SIGNATURES['fthmc_meta_deposit'] = [_D, c_int, c_int, c_int, c_double, c_double, _D, _P]      # qm, B, G, nb, qmax, w, vtab, stream
 SIGNATURES['fthmc_meta_force'] = [_D, c_int, c_int, c_double] + _MT + [_D, _P]                # x, B, L, beta, <table>, F, stream
 SIGNATURES['fthmc_meta_action'] = [_D, c_int, c_int, c_double] + _MT + [_D, _D, _D, _P]       # ..., S, qm, vb, stream
-_RESTYPE = {'fthmc_meta_ws_bytes': c_size_t, 'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
+# metadynamics through the flow: x, (v, u,) w, arch, n_layers, B, L, act, beta, (dt, nstep, integrator,) <table>, outputs,
+# ws, ws_bytes, stream, weights_version
+SIGNATURES['fthmc_ft_meta_ws_bytes'] = [_A, c_int, c_int, c_int]
+SIGNATURES['fthmc_ft_meta_trajectory_v'] = ([_D, _D, _D, _D, _A, c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_int] + _MT +
+                                            [_D] * 11 + [_P, c_size_t, _P, c_uint64])
+SIGNATURES['fthmc_ft_meta_force_v'] = [_D, _D, _A, c_int, c_int, c_int, c_int, c_double] + _MT + [_D, _P, c_size_t, _P, c_uint64]
+SIGNATURES['fthmc_ft_meta_action_v'] = [_D, _D, _A, c_int, c_int, c_int, c_int, c_double] + _MT + [_D, _D, _D, _D, _P, c_size_t, _P, c_uint64]
+_RESTYPE = {'fthmc_ft_meta_ws_bytes': c_size_t, 'fthmc_meta_ws_bytes': c_size_t, 'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None
 

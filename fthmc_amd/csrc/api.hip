@@ -127,16 +127,24 @@ int eval_action(const Ctx& C, const double* x, const WS& w, int nl, int B, int L
     return FTHMC_OK;
 }
 
+// The bias V(Q_m) of the flowed field (metadynamics) as force_gp and ft_md_ws take it: the table and sums[B][2]
+struct FlowBias { MetaTab T; double* sums; };
+
 // Plaquette-gradient field of sum_b S_eff (scaled): gp = scale*beta*sin P(F(x)) + sum_l gP_l,
 // with dL/dlogJ = glogj.  gw != null also accumulates weight gradients (training).
 // beta_b (optional): per-chain beta in place of beta_scaled (the per-chain-beta trajectories: fthmc_*_pb)
+// bias (optional): the seed is beta sin P + c_b cos P of the flowed field, c_b from the chain's sin sum (launch_meta_sums, launch_meta_gp)
 int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, int act, double beta_scaled,
-             double glogj, double* gw, hipStream_t s, bool have_forward = false, const double* beta_b = nullptr) {
+             double glogj, double* gw, hipStream_t s, bool have_forward = false, const double* beta_b = nullptr,
+             const FlowBias* bias = nullptr) {
+    auto seed = [&](double* gp) {
+        if (!bias) return launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gp, s, beta_b);
+        FT_TRY(launch_meta_sums(phys_field(x, w, nl), B, L, bias->sums, s));
+        return launch_meta_gp(phys_field(x, w, nl), B, L, beta_scaled, bias->sums, bias->T, gp, s);
+    };
     if (C.gen()) {                                // any other net shape (flow_generic.hip)
         if (nl > 0 && !have_forward) FT_TRY(sweep_forward(C, x, w, nl, B, L, act, nullptr, s, true));
-        return gen_backward<double>(C, gen_ws(C, w, B, L), nl, B, L, act, nullptr, glogj, gw, [&](double* gp) {
-            return launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gp, s, beta_b);
-        });
+        return gen_backward<double>(C, gen_ws(C, w, B, L), nl, B, L, act, nullptr, glogj, gw, seed);
     }
     // MFMA path without weight gradients: the forward sweep stashes act'(z1), act'(z2), s per site
     // and the backward kernels read them back instead of recomputing the network
@@ -148,7 +156,7 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
     // stash path: gather-form backward, gP ping-pongs between two fields and ends in w.gp
     double* gcur = (stash && (nl & 1)) ? w.gp2 : w.gp;
     double* galt = gcur == w.gp ? w.gp2 : w.gp;
-    FT_TRY(launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gcur, s, beta_b));
+    FT_TRY(seed(gcur));
     // training on the tiled-exactly shapes: the layer's backward and its weight gradients in ONE kernel (flow_bwd_train.hip: the
     // pre-activation gradients never leave LDS), one partial per workgroup
     const bool fused = gw && train && fused_train_bwd(C.A, B, L);
@@ -191,12 +199,13 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
 // in w.xa / w.va.  xreg (optional): regularize(result x), written by the last kick (the end point of a trajectory,
 // ipynb/ft_hmc.py:426) -- it may be `xshift` itself: nothing reads the shifted field once the kick behind it has its gP.
 int ft_md_ws(const Ctx& C, const double* x, const double* v, const WS& w, int nl, int B, int L, int act, double beta,
-             const Sched& sc, hipStream_t s, double* xshift, double* xreg = nullptr, const double* beta_b = nullptr) {
+             const Sched& sc, hipStream_t s, double* xshift, double* xreg = nullptr, const double* beta_b = nullptr,
+             const FlowBias* bias = nullptr) {
     FT_TRY(launch_axpy_copy(x, v, sc.b0, w.xa, w.va, w.n2, s));
     const double* xe = w.xa;                                               // where this stage's force is evaluated
     for (int it = 0; it < sc.n; ++it) {
         const SchedStage st = sc.stage(it);
-        FT_TRY(force_gp(C, xe, w, nl, B, L, act, beta, -1.0, nullptr, s, false, beta_b));
+        FT_TRY(force_gp(C, xe, w, nl, B, L, act, beta, -1.0, nullptr, s, false, beta_b, bias));
         if (st.kind == FT_STAGE_SHIFT) {
             FT_TRY(launch_shift_from_gp(w.gp, w.xa, xshift, B, L, st.a, s));
             xe = xshift;
@@ -469,6 +478,113 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
         if (Q && hipMemcpyAsync(Q, sel + 2 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
             return FTHMC_ERR_LAUNCH;
     }
+    return FTHMC_OK;
+}
+
+// ---------------------------------------------------------------- metadynamics through the flow (no reference counterpart)
+// The workspace of the fthmc_ft_meta_* calls: the first-order layout of the call's shape and behind it sums[B][2].  The per-chain rows
+// of the two ends live in W.vb, the momentum ping-pong field no flowed sequence touches (2 L^2 >= 32 rows of B): five rows per end
+// and for the selected one, (S_eff unbiased, plaq, Q, Q_m) and V behind them where launch_meta_energy leaves it.
+struct FMWS { WS W; double* sums; size_t total; };
+FMWS ft_meta_layout(const FlowArch& A, Carver& c, int B, int L, int nl) {
+    FMWS m{};
+    m.W = ws_layout(A, c, B, L, nl);
+    if (m.W.total == 0) return m;
+    m.sums = c.take((size_t)2 * B);
+    m.total = c.total();
+    return m;
+}
+// What every fthmc_ft_meta_* call refuses, in the ABI's order -- FTHMC_ERR_ARG (check_ft_meta_args; FTHMC_ERR_UNSUPPORTED for the
+// activation behind it), FTHMC_ERR_UNSUPPORTED, the workspace -- and what it opens: the context, the workspace, the weights.
+// seq_always: the force and action entry points, which never take the one-launch path.
+int check_ft_meta_args(bool ptrs_ok, const double* w, int nl, int B, int L, int act, const double* vtab, int G, int nb, double qmax,
+                       double wall) {
+    if (!ptrs_ok || (nl > 0 && !w) || bad_shape(B, L) || nl < 0 || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall))
+        return FTHMC_ERR_ARG;
+    return act < 0 || act > 2 ? FTHMC_ERR_UNSUPPORTED : FTHMC_OK;
+}
+int open_ft_meta_call(const double* w, const fthmc_arch_t* arch, int nl, int B, int L, bool seq_always, void* ws, size_t ws_bytes,
+                      void* stream, uint64_t wver, Ctx* C, FMWS* M) {
+    FT_TRY(open_call(arch, stream, C));
+    if ((seq_always || !C->small(L, nl)) && B > META_SEQ_MAX_B) return FTHMC_ERR_UNSUPPORTED;
+    if (C->A.is_default() && nl > 0 && B > (1 << 20)) return FTHMC_ERR_UNSUPPORTED;     // (open_ws: the default net's kernels)
+    Carver c(ws, ws_bytes);
+    *M = ft_meta_layout(C->A, c, B, L, nl);
+    FT_TRY(check_ws(M->total, ws, ws_bytes));
+    return use_weights(*C, w, nl, M->W.wint, wver);
+}
+
+// The biased flowed trajectory (FTHMC_MODE_MD): ft_trajectory_call's sequence with the bias in every force (ft_md_ws' FlowBias) and
+// V(Q_m) of the physical field added to either energy; launch_metropolis selects Q_m with the triple.  The carried state is
+// TABLE-FREE, [4][B] = (S_eff unbiased, plaq, Q, Q_m): V of a carried Q_m is looked up in the table of this call.
+int ft_meta_trajectory_call(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int nl, int B,
+                            int L, int act, double beta, double dt, int nstep, int integrator, const double* vtab, int G, int nb,
+                            double qmax, double wall, double* x_new, double* dH, double* acc, double* H0, double* H1, double* plaq,
+                            double* Q, double* qm_out, double* vb_out, const double* state_in, double* state_out, void* ws,
+                            size_t ws_bytes, void* stream, uint64_t wver) {
+    FT_TRY(check_ft_meta_args(x && v && u && x_new && nstep >= 1, w, nl, B, L, act, vtab, G, nb, qmax, wall));
+    const bool leap = integrator == FTHMC_INT_LEAPFROG;
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    Ctx C; FMWS M;
+    FT_TRY(open_ft_meta_call(w, arch, nl, B, L, false, ws, ws_bytes, stream, wver, &C, &M));
+    const WS& W = M.W;
+    const hipStream_t s = C.s;
+    const FlowBias bias{MetaTab{vtab, B / G, nb, qmax, wall}, M.sums};
+    const MetaTab& T = bias.T;
+    if (C.small(L, nl)) {                                            // the whole trajectory in one launch (flow_small.hip BIAS)
+        SmallArgs a = small_args(x, W, nl, B, act, beta, 3);
+        a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
+        a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
+        return launch_ft_small_meta(a, sc, T, qm_out, vb_out, L, s);
+    }
+    double* K = W.scal + (size_t)SC_K * B;
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    double* old = W.vb;                                              // rows 0 .. 3 the state, row 4 V
+    double* neu = W.vb + (size_t)5 * B;
+    double* sel = state_out ? state_out : W.vb + (size_t)10 * B;
+    // V(Q_m) into an end's energy and Q_m into its fourth row: of the field (sums) or of the carried state
+    auto add_bias = [&](const double* xphys, double* rows, double* h) {
+        if (!xphys) return launch_meta_energy_qm(rows + (size_t)3 * B, B, T, h, nullptr, s);
+        FT_TRY(launch_meta_sums(xphys, B, L, M.sums, s));
+        return launch_meta_energy(M.sums, B, T, h, rows + (size_t)3 * B, s);
+    };
+    if (state_in && hipMemcpyAsync(old + (size_t)3 * B, state_in + (size_t)3 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
+    const bool tuned = C.A.is_default() && nl > 0;
+    if (tuned) {                                                     // ft_trajectory_call's tuned branch
+        const int np = flow_fwd_geom(C.mfma).ntiles(L);
+        if (!state_in) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, nullptr, s, false, false, true));
+        FT_TRY(launch_traj_energy(phys_field(x, W, nl), B, L, beta, W.lj_part, np, nl, state_in, v, old, h0, s));
+        FT_TRY(add_bias(state_in ? nullptr : phys_field(x, W, nl), old, h0));
+        FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, nullptr, &bias));
+        FT_TRY(sweep_forward(C, W.xb, W, nl, B, L, act, nullptr, s, false, false, true));
+        FT_TRY(launch_traj_energy(phys_field(W.xb, W, nl), B, L, beta, W.lj_part, np, nl, nullptr, W.va, neu, h1, s));
+        FT_TRY(add_bias(phys_field(W.xb, W, nl), neu, h1));
+    } else {                                                         // other net shapes, no layers: its general branch
+        if (state_in) {
+            if (hipMemcpyAsync(old, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+        } else {
+            FT_TRY(eval_action(C, x, W, nl, B, L, act, beta, old, nullptr, old + B, old + 2 * B, s));
+        }
+        FT_TRY(launch_kinetic(v, B, L, K, s));
+        FT_TRY(launch_lincomb(old, 1.0, K, 0.5, 0.0, h0, B, s));
+        FT_TRY(add_bias(state_in ? nullptr : phys_field(x, W, nl), old, h0));
+        if (leap) {                                                   // as the unbiased leapfrog: a launch of its own regularizes
+            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, nullptr, nullptr, nullptr, &bias));
+            FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 1, s));
+        } else {
+            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, nullptr, &bias));
+        }
+        FT_TRY(eval_action(C, W.xb, W, nl, B, L, act, beta, neu, nullptr, neu + B, neu + 2 * B, s));
+        FT_TRY(launch_kinetic(W.va, B, L, K, s));
+        FT_TRY(launch_lincomb(neu, 1.0, K, 0.5, 0.0, h1, B, s));
+        FT_TRY(add_bias(phys_field(W.xb, W, nl), neu, h1));
+    }
+    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 4, s, plaq, Q));
+    if (qm_out && hipMemcpyAsync(qm_out, sel + (size_t)3 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    if (vb_out) FT_TRY(launch_meta_energy_qm(sel + (size_t)3 * B, B, T, nullptr, vb_out, s));
     return FTHMC_OK;
 }
 
@@ -1009,6 +1125,49 @@ int fthmc_meta_action(const double* x, int B, int L, double beta, const double* 
                       double* qm, double* vb, void* stream) {
     if (!x || bad_shape(B, L) || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall)) return FTHMC_ERR_ARG;
     return launch_meta_action(x, B, L, beta, MetaTab{vtab, B / G, nb, qmax, wall}, S, qm, vb, ft_stream(stream));
+}
+
+// Metadynamics through the flow: the checks and the workspace are open_ft_meta_call's
+size_t fthmc_ft_meta_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
+    Ctx C; Carver c;
+    if (B <= 0 || L <= 0 || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
+    return ft_meta_layout(C.A, c, B, L, n_layers).total * sizeof(double);
+}
+int fthmc_ft_meta_trajectory_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
+                               int B, int L, int act, double beta, double dt, int nstep, int integrator, const double* vtab, int G,
+                               int nb, double qmax, double wall, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                               double* plaq, double* Q, double* qm_out, double* vb_out, const double* state_in, double* state_out,
+                               void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
+    return ft_meta_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, dt, nstep, integrator, vtab, G, nb, qmax, wall, x_new, dH,
+                                   acc, H0, H1, plaq, Q, qm_out, vb_out, state_in, state_out, ws, ws_bytes, stream, weights_version);
+}
+int fthmc_ft_meta_force_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
+                          const double* vtab, int G, int nb, double qmax, double wall, double* F, void* ws, size_t ws_bytes,
+                          void* stream, uint64_t weights_version) {
+    FT_TRY(check_ft_meta_args(x && F, w, n_layers, B, L, act, vtab, G, nb, qmax, wall));
+    Ctx C; FMWS M;
+    FT_TRY(open_ft_meta_call(w, arch, n_layers, B, L, true, ws, ws_bytes, stream, weights_version, &C, &M));
+    const FlowBias bias{MetaTab{vtab, B / G, nb, qmax, wall}, M.sums};
+    FT_TRY(force_gp(C, x, M.W, n_layers, B, L, act, beta, -1.0, nullptr, C.s, false, nullptr, &bias));
+    return launch_kick_from_gp(M.W.gp, nullptr, nullptr, F, B, L, 0.0, 0.0, C.s);
+}
+int fthmc_ft_meta_action_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
+                           const double* vtab, int G, int nb, double qmax, double wall, double* S_b, double* logdet, double* qm,
+                           double* vbias, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
+    FT_TRY(check_ft_meta_args(x != nullptr, w, n_layers, B, L, act, vtab, G, nb, qmax, wall));
+    Ctx C; FMWS M;
+    FT_TRY(open_ft_meta_call(w, arch, n_layers, B, L, true, ws, ws_bytes, stream, weights_version, &C, &M));
+    const WS& W = M.W;
+    const hipStream_t s = C.s;
+    const size_t row = (size_t)B * sizeof(double);
+    if (n_layers == 0 && logdet && hipMemsetAsync(logdet, 0, row, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    double* sb = S_b ? S_b : W.vb + (size_t)2 * B;                   // S_eff first, V added in place
+    FT_TRY(eval_action(C, x, W, n_layers, B, L, act, beta, sb, logdet, nullptr, nullptr, s));
+    FT_TRY(launch_meta_sums(phys_field(x, W, n_layers), B, L, M.sums, s));
+    FT_TRY(launch_meta_energy(M.sums, B, MetaTab{vtab, B / G, nb, qmax, wall}, sb, W.vb, s));      // W.vb: (Q_m, V), [2][B]
+    if (qm && hipMemcpyAsync(qm, W.vb, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    if (vbias && hipMemcpyAsync(vbias, W.vb + B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    return FTHMC_OK;
 }
 
 int fthmc_ft_trajectory(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,

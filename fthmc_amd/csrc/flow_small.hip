@@ -19,6 +19,7 @@
 // (fthmc/utils/qed_helpers.py:212-242), the leapfrog and accept step of ipynb/ft_hmc.py:394-435.
 #include "flow_bwd_common.h"
 #include "flow_transform.h"
+#include "meta_tab.h"
 #include <stdlib.h>
 
 namespace {
@@ -142,9 +143,27 @@ __device__ __forceinline__ ColdSched& cold_sched() {
 // with the device array beta_b[B] behind it: beta is ONE load per workgroup at the chain's index, and state_in / state_out are the
 // beta-free triple (log det J, sum cos P, Q)
 struct SmallArgsPB : SmallArgsSched { const double* beta_b; };
-template <bool SCHED, bool PB = false> struct SmallArgsOf { typedef SmallArgs type; };
-template <> struct SmallArgsOf<true, false> { typedef SmallArgsSched type; };
-template <> struct SmallArgsOf<true, true> { typedef SmallArgsPB type; };
+// The biased instance (k_ft_small<..., SCHED, false, BIAS>: metadynamics through the flow, fthmc_ft_meta_trajectory_v)
+// takes the schedule-driven block with the table behind it: the struct stays in the kernel arguments and is read where a sweep looks
+// the bias up; state_in / state_out are the table-free [4][B] (S_eff unbiased, plaq, Q, Q_m)
+struct SmallArgsMeta : SmallArgsSched { MetaTab T; double *qm_out, *vb_out; };
+typedef const __attribute__((address_space(4))) SmallArgsMeta ColdMeta;
+__device__ __forceinline__ ColdMeta& cold_meta() {
+    ColdMeta* p = (ColdMeta*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+// the table and the chain's row, read from the kernarg segment where they are used (scalar loads; nothing of it lives through a sweep)
+__device__ __forceinline__ MetaTab meta_tab(const double** row, int b) {
+    ColdMeta& M = cold_meta();
+    const MetaTab T{M.T.v, M.T.cpr, M.T.nb, M.T.qmax, M.T.wall};
+    *row = mt_row(T, b);
+    return T;
+}
+template <bool SCHED, bool PB = false, bool BIAS = false> struct SmallArgsOf { typedef SmallArgs type; };
+template <> struct SmallArgsOf<true, false, false> { typedef SmallArgsSched type; };
+template <> struct SmallArgsOf<true, true, false> { typedef SmallArgsPB type; };
+template <> struct SmallArgsOf<true, false, true> { typedef SmallArgsMeta type; };
 
 // the stash values a backward pass multiplies by, loaded one pass ahead
 struct BwdPre { double tcv[4 * NMIX], fcs, fsn, d2v[4], d1v[4]; };
@@ -689,6 +708,26 @@ template <int L, bool TRAIN> struct Chain {
         }
         lds_barrier();
     }
+    // the biased seed: gP = beta sin P + c cos P, c = V'(Q_m) / 2 pi of the chain's row at Q_m = sum sin P / 2 pi of
+    // the flowed field -- wilson_seed's one ft_sincos per site, a block sum and the wave-uniform lookup
+    __device__ void meta_seed(double beta) {
+        constexpr int N = G::N;
+        double sn_ = 0.0, cs_ = 0.0;
+        if (tid < N) ft_sincos(plaq_at(sm + G::X, tid), &sn_, &cs_);
+        const double ssum = ft_block_sum(sn_, sm + G::RED);
+        const double* row;
+        const MetaTab T = meta_tab(&row, chain());
+        double qm, V, c;
+        mt_bias_row(row, T, ssum, &qm, &V, &c);
+        if (tid < N) sm[G::GP + tid] = beta * sn_ + c * cs_;
+        lds_barrier();
+    }
+    // sum sin P of the flowed field in the seed's (and k_meta_sums') order of the four links; valid in every thread
+    __device__ double sin_sum() {
+        double sn_ = 0.0, cs_ = 0.0;
+        if (tid < G::N) ft_sincos(plaq_at(sm + G::X, tid), &sn_, &cs_);
+        return ft_block_sum(sn_, sm + G::RED);
+    }
     // action_charge's sums themselves (the per-chain-beta instance keeps C = sum cos P: the beta-free state)
     __device__ void action_sums(double& Cs, double& Q) {
         constexpr int N = G::N;
@@ -739,9 +778,13 @@ enum { SM_ACTION = 0, SM_FORCE = 1, SM_LEAPFROG = 2, SM_TRAJ = 3, SM_TRAIN = 4 }
 // of the generic kernel only: compiled out, config 2 runs 4 % faster (0.497 -> 0.477 ms per trajectory).
 //   PB:          the SCHED instance with beta = beta_b[b] (one load per workgroup) and the beta-free state: thread 0 keeps
 //                (log det J, sum cos P) of x and of the proposal in the first four doubles of the profiling slots (DBG is off)
-template <int L, bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false>
-__global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArgsOf<SCHED, PB>::type Aarg) {
+//   BIAS:        the SCHED instance under V(Q_m) of the flowed field: a FORCE sweep seeds with meta_seed, an EVAL sweep adds the
+//                sin P sum; thread 0 keeps (Q_m, V) of x and of the proposal in the same four slots, H = S_eff + K / 2 + V, and
+//                the carried triple stays unbiased (the state's fourth row is Q_m: V is looked up in the table of the call)
+template <int L, bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false, bool BIAS = false>
+__global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArgsOf<SCHED, PB, BIAS>::type Aarg) {
     static_assert(!PB || (SCHED && !DBG && !TRAIN), "the per-chain-beta instance is a schedule-driven trajectory");
+    static_assert(!BIAS || (SCHED && !PB && !DBG && !TRAIN), "the biased instance is a schedule-driven trajectory");
     using G = GS<L>;
     constexpr int N = G::N;
     __shared__ __attribute__((aligned(16))) double sm[G::SIZE];
@@ -783,6 +826,16 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
             }
         } else
         if (have_state && tid == 0) { const double* si = cold().state_in; stt[0] = si[b]; stt[1] = si[hot.B + b]; stt[2] = si[2 * hot.B + b]; }
+        if constexpr (BIAS) {
+            if (have_state && tid == 0) {                                  // the carried Q_m under the table of THIS call
+                const double qm = cold().state_in[3 * (size_t)hot.B + b];
+                const double* row;
+                const MetaTab T = meta_tab(&row, b);
+                double V, c;
+                mt_lookup(row, T.nb, T.qmax, T.wall, qm, &V, &c);
+                sm[G::PROF] = qm; sm[G::PROF + 1] = V;
+            }
+        }
         const double k0 = ft_block_sum(v0 * v0 + v1 * v1, red);
         if (tid == 0) stt[6] = k0;
     }
@@ -832,6 +885,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
             // the stash of this sweep was written by other threads of this workgroup: complete and visible before it is read
             __syncthreads();
             C.bwd_issue(nl - 1, C.pre);
+            if constexpr (BIAS) C.meta_seed(bscale); else
             C.wilson_seed(bscale);
             C.stamp(17);
             for (int l = nl - 1; l >= 0; --l) C.layer_bwd(l, cb, l > 0, l > 0 ? l - 1 : (it < last ? 0 : -1));
@@ -876,6 +930,17 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
                 double* st = stt + (it < 0 ? 0 : 3);
                 st[0] = S - ld; st[1] = (-S) / (beta * (double)N); st[2] = Q; stt[7] = ld;
             }
+            if constexpr (BIAS) {
+                const double ssum = C.sin_sum();
+                if (tid == 0) {
+                    const double* row;
+                    const MetaTab T = meta_tab(&row, b);
+                    double qm, V, c;
+                    mt_bias_row(row, T, ssum, &qm, &V, &c);
+                    double* keep = sm + G::PROF + (it < 0 ? 0 : 2);
+                    keep[0] = qm; keep[1] = V;
+                }
+            }
             C.stamp(19);
         }
     }
@@ -903,7 +968,8 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
     // ---- Metropolis (ipynb/ft_hmc.py:427-435)
     const double k1 = ft_block_sum(v0 * v0 + v1 * v1, red);
     if (tid == 0) {
-        const double h0 = stt[0] + 0.5 * stt[6], h1 = stt[3] + 0.5 * k1;
+        double h0 = stt[0] + 0.5 * stt[6], h1 = stt[3] + 0.5 * k1;
+        if constexpr (BIAS) { h0 = h0 + sm[G::PROF + 1]; h1 = h1 + sm[G::PROF + 3]; }
         const double d = h1 - h0;
         const bool ok = A.u[b] < exp(-d);
         if (A.dH) A.dH[b] = d;
@@ -916,6 +982,13 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
             if (A.state_out) { A.state_out[b] = keep[0]; A.state_out[A.B + b] = keep[1]; A.state_out[2 * A.B + b] = sel[2]; }
         } else
         if (A.state_out) { A.state_out[b] = sel[0]; A.state_out[A.B + b] = sel[1]; A.state_out[2 * A.B + b] = sel[2]; }
+        if constexpr (BIAS) {
+            const double* keep = sm + G::PROF + (ok ? 2 : 0);
+            ColdMeta& M = cold_meta();
+            if (A.state_out) A.state_out[3 * (size_t)A.B + b] = keep[0];
+            if (M.qm_out) M.qm_out[b] = keep[0];
+            if (M.vb_out) M.vb_out[b] = keep[1];
+        }
         if (A.plaq) A.plaq[b] = sel[1];
         if (A.Q) A.Q[b] = sel[2];
         red[0] = ok ? 1.0 : 0.0;
@@ -943,13 +1016,13 @@ int get_small_path() {
 bool ft_small_shape(int L, int nl) { return nl >= 1 && (L == 8 || L == 12 || L == 16); }
 
 // one workgroup per chain: the instance of k_ft_small with these flags for the lattice size
-template <bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false>
-static int launch_instance(const typename SmallArgsOf<SCHED, PB>::type& a, int L, hipStream_t s) {
+template <bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false, bool BIAS = false>
+static int launch_instance(const typename SmallArgsOf<SCHED, PB, BIAS>::type& a, int L, hipStream_t s) {
     const dim3 grid(a.B), block(NT);
     switch (L) {
-        case 8: hipLaunchKernelGGL((k_ft_small<8, TRAIN, TRAJ, DBG, SCHED, PB>), grid, block, 0, s, a); break;
-        case 12: hipLaunchKernelGGL((k_ft_small<12, TRAIN, TRAJ, DBG, SCHED, PB>), grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_ft_small<16, TRAIN, TRAJ, DBG, SCHED, PB>), grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((k_ft_small<8, TRAIN, TRAJ, DBG, SCHED, PB, BIAS>), grid, block, 0, s, a); break;
+        case 12: hipLaunchKernelGGL((k_ft_small<12, TRAIN, TRAJ, DBG, SCHED, PB, BIAS>), grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((k_ft_small<16, TRAIN, TRAJ, DBG, SCHED, PB, BIAS>), grid, block, 0, s, a); break;
         default: return FTHMC_ERR_UNSUPPORTED;
     }
     FT_LAUNCH_CHECK(); return FTHMC_OK;
@@ -974,6 +1047,17 @@ int launch_ft_small_pb(const SmallArgs& a0, const Sched& sched, const double* be
     a.sched = sched;
     a.beta_b = beta_b;
     return launch_instance<false, false, false, true, true>(a, L, s);
+}
+
+// a trajectory of a schedule under the bias T (state_in / state_out: the table-free [4][B])
+int launch_ft_small_meta(const SmallArgs& a0, const Sched& sched, const MetaTab& T, double* qm_out, double* vb_out, int L, hipStream_t s) {
+    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
+    if (a0.mode != SM_TRAJ || a0.dbg || !T.v || T.cpr < 1 || T.nb < 2 || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
+    SmallArgsMeta a;
+    static_cast<SmallArgs&>(a) = a0;
+    a.sched = sched;
+    a.T = T; a.qm_out = qm_out; a.vb_out = vb_out;
+    return launch_instance<false, false, false, true, false, true>(a, L, s);
 }
 
 int launch_ft_small(const SmallArgs& a, int L, hipStream_t s) {

@@ -135,6 +135,8 @@ int launch_meta_trajectory(const double* x, const double* v, const double* u, in
 int launch_meta_sums(const double* x, int B, int L, double* sums, hipStream_t s);
 int launch_meta_gp(const double* x, int B, int L, double beta, const double* sums, const MetaTab& T, double* gp, hipStream_t s);
 int launch_meta_energy(const double* sums, int B, const MetaTab& T, double* H, double* qv, hipStream_t s);
+// the same at a carried charge qm[B] (no field): H[b] += V(qm[b]), vb[b] = V(qm[b]); each optional
+int launch_meta_energy_qm(const double* qm, int B, const MetaTab& T, double* H, double* vb, hipStream_t s);
 // the bias on its own
 int launch_meta_force(const double* x, int B, int L, double beta, const MetaTab& T, double* F, hipStream_t s);
 int launch_meta_action(const double* x, int B, int L, double beta, const MetaTab& T, double* S, double* qm, double* vb, hipStream_t s);
@@ -425,6 +427,9 @@ int launch_ft_small(const SmallArgs& a, int L, hipStream_t s);
 int launch_ft_small_sched(const SmallArgs& a, const Sched& sched, int L, hipStream_t s);   // mode 2 / 3 of a schedule (integrator.h)
 // mode 3 of a schedule with per-chain beta beta_b[B] (replica exchange); state_in / state_out: (log det J, sum cos P, Q)
 int launch_ft_small_pb(const SmallArgs& a, const Sched& sched, const double* beta_b, int L, hipStream_t s);
+// mode 3 of a schedule under the bias V(Q_m) of the flowed field (metadynamics); state_in / state_out: the table-free
+// [4][B] (S_eff unbiased, plaq, Q, Q_m); qm_out, vb_out (optional): Q_m and V(Q_m) of F(x_new)
+int launch_ft_small_meta(const SmallArgs& a, const Sched& sched, const MetaTab& T, double* qm_out, double* vb_out, int L, hipStream_t s);
 void set_small_path(int v);
 int get_small_path();
 // 0: VALU kernels everywhere; 1 (default): MFMA kernels for forward and backward-wrt-x

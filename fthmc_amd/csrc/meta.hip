@@ -11,57 +11,13 @@
 // energy / Metropolis kernels).  k_meta_deposit adds the walkers' hills to the table in chain order, without atomics.
 #include "common.h"
 #include "kernels.h"
+#include "meta_tab.h"
 
 namespace {
 
-using fthmc::MetaTab;
-
 constexpr int MT_NT = 1024, MT_MAXL = 64, MT_NSITE = MT_MAXL * MT_MAXL / MT_NT;     // wilson.hip TJ_NT, TJ_MAXL, TJ_NSITE
 
-// (fp contract off in the functions that hold the lookup's and the deposit's arithmetic, as in local.hip / topo.hip: which
-// products and sums become one FMA must not be left to the optimiser's view of different kernels)
-
-// t = (q + qmax) / delta -> inside: node i = floor(t) <= nb - 2 with t >= 0, f = t - i
-__device__ __forceinline__ bool mt_locate(double q, int nb, double qmax, int* i, double* f, double* delta) {
-#pragma clang fp contract(off)
-    const double d = (2.0 * qmax) / (double)(nb - 1);
-    const double t = (q + qmax) / d;
-    const double fl = floor(t);
-    *delta = d;
-    if (!(t >= 0.0) || !(fl <= (double)(nb - 2))) return false;                     // a NaN q is outside
-    *i = (int)fl;
-    *f = t - fl;
-    return true;
-}
-
-// V(q) and c = V'(q) / 2 pi of one table row (inside the table c is ONE quotient, dV / (delta 2 pi): the lookup sits on the critical
-// path of every stage of the one-launch trajectory)
-__device__ __forceinline__ void mt_lookup(const double* row, int nb, double qmax, double wall, double q, double* V, double* c) {
-#pragma clang fp contract(off)
-    int i; double f, delta;
-    if (mt_locate(q, nb, qmax, &i, &f, &delta)) {
-        const double v0 = row[i], dv = row[i + 1] - v0;
-        *V = v0 + f * dv;
-        *c = dv / (delta * FT_TWO_PI);
-    } else {
-        const double d = fabs(q) - qmax;
-        const double edge = q < 0.0 ? row[0] : row[nb - 1];
-        *V = edge + ((0.5 * wall) * d) * d;
-        *c = (q < 0.0 ? -(wall * d) : wall * d) / FT_TWO_PI;
-    }
-}
-__device__ __forceinline__ const double* mt_row(const MetaTab& T, int b) { return T.v + (size_t)(b / T.cpr) * T.nb; }
-
-// V and c = V' / 2 pi at the charge of a chain's sin sum, from the chain's row (wherever the caller keeps it)
-__device__ __forceinline__ void mt_bias_row(const double* row, const MetaTab& T, double ssum, double* qm, double* V, double* c) {
-#pragma clang fp contract(off)
-    const double q = ssum / FT_TWO_PI;
-    mt_lookup(row, T.nb, T.qmax, T.wall, q, V, c);
-    *qm = q;
-}
-__device__ __forceinline__ void mt_bias(const MetaTab& T, int b, double ssum, double* qm, double* V, double* c) {
-    mt_bias_row(mt_row(T, b), T, ssum, qm, V, c);
-}
+// (the table's lookup mt_locate / mt_lookup / mt_bias_row / mt_bias: meta_tab.h, shared with flow_small.hip)
 
 // sin and cos of the plaquette at site (i, j), the force kernels' order of the four links
 __device__ __forceinline__ void mt_sincos_site(const double* __restrict__ x0, const double* __restrict__ x1, int L, int i, int j,
@@ -119,6 +75,17 @@ __global__ void k_meta_energy(const double* __restrict__ sums, int B, MetaTab T,
     mt_bias(T, b, sums[2 * (size_t)b], &qm, &V, &c);
     if (H) H[b] = H[b] + V;
     if (qv) { qv[b] = qm; qv[(size_t)B + b] = V; }
+}
+
+// the same from a carried Q_m (the flowed trajectory's table-free state): H[b] += V(qm[b]), vb[b] = V(qm[b]); each optional
+__global__ void k_meta_energy_qm(const double* __restrict__ qm, int B, MetaTab T, double* __restrict__ H, double* __restrict__ vb) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double q = qm[b];
+    double V, c;
+    mt_lookup(mt_row(T, b), T.nb, T.qmax, T.wall, q, &V, &c);
+    if (H) H[b] = H[b] + V;
+    if (vb) vb[b] = V;
 }
 
 // ---------------------------------------------------------------- the bias on its own: force and action of one field
@@ -391,6 +358,10 @@ int launch_meta_gp(const double* x, int B, int L, double beta, const double* sum
 }
 int launch_meta_energy(const double* sums, int B, const MetaTab& T, double* H, double* qv, hipStream_t s) {
     hipLaunchKernelGGL(k_meta_energy, dim3((B + 255) / 256), dim3(256), 0, s, sums, B, T, H, qv);
+    FT_LAUNCH_CHECK(); return FTHMC_OK;
+}
+int launch_meta_energy_qm(const double* qm, int B, const MetaTab& T, double* H, double* vb, hipStream_t s) {
+    hipLaunchKernelGGL(k_meta_energy_qm, dim3((B + 255) / 256), dim3(256), 0, s, qm, B, T, H, vb);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_meta_force(const double* x, int B, int L, double beta, const MetaTab& T, double* F, hipStream_t s) {

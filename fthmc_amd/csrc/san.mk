@@ -38,7 +38,7 @@ san_integrator:
 # tests/hip/tempering_walk.cpp as a stand-alone program against the host-side sanitizer build of the library (built first when it
 # is missing or older than a source), the sanitizer runtimes linked in (nothing to preload), run by tests/test_tempering.py
 SANTEMP ?= $(SANDIR)/tempering_walk
-$(SANOUT): $(SRCS) common.h kernels.h integrator.h topo_int.h api_call.h ../../include/fthmc_hip.h san.mk
+$(SANOUT): $(SRCS) common.h kernels.h integrator.h topo_int.h meta_tab.h api_call.h ../../include/fthmc_hip.h san.mk
 	@$(MAKE) --no-print-directory -f san.mk san_build
 san_tempering: $(SANOUT)
 	mkdir -p $(dir $(SANTEMP))
@@ -87,3 +87,11 @@ san_meta: $(SANOUT)
 	mkdir -p $(dir $(SANMETA))
 	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
 	  ../../tests/hip/meta_walk.cpp -o $(SANMETA) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
+
+# The metadynamics-through-the-flow entry points (fthmc_ft_meta_ws_bytes, fthmc_ft_meta_trajectory_v, fthmc_ft_meta_force_v,
+# fthmc_ft_meta_action_v): tests/hip/ft_meta_walk.cpp in the same way, run by tests/test_ft_meta.py
+SANFTMETA ?= $(SANDIR)/ft_meta_walk
+san_ft_meta: $(SANOUT)
+	mkdir -p $(dir $(SANFTMETA))
+	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
+	  ../../tests/hip/ft_meta_walk.cpp -o $(SANFTMETA) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))

@@ -105,6 +105,25 @@ def run_meta(param: Param, x=None, potential: Optional[MetaPotential] = None, n_
     The seeds of trajectory t are ops.chain_seeds(param.seed, chain, t), formed on the device; momenta and accept uniforms come
     from ops.random_momenta; trajectory, deposit and measurement are captured once per phase (graph_loop) and replayed
     (`use_graph`, default on; FTHMC_RUN_GRAPH=0 turns it off): the same bits either way."""
+    return _run(param, x, potential, n_build, w, integrator, use_graph, None, 'silu')
+
+
+def run_ft_meta(param: Param, flow, x=None, potential: Optional[MetaPotential] = None, n_build: int = 0, w: float = 0.0,
+                integrator: str = 'leapfrog', use_graph: Optional[bool] = None, act: str = 'silu'):
+    """run_meta through a flow: field-transformation HMC under the bias in the charge of the PHYSICAL field F(x)
+    (ops.ft_meta_trajectory).  flow: what FieldTransformation takes, an nn.ModuleList of coupling layers (its weights
+    through utils.layers.flow_weights; act: their activation); an empty one is plain HMC under the bias.  The loop runs in the
+    latent field with the carried table-free state [4, B]; a deposit at the trajectory's own `qm` follows while the table is built;
+    plaq, Q, qm, vbias of the physical field come out of the trajectory itself, with no measurement launch.  One captured sequence
+    per phase, as run_meta.  -> (fields_arr, histories, potential) with run_meta's history keys; fields_arr[n] is the LATENT field,
+    as FieldTransformation.run returns it."""
+    if flow is None:
+        raise ValueError('run_ft_meta: a flow (a list of coupling layers, possibly empty) expected; run_meta is the driver without one')
+    return _run(param, x, potential, n_build, w, integrator, use_graph, flow, act)
+
+
+def _run(param, x, potential, n_build, w, integrator, use_graph, flow, act):
+    """the one loop behind run_meta (flow None) and run_ft_meta"""
     import torch
     from . import ops
     from .graph_loop import GraphLoop, Row, batched_start, chain_history, run_graph_default
@@ -120,6 +139,10 @@ def run_meta(param: Param, x=None, potential: Optional[MetaPotential] = None, n_
     if B % potential.groups:
         raise ValueError(f'run_meta: the potential has {potential.groups} rows, which do not divide the {B} chains')
     table = potential.table
+    if flow is not None:
+        from .utils.layers import flow_weights
+        nl = len(flow)
+        wflow = flow_weights(flow, dev) if nl else None
     histories, fields_arr = {}, []
     for n in range(param.nrun):
         t0 = time.time()
@@ -129,9 +152,30 @@ def run_meta(param: Param, x=None, potential: Optional[MetaPotential] = None, n_
         counter = torch.full((1,), n * param.ntraj, dtype=torch.int64, device=dev)      # trajectory t of the whole experiment
         row = Row(dev, acc=B, dH=B, plaq=B, Q=B, qm=B, vbias=B)
         out = {'x_new': xn, 'acc': row['acc'], 'dH': row['dH'], 'qm': row['qm'], 'vbias': row['vbias']}
-        q0 = ops.wilson_action_charge(xs, param.beta)[1].cpu().numpy()
+        if flow is not None:
+            # both state buffers exist before the capture; which one a trajectory reads is fixed per enqueue (they alternate by copy)
+            state = torch.empty(4, B, dtype=DTYPE, device=dev)
+            out.update(plaq=row['plaq'], Q=row['Q'], state=torch.empty(4, B, dtype=DTYPE, device=dev))
+            S0, _, plaq0, Q0 = ops.ft_action(xs, wflow, nl, param.beta, act)
+            _, _, qm0, _ = ops.ft_meta_action(xs, wflow, nl, param.beta, table, potential.qmax, potential.wall, act)
+            state.copy_(torch.stack([S0, plaq0, Q0, qm0]))
+            q0 = Q0.cpu().numpy()
+        else:
+            q0 = ops.wilson_action_charge(xs, param.beta)[1].cpu().numpy()
+
+        def enqueue_flow(deposit):
+            ops.chain_seeds(param.seed, 0, B, 0, counter=counter, advance=True, out=seeds)
+            ops.random_momenta(seeds, xs.shape, out_v=v, out_u=u)
+            ops.ft_meta_trajectory(xs, v, u, wflow, nl, param.beta, param.dt, param.nstep, table, potential.qmax, potential.wall, act,
+                                   integrator, out=out, state_in=state)
+            xs.copy_(xn)
+            state.copy_(out['state'])
+            if deposit:
+                ops.meta_deposit(out['qm'], table, potential.qmax, w)
 
         def enqueue(deposit):
+            if flow is not None:
+                return enqueue_flow(deposit)
             ops.chain_seeds(param.seed, 0, B, 0, counter=counter, advance=True, out=seeds)
             ops.random_momenta(seeds, xs.shape, out_v=v, out_u=u)
             ops.meta_trajectory(xs, v, u, param.beta, param.dt, param.nstep, table, potential.qmax, potential.wall, integrator=integrator,

@@ -81,6 +81,11 @@ def ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
     return int(_lib.load().fthmc_ws_bytes(_arch(arch), B, L, n_layers))
 
 
+def ft_meta_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
+    """Scratch of ft_meta_trajectory / ft_meta_force / ft_meta_action: ws_bytes and the two rows of chain sums behind it"""
+    return int(_lib.load().fthmc_ft_meta_ws_bytes(_arch(arch), B, L, n_layers))
+
+
 def vjp_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
     """Scratch of the second-order calls (ft_action_vjp, ft_force_vjp); 0 for a refused shape."""
     return int(_lib.load().fthmc_vjp_ws_bytes(_arch(arch), B, L, n_layers))
@@ -120,8 +125,11 @@ def _stream_buffer(t: torch.Tensor, need: int, family=None, zero_head: bool = Fa
     return buf.data_ptr(), buf.numel() * 8
 
 
-def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None, vjp: bool = False, force: bool = False):
-    if force:
+def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None, vjp: bool = False, force: bool = False,
+        meta: bool = False):
+    if meta:                                             # the flow workspace with the chain sums behind it: the same buffer, grown
+        need = ft_meta_ws_bytes(B, L, nl, arch)
+    elif force:
         need = train_force_ws_bytes(B, L, nl, arch)
         if need == 0:
             raise FthmcError(f'train_force_grad: shape B={B}, L={L}, {nl} layers is refused (fthmc_train_force_ws_bytes = 0)')
@@ -1117,6 +1125,95 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta, dt: float, nstep: int, act='s
     else:
         check(lib.fthmc_ft_trajectory_v(*head, float(beta), *tail, wv), 'fthmc_ft_trajectory')
     return out
+
+
+# ---------------------------------------------------------------- metadynamics through the flow
+def _meta_group_rows(table, B: int, edges):
+    """the table rows of the chain groups of `edges` -> [(row_lo, row_hi) or None (the whole table)]: with one row every group reads
+    it; otherwise a group must be whole rows (every edge a multiple of B / G), and is handed its own"""
+    G = 1 if table.dim() == 1 else table.shape[0]
+    if G == 1:
+        return [None] * (len(edges) - 1)
+    if G < 1 or B % G:
+        raise ValueError(f'meta table: {G} rows do not divide the {B} chains')
+    cpr = B // G
+    if any(e % cpr for e in edges):
+        raise ValueError(f'groups: the edges {tuple(edges)} split a table row ({cpr} chains per row): every chain group must be whole rows')
+    return [(edges[k] // cpr, edges[k + 1] // cpr) for k in range(len(edges) - 1)]
+
+
+def ft_meta_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int, table, qmax: float, wall: float = 0.0, act='silu',
+                       integrator='leapfrog', out: Optional[dict] = None, state_in: Optional[torch.Tensor] = None, groups: int = 1,
+                       arch=None, wkey=None, side_streams=None):
+    """One ftHMC trajectory per chain under the bias V(Q_m) of the PHYSICAL field F(x) (C ABI fthmc_ft_meta_trajectory_v; mode 'md')
+    -> dict(x_new, dH, acc, H0, H1, plaq, Q, qm, vbias, state): ft_trajectory's keys, qm / vbias = Q_m and V(Q_m) of F(x_new) under
+    the table the call ran on, and state [4, B] = (S_eff without the bias, plaq, Q, Q_m) of x_new.  The state is table-free: fed back
+    as `state_in` it stays valid across meta_deposit calls.  table, qmax, wall: as meta_trajectory.  groups, out, wkey, side_streams:
+    as ft_trajectory; with more than one table row every chain group must be whole rows.  Results do not depend on `groups`."""
+    ic = integrator_code(integrator)
+    x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
+    if u.numel() != B:
+        raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
+    if int(nstep) < 1:
+        raise ValueError(f'ft_meta_trajectory: nstep >= 1 expected, got {nstep}')
+    tab = _meta_table(table, B, qmax, wall)
+    edges = _group_edges(groups, B)
+    rows = _meta_group_rows(table, B, edges)                             # raises before anything is launched
+    w, ap, a = _wall(w, n_layers, arch)
+    if out is None:
+        out = {'x_new': torch.empty_like(x)}
+    for k in ('dH', 'acc', 'H0', 'H1', 'plaq', 'Q', 'qm', 'vbias'):
+        if k not in out:
+            out[k] = torch.empty(B, dtype=x.dtype, device=x.device)
+    if 'state' not in out:
+        out['state'] = torch.empty(4, B, dtype=x.dtype, device=x.device)
+    if state_in is not None:
+        state_in = _dev(state_in, 'state_in')
+        if state_in.numel() != 4 * B:
+            raise FthmcError(f'state_in: expected [4, {B}]')
+        state_in = state_in.reshape(4, B)
+    if len(edges) > 2:
+        parts = []
+        for (lo, hi, st) in _chain_groups(x.device, edges, side_streams):
+            r = rows[edges.index(lo)]
+            with torch.cuda.stream(st):
+                og = {k: t[lo:hi] for k, t in out.items() if k != 'state'}
+                sg = state_in[:, lo:hi].contiguous() if state_in is not None else None
+                ft_meta_trajectory(x[lo:hi], v[lo:hi], u[lo:hi], w, n_layers, beta, dt, nstep, table if r is None else table[r[0]:r[1]],
+                                   qmax, wall, act, integrator, og, sg, arch=a, wkey=wkey)
+                out['state'][:, lo:hi].copy_(og['state'])
+                parts.append(og)
+        return out
+    ws, nb = _ws(x, B, L, n_layers, arch=a, meta=True)
+    check(_lib.load().fthmc_ft_meta_trajectory_v(
+        _p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), float(beta), float(dt), int(nstep), ic, *tab, _p(out['x_new']),
+        _p(out['dH']), _p(out['acc']), _p(out['H0']), _p(out['H1']), _p(out['plaq']), _p(out['Q']), _p(out['qm']), _p(out['vbias']),
+        _p(state_in), _p(out['state']), ws, nb, _stream(x), weights_version(wkey)), 'fthmc_ft_meta_trajectory')
+    return out
+
+
+def ft_meta_force(x, w, n_layers: int, beta: float, table, qmax: float, wall: float = 0.0, act='silu', arch=None, wkey=None):
+    """F = dS_b / dx of S_b(x) = -beta sum cos P(F(x)) - log det J(x) + V(Q_m(F(x))) (C ABI fthmc_ft_meta_force_v), ft_force's sign"""
+    x = _field(x); B, _, L, _ = x.shape
+    tab = _meta_table(table, B, qmax, wall)
+    w, ap, a = _wall(w, n_layers, arch)
+    F = torch.empty_like(x)
+    ws, nb = _ws(x, B, L, n_layers, arch=a, meta=True)
+    check(_lib.load().fthmc_ft_meta_force_v(_p(x), _p(w), ap, n_layers, B, L, act_code(act), float(beta), *tab, _p(F), ws, nb, _stream(x),
+                                            weights_version(wkey)), 'fthmc_ft_meta_force')
+    return F
+
+
+def ft_meta_action(x, w, n_layers: int, beta: float, table, qmax: float, wall: float = 0.0, act='silu', arch=None, wkey=None):
+    """-> (S_b, logdet, Q_m, V(Q_m)) per chain, Q_m of the physical field F(x) (C ABI fthmc_ft_meta_action_v)"""
+    x = _field(x); B, _, L, _ = x.shape
+    tab = _meta_table(table, B, qmax, wall)
+    w, ap, a = _wall(w, n_layers, arch)
+    S, ld, qm, vb = (torch.empty(B, dtype=x.dtype, device=x.device) for _ in range(4))
+    ws, nb = _ws(x, B, L, n_layers, arch=a, meta=True)
+    check(_lib.load().fthmc_ft_meta_action_v(_p(x), _p(w), ap, n_layers, B, L, act_code(act), float(beta), *tab, _p(S), _p(ld), _p(qm),
+                                             _p(vb), ws, nb, _stream(x), weights_version(wkey)), 'fthmc_ft_meta_action')
+    return S, ld, qm, vb
 
 
 def train_grad(xi, w, n_layers: int, beta: float, act='silu', need_gw=True, groups: int = 1, _out=None, out_gw=None, arch=None):

@@ -520,6 +520,47 @@ int fthmc_meta_force(const double* x, int B, int L, double beta, const double* v
 int fthmc_meta_action(const double* x, int B, int L, double beta, const double* vtab, int G, int nb, double qmax, double wall,
                       double* S, double* qm, double* vb, void* stream);
 
+/* ---- Metadynamics ftHMC: the same bias through the flow.  Latent field x, physical field y = F(x) (n_layers coupling layers),
+ *     S_b(x) = -beta sum cos P(y) - log det J(x) + V(Q_m(y)),      H = S_b + sum v^2 / 2.
+ * Table, rows, lookup and wall as above.  The force with respect to x is fthmc_ft_force's backward sweep seeded with
+ * gP = beta sin P(y) + c cos P(y), c = V'(Q_m(y)) / 2 pi, in place of beta sin P(y).  Every output of a chain depends on the chain
+ * and its own table row only, never on B or on the chain's place in the batch.
+ * The reference has no counterpart to any of the four entry points below.
+ * What they refuse, in this order: a null x (v, u, x_new; F) / vtab, w null with n_layers > 0, B or L out of range, n_layers < 0,
+ * nstep < 1, G < 1 or B % G != 0, nb < 2 or nb > 65536, a qmax that is not finite and positive, a wall that is not finite and >= 0:
+ * FTHMC_ERR_ARG; an unknown activation or integrator, a refused arch, B > 65535 where the sequenced kernels run (they put the chain
+ * on grid y): FTHMC_ERR_UNSUPPORTED; then the workspace (FTHMC_ERR_WS) and the weights-version check.  Enqueue-only, capturable. */
+
+/* No reference counterpart.  Scratch of the three calls below: fthmc_ws_bytes(arch, B, L, n_layers) and behind it the two rows of
+ * chain sums (sum sin P, sum cos P), rounded like every region (a multiple of 256 bytes); 0 for refused arguments. */
+size_t fthmc_ft_meta_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers);
+
+/* No reference counterpart.  One biased flowed trajectory of every chain (FTHMC_MODE_MD only): H0, the MD of (integrator, dt,
+ * nstep) under the biased force, the end point regularized, H1, accept iff u[b] < exp(-(H1 - H0)).  x_new .. H1 as
+ * fthmc_ft_trajectory_int_v; plaq, Q, qm_out, vb_out [B]: of F(x_new), vb_out under the table of this call.  dH .. vb_out may be NULL.
+ * state_in / state_out (either may be NULL): [4][B] = (S_eff WITHOUT the bias, plaq, Q, Q_m) of x / of x_new.  The state is
+ * table-free: a chained call looks V(Q_m) up in the table it is given, so hills deposited between two calls leave it valid, and a
+ * chained call gives the bits of a stateless one at any table.
+ * L = 8, 12, 16 with the default net and the small path on: one launch (k_ft_small's biased instance); every other shape
+ * fthmc_ft_trajectory_int_v serves: its sequence with the biased seed in every force and V(Q_m) added to either energy.  With
+ * an all-zero table and no wall either gives the bits of fthmc_ft_trajectory_int_v. */
+int fthmc_ft_meta_trajectory_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
+                               int B, int L, int act, double beta, double dt, int nstep, int integrator, const double* vtab, int G,
+                               int nb, double qmax, double wall, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                               double* plaq, double* Q, double* qm_out, double* vb_out, const double* state_in /* [4][B] or NULL */,
+                               double* state_out /* [4][B] or NULL */, void* ws, size_t ws_bytes, void* stream,
+                               uint64_t weights_version);
+
+/* No reference counterpart.  The biased flowed force and action on their own, for tests and measurements (always the sequenced
+ * kernels): F[B][2][L][L] = dS_b / dx; per chain S_b, logdet = log det J, qm = Q_m(F(x)), vbias = V(Q_m) (each of the four may be
+ * NULL). */
+int fthmc_ft_meta_force_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
+                          const double* vtab, int G, int nb, double qmax, double wall, double* F, void* ws, size_t ws_bytes,
+                          void* stream, uint64_t weights_version);
+int fthmc_ft_meta_action_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
+                           const double* vtab, int G, int nb, double qmax, double wall, double* S_b, double* logdet, double* qm,
+                           double* vbias, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version);
+
 /* ---- training ------------------------------------------------------------ */
 /* Reverse-KL loss pieces and weight gradients for a fixed prior draw xi
  * (fthmc/train.py:191-210, fthmc/utils/samplers.py:40-56):
