@@ -276,103 +276,77 @@ int md_call(bool plain, const double* x, const double* v, const double* w, const
     return copy_pair(x_out, W.xa, v_out, W.va, W.n2, s);
 }
 
-// Plain HMC: H0, MD, H1, Metropolis -- the one sequence behind fthmc_hmc_trajectory, _int and _pb.  beta_b: per-chain beta
-// (null: the scalar `beta`; the kernels that take beta_b are handed beta = 0.0 beside it).
+// ---------------------------------------------------------------- metadynamics (meta.hip; no reference counterpart)
+// The table of a call, or FTHMC_ERR_ARG: what every fthmc_meta_* and fthmc_ft_meta_* call refuses about it.  `wall`: the wall's
+// stiffness (fthmc_meta_deposit: a hill's height, held to the same rule)
+inline int meta_tab(const double* vtab, int B, int G, int nb, double qmax, double wall, MetaTab* T) {
+    if (!vtab || G < 1 || B % G != 0 || nb < 2 || nb > 65536 || !isfinite(qmax) || !(qmax > 0.0) || !isfinite(wall) || !(wall >= 0.0))
+        return FTHMC_ERR_ARG;
+    *T = MetaTab{vtab, B / G, nb, qmax, wall};
+    return FTHMC_OK;
+}
+// The optional bias of a trajectory call: the table, the path the caller asked for (the plain sequence: fthmc_meta_trajectory) and
+// where Q_m and V(Q_m) of x_new go (each optional)
+struct BiasArg { MetaTab T; int path; double *qm_out, *vb_out; };
+
+// the sequenced paths launch the plain kernels' shapes (launch_kick_from_gp, launch_shift_from_gp, k_meta_gp: the chain on grid y)
+constexpr int META_SEQ_MAX_B = 65535;
+
+// Plain HMC: H0, MD, H1, Metropolis -- the one sequence behind fthmc_hmc_trajectory, _int and _pb and, with a bias, behind
+// fthmc_meta_trajectory.  beta_b: per-chain beta (null: the scalar `beta`; the kernels that take beta_b are handed beta = 0.0
+// beside it).  bias (optional): V(Q_m) in every force (ft_md_ws' FlowBias) and behind either energy, and the (Q_m, V) pairs of
+// the two ends through the Metropolis kernel beside the field; any L, x_new may be x on the sequenced path.
 int hmc_trajectory_call(const double* x, const double* v, const double* u, int B, int L, double beta, const double* beta_b, double dt,
-                        int nstep, int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                        int nstep, int integrator, const BiasArg* bias, double* x_new, double* dH, double* acc, double* H0, double* H1,
                         void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1) return FTHMC_ERR_ARG;
+    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1 || (bias && beta_b)) return FTHMC_ERR_ARG;
     const bool pb = beta_b != nullptr, leap = integrator == FTHMC_INT_LEAPFROG;
     if (pb) beta = 0.0;
     Sched sc;
     FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    Ctx C; WS W; FT_TRY(open_call(nullptr, stream, &C));
+    Ctx C; FT_TRY(open_call(nullptr, stream, &C));
     const hipStream_t s = C.s;
     // L <= 64 (x_new must not alias x): one persistent launch per trajectory, state in LDS / registers.  The scalar-beta leapfrog
-    // has a kernel of its own, the schedule-driven one serves every other integrator and per-chain beta with every integrator.
-    if (L <= 64 && C.mfma && x_new != x)
+    // has a kernel of its own, the schedule-driven one serves every other integrator and per-chain beta with every integrator,
+    // the biased one every integrator (path 1: the caller insists on it, 2: on the sequence).
+    const bool one_launch = L <= 64 && C.mfma && x_new != x;
+    if (bias) {
+        if (bias->path == 1 || (bias->path == 0 && one_launch))
+            return launch_meta_trajectory(x, v, u, B, L, beta, sc, bias->T, x_new, dH, acc, H0, H1, bias->qm_out, bias->vb_out, s);
+        if (B > META_SEQ_MAX_B) return FTHMC_ERR_UNSUPPORTED;
+    } else if (one_launch) {
         return leap && !pb ? launch_hmc_trajectory_fused(x, v, u, B, L, beta, dt, nstep, x_new, dH, acc, H0, H1, s)
                            : launch_hmc_trajectory_sched(x, v, u, B, L, beta, sc, x_new, dH, acc, H0, H1, s, beta_b);
-    FT_TRY(open_ws(C, ws, ws_bytes, B, L, 0, false, &W));
+    }
+    MWS M{};                                                         // unbiased: no sums, no pairs (null, 0 rows)
+    FT_TRY(bias ? open_meta_ws(C, ws, ws_bytes, B, L, 0, true, &M) : open_ws(C, ws, ws_bytes, B, L, 0, false, &M.W));
+    const WS& W = M.W;
+    const FlowBias fb{bias ? bias->T : MetaTab{}, M.sums};
     double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
-    auto energy = [&](const double* xf, const double* vf, double* h) {     // h = S_W(xf) + K(vf) / 2
+    auto energy = [&](const double* xf, const double* vf, double* h, double* qv) {     // h = S_W(xf) + K(vf) / 2 [+ V(Q_m(xf))]
         FT_TRY(launch_action_charge(xf, B, L, beta, S, nullptr, nullptr, s, nullptr, beta_b));
         FT_TRY(launch_kinetic(vf, B, L, K, s));
-        return launch_lincomb(S, 1.0, K, 0.5, 0.0, h, B, s);
-    };
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    FT_TRY(energy(x, v, h0));
-    double *xo = W.xb, *po = W.va;
-    if (leap) {                                                      // the fused launch_leap_step steps, then xr = regularize(x_)
-        FT_TRY(leapfrog_ws(x, v, W, B, L, beta, dt, nstep, &xo, &po, s, beta_b));
-        FT_TRY(launch_wrap(xo, xo, W.n2, 1, s));
-    } else {                                                         // the flowed schedule with zero layers: the shifted field
-        FT_TRY(ft_md_ws(C, x, v, W, 0, B, L, 0, beta, sc, s, W.xb, W.xb, beta_b));      // and then the regularized end point in W.xb
-    }
-    FT_TRY(energy(xo, po, h1));
-    return launch_metropolis(x, xo, u, h0, h1, B, L, 0, x_new, dH, acc, nullptr, nullptr, nullptr, 0, s);
-}
-
-// ---------------------------------------------------------------- metadynamics HMC (meta.hip; no reference counterpart)
-// what every fthmc_meta_* call refuses about the table
-inline bool bad_meta_table(const double* vtab, int B, int G, int nb, double qmax) {
-    return !vtab || G < 1 || B % G != 0 || nb < 2 || nb > 65536 || !isfinite(qmax) || !(qmax > 0.0);
-}
-inline bool bad_meta_weight(double w) { return !isfinite(w) || !(w >= 0.0); }      // the wall's stiffness, a hill's height
-
-// the sequenced path launches the plain kernels' shapes (launch_kick_from_gp, launch_shift_from_gp, k_meta_gp: the chain on grid y)
-constexpr int META_SEQ_MAX_B = 65535;
-
-// The workspace of the sequenced path: a first-order layout without layers, behind it sums[B][2] and the (Q_m, V) pairs of the
-// two ends and of the selected one, [2][B] each
-struct MWS { WS W; double *sums, *qv_old, *qv_new, *qv_sel; size_t total; };
-MWS meta_layout(Carver& c, int B, int L) {
-    MWS m{};
-    m.W = ws_layout(flow_arch_default(), c, B, L, 0);
-    if (m.W.total == 0) return m;
-    m.sums = c.take((size_t)2 * B);
-    m.qv_old = c.take((size_t)2 * B); m.qv_new = c.take((size_t)2 * B); m.qv_sel = c.take((size_t)2 * B);
-    m.total = c.total();
-    return m;
-}
-
-// The biased trajectory, sequenced: hmc_trajectory_call's H0, MD, H1, Metropolis with ft_md_ws' stages, the force of a stage from
-// the chain sums (launch_meta_sums) and the biased plaquette gradient (launch_meta_gp) in place of launch_wilson_gp, and V(Q_m)
-// added to either energy.  Any L; x_new may be x.
-int meta_trajectory_seq(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sc, const MetaTab& T,
-                        double* x_new, double* dH, double* acc, double* H0, double* H1, double* qm_out, double* vb_out,
-                        const MWS& M, hipStream_t s) {
-    const WS& W = M.W;
-    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
-    auto energy = [&](const double* xf, const double* vf, double* h, double* qv) {      // h = S_W(xf) + K(vf) / 2 + V(Q_m(xf))
-        FT_TRY(launch_action_charge(xf, B, L, beta, S, nullptr, nullptr, s));
-        FT_TRY(launch_kinetic(vf, B, L, K, s));
         FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h, B, s));
+        if (!bias) return FTHMC_OK;
         FT_TRY(launch_meta_sums(xf, B, L, M.sums, s));
-        return launch_meta_energy(M.sums, B, T, h, qv, s);
+        return launch_meta_energy(M.sums, B, fb.T, h, qv, s);
     };
     double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
     double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
     FT_TRY(energy(x, v, h0, M.qv_old));
-    FT_TRY(launch_axpy_copy(x, v, sc.b0, W.xa, W.va, W.n2, s));
-    const double* xe = W.xa;                                               // where this stage's force is evaluated
-    for (int it = 0; it < sc.n; ++it) {
-        const SchedStage st = sc.stage(it);
-        FT_TRY(launch_meta_sums(xe, B, L, M.sums, s));
-        FT_TRY(launch_meta_gp(xe, B, L, beta, M.sums, T, W.gp, s));
-        if (st.kind == FT_STAGE_SHIFT) {
-            FT_TRY(launch_shift_from_gp(W.gp, W.xa, W.xb, B, L, st.a, s));
-            xe = W.xb;
-        } else {                                                           // the last kick leaves the regularized end point in W.xb
-            FT_TRY(launch_kick_from_gp(W.gp, W.va, W.xa, nullptr, B, L, st.a, st.b, s, it == sc.n - 1 ? W.xb : nullptr));
-            xe = W.xa;
-        }
+    double *xo = W.xb, *po = W.va;
+    if (leap && !bias) {                                             // the fused launch_leap_step steps, then xr = regularize(x_)
+        FT_TRY(leapfrog_ws(x, v, W, B, L, beta, dt, nstep, &xo, &po, s, beta_b));
+        FT_TRY(launch_wrap(xo, xo, W.n2, 1, s));
+    } else {                                                         // the flowed schedule with zero layers: the shifted field
+        FT_TRY(ft_md_ws(C, x, v, W, 0, B, L, 0, beta, sc, s, W.xb, W.xb, beta_b, bias ? &fb : nullptr));      // and then the regularized end point in W.xb
     }
-    FT_TRY(energy(W.xb, W.va, h1, M.qv_new));
-    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, M.qv_old, M.qv_new, M.qv_sel, 2, s));
-    if (qm_out && hipMemcpyAsync(qm_out, M.qv_sel, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-    if (vb_out && hipMemcpyAsync(vb_out, M.qv_sel + B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    FT_TRY(energy(xo, po, h1, M.qv_new));
+    FT_TRY(launch_metropolis(x, xo, u, h0, h1, B, L, 0, x_new, dH, acc, M.qv_old, M.qv_new, M.qv_sel, bias ? 2 : 0, s));
+    if (!bias) return FTHMC_OK;
+    const size_t row = (size_t)B * sizeof(double);
+    if (bias->qm_out && hipMemcpyAsync(bias->qm_out, M.qv_sel, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    if (bias->vb_out && hipMemcpyAsync(bias->vb_out, M.qv_sel + B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     return FTHMC_OK;
 }
 
@@ -391,12 +365,32 @@ int pb_eval(const Ctx& C, const double* x, const WS& W, int nl, int B, int L, in
     return launch_pb_from_state(trip, beta_b, B, L, nl > 0, seff, nullptr, s);
 }
 
+// What every fthmc_ft_meta_* call refuses about its arguments -- FTHMC_ERR_ARG, the table included; FTHMC_ERR_UNSUPPORTED for the
+// activation behind it -- and what it then opens in the ABI's order: FTHMC_ERR_UNSUPPORTED, the workspace (the first-order layout
+// and sums[B][2] behind it), the weights.  seq_always: the force and action entry points, which never take the one-launch path.
+int check_ft_meta_args(bool ptrs_ok, const double* w, int nl, int B, int L, int act, const double* vtab, int G, int nb, double qmax,
+                       double wall, MetaTab* T) {
+    if (meta_tab(vtab, B, G, nb, qmax, wall, T) != FTHMC_OK) return FTHMC_ERR_ARG;
+    return check_flow_call(ptrs_ok, w, nl, B, L, act);
+}
+int open_ft_meta_call(const fthmc_arch_t* arch, void* stream, void* ws, size_t ws_bytes, const double* w, int nl, int B, int L,
+                      bool seq_always, uint64_t wver, Ctx* C, MWS* M) {
+    FT_TRY(open_call(arch, stream, C));
+    if ((seq_always || !C->small(L, nl)) && B > META_SEQ_MAX_B) return FTHMC_ERR_UNSUPPORTED;
+    if (C->A.is_default() && nl > 0 && B > (1 << 20)) return FTHMC_ERR_UNSUPPORTED;     // (open_ws: the default net's kernels)
+    FT_TRY(open_meta_ws(*C, ws, ws_bytes, B, L, nl, false, M));
+    return use_weights(*C, w, nl, M->W.wint, wver);
+}
+
 // The flowed trajectory: H0, MD, H1, Metropolis, plaq / Q of x_new -- the one sequence behind fthmc_ft_trajectory_v, _int_v and
-// _pb_v.  beta_b: per-chain beta (null: the scalar `beta`); the state triples are then BETA-FREE (log det J, sum cos P, Q)
-// instead of (S_eff, plaq, Q), and the kernels that take beta_b are handed beta = 0.0 beside it.
+// _pb_v and, with a bias, behind fthmc_ft_meta_trajectory_v.  beta_b: per-chain beta (null: the scalar `beta`); the state triples
+// are then BETA-FREE (log det J, sum cos P, Q) instead of (S_eff, plaq, Q), and the kernels that take beta_b are handed
+// beta = 0.0 beside it.  bias (optional, FTHMC_MODE_MD and scalar beta only): V(Q_m) of the physical field in every force
+// (ft_md_ws' FlowBias) and behind either end's energy; the state has a fourth row, Q_m, and is TABLE-FREE -- [4][B] = (S_eff
+// unbiased, plaq, Q, Q_m): V of a carried Q_m is looked up in the table of this call.
 int ft_trajectory_call(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int nl, int B,
                        int L, int act, double beta, const double* beta_b, double dt, int nstep, int integrator, int mode,
-                       double* x_new, double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
+                       const BiasArg* bias, double* x_new, double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
                        const double* state_in, double* state_out, void* ws, size_t ws_bytes, void* stream, uint64_t wver) {
     FT_TRY(check_flow_call(x && v && u && x_new && nstep >= 1, w, nl, B, L, act));
     const bool pb = beta_b != nullptr, leap = integrator == FTHMC_INT_LEAPFROG;
@@ -405,25 +399,47 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
     // FTHMC_MODE_LITERAL discards the MD: no integrator to choose, and no per-chain form of it
     if (mode == FTHMC_MODE_LITERAL && (!leap || pb)) return FTHMC_ERR_UNSUPPORTED;
     const bool md = mode == FTHMC_MODE_MD;
+    if (bias && (pb || !md)) return FTHMC_ERR_UNSUPPORTED;
     Sched sc;
     FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    Ctx C; WS W; FT_TRY(open_flow_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &W));
+    Ctx C; MWS M{};
+    FT_TRY(bias ? open_ft_meta_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &M)
+                : open_flow_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &M.W));
+    const WS& W = M.W;
     const hipStream_t s = C.s;
-    double* K = W.scal + (size_t)SC_K * B;
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    // per-chain state triples: of x (old), of the proposal (neu), of x_new (sel)
-    double* old = W.scal + (size_t)SC_OLD0 * B;      // slots SC_OLD0.. : 3 consecutive
-    double* neu = W.scal + (size_t)SC_NEW0 * B;
-    double* sel = state_out ? state_out : W.scal + (size_t)SC_S * B;
+    const FlowBias fb{bias ? bias->T : MetaTab{}, M.sums};
+    const FlowBias* fbp = bias ? &fb : nullptr;
     if (md && C.small(L, nl)) {                                      // the whole trajectory in one launch
         SmallArgs a = small_args(x, W, nl, B, act, beta, 3);
         a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
         a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
-        // three instances of k_ft_small: per-chain beta runs the schedule-driven one with every integrator, the leapfrog included
+        // four instances of k_ft_small: the biased one and per-chain beta run the schedule-driven one with every integrator, the
+        // leapfrog included
+        if (bias) return launch_ft_small_meta(a, sc, fb.T, bias->qm_out, bias->vb_out, L, s);
         if (pb) return launch_ft_small_pb(a, sc, beta_b, L, s);
         return leap ? launch_ft_small(a, L, s) : launch_ft_small_sched(a, sc, L, s);
     }
+    double* K = W.scal + (size_t)SC_K * B;
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    // per-chain state rows: of x (old), of the proposal (neu), of x_new (sel) -- three in W.scal (slots SC_OLD0.., SC_NEW0..: 3
+    // consecutive); with a bias four and V behind them where launch_meta_energy leaves it, in W.vb: the momentum ping-pong field
+    // no flowed sequence touches (2 L^2 >= 32 rows of B)
+    const int nrow = bias ? 4 : 3;
+    double* old = bias ? W.vb : W.scal + (size_t)SC_OLD0 * B;
+    double* neu = bias ? W.vb + (size_t)5 * B : W.scal + (size_t)SC_NEW0 * B;
+    double* sel = state_out ? state_out : (bias ? W.vb + (size_t)10 * B : W.scal + (size_t)SC_S * B);
+    double* qm_sel = sel + (size_t)3 * B;
+    // V(Q_m) into an end's energy and Q_m into its fourth row: of the field (sums) or of the carried state; no bias: nothing
+    auto add_bias = [&](const double* xphys, double* rows, double* h) {
+        if (!bias) return FTHMC_OK;
+        if (!xphys) return launch_meta_energy_qm(rows + (size_t)3 * B, B, fb.T, h, nullptr, s);
+        FT_TRY(launch_meta_sums(xphys, B, L, M.sums, s));
+        return launch_meta_energy(M.sums, B, fb.T, h, rows + (size_t)3 * B, s);
+    };
+    const size_t row = (size_t)B * sizeof(double);
+    if (bias && state_in && hipMemcpyAsync(old + (size_t)3 * B, state_in + (size_t)3 * B, row, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
     const bool tuned = md && C.A.is_default() && nl > 0;
     if (tuned) {
         // tuned kernels: the scalars of either end of the trajectory come from ONE launch each (launch_traj_energy: log det J
@@ -434,157 +450,55 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
         const int np = flow_fwd_geom(C.mfma).ntiles(L);
         if (!state_in) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, nullptr, s, false, false, true));
         FT_TRY(launch_traj_energy(phys_field(x, W, nl), B, L, beta, W.lj_part, np, nl, state_in, v, old, h0, s, beta_b));
-        FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b));
+        FT_TRY(add_bias(state_in ? nullptr : phys_field(x, W, nl), old, h0));
+        FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b, fbp));
         FT_TRY(sweep_forward(C, W.xb, W, nl, B, L, act, nullptr, s, false, false, true));
         FT_TRY(launch_traj_energy(phys_field(W.xb, W, nl), B, L, beta, W.lj_part, np, nl, nullptr, W.va, neu, h1, s, beta_b));
+        FT_TRY(add_bias(phys_field(W.xb, W, nl), neu, h1));
     } else {                                                         // other net shapes, no layers, FTHMC_MODE_LITERAL
         double* seff = W.scal + (size_t)SC_SEFF * B;                 // per-chain beta: S_eff beside the beta-free triple
         if (pb) {
             FT_TRY(pb_eval(C, x, W, nl, B, L, act, beta_b, state_in, old, seff, s));
         } else if (state_in) {    // chained trajectories: S_eff and observables of x are the previous call's state_out
-            if (hipMemcpyAsync(old, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-                return FTHMC_ERR_LAUNCH;
+            if (hipMemcpyAsync(old, state_in, 3 * row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
         } else {
             FT_TRY(eval_action(C, x, W, nl, B, L, act, beta, old, nullptr, old + B, old + 2 * B, s));
         }
         FT_TRY(launch_kinetic(v, B, L, K, s));
         FT_TRY(launch_lincomb(pb ? seff : old, 1.0, K, 0.5, 0.0, h0, B, s));
+        FT_TRY(add_bias(state_in ? nullptr : phys_field(x, W, nl), old, h0));
         const double* vend = W.va;
         if (!md) {
             FT_TRY(launch_axpy(x, v, 0.5 * dt, W.xa, W.n2, s));       // ft_hmc.py:187 (Q2)
             FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 0, s));              // wrap (ft_hmc.py:208)
             vend = v;
         } else if (leap && !pb) {                                     // scalar-beta leapfrog: the last kick writes no xreg,
-            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, nullptr));
+            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, nullptr, nullptr, nullptr, fbp));
             FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 1, s));              // a launch of its own regularizes (ipynb/ft_hmc.py:426)
         } else {                                                      // schedules and per-chain beta: xreg inside the last kick
-            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b));
+            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b, fbp));
         }
         if (pb) FT_TRY(pb_eval(C, W.xb, W, nl, B, L, act, beta_b, nullptr, neu, seff, s));
         else FT_TRY(eval_action(C, W.xb, W, nl, B, L, act, beta, neu, nullptr, neu + B, neu + 2 * B, s));
         FT_TRY(launch_kinetic(vend, B, L, K, s));
         FT_TRY(launch_lincomb(pb ? seff : neu, 1.0, K, 0.5, 0.0, h1, B, s));
+        FT_TRY(add_bias(phys_field(W.xb, W, nl), neu, h1));
     }
     // The state of x_new without another sweep: selected per chain.  Who hands plaq / Q out: the Metropolis kernel both on the
-    // tuned branch; per-chain beta: Q (the triple's third row) from the kernel on either branch, plaq from the triple's second
-    // row and beta_b; the scalar general branch: two copies out of `sel`.
-    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 3, s, tuned && !pb ? plaq : nullptr,
-                             tuned || pb ? Q : nullptr));
-    if (pb) {
+    // tuned branch and with a bias; per-chain beta: Q (the triple's third row) from the kernel on either branch, plaq from the
+    // triple's second row and beta_b; the scalar unbiased general branch: two copies out of `sel`.
+    const bool both = bias || (tuned && !pb);
+    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, nrow, s, both ? plaq : nullptr,
+                             both || pb ? Q : nullptr));
+    if (bias) {                                                      // Q_m of x_new: the fourth row; V of it from this call's table
+        if (bias->qm_out && hipMemcpyAsync(bias->qm_out, qm_sel, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+        if (bias->vb_out) FT_TRY(launch_meta_energy_qm(qm_sel, B, fb.T, nullptr, bias->vb_out, s));
+    } else if (pb) {
         if (plaq) FT_TRY(launch_pb_from_state(sel, beta_b, B, L, nl > 0, nullptr, plaq, s));
     } else if (!tuned) {
-        if (plaq && hipMemcpyAsync(plaq, sel + B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return FTHMC_ERR_LAUNCH;
-        if (Q && hipMemcpyAsync(Q, sel + 2 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return FTHMC_ERR_LAUNCH;
+        if (plaq && hipMemcpyAsync(plaq, sel + B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+        if (Q && hipMemcpyAsync(Q, sel + 2 * B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     }
-    return FTHMC_OK;
-}
-
-// ---------------------------------------------------------------- metadynamics through the flow (no reference counterpart)
-// The workspace of the fthmc_ft_meta_* calls: the first-order layout of the call's shape and behind it sums[B][2].  The per-chain rows
-// of the two ends live in W.vb, the momentum ping-pong field no flowed sequence touches (2 L^2 >= 32 rows of B): five rows per end
-// and for the selected one, (S_eff unbiased, plaq, Q, Q_m) and V behind them where launch_meta_energy leaves it.
-struct FMWS { WS W; double* sums; size_t total; };
-FMWS ft_meta_layout(const FlowArch& A, Carver& c, int B, int L, int nl) {
-    FMWS m{};
-    m.W = ws_layout(A, c, B, L, nl);
-    if (m.W.total == 0) return m;
-    m.sums = c.take((size_t)2 * B);
-    m.total = c.total();
-    return m;
-}
-// What every fthmc_ft_meta_* call refuses, in the ABI's order -- FTHMC_ERR_ARG (check_ft_meta_args; FTHMC_ERR_UNSUPPORTED for the
-// activation behind it), FTHMC_ERR_UNSUPPORTED, the workspace -- and what it opens: the context, the workspace, the weights.
-// seq_always: the force and action entry points, which never take the one-launch path.
-int check_ft_meta_args(bool ptrs_ok, const double* w, int nl, int B, int L, int act, const double* vtab, int G, int nb, double qmax,
-                       double wall) {
-    if (!ptrs_ok || (nl > 0 && !w) || bad_shape(B, L) || nl < 0 || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall))
-        return FTHMC_ERR_ARG;
-    return act < 0 || act > 2 ? FTHMC_ERR_UNSUPPORTED : FTHMC_OK;
-}
-int open_ft_meta_call(const double* w, const fthmc_arch_t* arch, int nl, int B, int L, bool seq_always, void* ws, size_t ws_bytes,
-                      void* stream, uint64_t wver, Ctx* C, FMWS* M) {
-    FT_TRY(open_call(arch, stream, C));
-    if ((seq_always || !C->small(L, nl)) && B > META_SEQ_MAX_B) return FTHMC_ERR_UNSUPPORTED;
-    if (C->A.is_default() && nl > 0 && B > (1 << 20)) return FTHMC_ERR_UNSUPPORTED;     // (open_ws: the default net's kernels)
-    Carver c(ws, ws_bytes);
-    *M = ft_meta_layout(C->A, c, B, L, nl);
-    FT_TRY(check_ws(M->total, ws, ws_bytes));
-    return use_weights(*C, w, nl, M->W.wint, wver);
-}
-
-// The biased flowed trajectory (FTHMC_MODE_MD): ft_trajectory_call's sequence with the bias in every force (ft_md_ws' FlowBias) and
-// V(Q_m) of the physical field added to either energy; launch_metropolis selects Q_m with the triple.  The carried state is
-// TABLE-FREE, [4][B] = (S_eff unbiased, plaq, Q, Q_m): V of a carried Q_m is looked up in the table of this call.
-int ft_meta_trajectory_call(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int nl, int B,
-                            int L, int act, double beta, double dt, int nstep, int integrator, const double* vtab, int G, int nb,
-                            double qmax, double wall, double* x_new, double* dH, double* acc, double* H0, double* H1, double* plaq,
-                            double* Q, double* qm_out, double* vb_out, const double* state_in, double* state_out, void* ws,
-                            size_t ws_bytes, void* stream, uint64_t wver) {
-    FT_TRY(check_ft_meta_args(x && v && u && x_new && nstep >= 1, w, nl, B, L, act, vtab, G, nb, qmax, wall));
-    const bool leap = integrator == FTHMC_INT_LEAPFROG;
-    Sched sc;
-    FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    Ctx C; FMWS M;
-    FT_TRY(open_ft_meta_call(w, arch, nl, B, L, false, ws, ws_bytes, stream, wver, &C, &M));
-    const WS& W = M.W;
-    const hipStream_t s = C.s;
-    const FlowBias bias{MetaTab{vtab, B / G, nb, qmax, wall}, M.sums};
-    const MetaTab& T = bias.T;
-    if (C.small(L, nl)) {                                            // the whole trajectory in one launch (flow_small.hip BIAS)
-        SmallArgs a = small_args(x, W, nl, B, act, beta, 3);
-        a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
-        a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
-        return launch_ft_small_meta(a, sc, T, qm_out, vb_out, L, s);
-    }
-    double* K = W.scal + (size_t)SC_K * B;
-    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
-    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
-    double* old = W.vb;                                              // rows 0 .. 3 the state, row 4 V
-    double* neu = W.vb + (size_t)5 * B;
-    double* sel = state_out ? state_out : W.vb + (size_t)10 * B;
-    // V(Q_m) into an end's energy and Q_m into its fourth row: of the field (sums) or of the carried state
-    auto add_bias = [&](const double* xphys, double* rows, double* h) {
-        if (!xphys) return launch_meta_energy_qm(rows + (size_t)3 * B, B, T, h, nullptr, s);
-        FT_TRY(launch_meta_sums(xphys, B, L, M.sums, s));
-        return launch_meta_energy(M.sums, B, T, h, rows + (size_t)3 * B, s);
-    };
-    if (state_in && hipMemcpyAsync(old + (size_t)3 * B, state_in + (size_t)3 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return FTHMC_ERR_LAUNCH;
-    const bool tuned = C.A.is_default() && nl > 0;
-    if (tuned) {                                                     // ft_trajectory_call's tuned branch
-        const int np = flow_fwd_geom(C.mfma).ntiles(L);
-        if (!state_in) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, nullptr, s, false, false, true));
-        FT_TRY(launch_traj_energy(phys_field(x, W, nl), B, L, beta, W.lj_part, np, nl, state_in, v, old, h0, s));
-        FT_TRY(add_bias(state_in ? nullptr : phys_field(x, W, nl), old, h0));
-        FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, nullptr, &bias));
-        FT_TRY(sweep_forward(C, W.xb, W, nl, B, L, act, nullptr, s, false, false, true));
-        FT_TRY(launch_traj_energy(phys_field(W.xb, W, nl), B, L, beta, W.lj_part, np, nl, nullptr, W.va, neu, h1, s));
-        FT_TRY(add_bias(phys_field(W.xb, W, nl), neu, h1));
-    } else {                                                         // other net shapes, no layers: its general branch
-        if (state_in) {
-            if (hipMemcpyAsync(old, state_in, (size_t)3 * B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-        } else {
-            FT_TRY(eval_action(C, x, W, nl, B, L, act, beta, old, nullptr, old + B, old + 2 * B, s));
-        }
-        FT_TRY(launch_kinetic(v, B, L, K, s));
-        FT_TRY(launch_lincomb(old, 1.0, K, 0.5, 0.0, h0, B, s));
-        FT_TRY(add_bias(state_in ? nullptr : phys_field(x, W, nl), old, h0));
-        if (leap) {                                                   // as the unbiased leapfrog: a launch of its own regularizes
-            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, nullptr, nullptr, nullptr, &bias));
-            FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 1, s));
-        } else {
-            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, nullptr, &bias));
-        }
-        FT_TRY(eval_action(C, W.xb, W, nl, B, L, act, beta, neu, nullptr, neu + B, neu + 2 * B, s));
-        FT_TRY(launch_kinetic(W.va, B, L, K, s));
-        FT_TRY(launch_lincomb(neu, 1.0, K, 0.5, 0.0, h1, B, s));
-        FT_TRY(add_bias(phys_field(W.xb, W, nl), neu, h1));
-    }
-    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, 4, s, plaq, Q));
-    if (qm_out && hipMemcpyAsync(qm_out, sel + (size_t)3 * B, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
-    if (vb_out) FT_TRY(launch_meta_energy_qm(sel + (size_t)3 * B, B, T, nullptr, vb_out, s));
     return FTHMC_OK;
 }
 
@@ -733,7 +647,7 @@ int fthmc_leapfrog(const double* x, const double* p, int B, int L, double beta, 
 int fthmc_hmc_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta,
                          double dt, int nstep, double* x_new, double* dH, double* acc, double* H0,
                          double* H1, void* ws, size_t ws_bytes, void* stream) {
-    return hmc_trajectory_call(x, v, u, B, L, beta, nullptr, dt, nstep, FTHMC_INT_LEAPFROG, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
+    return hmc_trajectory_call(x, v, u, B, L, beta, nullptr, dt, nstep, FTHMC_INT_LEAPFROG, nullptr, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
 }
 
 int fthmc_integrator_forces(int integrator, int nstep) { return integrator_forces(integrator, nstep); }
@@ -750,7 +664,7 @@ int fthmc_md(const double* x, const double* p, int B, int L, double beta, double
 int fthmc_hmc_trajectory_int(const double* x, const double* v, const double* u, int B, int L, double beta, double dt, int nstep,
                              int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
                              void* ws, size_t ws_bytes, void* stream) {
-    return hmc_trajectory_call(x, v, u, B, L, beta, nullptr, dt, nstep, integrator, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
+    return hmc_trajectory_call(x, v, u, B, L, beta, nullptr, dt, nstep, integrator, nullptr, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
 }
 
 int fthmc_flow_layer_fwd(const double* x, const double* w, const fthmc_arch_t* arch, int B, int L, int mu, int off, int act,
@@ -979,7 +893,7 @@ int fthmc_ft_trajectory_v(const double* x, const double* v, const double* u, con
                         double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
                         const double* state_in, double* state_out,
                         void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, nullptr, dt, nstep, FTHMC_INT_LEAPFROG, mode, x_new, dH, acc,
+    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, nullptr, dt, nstep, FTHMC_INT_LEAPFROG, mode, nullptr, x_new, dH, acc,
                               H0, H1, plaq, Q, state_in, state_out, ws, ws_bytes, stream, weights_version);
 }
 
@@ -995,7 +909,7 @@ int fthmc_ft_trajectory_int_v(const double* x, const double* v, const double* u,
                               double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
                               const double* state_in, double* state_out,
                               void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version) {
-    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, nullptr, dt, nstep, integrator, mode, x_new, dH, acc,
+    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, nullptr, dt, nstep, integrator, mode, nullptr, x_new, dH, acc,
                               H0, H1, plaq, Q, state_in, state_out, ws, ws_bytes, stream, weights_version);
 }
 
@@ -1006,7 +920,7 @@ int fthmc_ft_trajectory_pb_v(const double* x, const double* v, const double* u, 
                              const double* state_in, double* state_out,
                              void* ws, size_t ws_bytes, void* stream, int integrator, uint64_t weights_version) {
     if (!beta_b) return FTHMC_ERR_ARG;
-    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, 0.0, beta_b, dt, nstep, integrator, mode, x_new, dH, acc,
+    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, 0.0, beta_b, dt, nstep, integrator, mode, nullptr, x_new, dH, acc,
                               H0, H1, plaq, Q, state_in, state_out, ws, ws_bytes, stream, weights_version);
 }
 
@@ -1014,7 +928,7 @@ int fthmc_hmc_trajectory_pb(const double* x, const double* v, const double* u, i
                             int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1,
                             void* ws, size_t ws_bytes, void* stream) {
     if (!beta_b) return FTHMC_ERR_ARG;
-    return hmc_trajectory_call(x, v, u, B, L, 0.0, beta_b, dt, nstep, integrator, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
+    return hmc_trajectory_call(x, v, u, B, L, 0.0, beta_b, dt, nstep, integrator, nullptr, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
 }
 
 int fthmc_replica_swap(const double* betas, int K, int M, int parity, const double* C, const double* u, double* beta_b, int32_t* rung,
@@ -1086,77 +1000,71 @@ int fthmc_instanton_hit(const double* x, int B, int L, double beta, const double
                             ft_stream(stream));
 }
 
-// Metadynamics HMC (meta.hip): the argument checks, the choice of the path and the workspace of the sequenced one
+// Metadynamics HMC (meta.hip): the argument checks; the choice of the path and the workspace of the sequenced one are hmc_trajectory_call's
 size_t fthmc_meta_ws_bytes(int B, int L, int path) {
     if (bad_shape(B, L) || path < 0 || path > 2 || path == 1) return 0;             // the one-launch path needs none
     if (B > META_SEQ_MAX_B) return 0;                                               // the sequenced path does not serve it
     Carver c;
-    return meta_layout(c, B, L).total * sizeof(double);
+    return meta_layout(flow_arch_default(), c, B, L, 0, true).total * sizeof(double);
 }
 int fthmc_meta_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta, double dt, int nstep, int integrator,
                           const double* vtab, int G, int nb, double qmax, double wall, int path, double* x_new, double* dH, double* acc,
                           double* H0, double* H1, double* qm_out, double* vb_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1 || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall) ||
-        path < 0 || path > 2)
-        return FTHMC_ERR_ARG;
+    BiasArg bias{{}, path, qm_out, vb_out};
+    if (meta_tab(vtab, B, G, nb, qmax, wall, &bias.T) != FTHMC_OK || path < 0 || path > 2) return FTHMC_ERR_ARG;
     if (path == 1 && (L > 64 || x_new == x)) return FTHMC_ERR_ARG;
-    Sched sc;
-    FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    Ctx C; FT_TRY(open_call(nullptr, stream, &C));
-    const MetaTab T{vtab, B / G, nb, qmax, wall};
-    if (path == 1 || (path == 0 && L <= 64 && C.mfma && x_new != x))
-        return launch_meta_trajectory(x, v, u, B, L, beta, sc, T, x_new, dH, acc, H0, H1, qm_out, vb_out, C.s);
-    if (B > META_SEQ_MAX_B) return FTHMC_ERR_UNSUPPORTED;
-    Carver c(ws, ws_bytes);
-    const MWS M = meta_layout(c, B, L);
-    FT_TRY(check_ws(M.total, ws, ws_bytes));
-    return meta_trajectory_seq(x, v, u, B, L, beta, sc, T, x_new, dH, acc, H0, H1, qm_out, vb_out, M, C.s);
+    return hmc_trajectory_call(x, v, u, B, L, beta, nullptr, dt, nstep, integrator, &bias, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
 }
 int fthmc_meta_deposit(const double* qm, int B, int G, int nb, double qmax, double w, double* vtab, void* stream) {
-    if (!qm || B <= 0 || B > FTHMC_MAX_B || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(w)) return FTHMC_ERR_ARG;
+    MetaTab T;
+    if (!qm || B <= 0 || B > FTHMC_MAX_B || meta_tab(vtab, B, G, nb, qmax, w, &T) != FTHMC_OK) return FTHMC_ERR_ARG;
     return launch_meta_deposit(qm, B, G, nb, qmax, w, vtab, ft_stream(stream));
 }
 int fthmc_meta_force(const double* x, int B, int L, double beta, const double* vtab, int G, int nb, double qmax, double wall, double* F,
                      void* stream) {
-    if (!x || !F || bad_shape(B, L) || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall)) return FTHMC_ERR_ARG;
-    return launch_meta_force(x, B, L, beta, MetaTab{vtab, B / G, nb, qmax, wall}, F, ft_stream(stream));
+    MetaTab T;
+    if (!x || !F || bad_shape(B, L) || meta_tab(vtab, B, G, nb, qmax, wall, &T) != FTHMC_OK) return FTHMC_ERR_ARG;
+    return launch_meta_force(x, B, L, beta, T, F, ft_stream(stream));
 }
 int fthmc_meta_action(const double* x, int B, int L, double beta, const double* vtab, int G, int nb, double qmax, double wall, double* S,
                       double* qm, double* vb, void* stream) {
-    if (!x || bad_shape(B, L) || bad_meta_table(vtab, B, G, nb, qmax) || bad_meta_weight(wall)) return FTHMC_ERR_ARG;
-    return launch_meta_action(x, B, L, beta, MetaTab{vtab, B / G, nb, qmax, wall}, S, qm, vb, ft_stream(stream));
+    MetaTab T;
+    if (!x || bad_shape(B, L) || meta_tab(vtab, B, G, nb, qmax, wall, &T) != FTHMC_OK) return FTHMC_ERR_ARG;
+    return launch_meta_action(x, B, L, beta, T, S, qm, vb, ft_stream(stream));
 }
 
-// Metadynamics through the flow: the checks and the workspace are open_ft_meta_call's
+// Metadynamics through the flow: the checks are check_ft_meta_args', the workspace open_ft_meta_call's
 size_t fthmc_ft_meta_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
     Ctx C; Carver c;
     if (B <= 0 || L <= 0 || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
-    return ft_meta_layout(C.A, c, B, L, n_layers).total * sizeof(double);
+    return meta_layout(C.A, c, B, L, n_layers, false).total * sizeof(double);
 }
 int fthmc_ft_meta_trajectory_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
                                int B, int L, int act, double beta, double dt, int nstep, int integrator, const double* vtab, int G,
                                int nb, double qmax, double wall, double* x_new, double* dH, double* acc, double* H0, double* H1,
                                double* plaq, double* Q, double* qm_out, double* vb_out, const double* state_in, double* state_out,
                                void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    return ft_meta_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, dt, nstep, integrator, vtab, G, nb, qmax, wall, x_new, dH,
-                                   acc, H0, H1, plaq, Q, qm_out, vb_out, state_in, state_out, ws, ws_bytes, stream, weights_version);
+    BiasArg bias{{}, 0, qm_out, vb_out};
+    FT_TRY(check_ft_meta_args(x && v && u && x_new && nstep >= 1, w, n_layers, B, L, act, vtab, G, nb, qmax, wall, &bias.T));
+    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, nullptr, dt, nstep, integrator, FTHMC_MODE_MD, &bias, x_new, dH,
+                              acc, H0, H1, plaq, Q, state_in, state_out, ws, ws_bytes, stream, weights_version);
 }
 int fthmc_ft_meta_force_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
                           const double* vtab, int G, int nb, double qmax, double wall, double* F, void* ws, size_t ws_bytes,
                           void* stream, uint64_t weights_version) {
-    FT_TRY(check_ft_meta_args(x && F, w, n_layers, B, L, act, vtab, G, nb, qmax, wall));
-    Ctx C; FMWS M;
-    FT_TRY(open_ft_meta_call(w, arch, n_layers, B, L, true, ws, ws_bytes, stream, weights_version, &C, &M));
-    const FlowBias bias{MetaTab{vtab, B / G, nb, qmax, wall}, M.sums};
+    Ctx C; MWS M; FlowBias bias{};
+    FT_TRY(check_ft_meta_args(x && F, w, n_layers, B, L, act, vtab, G, nb, qmax, wall, &bias.T));
+    FT_TRY(open_ft_meta_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, true, weights_version, &C, &M));
+    bias.sums = M.sums;
     FT_TRY(force_gp(C, x, M.W, n_layers, B, L, act, beta, -1.0, nullptr, C.s, false, nullptr, &bias));
     return launch_kick_from_gp(M.W.gp, nullptr, nullptr, F, B, L, 0.0, 0.0, C.s);
 }
 int fthmc_ft_meta_action_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
                            const double* vtab, int G, int nb, double qmax, double wall, double* S_b, double* logdet, double* qm,
                            double* vbias, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
-    FT_TRY(check_ft_meta_args(x != nullptr, w, n_layers, B, L, act, vtab, G, nb, qmax, wall));
-    Ctx C; FMWS M;
-    FT_TRY(open_ft_meta_call(w, arch, n_layers, B, L, true, ws, ws_bytes, stream, weights_version, &C, &M));
+    Ctx C; MWS M; MetaTab T;
+    FT_TRY(check_ft_meta_args(x != nullptr, w, n_layers, B, L, act, vtab, G, nb, qmax, wall, &T));
+    FT_TRY(open_ft_meta_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, true, weights_version, &C, &M));
     const WS& W = M.W;
     const hipStream_t s = C.s;
     const size_t row = (size_t)B * sizeof(double);
@@ -1164,7 +1072,7 @@ int fthmc_ft_meta_action_v(const double* x, const double* w, const fthmc_arch_t*
     double* sb = S_b ? S_b : W.vb + (size_t)2 * B;                   // S_eff first, V added in place
     FT_TRY(eval_action(C, x, W, n_layers, B, L, act, beta, sb, logdet, nullptr, nullptr, s));
     FT_TRY(launch_meta_sums(phys_field(x, W, n_layers), B, L, M.sums, s));
-    FT_TRY(launch_meta_energy(M.sums, B, MetaTab{vtab, B / G, nb, qmax, wall}, sb, W.vb, s));      // W.vb: (Q_m, V), [2][B]
+    FT_TRY(launch_meta_energy(M.sums, B, T, sb, W.vb, s));          // W.vb: (Q_m, V), [2][B]
     if (qm && hipMemcpyAsync(qm, W.vb, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     if (vbias && hipMemcpyAsync(vbias, W.vb + B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     return FTHMC_OK;

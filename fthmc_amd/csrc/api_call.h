@@ -147,6 +147,23 @@ inline int open_ws(const Ctx& C, void* ws, size_t ws_bytes, int B, int L, int nl
     *W = ws_layout(C.A, c, B, L, nl, train);
     return check_ws(W->total, ws, ws_bytes);
 }
+// The workspace of the metadynamics calls (fthmc_meta_*, fthmc_ft_meta_*): a first-order layout and behind it sums[B][2]; pairs
+// (the plain sequence): the (Q_m, V) pairs of the two ends and of the selected one, [2][B] each
+struct MWS { WS W; double *sums, *qv_old, *qv_new, *qv_sel; size_t total; };
+MWS meta_layout(const FlowArch& A, Carver& c, int B, int L, int nl, bool pairs) {
+    MWS m{};
+    m.W = ws_layout(A, c, B, L, nl);
+    if (m.W.total == 0) return m;
+    m.sums = c.take((size_t)2 * B);
+    if (pairs) { m.qv_old = c.take((size_t)2 * B); m.qv_new = c.take((size_t)2 * B); m.qv_sel = c.take((size_t)2 * B); }
+    m.total = c.total();
+    return m;
+}
+inline int open_meta_ws(const Ctx& C, void* ws, size_t ws_bytes, int B, int L, int nl, bool pairs, MWS* M) {
+    Carver c(ws, ws_bytes);
+    *M = meta_layout(C.A, c, B, L, nl, pairs);
+    return check_ws(M->total, ws, ws_bytes);
+}
 
 // Workspace of the second-order entry points (fthmc_ft_action_vjp, fthmc_ft_force_vjp): the head of every layout (the weight
 // expansions and their stamps, fthmc_ws_head_bytes()) is skipped and never written; behind it, regions sized in dual numbers (the

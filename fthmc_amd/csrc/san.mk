@@ -34,39 +34,21 @@ san_integrator:
 	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	  -I. ../../tests/hip/integrator_walk.cpp -o $(SANWALK)
 
-# The replica-exchange entry points (fthmc_ft_trajectory_pb_v, fthmc_hmc_trajectory_pb, fthmc_replica_swap, fthmc_ladder_init):
-# tests/hip/tempering_walk.cpp as a stand-alone program against the host-side sanitizer build of the library (built first when it
-# is missing or older than a source), the sanitizer runtimes linked in (nothing to preload), run by tests/test_tempering.py
-SANTEMP ?= $(SANDIR)/tempering_walk
+# The stand-alone walkers of the entry points, tests/hip/<name>_walk.cpp: `make -f san.mk san_<name>` builds one where SANEXE says
+# (or the variable the walker's test has always passed: SANWALKVARS; default $(SANDIR)/<name>_walk), against the host-side sanitizer build of the library (built first when it is missing or older than a source), the sanitizer
+# runtimes linked in (nothing to preload).  tempering (fthmc_ft_trajectory_pb_v, fthmc_hmc_trajectory_pb, fthmc_replica_swap,
+# fthmc_ladder_init: tests/test_tempering.py), loops (the Wilson-loop entry points: tests/test_wilson_loops.py), local
+# (fthmc_local_update: tests/test_local_update.py), instanton (the instanton hits and the integer reductions of topo_int.h:
+# tests/test_instanton.py), meta (the fthmc_meta_* entry points: tests/test_meta.py), ft_meta (the fthmc_ft_meta_* entry points:
+# tests/test_ft_meta.py).  san_build, san_integrator and san_layout are rules of their own.
 $(SANOUT): $(SRCS) common.h kernels.h integrator.h topo_int.h meta_tab.h api_call.h ../../include/fthmc_hip.h san.mk
 	@$(MAKE) --no-print-directory -f san.mk san_build
-san_tempering: $(SANOUT)
-	mkdir -p $(dir $(SANTEMP))
+SANWALKVARS = tempering:SANTEMP loops:SANLOOPS local:SANLOCAL instanton:SANINST meta:SANMETA ft_meta:SANFTMETA
+SANEXE ?= $(or $($(patsubst $*:%,%,$(filter $*:%,$(SANWALKVARS)))),$(SANDIR)/$*_walk)
+san_%: $(SANOUT)
+	mkdir -p $(dir $(SANEXE))
 	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
-	  ../../tests/hip/tempering_walk.cpp -o $(SANTEMP) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
-
-# The Wilson-loop entry points (fthmc_wilson_loops_ws_bytes, fthmc_wilson_loops): tests/hip/loops_walk.cpp in the same way, run
-# by tests/test_wilson_loops.py
-SANLOOPS ?= $(SANDIR)/loops_walk
-san_loops: $(SANOUT)
-	mkdir -p $(dir $(SANLOOPS))
-	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
-	  ../../tests/hip/loops_walk.cpp -o $(SANLOOPS) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
-
-# The local-update entry point (fthmc_local_update): tests/hip/local_walk.cpp in the same way, run by tests/test_local_update.py
-SANLOCAL ?= $(SANDIR)/local_walk
-san_local: $(SANOUT)
-	mkdir -p $(dir $(SANLOCAL))
-	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
-	  ../../tests/hip/local_walk.cpp -o $(SANLOCAL) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
-
-# The instanton-hit entry points (fthmc_instanton_hit, fthmc_instanton_ws_bytes) and the integer reductions of topo_int.h:
-# tests/hip/instanton_walk.cpp in the same way, run by tests/test_instanton.py
-SANINST ?= $(SANDIR)/instanton_walk
-san_instanton: $(SANOUT)
-	mkdir -p $(dir $(SANINST))
-	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
-	  ../../tests/hip/instanton_walk.cpp -o $(SANINST) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
+	  ../../tests/hip/$*_walk.cpp -o $(SANEXE) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
 
 # The workspace layouts of api_call.h (ws_layout, vjp_layout, force_layout on one carver): tests/hip/layout_walk.cpp includes the
 # header itself (hipcc's host pass: the header pulls in the HIP headers) with the unsigned-overflow check on top, and asks the
@@ -79,19 +61,3 @@ san_layout: $(SANOUT)
 	  -c ../../tests/hip/layout_walk.cpp -o $(SANLAYOUT).o
 	$(ROCM)/lib/llvm/bin/clang++ -fsanitize=address,undefined -shared-libsan $(SANLAYOUT).o -o $(SANLAYOUT) \
 	  -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
-
-# The metadynamics entry points (fthmc_meta_ws_bytes, fthmc_meta_trajectory, fthmc_meta_deposit, fthmc_meta_force, fthmc_meta_action):
-# tests/hip/meta_walk.cpp in the same way, run by tests/test_meta.py
-SANMETA ?= $(SANDIR)/meta_walk
-san_meta: $(SANOUT)
-	mkdir -p $(dir $(SANMETA))
-	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
-	  ../../tests/hip/meta_walk.cpp -o $(SANMETA) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))
-
-# The metadynamics-through-the-flow entry points (fthmc_ft_meta_ws_bytes, fthmc_ft_meta_trajectory_v, fthmc_ft_meta_force_v,
-# fthmc_ft_meta_action_v): tests/hip/ft_meta_walk.cpp in the same way, run by tests/test_ft_meta.py
-SANFTMETA ?= $(SANDIR)/ft_meta_walk
-san_ft_meta: $(SANOUT)
-	mkdir -p $(dir $(SANFTMETA))
-	$(ROCM)/lib/llvm/bin/clang++ -O1 -g -std=c++17 -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -shared-libsan \
-	  ../../tests/hip/ft_meta_walk.cpp -o $(SANFTMETA) -L.. -lfthmc_hip_san -Wl,-rpath,$(abspath ..) -Wl,-rpath,$(dir $(SANRT))

@@ -518,25 +518,21 @@ def meta_trajectory(x, v, u, beta: float, dt: float, nstep: int, table, qmax: fl
     quadratic wall outside.  path: 0 the library chooses, 1 one launch per trajectory (L <= 64, x_new must not be x), 2 the
     sequenced path (any L; out['x_new'] may be x).  out: optional dict with any of the result keys to write into.  With an all-zero
     table and wall = 0 the result is hmc_trajectory's.  Not differentiable."""
-    ic = integrator_code(integrator)
-    x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
-    path = int(path)
-    if u.numel() != B:
-        raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
+    ic, path = integrator_code(integrator), int(path)
+    x, v, u, B, L, xn, r = _plain_trajectory_args(x, v, u, out, ('dH', 'acc', 'H0', 'H1', 'qm', 'vbias'))
     if path not in (0, 1, 2) or int(nstep) < 1:
         raise ValueError(f'meta_trajectory: path in 0 .. 2 and nstep >= 1 expected, got path={path}, nstep={nstep}')
     tab = _meta_table(table, B, qmax, wall)
-    xn = _out_like(None if out is None else out.get('x_new'), x, "out['x_new']")
     if path == 1 and (L > 64 or xn.data_ptr() == x.data_ptr()):
         raise ValueError("meta_trajectory: path 1 serves L <= 64 with out['x_new'] other than x")
-    dH, acc, H0, H1, qm, vb = (_out_vec(out, k, B, x) for k in ('dH', 'acc', 'H0', 'H1', 'qm', 'vbias'))
     with torch.cuda.device(x.device):
         # path 0 takes the one-launch kernel where fthmc_meta_trajectory says it does: no scratch is asked for there
         seq = path == 2 or (path == 0 and (L > 64 or xn.data_ptr() == x.data_ptr() or get_variant() != 1))
         ws, nb = _meta_ws(x, meta_ws_bytes(B, L, 2) if seq else 0)
         check(_lib.load().fthmc_meta_trajectory(_p(x), _p(v), _p(u), B, L, float(beta), float(dt), int(nstep), ic, *tab, path, _p(xn),
-                                                _p(dH), _p(acc), _p(H0), _p(H1), _p(qm), _p(vb), ws, nb, _stream(x)), 'fthmc_meta_trajectory')
-    return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1, 'qm': qm, 'vbias': vb}
+                                                *(_p(r[k]) for k in ('dH', 'acc', 'H0', 'H1', 'qm', 'vbias')), ws, nb, _stream(x)),
+              'fthmc_meta_trajectory')
+    return r
 
 
 def meta_deposit(qm, table, qmax: float, w: float):
@@ -710,21 +706,27 @@ def _beta_b(beta, B: int):
     return _expect(beta, B, 'beta (per chain)').view(-1) if isinstance(beta, torch.Tensor) else None
 
 
+def _plain_trajectory_args(x, v, u, out, keys):
+    """what hmc_trajectory and meta_trajectory open with -> (x, v, u, B, L, x_new, results): the fields, the B uniforms, out['x_new']
+    (or a fresh field) and the result dict: x_new and the per-chain vector of every key, from `out` where it carries one"""
+    x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
+    if u.numel() != B:
+        raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
+    xn = _out_like(None if out is None else out.get('x_new'), x, "out['x_new']")
+    return x, v, u, B, L, xn, {'x_new': xn, **{k: _out_vec(out, k, B, x) for k in keys}}
+
+
 def hmc_trajectory(x, v, u, beta, dt: float, nstep: int, out=None, integrator='leapfrog'):
     """-> dict(x_new, dH, acc, H0, H1), per chain; out: optional dict with any of these to write into (x_new must not be x).
     beta: a number, or a device tensor of B doubles -- per-chain beta (C ABI fthmc_hmc_trajectory_pb)."""
     ic = integrator_code(integrator)
-    x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
-    if u.numel() != B:
-        raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
+    x, v, u, B, L, xn, r = _plain_trajectory_args(x, v, u, out, ('dH', 'acc', 'H0', 'H1'))
     bb = _beta_b(beta, B)
-    xn = _out_like(None if out is None else out.get('x_new'), x, "out['x_new']")
     if xn.data_ptr() == x.data_ptr():
         raise FthmcError("out['x_new']: must not be x")
-    dH, acc, H0, H1 = (_out_vec(out, k, B, x) for k in ('dH', 'acc', 'H0', 'H1'))
     ws, nb = _ws(x, B, L, 0)
     lib, head, step = _lib.load(), (_p(x), _p(v), _p(u), B, L), (float(dt), int(nstep))
-    tail = (_p(xn), _p(dH), _p(acc), _p(H0), _p(H1), ws, nb, _stream(x))
+    tail = (_p(xn), _p(r['dH']), _p(r['acc']), _p(r['H0']), _p(r['H1']), ws, nb, _stream(x))
     # the entry point decides which kernel instance runs: a tensor beta -> _pb, 'leapfrog' with a number -> the old one, else _int
     if bb is not None:
         check(lib.fthmc_hmc_trajectory_pb(*head, _p(bb), *step, ic, *tail), 'fthmc_hmc_trajectory_pb')
@@ -732,7 +734,7 @@ def hmc_trajectory(x, v, u, beta, dt: float, nstep: int, out=None, integrator='l
         check(lib.fthmc_hmc_trajectory_int(*head, float(beta), *step, ic, *tail), 'fthmc_hmc_trajectory_int')
     else:
         check(lib.fthmc_hmc_trajectory(*head, float(beta), *step, *tail), 'fthmc_hmc_trajectory')
-    return {'x_new': xn, 'dH': dH, 'acc': acc, 'H0': H0, 'H1': H1}
+    return r
 
 
 # ---------------------------------------------------------------- replica exchange (parallel tempering)
@@ -1059,6 +1061,87 @@ def _chain_groups(device, edges, side_streams=None):
         main.wait_stream(st)
 
 
+def _meta_group_rows(table, B: int, edges):
+    """the table rows of the chain groups of `edges` -> [(row_lo, row_hi) or None (the whole table)]: with one row every group reads
+    it; otherwise a group must be whole rows (every edge a multiple of B / G), and is handed its own"""
+    G = 1 if table.dim() == 1 else table.shape[0]
+    if G == 1:
+        return [None] * (len(edges) - 1)
+    if G < 1 or B % G:
+        raise ValueError(f'meta table: {G} rows do not divide the {B} chains')
+    cpr = B // G
+    if any(e % cpr for e in edges):
+        raise ValueError(f'groups: the edges {tuple(edges)} split a table row ({cpr} chains per row): every chain group must be whole rows')
+    return [(edges[k] // cpr, edges[k + 1] // cpr) for k in range(len(edges) - 1)]
+
+
+def _ft_trajectory(x, v, u, w, n_layers, beta, dt, nstep, act, mode, out, state_in, groups, arch, wkey, side_streams, integrator,
+                   bias=None):
+    """The body of ft_trajectory and, with bias = (table, qmax, wall), of ft_meta_trajectory: the checks, the result tensors (the
+    state has nrow = 3 rows, 4 with a bias), the chain-group fork (a group is handed its own table rows) and the C call, chosen by
+    (bias, per-chain beta, integrator)."""
+    ic = integrator_code(integrator)
+    if ic and mode not in ('md',):
+        raise ValueError(f'mode {mode!r} discards the MD: it goes with integrator=\'leapfrog\' only, got {integrator!r}')
+    x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
+    if u.numel() != B:
+        raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
+    bb = _beta_b(beta, B)
+    if bb is not None and mode != 'md':
+        raise ValueError(f'a per-chain beta goes with mode \'md\' only, got {mode!r}')
+    nrow, keys, tab = 3, ('dH', 'acc', 'H0', 'H1', 'plaq', 'Q'), None
+    if bias is not None:
+        if int(nstep) < 1:
+            raise ValueError(f'ft_meta_trajectory: nstep >= 1 expected, got {nstep}')
+        nrow, keys, tab = 4, keys + ('qm', 'vbias'), _meta_table(bias[0], B, *bias[1:])
+    edges = _group_edges(groups, B)                                     # an int, or explicit group sizes (chains per group)
+    rows = _meta_group_rows(bias[0], B, edges) if bias is not None else None      # raises before anything is launched
+    w, ap, a = _wall(w, n_layers, arch)
+    out = {} if out is None else out
+    if 'x_new' not in out:
+        out['x_new'] = torch.empty_like(x)
+    for k in keys:
+        if k not in out:
+            out[k] = torch.empty(B, dtype=x.dtype, device=x.device)
+    if 'state' not in out:
+        out['state'] = torch.empty(nrow, B, dtype=x.dtype, device=x.device)
+    if state_in is not None:
+        state_in = _dev(state_in, 'state_in')
+        if state_in.numel() != nrow * B:
+            raise FthmcError(f'state_in: expected [{nrow}, {B}]')
+        state_in = state_in.reshape(nrow, B)
+    if len(edges) > 2:
+        parts = []
+        for lo, hi, st in _chain_groups(x.device, edges, side_streams):
+            r = rows[edges.index(lo)] if rows else None
+            with torch.cuda.stream(st):
+                og = {k: t[lo:hi] for k, t in out.items() if k != 'state'}
+                sg = state_in[:, lo:hi].contiguous() if state_in is not None else None
+                bg = bias if r is None else (bias[0][r[0]:r[1]],) + tuple(bias[1:])
+                _ft_trajectory(x[lo:hi], v[lo:hi], u[lo:hi], w, n_layers, beta if bb is None else bb[lo:hi], dt, nstep, act, mode, og,
+                               sg, 1, a, wkey, None, integrator, bg)      # one group: no side streams
+                out['state'][:, lo:hi].copy_(og['state'])
+                parts.append(og)                                        # keep the group's temporaries alive until the join
+        return out
+    m = {'md': MODE_MD, 'literal': MODE_LITERAL, 'reference_literal': MODE_LITERAL}[mode]
+    ws, nb = _ws(x, B, L, n_layers, arch=a, meta=bias is not None)
+    lib, wv = _lib.load(), weights_version(wkey)
+    head = (_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act))
+    res = tuple(_p(out[k]) for k in ('x_new',) + keys)
+    tail = (_p(state_in), _p(out['state']), ws, nb, _stream(x))
+    # the entry point decides which kernel instance runs: a table -> _meta, a tensor beta -> _pb, 'leapfrog' with a number -> the
+    # old one, else _int
+    if bias is not None:
+        check(lib.fthmc_ft_meta_trajectory_v(*head, float(beta), float(dt), int(nstep), ic, *tab, *res, *tail, wv), 'fthmc_ft_meta_trajectory')
+    elif bb is not None:
+        check(lib.fthmc_ft_trajectory_pb_v(*head, _p(bb), float(dt), int(nstep), m, *res, *tail, ic, wv), 'fthmc_ft_trajectory_pb')
+    elif ic:
+        check(lib.fthmc_ft_trajectory_int_v(*head, float(beta), float(dt), int(nstep), m, *res, *tail, ic, wv), 'fthmc_ft_trajectory_int')
+    else:
+        check(lib.fthmc_ft_trajectory_v(*head, float(beta), float(dt), int(nstep), m, *res, *tail, wv), 'fthmc_ft_trajectory')
+    return out
+
+
 def ft_trajectory(x, v, u, w, n_layers: int, beta, dt: float, nstep: int, act='silu', mode='md',
                   out: Optional[dict] = None, state_in: Optional[torch.Tensor] = None, groups: int = 1, arch=None, wkey=None,
                   side_streams=None, integrator='leapfrog'):
@@ -1078,70 +1161,10 @@ def ft_trajectory(x, v, u, w, n_layers: int, beta, dt: float, nstep: int, act='s
 
     beta: a number, or a device tensor of B doubles -- per-chain beta (C ABI fthmc_ft_trajectory_pb_v; mode 'md' only), read in
     place.  `state` is then the BETA-FREE triple [3, B] = (log det J, sum cos P, Q) of x_new, valid as `state_in` under any beta."""
-    ic = integrator_code(integrator)
-    if ic and mode not in ('md',):
-        raise ValueError(f'mode {mode!r} discards the MD: it goes with integrator=\'leapfrog\' only, got {integrator!r}')
-    x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
-    if u.numel() != B:
-        raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
-    bb = _beta_b(beta, B)
-    if bb is not None and mode != 'md':
-        raise ValueError(f'a per-chain beta goes with mode \'md\' only, got {mode!r}')
-    w, ap, a = _wall(w, n_layers, arch)
-    if out is None:
-        out = {'x_new': torch.empty_like(x)}
-        for k in ('dH', 'acc', 'H0', 'H1', 'plaq', 'Q'):
-            out[k] = torch.empty(B, dtype=x.dtype, device=x.device)
-    if 'state' not in out:
-        out['state'] = torch.empty(3, B, dtype=x.dtype, device=x.device)
-    if state_in is not None:
-        state_in = _dev(state_in, 'state_in')
-        if state_in.numel() != 3 * B:
-            raise FthmcError(f'state_in: expected [3, {B}]')
-        state_in = state_in.reshape(3, B)
-    edges = _group_edges(groups, B)                                     # an int, or explicit group sizes (chains per group)
-    if len(edges) > 2:
-        parts = []
-        for lo, hi, st in _chain_groups(x.device, edges, side_streams):
-            with torch.cuda.stream(st):
-                og = {k: t[lo:hi] for k, t in out.items() if k != 'state'}
-                sg = state_in[:, lo:hi].contiguous() if state_in is not None else None
-                ft_trajectory(x[lo:hi], v[lo:hi], u[lo:hi], w, n_layers, beta if bb is None else bb[lo:hi], dt, nstep, act, mode, og,
-                              sg, arch=a, wkey=wkey, integrator=integrator)    # one group: no side streams
-                out['state'][:, lo:hi].copy_(og['state'])
-                parts.append(og)                                        # keep the group's temporaries alive until the join
-        return out
-    m = {'md': MODE_MD, 'literal': MODE_LITERAL, 'reference_literal': MODE_LITERAL}[mode]
-    ws, nb = _ws(x, B, L, n_layers, arch=a)
-    lib, wv = _lib.load(), weights_version(wkey)
-    head = (_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act))
-    tail = (float(dt), int(nstep), m, _p(out['x_new']), _p(out['dH']), _p(out['acc']), _p(out['H0']), _p(out['H1']), _p(out['plaq']),
-            _p(out['Q']), _p(state_in), _p(out['state']), ws, nb, _stream(x))
-    # the entry point decides which kernel instance runs: a tensor beta -> _pb, 'leapfrog' with a number -> the old one, else _int
-    if bb is not None:
-        check(lib.fthmc_ft_trajectory_pb_v(*head, _p(bb), *tail, ic, wv), 'fthmc_ft_trajectory_pb')
-    elif ic:
-        check(lib.fthmc_ft_trajectory_int_v(*head, float(beta), *tail, ic, wv), 'fthmc_ft_trajectory_int')
-    else:
-        check(lib.fthmc_ft_trajectory_v(*head, float(beta), *tail, wv), 'fthmc_ft_trajectory')
-    return out
+    return _ft_trajectory(x, v, u, w, n_layers, beta, dt, nstep, act, mode, out, state_in, groups, arch, wkey, side_streams, integrator)
 
 
 # ---------------------------------------------------------------- metadynamics through the flow (DESIGN 4.16)
-def _meta_group_rows(table, B: int, edges):
-    """the table rows of the chain groups of `edges` -> [(row_lo, row_hi) or None (the whole table)]: with one row every group reads
-    it; otherwise a group must be whole rows (every edge a multiple of B / G), and is handed its own"""
-    G = 1 if table.dim() == 1 else table.shape[0]
-    if G == 1:
-        return [None] * (len(edges) - 1)
-    if G < 1 or B % G:
-        raise ValueError(f'meta table: {G} rows do not divide the {B} chains')
-    cpr = B // G
-    if any(e % cpr for e in edges):
-        raise ValueError(f'groups: the edges {tuple(edges)} split a table row ({cpr} chains per row): every chain group must be whole rows')
-    return [(edges[k] // cpr, edges[k + 1] // cpr) for k in range(len(edges) - 1)]
-
-
 def ft_meta_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep: int, table, qmax: float, wall: float = 0.0, act='silu',
                        integrator='leapfrog', out: Optional[dict] = None, state_in: Optional[torch.Tensor] = None, groups: int = 1,
                        arch=None, wkey=None, side_streams=None):
@@ -1150,46 +1173,8 @@ def ft_meta_trajectory(x, v, u, w, n_layers: int, beta: float, dt: float, nstep:
     the table the call ran on, and state [4, B] = (S_eff without the bias, plaq, Q, Q_m) of x_new.  The state is table-free: fed back
     as `state_in` it stays valid across meta_deposit calls.  table, qmax, wall: as meta_trajectory.  groups, out, wkey, side_streams:
     as ft_trajectory; with more than one table row every chain group must be whole rows.  Results do not depend on `groups`."""
-    ic = integrator_code(integrator)
-    x = _field(x); v = _field(v, 'v'); u = _dev(u, 'u').reshape(-1); B, _, L, _ = x.shape
-    if u.numel() != B:
-        raise FthmcError(f'u: expected {B} uniforms, got {u.numel()}')
-    if int(nstep) < 1:
-        raise ValueError(f'ft_meta_trajectory: nstep >= 1 expected, got {nstep}')
-    tab = _meta_table(table, B, qmax, wall)
-    edges = _group_edges(groups, B)
-    rows = _meta_group_rows(table, B, edges)                             # raises before anything is launched
-    w, ap, a = _wall(w, n_layers, arch)
-    if out is None:
-        out = {'x_new': torch.empty_like(x)}
-    for k in ('dH', 'acc', 'H0', 'H1', 'plaq', 'Q', 'qm', 'vbias'):
-        if k not in out:
-            out[k] = torch.empty(B, dtype=x.dtype, device=x.device)
-    if 'state' not in out:
-        out['state'] = torch.empty(4, B, dtype=x.dtype, device=x.device)
-    if state_in is not None:
-        state_in = _dev(state_in, 'state_in')
-        if state_in.numel() != 4 * B:
-            raise FthmcError(f'state_in: expected [4, {B}]')
-        state_in = state_in.reshape(4, B)
-    if len(edges) > 2:
-        parts = []
-        for (lo, hi, st) in _chain_groups(x.device, edges, side_streams):
-            r = rows[edges.index(lo)]
-            with torch.cuda.stream(st):
-                og = {k: t[lo:hi] for k, t in out.items() if k != 'state'}
-                sg = state_in[:, lo:hi].contiguous() if state_in is not None else None
-                ft_meta_trajectory(x[lo:hi], v[lo:hi], u[lo:hi], w, n_layers, beta, dt, nstep, table if r is None else table[r[0]:r[1]],
-                                   qmax, wall, act, integrator, og, sg, arch=a, wkey=wkey)
-                out['state'][:, lo:hi].copy_(og['state'])
-                parts.append(og)
-        return out
-    ws, nb = _ws(x, B, L, n_layers, arch=a, meta=True)
-    check(_lib.load().fthmc_ft_meta_trajectory_v(
-        _p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act), float(beta), float(dt), int(nstep), ic, *tab, _p(out['x_new']),
-        _p(out['dH']), _p(out['acc']), _p(out['H0']), _p(out['H1']), _p(out['plaq']), _p(out['Q']), _p(out['qm']), _p(out['vbias']),
-        _p(state_in), _p(out['state']), ws, nb, _stream(x), weights_version(wkey)), 'fthmc_ft_meta_trajectory')
-    return out
+    return _ft_trajectory(x, v, u, w, n_layers, beta, dt, nstep, act, 'md', out, state_in, groups, arch, wkey, side_streams, integrator,
+                          bias=(table, qmax, wall))
 
 
 def ft_meta_force(x, w, n_layers: int, beta: float, table, qmax: float, wall: float = 0.0, act='silu', arch=None, wkey=None):

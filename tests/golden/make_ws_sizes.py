@@ -2,7 +2,9 @@
 """Writes tests/golden/ws_sizes.json: what every workspace size query of libfthmc_hip.so answers over a grid of net shapes and
 (B, L, n_layers).  The committed file was recorded from the library of the commit before csrc/api.hip was split into api_call.h /
 api.hip / api_second_order.hip / api_diag.hip, so that tests/test_ws_sizes.py holds the layouts to the sizes they had: the scratch
-contract tests run in scratch of exactly the queried size, and a query and a layout that shrank together would pass them.
+contract tests run in scratch of exactly the queried size, and a query and a layout that shrank together would pass them.  The
+metadynamics columns (fthmc_meta_ws_bytes on its three paths, fthmc_ft_meta_ws_bytes) were recorded from the library of the commit
+before their two layouts became one (meta_layout).
 
     python tests/golden/make_ws_sizes.py [path/to/libfthmc_hip.so]      (default: the library of this tree)
 
@@ -18,7 +20,7 @@ BS = (1, 3, 64, 65, 1 << 20)
 LS = (4, 8, 16, 20, 64, 68, 132, 256)
 NLS = (0, 1, 8, 64, 65, 66)
 COLUMNS = ('ws', 'train_ws', 'vjp_ws', 'force_ws_path0', 'force_ws_path1', 'force_ws_path2', 'force_ws_path3', 'layer_stash_valu',
-           'layer_stash_mfma')
+           'layer_stash_mfma', 'meta_ws_path0', 'meta_ws_path1', 'meta_ws_path2', 'ft_meta_ws')
 
 
 def archs():
@@ -55,6 +57,8 @@ def query(lib, ops, arch, B, L, nl):
     finally:
         lib.fthmc_set_dual_path(path)
         lib.fthmc_set_variant(variant)
+    row += [int(lib.fthmc_meta_ws_bytes(B, L, p)) for p in range(3)]              # no net, no layers: the same on every row of a (B, L)
+    row.append(int(lib.fthmc_ft_meta_ws_bytes(ap, B, L, nl)))
     return row
 
 

@@ -4,16 +4,10 @@
 // of its own.  Every refusal the header lists and their precedence, the workspace rule, legal calls on every branch of the sequencer
 // (small path on and off, the default and a generic net, 0 to 66 layers, G = 1 and B, nb = 2 and 65536, the three integrators, carried
 // state and optional outputs) up to the largest shapes.  Device pointers are never dereferenced by the host side: stand-in addresses.
-#include "../../include/fthmc_hip.h"
+#include "walk.h"
 
 #include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
 
-static long calls = 0, refusals = 0;
-
-static double* dev(int k) { return (double*)(uintptr_t)(0x10000000ull + 0x1000000ull * (unsigned)k); }   // never dereferenced
-static void* wsp() { return (void*)(uintptr_t)0x90000000ull; }
 static const fthmc_arch_t GEN = {3, {4, 6, 5, 0, 0, 0, 0, 0}, 5, 3, 0};
 static const fthmc_arch_t BAD = {9, {4, 4, 4, 4, 4, 4, 4, 4}, 3, 2, 0};                                    // n_hidden > 8
 
@@ -49,15 +43,12 @@ static const char* const ENTRY[3] = {"fthmc_ft_meta_trajectory_v", "fthmc_ft_met
 
 static int want(const Call& c, int entry, int code, const char* what) {
     const int rc = c.run(entry);
-    ++calls;
-    if (code != FTHMC_OK) ++refusals;
-    if (rc == code) return 0;
+    if (answered(rc, code)) return 0;
     fprintf(stderr, "ft_meta_walk: %s: %s (B %d, L %d, layers %d, act %d, G %d, nb %d, qmax %g, wall %g, nstep %d, integrator %d, small %d, "
             "arch %s) -> %d, expected %d\n", ENTRY[entry], what, c.B, c.L, c.nl, c.act, c.G, c.nb, c.qmax, c.wall, c.nstep, c.integrator,
             fthmc_get_small_path(), c.arch == NULL ? "default" : (c.arch == &GEN ? "generic" : "refused"), rc, code);
     return 1;
 }
-#define WANT(c, entry, code, what) do { if (want((c), (entry), (code), (what))) return 1; } while (0)
 
 int main() {
     const double inf = INFINITY, nan_ = NAN;
@@ -166,6 +157,5 @@ int main() {
     }
     calls += 4;
     if (fthmc_set_small_path(1) != FTHMC_OK) return 1;
-    printf("{\"calls\": %ld, \"refusals\": %ld}\n", calls, refusals);
-    return 0;
+    return walked();
 }

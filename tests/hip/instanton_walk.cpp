@@ -5,18 +5,10 @@
 // on both paths from the smallest to the largest shapes; then the reductions for k = +-1024 at L = 4 and L = FTHMC_MAX_L: every result
 // in its range and congruent to the unreduced product, no signed overflow on the way.  Device pointers are never dereferenced by
 // the host side: stand-in addresses.
-#include "../../include/fthmc_hip.h"
+#include "walk.h"
 #include "../../fthmc_amd/csrc/topo_int.h"
 
-#include <stdio.h>
-#include <stdlib.h>
-
-static long calls = 0, refusals = 0, reductions = 0;
-
-static double* dev(int k) { return (double*)(uintptr_t)(0x10000000ull + 0x1000000ull * (unsigned)k); }   // never dereferenced
-static const int64_t* seeds() { return (const int64_t*)(uintptr_t)0x70000000ull; }
-static int32_t* ints(int k) { return (int32_t*)(uintptr_t)(0x80000000ull + 0x1000000ull * (unsigned)k); }
-static void* wsp() { return (void*)(uintptr_t)0x90000000ull; }
+static long reductions = 0;
 
 struct Call {
     int B = 2, L = 8, n_hit = 1, path = 1;
@@ -33,14 +25,11 @@ struct Call {
 
 static int want(const Call& c, int code, const char* what) {
     const int rc = c.run();
-    ++calls;
-    if (code != FTHMC_OK) ++refusals;
-    if (rc == code) return 0;
+    if (answered(rc, code)) return 0;
     fprintf(stderr, "instanton_walk: %s (B %d, L %d, n_hit %d, hit0 %lld, path %d) -> %d, expected %d\n", what, c.B, c.L, c.n_hit,
             (long long)c.hit0, c.path, rc, code);
     return 1;
 }
-#define WANT(c, code, what) do { if (want((c), (code), (what))) return 1; } while (0)
 
 static int reduce_walk(int L) {
     using namespace fthmc;

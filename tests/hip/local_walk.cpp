@@ -4,15 +4,7 @@
 // (fthmc_set_small_path 1 / 0) from the smallest to the largest shapes, every class mask, aliased and separate outputs, scalar and
 // per-chain beta, which take the host code through its geometry and its loops over sweeps and classes.  The launches themselves are
 // empty here: how many there are and in what order is what the device tests of the compositions see, not this program.  Device pointers are never dereferenced by the host side: stand-in addresses.
-#include "../../include/fthmc_hip.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-
-static long calls = 0, refusals = 0;
-
-static double* dev(int k) { return (double*)(uintptr_t)(0x10000000ull + 0x1000000ull * (unsigned)k); }   // never dereferenced
-static const int64_t* seeds() { return (const int64_t*)(uintptr_t)0x70000000ull; }
+#include "walk.h"
 
 struct Call {
     int B = 2, L = 8, n_hb = 1, n_or = 1, nsweep = 1, classes = 15;
@@ -26,14 +18,11 @@ struct Call {
 
 static int want(const Call& c, int code, const char* what) {
     const int rc = c.run();
-    ++calls;
-    if (code != FTHMC_OK) ++refusals;
-    if (rc == code) return 0;
+    if (answered(rc, code)) return 0;
     fprintf(stderr, "local_walk: %s (B %d, L %d, n_hb %d, n_or %d, nsweep %d, sweep0 %lld, classes %d) -> %d, expected %d\n", what, c.B, c.L,
             c.n_hb, c.n_or, c.nsweep, (long long)c.sweep0, c.classes, rc, code);
     return 1;
 }
-#define WANT(c, code, what) do { if (want((c), (code), (what))) return 1; } while (0)
 
 int main() {
     const int64_t two32 = (int64_t)1 << 32;
@@ -85,6 +74,5 @@ int main() {
         { Call c; c.nsweep = 2000; c.n_hb = 2; c.n_or = 3; c.L = 68; WANT(c, FTHMC_OK, "a long call refused"); }
     }
     if (fthmc_set_small_path(1) != FTHMC_OK) return 1;
-    printf("{\"calls\": %ld, \"refusals\": %ld}\n", calls, refusals);
-    return 0;
+    return walked();
 }

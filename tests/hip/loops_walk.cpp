@@ -3,26 +3,19 @@
 // build of the library (launches are no-ops there) and run as a program of its own.  Every refusal the header lists, the smallest
 // refused shapes, legal sizes up to B = 2^20 and L = FTHMC_MAX_L, workspace sizes monotone in every argument.  Device pointers are
 // never dereferenced by the host side, so they are stand-in addresses.
-#include "../../include/fthmc_hip.h"
-
-#include <stdio.h>
-#include <stdlib.h>
-
-static long calls = 0, refusals = 0;
+#include "walk.h"
 
 static int fail(const char* what, long a, long b, long c, long d, long rc) {
     fprintf(stderr, "loops_walk: %s (B %ld, L %ld, Rmax %ld, Tmax %ld) -> %ld\n", what, a, b, c, d, rc);
     return 1;
 }
-static double* dev(int k) { return (double*)(uintptr_t)(0x10000000ull + 0x1000000ull * (unsigned)k); }   // never dereferenced
-
-#define WANT(call, code, what, B, L, R, T) do { const int rc_ = (call); ++calls; if ((code) != FTHMC_OK) ++refusals; \
-    if (rc_ != (code)) return fail(what, B, L, R, T, rc_); } while (0)
 
 static int loops_call(int B, int L, int Rmax, int Tmax, int null_at, size_t ws_bytes) {
     return fthmc_wilson_loops(null_at == 0 ? NULL : dev(0), B, L, Rmax, Tmax, null_at == 1 ? NULL : dev(1), null_at == 2 ? NULL : dev(2),
                               null_at == 3 ? NULL : dev(3), ws_bytes, NULL);
 }
+
+static int want(int rc, int code, const char* what, long B, long L, long R, long T) { return answered(rc, code) ? 0 : fail(what, B, L, R, T, rc); }
 
 int main() {
     const size_t big = (size_t)1 << 62;
@@ -91,6 +84,5 @@ int main() {
             prevR = nR; prevT = nT;
         }
     }
-    printf("{\"calls\": %ld, \"refusals\": %ld}\n", calls, refusals);
-    return 0;
+    return walked();
 }

@@ -3,16 +3,9 @@
 // sanitizer build of the library (launches are no-ops there) and run as a program of its own.  Every refusal the header lists and
 // their precedence, the workspace rule, legal calls on both paths and the library's choice from the smallest to the largest shapes
 // and at the edges of the table's arguments.  Device pointers are never dereferenced by the host side: stand-in addresses.
-#include "../../include/fthmc_hip.h"
+#include "walk.h"
 
 #include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-static long calls = 0, refusals = 0;
-
-static double* dev(int k) { return (double*)(uintptr_t)(0x10000000ull + 0x1000000ull * (unsigned)k); }   // never dereferenced
-static void* wsp() { return (void*)(uintptr_t)0x90000000ull; }
 
 struct Call {
     int B = 4, L = 8, nstep = 2, integrator = 0, G = 2, nb = 11, path = 1;
@@ -38,14 +31,11 @@ static const char* const ENTRY[4] = {"fthmc_meta_trajectory", "fthmc_meta_deposi
 
 static int want(const Call& c, int entry, int code, const char* what) {
     const int rc = c.run(entry);
-    ++calls;
-    if (code != FTHMC_OK) ++refusals;
-    if (rc == code) return 0;
+    if (answered(rc, code)) return 0;
     fprintf(stderr, "meta_walk: %s: %s (B %d, L %d, G %d, nb %d, qmax %g, wall %g, w %g, nstep %d, integrator %d, path %d) -> %d, expected %d\n",
             ENTRY[entry], what, c.B, c.L, c.G, c.nb, c.qmax, c.wall, c.w, c.nstep, c.integrator, c.path, rc, code);
     return 1;
 }
-#define WANT(c, entry, code, what) do { if (want((c), (entry), (code), (what))) return 1; } while (0)
 
 int main() {
     const double inf = INFINITY, nan_ = NAN;
@@ -139,6 +129,5 @@ int main() {
                     if (path == 0) { WANT(c, 1, FTHMC_OK, "a legal deposit refused"); WANT(c, 2, FTHMC_OK, "a legal force call refused"); WANT(c, 3, FTHMC_OK, "a legal action call refused"); }
                 }
         }
-    printf("{\"calls\": %ld, \"refusals\": %ld}\n", calls, refusals);
-    return 0;
+    return walked();
 }

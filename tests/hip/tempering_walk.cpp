@@ -4,23 +4,16 @@
 // Every refusal the header lists, then legal sizes up to K M = 2^20 and every branch of the two trajectory calls.  Device
 // pointers are never dereferenced by the host side, so they are stand-in addresses; the one HOST array (the ladder handed to
 // fthmc_ladder_init) is a heap block of exactly K doubles, so a read past it is a heap overflow the sanitizer reports.
-#include "../../include/fthmc_hip.h"
+#include "walk.h"
 
 #include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-static long calls = 0, refusals = 0;
 
 static int fail(const char* what, long a, long b, int rc) {
     fprintf(stderr, "tempering_walk: %s (%ld, %ld) -> %d\n", what, a, b, rc);
     return 1;
 }
-static double* dev(int k) { return (double*)(uintptr_t)(0x10000000ull + 0x1000000ull * (unsigned)k); }   // never dereferenced
 static int32_t* devi(int k) { return (int32_t*)dev(k); }
-
-#define WANT(call, code, what, a, b) do { const int rc_ = (call); ++calls; if ((code) != FTHMC_OK) ++refusals; \
-    if (rc_ != (code)) return fail(what, (long)(a), (long)(b), rc_); } while (0)
+static int want(int rc, int code, const char* what, long a, long b) { return answered(rc, code) ? 0 : fail(what, a, b, rc); }
 
 static int swap_call(int K, int M, int parity, int null_at) {
     const double* p[3] = {dev(0), dev(1), dev(2)};
@@ -139,6 +132,5 @@ int main() {
     }
     WANT(ft_call(1 << 20, 8, 1, NULL, 0, FTHMC_MODE_MD, 1, dev(11), big, NULL), FTHMC_OK, "ft: B = 2^20 refused", 1 << 20, 8);
     WANT(hmc_call(1 << 20, 8, 2, 1, dev(11), big, 0), FTHMC_OK, "hmc: B = 2^20 refused", 1 << 20, 8);
-    printf("{\"calls\": %ld, \"refusals\": %ld}\n", calls, refusals);
-    return 0;
+    return walked();
 }

@@ -1,5 +1,5 @@
 """The numpy side of the hard-input metadynamics tests (tests/test_meta_hard.py, tests/test_z_meta_hard_gpu.py): the shapes at which
-the launch geometry of fthmc_amd/csrc/meta.hip and of meta_trajectory_seq (csrc/api.hip) changes, stencil_cases' hard inputs, a long
+the launch geometry of fthmc_amd/csrc/meta.hip and of the biased plain sequence (hmc_trajectory_call, csrc/api.hip) changes, stencil_cases' hard inputs, a long
 double reference of every operation that carries its own per-site / per-chain error bound, a float64 twin in the kernels' operation
 and summation order, and the named mutants of the twin.  Built on meta_cases (Table: rows, geometry, deposit; the definitions and
 trajectory(), against which the reference here is cross-checked on the CPU), stencil_cases (the per-operation bound forms, SLACK, the
@@ -471,7 +471,7 @@ def t_action(x, beta, tab, mutant=None):
 
 
 def t_energy(x, v, beta, tab, mutant=None):
-    """meta_trajectory_seq's energy: the plain H = S + K / 2 (stencil_cases.t_energy), then k_meta_energy: H + V, (Q_m, V).
+    """the biased plain sequence's energy: the plain H = S + K / 2 (stencil_cases.t_energy), then k_meta_energy: H + V, (Q_m, V).
       energy_second_block   chains >= 256 (the second workgroup of k_meta_energy) keep H without V"""
     h = SC.t_energy(x, v, beta)
     q, V, _ = t_bias(tab, t_sums(x, mutant)[0], mutant)
@@ -482,7 +482,7 @@ def t_energy(x, v, beta, tab, mutant=None):
 
 
 def t_trajectory(x, v, u, beta, name, dt, nstep, tab, mutant=None):
-    """meta_trajectory_seq, launch by launch -> dict(H0, H1, dH, acc, x_new, qm, vbias; x_prop: the regularized end point of every
+    """the biased plain sequence (hmc_trajectory_call with its bias), launch by launch -> dict(H0, H1, dH, acc, x_new, qm, vbias; x_prop: the regularized end point of every
     chain, which the device hands out only where it accepts).
       select_proposed   qm / vbias of the proposed end point, whatever the accept"""
     b0, stages = IC.schedule(name, dt, nstep)

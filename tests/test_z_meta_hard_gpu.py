@@ -1,4 +1,4 @@
-"""GPU tests that hold the metadynamics kernels (csrc/meta.hip, meta_trajectory_seq in csrc/api.hip) per site and per chain at their
+"""GPU tests that hold the metadynamics kernels (csrc/meta.hip, the biased hmc_trajectory_call in csrc/api.hip) per site and per chain at their
 launch edges, on hard inputs, inside bounds derived from the inputs (tests/meta_hard_cases.py; tests/test_meta_hard.py shows on the
 CPU that the float64 twin meets every bound with no chain and no lookup left out, and that twelve named defects do not).
 

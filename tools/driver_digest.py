@@ -4,7 +4,10 @@ checkout of another commit:  python3 tools/driver_digest.py > digest.json  there
 One digest per history key (the per-trajectory entries stacked, as raw little-endian bytes with dtype and shape), per final field,
 of the ft_run log's text and of the metadynamics table.  'dt' is a time and is left out; nothing else is.
 The cases are the smallest that reach every branch of the drivers' host code (captured and eager, batch and single chain, a second
-run from x_last, two chain groups, loops every third trajectory, instanton hits, two metadynamics phases, a tempering tail)."""
+run from x_last, two chain groups, loops every third trajectory, instanton hits, two metadynamics phases, a tempering tail); behind
+them the two trajectory sequences of csrc/api.hip through ops, on the branches the drivers do not reach (ops/...: B = 4, two table
+rows of two chains; the sequenced plain path with a fresh x_new and with x itself; the flowed tuned, generic-net and no-layer branches
+with and without a carried state; per-chain beta without layers)."""
 import hashlib, json, os, sys, tempfile
 import numpy as np
 import torch
@@ -14,10 +17,12 @@ from fthmc_amd.config import Param, TrainConfig, lfConfig
 from fthmc_amd.ft_hmc import FieldTransformation
 from fthmc_amd.hmc import run_hmc
 from fthmc_amd.local import run_local
-from fthmc_amd.meta import MetaPotential, run_meta
+from fthmc_amd import ops
+from fthmc_amd.meta import MetaPotential, run_ft_meta, run_meta
 from fthmc_amd.tempering import run_tempered
 from fthmc_amd.utils import layers as LY
 from fthmc_amd.utils import qed_helpers as qed
+from oracle import ref_cpu as R
 
 OUT = {}
 
@@ -119,6 +124,73 @@ def meta_case():
         put(f'{tag}/table', pot.numpy())
 
 
+def ft_meta_case():
+    for small in (True, False):
+        ops.set_small_path(small)
+        try:
+            for graph in (True, False):
+                torch.manual_seed(108)
+                _, model = flow(8, 3.0, 2, 6)
+                pot = MetaPotential(41, 2.0, 10.0, groups=2)
+                par = Param(beta=3.0, L=8, tau=0.6, nstep=3, ntraj=7, nrun=2, seed=5)
+                fields, hs, pot = run_ft_meta(par, model.layers, x=start(6, 8, 10), potential=pot, n_build=9, w=0.05, integrator='omelyan',
+                                              use_graph=graph)
+                tag = f'run_ft_meta/{"small" if small else "tiled"}/{"graph" if graph else "eager"}'
+                for n, h in hs.items():
+                    put_history(f'{tag}/{n}', h)
+                    put(f'{tag}/{n}/field', fields[n])
+                put(f'{tag}/table', pot.numpy())
+        finally:
+            ops.set_small_path(True)
+
+
+def ops_cases():
+    B, G, beta, dt, nstep = 4, 2, 2.0, 0.1, 2
+    g = torch.Generator().manual_seed(109)
+    rough = torch.cumsum(6 * torch.rand(G, 41, generator=g, dtype=torch.float64) - 3, dim=1).cuda()
+    tables = {'zero': (torch.zeros(G, 11, dtype=torch.float64).cuda(), 3.0, 0.0), 'rough': (rough, 2.0, 10.0)}
+
+    def draw(L, amp):
+        x = (amp * (2 * torch.rand(B, 2, L, L, generator=g, dtype=torch.float64) - 1)).cuda()
+        return x, torch.randn(B, 2, L, L, generator=g, dtype=torch.float64).cuda(), torch.rand(B, generator=g, dtype=torch.float64).cuda()
+
+    def put_all(tag, r):
+        for k in sorted(r):
+            put(f'{tag}/{k}', r[k])
+    for integ in ('leapfrog', 'force_gradient'):
+        x, v, u = draw(8, 1.5)
+        for tk, tab in tables.items():
+            put_all(f'ops/meta/{integ}/{tk}/fresh', ops.meta_trajectory(x, v, u, beta, dt, nstep, *tab, integrator=integ, path=2))
+            xa = x.clone()
+            put_all(f'ops/meta/{integ}/{tk}/alias', ops.meta_trajectory(xa, v, u, beta, dt, nstep, *tab, integrator=integ, path=2, out={'x_new': xa}))
+        put_all(f'ops/hmc/{integ}/L128', ops.hmc_trajectory(*draw(128, 0.3), beta, dt, nstep, integrator=integ))
+        bb = torch.tensor([1.5, 2.0, 2.5, 3.0], dtype=torch.float64).cuda()
+        a = ops.ft_trajectory(x, v, u, None, 0, bb, dt, nstep, integrator=integ)
+        put_all(f'ops/ft_pb_nolayers/{integ}/fresh', a)
+        put_all(f'ops/ft_pb_nolayers/{integ}/carried', ops.ft_trajectory(a['x_new'].clone(), v, u, None, 0, bb, dt, nstep, integrator=integ,
+                                                                         state_in=a['state'].clone()))
+    ops.set_small_path(False)
+    try:
+        for name, L, nl, arch in (('tuned', 8, 2, None), ('tuned', 20, 2, None), ('generic', 8, 2, ((4, 6, 5), 5, 3)), ('nolayers', 8, 0, None)):
+            wg = torch.Generator().manual_seed(110)
+            kw = dict(hidden=arch[0], k=arch[1], n_mix=arch[2]) if arch else {}
+            w = ops.pack_weights(R.default_flow(nl, wg, **kw), device='cuda') if nl else None
+            for integ in ('leapfrog', 'force_gradient'):
+                x, v, u = draw(L, 1.5)
+                for tk, tab in tables.items():
+                    a = ops.ft_meta_trajectory(x, v, u, w, nl, beta, dt, nstep, *tab, integrator=integ, arch=arch)
+                    put_all(f'ops/ft_meta/{name}-L{L}/{integ}/{tk}/fresh', a)
+                    put_all(f'ops/ft_meta/{name}-L{L}/{integ}/{tk}/carried',
+                            ops.ft_meta_trajectory(a['x_new'].clone(), v, u, w, nl, beta, dt, nstep, *tab, integrator=integ, arch=arch,
+                                                   state_in=a['state'].clone()))
+                a = ops.ft_trajectory(x, v, u, w, nl, beta, dt, nstep, integrator=integ, arch=arch)
+                put_all(f'ops/ft/{name}-L{L}/{integ}/fresh', a)
+                put_all(f'ops/ft/{name}-L{L}/{integ}/carried', ops.ft_trajectory(a['x_new'].clone(), v, u, w, nl, beta, dt, nstep, integrator=integ,
+                                                                                 arch=arch, state_in=a['state'].clone()))
+    finally:
+        ops.set_small_path(True)
+
+
 def tempered_case():
     for captured in (True, False):
         torch.manual_seed(106)
@@ -141,7 +213,7 @@ def trainer_case():
 
 
 if __name__ == '__main__':
-    for case in (ft_cases, ft_run_case, hmc_case, local_case, meta_case, tempered_case, trainer_case):
+    for case in (ft_cases, ft_run_case, hmc_case, local_case, meta_case, ft_meta_case, tempered_case, trainer_case, ops_cases):
         case()
     torch.cuda.synchronize()
     print(json.dumps(OUT, sort_keys=True))
