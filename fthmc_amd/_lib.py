@@ -117,6 +117,8 @@ SIGNATURES['fthmc_wilson_loops_ws_bytes'] = [c_int, c_int, c_int, c_int]
 SIGNATURES['fthmc_wilson_loops'] = [_D, c_int, c_int, c_int, c_int, _D, _D, _P, c_size_t, _P]
 # heatbath / overrelaxation sweeps: x, B, L, beta, beta_b, seeds, n_hb, n_or, nsweep, sweep0, classes, x_out, stream
 SIGNATURES['fthmc_local_update'] = [_D, c_int, c_int, c_double, _D, _D, c_int, c_int, c_int, ctypes.c_int64, c_int, _D, _P]
+# annealing: x, B, L, betas (device), n_step, seeds, n_hb, n_or, nsweep, sweep0, path, work_in, x_out, work_out, c_trace, stream
+SIGNATURES['fthmc_anneal'] = [_D, c_int, c_int, _D, c_int, _D, c_int, c_int, c_int, ctypes.c_int64, c_int, _D, _D, _D, _D, _P]
 # instanton hits: x, B, L, beta, beta_b, seeds, n_hit, hit0, path, x_out, k_out, nacc_out, cs_out, ws, ws_bytes, stream
 SIGNATURES['fthmc_instanton_ws_bytes'] = [c_int, c_int, c_int]
 SIGNATURES['fthmc_instanton_hit'] = [_D, c_int, c_int, c_double, _D, _D, c_int, ctypes.c_int64, c_int, _D, _D, _D, _D, _P, c_size_t, _P]

@@ -974,6 +974,23 @@ int fthmc_local_update(const double* x, int B, int L, double beta, const double*
     return launch_local_update(x, B, L, beta, beta_b, seeds, n_hb, n_or, nsweep, (uint32_t)sweep0, classes, x_out, resident, ft_stream(stream));
 }
 
+// Annealing (local.hip): the argument checks and the choice of the path; no workspace
+int fthmc_anneal(const double* x, int B, int L, const double* betas, int n_step, const int64_t* seeds, int n_hb, int n_or, int nsweep,
+                 int64_t sweep0, int path, const double* work_in, double* x_out, double* work_out, double* c_trace, void* stream) {
+    if (!x || !x_out || !betas || !work_out || bad_shape(B, L) || n_step < 0 || n_step > AN_MAX_STEPS || n_hb < 0 || n_or < 0 || nsweep < 0 ||
+        sweep0 < 0 || path < 0 || path > 2)
+        return FTHMC_ERR_ARG;
+    if (n_hb > 0 && !seeds) return FTHMC_ERR_ARG;                                       // overrelaxation draws nothing
+    if (n_step > 0 && n_hb + n_or == 0) return FTHMC_ERR_ARG;                           // a step that moves no link
+    if (path == 1 && L > LU_MAXL) return FTHMC_ERR_ARG;
+    // the heatbath-sweep index is one 32-bit word of the Philox counter: every index the ramp uses must fit
+    const long long per = (long long)nsweep * (long long)n_hb;                          // < 2^62
+    if (sweep0 > (1LL << 32) || (n_step > 0 && per > ((1LL << 32) - sweep0) / n_step)) return FTHMC_ERR_ARG;
+    const bool resident = path == 1 || (path == 0 && L <= LU_MAXL && get_small_path() != 0);
+    return launch_anneal(x, B, L, betas, n_step, seeds, n_hb, n_or, nsweep, (uint32_t)sweep0, work_in, x_out, work_out, c_trace, resident,
+                         ft_stream(stream));
+}
+
 // Instanton hits (topo.hip): the argument checks, the choice of the launch shape and the workspace of the split one:
 // part[B][nw][2] doubles | k[B] int32
 static bool instanton_split(int B, int L, int path) { return path == 2 || (path == 0 && B < 64 && L >= 128); }

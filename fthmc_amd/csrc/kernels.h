@@ -117,6 +117,12 @@ constexpr int LU_MAX_ATTEMPTS = 64;           // rejection attempts of one heatb
 // resident: the one-launch kernel (L <= LU_MAXL), else one launch per class and sweep; beta_b: per-chain beta or null
 int launch_local_update(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hb, int n_or,
                         int nsweep, uint32_t sweep0, int classes, double* x_out, bool resident, hipStream_t s);
+// annealing (fthmc_anneal): n_step steps of W += (betas[k] - betas[k+1]) sum cos P, then nsweep compound sweeps at
+// betas[k+1] (a device array [n_step + 1]); resident: the whole ramp in one launch (L <= LU_MAXL), else per step a work kernel and the
+// class kernels; work_in, c_trace ([B][n_step + 1]): optional; x_out may be x, work_out may be work_in
+constexpr int AN_MAX_STEPS = 65536;
+int launch_anneal(const double* x, int B, int L, const double* betas, int n_step, const int64_t* seeds, int n_hb, int n_or, int nsweep,
+                  uint32_t sweep0, const double* work_in, double* x_out, double* work_out, double* c_trace, bool resident, hipStream_t s);
 
 // ---- topo.hip: instanton hits, the Metropolis update across topological sectors (fthmc_instanton_hit)
 // split: one wave per workgroup + decision + apply (part: [B][chain_threads(L) / 64][2] doubles, kbuf: [B] int32) in place of one

@@ -108,11 +108,11 @@ __device__ __forceinline__ void lu_link(int mu, int p, int e, int L, int* i, int
 }
 
 // ---------------------------------------------------------------- any L: one launch per class, in place, the chain on grid x
-template <bool HEAT, bool PB>
-__global__ __launch_bounds__(256) void k_local_class(double* __restrict__ x, int L, typename BetaArg<PB>::type beta_,
-                                                     const int64_t* __restrict__ seeds, int mu, int p, uint32_t sweep) {
+// the links of class (mu, p) of chain b that this workgroup of the launch owns (k_local_class, k_anneal_class)
+template <bool HEAT>
+__device__ __forceinline__ void lu_class_links(double* __restrict__ x, int L, double beta, const int64_t* __restrict__ seeds, int mu, int p,
+                                               uint32_t sweep) {
     const int b = blockIdx.x, n = L * L;
-    const double beta = beta_at(beta_, b);
     uint32_t k0 = 0u, k1 = 0u;
     if (HEAT) { const uint64_t sd = (uint64_t)seeds[b]; k0 = (uint32_t)sd; k1 = (uint32_t)(sd >> 32); }
     double* xb = x + (size_t)b * 2 * n;
@@ -128,6 +128,12 @@ __global__ __launch_bounds__(256) void k_local_class(double* __restrict__ x, int
     }
 }
 
+template <bool HEAT, bool PB>
+__global__ __launch_bounds__(256) void k_local_class(double* __restrict__ x, int L, typename BetaArg<PB>::type beta_,
+                                                     const int64_t* __restrict__ seeds, int mu, int p, uint32_t sweep) {
+    lu_class_links<HEAT>(x, L, beta_at(beta_, (int)blockIdx.x), seeds, mu, p, sweep);
+}
+
 // ---------------------------------------------------------------- L <= LU_MAXL: the whole call in one launch, one workgroup per chain
 // Both planes live in LDS, each split by the PARITY OF THE COLUMN: slot(mu, i, j) = mu 2 H + (j & 1) H + i L / 2 + (j >> 1),
 // H = L^2 / 2 + 16.  Then
@@ -140,38 +146,57 @@ __global__ __launch_bounds__(256) void k_local_class(double* __restrict__ x, int
 //     pays a two-way conflict on some of them: its call is launch latency, not LDS).
 // A thread keeps the coordinates of its links (formed once, two divisions per link) and owns the same links of a class throughout.
 // The six neighbour slots are re-formed from them at every update (wrap selects and adds, ~30 integer instructions against ~700 of a
-// heatbath draw): kept, they would be 7 indices x 4 classes x LU_PER links = 56 registers on top of the 121 the kernel holds, beyond
-// the 128 a lane of a 1024-thread workgroup may have.
+// heatbath draw): kept, they would be 7 indices x 4 classes x LU_PER links = 56 registers on top of the 123 the kernel holds (126 with the
+// annealing step loop around it), beyond the 128 a lane of a 1024-thread workgroup may have.
 constexpr int LU_NT = 1024, LU_PER = LU_MAXL * LU_MAXL / 2 / LU_NT, LU_PAD = 16;
 static_assert(LU_PER * LU_NT * 2 == LU_MAXL * LU_MAXL, "k_local_resident: LU_PER links per thread and class cover L = LU_MAXL");
+constexpr int LU_LDS = 2 * (LU_MAXL * LU_MAXL + 2 * LU_PAD);       // doubles of a chain in LDS
 
-template <bool PB>
-__global__ __launch_bounds__(LU_NT) void k_local_resident(const double* x, int L, typename BetaArg<PB>::type beta_,
-                                                          const int64_t* __restrict__ seeds, int n_hb, int n_or, int nsweep,
-                                                          uint32_t sweep0, int classes, double* x_out) {     // x_out may be x
-    __shared__ double sx[2 * (LU_MAXL * LU_MAXL + 2 * LU_PAD)];
-    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, n = L * L, hl = L >> 1, H = n / 2 + LU_PAD;
-    const double beta = beta_at(beta_, b);
-    uint32_t k0 = 0u, k1 = 0u;
-    if (n_hb > 0) { const uint64_t sd = (uint64_t)seeds[b]; k0 = (uint32_t)sd; k1 = (uint32_t)(sd >> 32); }
-    auto slot = [&](int mu, int i, int j) { return mu * 2 * H + (j & 1) * H + i * hl + (j >> 1); };
-    const double* xb = x + (size_t)b * 2 * n;
+// a thread per link of a class, whole waves, at most LU_NT: the workgroup of the one-launch kernels (and of the annealing work kernel)
+inline int lu_threads(int L) {
+    const int nt = (L * L / 2 + FT_WAVE - 1) / FT_WAVE * FT_WAVE;
+    return nt > LU_NT ? LU_NT : nt;
+}
+
+struct LuLds {                                                      // the slot layout above
+    int L, n, hl, H;
+    __device__ __forceinline__ explicit LuLds(int L_) : L(L_), n(L_ * L_), hl(L_ >> 1), H(L_ * L_ / 2 + LU_PAD) {}
+    __device__ __forceinline__ int slot(int mu, int i, int j) const { return mu * 2 * H + (j & 1) * H + i * hl + (j >> 1); }
+};
+// a chain between global memory (row-major planes) and LDS
+__device__ __forceinline__ void lu_lds_load(double* sx, const LuLds& g, const double* xb, int tid, int nt) {
+    const int n = g.n;
     for (int s = tid; s < 2 * n; s += nt) {
-        const int mu = s >= n ? 1 : 0, t = s - mu * n, i = t / L, j = t - i * L;
-        sx[slot(mu, i, j)] = xb[s];
+        const int mu = s >= n ? 1 : 0, t = s - mu * n, i = t / g.L, j = t - i * g.L;
+        sx[g.slot(mu, i, j)] = xb[s];
     }
-    int r0[LU_PER], q0[LU_PER], r1[LU_PER], c1[LU_PER];             // link e = tid + k nt: (row, half column) as x0, (half row, column) as x1
+}
+__device__ __forceinline__ void lu_lds_store(const double* sx, const LuLds& g, double* xo, int tid, int nt) {
+    const int n = g.n;
+    for (int s = tid; s < 2 * n; s += nt) {
+        const int mu = s >= n ? 1 : 0, t = s - mu * n, i = t / g.L, j = t - i * g.L;
+        xo[s] = sx[g.slot(mu, i, j)];
+    }
+}
+// the links a thread owns: link e = tid + k nt of every class, as (row, half column) of x0 and (half row, column) of x1
+struct LuOwn {
+    int r0[LU_PER], q0[LU_PER], r1[LU_PER], c1[LU_PER];
     bool have[LU_PER];
+    __device__ __forceinline__ LuOwn(const LuLds& g, int tid, int nt) {
 #pragma unroll
-    for (int k = 0; k < LU_PER; ++k) {
-        const int e = tid + k * nt;
-        have[k] = e < n / 2;
-        const int ee = have[k] ? e : 0;
-        r0[k] = ee / hl; q0[k] = ee - r0[k] * hl;
-        r1[k] = ee / L; c1[k] = ee - r1[k] * L;
+        for (int k = 0; k < LU_PER; ++k) {
+            const int e = tid + k * nt;
+            have[k] = e < g.n / 2;
+            const int ee = have[k] ? e : 0;
+            r0[k] = ee / g.hl; q0[k] = ee - r0[k] * g.hl;
+            r1[k] = ee / g.L; c1[k] = ee - r1[k] * g.L;
+        }
     }
-    __syncthreads();
-    uint32_t sweep = sweep0;
+};
+// nsweep compound sweeps of the chain in LDS at one beta, from heatbath sweep `sweep` on -> the next heatbath sweep's index.
+// Behind a barrier, and every class ends in one
+__device__ __forceinline__ uint32_t lu_lds_sweeps(double* sx, const LuLds& g, const LuOwn& o, double beta, uint32_t k0, uint32_t k1, int n_hb,
+                                                  int n_or, int nsweep, uint32_t sweep, int classes) {
     for (int sw = 0; sw < nsweep; ++sw)
         for (int h = 0; h < n_hb + n_or; ++h) {
             const bool heat = h < n_hb;
@@ -180,14 +205,14 @@ __global__ __launch_bounds__(LU_NT) void k_local_resident(const double* x, int L
                 const int mu = cl >> 1, p = cl & 1;
 #pragma unroll
                 for (int k = 0; k < LU_PER; ++k)
-                    if (have[k]) {
-                        const int i = mu == 0 ? r0[k] : 2 * r1[k] + p, j = mu == 0 ? 2 * q0[k] + p : c1[k];
-                        const LuNb nb = lu_neighbours(mu, i, j, L);
+                    if (o.have[k]) {
+                        const int i = mu == 0 ? o.r0[k] : 2 * o.r1[k] + p, j = mu == 0 ? 2 * o.q0[k] + p : o.c1[k];
+                        const LuNb nb = lu_neighbours(mu, i, j, g.L);
                         double v[6];
 #pragma unroll
-                        for (int q = 0; q < 6; ++q) v[q] = sx[slot(nb.pl[q], nb.r[q], nb.c[q])];
-                        const int own = slot(mu, i, j);
-                        const uint32_t site = (uint32_t)(i * L + j);
+                        for (int q = 0; q < 6; ++q) v[q] = sx[g.slot(nb.pl[q], nb.r[q], nb.c[q])];
+                        const int own = g.slot(mu, i, j);
+                        const uint32_t site = (uint32_t)(i * g.L + j);
                         sx[own] = heat ? lu_update<true>(sx[own], mu, v, beta, k0, k1, site, sweep)
                                        : lu_update<false>(sx[own], mu, v, beta, k0, k1, site, sweep);
                     }
@@ -195,11 +220,119 @@ __global__ __launch_bounds__(LU_NT) void k_local_resident(const double* x, int L
             }
             if (heat) ++sweep;
         }
-    double* xo = x_out + (size_t)b * 2 * n;
-    for (int s = tid; s < 2 * n; s += nt) {
-        const int mu = s >= n ? 1 : 0, t = s - mu * n, i = t / L, j = t - i * L;
-        xo[s] = sx[slot(mu, i, j)];
+    return sweep;
+}
+
+template <bool PB>
+__global__ __launch_bounds__(LU_NT) void k_local_resident(const double* x, int L, typename BetaArg<PB>::type beta_,
+                                                          const int64_t* __restrict__ seeds, int n_hb, int n_or, int nsweep,
+                                                          uint32_t sweep0, int classes, double* x_out) {     // x_out may be x
+    __shared__ double sx[LU_LDS];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, n = L * L;
+    const double beta = beta_at(beta_, b);
+    uint32_t k0 = 0u, k1 = 0u;
+    if (n_hb > 0) { const uint64_t sd = (uint64_t)seeds[b]; k0 = (uint32_t)sd; k1 = (uint32_t)(sd >> 32); }
+    const LuLds g(L);
+    lu_lds_load(sx, g, x + (size_t)b * 2 * n, tid, nt);
+    const LuOwn own(g, tid, nt);
+    __syncthreads();
+    lu_lds_sweeps(sx, g, own, beta, k0, k1, n_hb, n_or, nsweep, sweep0, classes);
+    lu_lds_store(sx, g, x_out + (size_t)b * 2 * n, tid, nt);
+}
+
+// ---------------------------------------------------------------- annealing: a ramp of beta with the work it costs (fthmc_anneal, 4.17)
+// Step k of a chain: C_k = sum cos P(x_k), W += (beta_k - beta_{k+1}) C_k, then the compound sweeps at beta_{k+1}.  The sum is stated
+// once, over a reader of the links: thread tid of nt adds the sites tid, tid + nt, ... from 0.0, ft_block_sum adds the threads.  The
+// one-launch kernel reads LDS and the work kernel of the sequenced path global memory, with the same nt (lu_threads): the same
+// numbers in the same order, the same bits -- the rule of topo.hip's two shapes.
+template <class At>
+__device__ __forceinline__ double an_cos_sum(At at, int L, int tid, int nt) {
+#pragma clang fp contract(off)
+    const int n = L * L;
+    double c = 0.0;
+    for (int s = tid; s < n; s += nt) {
+        const int i = s / L, j = s - i * L;
+        const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
+        const double P = ((at(0, i, j) + at(1, ip, j)) - at(0, i, jp)) - at(1, i, j);
+        double sn, cs;
+        lu_sincos(P, &sn, &cs);
+        c += cs;
     }
+    return c;
+}
+// the work of one step: the difference, the product and the sum each rounded
+__device__ __forceinline__ double an_work(double W, double beta_k, double beta_next, double C) {
+#pragma clang fp contract(off)
+    const double d = beta_k - beta_next;
+    const double t = d * C;
+    return W + t;
+}
+// a value every lane holds alike, moved to scalar registers: beta of a step is read from memory inside the step loop, where the
+// compiler cannot prove the load uniform AND unclobbered, and as a vector value it would cost the heatbath two registers
+__device__ __forceinline__ double an_uniform(double v) {
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// The whole ramp in one launch: k_local_resident's walk inside a step loop.  The sum runs between two barriers out of LDS with
+// nothing of a link alive but the owner's coordinates.  ft_block_sum leaves C_k in every lane, so every lane forms the same W: it is
+// kept as a scalar pair (an_uniform) from work_in to the one store of work_out -- as a vector value it is the two registers that
+// push the heatbath's 123 beyond what the allocator can hold without scratch (measured: 128 + 12 bytes of scratch, against 126 and
+// none).  betas[k + 1] is one address for the workgroup: every lane reads it and an_uniform makes it the scalar the walk takes, so no
+// lane has to broadcast it through LDS
+__global__ __launch_bounds__(LU_NT) void k_anneal_resident(const double* x, int L, const double* betas, int n_step,
+                                                           const int64_t* __restrict__ seeds, int n_hb, int n_or, int nsweep, uint32_t sweep0,
+                                                           const double* work_in, double* x_out, double* work_out,
+                                                           double* c_trace) {     // x_out may be x, work_out may be work_in
+    __shared__ double sx[LU_LDS];
+    __shared__ double red[16];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, n = L * L;
+    uint32_t k0 = 0u, k1 = 0u;
+    if (n_hb > 0) { const uint64_t sd = (uint64_t)seeds[b]; k0 = (uint32_t)sd; k1 = (uint32_t)(sd >> 32); }
+    const LuLds g(L);
+    lu_lds_load(sx, g, x + (size_t)b * 2 * n, tid, nt);
+    const LuOwn own(g, tid, nt);
+    double W = an_uniform(work_in ? work_in[b] : 0.0);
+    double beta = an_uniform(betas[0]);
+    uint32_t sweep = sweep0;
+    __syncthreads();
+    for (int k = 0;; ++k) {
+        double C = an_cos_sum([&](int mu, int i, int j) { return sx[g.slot(mu, i, j)]; }, L, tid, nt);
+        C = ft_block_sum(C, red);
+        if (tid == 0 && c_trace) c_trace[(size_t)b * ((size_t)n_step + 1) + k] = C;
+        if (k == n_step) break;
+        const double beta_next = an_uniform(betas[k + 1]);
+        W = an_uniform(an_work(W, beta, beta_next, C));
+        beta = beta_next;
+        sweep = lu_lds_sweeps(sx, g, own, beta, k0, k1, n_hb, n_or, nsweep, sweep, 15);
+    }
+    if (tid == 0) work_out[b] = W;
+    lu_lds_store(sx, g, x_out + (size_t)b * 2 * n, tid, nt);
+}
+
+// The sequenced path, any L.  Its work kernel: one workgroup of lu_threads(L) per chain, step k's C out of global memory;
+// update: W = win[b] (null: 0) + (betas[0] - betas[1]) C, else W is copied (the last entry of the trace, n_step = 0)
+__global__ __launch_bounds__(LU_NT) void k_anneal_work(const double* __restrict__ x, int L, const double* __restrict__ betas, int update,
+                                                       const double* win, double* wout, double* c_out, size_t c_stride) {
+    __shared__ double red[16];
+    const int b = blockIdx.x, n = L * L;
+    const double* x0 = x + (size_t)b * 2 * n;
+    double C = an_cos_sum([&](int mu, int i, int j) { return x0[(size_t)mu * n + (size_t)i * L + j]; }, L, (int)threadIdx.x, (int)blockDim.x);
+    C = ft_block_sum(C, red);
+    if (threadIdx.x == 0) {
+        double W = win ? win[b] : 0.0;
+        if (update) W = an_work(W, betas[0], betas[1], C);
+        wout[b] = W;
+        if (c_out) c_out[(size_t)b * c_stride] = C;
+    }
+}
+// ... and its class kernels: k_local_class' links at the beta the step's entry of the schedule holds
+template <bool HEAT>
+__global__ __launch_bounds__(256) void k_anneal_class(double* __restrict__ x, int L, const double* __restrict__ beta_dev,
+                                                      const int64_t* __restrict__ seeds, int mu, int p, uint32_t sweep) {
+    lu_class_links<HEAT>(x, L, *beta_dev, seeds, mu, p, sweep);
 }
 
 template <bool HEAT>
@@ -220,8 +353,7 @@ int launch_local_update(const double* x, int B, int L, double beta, const double
                         int nsweep, uint32_t sweep0, int classes, double* x_out, bool resident, hipStream_t s) {
     if (resident) {
         if (L > LU_MAXL) return FTHMC_ERR_UNSUPPORTED;
-        int nt = (L * L / 2 + FT_WAVE - 1) / FT_WAVE * FT_WAVE;     // a thread per link of a class, whole waves, at most LU_NT
-        if (nt > LU_NT) nt = LU_NT;
+        const int nt = lu_threads(L);
         if (beta_b) hipLaunchKernelGGL(k_local_resident<true>, dim3(B), dim3(nt), 0, s, x, L, beta_b, seeds, n_hb, n_or, nsweep, sweep0, classes, x_out);
         else hipLaunchKernelGGL(k_local_resident<false>, dim3(B), dim3(nt), 0, s, x, L, beta, seeds, n_hb, n_or, nsweep, sweep0, classes, x_out);
         FT_LAUNCH_CHECK();
@@ -241,6 +373,45 @@ int launch_local_update(const double* x, int B, int L, double beta, const double
             }
             if (heat) ++sweep;
         }
+    return FTHMC_OK;
+}
+
+int launch_anneal(const double* x, int B, int L, const double* betas, int n_step, const int64_t* seeds, int n_hb, int n_or, int nsweep,
+                  uint32_t sweep0, const double* work_in, double* x_out, double* work_out, double* c_trace, bool resident, hipStream_t s) {
+    const int nt = lu_threads(L);
+    if (resident) {
+        if (L > LU_MAXL) return FTHMC_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(k_anneal_resident, dim3(B), dim3(nt), 0, s, x, L, betas, n_step, seeds, n_hb, n_or, nsweep, sweep0, work_in, x_out,
+                           work_out, c_trace);
+        FT_LAUNCH_CHECK();
+        return FTHMC_OK;
+    }
+    if (x_out != x && hipMemcpyAsync(x_out, x, (size_t)B * 2 * L * L * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return FTHMC_ERR_LAUNCH;
+    const size_t stride = (size_t)n_step + 1;
+    const long long blocks = ((long long)L * L / 2 + 255) / 256;
+    const dim3 grid((unsigned)B, (unsigned)(blocks > 65535 ? 65535 : blocks));
+    uint32_t sweep = sweep0;
+    for (int k = 0; k < n_step; ++k) {
+        hipLaunchKernelGGL(k_anneal_work, dim3(B), dim3(nt), 0, s, x_out, L, betas + k, 1, k == 0 ? work_in : work_out, work_out,
+                           c_trace ? c_trace + k : nullptr, stride);
+        FT_LAUNCH_CHECK();
+        for (int sw = 0; sw < nsweep; ++sw)
+            for (int h = 0; h < n_hb + n_or; ++h) {
+                const bool heat = h < n_hb;
+                for (int cl = 0; cl < 4; ++cl) {
+                    if (heat) hipLaunchKernelGGL(k_anneal_class<true>, grid, dim3(256), 0, s, x_out, L, betas + k + 1, seeds, cl >> 1, cl & 1, sweep);
+                    else hipLaunchKernelGGL(k_anneal_class<false>, grid, dim3(256), 0, s, x_out, L, betas + k + 1, seeds, cl >> 1, cl & 1, sweep);
+                    FT_LAUNCH_CHECK();
+                }
+                if (heat) ++sweep;
+            }
+    }
+    if (n_step == 0 || c_trace) {                                   // the final field's entry of the trace; n_step = 0: the work is copied
+        hipLaunchKernelGGL(k_anneal_work, dim3(B), dim3(nt), 0, s, x_out, L, betas + n_step, 0, n_step == 0 ? work_in : work_out, work_out,
+                           c_trace ? c_trace + n_step : nullptr, stride);
+        FT_LAUNCH_CHECK();
+    }
     return FTHMC_OK;
 }
 

@@ -433,6 +433,54 @@ def local_update(x, beta, seeds=None, n_hb: int = 1, n_or: int = 0, nsweep: int 
     return out
 
 
+def anneal(x, betas, seeds=None, n_hb: int = 1, n_or: int = 0, nsweep: int = 1, sweep0: int = 0, work=None, trace=False, path: int = 0,
+           out=None):
+    """An annealing ramp through the local updates with the work of every chain (C ABI fthmc_anneal) -> dict(x, work, trace).
+    betas: the schedule beta_0 .. beta_n, n + 1 entries: a float64 device tensor, read by the kernels when they run (a captured call
+    follows what the tensor holds at replay; finite entries >= 0 are then the caller's promise), or a sequence of numbers, checked
+    and uploaded once.  Step k adds (beta_k - beta_{k+1}) sum cos P(x_k) to the work and runs `nsweep` compound sweeps (`n_hb`
+    heatbath, `n_or` overrelaxation) at beta_{k+1}; the heatbath sweeps are those of local_update(..., sweep0 = sweep0 + k nsweep n_hb).
+    work: the work the chains arrive with, [B] (None: 0).  trace: True (or a [B, n + 1] tensor to write) for sum cos P of x_0 .. x_n.
+    path: 0 the library chooses, 1 the whole ramp in one launch (L <= 64), 2 per step a work kernel and the class kernels; the
+    same bits.  out: optional dict with 'x' (may be x) and 'work' (may be `work`) to write into.  exp(-work) is the importance
+    weight of x as a sample at beta_n when the start was drawn at beta_0.  Not differentiable."""
+    x = _field(x); B, _, L, _ = x.shape
+    if isinstance(betas, torch.Tensor):
+        bt = _dev(betas, 'betas').reshape(-1)
+        if bt.device != x.device:
+            raise FthmcError(f'betas: tensor lives on {bt.device}, x on {x.device}')
+    else:
+        host = [float(b) for b in betas]
+        if not all(math.isfinite(b) and b >= 0.0 for b in host):
+            raise ValueError('anneal: finite betas >= 0 expected')
+        bt = torch.tensor(host, dtype=torch.float64, device=x.device)
+    n_step = bt.numel() - 1
+    n_hb, n_or, nsweep, sweep0, path = int(n_hb), int(n_or), int(nsweep), int(sweep0), int(path)
+    if n_step < 0 or n_step > 65536 or min(n_hb, n_or, nsweep, sweep0) < 0 or path not in (0, 1, 2) or (n_step > 0 and n_hb + n_or == 0):
+        raise ValueError(f'anneal: 1 .. 65537 betas, counts and sweep0 >= 0, n_hb + n_or > 0 and path in 0 .. 2 expected, got {n_step + 1} '
+                         f'betas, n_hb={n_hb}, n_or={n_or}, nsweep={nsweep}, sweep0={sweep0}, path={path}')
+    if sweep0 + n_step * nsweep * n_hb > 2 ** 32:
+        raise ValueError(f'anneal: sweep0 + n_step nsweep n_hb = {sweep0 + n_step * nsweep * n_hb} is beyond 2^32')
+    if path == 1 and L > 64:
+        raise ValueError('anneal: path 1 serves L <= 64')
+    if n_hb > 0 and seeds is None:
+        raise ValueError('anneal: heatbath sweeps need per-chain seeds')
+    seeds = _seeds(seeds, B)
+    if work is not None:
+        _expect(work, B, 'work')
+    out = {} if out is None else out
+    xo = _out_like(out.get('x'), x, "out['x']")
+    wo = _out_vec(out, 'work', B, x)
+    tr = None
+    if isinstance(trace, torch.Tensor):
+        tr = _expect(trace, B * (n_step + 1), 'trace')
+    elif trace:
+        tr = torch.empty(B, n_step + 1, dtype=torch.float64, device=x.device)
+    check(_lib.load().fthmc_anneal(_p(x), B, L, _p(bt), n_step, _p(seeds), n_hb, n_or, nsweep, sweep0, path, _p(work), _p(xo), _p(wo),
+                                   _p(tr), _stream(x)), 'fthmc_anneal')
+    return {'x': xo, 'work': wo, 'trace': None if tr is None else tr.view(B, n_step + 1)}
+
+
 def instanton_ws_bytes(B: int, L: int, path: int = 0) -> int:
     """Scratch of instanton_hit: 0 where the path that (B, L, path) selects needs none."""
     return int(_lib.load().fthmc_instanton_ws_bytes(B, L, path))

@@ -205,6 +205,50 @@ def exact_charge_moment(beta: float, L: int, power: int = 2) -> float:
     return float((Q ** int(power) * p).sum())
 
 
+# ---------------------------------------------------------------- annealed importance sampling: the exact partition function, the work
+def exact_log_partition(beta: float, L: int, nmax: int = 40) -> float:
+    """log Z(beta) of 2D U(1) with the Wilson action on the periodic L x L lattice in the measure prod dx / 2 pi (Z(0) = 1):
+        Z = int prod dx / 2 pi  exp(beta sum cos P) = sum_n I_n(beta)^V,      log Z = V log I_0 + log sum_n (I_n / I_0)^V,
+    the denominator of `exact_loop_of_area` with its common factor put back.  log I_0 from the generating function at its maximum,
+    e^beta = I_0 + 2 sum_{n >= 1} I_n, with the ratios of `_log_bessel_ratios`: extended precision throughout (V log I_0 is 1077.30
+    at L = 16, beta = 6).  What <exp(-W)> of an annealing run from beta = 0 estimates (anneal.run_annealed)."""
+    beta, V = float(beta), int(L) * int(L)
+    if beta == 0.0:
+        return 0.0
+    N = nmax + 64 + int(2 * beta) + int(12 * np.sqrt(beta))                # I_n / I_0 ~ exp(-n^2 / 2 beta) beyond n ~ beta: < e^-70 at N
+    l = _log_bessel_ratios(beta, N)
+    log_i0 = np.longdouble(beta) - np.log1p(2 * np.exp(l[1:]).sum())
+    n = np.arange(-nmax, nmax + 1)
+    return float(V * log_i0 + np.log(np.exp(V * l[np.abs(n)]).sum()))      # l <= 0: the largest term is 1
+
+
+def jarzynski_log_mean(work, n_block: int = N_BLOCK):
+    """log < exp(-W) > over the chains of an annealing run -> (value, delete-one-block jackknife error): the estimate of
+    log Z(beta_1) / Z(beta_0) (Jarzynski's equality).  The smallest work is taken out before exponentiating; the chains are dealt
+    into `n_block` blocks (at most one per chain) as `reweighted_mean` deals its units."""
+    w = np.asarray(work, dtype=np.float64).reshape(-1)
+    if w.size == 0:
+        raise ValueError('jarzynski_log_mean: no work values')
+    w0 = w.min()
+    e = np.exp(-(w - w0))
+    nb = max(1, min(int(n_block), e.size))
+    parts = np.array_split(e, nb)
+    sums, cnts = np.array([c.sum() for c in parts]), np.array([c.size for c in parts], dtype=np.float64)
+    val = float(np.log(sums.sum() / cnts.sum()) - w0)
+    if nb < 2:
+        return val, float('nan')
+    rest = np.array([np.delete(sums, i).sum() for i in range(nb)])         # added, not subtracted: one block may carry all the weight
+    jk = np.log(rest / (cnts.sum() - cnts))
+    return val, float(np.sqrt((nb - 1) * np.mean((jk - jk.mean()) ** 2)))
+
+
+def work_ess(work) -> float:
+    """The effective sample size (sum w)^2 / sum w^2 of the weights w = exp(-W): between 1 and the number of chains."""
+    w = np.asarray(work, dtype=np.float64).reshape(-1)
+    e = np.exp(-(w - w.min()))
+    return float(e.sum() ** 2 / (e * e).sum())
+
+
 def reweighted_mean(values, vbias, n_block: int = N_BLOCK):
     """Unbiased mean of an observable sampled under a frozen metadynamics bias (meta.run_meta):
         <O> = sum O e^{V} / sum e^{V},      V = `vbias`, the bias potential at each sample's Q_m

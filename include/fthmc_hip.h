@@ -445,6 +445,33 @@ int fthmc_wilson_loops(const double* x, int B, int L, int Rmax, int Tmax, double
 int fthmc_local_update(const double* x, int B, int L, double beta, const double* beta_b, const int64_t* seeds, int n_hb, int n_or,
                        int nsweep, int64_t sweep0, int classes, double* x_out, void* stream);
 
+/* ---- Annealed importance sampling: a ramp of beta through the local updates above, with the Jarzynski work of every chain.  The
+ * reference has no counterpart.  betas: a DEVICE array [n_step + 1].  With x_0 = x and W = work_in[b] (NULL: 0), step
+ * k = 0 .. n_step - 1 of chain b is
+ *     C_k = sum_{i,j} cos P(x_k),   P = ((x0[i][j] + x1[i+1][j]) - x0[i][j+1]) - x1[i][j]   (the order of the roundings),
+ *     W  <- W + (betas[k] - betas[k+1]) C_k     (the difference, the product and the sum each rounded: no fused multiply-add),
+ *     x_{k+1} = x_k after nsweep compound sweeps (n_hb heatbath, then n_or overrelaxation) at betas[k+1], all four classes, with the
+ *               heatbath-sweep indices of fthmc_local_update(..., nsweep, sweep0 + k nsweep n_hb, 15, ...).
+ * x_out = x_{n_step}, work_out[b] = W, and c_trace[b][k] = C_k for k = 0 .. n_step (optional; the last entry is the sum of the final
+ * field).  exp(-W) is the importance weight of x_out as a sample of exp(betas[n_step] sum cos P) when x was drawn from
+ * exp(betas[0] sum cos P) (Jarzynski: < exp(-W) > = Z(betas[n_step]) / Z(betas[0])).  C_k is added in a fixed order: thread t of the
+ * chain's nt = min(1024, L^2 / 2 rounded up to 64) threads adds the sites t, t + nt, ... from 0.0, the 64 lanes of a wave by the xor
+ * butterfly, the waves in order.  Inside the one-launch kernel a chain's work stays in registers and is stored once.
+ *   * The fields are bit for bit those of the chain of fthmc_local_update calls above; they do not depend on work_in, c_trace or path.
+ *   * A ramp cut at any step m equals two calls, the second with betas + m, work_in = the first's work_out and
+ *     sweep0 + m nsweep n_hb: the same bits in the fields, the work and the trace.  Chain b of a batch equals the chain alone.
+ *   * x_out may be x, work_out may be work_in.  n_step = 0 copies the field, copies the work and writes C_0.
+ *   * betas is read on the device: the call only enqueues, can be captured, and a replay follows the schedule the array holds then.
+ *     Finite betas >= 0 are the caller's promise (they are not looked at on the host).
+ * path: 1 = the whole ramp in one launch, one workgroup per chain with the chain's links in LDS, L <= 64; 2 = sequenced: per step
+ * one work kernel, then the class kernels, any L; 0 = as fthmc_local_update chooses (fthmc_set_small_path).  For L <= 64 both give
+ * the same bits in every output.  No workspace, no hidden state.
+ * A null x / x_out / betas / work_out (seeds: with n_hb > 0), B or L out of range, a negative count or sweep0, n_hb + n_or = 0 with
+ * n_step > 0, n_step > 65536, path outside 0 .. 2, path 1 with L > 64, or sweep0 + n_step nsweep n_hb > 2^32: FTHMC_ERR_ARG. */
+int fthmc_anneal(const double* x, int B, int L, const double* betas /* device [n_step + 1] */, int n_step, const int64_t* seeds, int n_hb,
+                 int n_or, int nsweep, int64_t sweep0, int path, const double* work_in /* [B] or NULL = 0 */, double* x_out,
+                 double* work_out /* [B] */, double* c_trace /* [B][n_step + 1] or NULL */, void* stream);
+
 /* ---- Instanton hits: a Metropolis update of the plain Wilson action across topological sectors.  The reference has no counterpart:
  * it updates by leapfrog molecular dynamics only.  With A the constant-field-strength configuration of charge 1,
  *     A1[i][j] = (2 pi / L^2) i,      A0[L-1][j] = -(2 pi / L) j,      A0[i][j] = 0 for i < L - 1,
