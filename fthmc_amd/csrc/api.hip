@@ -306,10 +306,10 @@ int hmc_trajectory_call(const double* x, const double* v, const double* u, int B
     FT_TRY(sched_of(integrator, dt, nstep, &sc));
     Ctx C; FT_TRY(open_call(nullptr, stream, &C));
     const hipStream_t s = C.s;
-    // L <= 64 (x_new must not alias x): one persistent launch per trajectory, state in LDS / registers.  The scalar-beta leapfrog
+    // L <= HMC_RESIDENT_MAXL (x_new must not alias x): one persistent launch per trajectory, state in LDS / registers.  The scalar-beta leapfrog
     // has a kernel of its own, the schedule-driven one serves every other integrator and per-chain beta with every integrator,
     // the biased one every integrator (path 1: the caller insists on it, 2: on the sequence).
-    const bool one_launch = L <= 64 && C.mfma && x_new != x;
+    const bool one_launch = L <= HMC_RESIDENT_MAXL && C.mfma && x_new != x;
     if (bias) {
         if (bias->path == 1 || (bias->path == 0 && one_launch))
             return launch_meta_trajectory(x, v, u, B, L, beta, sc, bias->T, x_new, dH, acc, H0, H1, bias->qm_out, bias->vb_out, s);
@@ -1029,7 +1029,7 @@ int fthmc_meta_trajectory(const double* x, const double* v, const double* u, int
                           double* H0, double* H1, double* qm_out, double* vb_out, void* ws, size_t ws_bytes, void* stream) {
     BiasArg bias{{}, path, qm_out, vb_out};
     if (meta_tab(vtab, B, G, nb, qmax, wall, &bias.T) != FTHMC_OK || path < 0 || path > 2) return FTHMC_ERR_ARG;
-    if (path == 1 && (L > 64 || x_new == x)) return FTHMC_ERR_ARG;
+    if (path == 1 && (L > HMC_RESIDENT_MAXL || x_new == x)) return FTHMC_ERR_ARG;
     return hmc_trajectory_call(x, v, u, B, L, beta, nullptr, dt, nstep, integrator, &bias, x_new, dH, acc, H0, H1, ws, ws_bytes, stream);
 }
 int fthmc_meta_deposit(const double* qm, int B, int G, int nb, double qmax, double w, double* vtab, void* stream) {

@@ -101,6 +101,12 @@ __device__ __forceinline__ void ft_sincos(double x, double* sn, double* cs) {
     *sn = (q & 2) ? -s_ : s_;
     *cs = ((q + 1) & 2) ? -c_ : c_;
 }
+// the same for any argument: beyond ft_sincos' range (a segment sum at L ~ 3e4 with every link near +pi, or links far outside the
+// principal range) ocml's
+__device__ __forceinline__ void ft_sincos_wide(double a, double* sn, double* cs) {
+    if (fabs(a) <= 1.0e5) ft_sincos(a, sn, cs);
+    else sincos(a, sn, cs);
+}
 
 // atan for the tan-mixture transform.  |x| > 1 folds to 1 / |x| (v_rcp_f64 + one third-order step; |x| clamped to 1e300 first, so
 // that an infinite tangent gives pi/2 and not 0 * inf), then atan(a) = a + a s p(s), s = a^2, with the 20-coefficient near-minimax

@@ -123,22 +123,21 @@ struct Hot {
     int B, nl, act;
     double* gz;              // training sweep: the pre-activation gradients of every layer (null otherwise)
 };
-typedef const __attribute__((address_space(4))) SmallArgs ColdArgs;        // the kernarg segment is constant memory: scalar loads
-__device__ __forceinline__ ColdArgs& cold() {
-    ColdArgs* p = (ColdArgs*)__builtin_amdgcn_kernarg_segment_ptr();                     // the one explicit kernel argument, offset 0
+// the kernel's one explicit argument (offset 0 of the kernarg segment) as the block T; constant memory: scalar loads
+template <class T> __device__ __forceinline__ const __attribute__((address_space(4))) T& kernarg() {
+    typedef const __attribute__((address_space(4))) T Cold;
+    Cold* p = (Cold*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
     return *p;
 }
+typedef const __attribute__((address_space(4))) SmallArgs ColdArgs;
+__device__ __forceinline__ ColdArgs& cold() { return kernarg<SmallArgs>(); }
 
 // The schedule-driven instance (k_ft_small<..., SCHED>) takes the same block with the MD schedule behind it (integrator.h): the other
 // instances' argument block, and with it their code, is what it was
 struct SmallArgsSched : SmallArgs { Sched sched; };
 typedef const __attribute__((address_space(4))) SmallArgsSched ColdSched;
-__device__ __forceinline__ ColdSched& cold_sched() {
-    ColdSched* p = (ColdSched*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return *p;
-}
+__device__ __forceinline__ ColdSched& cold_sched() { return kernarg<SmallArgsSched>(); }
 // The per-chain-beta instance (k_ft_small<..., SCHED, PB>: replica exchange, fthmc_ft_trajectory_pb_v) takes the schedule-driven block
 // with the device array beta_b[B] behind it: beta is ONE load per workgroup at the chain's index, and state_in / state_out are the
 // beta-free triple (log det J, sum cos P, Q)
@@ -148,11 +147,7 @@ struct SmallArgsPB : SmallArgsSched { const double* beta_b; };
 // the bias up; state_in / state_out are the table-free [4][B] (S_eff unbiased, plaq, Q, Q_m)
 struct SmallArgsMeta : SmallArgsSched { MetaTab T; double *qm_out, *vb_out; };
 typedef const __attribute__((address_space(4))) SmallArgsMeta ColdMeta;
-__device__ __forceinline__ ColdMeta& cold_meta() {
-    ColdMeta* p = (ColdMeta*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return *p;
-}
+__device__ __forceinline__ ColdMeta& cold_meta() { return kernarg<SmallArgsMeta>(); }
 // the table and the chain's row, read from the kernarg segment where they are used (scalar loads; nothing of it lives through a sweep)
 __device__ __forceinline__ MetaTab meta_tab(const double** row, int b) {
     ColdMeta& M = cold_meta();
@@ -678,8 +673,9 @@ template <int L, bool TRAIN> struct Chain {
         const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
         return sX[s] - sX[N + s] - sX[i * L + jp] + sX[N + ip * L + j];
     }
-    // S_W = -beta sum cos P, Q = sum wrap(P) / 2 pi of the field in sX; results valid in every thread
-    __device__ void action_charge(double beta, double& S, double& Q) {
+    // C = sum cos P, Q = sum wrap(P) / 2 pi of the field in sX; results valid in every thread (the per-chain-beta instance keeps C
+    // itself: the beta-free state)
+    __device__ void action_sums(double& Cs, double& Q) {
         constexpr int N = G::N;
         const double* sX = sm + G::X;
         double* red = sm + G::RED;
@@ -693,10 +689,14 @@ template <int L, bool TRAIN> struct Chain {
             c = cs_;
             q = ft_wrap(a - bb - cc + d);                                  // summation order of batch_plaqs
         }
-        c = ft_block_sum(c, red);
-        q = ft_block_sum(q, red);
+        Cs = ft_block_sum(c, red);
+        Q = ft_block_sum(q, red) / FT_TWO_PI;
+    }
+    // S_W = -beta sum cos P and Q
+    __device__ void action_charge(double beta, double& S, double& Q) {
+        double c;
+        action_sums(c, Q);
         S = (-beta) * c;
-        Q = q / FT_TWO_PI;
     }
     // gP = beta sin P of the flowed field: seeds the backward sweep
     __device__ void wilson_seed(double beta) {
@@ -727,24 +727,6 @@ template <int L, bool TRAIN> struct Chain {
         double sn_ = 0.0, cs_ = 0.0;
         if (tid < G::N) ft_sincos(plaq_at(sm + G::X, tid), &sn_, &cs_);
         return ft_block_sum(sn_, sm + G::RED);
-    }
-    // action_charge's sums themselves (the per-chain-beta instance keeps C = sum cos P: the beta-free state)
-    __device__ void action_sums(double& Cs, double& Q) {
-        constexpr int N = G::N;
-        const double* sX = sm + G::X;
-        double* red = sm + G::RED;
-        double c = 0.0, q = 0.0;
-        if (tid < N) {
-            const int i = fdiv<L>(tid), j = tid - i * L;
-            const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
-            const double a = sX[tid], bb = sX[N + tid], cc = sX[i * L + jp], d = sX[N + ip * L + j];
-            double sn_, cs_;
-            ft_sincos(a + d - cc - bb, &sn_, &cs_);
-            c = cs_;
-            q = ft_wrap(a - bb - cc + d);
-        }
-        Cs = ft_block_sum(c, red);
-        Q = ft_block_sum(q, red) / FT_TWO_PI;
     }
     // force of site tid from sGP (adjoint of the plaquette stencil)
     __device__ __forceinline__ void site_force(double& f0, double& f1) const {
@@ -1028,34 +1010,37 @@ static int launch_instance(const typename SmallArgsOf<SCHED, PB, BIAS>::type& a,
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 
+// What the schedule-driven launches share: the stash limit, a trajectory (leap: or a leapfrog) without diagnostics, a sound schedule;
+// fills the block's head (the plain block and the schedule)
+template <class A> static int sched_block(const SmallArgs& a0, const Sched& sched, int L, bool leap, A* a) {
+    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
+    if ((a0.mode != SM_TRAJ && !(leap && a0.mode == SM_LEAPFROG)) || a0.dbg || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
+    static_cast<SmallArgs&>(*a) = a0;
+    a->sched = sched;
+    return FTHMC_OK;
+}
+
 // leapfrog / trajectory of a schedule (integrator.h): the SCHED instance, mode at run time
 int launch_ft_small_sched(const SmallArgs& a0, const Sched& sched, int L, hipStream_t s) {
-    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
-    if ((a0.mode != SM_TRAJ && a0.mode != SM_LEAPFROG) || a0.dbg || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
     SmallArgsSched a;
-    static_cast<SmallArgs&>(a) = a0;
-    a.sched = sched;
+    if (const int rc = sched_block(a0, sched, L, true, &a)) return rc;
     return launch_instance<false, false, false, true>(a, L, s);
 }
 
 // a trajectory of a schedule with per-chain beta (a0.beta is not read; state_in / state_out: the beta-free triple)
 int launch_ft_small_pb(const SmallArgs& a0, const Sched& sched, const double* beta_b, int L, hipStream_t s) {
-    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
-    if (a0.mode != SM_TRAJ || a0.dbg || !beta_b || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
     SmallArgsPB a;
-    static_cast<SmallArgs&>(a) = a0;
-    a.sched = sched;
+    if (const int rc = sched_block(a0, sched, L, false, &a)) return rc;
+    if (!beta_b) return FTHMC_ERR_ARG;
     a.beta_b = beta_b;
     return launch_instance<false, false, false, true, true>(a, L, s);
 }
 
 // a trajectory of a schedule under the bias T (state_in / state_out: the table-free [4][B])
 int launch_ft_small_meta(const SmallArgs& a0, const Sched& sched, const MetaTab& T, double* qm_out, double* vb_out, int L, hipStream_t s) {
-    if (!flow_stash_fits32(a0.B, L, true)) return FTHMC_ERR_UNSUPPORTED;
-    if (a0.mode != SM_TRAJ || a0.dbg || !T.v || T.cpr < 1 || T.nb < 2 || sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
     SmallArgsMeta a;
-    static_cast<SmallArgs&>(a) = a0;
-    a.sched = sched;
+    if (const int rc = sched_block(a0, sched, L, false, &a)) return rc;
+    if (!T.v || T.cpr < 1 || T.nb < 2) return FTHMC_ERR_ARG;
     a.T = T; a.qm_out = qm_out; a.vb_out = vb_out;
     return launch_instance<false, false, false, true, false, true>(a, L, s);
 }

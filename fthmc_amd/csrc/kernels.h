@@ -37,7 +37,8 @@ void set_leap_rows(int v);      // 1 (default): row-strip leapfrog kernel when L
 int launch_leap_step(const double* x, const double* p, double* xo, double* po, int B, int L,
                      double beta, double a, double dt, hipStream_t s, const double* beta_b = nullptr);
 int launch_wilson_gp(const double* x, int B, int L, double beta, double* gp, hipStream_t s, const double* beta_b = nullptr);
-// whole plain-HMC trajectory in one launch (L <= 64: links in LDS, momenta in registers)
+// whole plain-HMC trajectory in one launch (L <= HMC_RESIDENT_MAXL: links in LDS, momenta in registers; the plan: traj_resident.h)
+constexpr int HMC_RESIDENT_MAXL = 64;
 int launch_hmc_trajectory_fused(const double* x, const double* v, const double* u, int B, int L, double beta,
                                 double dt, int nstep, double* x_new, double* dH, double* acc, double* H0,
                                 double* H1, hipStream_t s);

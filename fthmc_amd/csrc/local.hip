@@ -23,11 +23,6 @@ using fthmc::LU_MAX_ATTEMPTS;
 // own limit r -> inf, f = z, c = 1 (accepted at once): uniform on the circle.  Above it nothing of the setup cancels (rho below)
 constexpr double LU_KAPPA_MIN = 8.673617379884035e-19;      // 2^-60
 
-__device__ __forceinline__ void lu_sincos(double a, double* sn, double* cs) {      // loops.hip lp_sincos: ft_sincos' range is 1e5
-    if (fabs(a) <= 1.0e5) ft_sincos(a, sn, cs);
-    else sincos(a, sn, cs);
-}
-
 // the staple angles from the six neighbours in the order the callers load them (lu_neighbours)
 // (fp contract off in the three functions that hold the update's arithmetic: which products and sums become one FMA must not be left
 // to the optimiser's view of two different kernels -- the two paths promise the same bits)
@@ -50,7 +45,7 @@ __device__ __forceinline__ double lu_heatbath(double xold, double a, double b, d
                                               uint32_t mu, uint32_t sweep) {
 #pragma clang fp contract(off)
     double sn, ch;
-    lu_sincos(0.5 * (a + b), &sn, &ch);
+    ft_sincos_wide(0.5 * (a + b), &sn, &ch);
     const double kappa = 2.0 * beta * fabs(ch);
     double phi = 0.5 * (b - a);
     if (ch < 0.0) phi += FT_PI;
@@ -255,7 +250,7 @@ __device__ __forceinline__ double an_cos_sum(At at, int L, int tid, int nt) {
         const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
         const double P = ((at(0, i, j) + at(1, ip, j)) - at(0, i, jp)) - at(1, i, j);
         double sn, cs;
-        lu_sincos(P, &sn, &cs);
+        ft_sincos_wide(P, &sn, &cs);
         c += cs;
     }
     return c;

@@ -16,13 +16,6 @@ namespace {
 using fthmc::LP_THREADS;
 using fthmc::LP_SITES;
 
-// sin and cos of a segment sum: the project's own (common.h: 2.5 ulp for |a| <= 1e5, far beyond L pi of any lattice a workgroup
-// holds in LDS); a sum beyond that (L ~ 3e4 with every link near +pi, or links far outside the principal range) takes ocml's
-__device__ __forceinline__ void lp_sincos(double a, double* sn, double* cs) {
-    if (fabs(a) <= 1.0e5) ft_sincos(a, sn, cs);
-    else sincos(a, sn, cs);
-}
-
 // ---------------------------------------------------------------- prefix sums of x0 along i
 // S[b][i][j] = sum_{a<i} x0[a][j], i = 0 .. L (row L: the column totals), one thread per column (coalesced in j), the running sum
 // as an unevaluated pair hi + lo (two-sum), so that a stored prefix carries ONE rounding, 2^-53 |S|, instead of the i roundings of
@@ -58,9 +51,9 @@ __device__ __forceinline__ void lp_build(const double* __restrict__ Sb, const do
         const int r = s / L, j = s - r * L, i = i0 + r;
         const int ir = i + R >= L ? i + R - L : i + R;
         double sn, cs;
-        lp_sincos(lp_segment(Sb, L, i, R, j), &sn, &cs);
+        ft_sincos_wide(lp_segment(Sb, L, i, R, j), &sn, &cs);
         E[s] = make_double2(cs, sn);
-        lp_sincos(x1[(size_t)ir * L + j] - x1[(size_t)i * L + j], &sn, &cs);
+        ft_sincos_wide(x1[(size_t)ir * L + j] - x1[(size_t)i * L + j], &sn, &cs);
         d[s] = make_double2(cs, sn);
     }
 }

@@ -7,15 +7,14 @@
 // quadratic wall outside; chain b reads row b / (B / G).  With an all-zero table (and no wall in reach) every kernel here does
 // the arithmetic of its plain twin in wilson.hip: beta sn + 0 cs, h + 0.
 // Two trajectory shapes: k_meta_trajectory (L <= 64: one launch, one workgroup per chain, links in LDS, momenta in registers --
-// k_hmc_trajectory_sched's plan and a cos P plane) and the sequenced one for any L (api.hip: k_meta_sums, k_meta_gp and the plain kick / shift /
+// the resident plan of traj_resident.h with a sin P and a cos P plane) and the sequenced one for any L (api.hip: k_meta_sums, k_meta_gp and the plain kick / shift /
 // energy / Metropolis kernels).  k_meta_deposit adds the walkers' hills to the table in chain order, without atomics.
 #include "common.h"
 #include "kernels.h"
 #include "meta_tab.h"
+#include "traj_resident.h"
 
 namespace {
-
-constexpr int MT_NT = 1024, MT_MAXL = 64, MT_NSITE = MT_MAXL * MT_MAXL / MT_NT;     // wilson.hip TJ_NT, TJ_MAXL, TJ_NSITE
 
 // (the table's lookup mt_locate / mt_lookup / mt_bias_row / mt_bias: meta_tab.h, shared with flow_small.hip)
 
@@ -197,7 +196,7 @@ template <bool DPP, int N> __device__ __forceinline__ void mt_block_sums(double 
     // the stage's sum knows the kernel's workgroup, so that its reads below are issued together; the energies' keep ft_block_sum's loop
     // as it is (with their loop unrolled the compiler contracted H = -beta C + K / 2 another way than it does in the parent's kernels:
     // the last bit of H moved in three zero-table cases, two at L = 20 and one at L = 64)
-    const int nw = DPP ? MT_NT / FT_WAVE : (int)((blockDim.x + 63) >> 6);
+    const int nw = DPP ? TJ_NT / FT_WAVE : (int)((blockDim.x + 63) >> 6);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         v[k] = DPP ? mt_wave_sum_dpp(v[k]) : ft_wave_sum(v[k]);
@@ -209,7 +208,7 @@ template <bool DPP, int N> __device__ __forceinline__ void mt_block_sums(double 
         double t = 0.0;
         if (DPP) {
 #pragma unroll 8                                         // (all 16 at once: 128 VGPRs and 12 B of scratch per lane)
-            for (int i = 0; i < MT_NT / FT_WAVE; ++i) t += red[k][i];
+            for (int i = 0; i < TJ_NT / FT_WAVE; ++i) t += red[k][i];
         } else {
             for (int i = 0; i < nw; ++i) t += red[k][i];
         }
@@ -217,31 +216,31 @@ template <bool DPP, int N> __device__ __forceinline__ void mt_block_sums(double 
     }
 }
 
-// k_hmc_trajectory_sched's thread-to-site map and its LDS plan with one plane more (wilson.hip): links 64 KB, sin P 32 KB, cos P 32 KB of
-// the CU's 160 KB.  Per stage, behind the barrier that closes the stage before: one ft_sincos per site into the two planes and the
+// k_hmc_trajectory_sched's thread-to-site map and its LDS plan with one plane more (the resident plan: traj_resident.h, with the two
+// orders of the plaquette and the stage body): links 64 KB, sin P 32 KB, cos P 32 KB of the CU's 160 KB.  Per stage, behind the barrier that closes the stage before: one ft_sincos per site into the two planes and the
 // wave sums of sin P; ONE barrier; every thread adds the wave sums (Q_m), looks the wave-uniform slope up and forms
 // gP = beta sn + c cs of its site and of the two neighbours the stencil needs from the planes (two FMAs more than one plane of gP
 // would cost, and two barriers less), then the plain KICK / SHIFT: two barrier phases a stage, as the parent has.  h0 / h1 add
 // V(Q_m) of the start and of the regularized end field; their three sums (cos P, sin P, v^2) share one barrier.
-__global__ __launch_bounds__(MT_NT) void k_meta_trajectory(const double* __restrict__ x, const double* __restrict__ v,
+__global__ __launch_bounds__(TJ_NT) void k_meta_trajectory(const double* __restrict__ x, const double* __restrict__ v,
                                                            const double* __restrict__ u, int L, double beta, fthmc::Sched sched, MetaTab T,
                                                            double* __restrict__ x_new, double* __restrict__ dH, double* __restrict__ acc,
                                                            double* __restrict__ H0o, double* __restrict__ H1o, double* __restrict__ qm_out,
                                                            double* __restrict__ vb_out) {
-    __shared__ double sx[2 * MT_MAXL * MT_MAXL];        // links
-    __shared__ double ssn[MT_MAXL * MT_MAXL];           // sin P
-    __shared__ double scs[MT_MAXL * MT_MAXL];           // cos P
+    __shared__ double sx[2 * TJ_MAXL * TJ_MAXL];        // links
+    __shared__ double ssn[TJ_MAXL * TJ_MAXL];           // sin P
+    __shared__ double scs[TJ_MAXL * TJ_MAXL];           // cos P
     __shared__ double red[3][16];
     const int b = blockIdx.x, tid = threadIdx.x, n = L * L;
     const double* xb = x + (size_t)b * 2 * n;
     const double* vb = v + (size_t)b * 2 * n;
     const double* row = mt_row(T, b);                    // (a copy of the row in LDS was measured: no gain at nb = 81, the row stays cached)
-    double v0[MT_NSITE], v1[MT_NSITE], k0[MT_NSITE], k1[MT_NSITE];
-    int st[MT_NSITE], sjm[MT_NSITE], sim[MT_NSITE], sjp[MT_NSITE], sip[MT_NSITE];
+    double v0[TJ_NSITE], v1[TJ_NSITE], k0[TJ_NSITE], k1[TJ_NSITE];
+    int st[TJ_NSITE], sjm[TJ_NSITE], sim[TJ_NSITE], sjp[TJ_NSITE], sip[TJ_NSITE];
     double kin = 0.0;
 #pragma unroll
-    for (int k = 0; k < MT_NSITE; ++k) {
-        const int s = tid + k * MT_NT;
+    for (int k = 0; k < TJ_NSITE; ++k) {
+        const int s = tid + k * TJ_NT;
         st[k] = s < n ? s : -1;
         v0[k] = v1[k] = k0[k] = k1[k] = 0.0; sjm[k] = sim[k] = sjp[k] = sip[k] = 0;
         if (s < n) {
@@ -259,10 +258,10 @@ __global__ __launch_bounds__(MT_NT) void k_meta_trajectory(const double* __restr
     auto energy = [&](double ksum, double* qm, double* V) {
         double s3[3] = {0.0, 0.0, ksum};
 #pragma unroll
-        for (int k = 0; k < MT_NSITE; ++k)
+        for (int k = 0; k < TJ_NSITE; ++k)
             if (st[k] >= 0) {
                 double sn_, cs_;
-                ft_sincos(sx[st[k]] + sx[n + sip[k]] - sx[sjp[k]] - sx[n + st[k]], &sn_, &cs_);
+                ft_sincos(tj_plaq_energy(sx, n, st[k], sjp[k], sip[k]), &sn_, &cs_);
                 s3[0] += cs_; s3[1] += sn_;
             }
         mt_block_sums<false>(s3, red);
@@ -274,7 +273,7 @@ __global__ __launch_bounds__(MT_NT) void k_meta_trajectory(const double* __restr
     double qm0, vb0, qm1, vb1;
     const double h0 = energy(kin, &qm0, &vb0);
 #pragma unroll
-    for (int k = 0; k < MT_NSITE; ++k)
+    for (int k = 0; k < TJ_NSITE; ++k)
         if (st[k] >= 0) { sx[st[k]] += sched.b0 * v0[k]; sx[n + st[k]] += sched.b0 * v1[k]; }
     bool shifted = false;                                // sx holds the shifted links of the own sites, k0 / k1 the links themselves
     for (int it = 0; it < sched.n; ++it) {
@@ -282,10 +281,10 @@ __global__ __launch_bounds__(MT_NT) void k_meta_trajectory(const double* __restr
         __syncthreads();
         double q1[1] = {0.0};
 #pragma unroll
-        for (int k = 0; k < MT_NSITE; ++k)
+        for (int k = 0; k < TJ_NSITE; ++k)
             if (st[k] >= 0) {
                 double sn_, cs_;
-                ft_sincos(sx[st[k]] - sx[n + st[k]] - sx[sjp[k]] + sx[n + sip[k]], &sn_, &cs_);
+                ft_sincos(tj_plaq_force(sx, n, st[k], sjp[k], sip[k]), &sn_, &cs_);
                 ssn[st[k]] = sn_; scs[st[k]] = cs_;
                 q1[0] += sn_;
             }
@@ -293,24 +292,17 @@ __global__ __launch_bounds__(MT_NT) void k_meta_trajectory(const double* __restr
         double qm, V, c;
         mt_bias_row(row, T, q1[0], &qm, &V, &c);
 #pragma unroll
-        for (int k = 0; k < MT_NSITE; ++k)
+        for (int k = 0; k < TJ_NSITE; ++k)
             if (st[k] >= 0) {
                 const double sc = beta * ssn[st[k]] + c * scs[st[k]];
                 const double f0 = sc - (beta * ssn[sjm[k]] + c * scs[sjm[k]]), f1 = (beta * ssn[sim[k]] + c * scs[sim[k]]) - sc;
-                if (sg.kind == fthmc::FT_STAGE_SHIFT) {
-                    k0[k] = sx[st[k]]; k1[k] = sx[n + st[k]];
-                    sx[st[k]] = k0[k] - sg.a * f0; sx[n + st[k]] = k1[k] - sg.a * f1;
-                } else {
-                    v0[k] -= sg.a * f0; v1[k] -= sg.a * f1;
-                    const double y0 = shifted ? k0[k] : sx[st[k]], y1 = shifted ? k1[k] : sx[n + st[k]];
-                    sx[st[k]] = y0 + sg.b * v0[k]; sx[n + st[k]] = y1 + sg.b * v1[k];
-                }
+                tj_stage(sg, shifted, f0, f1, sx, n, st[k], v0[k], v1[k], k0[k], k1[k]);
             }
         shifted = sg.kind == fthmc::FT_STAGE_SHIFT;
     }
     kin = 0.0;
 #pragma unroll
-    for (int k = 0; k < MT_NSITE; ++k)
+    for (int k = 0; k < TJ_NSITE; ++k)
         if (st[k] >= 0) {
             sx[st[k]] = ft_regularize(sx[st[k]]); sx[n + st[k]] = ft_regularize(sx[n + st[k]]);
             kin += v0[k] * v0[k] + v1[k] * v1[k];
@@ -329,7 +321,7 @@ __global__ __launch_bounds__(MT_NT) void k_meta_trajectory(const double* __restr
     }
     double* xo = x_new + (size_t)b * 2 * n;
 #pragma unroll
-    for (int k = 0; k < MT_NSITE; ++k)
+    for (int k = 0; k < TJ_NSITE; ++k)
         if (st[k] >= 0) {
             xo[st[k]] = ok ? sx[st[k]] : xb[st[k]];
             xo[n + st[k]] = ok ? sx[n + st[k]] : xb[n + st[k]];
@@ -342,9 +334,9 @@ namespace fthmc {
 
 int launch_meta_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta, const Sched& sched, const MetaTab& T,
                            double* x_new, double* dH, double* acc, double* H0, double* H1, double* qm_out, double* vb_out, hipStream_t s) {
-    if (L > MT_MAXL) return FTHMC_ERR_UNSUPPORTED;
+    if (L > TJ_MAXL) return FTHMC_ERR_UNSUPPORTED;
     if (sched.n < 1 || sched.nper < 1 || sched.nper > 3) return FTHMC_ERR_ARG;
-    hipLaunchKernelGGL(k_meta_trajectory, dim3(B), dim3(MT_NT), 0, s, x, v, u, L, beta, sched, T, x_new, dH, acc, H0, H1, qm_out, vb_out);
+    hipLaunchKernelGGL(k_meta_trajectory, dim3(B), dim3(TJ_NT), 0, s, x, v, u, L, beta, sched, T, x_new, dH, acc, H0, H1, qm_out, vb_out);
     FT_LAUNCH_CHECK(); return FTHMC_OK;
 }
 int launch_meta_sums(const double* x, int B, int L, double* sums, hipStream_t s) {

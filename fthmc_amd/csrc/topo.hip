@@ -23,11 +23,6 @@ using fthmc::it_shift_num_seam;
 using fthmc::it_shift_num_x1;
 using fthmc::it_theta_num;
 
-__device__ __forceinline__ void it_sincos(double a, double* sn, double* cs) {      // local.hip lu_sincos: ft_sincos' range is 1e5
-    if (fabs(a) <= 1.0e5) ft_sincos(a, sn, cs);
-    else sincos(a, sn, cs);
-}
-
 // (fp contract off in the functions that hold the update's arithmetic, as in local.hip: which products and sums become one FMA must
 // not be left to the optimiser's view of different kernels -- the two launch shapes promise the same bits)
 
@@ -43,7 +38,7 @@ __device__ __forceinline__ void it_chain_sums(const double* x0, int L, int tid, 
         const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
         const double P = ((x0[s] + x1[ip * L + j]) - x0[i * L + jp]) - x1[s];
         double sn, cs;
-        it_sincos(P, &sn, &cs);
+        ft_sincos_wide(P, &sn, &cs);
         c += cs;
         q += sn;
     }

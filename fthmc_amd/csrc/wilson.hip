@@ -4,6 +4,7 @@
 // [B][2][L][L] field are contiguous in j) and shares plaquettes through LDS.
 #include "common.h"
 #include "kernels.h"
+#include "traj_resident.h"
 #include <type_traits>
 
 namespace {
@@ -560,14 +561,6 @@ __global__ __launch_bounds__(256) void k_stats_accumulate(const double* __restri
     }
 }
 
-// ---------------------------------------------------------------- whole plain-HMC trajectory, one launch
-// One workgroup per chain, links in LDS, momenta in registers (every thread owns NSITE sites of
-// its chain for the whole trajectory): between H0 and the Metropolis select nothing touches HBM.
-// For L <= 64 (x: 64 KB + beta sin P plane: 32 KB of LDS).  Same arithmetic as the step kernels:
-//   x' = x + dt/2 v;  v' = v - dt F(x');  (nstep-1) x {x' += dt v'; v' -= dt F(x')};  x' += dt/2 v'
-//   xr = regularize(x');  dH = S(xr) + v'^2/2 - S(x) - v^2/2;  acc = u < exp(-dH)
-constexpr int TJ_NT = 1024, TJ_MAXL = 64, TJ_NSITE = TJ_MAXL * TJ_MAXL / TJ_NT;
-
 // Metrics of one reverse-KL training step (train_step, fthmc/train.py:206-228; calc_dkl / calc_ess,
 // fthmc/utils/distributions.py:23-37) in one workgroup:
 //   row = [loss_dkl, ess, logp[B], logq[B], q[B], dq[B], plaq[B]]
@@ -635,6 +628,15 @@ __global__ __launch_bounds__(256) void k_adam(double* __restrict__ p, const doub
     }
 }
 
+// ---------------------------------------------------------------- whole plain-HMC trajectory, one launch
+// One workgroup per chain, links in LDS, momenta in registers (every thread owns NSITE sites of
+// its chain for the whole trajectory): between H0 and the Metropolis select nothing touches HBM.
+// For L <= 64 (x: 64 KB + beta sin P plane: 32 KB of LDS).  Same arithmetic as the step kernels:
+//   x' = x + dt/2 v;  v' = v - dt F(x');  (nstep-1) x {x' += dt v'; v' -= dt F(x')};  x' += dt/2 v'
+//   xr = regularize(x');  dH = S(xr) + v'^2/2 - S(x) - v^2/2;  acc = u < exp(-dH)
+// The plan's constants, the two orders of the plaquette, the action sum and the stage body of the schedule kernel are
+// traj_resident.h's (shared with meta.hip).  The action sum is called through a lambda, as it was written: called directly it is
+// inlined before the kernel is optimised and the kernel's code comes out in another order (tools/isa_diff.py).
 __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory(const double* __restrict__ x, const double* __restrict__ v,
                                                           const double* __restrict__ u, int L, double beta, double dt,
                                                           int nstep, double* __restrict__ x_new, double* __restrict__ dH,
@@ -664,13 +666,7 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory(const double* __restri
         }
     }
     __syncthreads();
-    auto action = [&]() {                                // -beta sum cos P over the chain (summation order of BatchAction)
-        double c = 0.0;
-#pragma unroll
-        for (int k = 0; k < TJ_NSITE; ++k)
-            if (st[k] >= 0) { double sn_, cs_; ft_sincos(sx[st[k]] + sx[n + sip[k]] - sx[sjp[k]] - sx[n + st[k]], &sn_, &cs_); c += cs_; }
-        return (-beta) * ft_block_sum(c, red);
-    };
+    auto action = [&]() { return tj_action(st, sjp, sip, sx, n, beta, red); };
     const double h0 = action() + 0.5 * ft_block_sum(kin, red);
     for (int step = 0; step <= nstep; ++step) {
         const double a = (step == 0 || step == nstep) ? 0.5 * dt : dt;
@@ -683,7 +679,7 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory(const double* __restri
         for (int k = 0; k < TJ_NSITE; ++k)
             if (st[k] >= 0) {                       // own sincos (common.h): ~3x shorter than ocml's sin, same accuracy class
                 double sn_, cs_;
-                ft_sincos(sx[st[k]] - sx[n + st[k]] - sx[sjp[k]] + sx[n + sip[k]], &sn_, &cs_);
+                ft_sincos(tj_plaq_force(sx, n, st[k], sjp[k], sip[k]), &sn_, &cs_);
                 sp[st[k]] = beta * sn_;
             }
         __syncthreads();
@@ -722,9 +718,7 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory(const double* __restri
 }
 
 // The same trajectory for any schedule (integrator.h): the same LDS plan and thread-to-site map, x += b0 v and then per stage
-//   beta sin P of the links in LDS;  KICK(a, b): v -= a F, x += b v  |  SHIFT(c): the thread keeps its own links in registers and
-//   puts x - c F in their place for the NEXT stage's beta sin P, whose kick first puts the kept links back: sx itself is as if
-//   never touched (restored bit for bit, not recomputed)
+// beta sin P of the links in LDS and the KICK / SHIFT of traj_resident.h (tj_stage) with the stencil's two differences of the plane
 template <bool PB>
 __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __restrict__ x, const double* __restrict__ v,
                                                                 const double* __restrict__ u, int L, typename BetaArg<PB>::type beta_, fthmc::Sched sched,
@@ -756,13 +750,7 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __
         }
     }
     __syncthreads();
-    auto action = [&]() {                                // -beta sum cos P over the chain (summation order of BatchAction)
-        double c = 0.0;
-#pragma unroll
-        for (int k = 0; k < TJ_NSITE; ++k)
-            if (st[k] >= 0) { double sn_, cs_; ft_sincos(sx[st[k]] + sx[n + sip[k]] - sx[sjp[k]] - sx[n + st[k]], &sn_, &cs_); c += cs_; }
-        return (-beta) * ft_block_sum(c, red);
-    };
+    auto action = [&]() { return tj_action(st, sjp, sip, sx, n, beta, red); };
     const double h0 = action() + 0.5 * ft_block_sum(kin, red);
 #pragma unroll
     for (int k = 0; k < TJ_NSITE; ++k)
@@ -775,7 +763,7 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __
         for (int k = 0; k < TJ_NSITE; ++k)
             if (st[k] >= 0) {
                 double sn_, cs_;
-                ft_sincos(sx[st[k]] - sx[n + st[k]] - sx[sjp[k]] + sx[n + sip[k]], &sn_, &cs_);
+                ft_sincos(tj_plaq_force(sx, n, st[k], sjp[k], sip[k]), &sn_, &cs_);
                 sp[st[k]] = beta * sn_;
             }
         __syncthreads();
@@ -783,15 +771,7 @@ __global__ __launch_bounds__(TJ_NT) void k_hmc_trajectory_sched(const double* __
         for (int k = 0; k < TJ_NSITE; ++k)
             if (st[k] >= 0) {
                 const double sc = sp[st[k]];
-                const double f0 = sc - sp[sjm[k]], f1 = sp[sim[k]] - sc;
-                if (sg.kind == fthmc::FT_STAGE_SHIFT) {
-                    k0[k] = sx[st[k]]; k1[k] = sx[n + st[k]];
-                    sx[st[k]] = k0[k] - sg.a * f0; sx[n + st[k]] = k1[k] - sg.a * f1;
-                } else {
-                    v0[k] -= sg.a * f0; v1[k] -= sg.a * f1;
-                    const double y0 = shifted ? k0[k] : sx[st[k]], y1 = shifted ? k1[k] : sx[n + st[k]];
-                    sx[st[k]] = y0 + sg.b * v0[k]; sx[n + st[k]] = y1 + sg.b * v1[k];
-                }
+                tj_stage(sg, shifted, sc - sp[sjm[k]], sp[sim[k]] - sc, sx, n, st[k], v0[k], v1[k], k0[k], k1[k]);
             }
         shifted = sg.kind == fthmc::FT_STAGE_SHIFT;
     }

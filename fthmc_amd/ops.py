@@ -11,6 +11,9 @@ import torch
 from . import _lib
 from ._lib import ACT_CODES, INTEGRATORS, MODE_LITERAL, MODE_MD, W_PER_LAYER, FthmcError, check
 
+# up to here a chain's links stay in one workgroup's LDS for a whole launch (csrc/kernels.h HMC_RESIDENT_MAXL, LU_MAXL)
+RESIDENT_MAXL = 64
+
 # The one scratch cache: (device index, stream) -> the flow workspace, (device index, stream, family) -> the buffer of a call
 # family that keeps its own ('train_force', 'loops', 'instanton', 'meta'); all grown on demand by _stream_buffer
 _WS = {}
@@ -461,8 +464,8 @@ def anneal(x, betas, seeds=None, n_hb: int = 1, n_or: int = 0, nsweep: int = 1, 
                          f'betas, n_hb={n_hb}, n_or={n_or}, nsweep={nsweep}, sweep0={sweep0}, path={path}')
     if sweep0 + n_step * nsweep * n_hb > 2 ** 32:
         raise ValueError(f'anneal: sweep0 + n_step nsweep n_hb = {sweep0 + n_step * nsweep * n_hb} is beyond 2^32')
-    if path == 1 and L > 64:
-        raise ValueError('anneal: path 1 serves L <= 64')
+    if path == 1 and L > RESIDENT_MAXL:
+        raise ValueError(f'anneal: path 1 serves L <= {RESIDENT_MAXL}')
     if n_hb > 0 and seeds is None:
         raise ValueError('anneal: heatbath sweeps need per-chain seeds')
     seeds = _seeds(seeds, B)
@@ -571,11 +574,11 @@ def meta_trajectory(x, v, u, beta: float, dt: float, nstep: int, table, qmax: fl
     if path not in (0, 1, 2) or int(nstep) < 1:
         raise ValueError(f'meta_trajectory: path in 0 .. 2 and nstep >= 1 expected, got path={path}, nstep={nstep}')
     tab = _meta_table(table, B, qmax, wall)
-    if path == 1 and (L > 64 or xn.data_ptr() == x.data_ptr()):
-        raise ValueError("meta_trajectory: path 1 serves L <= 64 with out['x_new'] other than x")
+    if path == 1 and (L > RESIDENT_MAXL or xn.data_ptr() == x.data_ptr()):
+        raise ValueError(f"meta_trajectory: path 1 serves L <= {RESIDENT_MAXL} with out['x_new'] other than x")
     with torch.cuda.device(x.device):
         # path 0 takes the one-launch kernel where fthmc_meta_trajectory says it does: no scratch is asked for there
-        seq = path == 2 or (path == 0 and (L > 64 or xn.data_ptr() == x.data_ptr() or get_variant() != 1))
+        seq = path == 2 or (path == 0 and (L > RESIDENT_MAXL or xn.data_ptr() == x.data_ptr() or get_variant() != 1))
         ws, nb = _meta_ws(x, meta_ws_bytes(B, L, 2) if seq else 0)
         check(_lib.load().fthmc_meta_trajectory(_p(x), _p(v), _p(u), B, L, float(beta), float(dt), int(nstep), ic, *tab, path, _p(xn),
                                                 *(_p(r[k]) for k in ('dH', 'acc', 'H0', 'H1', 'qm', 'vbias')), ws, nb, _stream(x)),
