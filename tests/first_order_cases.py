@@ -12,9 +12,12 @@ adds the lattice kinds that the tuned first-order kernels distinguish and the du
 second_order_cases.inputs, with the seed 61000 + 100 L + 10 layers + index."""
 import math
 
+import numpy as np
 import torch
 
 import second_order_cases as C
+import walk_model as W
+from conftest import golden_flow, load_golden
 from oracle import ref_cpu as R
 from second_order_cases import (BETA, BOUND, NUDGES, SENS_BOUND, Case, Inputs, hold, nudged, per_chain,  # noqa: F401
                                 per_tensor, pin_links, split, tensor_spread, worst)
@@ -138,3 +141,36 @@ def sensitivity(inp, ref, seed):
         for key, e in compare(oracle_results(nudged(inp, seed + n)), ref, inp.flow).items():
             errs[key] = max(errs.get(key, 0.0), e) if e == e else e
     return errs
+
+
+def steep_fixture():
+    """(fixture, Inputs, reference results keyed like first_order_cases.oracle_results) of tests/golden/first_order_steep_L8.npz"""
+    g = load_golden('first_order_steep_L8')
+    nl = int(g['n_layers'])
+    t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
+    x = t(g['x'])
+    z = torch.zeros(x.shape[0], dtype=torch.float64)
+    inp = Inputs(golden_flow(g), x, torch.zeros_like(x), z, z, str(g['act']))
+    ref = {'F': t(g['F']), 'S_eff': t(g['S_eff']), 'logq': t(g['logq']), 'logp': t(g['logp']),
+           'gw': [tuple(t(g[f'gw{li}_{pi}']) for pi in range(6)) for li in range(nl)]}
+    return g, inp, ref
+
+
+# ---------------------------------------------------------------- which kernels serve a case under a setting of the switches
+SETTINGS = {'mfma': (1, True), 'mfma-tiled': (1, False), 'valu': (0, True)}
+
+
+def default_net(case):
+    return case.arch is None and not case.tanh
+
+
+def train_path(case, setting):
+    """the kernels behind ops.train_grad's weight gradients for a case under a setting"""
+    if not default_net(case):
+        return 'generic'
+    if setting == 'valu':
+        return 'valu'
+    if setting == 'mfma':
+        return W.train_launch(case.B, case.L, case.nl)[0]
+    assert W.ft_small_shape(case.L, case.nl) and not W.flow_bwd_train_shape(case.L)
+    return 'two-kernel'

@@ -21,8 +21,10 @@ signs."""
 import collections
 import math
 
+import numpy as np
 import torch
 
+from conftest import golden_flow, load_golden
 from oracle import ref_cpu as R
 
 BOUND = 1e-9
@@ -180,3 +182,16 @@ def tensor_spread(rows):
     """smallest / largest max|.| over the parameter tensors of a weight gradient"""
     m = [float(t.abs().max()) for lw in rows for t in lw]
     return min(m) / max(m)
+
+
+def steep_fixture():
+    """(Inputs, reference results shaped like oracle_results) of tests/golden/second_order_steep_L8.npz; its action VJP carries gS
+    alone (the reference's ft_action returns S_eff): glogdet = 0"""
+    g = load_golden('second_order_steep_L8')
+    nl = int(g['n_layers'])
+    t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
+    inp = Inputs(golden_flow(g), t(g['x']), t(g['g']), t(g['gS']), torch.zeros(2, dtype=torch.float64), str(g['act']))
+    rows = lambda key: [tuple(t(g[f'{key}{li}_{pi}']) for pi in range(6)) for li in range(nl)]
+    ref = {'F': t(g['F']), 'Hg': t(g['Hg']), 'gw_vjp': rows('gw'), 'ax': t(g['ga_x']), 'aw': rows('ga_w'),
+           'force_sq': t(g['force_sq']), 'gw_force': rows('gq')}
+    return g, inp, ref

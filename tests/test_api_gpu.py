@@ -1,26 +1,19 @@
 """GPU tests of the reference-shaped Python API (fthmc_amd.ft_hmc / hmc / train / utils.*)
 against golden vectors from the reference and against the oracle."""
+import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import golden_flow, load_golden
+import gpu_support
+from conftest import load_golden
+from gpu_support import D, H, module_defaults
 
 pytestmark = pytest.mark.gpu
-
-
-def D(a):
-    return torch.from_numpy(np.asarray(a, dtype=np.float64).copy()).cuda()
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def close(a, b, rtol=1e-9, atol=1e-9):
-    np.testing.assert_allclose(H(a), H(b), rtol=rtol, atol=atol)
+_defaults = module_defaults()
+close = functools.partial(gpu_support.close, rtol=1e-9, atol=1e-9)
 
 
 def build_layers(g, L, act='silu'):

@@ -16,58 +16,17 @@ import batch_kernel_cases as C
 import integrator_cases as IC
 import tempering_cases as TC
 
+from gpu_support import D, H, Poisoned, R, bits, module_defaults, ops  # noqa: F401
+
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
-ops = None
-R = None
 U = C.U
-GUARD = 8
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, R
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    from oracle import ref_cpu as _R
-    ops, R = _ops, _R
-    ops.set_variant(1)
-    ops.set_small_path(True)
 
 
 @pytest.fixture(scope='module')
 def G():
     return load_golden('batch_kernels')
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def D(a, dtype=torch.float64):
-    return torch.as_tensor(np.asarray(a), dtype=dtype).cuda()
-
-
-def bits(a):
-    return np.ascontiguousarray(H(a)).view(np.int64)
-
-
-class Poisoned:
-    """n doubles at offset GUARD of a NaN-filled allocation with GUARD words behind them"""
-
-    def __init__(self, n, init=None):
-        self.n = n
-        self.buf = torch.full((2 * GUARD + n,), float('nan'), dtype=torch.float64, device='cuda')
-        self.t = self.buf[GUARD:GUARD + n]
-        if init is not None:
-            self.t.copy_(torch.as_tensor(np.asarray(init, dtype=np.float64)))
-        self.before = self.guards()
-
-    def guards(self):
-        return np.concatenate([bits(self.buf[:GUARD]), bits(self.buf[GUARD + self.n:])])
-
-    def intact(self):
-        return np.array_equal(self.guards(), self.before)
 
 
 def report(name, value):

@@ -1,33 +1,48 @@
-"""GPU tests added in round 5: the reference-shaped drivers as captured loops (FieldTransformation.run, qed_helpers.ft_run)
-against their eager loops, the carried state keyed by the weights' content, per-chain seeds formed on the device, the
-weight versions of the C ABI (round 6: checked on the device)."""
+"""GPU tests of graph capture and of what a captured loop carries: workspaces under capture, the reference-shaped drivers
+(FieldTransformation.run, qed_helpers.ft_run) as captured loops against their eager loops, the carried state keyed by the weights'
+content, the weight versions of the C ABI checked on the device, and graph_loop.capture itself."""
 import math
 
-import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT  # noqa: F401
-from fthmc_amd.graph_loop import capture       # torch.cuda.graph with the garbage collector held off (see there)
+from gpu_support import R, capture, close, module_defaults, ops
 
 pytestmark = pytest.mark.gpu
-
-ops = None
-R = None
+_defaults = module_defaults()
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, R
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    from oracle import ref_cpu as _R
-    ops, R = _ops, _R
-    ops.set_variant(1)
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+# ---------------------------------------------------------------- workspace vs captured graphs
+def test_workspace_survives_growth_after_capture():
+    """A graph captured on a stream keeps replaying correctly after a larger call on the same stream replaced
+    that stream's workspace; and growing a workspace during capture is refused."""
+    from fthmc_amd._lib import FthmcError
+    gen = torch.Generator().manual_seed(3)
+    nl, beta = 2, 2.0
+    flow = R.default_flow(nl, gen)
+    w = ops.pack_weights(flow, device='cuda')
+    xs = ((torch.rand(2, 2, 16, 16, generator=gen, dtype=torch.float64) * 2 - 1) * math.pi).cuda()
+    xl = ((torch.rand(8, 2, 32, 32, generator=gen, dtype=torch.float64) * 2 - 1) * math.pi).cuda()
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        want = ops.ft_force(xs, w, nl, beta).clone()            # warm-up: allocates this stream's workspace
+        st.synchronize()
+        out = torch.empty_like(xs)
+        graph = torch.cuda.CUDAGraph()
+        with capture(graph, st):
+            out.copy_(ops.ft_force(xs, w, nl, beta))
+        with pytest.raises(FthmcError, match='graph capture'):
+            g2 = torch.cuda.CUDAGraph()
+            with capture(g2, st):
+                ops.ft_force(xl, w, nl, beta)                     # would have to grow the workspace while capturing
+        big = ops.ft_force(xl, w, nl, beta)                       # eager: the workspace is replaced, the old one retired
+        big2 = ops.ft_force(xl, w, nl, beta)
+        out.zero_()
+        graph.replay()
+        st.synchronize()
+        assert torch.equal(out, want)
+        assert torch.equal(big, big2)
+    close(big, R.ft_force(xl.cpu(), flow, beta), rtol=1e-8, atol=1e-9)
 
 
 def _model(L, nl, B, beta=2.0, seed=11):
@@ -36,23 +51,6 @@ def _model(L, nl, B, beta=2.0, seed=11):
     cfg = TrainConfig(L=L, beta=beta, n_layers=nl, batch_size=B, print_freq=0)
     torch.manual_seed(seed)
     return cfg, T.get_model(cfg)
-
-
-# ---------------------------------------------------------------- seeds on the device
-@pytest.mark.parametrize('seed,lo,B,traj', [(1331, 0, 128, 0), (7, 96, 32, 41), (2 ** 40 + 3, 1000, 5, 2 ** 33)])
-def test_chain_seeds_on_the_device_equal_the_host_helper(seed, lo, B, traj):
-    """fthmc_chain_seeds = parallel.chain_seeds (SplitMix64 of (seed, global chain id, trajectory)), also through a device
-    counter that a captured launch advances."""
-    from fthmc_amd import parallel
-    want = parallel.chain_seeds(seed, lo, lo + B, traj)
-    got = ops.chain_seeds(seed, lo, B, traj=traj, device='cuda')
-    assert torch.equal(got.cpu(), want)
-    counter = torch.tensor([traj], dtype=torch.int64, device='cuda')
-    out = torch.empty(B, dtype=torch.int64, device='cuda')
-    for k in range(3):
-        ops.chain_seeds(seed, lo, B, counter=counter, advance=True, out=out)
-        assert torch.equal(out.cpu(), parallel.chain_seeds(seed, lo, lo + B, traj + k)), k
-    assert int(counter) == traj + 3
 
 
 # ---------------------------------------------------------------- the captured run loop
@@ -262,36 +260,6 @@ def test_captured_ft_run_equals_the_eager_loop(tmp_path):
     assert res['graph'][2] == res['eager'][2]
 
 
-# ---------------------------------------------------------------- the reference's GradScaler option
-def test_train_step_with_a_grad_scaler_equals_the_plain_step():
-    """train_step(scaler=GradScaler()) (train.py:206-209, 321-324): scale(loss).backward(), scaler.step, scaler.update on the
-    autograd route leave the weights of the plain step (fp64: the scale is a power of two, scaling and unscaling are exact) and
-    the same metrics; train(use_scaler=True) runs."""
-    from fthmc_amd import train as T
-    from fthmc_amd.config import TrainConfig
-    from fthmc_amd.utils import layers as LY
-    from fthmc_amd.utils import qed_helpers as qed
-    tc = TrainConfig(L=8, beta=2.0, n_layers=2, batch_size=6, base_lr=1e-3, print_freq=0, n_era=1, n_epoch=3)
-    torch.manual_seed(4)
-    m0 = T.get_model(tc)
-    init = {k: v.clone() for k, v in m0.layers.state_dict().items()}
-    xi = m0.prior.sample_n(6)
-    act = qed.BatchAction(tc.beta)
-    res = {}
-    for tag in ('plain', 'scaler'):
-        model = T.get_model(tc); model.layers.load_state_dict(init)
-        opt = torch.optim.Adam(model.layers.parameters(), lr=tc.base_lr)
-        sc = torch.amp.GradScaler('cuda') if tag == 'scaler' else None
-        met = [T.train_step(model, tc, act, opt, 6, xi=xi, scaler=sc, fused=False) for _ in range(3)]
-        res[tag] = (LY.flow_weights(model.layers).clone(), met)
-    assert torch.equal(res['plain'][0], res['scaler'][0])
-    for a, b in zip(res['plain'][1], res['scaler'][1]):
-        for k in T.METRIC_KEYS:
-            np.testing.assert_array_equal(a[k], b[k])
-    out = T.train(tc, use_scaler=True, verbose=False)
-    assert len(out['history']['loss_dkl']) == 3 and np.isfinite(out['history']['loss_dkl'][-1])
-
-
 def test_two_captured_loops_with_different_flows_do_not_disturb_each_other():
     """Two FieldTransformations over different flows, their captured runs interleaved (and an eager batch call in between on
     the shared stream pool): every run equals the eager loop of its own flow -- the replays carry no weight expansion, so each
@@ -331,33 +299,26 @@ def test_two_captured_loops_with_different_flows_do_not_disturb_each_other():
     assert type(plain) is dict and torch.equal(torch.stack(plain['dh']), torch.stack(ha1['dh']))
 
 
-# ---------------------------------------------------------------- more of the headline size against the oracle
-def test_headline_size_two_chain_groups_against_the_oracle():
-    """BASELINE configs[2] at its own lattice size and depth (L = 64, beta = 6, 8 layers), 24 chains = two chain groups on two
-    streams: S_eff, log det J, plaquette, Q, the force and ONE WHOLE 10-step trajectory (H0, H1, dH, accepts, end field) against
-    the oracle on all 24 chains (the round-4 suite compared 3 chains at this size; bench.py compares 128 in every run)."""
-    B, L, nl, beta, dt, nstep = 24, 64, 8, 6.0, 0.1, 10
-    gen = torch.Generator().manual_seed(4242)
-    flow = R.default_flow(nl, gen)
-    w = ops.pack_weights(flow, device='cuda')
-    x = 0.35 * (torch.rand(B, 2, L, L, generator=gen, dtype=torch.float64) * 2 - 1)        # near-cold, as the bench's chains
-    v = torch.randn(B, 2, L, L, generator=gen, dtype=torch.float64)
-    u = torch.rand(B, generator=gen, dtype=torch.float64)
-    torch.set_num_threads(max(1, min(16, torch.get_num_threads())))
-    y, ld = R.flow_forward(x, flow)
-    Sg, ldg, pg, qg = ops.ft_action(x.cuda(), w, nl, beta)
-    np.testing.assert_allclose(H(ldg), H(ld), rtol=1e-11, atol=1e-10)
-    np.testing.assert_allclose(H(Sg), H(R.ft_action(x, flow, beta)), rtol=1e-12)
-    np.testing.assert_allclose(H(pg), H(R.plaq_mean(y, beta)), rtol=1e-12)
-    np.testing.assert_allclose(H(qg), H(R.charge(y)), atol=1e-8)
-    F = R.ft_force(x, flow, beta)
-    np.testing.assert_allclose(H(ops.ft_force(x.cuda(), w, nl, beta)), H(F), rtol=1e-8, atol=1e-9 * float(F.abs().max()))
-    dH, _, acc, newx, h0, h1 = R.ft_hmc(x, v, u, flow, beta, dt, nstep, mode='md')
-    r = ops.ft_trajectory(x.cuda(), v.cuda(), u.cuda(), w, nl, beta, dt, nstep, mode='md', groups=2)
-    np.testing.assert_allclose(H(r['H0']), H(h0), rtol=1e-12)
-    np.testing.assert_allclose(H(r['H1']), H(h1), rtol=1e-9)                     # ten MD steps amplify rounding
-    np.testing.assert_allclose(H(r['dH']), H(dH), rtol=0, atol=1e-6 * float(h1.abs().max()))
-    border = (u - torch.exp(-dH)).abs() < 1e-9
-    assert bool((((r['acc'].cpu() > 0.5) == acc) | border).all())
-    d = (r['x_new'].cpu() - newx + math.pi) % (2 * math.pi) - math.pi
-    assert float(d.abs().max()) < 1e-6
+def test_capture_holds_the_garbage_collector_off():
+    """graph_loop.capture: no automatic collection starts in the capturing thread (a finaliser that calls into the HIP runtime --
+    an older graph's, a stream's -- would end the process there); the collector's state comes back, also after an error"""
+    import gc
+    from fthmc_amd.graph_loop import capture
+    st, t = torch.cuda.Stream(), torch.zeros(4, dtype=torch.float64, device='cuda')
+    st.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(st):
+        t.add_(1.0)
+        st.synchronize()
+        g = torch.cuda.CUDAGraph()
+        assert gc.isenabled()
+        with capture(g, st):
+            assert not gc.isenabled()
+            t.add_(1.0)
+        assert gc.isenabled()
+        g.replay(); g.replay()
+        st.synchronize()
+        assert float(t[0]) == 3.0
+        with pytest.raises(ZeroDivisionError):
+            with capture(torch.cuda.CUDAGraph(), st):
+                1 / 0
+        assert gc.isenabled() and not torch.cuda.is_current_stream_capturing()

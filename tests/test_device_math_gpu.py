@@ -21,8 +21,10 @@ import pytest
 import torch  # noqa: F401  (before the probe: its libamdhip64 is the process's one HIP runtime, as fthmc_amd/_lib.py does)
 
 from conftest import ROOT
+from gpu_support import module_defaults
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
 mpmath = pytest.importorskip('mpmath')
 mpmath.mp.dps = 40

@@ -45,9 +45,11 @@ import pytest
 import torch  # noqa: F401  (before the probe: its libamdhip64 is the process's one HIP runtime)
 
 import test_device_math_gpu as M
+from gpu_support import module_defaults
 from test_device_math_gpu import probe  # noqa: F401  (the module-scoped fixture that builds and loads the probe)
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
 mpmath = pytest.importorskip('mpmath')
 mpmath.mp.dps = 40

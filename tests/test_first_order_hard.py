@@ -16,7 +16,7 @@ import torch
 
 import first_order_cases as FC
 import second_order_cases as C
-from conftest import ROOT, golden_flow, load_golden
+from conftest import ROOT, load_golden
 from oracle import ref_cpu as R
 
 
@@ -68,25 +68,12 @@ def test_training_gradient_is_the_action_vjp(case):
     FC.hold(FC.per_chain(a['F'], FC.oracle(case)['F'], 'F'), FC.SENS_BOUND, case.name)
 
 
-def steep_fixture():
-    """(fixture, Inputs, reference results keyed like first_order_cases.oracle_results) of tests/golden/first_order_steep_L8.npz"""
-    g = load_golden('first_order_steep_L8')
-    nl = int(g['n_layers'])
-    t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
-    x = t(g['x'])
-    z = torch.zeros(x.shape[0], dtype=torch.float64)
-    inp = FC.Inputs(golden_flow(g), x, torch.zeros_like(x), z, z, str(g['act']))
-    ref = {'F': t(g['F']), 'S_eff': t(g['S_eff']), 'logq': t(g['logq']), 'logp': t(g['logp']),
-           'gw': [tuple(t(g[f'gw{li}_{pi}']) for pi in range(6)) for li in range(nl)]}
-    return g, inp, ref
-
-
 def test_oracle_reproduces_the_steep_fixture():
     """the oracle against the reference's own ft_force, ft_action and train_step at the hard case, per tensor and per chain, at
     the conditioning bound of the cases: two fp64 implementations of the same graph"""
     path = os.path.join(ROOT, 'tests', 'golden', 'first_order_steep_L8.npz')
     assert os.path.getsize(path) < 512 * 1024
-    g, inp, ref = steep_fixture()
+    g, inp, ref = FC.steep_fixture()
     assert (int(g['n_layers']), g['x'].shape, float(g['beta']), str(g['act'])) == (8, (2, 2, 8, 8), FC.BETA, 'silu')
     assert np.all(g['x'][0, 0, 0, :] == np.pi - 1e-9) and np.all(g['x'][0, 1, :, 0] == -np.pi + 1e-9)
     # the parameters are the scaled ones: three times the default init's range 1 / sqrt(fan_in)

@@ -3,12 +3,12 @@
 ops.flow_forward, ops.ft_action, ops.ft_force, ops.ft_leapfrog (one step), ops.train_grad and, layer by layer, ops.flow_layer_bwd
 (with the stash route beside it) against the CPU oracle, with scaled-up weights and links pinned 1e-9 from +-pi, under every
 setting that serves the case:
-  mfma        set_variant(1), small path on (the default): csrc/flow_small.hip for the default net on L = 8, 12, 16, the tiled
+  mfma        variant 1, small path on (the default): csrc/flow_small.hip for the default net on L = 8, 12, 16, the tiled
               kernels (flow_fwd.hip, flow_bwd_gather.hip, flow_bwd_train.hip, flow_wgrad.hip) on its other lattices,
               csrc/flow_generic.hip for the other net and for the final tanh
-  mfma-tiled  set_variant(1), set_small_path(False): the default net on L = 8, 12, 16 through the tiled kernels (one wrapping tile,
+  mfma-tiled  variant 1, small path off: the default net on L = 8, 12, 16 through the tiled kernels (one wrapping tile,
               ragged tiles)
-  valu        set_variant(0): the default net through the VALU twins of csrc/flow.hip, every L
+  valu        variant 0: the default net through the VALU twins of csrc/flow.hip, every L
 Measure and bound (second_order_cases.py): max|got - ref| / max|ref| <= 1e-9 for every layer's every parameter tensor and for every
 chain of every output (links as angle differences), where tests/test_hip_parity.py test_activations_and_extremes_vs_oracle takes
 rtol 1e-7 over the batch and an atol from the largest gradient of all tensors; tests/test_first_order_hard.py asserts on the CPU
@@ -73,19 +73,18 @@ pass (its 10 under valu, and under mfma and mfma-tiled the three of scale 1 on L
 weight-gradient tensor (2 .. 11 entries beyond atol = 1e-9 max|g|), none in the force: at rtol = 1e-7 over the batch a force that is
 wrong by 2e-8 in every chain passes in all 30.
 """
+import contextlib
+
 import pytest
 import torch
 
 import first_order_cases as FC
 import walk_model as W
+from first_order_cases import SETTINGS, train_path
+from gpu_support import D, R, lib, module_defaults, ops, switches
 
 pytestmark = pytest.mark.gpu
-
-SETTINGS = {'mfma': (1, True), 'mfma-tiled': (1, False), 'valu': (0, True)}
-
-
-def _default_net(case):
-    return case.arch is None and not case.tanh
+_defaults = module_defaults()
 
 
 def serves(case, setting):
@@ -93,8 +92,8 @@ def serves(case, setting):
     if setting == 'mfma':
         return True
     if setting == 'mfma-tiled':
-        return _default_net(case) and W.ft_small_shape(case.L, case.nl)
-    return _default_net(case)
+        return FC.default_net(case) and W.ft_small_shape(case.L, case.nl)
+    return FC.default_net(case)
 
 
 PAIRS = [(c, s) for c in FC.CASES for s in SETTINGS if serves(c, s)]
@@ -104,45 +103,19 @@ LAYER_PAIRS = [(c, s) for c, s in PAIRS if s != 'mfma-tiled']
 LAYER_IDS = [f'{c.name}-{s}' for c, s in LAYER_PAIRS]
 
 
-def train_path(case, setting):
-    """the kernels behind ops.train_grad's weight gradients for a case under a setting"""
-    if not _default_net(case):
-        return 'generic'
-    if setting == 'valu':
-        return 'valu'
-    if setting == 'mfma':
-        return W.train_launch(case.B, case.L, case.nl)[0]
-    assert W.ft_small_shape(case.L, case.nl) and not W.flow_bwd_train_shape(case.L)
-    return 'two-kernel'
-
-
-def D(t):
-    return torch.as_tensor(t, dtype=torch.float64).cuda()
-
-
-@pytest.fixture(autouse=True)
-def _switches_back():
-    from fthmc_amd import ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    yield
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
+@contextlib.contextmanager
 def select(case, setting):
-    """set the switches of a setting and assert, before any call, that they are what the case runs under"""
-    from fthmc_amd import _lib, ops
+    """the switches of a setting for the block, asserted, before any call, to be what the case runs under"""
     assert serves(case, setting)
     variant, small = SETTINGS[setting]
-    ops.set_variant(variant)
-    ops.set_small_path(small)
-    assert ops.get_variant() == variant and ops.get_small_path() == small
-    # the library's own view of the variant: the default net has a layer stash under the MFMA kernels alone
-    assert (_lib.load().fthmc_layer_stash_bytes(None, case.B, case.L) != 0) == (variant == 1)
+    with switches(variant=variant, small=small):
+        assert ops.get_variant() == variant and ops.get_small_path() == small
+        # the library's own view of the variant: the default net has a layer stash under the MFMA kernels alone
+        assert (lib.fthmc_layer_stash_bytes(None, case.B, case.L) != 0) == (variant == 1)
+        yield
 
 
 def _weights(inp, case, layers=None):
-    from fthmc_amd import ops
     return ops.pack_weights(inp.flow if layers is None else [inp.flow[li] for li in layers], device='cuda', final_tanh=case.tanh)
 
 
@@ -155,16 +128,15 @@ def _show(case, setting, what, errs):
 def test_forward_action_force_and_leapfrog_per_chain(case, setting):
     """flow_forward, ft_action, ft_force and one ft_leapfrog step (the trajectory's own sweep instances, in place on the exact
     tiles) per chain; the force twice, the same bits"""
-    from fthmc_amd import ops
     inp, ref = FC.inputs(case), FC.oracle(case)
-    select(case, setting)
-    w, x, nl, act = _weights(inp, case), D(inp.x), case.nl, case.act
-    y, ld = ops.flow_forward(x, w, nl, act)
-    S, ld2 = ops.ft_action(x, w, nl, FC.BETA, act)[:2]
-    F = ops.ft_force(x, w, nl, FC.BETA, act)
-    lf_x, lf_v = ops.ft_leapfrog(x, D(inp.g), w, nl, FC.BETA, FC.DT, 1, act)
-    assert torch.equal(ops.ft_force(x, w, nl, FC.BETA, act), F)
-    assert torch.equal(x, D(inp.x))
+    with select(case, setting):
+        w, x, nl, act = _weights(inp, case), D(inp.x), case.nl, case.act
+        y, ld = ops.flow_forward(x, w, nl, act)
+        S, ld2 = ops.ft_action(x, w, nl, FC.BETA, act)[:2]
+        F = ops.ft_force(x, w, nl, FC.BETA, act)
+        lf_x, lf_v = ops.ft_leapfrog(x, D(inp.g), w, nl, FC.BETA, FC.DT, 1, act)
+        assert torch.equal(ops.ft_force(x, w, nl, FC.BETA, act), F)
+        assert torch.equal(x, D(inp.x))
     errs = FC.compare({'y': y, 'logdet': ld, 'S_eff': S, 'F': F, 'lf_x': lf_x, 'lf_v': lf_v}, ref, inp.flow)
     errs.update({f'{k} (ft_action)': v for k, v in FC.compare({'logdet': ld2}, ref, inp.flow).items()})
     assert len(errs) == 7 * case.B
@@ -174,14 +146,13 @@ def test_forward_action_force_and_leapfrog_per_chain(case, setting):
 @pytest.mark.parametrize('case,setting', PAIRS, ids=PAIR_IDS)
 def test_train_grad_per_tensor(case, setting):
     """train_grad: the weight gradient per tensor, log q, log p and the flowed links per chain; twice, the same bits"""
-    from fthmc_amd import ops
     inp, ref = FC.inputs(case), FC.oracle(case)
-    select(case, setting)
     path = train_path(case, setting)
     assert path == {'mfma': EXPECTED_PATHS[case.name], 'mfma-tiled': 'two-kernel', 'valu': 'valu'}[setting]
-    w, x = _weights(inp, case), D(inp.x)
-    r = ops.train_grad(x, w, case.nl, FC.BETA, case.act)
-    r2 = ops.train_grad(x, w, case.nl, FC.BETA, case.act)
+    with select(case, setting):
+        w, x = _weights(inp, case), D(inp.x)
+        r = ops.train_grad(x, w, case.nl, FC.BETA, case.act)
+        r2 = ops.train_grad(x, w, case.nl, FC.BETA, case.act)
     assert all(torch.equal(r[k], r2[k]) for k in ('gw', 'logq', 'logp', 'x'))
     errs = FC.compare({'gw': r['gw'], 'logq': r['logq'], 'logp': r['logp'], 'y': r['x']}, ref, inp.flow)
     assert len(errs) == 6 * case.nl + 3 * case.B
@@ -192,23 +163,21 @@ def test_train_grad_per_tensor(case, setting):
 def test_layer_vjps_per_tensor(case, setting):
     """every layer on its own at its (mu, off): flow_layer_bwd's link gradient per chain and weight gradient per tensor, the
     layer's links and log J from the stash forward; where the variant has a stash, the two-call route returns the same bits"""
-    from fthmc_amd import ops
-    from oracle import ref_cpu as R
     inp, ref = FC.inputs(case), FC.oracle(case)
-    select(case, setting)
     x, c, dlog, act = D(inp.x), D(inp.g), D(inp.gS), case.act
     got = {'layer_y': [], 'layer_logJ': [], 'layer_gx': [], 'layer_gw': []}
-    for li in range(case.nl):
-        mu, off = R.layer_mu_off(li)
-        wl = _weights(inp, case, [li])
-        gx, gw = ops.flow_layer_bwd(x, wl, c, dlog, mu, off, act, need_gw=True)
-        y, logJ, stash = ops.flow_layer_fwd_stash(x, wl, mu, off, act)
-        assert (stash is not None) == (setting == 'mfma')
-        if stash is not None:
-            gxs, gws = ops.flow_layer_bwd_stash(stash, tuple(x.shape), wl, c, dlog, mu, off, act, need_gw=True)
-            assert torch.equal(gxs, gx) and torch.equal(gws, gw), (case.name, li)
-        for k, v in zip(('layer_y', 'layer_logJ', 'layer_gx', 'layer_gw'), (y, logJ, gx, gw)):
-            got[k].append(v)
+    with select(case, setting):
+        for li in range(case.nl):
+            mu, off = R.layer_mu_off(li)
+            wl = _weights(inp, case, [li])
+            gx, gw = ops.flow_layer_bwd(x, wl, c, dlog, mu, off, act, need_gw=True)
+            y, logJ, stash = ops.flow_layer_fwd_stash(x, wl, mu, off, act)
+            assert (stash is not None) == (setting == 'mfma')
+            if stash is not None:
+                gxs, gws = ops.flow_layer_bwd_stash(stash, tuple(x.shape), wl, c, dlog, mu, off, act, need_gw=True)
+                assert torch.equal(gxs, gx) and torch.equal(gws, gw), (case.name, li)
+            for k, v in zip(('layer_y', 'layer_logJ', 'layer_gx', 'layer_gw'), (y, logJ, gx, gw)):
+                got[k].append(v)
     errs = FC.compare(got, ref, inp.flow)
     assert len(errs) == 6 * case.nl + 2 * case.nl * case.B + case.B
     _show(case, setting, 'layers', errs)
@@ -240,18 +209,16 @@ def test_cases_reach_every_path():
 def test_entry_points_match_the_steep_reference_fixture():
     """tests/golden/first_order_steep_L8.npz: the reference's own ft_force, ft_action and train_step gradients at scale 3 on 8
     layers with the pinned links, under the three settings"""
-    from fthmc_amd import ops
-    from test_first_order_hard import steep_fixture
-    g, inp, ref = steep_fixture()
+    g, inp, ref = FC.steep_fixture()
     beta, nl, act = float(g['beta']), int(g['n_layers']), str(g['act'])
     case = FC.Case('steep_fixture', 8, 2, nl, 3.0, act, None, False)
     w, x = ops.pack_weights(inp.flow, device='cuda'), D(inp.x)
     errs = {}
     for setting in SETTINGS:
-        select(case, setting)
-        r = ops.train_grad(x, w, nl, beta, act)
-        got = {'F': ops.ft_force(x, w, nl, beta, act), 'S_eff': ops.ft_action(x, w, nl, beta, act)[0],
-               'gw': r['gw'], 'logq': r['logq'], 'logp': r['logp']}
+        with select(case, setting):
+            r = ops.train_grad(x, w, nl, beta, act)
+            got = {'F': ops.ft_force(x, w, nl, beta, act), 'S_eff': ops.ft_action(x, w, nl, beta, act)[0],
+                   'gw': r['gw'], 'logq': r['logq'], 'logp': r['logp']}
         errs.update({f'{k} ({setting})': v for k, v in FC.compare(got, ref, inp.flow).items()})
     assert len(errs) == 3 * (48 + 4 * 2)
     print('steep fixture: worst %.1e (%s)' % FC.worst(errs)[::-1])

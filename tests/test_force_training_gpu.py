@@ -12,14 +12,12 @@ import pytest
 import torch
 
 from conftest import golden_flow, load_golden
+from gpu_support import D, R, module_defaults, ops, switches
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults(dual=1)
 
 TOL = 1e-9
-
-
-def D(a):
-    return torch.as_tensor(np.asarray(a), dtype=torch.float64).cuda() if not torch.is_tensor(a) else a.to(torch.float64).cuda()
 
 
 def rel(a, b):
@@ -33,7 +31,6 @@ def field(B, L, gen, scale=math.pi):
 
 def oracle_force_loss(x, flow, beta, act='silu'):
     """CPU double backward of oracle.ref_cpu.ft_action: F, sum F_b^2, d/dw sum_b |F_b|^2 (flat, canonical order)"""
-    from oracle import ref_cpu as R
     fl = [tuple(t.detach().clone().requires_grad_(True) for t in layer) for layer in flow]
     params = [t for layer in fl for t in layer]
     xg = x.detach().cpu().clone().requires_grad_(True)
@@ -43,17 +40,9 @@ def oracle_force_loss(x, flow, beta, act='silu'):
     return F.detach(), (F.detach() ** 2).sum((1, 2, 3)), cat
 
 
-@pytest.fixture(autouse=True)
-def _switches_back():
-    from fthmc_amd import ops
-    yield
-    ops.set_dual_path(1); ops.set_variant(1); ops.set_small_path(True)
-
-
 # ---------------------------------------------------------------- 1. fixture
 def test_matches_the_reference_fixture():
     """tests/golden/force_train_L8.npz: the reference's own autograd through ft_force(create_graph=True) and (F ** 2).sum()"""
-    from fthmc_amd import ops
     g = load_golden('force_train_L8')
     nl, beta = int(g['n_layers']), float(g['beta'])
     w = ops.pack_weights(golden_flow(g), device='cuda')
@@ -80,7 +69,6 @@ _CASES = {}
 def _case(i):
     """inputs and the oracle's results of shape i, computed once and never modified"""
     if i not in _CASES:
-        from oracle import ref_cpu as R
         L, B, nl, act, arch = SHAPES[i]
         gen = torch.Generator().manual_seed(1000 * L + 10 * nl + B)
         flow = R.default_flow(nl, gen) if arch is None else R.default_flow(nl, gen, hidden=arch[0], k=arch[1], n_mix=arch[2])
@@ -91,7 +79,6 @@ def _case(i):
 
 @pytest.mark.parametrize('i', range(len(SHAPES)))
 def test_matches_the_oracle_double_backward(i):
-    from fthmc_amd import ops
     L, B, nl, act, arch = SHAPES[i]
     flow, x, (F_r, fs_r, gw_r) = _case(i)
     w = ops.pack_weights(flow, device='cuda')
@@ -107,31 +94,27 @@ def test_matches_the_oracle_double_backward(i):
 
 
 def test_fused_kernels_agree_with_the_plain_dual_sweep_and_serve_their_shapes():
-    from fthmc_amd import ops
     fused = 0
-    try:
-        for i, (L, B, nl, act, arch) in enumerate(SHAPES):
-            ops.set_dual_path(1)
+    for i, (L, B, nl, act, arch) in enumerate(SHAPES):
+        with switches(dual=1):
             if ops.train_force_path(B, L, arch) != 1:
                 continue
             fused += 1
             flow, x, (F_r, fs_r, gw_r) = _case(i)
             w = ops.pack_weights(flow, device='cuda')
             on = ops.train_force_grad(D(x), w, nl, 2.0, act)
-            ops.set_dual_path(0)
+        with switches(dual=0):
             assert ops.train_force_path(B, L, arch) == 0
             off = ops.train_force_grad(D(x), w, nl, 2.0, act)
             vjp = 2 * ops.ft_force_vjp(D(x), w, nl, 2.0, on['F'], act, need_gx=False)[1]
-            assert torch.equal(on['F'], off['F']) and torch.equal(on['force_sq'], off['force_sq'])
-            assert torch.equal(off['gw'], vjp)                    # the plain sweep IS the force VJP's, seeded with F, times two
-            errs = [rel(on['gw'], off['gw']), rel(on['gw'], vjp), rel(off['gw'], gw_r)]
-            print(f'L={L} B={B} layers={nl} {act}: fused vs plain, fused vs 2 vjp, plain vs oracle', errs)
-            assert max(errs) < TOL, errs
-            for tile in (2, 3):                                   # 8 x 8 tiles always / 8 x 16 tiles where they divide L
-                ops.set_dual_path(tile)
+        assert torch.equal(on['F'], off['F']) and torch.equal(on['force_sq'], off['force_sq'])
+        assert torch.equal(off['gw'], vjp)                    # the plain sweep IS the force VJP's, seeded with F, times two
+        errs = [rel(on['gw'], off['gw']), rel(on['gw'], vjp), rel(off['gw'], gw_r)]
+        print(f'L={L} B={B} layers={nl} {act}: fused vs plain, fused vs 2 vjp, plain vs oracle', errs)
+        assert max(errs) < TOL, errs
+        for tile in (2, 3):                                   # 8 x 8 tiles always / 8 x 16 tiles where they divide L
+            with switches(dual=tile):
                 assert rel(ops.train_force_grad(D(x), w, nl, 2.0, act)['gw'], off['gw']) < TOL
-    finally:
-        ops.set_dual_path(1)
     assert fused >= 3, fused            # a silent fallback to the plain sweep cannot pass
 
 
@@ -141,8 +124,6 @@ def test_fused_kernels_agree_with_the_plain_dual_sweep_and_serve_their_shapes():
 # L >= 32: L = 64 with 9 chains is 576 items of 8 x 8 tiles and 288 of 8 x 16, eight / four tiles per dimension; 288 also makes the
 # default setting pick the 8 x 16 tiles.  65 chains are 4160 items of 8 x 8 tiles: beyond the forward's 4096 workgroups.
 def test_many_items_per_workgroup_agree_with_the_plain_sweep_and_the_oracle():
-    from fthmc_amd import ops
-    from oracle import ref_cpu as R
     L, B, nl, act = 64, 9, 3, 'silu'
     gen = torch.Generator().manual_seed(640903)
     flow = R.default_flow(nl, gen)
@@ -150,46 +131,41 @@ def test_many_items_per_workgroup_agree_with_the_plain_sweep_and_the_oracle():
     x = field(B, L, gen)
     F_r, fs_r, gw_r = oracle_force_loss(x, flow, 2.0, act)
     x = D(x)
-    try:
-        ops.set_dual_path(0)
+    with switches(dual=0):
         assert ops.train_force_path(B, L) == 0
         off = ops.train_force_grad(x, w, nl, 2.0, act)
         vjp = 2 * ops.ft_force_vjp(x, w, nl, 2.0, off['F'], act, need_gx=False)[1]
         assert torch.equal(off['gw'], vjp)
-        wsb = {}
-        for path in (1, 2, 3):
-            ops.set_dual_path(path)
+    wsb = {}
+    for path in (1, 2, 3):
+        with switches(dual=path):
             assert ops.train_force_path(B, L) == 1
             wsb[path] = ops.train_force_ws_bytes(B, L, nl)
             on = ops.train_force_grad(x, w, nl, 2.0, act)
             again = ops.train_force_grad(x, w, nl, 2.0, act)
-            assert torch.equal(on['gw'], again['gw']) and torch.equal(on['F'], off['F'])
-            errs = [rel(on['gw'], off['gw']), rel(on['gw'], vjp), rel(on['gw'], gw_r), rel(on['F'], F_r), rel(on['force_sq'], fs_r)]
-            print(f'L={L} B={B} layers={nl} path {path}: fused vs plain, vs 2 vjp, vs oracle; F, force_sq vs oracle', errs)
-            assert max(errs) < TOL, (path, errs)
-        # the default picked the 8 x 16 tiles here: its workspace is theirs, not the 8 x 8 tiles'
-        assert wsb[1] == wsb[3] != wsb[2]
-        # more items than the forward kernel has workgroups
-        B2, nl2 = 65, 2
-        w2 = ops.pack_weights(R.default_flow(nl2, gen), device='cuda')
-        x2 = D(field(B2, L, gen))
-        ops.set_dual_path(0)
+        assert torch.equal(on['gw'], again['gw']) and torch.equal(on['F'], off['F'])
+        errs = [rel(on['gw'], off['gw']), rel(on['gw'], vjp), rel(on['gw'], gw_r), rel(on['F'], F_r), rel(on['force_sq'], fs_r)]
+        print(f'L={L} B={B} layers={nl} path {path}: fused vs plain, vs 2 vjp, vs oracle; F, force_sq vs oracle', errs)
+        assert max(errs) < TOL, (path, errs)
+    # the default picked the 8 x 16 tiles here: its workspace is theirs, not the 8 x 8 tiles'
+    assert wsb[1] == wsb[3] != wsb[2]
+    # more items than the forward kernel has workgroups
+    B2, nl2 = 65, 2
+    w2 = ops.pack_weights(R.default_flow(nl2, gen), device='cuda')
+    x2 = D(field(B2, L, gen))
+    with switches(dual=0):
         off2 = ops.train_force_grad(x2, w2, nl2, 2.0, 'relu')
-        ops.set_dual_path(2)
+    with switches(dual=2):
         assert ops.train_force_path(B2, L) == 1
         on2 = ops.train_force_grad(x2, w2, nl2, 2.0, 'relu')
         vjp2 = 2 * ops.ft_force_vjp(x2, w2, nl2, 2.0, on2['F'], 'relu', need_gx=False)[1]
-        errs = [rel(on2['gw'], off2['gw']), rel(on2['gw'], vjp2)]
-        print(f'L={L} B={B2} layers={nl2} path 2: fused vs plain, vs 2 vjp', errs)
-        assert max(errs) < TOL and torch.equal(on2['F'], off2['F']), errs
-    finally:
-        ops.set_dual_path(1)
+    errs = [rel(on2['gw'], off2['gw']), rel(on2['gw'], vjp2)]
+    print(f'L={L} B={B2} layers={nl2} path 2: fused vs plain, vs 2 vjp', errs)
+    assert max(errs) < TOL and torch.equal(on2['F'], off2['F']), errs
 
 
 # ---------------------------------------------------------------- 4. determinism and independence
 def test_determinism_chain_independence_and_the_other_switches():
-    from fthmc_amd import ops
-    from oracle import ref_cpu as R
     L, B, nl = 16, 3, 4
     gen = torch.Generator().manual_seed(77)
     w = ops.pack_weights(R.default_flow(nl, gen), device='cuda')
@@ -203,16 +179,15 @@ def test_determinism_chain_independence_and_the_other_switches():
     assert rel(sum(o['gw'] for o in ones), a['gw']) < 1e-12
     # the first-order force may differ between the variants and the small path by its own rounding, gw follows at 1e-9
     for variant, small in ((0, True), (1, False), (0, False)):
-        ops.set_variant(variant); ops.set_small_path(small)
-        c = ops.train_force_grad(x, w, nl, 2.0)
-        assert rel(c['F'], ops.ft_force(x, w, nl, 2.0)) == 0.0
+        with switches(variant=variant, small=small):
+            c = ops.train_force_grad(x, w, nl, 2.0)
+            assert rel(c['F'], ops.ft_force(x, w, nl, 2.0)) == 0.0
         assert rel(c['F'], a['F']) < TOL and rel(c['force_sq'], a['force_sq']) < TOL and rel(c['gw'], a['gw']) < TOL
 
 
 # ---------------------------------------------------------------- 5. edge inputs
 def test_edge_inputs():
     from fthmc_amd import _lib, ops
-    from oracle import ref_cpu as R
     L, B, nl = 8, 2, 2
     gen = torch.Generator().manual_seed(5)
     w = ops.pack_weights(R.default_flow(nl, gen), device='cuda')
@@ -357,8 +332,6 @@ def test_train_step_with_force_and_a_pre_model_follows_the_notebook(monkeypatch)
 
 def test_operator_agrees_with_ops():
     import fthmc_amd.torch_ops as TO
-    from fthmc_amd import ops
-    from oracle import ref_cpu as R
     assert 'train_force_grad' in TO.__all__
     L, B, nl = 16, 2, 3
     gen = torch.Generator().manual_seed(41)

@@ -27,34 +27,12 @@ import torch
 import steep_fixture as SF
 from steep_fixture import ULP_PI
 
-pytestmark = pytest.mark.gpu
+from gpu_support import H, R, close, module_defaults, ops
 
-ops = None
-R = None
+pytestmark = pytest.mark.gpu
+_defaults = module_defaults(small=False)          # L = 16 on the tiled kernels
 
 LAYERS = [(mu, off) for off in range(4) for mu in range(2)]
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, R
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    from oracle import ref_cpu as _R
-    ops, R = _ops, _R
-    ops.set_variant(1)
-    ops.set_small_path(False)          # L = 16 on the tiled kernels
-    yield
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def close(a, b, rtol=1e-10, atol=1e-10):
-    np.testing.assert_allclose(H(a), H(b), rtol=rtol, atol=atol)
 
 
 def draw(B, L, seed, nl=8):

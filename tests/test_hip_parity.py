@@ -8,52 +8,18 @@ import pytest
 import torch
 
 from conftest import golden_flow, load_golden
+from gpu_support import D, H, R, angle_close, close, module_defaults, ops, switches
 
 pytestmark = pytest.mark.gpu
-
-ops = None
-R = None
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, R
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    from oracle import ref_cpu as _R
-    ops, R = _ops, _R
+_defaults = module_defaults()
 
 
 @pytest.fixture(params=[(1, 1), (0, 1), (1, 0)], ids=['mfma', 'valu', 'mfma-tiled'], autouse=True)
-def variant(request, _mods):
-    """Every parity test runs against both conv-kernel variants (C ABI: fthmc_set_variant), and the MFMA variant also
-    with the small-lattice fused path switched off (fthmc_set_small_path: L = 8, 12, 16 then take the tiled kernels)."""
-    ops.set_variant(request.param[0])
-    ops.set_small_path(bool(request.param[1]))
-    yield request.param[0]
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def D(a):
-    return torch.from_numpy(np.asarray(a, dtype=np.float64).copy()).cuda()
-
-
-def H(t):
-    return t.detach().cpu().numpy()
-
-
-def close(a, b, rtol=1e-10, atol=1e-10):
-    a = H(a) if torch.is_tensor(a) else np.asarray(a)
-    b = H(b) if torch.is_tensor(b) else np.asarray(b)
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol)
-
-
-def angle_close(a, b, atol=1e-9):
-    a = H(a) if torch.is_tensor(a) else np.asarray(a)
-    b = H(b) if torch.is_tensor(b) else np.asarray(b)
-    d = (a - b + np.pi) % (2 * np.pi) - np.pi
-    assert np.max(np.abs(d)) < atol, np.max(np.abs(d))
+def variant(request):
+    """Every parity test runs against both conv-kernel variants, and the MFMA variant also with the small-lattice fused path
+    switched off (L = 8, 12, 16 then take the tiled kernels)."""
+    with switches(variant=request.param[0], small=bool(request.param[1])):
+        yield request.param[0]
 
 
 def W(flow):

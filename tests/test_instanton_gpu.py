@@ -14,29 +14,12 @@ from conftest import ROOT  # noqa: F401
 import instanton_cases as IC
 import local_update_cases as LC
 
+from gpu_support import D, H, module_defaults, ops
+
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
-ops = None
 LD = np.longdouble
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    ops.set_variant(1)
-    ops.set_small_path(True)
-    yield
-
-
-def H(t):
-    return t.detach().cpu().numpy()
-
-
-def D(a):
-    return torch.as_tensor(np.asarray(a, dtype=np.float64)).cuda()
 
 
 def S(seeds):

@@ -16,38 +16,14 @@ from conftest import ROOT  # noqa: F401
 
 import integrator_cases as IC
 
-pytestmark = pytest.mark.gpu
+from gpu_support import H, angle_close, close, module_defaults, ops, switches
 
-ops = None
-R = None
+pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
 TAU = 0.5
 INTEGRATORS = (('omelyan', 3), ('force_gradient', 2))
 BETA_PLAIN, BETA_FT = 3.0, 2.0
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, R
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    from oracle import ref_cpu as _R
-    ops, R = _ops, _R
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def close(a, b, rtol=1e-10, atol=1e-10):
-    np.testing.assert_allclose(H(a), H(b), rtol=rtol, atol=atol)
-
-
-def angle_close(a, b, atol):
-    d = (H(a) - H(b) + np.pi) % (2 * np.pi) - np.pi
-    assert np.max(np.abs(d)) < atol, np.max(np.abs(d))
 
 
 def flow_of(seed, nl, arch=None):
@@ -157,16 +133,11 @@ def test_ft_trajectory_vs_oracle(case, name, nstep):
     _, seed, B, L, nl, arch, variant, small = case
     flow, s, x, v, u, res = ft_case(seed, B, L, nl, name, nstep, arch)
     dt = TAU / nstep
-    try:
-        ops.set_variant(variant)
-        ops.set_small_path(small)
+    with switches(variant=variant, small=small):
         w = ops.pack_weights(flow, device='cuda')
         r = ops.ft_trajectory(x.cuda(), v.cuda(), u.cuda(), w, nl, BETA_FT, dt, nstep, mode='md', integrator=name)
         xo, vo = ops.ft_leapfrog(x.cuda(), v.cuda(), w, nl, BETA_FT, dt, nstep, integrator=name)
         torch.cuda.synchronize()
-    finally:
-        ops.set_variant(1)
-        ops.set_small_path(True)
     close(r['H0'], res['H0'], rtol=1e-10); close(r['H1'], res['H1'], rtol=1e-7)
     close(r['dH'], res['dH'], rtol=1e-6, atol=1e-6)
     assert np.array_equal(H(r['acc']) > 0.5, res['acc'].numpy())

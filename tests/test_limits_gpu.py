@@ -14,8 +14,10 @@ import pytest
 import torch
 
 from conftest import ROOT
+from gpu_support import module_defaults
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
 HDR = open(os.path.join(ROOT, 'include', 'fthmc_hip.h')).read()
 MAX_B = int(re.search(r'#define FTHMC_MAX_B (\d+)', HDR).group(1))

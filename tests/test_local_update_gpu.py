@@ -15,45 +15,15 @@ from conftest import ROOT  # noqa: F401
 import local_update_cases as LC
 import wilson_loop_cases as WC
 
-pytestmark = pytest.mark.gpu
+from gpu_support import D, H, module_defaults, ops, switches
 
-ops = None
+pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
+
 BETA, SWEEP = LC.BETA, LC.SWEEP
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    ops.set_variant(1)
-    ops.set_small_path(True)
-    yield
-    ops.set_small_path(True)
-
-
-class path:
-    """the class kernels at every L (False), or the one-launch kernel where it serves (True)"""
-
-    def __init__(self, resident):
-        self.resident = bool(resident)
-
-    def __enter__(self):
-        ops.set_small_path(self.resident)
-
-    def __exit__(self, *a):
-        ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy()
-
-
-def D(a):
-    return torch.as_tensor(np.asarray(a, dtype=np.float64)).cuda()
-
-
+# switches(small=resident): the one-launch kernel where it serves (True), or the class kernels at every L (False)
 def S(seeds):
     return torch.from_numpy(np.asarray(seeds, dtype=np.int64)).cuda()
 
@@ -74,7 +44,7 @@ def test_every_class_alone_against_the_twin_link_by_link(B, L, amp, kind, reside
     xd, sd = D(x), S(seeds)
     for k, t in enumerate(twin):
         mu, p = LC.CLASSES[k]
-        with path(resident):
+        with switches(small=bool(resident)):
             y = H(update(xd, kind, sd, classes=1 << k, sweep0=SWEEP))
         other = np.ones((2, L, L), dtype=bool); other[mu, t['ii'], t['jj']] = False
         assert np.array_equal(y[:, other], x[:, other]), f'class {mu, p}: a link outside the class changed'
@@ -97,7 +67,7 @@ def test_compositions_are_bit_equal(B, L):
     xd, sd = D(x), S(seeds)
     outs = {}
     for resident in (True, False):
-        with path(resident):
+        with switches(small=bool(resident)):
             full = ops.local_update(xd, BETA, sd, n_hb=1, n_or=1, sweep0=5)
             y = xd
             for n_hb, n_or in ((1, 0), (0, 1)):
@@ -126,7 +96,7 @@ def test_a_chain_of_a_batch_equals_the_chain_alone_and_per_chain_beta_equals_sca
     x, seeds = LC.uniform_links(B, L, 1000 + L), LC.chain_seeds(B, 2000 + L)      # the issue's shapes, two chains where it has one
     xd, sd = D(x), S(seeds)
     kw = dict(n_hb=1, n_or=1, nsweep=2, sweep0=1)
-    with path(resident):
+    with switches(small=bool(resident)):
         full = ops.local_update(xd, BETA, sd, **kw)
         for b in sorted({0, B // 2, B - 1}):
             assert torch.equal(ops.local_update(xd[b:b + 1].contiguous(), BETA, sd[b:b + 1].contiguous(), **kw)[0], full[b]), b
@@ -160,7 +130,7 @@ def test_overrelaxation_conserves_action_and_charge_over_ten_sweeps(B, L, reside
     tol = BETA * (2.0 * moved + 2.0 * LC.U * n * (n / 64.0 + 19.0))
     xd = D(x)
     S0, Q0, _ = ops.wilson_action_charge(xd, BETA)
-    with path(resident):
+    with switches(small=bool(resident)):
         yd = ops.local_update(xd, BETA, None, n_hb=0, n_or=10)
     S1, Q1, _ = ops.wilson_action_charge(yd, BETA)
     dS = np.abs(H(S1) - H(S0))
@@ -183,7 +153,7 @@ def test_the_cancelling_staple_pair_gives_finite_links_in_range(resident):
     sd = S(LC.chain_seeds(2, 9))
     for kind in ('hb', 'or'):
         for classes in (1, 2, 4, 8, 15):
-            with path(resident):
+            with switches(small=bool(resident)):
                 y = H(update(D(x), kind, sd, classes=classes, nsweep=3))
             assert np.all(np.isfinite(y)), (kind, classes)
             touched = y != x

@@ -10,7 +10,7 @@ Before its calls each test asserts that the packed weights carry the case's shap
   one layer     at all eight (mu, off), a layer beyond the case's own with the weights of layer li % layers: flow_layer_fwd,
                 flow_layer_bwd(need_gw=True), the stash route bit-equal to it; plaq_coupling_fwd / _bwd at (0, 0) and (1, 3)
   inverse       flow_layer_rev o flow_layer_fwd, flow_reverse o flow_forward, plaq_coupling_rev o plaq_coupling_fwd return the
-                input (links 1e-9 / 1e-8, log J 1e-8 / 1e-7: those of tests/test_round3_gpu.py
+                input (links 1e-9 / 1e-8, log J 1e-8 / 1e-7: those of tests/test_layer_calls_gpu.py
                 test_generic_net_shapes_against_the_oracle); mix64 and uneven_mix1 are the Newton solve on 64 and on 1 component
   exact         chain b of the batch == the chain alone, a second call == the first, in place == out of place, bit for bit; for
                 k9_L4 the field tiled 2 x 2 to L = 8 (there the k = 9 stencil is the un-aliased sum of the same taps) gives the
@@ -47,7 +47,7 @@ no address.
 5 of the 67 tests here fail on it, all of L132_stride, the one case whose site loop goes round twice: the sweeps (the force
 off by 0.7 of its largest entry), the second-order calls (already their second, identical call differs: the tails hold what the
 workspace held before), the one-layer calls (the stash route differs from the direct one), the chain alone, and the trajectory.  Its inverse test passes: forward and reverse read the same
-stale planes.  tests/test_round3_gpu.py test_generic_net_shapes_against_the_oracle (6 cases, L <= 20) and the hard-input suites
+stale planes.  tests/test_layer_calls_gpu.py test_generic_net_shapes_against_the_oracle (6 cases, L <= 20) and the hard-input suites
 tests/test_first_order_hard_gpu.py and tests/test_second_order_hard_gpu.py (122 tests, generic cases at L = 8) pass it.
 """
 import math
@@ -56,10 +56,11 @@ import pytest
 import torch
 
 import net_shape_cases as N
-from oracle import ref_cpu as R
-from test_first_order_hard_gpu import train_path
+from first_order_cases import train_path
+from gpu_support import D, R, module_defaults, ops
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
 FC, C = N.FC, N.C
 DT = FC.DT
@@ -70,13 +71,8 @@ SENSITIVITY = {'k9_L4': (1.7e-14, 1.1e-13), 'k5_L4_nohidden': (1.1e-13, 2.8e-14)
                'L20_k7': (5.7e-15, 9.8e-15), 'L132_stride': (1.2e-14, 6.6e-14)}
 
 
-def D(t):
-    return torch.as_tensor(t, dtype=torch.float64).cuda()
-
-
 def weights(case, layers=None):
     """the case's packed weights (of the listed layers), after asserting that they carry its shape and select the generic kernels"""
-    from fthmc_amd import ops
     inp = N.inputs(case)
     w = ops.pack_weights(inp.flow if layers is None else [inp.flow[li] for li in layers], device='cuda', final_tanh=case.tanh)
     assert ops.arch_of(w) == N.arch(case) != ops.DEFAULT_ARCH
@@ -99,7 +95,6 @@ def angle_err(a, b):
 def test_sweeps_per_chain_and_per_tensor(case):
     """flow_forward, ft_action, ft_force, one ft_leapfrog step and train_grad; the force and the training gradient twice, the
     same bits; the input untouched"""
-    from fthmc_amd import ops
     inp, ref = N.inputs(case), N.first_order(case)
     w, x, nl, act = weights(case), D(inp.x), case.nl, case.act
     y, ld = ops.flow_forward(x, w, nl, act)
@@ -122,7 +117,6 @@ def test_sweeps_per_chain_and_per_tensor(case):
 @pytest.mark.parametrize('case', N.CASES, ids=N.IDS)
 def test_second_order_per_chain_and_per_tensor(case):
     """ft_force_vjp, ft_action_vjp and train_force_grad (the Dual instances of the generic kernels); twice, the same bits"""
-    from fthmc_amd import ops
     inp, ref = N.inputs(case), N.second_order(case)
     w, x, nl, act = weights(case), D(inp.x), case.nl, case.act
     assert ops.vjp_ws_bytes(case.B, case.L, nl, N.arch(case)) > 0
@@ -143,7 +137,7 @@ def test_second_order_per_chain_and_per_tensor(case):
 def test_one_layer_at_every_stripe(case):
     """every (mu, off): the layer's links and log J, its link gradient per chain and its weight gradient per tensor; the stash
     route and the in-place forward return the same bits; the plaquette-level map and its VJP at (0, 0) and (1, 3)"""
-    from fthmc_amd import _lib, ops
+    from fthmc_amd import _lib
     inp, ref = N.inputs(case), N.layers_at_every_stripe(case)
     flow8 = N.eight_layers(inp).flow
     x, c, dlog, act = D(inp.x), D(inp.g), D(inp.gS), case.act
@@ -192,7 +186,6 @@ def test_one_layer_at_every_stripe(case):
 @pytest.mark.parametrize('case', N.CASES, ids=N.IDS)
 def test_inverses_return_the_input(case):
     """flow_layer_rev o flow_layer_fwd at every (mu, off), flow_reverse o flow_forward, plaq_coupling_rev o plaq_coupling_fwd"""
-    from fthmc_amd import ops
     inp = N.inputs(case)
     x, act, nl = D(inp.x), case.act, case.nl
     worst = {'layer x': 0.0, 'layer logJ': 0.0, 'plaq P': 0.0, 'plaq logJ': 0.0}
@@ -221,7 +214,6 @@ def test_inverses_return_the_input(case):
 @pytest.mark.parametrize('case', N.CASES, ids=N.IDS)
 def test_a_chain_of_the_batch_is_the_chain_alone(case):
     """every chain's results do not depend on the chains beside it, bit for bit: the sweeps, a layer, the Hessian product"""
-    from fthmc_amd import ops
     inp = N.inputs(case)
     w, w0, x, g, nl, act = weights(case), weights(case, [0]), D(inp.x), D(inp.g), case.nl, case.act
     full = (*ops.flow_forward(x, w, nl, act), *ops.ft_action(x, w, nl, N.BETA, act), ops.ft_force(x, w, nl, N.BETA, act),
@@ -241,7 +233,6 @@ def test_k9_on_L4_is_the_same_stencil_unaliased_on_L8():
     """k9_L4 tiled 2 x 2 to L = 8 with the same weights: on L = 8 the nine taps of a kernel row land on nine sites (one wraps),
     on L = 4 on four; the field has period 4, so every site sees the same sum in another order.  The flowed field and the force
     site for site to the bound, S_eff and log det times 4."""
-    from fthmc_amd import ops
     case = N.BY_NAME['k9_L4']
     inp = N.inputs(case)
     w, x, nl, act = weights(case), D(inp.x), case.nl, case.act
@@ -263,7 +254,6 @@ def test_k9_on_L4_is_the_same_stencil_unaliased_on_L8():
 @pytest.mark.parametrize('case', N.CASES, ids=N.IDS)
 def test_trajectory_against_the_oracle(case):
     """one 4-step MD trajectory from the case's links with v = g"""
-    from fthmc_amd import ops
     inp = N.inputs(case)
     w, nl, act = weights(case), case.nl, case.act
     u = torch.rand(case.B, generator=torch.Generator().manual_seed(N.seed(case) + 1), dtype=torch.float64)

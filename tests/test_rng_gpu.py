@@ -34,10 +34,11 @@ import torch
 
 import philox_ref as PR
 from conftest import ROOT
-from fthmc_amd import ops, parallel
-from fthmc_amd.graph_loop import capture
+from fthmc_amd import parallel
+from gpu_support import R, capture, module_defaults, ops, switches
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
 import mpmath          # a plain import: a missing mpmath must fail this file, not skip its bit-exact tests
 
@@ -386,7 +387,6 @@ def _hmc(x, v, u):
 
 
 def _flow(nl):
-    from oracle import ref_cpu as R
     return ops.pack_weights(R.default_flow(nl, torch.Generator().manual_seed(21)), device='cuda')
 
 
@@ -395,38 +395,14 @@ def _ft(nl):
     return lambda x, v, u: ops.ft_trajectory(x, v, u, w, nl, 2.0, 0.15, 3, mode='md')
 
 
-class _variant0:
-    def __enter__(self):
-        ops.set_variant(0)
-
-    def __exit__(self, *a):
-        ops.set_variant(1)
-
-
-class _small_off:
-    def __enter__(self):
-        ops.set_small_path(False)
-
-    def __exit__(self, *a):
-        ops.set_small_path(True)
-
-
-class _default:
-    def __enter__(self):
-        pass
-
-    def __exit__(self, *a):
-        pass
-
-
 # every accept site: k_hmc_trajectory (one launch, L <= 64), k_metropolis behind the step kernels (the row-strip leapfrog at
 # L = 64 with the VALU variant, which leaves the one-launch kernel aside), the small-lattice ftHMC kernel (flow_small.hip), and
-# k_metropolis behind the tiled flow kernels at L = 8 (small path off) and L = 32
-SITES = {'plain, one launch, L = 8': (8, lambda: _hmc, _default),
-         'plain, row strips, L = 64': (64, lambda: _hmc, _variant0),
-         'ftHMC, small-lattice path, L = 8': (8, lambda: _ft(2), _default),
-         'ftHMC, small-lattice path off, L = 8': (8, lambda: _ft(2), _small_off),
-         'ftHMC, tiled, L = 32': (32, lambda: _ft(2), _default)}
+# k_metropolis behind the tiled flow kernels at L = 8 (small path off) and L = 32; the third entry: the switches of the site
+SITES = {'plain, one launch, L = 8': (8, lambda: _hmc, {}),
+         'plain, row strips, L = 64': (64, lambda: _hmc, {'variant': 0}),
+         'ftHMC, small-lattice path, L = 8': (8, lambda: _ft(2), {}),
+         'ftHMC, small-lattice path off, L = 8': (8, lambda: _ft(2), {'small': False}),
+         'ftHMC, tiled, L = 32': (32, lambda: _ft(2), {})}
 
 
 @pytest.mark.parametrize('site', list(SITES))
@@ -443,7 +419,7 @@ def test_accept_step_at_the_ends_of_u(site):
     v = torch.randn(B, 2, L, L, generator=gen, dtype=torch.float64).cuda()
     zero = torch.zeros(B, dtype=torch.float64, device='cuda')
     top = torch.full((B,), 1.0 - U, dtype=torch.float64, device='cuda')
-    with ctx():
+    with switches(**ctx):
         run = make()
         lo = {k: t.clone() for k, t in run(x, v, zero).items() if k in ('x_new', 'dH', 'acc')}
         hi = {k: t.clone() for k, t in run(x, v, top).items() if k in ('x_new', 'dH', 'acc')}
@@ -505,3 +481,20 @@ def test_grid_stride_loop_does_each_pair_once():
         print(f'{draw}: wide {wide:.3f} ms, long {long_:.3f} ms, ratio {long_ / wide:.2f} (bound 4)')
     for draw, (wide, long_) in times.items():
         assert long_ <= 4 * wide, (draw, wide, long_)
+
+
+# ---------------------------------------------------------------- seeds on the device
+@pytest.mark.parametrize('seed,lo,B,traj', [(1331, 0, 128, 0), (7, 96, 32, 41), (2 ** 40 + 3, 1000, 5, 2 ** 33)])
+def test_chain_seeds_on_the_device_equal_the_host_helper(seed, lo, B, traj):
+    """fthmc_chain_seeds = parallel.chain_seeds (SplitMix64 of (seed, global chain id, trajectory)), also through a device
+    counter that a captured launch advances."""
+    from fthmc_amd import parallel
+    want = parallel.chain_seeds(seed, lo, lo + B, traj)
+    got = ops.chain_seeds(seed, lo, B, traj=traj, device='cuda')
+    assert torch.equal(got.cpu(), want)
+    counter = torch.tensor([traj], dtype=torch.int64, device='cuda')
+    out = torch.empty(B, dtype=torch.int64, device='cuda')
+    for k in range(3):
+        ops.chain_seeds(seed, lo, B, counter=counter, advance=True, out=out)
+        assert torch.equal(out.cpu(), parallel.chain_seeds(seed, lo, lo + B, traj + k)), k
+    assert int(counter) == traj + 3

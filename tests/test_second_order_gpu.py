@@ -8,12 +8,10 @@ import pytest
 import torch
 
 from conftest import load_golden
+from gpu_support import D, module_defaults
 
 pytestmark = pytest.mark.gpu
-
-
-def D(a):
-    return torch.as_tensor(np.asarray(a), dtype=torch.float64).cuda() if not torch.is_tensor(a) else a.to(torch.float64).cuda()
+_defaults = module_defaults()
 
 
 def rel(a, b):

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import second_order_cases as C
-from conftest import ROOT, golden_flow, load_golden
+from conftest import ROOT
 
 
 @pytest.mark.parametrize('case', C.CASES, ids=[c.name for c in C.CASES])
@@ -40,25 +40,12 @@ def test_cases_cover_what_they_are_for():
     assert a is b and C.oracle(C.CASES[0]) is C.oracle(C.CASES[0])
 
 
-def steep_fixture():
-    """(Inputs, reference results shaped like oracle_results) of tests/golden/second_order_steep_L8.npz; its action VJP carries gS
-    alone (the reference's ft_action returns S_eff): glogdet = 0"""
-    g = load_golden('second_order_steep_L8')
-    nl = int(g['n_layers'])
-    t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
-    inp = C.Inputs(golden_flow(g), t(g['x']), t(g['g']), t(g['gS']), torch.zeros(2, dtype=torch.float64), str(g['act']))
-    rows = lambda key: [tuple(t(g[f'{key}{li}_{pi}']) for pi in range(6)) for li in range(nl)]
-    ref = {'F': t(g['F']), 'Hg': t(g['Hg']), 'gw_vjp': rows('gw'), 'ax': t(g['ga_x']), 'aw': rows('ga_w'),
-           'force_sq': t(g['force_sq']), 'gw_force': rows('gq')}
-    return g, inp, ref
-
-
 def test_oracle_reproduces_the_steep_fixture():
     """the oracle's double backward against the reference's own autograd at the hard case, per tensor and per chain, at the
     conditioning bound of the cases: two fp64 implementations of the same graph"""
     path = os.path.join(ROOT, 'tests', 'golden', 'second_order_steep_L8.npz')
     assert os.path.getsize(path) < 512 * 1024
-    g, inp, ref = steep_fixture()
+    g, inp, ref = C.steep_fixture()
     assert (int(g['n_layers']), g['x'].shape, float(g['beta'])) == (8, (2, 2, 8, 8), C.BETA)
     assert np.all(g['x'][0, 0, 0, :] == np.pi - 1e-9) and np.all(g['x'][0, 1, :, 0] == -np.pi + 1e-9)
     # the parameters are the scaled ones: three times the default init's range 1 / sqrt(fan_in)

@@ -1,7 +1,7 @@
 """GPU: the three second-order sweeps on the hard cases of tests/second_order_cases.py, tensor by tensor.
 
 ops.ft_force_vjp (H g, d/dw <g, F>), ops.ft_action_vjp (d/dx, d/dw of sum gS S_eff + glogdet logdet) and ops.train_force_grad
-(F, sum F^2, d/dw sum |F|^2) under every ops.set_dual_path setting that serves the shape -- 0: the plain dual sweep
+(F, sum F^2, d/dw sum |F|^2) under every setting of the dual-path switch that serves the shape -- 0: the plain dual sweep
 (csrc/flow_generic.hip on Dual), 2: the fused kernels of csrc/flow_dual.hip on 8 x 8 tiles, 3: on 8 x 16 tiles where they divide L,
 1: the default -- against the oracle's double backward, with scaled-up weights and links pinned 1e-9 from +-pi.  Before each call
 ops.train_force_path asserts which path serves it: a silent fallback cannot pass.  Measure and bound (second_order_cases.py):
@@ -35,21 +35,12 @@ import pytest
 import torch
 
 import second_order_cases as C
+from gpu_support import D, module_defaults, ops, switches
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults(dual=1)
 
 IDS = [c.name for c in C.CASES]
-
-
-def D(t):
-    return torch.as_tensor(t, dtype=torch.float64).cuda()
-
-
-@pytest.fixture(autouse=True)
-def _switches_back():
-    from fthmc_amd import ops
-    yield
-    ops.set_dual_path(1)
 
 
 def _arch(case):
@@ -65,12 +56,10 @@ def _fused(case):
 
 
 def _weights(inp, tanh=False):
-    from fthmc_amd import ops
     return ops.pack_weights(inp.flow, device='cuda', final_tanh=tanh)
 
 
 def _vjps(inp, w, beta=C.BETA, glogdet=True):
-    from fthmc_amd import ops
     nl = len(inp.flow)
     x = D(inp.x)
     hx, hw = ops.ft_force_vjp(x, w, nl, beta, D(inp.g), inp.act.replace('+tanh', ''))
@@ -79,7 +68,6 @@ def _vjps(inp, w, beta=C.BETA, glogdet=True):
 
 
 def _force(inp, w, beta=C.BETA):
-    from fthmc_amd import ops
     r = ops.train_force_grad(D(inp.x), w, len(inp.flow), beta, inp.act.replace('+tanh', ''))
     return {'F': r['F'], 'force_sq': r['force_sq'], 'gw_force': r['gw']}
 
@@ -95,27 +83,26 @@ def test_force_and_action_vjps_per_tensor(case):
 @pytest.mark.parametrize('case', C.CASES, ids=IDS)
 def test_train_force_grad_on_every_path_per_tensor(case):
     """every path that serves the shape against the oracle; fused against plain; plain against 2 ft_force_vjp(g = F)"""
-    from fthmc_amd import ops
     inp, ref = C.inputs(case), C.oracle(case)
     w = _weights(inp, case.tanh)
     arch, act, nl = _arch(case), case.act, case.nl
-    ops.set_dual_path(0)
-    assert ops.train_force_path(case.B, case.L, arch) == 0
-    plain = _force(inp, w)
-    errs = C.compare(plain, ref, inp.flow)
-    print(f'{case.name} path 0: worst %.1e (%s)' % C.worst(errs)[::-1])
-    C.hold(errs, C.BOUND, f'{case.name} path 0')
-    vjp = 2 * ops.ft_force_vjp(D(inp.x), w, nl, C.BETA, plain['F'], act, need_gx=False)[1]
+    with switches(dual=0):
+        assert ops.train_force_path(case.B, case.L, arch) == 0
+        plain = _force(inp, w)
+        errs = C.compare(plain, ref, inp.flow)
+        print(f'{case.name} path 0: worst %.1e (%s)' % C.worst(errs)[::-1])
+        C.hold(errs, C.BOUND, f'{case.name} path 0')
+        vjp = 2 * ops.ft_force_vjp(D(inp.x), w, nl, C.BETA, plain['F'], act, need_gx=False)[1]
     assert torch.equal(plain['gw_force'], vjp)                # the plain sweep IS the force VJP's, seeded with F, times two
     plain_rows = C.split(plain['gw_force'], inp.flow)
     wsb = {}
     for path in (2, 3, 1):
-        ops.set_dual_path(path)
-        assert ops.train_force_path(case.B, case.L, arch) == int(_fused(case)), (case.name, path)
-        if not _fused(case):
-            continue
-        wsb[path] = ops.train_force_ws_bytes(case.B, case.L, nl)
-        on = _force(inp, w)
+        with switches(dual=path):
+            assert ops.train_force_path(case.B, case.L, arch) == int(_fused(case)), (case.name, path)
+            if not _fused(case):
+                continue
+            wsb[path] = ops.train_force_ws_bytes(case.B, case.L, nl)
+            on = _force(inp, w)
         assert torch.equal(on['F'], plain['F']) and torch.equal(on['force_sq'], plain['force_sq'])
         errs = C.compare(on, ref, inp.flow)
         vs_plain = C.per_tensor(C.split(on['gw_force'], inp.flow), plain_rows, 'fused vs plain')
@@ -137,16 +124,14 @@ def test_cases_reach_every_path():
 def test_entry_points_match_the_steep_reference_fixture():
     """tests/golden/second_order_steep_L8.npz: the reference's own autograd at scale 3 on 8 layers with the pinned links; the
     fixture's action VJP has gS alone"""
-    from fthmc_amd import ops
-    from test_second_order_hard import steep_fixture
-    g, inp, ref = steep_fixture()
+    g, inp, ref = C.steep_fixture()
     beta = float(g['beta'])
     w = _weights(inp)
     errs = C.compare(_vjps(inp, w, beta, glogdet=False), ref, inp.flow)
     for path in (0, 2, 1):
-        ops.set_dual_path(path)
-        assert ops.train_force_path(2, 8) == int(path != 0)
-        e = C.compare(_force(inp, w, beta), ref, inp.flow)
+        with switches(dual=path):
+            assert ops.train_force_path(2, 8) == int(path != 0)
+            e = C.compare(_force(inp, w, beta), ref, inp.flow)
         errs.update({f'{k} (path {path})': v for k, v in e.items()})
     print('steep fixture: worst %.1e (%s)' % C.worst(errs)[::-1])
     C.hold(errs, C.BOUND, 'steep fixture')

@@ -35,33 +35,15 @@ import torch
 import steep_fixture as SF
 from steep_fixture import TOL, ULP_PI
 
+from gpu_support import D, H, module_defaults, ops, switches
+
 pytestmark = pytest.mark.gpu
-
-ops = None
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    yield
-    ops.set_variant(1)
-    ops.set_small_path(True)
+_defaults = module_defaults()
 
 
 @pytest.fixture(scope='module')
 def g():
     return SF.load()
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
-
-
-def H(t):
-    return t.detach().cpu().numpy()
 
 
 def W(ws):
@@ -110,16 +92,14 @@ def check_plaq_level(wst, w, P, act, e, delta, where, arch=None, tol=TOL, sanity
 def test_mfma_plaquette_level(g, L):
     """k_flow_fwd<.., REV>: exact two-by-two tiles at L = 32 (all eight (mu, off)), ragged tiles at L = 20, and L = 16 on the tiled
     kernels (the fused small-lattice path switched off)."""
-    ops.set_variant(1)
-    ops.set_small_path(L != 16)
     wst = Worst()
     try:
-        for r, ci, si, mu, off in SF.plaq_combos(g, L):
-            e = {k: g[f'{k}_L{L}'][r] for k in ('fP', 'fp', 'logJ', 'labs', 'sens')}
-            check_plaq_level(wst, W(SF.case_weights(g, ci)), g[f'P_L{L}'][si], SF.active_mask(L, mu, off), e, g['delta_ref'][si],
-                             (L, ci, mu, off), sanity=(si == 3))
+        with switches(variant=1, small=(L != 16)):
+            for r, ci, si, mu, off in SF.plaq_combos(g, L):
+                e = {k: g[f'{k}_L{L}'][r] for k in ('fP', 'fp', 'logJ', 'labs', 'sens')}
+                check_plaq_level(wst, W(SF.case_weights(g, ci)), g[f'P_L{L}'][si], SF.active_mask(L, mu, off), e, g['delta_ref'][si],
+                                 (L, ci, mu, off), sanity=(si == 3))
     finally:
-        ops.set_small_path(True)
         wst.show(f'mfma L={L}')
 
 
@@ -167,15 +147,12 @@ def check_link_level(wst, g, ci, tol=TOL):
 def test_link_level(g, variant):
     """k_flow_layer<MODE 0 / 3> (the VALU variant has no plaquette-level entry) and the MFMA kernels' link output, on link fields
     whose plaquettes are exact sums (links are multiples of 2^-40) with |P| < pi."""
-    ops.set_variant(variant)
-    ops.set_small_path(False)
     wst = Worst()
     try:
-        for ci in range(len(g['case_s0'])):
-            check_link_level(wst, g, ci)
+        with switches(variant=variant, small=False):
+            for ci in range(len(g['case_s0'])):
+                check_link_level(wst, g, ci)
     finally:
-        ops.set_variant(1)
-        ops.set_small_path(True)
         wst.show('link level, variant %d' % variant)
 
 
@@ -185,20 +162,18 @@ def test_loop_ends_without_a_tolerance(g):
     site.  Once per caller, at L = 16, on the steepest regular case (s0 = 10, (+,+): at the planted pi - d the target lies 2e-13
     below pi and the start of the iteration itself saturates the atan)."""
     wst = Worst()
-    ops.set_small_path(False)
     try:
-        r, ci, si, mu, off = [c for c in SF.plaq_combos(g, 16)
-                              if g['case_s0'][c[1]] == 10.0 and tuple(g['case_sign'][c[1]]) == (1, 1)][0]
-        e = {k: g[f'{k}_L16'][r] for k in ('fP', 'fp', 'logJ', 'labs', 'sens')}
-        check_plaq_level(wst, W(SF.case_weights(g, ci)), g['P_L16'][si], SF.active_mask(16, mu, off), e, g['delta_ref'][si],
-                         ('tol0', ci, mu, off), tol=0.0)
-        K, si, mu, off = (int(v) for v in g['gen3_meta'])
-        e = {k: g[f'gen3_{k}'] for k in ('fP', 'fp', 'logJ', 'labs', 'sens')}
-        check_plaq_level(wst, W([g[f'gen3_w{pi}'] for pi in range(4)]), g['P_L16'][si], SF.active_mask(16, mu, off), e,
-                         g['delta_ref'][si], ('tol0 gen', 3, mu, off), tol=0.0)
-        ops.set_variant(0)
-        check_link_level(wst, g, 6, tol=0.0)                    # s0 = 10, (+,+), L = 16
+        with switches(small=False):
+            r, ci, si, mu, off = [c for c in SF.plaq_combos(g, 16)
+                                  if g['case_s0'][c[1]] == 10.0 and tuple(g['case_sign'][c[1]]) == (1, 1)][0]
+            e = {k: g[f'{k}_L16'][r] for k in ('fP', 'fp', 'logJ', 'labs', 'sens')}
+            check_plaq_level(wst, W(SF.case_weights(g, ci)), g['P_L16'][si], SF.active_mask(16, mu, off), e, g['delta_ref'][si],
+                             ('tol0', ci, mu, off), tol=0.0)
+            K, si, mu, off = (int(v) for v in g['gen3_meta'])
+            e = {k: g[f'gen3_{k}'] for k in ('fP', 'fp', 'logJ', 'labs', 'sens')}
+            check_plaq_level(wst, W([g[f'gen3_w{pi}'] for pi in range(4)]), g['P_L16'][si], SF.active_mask(16, mu, off), e,
+                             g['delta_ref'][si], ('tol0 gen', 3, mu, off), tol=0.0)
+            with switches(variant=0):
+                check_link_level(wst, g, 6, tol=0.0)                    # s0 = 10, (+,+), L = 16
     finally:
-        ops.set_variant(1)
-        ops.set_small_path(True)
         wst.show('tol = 0')

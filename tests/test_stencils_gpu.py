@@ -11,37 +11,19 @@ tests/test_stencils.py holds the float64 twin to the same bounds on the CPU and 
 is called directly: every output lands in a slice of a NaN-filled buffer whose guard words must keep their bits, every call runs
 twice and gives the same bits, every test leaves FTHMC_LEAP_ROWS, the variant and the small-path switch as it found them.  Each test
 prints its worst error as a fraction of the bound under the kernel family it belongs to (WORST <family> <value>)."""
-import contextlib
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT  # noqa: F401
-
 import stencil_cases as C
-from test_batch_kernels_gpu import Poisoned
+from gpu_support import D, Poisoned, lib, module_defaults, ops, switches
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
-ops = None
-lib = None
 CODES = C.IC.CODES
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, lib
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import _lib, ops as _ops
-    ops, lib = _ops, _lib.load()
-    before = (ops.get_variant(), ops.get_small_path())
-    ops.set_variant(1)
-    ops.set_small_path(True)
-    yield
-    ops.set_variant(before[0])
-    ops.set_small_path(before[1])
 
 
 @pytest.fixture(autouse=True)
@@ -49,36 +31,6 @@ def _switches_left_as_found():
     before = (os.environ.get('FTHMC_LEAP_ROWS'), ops.get_variant(), ops.get_small_path())
     yield
     assert (os.environ.get('FTHMC_LEAP_ROWS'), ops.get_variant(), ops.get_small_path()) == before
-
-
-@contextlib.contextmanager
-def leap_rows(on):
-    """FTHMC_LEAP_ROWS = on for the block (the library reads it with the variant); afterwards the row strips are on again, as the
-    library starts, and the variable is what it was"""
-    old = os.environ.get('FTHMC_LEAP_ROWS')
-    os.environ['FTHMC_LEAP_ROWS'] = '1' if on else '0'
-    try:
-        ops.set_variant(ops.get_variant())
-        yield
-    finally:
-        os.environ['FTHMC_LEAP_ROWS'] = '1' if old is None else old
-        ops.set_variant(ops.get_variant())
-        if old is None:
-            del os.environ['FTHMC_LEAP_ROWS']
-
-
-@contextlib.contextmanager
-def variant(v):
-    old = ops.get_variant()
-    try:
-        ops.set_variant(v)
-        yield
-    finally:
-        ops.set_variant(old)
-
-
-def D(a):
-    return torch.from_numpy(np.array(a, dtype=np.float64)).cuda()
 
 
 def note(family, value):
@@ -156,7 +108,7 @@ def both_settings(L, run):
     -> [(setting, result), ...]"""
     out = [(1, run())]
     if L % 64 == 0:
-        with leap_rows(False):
+        with switches(leap_rows=False):
             out.append((0, run()))
     return out
 
@@ -252,7 +204,7 @@ def test_one_launch_trajectory(L, name):
 def test_multi_launch_trajectory(L, name):
     """the step kernels, k_wrap and k_metropolis; L = 8, 36 with the VALU variant, which has no one-launch kernel"""
     fam = 'tile' if name == 'leapfrog' else 'grid-stride'
-    with variant(0 if L <= 64 else 1):
+    with switches(variant=0 if L <= 64 else 1):
         for n in C.TRAJ_NSTEP:
             check_traj(case_of(C.TRAJ_CASES, L, name), n, fam)
 

@@ -16,30 +16,12 @@ from conftest import ROOT  # noqa: F401
 import integrator_cases as IC
 import tempering_cases as TC
 
+from gpu_support import D, H, R, module_defaults, ops, switches
+
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
-ops = None
-R = None
 KEYS = ('x_new', 'dH', 'acc', 'H0', 'H1', 'plaq', 'Q')
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, R
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    from oracle import ref_cpu as _R
-    ops, R = _ops, _R
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def D(a, dtype=torch.float64):
-    return torch.as_tensor(np.asarray(a), dtype=dtype).cuda()
 
 
 def flow_of(seed, nl, arch=None):
@@ -47,19 +29,6 @@ def flow_of(seed, nl, arch=None):
     if arch is None:
         return R.default_flow(nl, gen)
     return R.default_flow(nl, gen, hidden=arch[0], k=arch[1], n_mix=arch[2])
-
-
-class paths:
-    """the two process-wide switches of a case, restored behind it"""
-
-    def __init__(self, variant, small):
-        self.v, self.s = variant, small
-
-    def __enter__(self):
-        ops.set_variant(self.v); ops.set_small_path(self.s)
-
-    def __exit__(self, *a):
-        ops.set_variant(1); ops.set_small_path(True)
 
 
 def ft_rows():
@@ -87,7 +56,7 @@ def scalar_ft(case, name, nstep, beta):
 def _scalar_ft(case, name, nstep, beta):
     cid, L, B, nl, arch, variant, small = case
     flow, x, v, u = ft_inputs(cid, L, B, nl, arch)
-    with paths(variant, small):
+    with switches(variant=variant, small=small):
         w = ops.pack_weights(flow, device='cuda') if nl else None
         r = ops.ft_trajectory(x.cuda(), v.cuda(), u.cuda(), w, nl, beta, TC.TAU / nstep, nstep, mode='md', integrator=name)
         torch.cuda.synchronize()
@@ -97,7 +66,7 @@ def _scalar_ft(case, name, nstep, beta):
 def pb_ft(case, name, nstep, beta_b, state_in=None):
     cid, L, B, nl, arch, variant, small = case
     flow, x, v, u = ft_inputs(cid, L, B, nl, arch)
-    with paths(variant, small):
+    with switches(variant=variant, small=small):
         w = ops.pack_weights(flow, device='cuda') if nl else None
         r = ops.ft_trajectory(x.cuda(), v.cuda(), u.cuda(), w, nl, D(beta_b), TC.TAU / nstep, nstep, mode='md', integrator=name,
                               state_in=state_in)
@@ -216,7 +185,7 @@ def test_chained_call_after_a_permutation_of_beta_b_equals_the_stateless_call(ca
     perm = np.roll(beta_b, 1)
     assert not np.array_equal(perm, beta_b)
     nstep, dt = 3, TC.TAU / 3
-    with paths(variant, small):
+    with switches(variant=variant, small=small):
         w = ops.pack_weights(flow, device='cuda') if nl else None
         u1 = u.clone(); u1[::2] = 0.0                               # every other chain accepts whatever its dH: both kinds of state are carried
         r1 = ops.ft_trajectory(x.cuda(), v.cuda(), u1.cuda(), w, nl, D(beta_b), dt, nstep)

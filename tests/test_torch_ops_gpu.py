@@ -1,20 +1,18 @@
 """GPU tests of the `torch.ops.fthmc_hip.*` operator boundary (fthmc_amd/torch_ops.py) against the
 reference's golden vectors: values, autograd through the registered formulas, schema checks."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
+import gpu_support
 from conftest import golden_flow, load_golden
+from gpu_support import D, module_defaults
 
 pytestmark = pytest.mark.gpu
-
-
-def D(a):
-    return torch.from_numpy(np.asarray(a, dtype=np.float64).copy()).cuda()
-
-
-def close(a, b, rtol=1e-9, atol=1e-10):
-    np.testing.assert_allclose(a.detach().cpu().numpy() if torch.is_tensor(a) else a, np.asarray(b), rtol=rtol, atol=atol)
+_defaults = module_defaults()
+close = functools.partial(gpu_support.close, rtol=1e-9, atol=1e-10)
 
 
 def packed(g):

@@ -302,5 +302,5 @@ def test_the_small_path_switched_off_does_not_walk_at_config_2():
 
 
 def test_fused_cases_of_the_earlier_suite_walk_two_items_everywhere():
-    """tests/test_round6_gpu.py (20, 64, 2): 320 items on 160 workgroups, every one walks exactly two -- no ragged round"""
+    """tests/test_training_gpu.py (20, 64, 2): 320 items on 160 workgroups, every one walks exactly two -- no ragged round"""
     assert M.fused_launch(20, 64) == (320, 2, 20, 160) and M.fused_histogram(20, 64) == {2: 160}

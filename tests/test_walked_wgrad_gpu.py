@@ -10,7 +10,7 @@ links, random upstream gradients, random d/dlogJ per chain), so an item dropped,
 the result; the whole batch is compared, nothing is sampled.
 
 Bounds (none of them taken from the kernels): weight gradients max|gpu - oracle| / max(1, max|oracle|) <= 1e-10 per parameter
-tensor -- the atol factor of tests/test_round3_gpu.py and test_round6_gpu.py; the oracle's own noise under a permutation of the
+tensor -- the atol factor of tests/test_layer_calls_gpu.py and test_training_gpu.py; the oracle's own noise under a permutation of the
 chains is 5.4e-15 of that scale at most on these shapes.  gx: rtol 1e-9, atol 1e-10 max|gx|.  logq, logp: rtol 1e-11.  The
 summation order is fixed: a second call returns the same bits.
 
@@ -46,26 +46,12 @@ import pytest
 import torch
 
 import walk_model as M
-from conftest import ROOT  # noqa: F401
+from gpu_support import R, module_defaults, ops, switches
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
 GW_BOUND = 1e-10
-ops = None
-R = None
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, R
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    from oracle import ref_cpu as _R
-    ops, R = _ops, _R
-    variant, small = ops.get_variant(), ops.get_small_path()
-    ops.set_variant(1); ops.set_small_path(True)
-    yield
-    ops.set_variant(variant); ops.set_small_path(small)
 
 
 def field(B, L, gen):
@@ -139,7 +125,7 @@ def test_walked_layer_weight_gradient_vs_oracle(L, B, mu, off):
 def test_walked_layer_from_a_callers_stash_is_bit_equal():
     """fthmc_flow_layer_fwd_stash + fthmc_flow_layer_bwd_stash(need_gw): the same forward launch and the same two backward
     kernels on the caller's stash as fthmc_flow_layer_bwd(need_gw) runs on the workspace's -- the same bits (csrc/api.hip
-    layer_bwd_impl; tests/test_round3_gpu.py has the ragged L = 24, this is an exact-tile shape at a walk of two)"""
+    layer_bwd_impl; tests/test_layer_calls_gpu.py has the ragged L = 24, this is an exact-tile shape at a walk of two)"""
     L, B, mu, off = 32, 257, 1, 2
     assert_layer_walks(L, B)
     wt, x, c, dlog = layer_inputs(L, B)
@@ -190,11 +176,8 @@ def test_walked_training_gradient_at_config_2_vs_oracle_and_vs_the_unwalked_path
     L, B, nl = 16, 512, 8
     r, xd, w, beta, grads = run_train_case(L, B, nl)
     assert M.wgrad_histogram(B, L, 1) == {1: B}
-    try:
-        ops.set_small_path(False)
+    with switches(small=False):
         plain = ops.train_grad(xd, w, nl, beta)
-    finally:
-        ops.set_small_path(True)
     ref = [[g.cpu() for g in row] for row in ops.unpack_weight_grads(plain['gw'], nl)]
     ew = gw_metric(ops.unpack_weight_grads(r['gw'], nl), ref)
     eo = gw_metric(ref, grads)

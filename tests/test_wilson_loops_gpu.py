@@ -17,29 +17,13 @@ from conftest import ROOT  # noqa: F401
 
 import wilson_loop_cases as WC
 
-pytestmark = pytest.mark.gpu
+from gpu_support import D, H, module_defaults, ops
 
-ops = None
+pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
+
 # the shapes of the issue, the last lattice whose row lives in LDS and the first whose row lives in global scratch
 SHAPES = WC.SHAPES + ((1, 1024, 1, 2), (1, 1028, 2, 3))
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy()
-
-
-def D(a):
-    return torch.as_tensor(np.asarray(a, dtype=np.float64)).cuda()
 
 
 @functools.lru_cache(maxsize=None)

@@ -32,8 +32,8 @@ state the rounded one.  Nothing else: no entry point is other than bit-reproduci
 writes outside the queried size, none keeps anything in the head but the expansion, and no listed refusal had enqueued anything.
 
 Observed on an MI355X (5142 tests, 47 s; the slowest 0.25 s).  (case, setting) pairs per entry point, each run by (a) and by (b),
-2468 in all -- settings: default; `tiled` = small path off (L = 8, 12, 16 with layers); `valu` = fthmc_set_variant(0); dual0 /
-dual2 / dual3 = the other fthmc_set_dual_path settings (train_force_grad only):
+2468 in all -- settings: default; `tiled` = small path off (L = 8, 12, 16 with layers); `valu` = variant 0; dual0 /
+dual2 / dual3 = the other settings of the dual-path switch (train_force_grad only):
   flow_layer_fwd                    32   flow_layer_fwd_inplace            32   flow_layer_rev                    32
   flow_layer_bwd                    32   flow_layer_bwd_gw                 34   flow_layer_stash_pair             17
   plaq_coupling_fwd                 17   plaq_coupling_rev                 17   plaq_coupling_bwd                 17
@@ -74,11 +74,11 @@ import torch
 
 import first_order_cases as FC
 import workspace_cases as W
-from conftest import ROOT  # noqa: F401
+from gpu_support import module_defaults, ops, switches
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults(dual=1)                             # W.SETTING['default']
 
-ops = None
 TABLE = W.table()
 IDS = W.table_ids(TABLE)
 FIRST_ORDER_SETTINGS = [W.SETTING[n] for n in ('default', 'tiled', 'valu')]
@@ -87,14 +87,8 @@ REFUSALS = {'short': WS, 'null': WS, 'Lmod4': ARG, 'mu2': ARG, 'off4': ARG, 'nul
 
 
 @pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    W.apply_setting(ops, W.SETTING['default'])
+def _workspaces_released():
     yield
-    W.apply_setting(ops, W.SETTING['default'])
     ops.release_workspaces()
 
 
@@ -104,8 +98,14 @@ def route(monkeypatch):
     yield r
     torch.cuda.synchronize()
     monkeypatch.undo()
-    W.apply_setting(ops, W.SETTING['default'])
     ops.release_workspaces()
+
+
+@pytest.fixture()
+def under(setting):
+    """the switches of the test's `setting` parameter, for the test"""
+    with switches(variant=setting.variant, small=setting.small, dual=setting.dual):
+        yield
 
 
 def run(route, row, case, wkey=None, I=None, **mode):
@@ -128,8 +128,7 @@ def say(broken):
 
 # ---------------------------------------------------------------- (a), (c)
 @pytest.mark.parametrize('row,case,setting', TABLE, ids=IDS)
-def test_a_exact_scratch_suffices_and_nothing_else_is_written(route, row, case, setting):
-    W.apply_setting(ops, setting)
+def test_a_exact_scratch_suffices_and_nothing_else_is_written(route, under, row, case, setting):
     label = f'{row.name} at {case.name} under {setting.name}'
     out, I, guards, host = run(route, row, case, fill='nan')
     assert route.handed, f'{label}: no workspace was asked for'
@@ -155,8 +154,7 @@ def test_a_exact_scratch_suffices_and_nothing_else_is_written(route, row, case, 
 
 # ---------------------------------------------------------------- (b)
 @pytest.mark.parametrize('row,case,setting', TABLE, ids=IDS)
-def test_b_no_read_of_unwritten_scratch(route, row, case, setting):
-    W.apply_setting(ops, setting)
+def test_b_no_read_of_unwritten_scratch(route, under, row, case, setting):
     label = f'{row.name} at {case.name} under {setting.name}'
     other = W.donor(row, case, setting)
     first = run(route, row, case, fill='nan')[0]
@@ -177,8 +175,7 @@ def test_b_no_read_of_unwritten_scratch(route, row, case, setting):
 
 # ---------------------------------------------------------------- (d)
 @pytest.mark.parametrize('setting', FIRST_ORDER_SETTINGS, ids=[s.name for s in FIRST_ORDER_SETTINGS])
-def test_d_the_head_is_only_ever_the_weight_expansion(route, setting):
-    W.apply_setting(ops, setting)
+def test_d_the_head_is_only_ever_the_weight_expansion(route, under, setting):
     cases = [c for c in W.CASES if c.arch is None and c.nl <= 8 and c.only is None]
     rows = [r for r in W.ROWS if r.versioned]
     head = route.head_bytes // 8
@@ -211,8 +208,7 @@ def test_d_the_head_is_only_ever_the_weight_expansion(route, setting):
 
 # ---------------------------------------------------------------- (e)
 @pytest.mark.parametrize('setting', FIRST_ORDER_SETTINGS, ids=[s.name for s in FIRST_ORDER_SETTINGS])
-def test_e_the_deep_flow_against_the_oracle(setting):
-    W.apply_setting(ops, setting)
+def test_e_the_deep_flow_against_the_oracle(under, setting):
     ops.release_workspaces()
     try:
         c, inp, ref = W.DEEP, W.deep_inputs(), W.deep_oracle()
@@ -239,7 +235,6 @@ def test_e_the_deep_flow_against_the_oracle(setting):
             a, b = f(W.WKEY), f(W.WKEY)
             assert all(W.same_bits(p, q) and W.same_bits(p, r) for p, q, r in zip(plain[name], a, b)), name
     finally:
-        W.apply_setting(ops, W.SETTING['default'])
         ops.release_workspaces()
 
 

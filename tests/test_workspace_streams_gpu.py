@@ -1,6 +1,6 @@
 """GPU tests of the host plumbing of fthmc_amd/ops.py (the CPU half: tests/test_scratch_cache.py): a captured graph keeps
 replaying into the scratch of the families beside the flow workspace ('loops', 'instanton', 'train_force') after a larger call
-replaced it -- tests/test_round2_gpu.py::test_workspace_survives_growth_after_capture holds the flow family to the same --, and
+replaced it -- tests/test_capture_gpu.py::test_workspace_survives_growth_after_capture holds the flow family to the same --, and
 train_grad over explicit chain-group sizes."""
 import math
 
@@ -8,23 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-from fthmc_amd.graph_loop import capture
+from gpu_support import R, capture, module_defaults, ops
 
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
-ops = None
-R = None
 BETA = 2.0
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops, R
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    from oracle import ref_cpu as _R
-    ops, R = _ops, _R
-    ops.set_variant(1)
 
 
 def links(B, L, gen):
@@ -110,7 +99,7 @@ def test_family_scratch_survives_growth_after_capture(family):
 def test_train_grad_takes_explicit_group_sizes():
     """groups=[1, 2] of three chains: x, logq, logp are per chain and keep their bits; gw adds the groups' partial gradients
     (1/3 g_0 + 2/3 g_1) where one group adds the chains, so it agrees to rounding: 1e-12 of max |gw|; and with the oracle within
-    what tests/test_round3_gpu.py asks of a training gradient at this size."""
+    what tests/test_layer_calls_gpu.py asks of a training gradient at this size."""
     gen = torch.Generator().manual_seed(77)
     B, L, nl = 3, 8, 2
     flow = R.default_flow(nl, gen)

@@ -14,30 +14,12 @@ from conftest import ROOT  # noqa: F401
 
 import anneal_cases as AC
 
+from gpu_support import D, H, capture, module_defaults, ops, switches
+
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
-ops = None
 BETAS, N, B = AC.BETAS, AC.N_STEP, AC.B
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    ops.set_variant(1)
-    ops.set_small_path(True)
-    yield
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy()
-
-
-def D(a):
-    return torch.from_numpy(np.array(a, dtype=np.float64)).cuda()
 
 
 def S(seeds):
@@ -120,11 +102,8 @@ def test_both_paths_give_the_same_bits_in_every_output(L, counts):
     for k in ('x', 'work', 'trace'):
         assert torch.equal(a[k], b[k]), f'{k}: the one-launch kernel and the sequenced path differ'
         assert torch.equal(a[k], c[k]), k
-    ops.set_small_path(False)
-    try:
+    with switches(small=False):
         d = run(r, 0)
-    finally:
-        ops.set_small_path(True)
     assert all(torch.equal(a[k], d[k]) for k in ('x', 'work', 'trace'))
 
 
@@ -161,7 +140,6 @@ def test_cut_batch_aliases_and_zero_steps(L, counts):
 
 @pytest.mark.parametrize('path', [1, 2])
 def test_a_captured_replay_follows_the_schedule_the_tensor_holds(path):
-    from fthmc_amd.graph_loop import capture
     r = reference(8, (1, 2, 1))
     other = torch.tensor([3.0, 0.25, 1.0, 1.0], dtype=torch.float64, device='cuda')
     want_a, want_b = run(r, path), run(r, path, betas=other)

@@ -9,9 +9,6 @@ integrators, the zero / quadratic / rough tables of meta_cases.table, field ampl
 
 Bounds: the figures tests/test_hip_parity.py holds the unbiased flowed force, action and trajectories to (stated at each check).
 Accept flags are compared on every chain: the twin leaves none out on these inputs (tests/test_ft_meta.py)."""
-import contextlib
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -21,28 +18,12 @@ from conftest import ROOT  # noqa: F401
 import ft_meta_cases as FC
 import meta_cases as MC
 
+from gpu_support import D, H, angle_close, module_defaults, ops, switches
+
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
-ops = None
 Q2_EXACT_L16_B6 = 1.1947014482
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(H(a).astype(np.float64))).cuda()
 
 
 def bits(a, b):
@@ -50,22 +31,9 @@ def bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
-def angle_close(a, b, atol):
-    d = H(a) - H(b)
-    d = d - 2 * math.pi * np.rint(d / (2 * math.pi))
-    assert np.abs(d).max() <= atol, np.abs(d).max()
-
-
-@contextlib.contextmanager
 def setting(path):
     """the library's switches for a path of the case table: 'off' the small path off, 'valu' the VALU variant"""
-    ops.set_small_path(path != 'off')
-    ops.set_variant(0 if path == 'valu' else 1)
-    try:
-        yield
-    finally:
-        ops.set_small_path(True)
-        ops.set_variant(1)
+    return switches(variant=0 if path == 'valu' else 1, small=path != 'off')
 
 
 def dev(c):

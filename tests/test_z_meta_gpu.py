@@ -12,9 +12,6 @@ x_new atol 1e-9, dH rtol 1e-8 / atol 1e-9, H1 rtol 1e-8).  The float64 twin agai
 (tests/test_meta.py, measured): force 2.4e-15 of its scale, S_b 5.2e-14 relative, x_new 2.1e-15, H1 1.4e-14 relative, dH 5.7e-7 of
 its bound -- 8 x each is far inside the figures above, so no table widens a bound.  Accept flags are compared on every chain: the
 twin leaves none out on these inputs (min |t - round(t)| >= 1e-9 at every lookup, |u - exp(-dH)| >= 1e-6 exp(-dH))."""
-import functools
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -23,33 +20,19 @@ from conftest import ROOT  # noqa: F401
 
 import meta_cases as MC
 
+import gpu_support
+from gpu_support import D, H, module_defaults, ops, switches
+
 pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
 
 LD = np.longdouble
-ops = None
 Q2_EXACT_L16_B6 = 1.1947014482
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(MC.f64(a))).cuda()
-
-
 def close(a, b, rtol=1e-10, atol=1e-10):
-    np.testing.assert_allclose(H(a), MC.f64(b), rtol=rtol, atol=atol)
+    """against the twin's longdouble figures, rounded to fp64 first"""
+    gpu_support.close(a, MC.f64(b), rtol=rtol, atol=atol)
 
 
 def bits(a, b):
@@ -208,12 +191,9 @@ def test_scratch_is_asked_for_only_on_the_sequenced_path():
     ops.meta_trajectory(xa, v, u, beta, MC.DT, nstep, V, tab.qmax, tab.wall, integrator=integ, path=0, out={'x_new': xa})
     assert len(meta_keys()) == 1                                         # path 0 with aliased output: the sequenced path
     ops.release_workspaces()
-    try:                                                                 # ... and with the VALU variant set, as fthmc_hmc_trajectory_int chooses
-        ops.set_variant(0)
+    with switches(variant=0):                                            # ... and with the VALU variant set, as fthmc_hmc_trajectory_int chooses
         rv = run(c, 0)
         assert len(meta_keys()) == 1 and all(bits(rv[k], run(c, 2)[k]) for k in rv)
-    finally:
-        ops.set_variant(1)
     assert all(bits(r0[k], r1[k]) for k in r0)
     # more chains than the sequenced path's launch shapes serve: refused, nothing launched
     from fthmc_amd._lib import FthmcError

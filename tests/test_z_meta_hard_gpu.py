@@ -58,29 +58,13 @@ import meta_cases as MC
 import meta_hard_cases as MH
 import stencil_cases as SC
 
-pytestmark = pytest.mark.gpu
+from gpu_support import D, H, module_defaults, ops
 
-ops = None
+pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
+
 BETA, DT = MH.BETA, MH.DT
 TRAJ_KEYS = ('x_new', 'dH', 'acc', 'H0', 'H1', 'qm', 'vbias')
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(MH.f64(a))).cuda()
 
 
 def bits(a, b):

@@ -16,7 +16,6 @@ What is asserted is what those files assert, with their bounds: with a zero tabl
 call; with the rough table of meta_cases.table (G = 2; that table has nb = 41) the numpy / torch twin within test_z_meta_gpu.py's
 and test_z_ft_meta_gpu.py's bounds; state[k] bit-equal to the plaq / Q / qm vectors handed out beside it; a carried state gives the
 bits of the stateless call."""
-import contextlib
 import math
 
 import numpy as np
@@ -29,51 +28,20 @@ import ft_meta_cases as FC
 import meta_cases as MC
 import tempering_cases as TC
 
-pytestmark = pytest.mark.gpu
+from gpu_support import D, H, angle_close, module_defaults, ops, switches
 
-ops = None
+pytestmark = pytest.mark.gpu
+_defaults = module_defaults()
+
 B, G, NB0 = 4, 2, 11
 INTEGS = ('leapfrog', 'force_gradient')
 KEYS = ('x_new', 'dH', 'acc', 'H0', 'H1', 'plaq', 'Q')
 ALL = KEYS + ('qm', 'vbias', 'state')
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _mods():
-    global ops
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    from fthmc_amd import ops as _ops
-    ops = _ops
-    ops.set_variant(1)
-    ops.set_small_path(True)
-
-
-def H(t):
-    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-
-
-def D(a):
-    return torch.from_numpy(np.ascontiguousarray(MC.f64(H(a)))).cuda()
-
-
 def bits(a, b):
     a, b = np.ascontiguousarray(H(a)), np.ascontiguousarray(H(b))
     return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
-
-
-def angle_close(a, b, atol):
-    d = H(a) - H(b)
-    d = d - 2 * math.pi * np.rint(d / (2 * math.pi))
-    assert np.abs(d).max() <= atol, np.abs(d).max()
-
-
-@contextlib.contextmanager
-def small_path_off():
-    ops.set_small_path(False)
-    try:
-        yield
-    finally:
-        ops.set_small_path(True)
 
 
 def zero_table():
@@ -170,7 +138,7 @@ def flowed_inputs(c, table, carried):
 def test_flowed_zero_table_gives_the_bits_of_ft_trajectory(c, carried):
     path, _, L, nl, amp, beta, nstep, integ, tk, _, sc = c
     Z = zero_table()
-    with small_path_off():
+    with switches(small=False):
         x, v, u, w, flow, st = flowed_inputs(c, Z, carried)
         r = ops.ft_meta_trajectory(x, v, u, w, nl, beta, FC.DT, nstep, *Z, integrator=integ, state_in=st)
         p = ops.ft_trajectory(x, v, u, w, nl, beta, FC.DT, nstep, integrator=integ, state_in=None if st is None else st[:3].contiguous())
@@ -189,7 +157,7 @@ def test_flowed_rough_table_against_the_twin(c, carried):
     tab = FC.inputs(c)[3]
     assert tab.G == G
     T = (D(tab.V), tab.qmax, tab.wall)
-    with small_path_off():
+    with switches(small=False):
         x, v, u, w, flow, st = flowed_inputs(c, T, carried)
         r = ops.ft_meta_trajectory(x, v, u, w, nl, beta, FC.DT, nstep, *T, integrator=integ, state_in=st)
         if carried:
