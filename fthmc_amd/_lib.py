@@ -137,7 +137,15 @@ SIGNATURES['fthmc_ft_meta_trajectory_v'] = ([_D, _D, _D, _D, _A, c_int, c_int, c
                                             [_D] * 11 + [_P, c_size_t, _P, c_uint64])
 SIGNATURES['fthmc_ft_meta_force_v'] = [_D, _D, _A, c_int, c_int, c_int, c_int, c_double] + _MT + [_D, _P, c_size_t, _P, c_uint64]
 SIGNATURES['fthmc_ft_meta_action_v'] = [_D, _D, _A, c_int, c_int, c_int, c_int, c_double] + _MT + [_D, _D, _D, _D, _P, c_size_t, _P, c_uint64]
-_RESTYPE = {'fthmc_ft_meta_ws_bytes': c_size_t, 'fthmc_meta_ws_bytes': c_size_t, 'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
+# boundary-condition tempering: the defect travels as (g_b, i0, j0, Ld)
+#   trajectory: x, v, u, B, L, beta, <defect>, dt, nstep, integrator, path, x_new, dH, acc, H0, H1, csum, dsum, q, ws, ws_bytes, stream
+_DF = [_D, c_int, c_int, c_int]
+SIGNATURES['fthmc_defect_ws_bytes'] = [c_int, c_int, c_int]
+SIGNATURES['fthmc_defect_trajectory'] = [_D, _D, _D, c_int, c_int, c_double] + _DF + [c_double, c_int, c_int, c_int] + [_D] * 8 + [_P, c_size_t, _P]
+SIGNATURES['fthmc_defect_force'] = [_D, c_int, c_int, c_double] + _DF + [_D, _P]                  # x, B, L, beta, <defect>, F, stream
+SIGNATURES['fthmc_defect_action'] = [_D, c_int, c_int, c_double] + _DF + [_D, _D, _D, _D, _P]     # ..., S, csum, dsum, Q, stream
+SIGNATURES['fthmc_defect_translate'] = [_D, c_int, c_int, _D, c_int, _D, _D, _P]                  # x, B, L, rung, top, shift, x_out, stream
+_RESTYPE = {'fthmc_defect_ws_bytes': c_size_t, 'fthmc_ft_meta_ws_bytes': c_size_t, 'fthmc_meta_ws_bytes': c_size_t, 'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None
 

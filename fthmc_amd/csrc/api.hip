@@ -350,6 +350,72 @@ int hmc_trajectory_call(const double* x, const double* v, const double* u, int B
     return FTHMC_OK;
 }
 
+// ---------------------------------------------------------------- boundary-condition tempering (defect.hip; no reference counterpart)
+// The workspace of fthmc_defect_trajectory's sequenced path: a first-order layout without layers and behind it the (C, Dsum, Q) rows
+// of the two ends and of the selected one, [3][B] each
+struct DWS { WS W; double *old, *neu, *sel; size_t total; };
+DWS defect_layout(Carver& c, int B, int L) {
+    DWS d{};
+    d.W = ws_layout(flow_arch_default(), c, B, L, 0);
+    if (d.W.total == 0) return d;
+    d.old = c.take((size_t)3 * B); d.neu = c.take((size_t)3 * B); d.sel = c.take((size_t)3 * B);
+    d.total = c.total();
+    return d;
+}
+// what every fthmc_defect_* call refuses about the defect and the couplings
+inline bool bad_defect(int L, double beta, const double* g_b, int i0, int j0, int Ld) {
+    return !g_b || !isfinite(beta) || Ld < 0 || Ld > L || i0 < 0 || i0 >= L || j0 < 0 || j0 >= L;
+}
+
+// Plain HMC with a defect: H0, MD, H1, Metropolis -- hmc_trajectory_call's per-chain-beta sequence (the schedule with zero layers: ft_md_ws)
+// with the weighted plane in every force, (beta - g_b) Dsum behind either energy and the (C, Dsum, Q) rows of the two ends through the
+// Metropolis kernel beside the field; a sibling of that sequence, which keeps its launches.  Any L, x_new may be x on the sequenced path.
+int defect_trajectory_call(const double* x, const double* v, const double* u, int B, int L, double beta, const double* g_b,
+                           const DefectLine& df, double dt, int nstep, int integrator, int path, double* x_new, double* dH, double* acc,
+                           double* H0, double* H1, double* csum_out, double* dsum_out, double* q_out, void* ws, size_t ws_bytes,
+                           void* stream) {
+    Sched sc;
+    FT_TRY(sched_of(integrator, dt, nstep, &sc));
+    Ctx C; FT_TRY(open_call(nullptr, stream, &C));
+    const hipStream_t s = C.s;
+    const bool one_launch = L <= HMC_RESIDENT_MAXL && C.mfma && x_new != x;       // as hmc_trajectory_call chooses
+    if (path == 1 || (path == 0 && one_launch))
+        return launch_defect_trajectory(x, v, u, B, L, beta, g_b, df, sc, x_new, dH, acc, H0, H1, csum_out, dsum_out, q_out, s);
+    if (B > META_SEQ_MAX_B) return FTHMC_ERR_UNSUPPORTED;
+    Carver c(ws, ws_bytes);
+    const DWS D = defect_layout(c, B, L);
+    FT_TRY(check_ws(D.total, ws, ws_bytes));
+    const WS& W = D.W;
+    double* S = W.scal + (size_t)SC_S * B; double* K = W.scal + (size_t)SC_K * B;
+    auto energy = [&](const double* xf, const double* vf, double* h, double* sums) {   // h = (-beta) C + K(vf) / 2 + (beta - g_b) Dsum
+        FT_TRY(launch_defect_sums(xf, B, L, beta, df, S, sums, s));
+        FT_TRY(launch_kinetic(vf, B, L, K, s));
+        FT_TRY(launch_lincomb(S, 1.0, K, 0.5, 0.0, h, B, s));
+        return launch_defect_energy(sums, B, beta, g_b, h, s);
+    };
+    double* h0 = H0 ? H0 : W.scal + (size_t)SC_H0 * B;
+    double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
+    FT_TRY(energy(x, v, h0, D.old));
+    FT_TRY(launch_axpy_copy(x, v, sc.b0, W.xa, W.va, W.n2, s));        // ft_md_ws' loop with the weighted plane as its force's seed
+    const double* xe = W.xa;
+    for (int it = 0; it < sc.n; ++it) {
+        const SchedStage st = sc.stage(it);
+        FT_TRY(launch_defect_gp(xe, B, L, beta, g_b, df, W.gp, s));
+        if (st.kind == FT_STAGE_SHIFT) {
+            FT_TRY(launch_shift_from_gp(W.gp, W.xa, W.xb, B, L, st.a, s));
+            xe = W.xb;
+        } else {
+            FT_TRY(launch_kick_from_gp(W.gp, W.va, W.xa, nullptr, B, L, st.a, st.b, s, it == sc.n - 1 ? W.xb : nullptr));
+            xe = W.xa;
+        }
+    }
+    FT_TRY(energy(W.xb, W.va, h1, D.neu));                            // W.xb: the regularized end point
+    // rows 1 and 2 of the selected end (Dsum, Q) leave through the Metropolis kernel itself, row 0 (C) by one copy
+    FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, D.old, D.neu, D.sel, 3, s, dsum_out, q_out));
+    if (csum_out && hipMemcpyAsync(csum_out, D.sel, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    return FTHMC_OK;
+}
+
 // ---------------------------------------------------------------- per-chain beta and replica exchange (no reference counterpart)
 // The beta-free triple (log det J, C = sum cos P, Q) of x into `trip` -- carried over (state_in) or evaluated -- and S_eff of it
 // at beta_b into `seff`: the general branch's eval_action + launch_lincomb with beta read per chain
@@ -1048,6 +1114,37 @@ int fthmc_meta_action(const double* x, int B, int L, double beta, const double* 
     MetaTab T;
     if (!x || bad_shape(B, L) || meta_tab(vtab, B, G, nb, qmax, wall, &T) != FTHMC_OK) return FTHMC_ERR_ARG;
     return launch_meta_action(x, B, L, beta, T, S, qm, vb, ft_stream(stream));
+}
+
+// Boundary-condition tempering (defect.hip): the argument checks; the choice of the path and the workspace of the sequenced
+// one are defect_trajectory_call's
+size_t fthmc_defect_ws_bytes(int B, int L, int path) {
+    if (bad_shape(B, L) || path < 0 || path > 2 || path == 1) return 0;             // the one-launch path needs none
+    if (B > META_SEQ_MAX_B) return 0;                                               // the sequenced path does not serve it
+    Carver c;
+    return defect_layout(c, B, L).total * sizeof(double);
+}
+int fthmc_defect_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta, const double* g_b, int i0, int j0,
+                            int Ld, double dt, int nstep, int integrator, int path, double* x_new, double* dH, double* acc, double* H0,
+                            double* H1, double* csum_out, double* dsum_out, double* q_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !v || !u || !x_new || bad_shape(B, L) || nstep < 1 || bad_defect(L, beta, g_b, i0, j0, Ld) || path < 0 || path > 2)
+        return FTHMC_ERR_ARG;
+    if (path == 1 && (L > HMC_RESIDENT_MAXL || x_new == x)) return FTHMC_ERR_ARG;
+    return defect_trajectory_call(x, v, u, B, L, beta, g_b, DefectLine{i0, j0, Ld}, dt, nstep, integrator, path, x_new, dH, acc, H0, H1,
+                                  csum_out, dsum_out, q_out, ws, ws_bytes, stream);
+}
+int fthmc_defect_force(const double* x, int B, int L, double beta, const double* g_b, int i0, int j0, int Ld, double* F, void* stream) {
+    if (!x || !F || bad_shape(B, L) || bad_defect(L, beta, g_b, i0, j0, Ld)) return FTHMC_ERR_ARG;
+    return launch_defect_force(x, B, L, beta, g_b, DefectLine{i0, j0, Ld}, F, ft_stream(stream));
+}
+int fthmc_defect_action(const double* x, int B, int L, double beta, const double* g_b, int i0, int j0, int Ld, double* S, double* csum,
+                        double* dsum, double* Q, void* stream) {
+    if (!x || bad_shape(B, L) || bad_defect(L, beta, g_b, i0, j0, Ld)) return FTHMC_ERR_ARG;
+    return launch_defect_action(x, B, L, beta, g_b, DefectLine{i0, j0, Ld}, S, csum, dsum, Q, ft_stream(stream));
+}
+int fthmc_defect_translate(const double* x, int B, int L, const int32_t* rung, int top, const int32_t* shift, double* x_out, void* stream) {
+    if (!x || !x_out || x_out == x || !rung || !shift || bad_shape(B, L)) return FTHMC_ERR_ARG;
+    return launch_defect_translate(x, B, L, rung, top, shift, x_out, ft_stream(stream));
 }
 
 // Metadynamics through the flow: the checks are check_ft_meta_args', the workspace open_ft_meta_call's

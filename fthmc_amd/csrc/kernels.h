@@ -150,6 +150,24 @@ int launch_meta_action(const double* x, int B, int L, double beta, const MetaTab
 // one hill of height w per walker at qm[b], added to the table in chain order (in place)
 int launch_meta_deposit(const double* qm, int B, int G, int nb, double qmax, double w, double* vtab, hipStream_t s);
 
+// ---- defect.hip: boundary-condition tempering, plain HMC with a per-chain coupling g_b on a line of plaquettes (fthmc_defect_*)
+// the defect of a call: the plaquettes ((i0 + a) mod L, j0), 0 <= a < Ld, the same for every chain
+struct DefectLine { int i0, j0, Ld; };
+// the whole trajectory in one launch (L <= 64): launch_hmc_trajectory_sched's twin; csum_out, dsum_out, q_out: of the field x_new holds
+int launch_defect_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta, const double* g_b,
+                             const DefectLine& df, const Sched& sched, double* x_new, double* dH, double* acc, double* H0, double* H1,
+                             double* csum_out, double* dsum_out, double* q_out, hipStream_t s);
+// the sequenced path: S[b] = (-beta) C (optional), sums[3][B] = (C, Dsum, Q); gP = w sin P; H[b] += (beta - g_b) Dsum.  B <= 65535 (launch_defect_gp)
+int launch_defect_sums(const double* x, int B, int L, double beta, const DefectLine& df, double* S, double* sums, hipStream_t s);
+int launch_defect_gp(const double* x, int B, int L, double beta, const double* g_b, const DefectLine& df, double* gp, hipStream_t s);
+int launch_defect_energy(const double* sums, int B, double beta, const double* g_b, double* H, hipStream_t s);
+// the pieces on their own
+int launch_defect_force(const double* x, int B, int L, double beta, const double* g_b, const DefectLine& df, double* F, hipStream_t s);
+int launch_defect_action(const double* x, int B, int L, double beta, const double* g_b, const DefectLine& df, double* S, double* csum,
+                         double* dsum, double* Q, hipStream_t s);
+// the chains on rung `top` translated by shift[b] = (s0, s1), every other chain copied; x_out != x
+int launch_defect_translate(const double* x, int B, int L, const int32_t* rung, int top, const int32_t* shift, double* x_out, hipStream_t s);
+
 // ---- rng.hip
 int launch_random_momenta(const int64_t* seeds, int B, int n, double* v, double* u, hipStream_t s);
 int launch_random_uniform(const int64_t* seeds, int B, int n, double lo, double hi, double* out, hipStream_t s);

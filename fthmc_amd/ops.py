@@ -15,7 +15,7 @@ from ._lib import ACT_CODES, INTEGRATORS, MODE_LITERAL, MODE_MD, W_PER_LAYER, Ft
 RESIDENT_MAXL = 64
 
 # The one scratch cache: (device index, stream) -> the flow workspace, (device index, stream, family) -> the buffer of a call
-# family that keeps its own ('train_force', 'loops', 'instanton', 'meta'); all grown on demand by _stream_buffer
+# family that keeps its own ('train_force', 'loops', 'instanton', 'meta', 'defect'); all grown on demand by _stream_buffer
 _WS = {}
 _WS_CAPTURED = set()   # keys whose CURRENT buffer was handed out during a graph capture
 _WS_RETIRED = []   # superseded buffers a captured hipGraph may still point into, kept alive
@@ -614,6 +614,81 @@ def meta_action(x, beta: float, table, qmax: float, wall: float = 0.0, out=None)
     check(_lib.load().fthmc_meta_action(_p(x), B, L, float(beta), *_meta_table(table, B, qmax, wall), _p(S), _p(qm), _p(vb), _stream(x)),
           'fthmc_meta_action')
     return S, qm, vb
+
+
+# ---------------------------------------------------------------- boundary-condition tempering (csrc/defect.hip)
+def defect_ws_bytes(B: int, L: int, path: int = 0) -> int:
+    """Scratch of defect_trajectory: 0 for path 1 (the one-launch path needs none)."""
+    return int(_lib.load().fthmc_defect_ws_bytes(B, L, path))
+
+
+def _defect_args(beta, g_b, defect, B: int, L: int):
+    """the defect of a call as the library reads it -> (beta, pointer of g_b, i0, j0, Ld): g_b a float64 device tensor of B entries
+    used IN PLACE (a replica exchange updates it between calls), defect = (i0, j0, Ld)"""
+    g_b = _expect(g_b, B, 'g_b (per chain)').view(-1)
+    try:
+        i0, j0, Ld = (int(t) for t in defect)
+    except (TypeError, ValueError):
+        raise ValueError(f'defect: expected (i0, j0, Ld), got {defect!r}') from None
+    beta = float(beta)
+    if not (0 <= Ld <= L and 0 <= i0 < L and 0 <= j0 < L and math.isfinite(beta)):
+        raise ValueError(f'defect: 0 <= Ld <= L = {L}, 0 <= i0, j0 < L and a finite beta expected, got {(i0, j0, Ld)}, beta={beta}')
+    return (beta, _p(g_b), i0, j0, Ld)
+
+
+def defect_trajectory(x, v, u, beta: float, g_b, defect, dt: float, nstep: int, integrator='leapfrog', path: int = 0, out=None):
+    """One HMC trajectory of every chain under S_d = -beta sum cos P + (beta - g_b) sum over the defect of cos P (C ABI
+    fthmc_defect_trajectory) -> dict(x_new, dH, acc, H0, H1, csum, dsum, Q) per chain; csum, dsum, Q: sum cos P, its part on the defect
+    and the integer charge of the field x_new holds.  g_b: the defect coupling per chain, a float64 device tensor [B] read in place;
+    defect = (i0, j0, Ld): the plaquettes ((i0 + a) mod L, j0), a < Ld.  path: 0 the library chooses, 1 one launch per trajectory
+    (L <= 64, x_new must not be x), 2 the sequenced path (any L; out['x_new'] may be x).  out: optional dict with any of the result
+    keys to write into.  With g_b = beta everywhere the result is hmc_trajectory's with a beta tensor.  Not differentiable."""
+    ic, path = integrator_code(integrator), int(path)
+    x, v, u, B, L, xn, r = _plain_trajectory_args(x, v, u, out, ('dH', 'acc', 'H0', 'H1', 'csum', 'dsum', 'Q'))
+    if path not in (0, 1, 2) or int(nstep) < 1:
+        raise ValueError(f'defect_trajectory: path in 0 .. 2 and nstep >= 1 expected, got path={path}, nstep={nstep}')
+    df = _defect_args(beta, g_b, defect, B, L)
+    if path == 1 and (L > RESIDENT_MAXL or xn.data_ptr() == x.data_ptr()):
+        raise ValueError(f"defect_trajectory: path 1 serves L <= {RESIDENT_MAXL} with out['x_new'] other than x")
+    with torch.cuda.device(x.device):
+        # path 0 takes the one-launch kernel where fthmc_defect_trajectory says it does: no scratch is asked for there
+        seq = path == 2 or (path == 0 and (L > RESIDENT_MAXL or xn.data_ptr() == x.data_ptr() or get_variant() != 1))
+        ws, nb = _stream_buffer(x, defect_ws_bytes(B, L, 2), 'defect') if seq else (None, 0)
+        check(_lib.load().fthmc_defect_trajectory(_p(x), _p(v), _p(u), B, L, *df, float(dt), int(nstep), ic, path, _p(xn),
+                                                  *(_p(r[k]) for k in ('dH', 'acc', 'H0', 'H1', 'csum', 'dsum', 'Q')), ws, nb, _stream(x)),
+              'fthmc_defect_trajectory')
+    return r
+
+
+def defect_force(x, beta: float, g_b, defect):
+    """F = dS_d / dx of the action with a defect (C ABI fthmc_defect_force), wilson_force's sign"""
+    x = _field(x); B, _, L, _ = x.shape
+    F = torch.empty_like(x)
+    check(_lib.load().fthmc_defect_force(_p(x), B, L, *_defect_args(beta, g_b, defect, B, L), _p(F), _stream(x)), 'fthmc_defect_force')
+    return F
+
+
+def defect_action(x, beta: float, g_b, defect, out=None):
+    """-> (S_d, csum, dsum, Q) per chain (C ABI fthmc_defect_action); out: optional dict with any of 'S', 'csum', 'dsum', 'Q' to write into"""
+    x = _field(x); B, _, L, _ = x.shape
+    S, cs, ds, Q = (_out_vec(out, k, B, x) for k in ('S', 'csum', 'dsum', 'Q'))
+    check(_lib.load().fthmc_defect_action(_p(x), B, L, *_defect_args(beta, g_b, defect, B, L), _p(S), _p(cs), _p(ds), _p(Q), _stream(x)),
+          'fthmc_defect_action')
+    return S, cs, ds, Q
+
+
+def defect_translate(x, rung, top: int, shift, out=None):
+    """The chains on rung `top` translated by shift[b] = (s0, s1), x_out[b, mu, (i + s0) % L, (j + s1) % L] = x[b, mu, i, j], every other
+    chain copied (C ABI fthmc_defect_translate): bit for bit torch.roll(x[b], (s0, s1), (1, 2)).  rung: int32 [B], shift: int32 [B, 2],
+    both on the device and read there; out (a field other than x) or a fresh one -> x_out"""
+    x = _field(x); B, _, L, _ = x.shape
+    _expect(rung, B, 'rung', torch.int32); _expect(shift, 2 * B, 'shift', torch.int32)
+    xo = _out_like(out, x, 'out')
+    if xo.data_ptr() == x.data_ptr():
+        raise FthmcError('defect_translate: out must not be x')
+    with torch.cuda.device(x.device):
+        check(_lib.load().fthmc_defect_translate(_p(x), B, L, _p(rung), int(top), _p(shift), _p(xo), _stream(x)), 'fthmc_defect_translate')
+    return xo
 
 
 def wilson_force(x, beta: float):

@@ -133,6 +133,35 @@ def exact_loop_of_area(beta: float, V: int, A: int, nmax: int = 40) -> float:
     return float(np.exp(num - m).sum() / np.exp(den - m).sum())
 
 
+def exact_defect_plaquette(beta: float, L: int, c: float, Ld: int, on_defect: bool = True, nmax: int = 40) -> float:
+    """<cos P> of one plaquette of 2D U(1) on the periodic L x L lattice whose Ld plaquettes of a defect carry the coupling c beta in
+    place of beta (boundary-condition tempering), on the defect or off it.  The plaquettes still decouple sector by sector,
+        Z = sum_n I_n(beta)^(V - Ld) I_n(c beta)^Ld = sum_n w_n,      <cos P> = sum_n w_n I_n'(y) / I_n(y) / sum_n w_n,
+    y = c beta on the defect and beta off it, I_n'(y) / I_n(y) = I_{n+1}(y) / I_n(y) + n / y (n >= 0; I_{-n} = I_n).  At c = 0 only
+    n = 0 is left on an open line: 0 on the defect, I_1(beta) / I_0(beta) off it.  c = 1 or Ld = 0 is `exact_wilson_loop(beta, L, 1, 1)`.
+    Logarithms relative to I_0 in extended precision, as there."""
+    beta, c, V, Ld = float(beta), float(c), int(L) * int(L), int(Ld)
+    if not (0.0 <= c <= 1.0 and 0 <= Ld <= V):
+        raise ValueError(f'0 <= c <= 1 and 0 <= Ld <= V = {V} expected, got {c}, {Ld}')
+    if on_defect and Ld == 0:
+        raise ValueError('on_defect: the defect has no plaquette (Ld = 0)')
+    LD = np.longdouble
+    n = np.abs(np.arange(-nmax, nmax + 1))
+    lb = _log_bessel_ratios(beta, nmax + 1)
+    open_line = c == 0.0 and Ld > 0                                          # I_n(0) = 0 for n != 0
+    if open_line and on_defect:
+        return 0.0
+    ly = lb if (not on_defect or c == 1.0) else _log_bessel_ratios(c * beta, nmax + 1)
+    y = LD(beta) if not on_defect else LD(c) * LD(beta)
+    ratio = np.exp(ly[n + 1] - ly[n]) + n.astype(LD) / y                       # I_n'(y) / I_n(y)
+    if open_line:
+        return float(ratio[nmax])                                            # the sector n = 0 alone
+    lc = lb if (c == 1.0 or Ld == 0) else _log_bessel_ratios(c * beta, nmax + 1)
+    logw = (V - Ld) * lb[n] + Ld * lc[n]
+    w = np.exp(logw - logw.max())
+    return float((w * ratio).sum() / w.sum())
+
+
 def string_tension_exact(beta: float) -> float:
     """sigma = -log(I_1(beta) / I_0(beta)): W(R, T) = exp(-sigma R T) in infinite volume, an exact area law."""
     return float(-_log_bessel_ratios(beta, 1)[1])

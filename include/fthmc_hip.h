@@ -588,6 +588,53 @@ int fthmc_ft_meta_action_v(const double* x, const double* w, const fthmc_arch_t*
                            const double* vtab, int G, int nb, double qmax, double wall, double* S_b, double* logdet, double* qm,
                            double* vbias, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version);
 
+/* ---- Boundary-condition tempering: plain HMC whose action carries a per-chain coupling on a short line of plaquettes, the defect
+ * (Hasenbusch 2017; Bonanno, Bonati, D'Elia 2021; after the open boundaries of Luescher and Schaefer 2011).  The reference has no
+ * counterpart to any of the five entry points below: it samples the periodic lattice only.
+ * P(i,j) is the plaquette as fthmc_plaquettes forms it.  The defect is the row of plaquettes
+ *     D = {((i0 + a) mod L, j0) : 0 <= a < Ld},      0 <= Ld <= L,  0 <= i0, j0 < L,
+ * the same for every chain of a call.  Chain b has the defect coupling g_b[b] = beta c_b (a device array [B], c_b in [0, 1] the
+ * caller's promise: 0 opens the line, 1 is the periodic lattice).  With C = sum over all plaquettes of cos P (BatchAction's order of
+ * the four links, the chain sums of fthmc_wilson_action_charge) and Dsum = the same cosines summed over D
+ *     S_d = (-beta) C + (beta - g_b) Dsum,      H = S_d + sum v^2 / 2,
+ *     gP(p) = w(p) sin P(p),  w = g_b on D, beta elsewhere:   F0 = gP(i,j) - gP(i,j-1),  F1 = gP(i-1,j) - gP(i,j)
+ * (fthmc_wilson_force's sign).  With g_b = beta for every chain the second term of S_d is an exact zero and every weight is beta:
+ * fthmc_defect_trajectory then gives the bits of fthmc_hmc_trajectory_pb with beta_b = beta on the same path.
+ * A ladder of such chains at ONE beta is exchanged by fthmc_replica_swap as it is, given betas := the ladder of g, C := Dsum and
+ * beta_b := g_b: the pair (a on rung k, c on rung k + 1) is accepted with min(1, exp((g_k - g_{k+1}) (Dsum_c - Dsum_a))).
+ * What the calls refuse: a null x (v, u, x_new; F) / g_b, B or L out of range, nstep < 1, Ld outside [0, L], i0 or j0 outside [0, L),
+ * a beta that is not finite, path outside 0 .. 2, path 1 with L > 64 or x_new == x: FTHMC_ERR_ARG; an unknown integrator, B > 65535 on
+ * the sequenced path: FTHMC_ERR_UNSUPPORTED; a short (or null) workspace where one is needed: FTHMC_ERR_WS. */
+
+/* No reference counterpart.  Scratch of fthmc_defect_trajectory, by fthmc_meta_ws_bytes' rule: 0 for path 1 (the one-launch path needs
+ * none) and for refused arguments, else the sequenced path's (path 0 may take it: x_new == x, L > 64), a multiple of 256 bytes. */
+size_t fthmc_defect_ws_bytes(int B, int L, int path);
+
+/* No reference counterpart.  One trajectory of every chain: H0 = S_d(x) + v^2 / 2, the MD of (integrator, dt, nstep) (FTHMC_INT_*) under
+ * the force above, the end point regularized, H1, accept iff u[b] < exp(-(H1 - H0)).  x_new, dH, acc, H0, H1 as
+ * fthmc_hmc_trajectory_int; csum_out[B], dsum_out[B], q_out[B]: C, Dsum and the integer charge (the rounded sum of the wrapped
+ * plaquettes over 2 pi) of the field x_new holds.  dH .. q_out may be NULL.
+ * path: 1 = one launch per trajectory, one workgroup per chain (L <= 64, x_new must not be x, no workspace); 2 = the sequenced path
+ * (any L, x_new may be x, workspace fthmc_defect_ws_bytes, B <= 65535); 0 = the library chooses, as fthmc_meta_trajectory does.
+ * Enqueue-only, capturable; two calls give the same bits; a chain's result does not depend on B or on its place in the batch. */
+int fthmc_defect_trajectory(const double* x, const double* v, const double* u, int B, int L, double beta, const double* g_b /* [B] */,
+                            int i0, int j0, int Ld, double dt, int nstep, int integrator, int path, double* x_new, double* dH,
+                            double* acc, double* H0, double* H1, double* csum_out /* [B] or NULL */, double* dsum_out /* [B] or NULL */,
+                            double* q_out /* [B] or NULL */, void* ws, size_t ws_bytes, void* stream);
+
+/* No reference counterpart.  The pieces on their own, for tests and tools: F[B][2][L][L] = dS_d / dx, and per chain S = S_d, csum = C,
+ * dsum = Dsum, Q = the integer charge (each of the four may be NULL).  B up to FTHMC_MAX_B. */
+int fthmc_defect_force(const double* x, int B, int L, double beta, const double* g_b, int i0, int j0, int Ld, double* F, void* stream);
+int fthmc_defect_action(const double* x, int B, int L, double beta, const double* g_b, int i0, int j0, int Ld, double* S, double* csum,
+                        double* dsum, double* Q, void* stream);
+
+/* No reference counterpart.  The translation that moves the defect relative to the field: for the chains with rung[b] == top
+ *     x_out[b][mu][(i + s0) mod L][(j + s1) mod L] = x[b][mu][i][j],      (s0, s1) = shift[b][0 .. 1] (any integers),
+ * every other chain is copied; a copy bit for bit either way.  rung: int32 [B], shift: int32 [B][2], both on the device.  A symmetry of
+ * the periodic rung only.  x_out must not be x (it closes the two-buffer ping-pong of path 1: the trajectory goes x -> x_new, the
+ * translation x_new -> x).  A null x / x_out / rung / shift, x_out == x, B or L out of range: FTHMC_ERR_ARG. */
+int fthmc_defect_translate(const double* x, int B, int L, const int32_t* rung, int top, const int32_t* shift, double* x_out, void* stream);
+
 /* ---- training ------------------------------------------------------------ */
 /* Reverse-KL loss pieces and weight gradients for a fixed prior draw xi
  * (fthmc/train.py:191-210, fthmc/utils/samplers.py:40-56):
