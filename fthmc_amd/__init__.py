@@ -4,7 +4,7 @@ __version__ = '0.1.0'
 
 # the samplers beyond the reference that a caller reaches from the package itself; resolved on first use (importing the package
 # loads neither PyTorch nor the library)
-_LAZY = {'MetaPotential': 'meta', 'run_meta': 'meta', 'run_ft_meta': 'meta', 'run_ptbc': 'defect'}
+_LAZY = {'MetaPotential': 'meta', 'run_meta': 'meta', 'run_ft_meta': 'meta', 'run_ptbc': 'defect', 'run_ft_ptbc': 'defect'}
 __all__ = sorted(_LAZY)
 
 

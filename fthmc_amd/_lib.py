@@ -145,7 +145,14 @@ SIGNATURES['fthmc_defect_trajectory'] = [_D, _D, _D, c_int, c_int, c_double] + _
 SIGNATURES['fthmc_defect_force'] = [_D, c_int, c_int, c_double] + _DF + [_D, _P]                  # x, B, L, beta, <defect>, F, stream
 SIGNATURES['fthmc_defect_action'] = [_D, c_int, c_int, c_double] + _DF + [_D, _D, _D, _D, _P]     # ..., S, csum, dsum, Q, stream
 SIGNATURES['fthmc_defect_translate'] = [_D, c_int, c_int, _D, c_int, _D, _D, _P]                  # x, B, L, rung, top, shift, x_out, stream
-_RESTYPE = {'fthmc_defect_ws_bytes': c_size_t, 'fthmc_ft_meta_ws_bytes': c_size_t, 'fthmc_meta_ws_bytes': c_size_t, 'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
+# the defect through the flow: x, (v, u,) w, arch, n_layers, B, L, act, beta, <defect>, (dt, nstep, integrator,) outputs,
+# ws, ws_bytes, stream, weights_version
+SIGNATURES['fthmc_ft_defect_ws_bytes'] = [_A, c_int, c_int, c_int]
+SIGNATURES['fthmc_ft_defect_trajectory_v'] = ([_D, _D, _D, _D, _A, c_int, c_int, c_int, c_int, c_double] + _DF + [c_double, c_int, c_int] +
+                                              [_D] * 10 + [_P, c_size_t, _P, c_uint64])
+SIGNATURES['fthmc_ft_defect_force_v'] = [_D, _D, _A, c_int, c_int, c_int, c_int, c_double] + _DF + [_D, _P, c_size_t, _P, c_uint64]
+SIGNATURES['fthmc_ft_defect_action_v'] = [_D, _D, _A, c_int, c_int, c_int, c_int, c_double] + _DF + [_D] * 5 + [_P, c_size_t, _P, c_uint64]
+_RESTYPE = {'fthmc_ft_defect_ws_bytes': c_size_t, 'fthmc_defect_ws_bytes': c_size_t, 'fthmc_ft_meta_ws_bytes': c_size_t, 'fthmc_meta_ws_bytes': c_size_t, 'fthmc_instanton_ws_bytes': c_size_t, 'fthmc_wilson_loops_ws_bytes': c_size_t, 'fthmc_ws_head_bytes': c_size_t, 'fthmc_layer_stash_bytes': c_size_t, 'fthmc_version': c_char_p, 'fthmc_last_error': c_char_p, 'fthmc_train_ws_bytes': c_size_t, 'fthmc_strerror': c_char_p, 'fthmc_ws_bytes': c_size_t, 'fthmc_vjp_ws_bytes': c_size_t, 'fthmc_train_force_ws_bytes': c_size_t}
 
 _lib = None
 

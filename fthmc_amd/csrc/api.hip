@@ -129,15 +129,19 @@ int eval_action(const Ctx& C, const double* x, const WS& w, int nl, int B, int L
 
 // The bias V(Q_m) of the flowed field (metadynamics) as force_gp and ft_md_ws take it: the table and sums[B][2]
 struct FlowBias { MetaTab T; double* sums; };
+// The defect of the flowed field (boundary-condition tempering through the flow) as force_gp and ft_md_ws take it
+struct FlowDefect { const double* g_b; DefectLine df; };
 
 // Plaquette-gradient field of sum_b S_eff (scaled): gp = scale*beta*sin P(F(x)) + sum_l gP_l,
 // with dL/dlogJ = glogj.  gw != null also accumulates weight gradients (training).
 // beta_b (optional): per-chain beta in place of beta_scaled (the per-chain-beta trajectories: fthmc_*_pb)
 // bias (optional): the seed is beta sin P + c_b cos P of the flowed field, c_b from the chain's sin sum (launch_meta_sums, launch_meta_gp)
+// defect (optional, no bias beside it): the seed is w sin P of the flowed field, w = g_b on the defect and beta elsewhere (launch_defect_gp: one pass)
 int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, int act, double beta_scaled,
              double glogj, double* gw, hipStream_t s, bool have_forward = false, const double* beta_b = nullptr,
-             const FlowBias* bias = nullptr) {
+             const FlowBias* bias = nullptr, const FlowDefect* defect = nullptr) {
     auto seed = [&](double* gp) {
+        if (defect) return launch_defect_gp(phys_field(x, w, nl), B, L, beta_scaled, defect->g_b, defect->df, gp, s);
         if (!bias) return launch_wilson_gp(phys_field(x, w, nl), B, L, beta_scaled, gp, s, beta_b);
         FT_TRY(launch_meta_sums(phys_field(x, w, nl), B, L, bias->sums, s));
         return launch_meta_gp(phys_field(x, w, nl), B, L, beta_scaled, bias->sums, bias->T, gp, s);
@@ -200,12 +204,12 @@ int force_gp(const Ctx& C, const double* x, const WS& w, int nl, int B, int L, i
 // ipynb/ft_hmc.py:426) -- it may be `xshift` itself: nothing reads the shifted field once the kick behind it has its gP.
 int ft_md_ws(const Ctx& C, const double* x, const double* v, const WS& w, int nl, int B, int L, int act, double beta,
              const Sched& sc, hipStream_t s, double* xshift, double* xreg = nullptr, const double* beta_b = nullptr,
-             const FlowBias* bias = nullptr) {
+             const FlowBias* bias = nullptr, const FlowDefect* defect = nullptr) {
     FT_TRY(launch_axpy_copy(x, v, sc.b0, w.xa, w.va, w.n2, s));
     const double* xe = w.xa;                                               // where this stage's force is evaluated
     for (int it = 0; it < sc.n; ++it) {
         const SchedStage st = sc.stage(it);
-        FT_TRY(force_gp(C, xe, w, nl, B, L, act, beta, -1.0, nullptr, s, false, beta_b, bias));
+        FT_TRY(force_gp(C, xe, w, nl, B, L, act, beta, -1.0, nullptr, s, false, beta_b, bias, defect));
         if (st.kind == FT_STAGE_SHIFT) {
             FT_TRY(launch_shift_from_gp(w.gp, w.xa, xshift, B, L, st.a, s));
             xe = xshift;
@@ -448,16 +452,51 @@ int open_ft_meta_call(const fthmc_arch_t* arch, void* stream, void* ws, size_t w
     return use_weights(*C, w, nl, M->W.wint, wver);
 }
 
+// The workspace of the fthmc_ft_defect_* calls: a first-order layout and behind it the (C, Dsum, Q) rows launch_defect_sums leaves
+struct FDWS { WS W; double* sums; size_t total; };
+FDWS ft_defect_layout(const FlowArch& A, Carver& c, int B, int L, int nl) {
+    FDWS d{};
+    d.W = ws_layout(A, c, B, L, nl);
+    if (d.W.total == 0) return d;
+    d.sums = c.take((size_t)3 * B);
+    d.total = c.total();
+    return d;
+}
+// The optional defect of a flowed trajectory call: the couplings, the line and where Dsum of x_new goes (optional)
+struct DefectArg { const double* g_b; DefectLine df; double* dsum_out; };
+// What every fthmc_ft_defect_* call refuses about its arguments -- FTHMC_ERR_ARG, the defect included; FTHMC_ERR_UNSUPPORTED for the
+// activation behind it -- and what it then opens in the ABI's order: FTHMC_ERR_UNSUPPORTED (the sequenced kernels put the chain on
+// grid y), the workspace (the first-order layout and the three rows behind it), the weights.  seq_always: the force and action entry
+// points, which never take the one-launch path.
+int check_ft_defect_args(bool ptrs_ok, const double* w, int nl, int B, int L, int act, double beta, const double* g_b, int i0, int j0, int Ld) {
+    if (bad_defect(L, beta, g_b, i0, j0, Ld)) return FTHMC_ERR_ARG;
+    return check_flow_call(ptrs_ok, w, nl, B, L, act);
+}
+int open_ft_defect_call(const fthmc_arch_t* arch, void* stream, void* ws, size_t ws_bytes, const double* w, int nl, int B, int L,
+                        bool seq_always, uint64_t wver, Ctx* C, FDWS* D) {
+    FT_TRY(open_call(arch, stream, C));
+    if ((seq_always || !C->small(L, nl)) && B > META_SEQ_MAX_B) return FTHMC_ERR_UNSUPPORTED;
+    if (C->A.is_default() && nl > 0 && B > (1 << 20)) return FTHMC_ERR_UNSUPPORTED;     // (open_ws: the default net's kernels)
+    Carver c(ws, ws_bytes);
+    *D = ft_defect_layout(C->A, c, B, L, nl);
+    FT_TRY(check_ws(D->total, ws, ws_bytes));
+    return use_weights(*C, w, nl, D->W.wint, wver);
+}
+
 // The flowed trajectory: H0, MD, H1, Metropolis, plaq / Q of x_new -- the one sequence behind fthmc_ft_trajectory_v, _int_v and
 // _pb_v and, with a bias, behind fthmc_ft_meta_trajectory_v.  beta_b: per-chain beta (null: the scalar `beta`); the state triples
 // are then BETA-FREE (log det J, sum cos P, Q) instead of (S_eff, plaq, Q), and the kernels that take beta_b are handed
 // beta = 0.0 beside it.  bias (optional, FTHMC_MODE_MD and scalar beta only): V(Q_m) of the physical field in every force
 // (ft_md_ws' FlowBias) and behind either end's energy; the state has a fourth row, Q_m, and is TABLE-FREE -- [4][B] = (S_eff
 // unbiased, plaq, Q, Q_m): V of a carried Q_m is looked up in the table of this call.
+// dfa (optional, FTHMC_MODE_MD, scalar beta, no bias): the defect of the physical field -- w sin P seeds every force
+// (ft_md_ws' FlowDefect), (beta - g_b) Dsum goes behind either end's energy; the state has a fourth row, Dsum, and is G-FREE --
+// [4][B] = (S_eff of the periodic action, plaq, Q, Dsum).
 int ft_trajectory_call(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int nl, int B,
                        int L, int act, double beta, const double* beta_b, double dt, int nstep, int integrator, int mode,
                        const BiasArg* bias, double* x_new, double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
-                       const double* state_in, double* state_out, void* ws, size_t ws_bytes, void* stream, uint64_t wver) {
+                       const double* state_in, double* state_out, void* ws, size_t ws_bytes, void* stream, uint64_t wver,
+                       const DefectArg* dfa = nullptr) {
     FT_TRY(check_flow_call(x && v && u && x_new && nstep >= 1, w, nl, B, L, act));
     const bool pb = beta_b != nullptr, leap = integrator == FTHMC_INT_LEAPFROG;
     if (pb) beta = 0.0;
@@ -465,22 +504,27 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
     // FTHMC_MODE_LITERAL discards the MD: no integrator to choose, and no per-chain form of it
     if (mode == FTHMC_MODE_LITERAL && (!leap || pb)) return FTHMC_ERR_UNSUPPORTED;
     const bool md = mode == FTHMC_MODE_MD;
-    if (bias && (pb || !md)) return FTHMC_ERR_UNSUPPORTED;
+    if ((bias || dfa) && (pb || !md)) return FTHMC_ERR_UNSUPPORTED;
+    if (bias && dfa) return FTHMC_ERR_UNSUPPORTED;
     Sched sc;
     FT_TRY(sched_of(integrator, dt, nstep, &sc));
-    Ctx C; MWS M{};
-    FT_TRY(bias ? open_ft_meta_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &M)
-                : open_flow_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &M.W));
+    Ctx C; MWS M{}; FDWS D{};
+    if (dfa) { FT_TRY(open_ft_defect_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &D)); M.W = D.W; }
+    else FT_TRY(bias ? open_ft_meta_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &M)
+                     : open_flow_call(arch, stream, ws, ws_bytes, w, nl, B, L, false, wver, &C, &M.W));
     const WS& W = M.W;
     const hipStream_t s = C.s;
     const FlowBias fb{bias ? bias->T : MetaTab{}, M.sums};
     const FlowBias* fbp = bias ? &fb : nullptr;
+    const FlowDefect fd{dfa ? dfa->g_b : nullptr, dfa ? dfa->df : DefectLine{}};
+    const FlowDefect* fdp = dfa ? &fd : nullptr;
     if (md && C.small(L, nl)) {                                      // the whole trajectory in one launch
         SmallArgs a = small_args(x, W, nl, B, act, beta, 3);
         a.v = v; a.u = u; a.dt = dt; a.nstep = nstep; a.x_out = x_new; a.state_in = state_in; a.state_out = state_out;
         a.dH = dH; a.acc = acc; a.H0 = H0; a.H1 = H1; a.plaq = plaq; a.Q = Q;
-        // four instances of k_ft_small: the biased one and per-chain beta run the schedule-driven one with every integrator, the
-        // leapfrog included
+        // five instances of k_ft_small: the biased one, the one with a defect and per-chain beta run the schedule-driven one with
+        // every integrator, the leapfrog included
+        if (dfa) return launch_ft_small_defect(a, sc, dfa->g_b, dfa->df, dfa->dsum_out, L, s);
         if (bias) return launch_ft_small_meta(a, sc, fb.T, bias->qm_out, bias->vb_out, L, s);
         if (pb) return launch_ft_small_pb(a, sc, beta_b, L, s);
         return leap ? launch_ft_small(a, L, s) : launch_ft_small_sched(a, sc, L, s);
@@ -490,21 +534,31 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
     double* h1 = H1 ? H1 : W.scal + (size_t)SC_H1 * B;
     // per-chain state rows: of x (old), of the proposal (neu), of x_new (sel) -- three in W.scal (slots SC_OLD0.., SC_NEW0..: 3
     // consecutive); with a bias four and V behind them where launch_meta_energy leaves it, in W.vb: the momentum ping-pong field
-    // no flowed sequence touches (2 L^2 >= 32 rows of B)
-    const int nrow = bias ? 4 : 3;
-    double* old = bias ? W.vb : W.scal + (size_t)SC_OLD0 * B;
-    double* neu = bias ? W.vb + (size_t)5 * B : W.scal + (size_t)SC_NEW0 * B;
-    double* sel = state_out ? state_out : (bias ? W.vb + (size_t)10 * B : W.scal + (size_t)SC_S * B);
+    // no flowed sequence touches (2 L^2 >= 32 rows of B); with a defect four as well, Dsum the fourth, in the same places
+    const bool four = bias || dfa;
+    const int nrow = four ? 4 : 3;
+    double* old = four ? W.vb : W.scal + (size_t)SC_OLD0 * B;
+    double* neu = four ? W.vb + (size_t)5 * B : W.scal + (size_t)SC_NEW0 * B;
+    double* sel = state_out ? state_out : (four ? W.vb + (size_t)10 * B : W.scal + (size_t)SC_S * B);
     double* qm_sel = sel + (size_t)3 * B;
-    // V(Q_m) into an end's energy and Q_m into its fourth row: of the field (sums) or of the carried state; no bias: nothing
+    const size_t row = (size_t)B * sizeof(double);
+    // V(Q_m) into an end's energy and Q_m into its fourth row: of the field (sums) or of the carried state; no bias: nothing.
+    // With a defect: (beta - g_b) Dsum into the energy and Dsum into the fourth row -- launch_defect_energy reads Dsum one row behind
+    // the pointer it is given, so the state's own fourth row serves it
     auto add_bias = [&](const double* xphys, double* rows, double* h) {
-        if (!bias) return FTHMC_OK;
+        if (dfa) {
+            if (xphys) {
+                FT_TRY(launch_defect_sums(xphys, B, L, beta, dfa->df, nullptr, D.sums, s));
+                if (hipMemcpyAsync(rows + (size_t)3 * B, D.sums + B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return (int)FTHMC_ERR_LAUNCH;
+            }
+            return launch_defect_energy(rows + (size_t)2 * B, B, beta, dfa->g_b, h, s);
+        }
+        if (!bias) return (int)FTHMC_OK;
         if (!xphys) return launch_meta_energy_qm(rows + (size_t)3 * B, B, fb.T, h, nullptr, s);
         FT_TRY(launch_meta_sums(xphys, B, L, M.sums, s));
         return launch_meta_energy(M.sums, B, fb.T, h, rows + (size_t)3 * B, s);
     };
-    const size_t row = (size_t)B * sizeof(double);
-    if (bias && state_in && hipMemcpyAsync(old + (size_t)3 * B, state_in + (size_t)3 * B, row, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    if (four && state_in && hipMemcpyAsync(old + (size_t)3 * B, state_in + (size_t)3 * B, row, hipMemcpyDeviceToDevice, s) != hipSuccess)
         return FTHMC_ERR_LAUNCH;
     const bool tuned = md && C.A.is_default() && nl > 0;
     if (tuned) {
@@ -517,7 +571,7 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
         if (!state_in) FT_TRY(sweep_forward(C, x, W, nl, B, L, act, nullptr, s, false, false, true));
         FT_TRY(launch_traj_energy(phys_field(x, W, nl), B, L, beta, W.lj_part, np, nl, state_in, v, old, h0, s, beta_b));
         FT_TRY(add_bias(state_in ? nullptr : phys_field(x, W, nl), old, h0));
-        FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b, fbp));
+        FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b, fbp, fdp));
         FT_TRY(sweep_forward(C, W.xb, W, nl, B, L, act, nullptr, s, false, false, true));
         FT_TRY(launch_traj_energy(phys_field(W.xb, W, nl), B, L, beta, W.lj_part, np, nl, nullptr, W.va, neu, h1, s, beta_b));
         FT_TRY(add_bias(phys_field(W.xb, W, nl), neu, h1));
@@ -539,10 +593,10 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
             FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 0, s));              // wrap (ft_hmc.py:208)
             vend = v;
         } else if (leap && !pb) {                                     // scalar-beta leapfrog: the last kick writes no xreg,
-            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, nullptr, nullptr, nullptr, fbp));
+            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, nullptr, nullptr, nullptr, fbp, fdp));
             FT_TRY(launch_wrap(W.xa, W.xb, W.n2, 1, s));              // a launch of its own regularizes (ipynb/ft_hmc.py:426)
         } else {                                                      // schedules and per-chain beta: xreg inside the last kick
-            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b, fbp));
+            FT_TRY(ft_md_ws(C, x, v, W, nl, B, L, act, beta, sc, s, W.xb, W.xb, beta_b, fbp, fdp));
         }
         if (pb) FT_TRY(pb_eval(C, W.xb, W, nl, B, L, act, beta_b, nullptr, neu, seff, s));
         else FT_TRY(eval_action(C, W.xb, W, nl, B, L, act, beta, neu, nullptr, neu + B, neu + 2 * B, s));
@@ -553,12 +607,14 @@ int ft_trajectory_call(const double* x, const double* v, const double* u, const 
     // The state of x_new without another sweep: selected per chain.  Who hands plaq / Q out: the Metropolis kernel both on the
     // tuned branch and with a bias; per-chain beta: Q (the triple's third row) from the kernel on either branch, plaq from the
     // triple's second row and beta_b; the scalar unbiased general branch: two copies out of `sel`.
-    const bool both = bias || (tuned && !pb);
+    const bool both = four || (tuned && !pb);
     FT_TRY(launch_metropolis(x, W.xb, u, h0, h1, B, L, 0, x_new, dH, acc, old, neu, sel, nrow, s, both ? plaq : nullptr,
                              both || pb ? Q : nullptr));
     if (bias) {                                                      // Q_m of x_new: the fourth row; V of it from this call's table
         if (bias->qm_out && hipMemcpyAsync(bias->qm_out, qm_sel, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
         if (bias->vb_out) FT_TRY(launch_meta_energy_qm(qm_sel, B, fb.T, nullptr, bias->vb_out, s));
+    } else if (dfa) {                                                // Dsum of x_new: the fourth row
+        if (dfa->dsum_out && hipMemcpyAsync(dfa->dsum_out, qm_sel, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     } else if (pb) {
         if (plaq) FT_TRY(launch_pb_from_state(sel, beta_b, B, L, nl > 0, nullptr, plaq, s));
     } else if (!tuned) {
@@ -1189,6 +1245,52 @@ int fthmc_ft_meta_action_v(const double* x, const double* w, const fthmc_arch_t*
     FT_TRY(launch_meta_energy(M.sums, B, T, sb, W.vb, s));          // W.vb: (Q_m, V), [2][B]
     if (qm && hipMemcpyAsync(qm, W.vb, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     if (vbias && hipMemcpyAsync(vbias, W.vb + B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    return FTHMC_OK;
+}
+
+// Boundary-condition tempering through the flow: the checks are check_ft_defect_args', the workspace open_ft_defect_call's
+size_t fthmc_ft_defect_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers) {
+    Ctx C; Carver c;
+    if (B <= 0 || L <= 0 || n_layers < 0 || make_ctx(arch, nullptr, &C) != FTHMC_OK) return 0;
+    return ft_defect_layout(C.A, c, B, L, n_layers).total * sizeof(double);
+}
+int fthmc_ft_defect_trajectory_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
+                                 int B, int L, int act, double beta, const double* g_b, int i0, int j0, int Ld, double dt, int nstep,
+                                 int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1, double* plaq, double* Q,
+                                 double* dsum_out, const double* state_in, double* state_out, void* ws, size_t ws_bytes, void* stream,
+                                 uint64_t weights_version) {
+    const DefectArg dfa{g_b, DefectLine{i0, j0, Ld}, dsum_out};
+    FT_TRY(check_ft_defect_args(x && v && u && x_new && nstep >= 1, w, n_layers, B, L, act, beta, g_b, i0, j0, Ld));
+    return ft_trajectory_call(x, v, u, w, arch, n_layers, B, L, act, beta, nullptr, dt, nstep, integrator, FTHMC_MODE_MD, nullptr, x_new, dH,
+                              acc, H0, H1, plaq, Q, state_in, state_out, ws, ws_bytes, stream, weights_version, &dfa);
+}
+int fthmc_ft_defect_force_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
+                            const double* g_b, int i0, int j0, int Ld, double* F, void* ws, size_t ws_bytes, void* stream,
+                            uint64_t weights_version) {
+    Ctx C; FDWS D;
+    FT_TRY(check_ft_defect_args(x && F, w, n_layers, B, L, act, beta, g_b, i0, j0, Ld));
+    FT_TRY(open_ft_defect_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, true, weights_version, &C, &D));
+    const FlowDefect fd{g_b, DefectLine{i0, j0, Ld}};
+    FT_TRY(force_gp(C, x, D.W, n_layers, B, L, act, beta, -1.0, nullptr, C.s, false, nullptr, nullptr, &fd));
+    return launch_kick_from_gp(D.W.gp, nullptr, nullptr, F, B, L, 0.0, 0.0, C.s);
+}
+int fthmc_ft_defect_action_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
+                             const double* g_b, int i0, int j0, int Ld, double* S, double* logdet, double* csum, double* dsum, double* Q,
+                             void* ws, size_t ws_bytes, void* stream, uint64_t weights_version) {
+    Ctx C; FDWS D;
+    FT_TRY(check_ft_defect_args(x != nullptr, w, n_layers, B, L, act, beta, g_b, i0, j0, Ld));
+    FT_TRY(open_ft_defect_call(arch, stream, ws, ws_bytes, w, n_layers, B, L, true, weights_version, &C, &D));
+    const WS& W = D.W;
+    const hipStream_t s = C.s;
+    const size_t row = (size_t)B * sizeof(double);
+    if (n_layers == 0 && logdet && hipMemsetAsync(logdet, 0, row, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    double* sb = S ? S : W.vb;                                       // S_eff of the periodic action first, the defect's term added in place
+    FT_TRY(eval_action(C, x, W, n_layers, B, L, act, beta, sb, logdet, nullptr, nullptr, s));
+    FT_TRY(launch_defect_sums(phys_field(x, W, n_layers), B, L, beta, DefectLine{i0, j0, Ld}, nullptr, D.sums, s));
+    FT_TRY(launch_defect_energy(D.sums, B, beta, g_b, sb, s));
+    if (csum && hipMemcpyAsync(csum, D.sums, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    if (dsum && hipMemcpyAsync(dsum, D.sums + B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
+    if (Q && hipMemcpyAsync(Q, D.sums + 2 * (size_t)B, row, hipMemcpyDeviceToDevice, s) != hipSuccess) return FTHMC_ERR_LAUNCH;
     return FTHMC_OK;
 }
 

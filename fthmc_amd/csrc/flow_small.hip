@@ -155,10 +155,18 @@ __device__ __forceinline__ MetaTab meta_tab(const double** row, int b) {
     *row = mt_row(T, b);
     return T;
 }
-template <bool SCHED, bool PB = false, bool BIAS = false> struct SmallArgsOf { typedef SmallArgs type; };
-template <> struct SmallArgsOf<true, false, false> { typedef SmallArgsSched type; };
-template <> struct SmallArgsOf<true, true, false> { typedef SmallArgsPB type; };
-template <> struct SmallArgsOf<true, false, true> { typedef SmallArgsMeta type; };
+// The instance with a defect (k_ft_small<..., SCHED, false, false, DEFECT>: boundary-condition tempering through the flow,
+// fthmc_ft_defect_trajectory_v) takes the schedule-driven block with the couplings g_b[B], the three integers of the line
+// and dsum_out behind it, all read from the kernel arguments where a sweep needs them; state_in / state_out are the g-free [4][B]
+// (S_eff of the periodic action, plaq, Q, Dsum)
+struct SmallArgsDefect : SmallArgsSched { const double* g_b; int i0, j0, Ld; double* dsum_out; };
+typedef const __attribute__((address_space(4))) SmallArgsDefect ColdDefect;
+__device__ __forceinline__ ColdDefect& cold_defect() { return kernarg<SmallArgsDefect>(); }
+template <bool SCHED, bool PB = false, bool BIAS = false, bool DEFECT = false> struct SmallArgsOf { typedef SmallArgs type; };
+template <> struct SmallArgsOf<true, false, false, false> { typedef SmallArgsSched type; };
+template <> struct SmallArgsOf<true, true, false, false> { typedef SmallArgsPB type; };
+template <> struct SmallArgsOf<true, false, true, false> { typedef SmallArgsMeta type; };
+template <> struct SmallArgsOf<true, false, false, true> { typedef SmallArgsDefect type; };
 
 // the stash values a backward pass multiplies by, loaded one pass ahead
 struct BwdPre { double tcv[4 * NMIX], fcs, fsn, d2v[4], d1v[4]; };
@@ -673,9 +681,18 @@ template <int L, bool TRAIN> struct Chain {
         const int ip = i + 1 == L ? 0 : i + 1, jp = j + 1 == L ? 0 : j + 1;
         return sX[s] - sX[N + s] - sX[i * L + jp] + sX[N + ip * L + j];
     }
+    // is the plaquette of site tid on the defect of this call?  The three integers come from the kernel arguments at every use: nothing
+    // of the line lives through a layer pass (0 <= i0 < L, 0 <= Ld <= L: i - i0 + L lies in [1, 2 L))
+    __device__ __forceinline__ bool on_defect() const {
+        ColdDefect& Dc = cold_defect();
+        const int i = fdiv<L>(tid), j = tid - i * L;
+        int a = i - Dc.i0;
+        a = a < 0 ? a + L : a;
+        return j == Dc.j0 && a < Dc.Ld;
+    }
     // C = sum cos P, Q = sum wrap(P) / 2 pi of the field in sX; results valid in every thread (the per-chain-beta instance keeps C
-    // itself: the beta-free state)
-    __device__ void action_sums(double& Cs, double& Q) {
+    // itself: the beta-free state).  DEF: behind these two block sums a third, Dsum = the same cosines on the defect
+    template <bool DEF = false> __device__ void action_sums(double& Cs, double& Q, double* Ds = nullptr) {
         constexpr int N = G::N;
         const double* sX = sm + G::X;
         double* red = sm + G::RED;
@@ -691,6 +708,7 @@ template <int L, bool TRAIN> struct Chain {
         }
         Cs = ft_block_sum(c, red);
         Q = ft_block_sum(q, red) / FT_TWO_PI;
+        if constexpr (DEF) *Ds = ft_block_sum(tid < N && on_defect() ? c : 0.0, red);
     }
     // S_W = -beta sum cos P and Q
     __device__ void action_charge(double beta, double& S, double& Q) {
@@ -705,6 +723,18 @@ template <int L, bool TRAIN> struct Chain {
             double sn_, cs_;
             ft_sincos(plaq_at(sm + G::X, tid), &sn_, &cs_);
             sm[G::GP + tid] = beta * sn_;
+        }
+        lds_barrier();
+    }
+    // the seed under a defect: gP = w sin P, w = g_b of the chain on the defect and beta elsewhere -- wilson_seed's one
+    // ft_sincos per site times a weight decided here from (i, j) and the line, so that no weight is held through the layer passes
+    __device__ void defect_seed(double beta) {
+        constexpr int N = G::N;
+        if (tid < N) {
+            double sn_, cs_;
+            ft_sincos(plaq_at(sm + G::X, tid), &sn_, &cs_);
+            const double g = gld(cold_defect().g_b + chain());
+            sm[G::GP + tid] = (on_defect() ? g : beta) * sn_;
         }
         lds_barrier();
     }
@@ -763,10 +793,15 @@ enum { SM_ACTION = 0, SM_FORCE = 1, SM_LEAPFROG = 2, SM_TRAJ = 3, SM_TRAIN = 4 }
 //   BIAS:        the SCHED instance under V(Q_m) of the flowed field: a FORCE sweep seeds with meta_seed, an EVAL sweep adds the
 //                sin P sum; thread 0 keeps (Q_m, V) of x and of the proposal in the same four slots, H = S_eff + K / 2 + V, and
 //                the carried triple stays unbiased (the state's fourth row is Q_m: V is looked up in the table of the call)
-template <int L, bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false, bool BIAS = false>
-__global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArgsOf<SCHED, PB, BIAS>::type Aarg) {
+//   DEFECT:      the SCHED instance with the coupling g_b[b] on a line of plaquettes of the flowed field: a FORCE sweep seeds with
+//                defect_seed, an EVAL sweep takes a third block sum, Dsum, from the cosines it has; thread 0 keeps Dsum of x and of the
+//                proposal in two of the same four slots, H = S_eff + K / 2 + (beta - g_b) Dsum, and the carried triple stays the periodic
+//                action's (the state's fourth row is Dsum: the term is formed with the g_b of the call)
+template <int L, bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false, bool BIAS = false, bool DEFECT = false>
+__global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArgsOf<SCHED, PB, BIAS, DEFECT>::type Aarg) {
     static_assert(!PB || (SCHED && !DBG && !TRAIN), "the per-chain-beta instance is a schedule-driven trajectory");
     static_assert(!BIAS || (SCHED && !PB && !DBG && !TRAIN), "the biased instance is a schedule-driven trajectory");
+    static_assert(!DEFECT || (SCHED && !PB && !BIAS && !DBG && !TRAIN), "the instance with a defect is a schedule-driven trajectory");
     using G = GS<L>;
     constexpr int N = G::N;
     __shared__ __attribute__((aligned(16))) double sm[G::SIZE];
@@ -818,6 +853,9 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
                 sm[G::PROF] = qm; sm[G::PROF + 1] = V;
             }
         }
+        if constexpr (DEFECT) {
+            if (have_state && tid == 0) sm[G::PROF] = cold().state_in[3 * (size_t)hot.B + b];     // the carried Dsum
+        }
         const double k0 = ft_block_sum(v0 * v0 + v1 * v1, red);
         if (tid == 0) stt[6] = k0;
     }
@@ -868,6 +906,7 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
             __syncthreads();
             C.bwd_issue(nl - 1, C.pre);
             if constexpr (BIAS) C.meta_seed(bscale); else
+            if constexpr (DEFECT) C.defect_seed(bscale); else
             C.wilson_seed(bscale);
             C.stamp(17);
             for (int l = nl - 1; l >= 0; --l) C.layer_bwd(l, cb, l > 0, l > 0 ? l - 1 : (it < last ? 0 : -1));
@@ -907,6 +946,12 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
             }
         } else {
             double S, Q;
+            if constexpr (DEFECT) {                                        // action_charge's two block sums in their order, then Dsum
+                double c, d;
+                C.template action_sums<true>(c, Q, &d);
+                S = (-beta) * c;
+                if (tid == 0) sm[G::PROF + (it < 0 ? 0 : 2)] = d;
+            } else
             C.action_charge(beta, S, Q);
             if (tid == 0) {                                                // ld lives in thread 0
                 double* st = stt + (it < 0 ? 0 : 3);
@@ -952,6 +997,10 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
     if (tid == 0) {
         double h0 = stt[0] + 0.5 * stt[6], h1 = stt[3] + 0.5 * k1;
         if constexpr (BIAS) { h0 = h0 + sm[G::PROF + 1]; h1 = h1 + sm[G::PROF + 3]; }
+        if constexpr (DEFECT) {                                            // k_defect_energy's H + (beta - g_b) Dsum
+            const double dg = beta - gld(cold_defect().g_b + b);
+            h0 = h0 + dg * sm[G::PROF]; h1 = h1 + dg * sm[G::PROF + 2];
+        }
         const double d = h1 - h0;
         const bool ok = A.u[b] < exp(-d);
         if (A.dH) A.dH[b] = d;
@@ -970,6 +1019,12 @@ __global__ FT_LDS_B64 __launch_bounds__(NT, 2) void k_ft_small(typename SmallArg
             if (A.state_out) A.state_out[3 * (size_t)A.B + b] = keep[0];
             if (M.qm_out) M.qm_out[b] = keep[0];
             if (M.vb_out) M.vb_out[b] = keep[1];
+        }
+        if constexpr (DEFECT) {
+            const double dsel = sm[G::PROF + (ok ? 2 : 0)];
+            ColdDefect& Dc = cold_defect();
+            if (A.state_out) A.state_out[3 * (size_t)A.B + b] = dsel;
+            if (Dc.dsum_out) Dc.dsum_out[b] = dsel;
         }
         if (A.plaq) A.plaq[b] = sel[1];
         if (A.Q) A.Q[b] = sel[2];
@@ -998,13 +1053,13 @@ int get_small_path() {
 bool ft_small_shape(int L, int nl) { return nl >= 1 && (L == 8 || L == 12 || L == 16); }
 
 // one workgroup per chain: the instance of k_ft_small with these flags for the lattice size
-template <bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false, bool BIAS = false>
-static int launch_instance(const typename SmallArgsOf<SCHED, PB, BIAS>::type& a, int L, hipStream_t s) {
+template <bool TRAIN, bool TRAJ, bool DBG, bool SCHED, bool PB = false, bool BIAS = false, bool DEFECT = false>
+static int launch_instance(const typename SmallArgsOf<SCHED, PB, BIAS, DEFECT>::type& a, int L, hipStream_t s) {
     const dim3 grid(a.B), block(NT);
     switch (L) {
-        case 8: hipLaunchKernelGGL((k_ft_small<8, TRAIN, TRAJ, DBG, SCHED, PB, BIAS>), grid, block, 0, s, a); break;
-        case 12: hipLaunchKernelGGL((k_ft_small<12, TRAIN, TRAJ, DBG, SCHED, PB, BIAS>), grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_ft_small<16, TRAIN, TRAJ, DBG, SCHED, PB, BIAS>), grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((k_ft_small<8, TRAIN, TRAJ, DBG, SCHED, PB, BIAS, DEFECT>), grid, block, 0, s, a); break;
+        case 12: hipLaunchKernelGGL((k_ft_small<12, TRAIN, TRAJ, DBG, SCHED, PB, BIAS, DEFECT>), grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL((k_ft_small<16, TRAIN, TRAJ, DBG, SCHED, PB, BIAS, DEFECT>), grid, block, 0, s, a); break;
         default: return FTHMC_ERR_UNSUPPORTED;
     }
     FT_LAUNCH_CHECK(); return FTHMC_OK;
@@ -1043,6 +1098,15 @@ int launch_ft_small_meta(const SmallArgs& a0, const Sched& sched, const MetaTab&
     if (!T.v || T.cpr < 1 || T.nb < 2) return FTHMC_ERR_ARG;
     a.T = T; a.qm_out = qm_out; a.vb_out = vb_out;
     return launch_instance<false, false, false, true, false, true>(a, L, s);
+}
+
+// a trajectory of a schedule with the couplings g_b on the defect df (state_in / state_out: the g-free [4][B])
+int launch_ft_small_defect(const SmallArgs& a0, const Sched& sched, const double* g_b, const DefectLine& df, double* dsum_out, int L, hipStream_t s) {
+    SmallArgsDefect a;
+    if (const int rc = sched_block(a0, sched, L, false, &a)) return rc;
+    if (!g_b || df.Ld < 0 || df.Ld > L || df.i0 < 0 || df.i0 >= L || df.j0 < 0 || df.j0 >= L) return FTHMC_ERR_ARG;
+    a.g_b = g_b; a.i0 = df.i0; a.j0 = df.j0; a.Ld = df.Ld; a.dsum_out = dsum_out;
+    return launch_instance<false, false, false, true, false, false, true>(a, L, s);
 }
 
 int launch_ft_small(const SmallArgs& a, int L, hipStream_t s) {

@@ -455,6 +455,9 @@ int launch_ft_small_pb(const SmallArgs& a, const Sched& sched, const double* bet
 // mode 3 of a schedule under the bias V(Q_m) of the flowed field (metadynamics); state_in / state_out: the table-free
 // [4][B] (S_eff unbiased, plaq, Q, Q_m); qm_out, vb_out (optional): Q_m and V(Q_m) of F(x_new)
 int launch_ft_small_meta(const SmallArgs& a, const Sched& sched, const MetaTab& T, double* qm_out, double* vb_out, int L, hipStream_t s);
+// mode 3 of a schedule with the couplings g_b on the defect df of the flowed field; state_in / state_out: the g-free
+// [4][B] = (S_eff of the periodic action, plaq, Q, Dsum)
+int launch_ft_small_defect(const SmallArgs& a, const Sched& sched, const double* g_b, const DefectLine& df, double* dsum_out, int L, hipStream_t s);
 void set_small_path(int v);
 int get_small_path();
 // 0: VALU kernels everywhere; 1 (default): MFMA kernels for forward and backward-wrt-x

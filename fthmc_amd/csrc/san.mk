@@ -40,7 +40,7 @@ san_integrator:
 # fthmc_ladder_init: tests/test_tempering.py), loops (the Wilson-loop entry points: tests/test_wilson_loops.py), local
 # (fthmc_local_update: tests/test_local_update.py), instanton (the instanton hits and the integer reductions of topo_int.h:
 # tests/test_instanton.py), meta (the fthmc_meta_* entry points: tests/test_meta.py), ft_meta (the fthmc_ft_meta_* entry points:
-# tests/test_ft_meta.py).  san_build, san_integrator and san_layout are rules of their own.
+# tests/test_ft_meta.py), ft_defect (the fthmc_ft_defect_* entry points: tests/test_ft_defect.py, through SANEXE).  san_build, san_integrator and san_layout are rules of their own.
 $(SANOUT): $(SRCS) common.h kernels.h integrator.h topo_int.h meta_tab.h api_call.h ../../include/fthmc_hip.h san.mk
 	@$(MAKE) --no-print-directory -f san.mk san_build
 SANWALKVARS = tempering:SANTEMP loops:SANLOOPS local:SANLOCAL instanton:SANINST meta:SANMETA ft_meta:SANFTMETA

@@ -19,6 +19,11 @@ The reference (nftqcd/fthmc) samples the periodic lattice only and has no counte
 Random numbers: momenta, accept uniforms and swap uniforms as tempering.run_tempered draws them (the same seed and key-domain rules);
 the shifts of iteration t come from a stream of their own key domain, (shift_seed(seed), GLOBAL chain id, t), as floor(U[0, 1) L)
 formed on the device: a replay of the captured loop draws new ones.
+
+run_ft_ptbc is the same ladder through a flow: the loop runs in the latent field of ftHMC, the defect sits on the
+physical field F(x) (ops.ft_defect_trajectory), the swaps read Dsum of the physical field.  The coupling layers' stripe masks have
+period 4 across the stripes, so the flow commutes with the translations by multiples of 4 in both directions and with no others: the
+shifts there are 4 floor(U[0, 1) L / 4), from the same stream.
 """
 from __future__ import annotations
 
@@ -61,6 +66,27 @@ def run_ptbc(param: Param, cs: Sequence[float], n_ladders: int, ntraj: int, defe
     acceptance per neighbouring pair, 'swap_tried' [K - 1] and 'swap_rounds' [ntraj, M_local, K - 1] the rounds themselves (1, 0, or -1:
     not tried); 'rung' [ntraj, B_local] the rung each chain ran on; 'round_trips' [B_local]; 'cs' and 'defect' as the run used them;
     'x' the final fields, 'g_b' / 'rung_last' their ladder positions (run_tempered's 'beta_b' / 'rung_last')."""
+    return _run(param, None, cs, n_ladders, ntraj, defect, swap_every, translate, integrator, seed, x, captured, shard, 'silu')
+
+
+def run_ft_ptbc(param: Param, flow, cs: Sequence[float], n_ladders: int, ntraj: int, defect=None, swap_every: int = 1,
+                translate: bool = True, integrator: str = 'leapfrog', seed: Optional[int] = None, x: Optional[torch.Tensor] = None,
+                captured: bool = True, shard=None, act: str = 'silu'):
+    """run_ptbc through a flow: field-transformation HMC whose PHYSICAL field F(x) carries the defect (ops.ft_defect_trajectory,
+    DESIGN 4.19).  flow: an nn.ModuleList of coupling layers (its weights through utils.layers.flow_weights; act: their activation);
+    an empty one is run_ptbc's sequenced trajectory.  The loop runs in the latent field; the swaps are ops.replica_swap on Dsum of the
+    physical field; the translation of the top rung is ops.defect_translate on the latent field by multiples of 4 in both directions,
+    the translations the flow commutes with.  A translation changes Dsum of the translated chains: with translate=True every trajectory
+    evaluates its own start, with translate=False the g-free state [4, B] is carried from trajectory to trajectory (bit-equal).
+
+    -> run_ptbc's history; 'plaq', 'Q', 'acc', 'dH', 'dsum' are of the PHYSICAL field, 'x' is the final LATENT field."""
+    if flow is None:
+        raise ValueError('run_ft_ptbc: a flow (a list of coupling layers, possibly empty) expected; run_ptbc is the driver without one')
+    return _run(param, flow, cs, n_ladders, ntraj, defect, swap_every, translate, integrator, seed, x, captured, shard, act)
+
+
+def _run(param, flow, cs, n_ladders, ntraj, defect, swap_every, translate, integrator, seed, x, captured, shard, act):
+    """the one loop behind run_ptbc (flow None) and run_ft_ptbc"""
     ops.integrator_code(integrator)
     cl = [float(c) for c in cs]
     K, M_all = len(cl), int(n_ladders)
@@ -81,6 +107,14 @@ def run_ptbc(param: Param, cs: Sequence[float], n_ladders: int, ntraj: int, defe
     seed = int(param.seed if seed is None else seed)
     dev = device() if x is None else x.device
     dt, nstep = param.tau / param.nstep, param.nstep
+    if flow is not None:
+        ops.act_code(act)
+        nl = len(flow)
+        if nl:
+            from .utils.layers import flow_weights
+            wflow = flow_weights(flow, dev).detach()
+        else:
+            wflow = None
 
     if x is None:
         xs = torch.zeros(B, 2, L, L, dtype=DTYPE, device=dev)
@@ -94,7 +128,8 @@ def run_ptbc(param: Param, cs: Sequence[float], n_ladders: int, ntraj: int, defe
     lad = ops.ladder_init([beta * c for c in cl], M, device=dev)         # the ladder of g: g_0 = 0 is a rung like any other
     g_b, rung, chain_of, dg = lad['beta_b'], lad['rung'], lad['chain_of'], lad['betas']
     P = 2 * int(swap_every)                                              # one period: both parities once
-    layout = Row(None, acc=B, dH=B, csum=B, dsum=B, Q=B, rung=B, swap_acc=(M, K - 1))   # swap_acc: of the round behind the trajectory
+    pk = 'csum' if flow is None else 'plaq'                              # what the trajectory hands out: sum cos P, or its mean
+    layout = Row(None, acc=B, dH=B, **{pk: B}, dsum=B, Q=B, rung=B, swap_acc=(M, K - 1))   # swap_acc: of the round behind the trajectory
     rows = torch.empty(P, layout.width, dtype=torch.float64, device=dev)
     xn, v = torch.empty_like(xs), torch.empty_like(xs)                   # the trajectory goes xs -> xn, the translation xn -> xs
     u = torch.empty(B, dtype=torch.float64, device=dev)
@@ -109,15 +144,23 @@ def run_ptbc(param: Param, cs: Sequence[float], n_ladders: int, ntraj: int, defe
     h_cnt = torch.zeros(1, dtype=torch.int64, device=dev)                # translations done
     scratch = {k: torch.empty(B, dtype=torch.float64, device=dev) for k in ('H0', 'H1')}
     dscr = torch.empty(M, K - 1, dtype=torch.float64, device=dev)
+    state = torch.empty(4, B, dtype=torch.float64, device=dev) if flow is not None else None
+    have_state = [False]                                                 # translate=False: the g-free state is carried
 
     def one(j: int):
         """trajectory j of a period, the swap round and the translation behind it -> rows[j]"""
         row = layout.over(rows[j])
-        out = {'x_new': xn, 'acc': row['acc'], 'dH': row['dH'], 'csum': row['csum'], 'dsum': row['dsum'], 'Q': row['Q'],
+        out = {'x_new': xn, 'acc': row['acc'], 'dH': row['dH'], pk: row[pk], 'dsum': row['dsum'], 'Q': row['Q'],
                'H0': scratch['H0'], 'H1': scratch['H1']}
         ops.chain_seeds(seed, lo, B, 0, counter=t_cnt, advance=True, out=seeds)
         ops.random_momenta(seeds, (B, 2, L, L), out_v=v, out_u=u)
-        ops.defect_trajectory(xs, v, u, beta, g_b, df, dt, nstep, integrator=integrator, path=0, out=out)
+        if flow is None:
+            ops.defect_trajectory(xs, v, u, beta, g_b, df, dt, nstep, integrator=integrator, path=0, out=out)
+        else:
+            out['state'] = state
+            ops.ft_defect_trajectory(xs, v, u, wflow, nl, beta, g_b, df, dt, nstep, act, integrator, out=out,
+                                     state_in=state if have_state[0] else None)
+            have_state[0] = not translate
         row['rung'].copy_(rung)                                          # the rung this trajectory ran on
         sw = row['swap_acc']
         if (j + 1) % swap_every == 0:
@@ -130,7 +173,10 @@ def run_ptbc(param: Param, cs: Sequence[float], n_ladders: int, ntraj: int, defe
         if translate:
             ops.chain_seeds(shift_seed(seed), lo, B, 0, counter=h_cnt, advance=True, out=hseeds)
             ops.random_uniform(hseeds, (B, 2), 0.0, 1.0, out=ush)
-            shift.copy_(ush.mul_(float(L)).floor_())                     # floor(U[0, 1) L), on the device
+            if flow is None:
+                shift.copy_(ush.mul_(float(L)).floor_())                 # floor(U[0, 1) L), on the device
+            else:
+                shift.copy_(ush.mul_(float(L // 4)).floor_().mul_(4.0))  # 4 floor(U[0, 1) L / 4): what the flow commutes with
             ops.defect_translate(xn, rung, K - 1, shift, out=xs)
         else:
             xs.copy_(xn)
@@ -164,9 +210,10 @@ def run_ptbc(param: Param, cs: Sequence[float], n_ladders: int, ntraj: int, defe
         # chain on rung k of ladder m at trajectory t: the inverse permutation of rg within every ladder
         order = np.argsort(rg.reshape(n, M, K), axis=2) + (np.arange(M) * K)[None, :, None]   # [n, M, K] -> chain index
         h = {}
-        for key in ('acc', 'dH', 'csum', 'dsum', 'Q'):
+        for key in ('acc', 'dH', pk, 'dsum', 'Q'):
             h[key] = np.take_along_axis(c[key], order.reshape(n, B), axis=1).reshape(n, M, K).transpose(0, 2, 1)   # [n, K, M]
-        h['plaq'] = h.pop('csum') / float(L * L)
+        if flow is None:
+            h['plaq'] = h.pop('csum') / float(L * L)
         sw = c['swap_acc']
         tried = (sw >= 0).sum(axis=(0, 1))
         h['swap_tried'] = tried

@@ -89,6 +89,11 @@ def ft_meta_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
     return int(_lib.load().fthmc_ft_meta_ws_bytes(_arch(arch), B, L, n_layers))
 
 
+def ft_defect_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
+    """Scratch of ft_defect_trajectory / ft_defect_force / ft_defect_action: ws_bytes and the three rows of chain sums behind it"""
+    return int(_lib.load().fthmc_ft_defect_ws_bytes(_arch(arch), B, L, n_layers))
+
+
 def vjp_ws_bytes(B: int, L: int, n_layers: int, arch=None) -> int:
     """Scratch of the second-order calls (ft_action_vjp, ft_force_vjp); 0 for a refused shape."""
     return int(_lib.load().fthmc_vjp_ws_bytes(_arch(arch), B, L, n_layers))
@@ -129,9 +134,11 @@ def _stream_buffer(t: torch.Tensor, need: int, family=None, zero_head: bool = Fa
 
 
 def _ws(t: torch.Tensor, B: int, L: int, nl: int, train: bool = False, arch=None, vjp: bool = False, force: bool = False,
-        meta: bool = False):
+        meta: bool = False, defect: bool = False):
     if meta:                                             # the flow workspace with the chain sums behind it: the same buffer, grown
         need = ft_meta_ws_bytes(B, L, nl, arch)
+    elif defect:                                         # likewise, with the defect calls' three rows
+        need = ft_defect_ws_bytes(B, L, nl, arch)
     elif force:
         need = train_force_ws_bytes(B, L, nl, arch)
         if need == 0:
@@ -1202,10 +1209,11 @@ def _meta_group_rows(table, B: int, edges):
 
 
 def _ft_trajectory(x, v, u, w, n_layers, beta, dt, nstep, act, mode, out, state_in, groups, arch, wkey, side_streams, integrator,
-                   bias=None):
-    """The body of ft_trajectory and, with bias = (table, qmax, wall), of ft_meta_trajectory: the checks, the result tensors (the
-    state has nrow = 3 rows, 4 with a bias), the chain-group fork (a group is handed its own table rows) and the C call, chosen by
-    (bias, per-chain beta, integrator)."""
+                   bias=None, defect=None):
+    """The body of ft_trajectory and, with bias = (table, qmax, wall), of ft_meta_trajectory, with defect = (g_b, (i0, j0, Ld)) of
+    ft_defect_trajectory: the checks, the result tensors (the state has nrow = 3 rows, 4 with a bias or a defect), the chain-group
+    fork (a group is handed its own table rows, its own slice of g_b) and the C call, chosen by (bias, defect, per-chain beta,
+    integrator)."""
     ic = integrator_code(integrator)
     if ic and mode not in ('md',):
         raise ValueError(f'mode {mode!r} discards the MD: it goes with integrator=\'leapfrog\' only, got {integrator!r}')
@@ -1220,6 +1228,12 @@ def _ft_trajectory(x, v, u, w, n_layers, beta, dt, nstep, act, mode, out, state_
         if int(nstep) < 1:
             raise ValueError(f'ft_meta_trajectory: nstep >= 1 expected, got {nstep}')
         nrow, keys, tab = 4, keys + ('qm', 'vbias'), _meta_table(bias[0], B, *bias[1:])
+    if defect is not None:
+        if int(nstep) < 1:
+            raise ValueError(f'ft_defect_trajectory: nstep >= 1 expected, got {nstep}')
+        if bb is not None:
+            raise ValueError('ft_defect_trajectory: ONE beta per call (a number); the couplings of the chains are g_b')
+        nrow, keys, dfa = 4, keys + ('dsum',), _defect_args(beta, defect[0], defect[1], B, L)
     edges = _group_edges(groups, B)                                     # an int, or explicit group sizes (chains per group)
     rows = _meta_group_rows(bias[0], B, edges) if bias is not None else None      # raises before anything is launched
     w, ap, a = _wall(w, n_layers, arch)
@@ -1244,13 +1258,14 @@ def _ft_trajectory(x, v, u, w, n_layers, beta, dt, nstep, act, mode, out, state_
                 og = {k: t[lo:hi] for k, t in out.items() if k != 'state'}
                 sg = state_in[:, lo:hi].contiguous() if state_in is not None else None
                 bg = bias if r is None else (bias[0][r[0]:r[1]],) + tuple(bias[1:])
+                dg = None if defect is None else (defect[0].view(-1)[lo:hi], defect[1])
                 _ft_trajectory(x[lo:hi], v[lo:hi], u[lo:hi], w, n_layers, beta if bb is None else bb[lo:hi], dt, nstep, act, mode, og,
-                               sg, 1, a, wkey, None, integrator, bg)      # one group: no side streams
+                               sg, 1, a, wkey, None, integrator, bg, dg)  # one group: no side streams
                 out['state'][:, lo:hi].copy_(og['state'])
                 parts.append(og)                                        # keep the group's temporaries alive until the join
         return out
     m = {'md': MODE_MD, 'literal': MODE_LITERAL, 'reference_literal': MODE_LITERAL}[mode]
-    ws, nb = _ws(x, B, L, n_layers, arch=a, meta=bias is not None)
+    ws, nb = _ws(x, B, L, n_layers, arch=a, meta=bias is not None, defect=defect is not None)
     lib, wv = _lib.load(), weights_version(wkey)
     head = (_p(x), _p(v), _p(u), _p(w), ap, n_layers, B, L, act_code(act))
     res = tuple(_p(out[k]) for k in ('x_new',) + keys)
@@ -1259,6 +1274,8 @@ def _ft_trajectory(x, v, u, w, n_layers, beta, dt, nstep, act, mode, out, state_
     # old one, else _int
     if bias is not None:
         check(lib.fthmc_ft_meta_trajectory_v(*head, float(beta), float(dt), int(nstep), ic, *tab, *res, *tail, wv), 'fthmc_ft_meta_trajectory')
+    elif defect is not None:
+        check(lib.fthmc_ft_defect_trajectory_v(*head, *dfa, float(dt), int(nstep), ic, *res, *tail, wv), 'fthmc_ft_defect_trajectory')
     elif bb is not None:
         check(lib.fthmc_ft_trajectory_pb_v(*head, _p(bb), float(dt), int(nstep), m, *res, *tail, ic, wv), 'fthmc_ft_trajectory_pb')
     elif ic:
@@ -1325,6 +1342,46 @@ def ft_meta_action(x, w, n_layers: int, beta: float, table, qmax: float, wall: f
     check(_lib.load().fthmc_ft_meta_action_v(_p(x), _p(w), ap, n_layers, B, L, act_code(act), float(beta), *tab, _p(S), _p(ld), _p(qm),
                                              _p(vb), ws, nb, _stream(x), weights_version(wkey)), 'fthmc_ft_meta_action')
     return S, ld, qm, vb
+
+
+# ---------------------------------------------------------------- boundary-condition tempering through the flow
+def ft_defect_trajectory(x, v, u, w, n_layers: int, beta: float, g_b, defect, dt: float, nstep: int, act='silu', integrator='leapfrog',
+                         out: Optional[dict] = None, state_in: Optional[torch.Tensor] = None, groups: int = 1, arch=None, wkey=None,
+                         side_streams=None):
+    """One ftHMC trajectory per chain whose PHYSICAL field F(x) carries the defect of defect_trajectory (C ABI
+    fthmc_ft_defect_trajectory_v; mode 'md'): S(x) = -beta C + (beta - g_b) Dsum - log det J(x), C and Dsum the cosine sums of F(x)
+    -> dict(x_new, dH, acc, H0, H1, plaq, Q, dsum, state): ft_trajectory's keys, dsum = Dsum of F(x_new), and state [4, B] = (S_eff of
+    the periodic action, plaq, Q, Dsum) of x_new.  The state is g-free: fed back as `state_in` it stays valid when a replica exchange
+    has changed g_b in between.  g_b: a float64 device tensor [B] read in place; defect = (i0, j0, Ld).  groups, out, wkey,
+    side_streams: as ft_trajectory; every chain group is handed its slice of g_b.  Results do not depend on `groups`."""
+    return _ft_trajectory(x, v, u, w, n_layers, beta, dt, nstep, act, 'md', out, state_in, groups, arch, wkey, side_streams, integrator,
+                          defect=(g_b, defect))
+
+
+def ft_defect_force(x, w, n_layers: int, beta: float, g_b, defect, act='silu', arch=None, wkey=None):
+    """F = dS / dx of S(x) = -beta C + (beta - g_b) Dsum - log det J(x) on the physical field F(x) (C ABI fthmc_ft_defect_force_v),
+    ft_force's sign"""
+    x = _field(x); B, _, L, _ = x.shape
+    df = _defect_args(beta, g_b, defect, B, L)
+    w, ap, a = _wall(w, n_layers, arch)
+    F = torch.empty_like(x)
+    ws, nb = _ws(x, B, L, n_layers, arch=a, defect=True)
+    check(_lib.load().fthmc_ft_defect_force_v(_p(x), _p(w), ap, n_layers, B, L, act_code(act), *df, _p(F), ws, nb, _stream(x),
+                                              weights_version(wkey)), 'fthmc_ft_defect_force')
+    return F
+
+
+def ft_defect_action(x, w, n_layers: int, beta: float, g_b, defect, act='silu', arch=None, wkey=None):
+    """-> (S, logdet, csum, dsum, Q) per chain, the sums and the integer charge of the physical field F(x) (C ABI
+    fthmc_ft_defect_action_v)"""
+    x = _field(x); B, _, L, _ = x.shape
+    df = _defect_args(beta, g_b, defect, B, L)
+    w, ap, a = _wall(w, n_layers, arch)
+    S, ld, cs, ds, Q = (torch.empty(B, dtype=x.dtype, device=x.device) for _ in range(5))
+    ws, nb = _ws(x, B, L, n_layers, arch=a, defect=True)
+    check(_lib.load().fthmc_ft_defect_action_v(_p(x), _p(w), ap, n_layers, B, L, act_code(act), *df, _p(S), _p(ld), _p(cs), _p(ds), _p(Q),
+                                               ws, nb, _stream(x), weights_version(wkey)), 'fthmc_ft_defect_action')
+    return S, ld, cs, ds, Q
 
 
 def train_grad(xi, w, n_layers: int, beta: float, act='silu', need_gw=True, groups: int = 1, _out=None, out_gw=None, arch=None):

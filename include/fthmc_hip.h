@@ -713,6 +713,50 @@ int fthmc_profile_stages(int kind, const double* x, const double* w, const fthmc
                          int act, double beta, double* cycles_host16,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Flowed boundary-condition tempering: the defect above on the PHYSICAL field of ftHMC.  Latent field x, physical field
+ * y = F(x) (n_layers coupling layers); the defect D, the couplings g_b [B] (device) and ONE beta per call as for fthmc_defect_*.
+ * With C = sum cos P(y) and Dsum = the cosines of D among them, in fthmc_defect_action's order,
+ *     S(x) = (-beta) C + (beta - g_b) Dsum - log det J(x),      H = S + sum v^2 / 2.
+ * The force with respect to x is fthmc_ft_force's backward sweep seeded with gP(p) = w(p) sin P(y)(p), w = g_b on D and beta
+ * elsewhere, in place of beta sin P(y): one pass over the field, no chain-wide sum.  Every output of a chain depends on the chain and
+ * its own g_b only, never on B or on the chain's place in the batch.
+ * The reference has no counterpart to any of the four entry points below.
+ * What they refuse, in this order: a null x (v, u, x_new; F) / g_b, w null with n_layers > 0, B or L out of range, n_layers < 0,
+ * nstep < 1, Ld outside [0, L], i0 or j0 outside [0, L), a beta that is not finite: FTHMC_ERR_ARG; an unknown activation or
+ * integrator, a refused arch, B > 65535 where the sequenced kernels run (they put the chain on grid y): FTHMC_ERR_UNSUPPORTED; then
+ * the workspace (FTHMC_ERR_WS) and the weights-version check.  Enqueue-only, capturable. */
+
+/* No reference counterpart.  Scratch of the three calls below: fthmc_ws_bytes(arch, B, L, n_layers) and behind it the three rows of
+ * chain sums (C, Dsum, Q), rounded like every region (a multiple of 256 bytes); 0 for refused arguments. */
+size_t fthmc_ft_defect_ws_bytes(const fthmc_arch_t* arch, int B, int L, int n_layers);
+
+/* No reference counterpart.  One flowed trajectory of every chain with the defect (FTHMC_MODE_MD only): H0, the MD of (integrator,
+ * dt, nstep) under the force above, the end point regularized, H1, accept iff u[b] < exp(-(H1 - H0)).  x_new .. H1 as
+ * fthmc_ft_trajectory_int_v; plaq, Q, dsum_out [B]: of F(x_new).  dH .. dsum_out may be NULL.
+ * state_in / state_out (either may be NULL): [4][B] = (S_eff of the PERIODIC action = (-beta) C - log det J, plaq, Q, Dsum) of x /
+ * of x_new.  The state is g-free: a call forms H = S_eff + (beta - g_b) Dsum + K / 2 from it, so a swap of g between two chains
+ * leaves it valid, and a chained call gives the bits of a stateless one at any g_b.
+ * L = 8, 12, 16 with the default net and the small path on: one launch (k_ft_small's instance with a defect); every other shape
+ * fthmc_ft_trajectory_int_v serves: its sequence with the weighted seed in every force and (beta - g_b) Dsum added to either
+ * energy.  With g_b = beta for every chain, or with Ld = 0, either gives the bits of fthmc_ft_trajectory_int_v; with n_layers = 0
+ * the call gives those of fthmc_defect_trajectory on path 2. */
+int fthmc_ft_defect_trajectory_v(const double* x, const double* v, const double* u, const double* w, const fthmc_arch_t* arch, int n_layers,
+                                 int B, int L, int act, double beta, const double* g_b /* [B] */, int i0, int j0, int Ld, double dt,
+                                 int nstep, int integrator, double* x_new, double* dH, double* acc, double* H0, double* H1, double* plaq,
+                                 double* Q, double* dsum_out, const double* state_in /* [4][B] or NULL */,
+                                 double* state_out /* [4][B] or NULL */, void* ws, size_t ws_bytes, void* stream, uint64_t weights_version);
+
+/* No reference counterpart.  The flowed force and action with the defect on their own, for tests and measurements (always the
+ * sequenced kernels):
+ * F[B][2][L][L] = dS / dx; per chain S, logdet = log det J, csum = C, dsum = Dsum, Q = the integer charge of F(x) (each of the five may
+ * be NULL). */
+int fthmc_ft_defect_force_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
+                            const double* g_b, int i0, int j0, int Ld, double* F, void* ws, size_t ws_bytes, void* stream,
+                            uint64_t weights_version);
+int fthmc_ft_defect_action_v(const double* x, const double* w, const fthmc_arch_t* arch, int n_layers, int B, int L, int act, double beta,
+                             const double* g_b, int i0, int j0, int Ld, double* S, double* logdet, double* csum, double* dsum, double* Q,
+                             void* ws, size_t ws_bytes, void* stream, uint64_t weights_version);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,13 +2,19 @@
 """Per-kernel comparison of the device code of two source trees: is a kernel of this tree the code it was in the parent commit?
 
     python tools/isa_diff.py --parent-tree DIR [--files wilson.hip meta.hip ...] [--jobs 6] [--dump DIR] [--out profiles/resident_plan_isa.json]
+                             [--rename PATTERN REPLACEMENT ...]
 
 Every file is compiled to device assembly in both trees with exactly the flags the Makefile gives it (the command `make -n FILE.o`
 prints, -c swapped for --cuda-device-only -S), every kernel is cut from its label to its .Lfunc_end, comments and directives are
 dropped and basic-block labels renumbered in order of appearance, and the two texts are compared.  Per kernel the document says
 whether they are equal and gives, for both trees, the instruction count and VGPRs, SGPRs, scratch and LDS bytes of the metadata.
 An equal kernel has the parent's behaviour and speed by construction.  Needs hipcc, no GPU.  Exit status 1 if a kernel differs,
-appeared or went away."""
+appeared or went away.
+
+--rename PATTERN REPLACEMENT (a regular expression and its substitution, repeatable): a parent symbol's new name, for a kernel template
+that gained a parameter -- the mangled names of all its instances change though their code need not.  The substitution is applied to
+the parent's kernel symbols and to the same names where the parent's instructions mention them; the instances are then compared
+pairwise under their new names, and a row says which parent symbol it was compared with."""
 import argparse
 import concurrent.futures
 import json
@@ -77,13 +83,28 @@ def side(body, meta):
     return dict(instructions=sum(not l.endswith(':') for l in body), **meta)
 
 
-def compare(src, parent, new, dump=None):
+def renamed(kp, renames):
+    """the parent's kernels under their new names -> ({new name: (body, meta)}, {new name: parent symbol} of those that changed)"""
+    def new_name(sym):
+        for pat, repl in renames:
+            sym = re.sub(pat, repl, sym)
+        return sym
+    names = {k: new_name(k) for k in kp}
+    was = {n: k for k, n in names.items() if n != k}
+    sym = re.compile(r'_Z\w+')
+    return {names[k]: ([sym.sub(lambda m: new_name(m.group(0)), l) for l in body], meta) for k, (body, meta) in kp.items()}, was
+
+
+def compare(src, parent, new, dump=None, renames=()):
     with tempfile.TemporaryDirectory() as dp, tempfile.TemporaryDirectory() as dn:
         kp, kn = kernels(assembly(parent, src, dp)), kernels(assembly(new, src, dn))
+    kp, was = renamed(kp, renames)
     rows = {}
     for k in sorted(set(kp) | set(kn)):
         if k in kp and k in kn:
             rows[k] = dict(equal=kp[k][0] == kn[k][0], parent=side(*kp[k]), new=side(*kn[k]))
+            if k in was:
+                rows[k]['parent_symbol'] = was[k]
             if dump and not rows[k]['equal']:                # the two normalised texts, for diff
                 os.makedirs(dump, exist_ok=True)
                 for tag, body in (('parent', kp[k][0]), ('new', kn[k][0])):
@@ -111,17 +132,25 @@ def main():
     ap.add_argument('--jobs', type=int, default=6)
     ap.add_argument('--out', default=None)
     ap.add_argument('--dump', default=None, help='a directory for the normalised texts of the kernels that differ')
+    ap.add_argument('--rename', nargs=2, action='append', default=[], metavar=('PATTERN', 'REPLACEMENT'),
+                    help='a parent symbol -> its new name (re.sub), for a kernel template that gained a parameter; repeatable')
+    ap.add_argument('--new-only', nargs='*', default=[], metavar='REGEX',
+                    help='demangled names of kernels this tree adds on purpose: listed, not counted as a difference')
     args = ap.parse_args()
     parent = os.path.abspath(args.parent_tree)
     with concurrent.futures.ThreadPoolExecutor(args.jobs) as pool:
-        res = dict(zip(args.files, pool.map(lambda f: compare(f, parent, ROOT, args.dump), args.files)))
-    doc = dict(tool='tools/isa_diff.py', files={})
+        res = dict(zip(args.files, pool.map(lambda f: compare(f, parent, ROOT, args.dump, args.rename), args.files)))
+    doc = dict(tool='tools/isa_diff.py', files={}, renames=[list(r) for r in args.rename], added=[])
     bad = []
     for f, rows in res.items():
         names = demangled(list(rows))
         doc['files'][f] = dict(kernels=len(rows), equal=sum(r['equal'] for r in rows.values()),
                                rows={names[k]: dict(symbol=k, **r) for k, r in rows.items()})
-        bad += [f'{f}: {names[k]}' for k, r in rows.items() if not r['equal']]
+        for k, r in rows.items():
+            if r['parent'] is None and any(re.search(p, names[k]) for p in args.new_only):
+                doc['added'].append(f'{f}: {names[k]}')
+            elif not r['equal']:
+                bad.append(f'{f}: {names[k]}')
     doc['all_equal'] = not bad
     doc['not_equal'] = bad
     text = json.dumps(doc, indent=1)
